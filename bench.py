@@ -8,14 +8,21 @@ Default workload = BASELINE.json's metric configuration, configs[2] as SURVEY.md
 65 536 Bell-202 1200-baud streams x 480 000 samples (10 s) per GPU = 126 GB resident.  Streams shard across GPUs with
 no collective.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run does what the headline needs and no more: set-up, W warm-ups, K timed steps, one JSON line.  --full adds what
+is measured or checked beyond it (the CPU baseline and its oracle check, the shader-clock probe, the strong-scaling pass,
+the side measurements, the c5 quality score).  --dump-outputs DIR writes, after the timed steps, what the last of them
+returned (rank 0) as DIR/<name>.npy in float32 / float64: for the demodulator every stream's byte and 'eod' counts and the
+bytes of a fixed, seeded sample of streams; for --workload mod the signal of such a sample and every stream's output length.
+With the same arguments the inputs are the same from run to run (seeded synthesis on the device).
 
 N > 1 without a launcher (no WORLD_SIZE in the environment): this process starts its own N ranks -- BEFORE anything
 touches the GPU -- as a child `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...
 bench.py <same arguments>`, relays rank 0's JSON line and exits with the child's code.  Under a launcher (the driver's
 own torch.distributed.run) RANK / LOCAL_RANK / WORLD_SIZE come from the environment as usual.
 
-With N > 1 ONE line carries both shapes:
+With N > 1 and --full ONE line carries both shapes:
   value                    weak scaling: every rank holds its own --streams streams (65 536 per GPU)
   config.strong_scaling    BASELINE config #3 as written: --streams streams IN TOTAL, a contiguous block per rank
                            (sharding.stream_shard: 8 192 per GPU at 8), measured right after the weak pass
@@ -27,15 +34,16 @@ Prints ONE JSON line on rank 0 (driver contract) with the extra objects
                 launched (fskhip_last_kernel).  `binding_bound` names the ceiling that actually binds and
                 `valu_issue` is the same run against it: vector instructions issued per second (committed PMC
                 instruction mix x this run's rate) against 1024 SIMDs x one wave64 instruction per 2 cycles at 2.4 GHz
-  cpu_baseline  the CPU oracle (scalar fp64 C port of the reference, oracle/) timed on one host core on a bounded
-                sample of the same buffers; doubles as a parity check of that sample (GPU bytes == oracle bytes): a
-                mismatch sets parity_ok false and the exit code of EVERY rank to 3
-and, at N = 1, side measurements in `config` (never the headline): the fp64 parity path on the same shape, a large
-batch (262 144 streams), and the PCIe-inclusive rate through fskhip_demodulate_host.
+  cpu_baseline  (--full; null otherwise) the CPU oracle (scalar fp64 C port of the reference, oracle/) timed on one host
+                core on a bounded sample of the same buffers; doubles as a parity check of that sample (GPU bytes ==
+                oracle bytes): a mismatch sets parity_ok false and the exit code of EVERY rank to 3
+and, with --full at N = 1, side measurements in `config` (never the headline): the fp64 parity path on the same shape, a
+large batch (262 144 streams), and the PCIe-inclusive rate through fskhip_demodulate_host.  Without --full the clock in
+`roofline.valu_issue` is the part's maximum (the probe that measures it runs with --full).
 
 --workload c5 is BASELINE config #5 as BASELINE.md defines it: every stream's frames come from fskhip_modulate_device
 (FSKCore.modulateData), Gaussian noise at 10 dB with the reference tests' power definition (mean square over the whole
-buffer incl. padding, fsk-demodulation.node.test.ts:1184-1205), and besides the throughput the line carries
+buffer incl. padding, fsk-demodulation.node.test.ts:1184-1205), and with --full besides the throughput the line carries
 config.c5_quality: frame success rate, BER against the transmitted payloads, and the oracle comparison of a stream sample.
 """
 import argparse
@@ -96,8 +104,8 @@ def build_parser():
                     help="strong scaling only: this many streams in total, sharded over the ranks (0 = weak + strong in one line)")
     ap.add_argument("--seconds", type=float, default=10.0, help="audio seconds per stream per step")
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for the cpu_baseline leg (0 = skip)")
-    ap.add_argument("--no-side", action="store_true", help="skip the side measurements (fp64 path, large batch, PCIe)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for the cpu_baseline leg of --full (0 = skip)")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the side measurements (fp64 path, large batch, PCIe)")
     ap.add_argument("--probe-reads", type=int, default=0,
                     help="also launch the read-pattern probe kernel this many times (FETCH_SIZE calibration)")
     ap.add_argument("--pitch-pad", type=int, default=0, help="extra floats of row pitch (experiments)")
@@ -106,13 +114,48 @@ def build_parser():
                     help="every stream's first frame starts at a random offset below this many samples (default: ten bit cells, so "
                          "that the streams' frames -- and their resets -- nearly line up; a frame length = streams that do not)")
     ap.add_argument("--no-clock-probe", action="store_true",
-                    help="skip the shader-clock probe and its extra steps (profiler passes: their kernel statistics then hold the timed launches only)")
+                    help="with --full: skip the shader-clock probe and its extra steps (profiler passes: their kernel statistics then hold the timed launches only)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="fskhip_set_option for every engine of this run (measurements: kernel=two-wave, blk_y_slots=12, ...)")
     ap.add_argument("--dry-engine", action="store_true",
                     help="launcher / aggregation test without a GPU: gloo backend and a stand-in engine that only sleeps "
                          "(tests/test_bench_launcher_cpu.py); the line says so in `data`")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline: the CPU oracle baseline and its parity check of a sample, the "
+                         "shader-clock probe, the strong-scaling pass (N > 1) and the side measurements (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy")
     return ap
+
+
+def check_args(ap, args):
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.dry_engine:
+        ap.error("--dump-outputs needs the real engine")
+
+
+DUMP_ROWS_BUDGET = 32 << 20     # bytes of per-sample rows one --dump-outputs writes at most (64 MB in all with the rest)
+DUMP_SEED = 0xD0E5
+
+
+def dump_rows(n_rows, row_bytes):
+    """the fixed sample of rows a dump holds when all of them would not fit: a function of the shape alone"""
+    k = int(max(1, min(n_rows, DUMP_ROWS_BUDGET // max(1, row_bytes))))
+    if k == n_rows:
+        return list(range(n_rows))
+    import numpy as np
+    return sorted(np.random.RandomState(DUMP_SEED).choice(n_rows, k, replace=False).tolist())
+
+
+def write_dump(dirname, arrays):
+    """arrays: name -> float32 / float64 numpy array, written as dirname/<name>.npy"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -209,11 +252,11 @@ def measure(sync, dist, eng, step, steps, warmup, dev):
     return max_over_ranks(elapsed, dist, dev), n_launch, kernel_ms
 
 
-def c5_build_and_score(torch, np, wm, eng, cfg, x, N, pitch, snr, seed, payload_len, stream, oracle_seconds, first_stream):
+def c5_build_and_score(torch, np, wm, eng, cfg, x, N, pitch, snr, seed, payload_len, stream, oracle_seconds, first_stream, score):
     """BASELINE config #5: fill x with FSKCore.modulateData frames (fskhip_modulate_device), one per time slot, add AWGN
-    with the reference tests' power definition, demodulate slot by slot (the engine is a streaming state machine: any
-    cut of a stream gives the same bytes) so that every frame's bytes are attributed to it, and score them against the
-    transmitted payloads; a strided sample of streams is demodulated by the CPU oracle with the same cuts."""
+    with the reference tests' power definition; with `score` (--full), demodulate slot by slot (the engine is a streaming
+    state machine: any cut of a stream gives the same bytes) so that every frame's bytes are attributed to it, and score
+    them against the transmitted payloads; a strided sample of streams is demodulated by the CPU oracle with the same cuts."""
     S = x.shape[0]
     frame_len = eng.modulated_length(payload_len)
     slot = (frame_len + 1952 + 15) // 16 * 16           # frame + 1 952 samples of silence, whole 16-sample tiles
@@ -232,6 +275,8 @@ def c5_build_and_score(torch, np, wm, eng, cfg, x, N, pitch, snr, seed, payload_
     t_mod = time.perf_counter() - t0
     eng.add_awgn_device(x.data_ptr(), N, pitch, snr, seed ^ 0xA36, stream)
     torch.cuda.synchronize()
+    if not score:
+        return None
     # ---- demodulate slot by slot
     eng.reset()
     op = eng.max_bytes(slot + N - F * slot)
@@ -304,7 +349,7 @@ def c5_build_and_score(torch, np, wm, eng, cfg, x, N, pitch, snr, seed, payload_
 def measure_modulate(torch, np, wm, eng, S, N, pitch, payload_len, seed, stream, steps, warmup, sync):
     """FSKCore.modulateData on the GPU (fskhip_modulate_device): every stream's 10 s buffer filled with back-to-back frames, one
     modulate call per frame slot (what --workload c5 transmits).  Returns (samples written per step, kernel ms per step from the
-    library's HIP events, launches per step, the device buffer, payloads, slot)."""
+    library's HIP events, launches per step, the device buffer and output lengths, payloads, slot)."""
     frame_len = eng.modulated_length(payload_len)
     slot = (frame_len + 1952 + 15) // 16 * 16
     F = max(1, N // slot)
@@ -330,7 +375,7 @@ def measure_modulate(torch, np, wm, eng, S, N, pitch, payload_len, seed, stream,
     wall = time.perf_counter() - t0
     nl, ms = eng.timing_end()
     return dict(samples_per_step=float(S) * F * frame_len, kernel_ms_per_step=ms / steps, launches_per_step=nl // steps,
-                wall_s_per_step=wall / steps, x=x, payloads=payloads, slot=slot, frames=F, frame_len=frame_len)
+                wall_s_per_step=wall / steps, x=x, olens=d_olens, payloads=payloads, slot=slot, frames=F, frame_len=frame_len)
 
 
 def worker_mod(args):
@@ -371,9 +416,16 @@ def worker_mod(args):
         dist.barrier()
     m = measure_modulate(torch, np, wm, eng, S, N, pitch, payload_len, 0xF5C0DE + 0x1000 * rank, stream, args.steps, args.warmup, sync)
     elapsed = max_over_ranks(m["wall_s_per_step"] * args.steps, dist, "cuda")
+    if rank == 0 and args.dump_outputs:
+        # the last step's signal (a fixed sample of streams, whole rows) and every stream's output length (that of the last frame slot)
+        rows = dump_rows(S, 4 * pitch)
+        write_dump(args.dump_outputs, {
+            "signal": m["x"].index_select(0, torch.as_tensor(rows, device="cuda")).cpu().numpy(),
+            "signal_rows": np.asarray(rows, np.float64),
+            "out_lengths": m["olens"].cpu().numpy().astype(np.float64)})
     # ---- parity + cpu baseline on a strided sample (rank 0): frame 0 of each sampled stream against the oracle's modulateData
     cpu_obj, parity_ok = None, True
-    if rank == 0 and args.cpu_seconds > 0:
+    if rank == 0 and args.full and args.cpu_seconds > 0:
         from oracle import pyoracle as po
         rows = np.unique(np.linspace(0, S - 1, 64).astype(np.int64))
         xs = m["x"].index_select(0, torch.as_tensor(rows, device="cuda"))[:, :m["frame_len"]].cpu().numpy()
@@ -509,7 +561,7 @@ def worker(args):
         eod = torch.empty(S, dtype=torch.int32, device="cuda")
         if wl.get("roundtrip"):
             c5q = c5_build_and_score(torch, np, wm, eng, cfg, x, N, pitch, snr, seed, wl["payload"], stream,
-                                     args.cpu_seconds if rank == 0 else 0, first_stream)
+                                     args.cpu_seconds if rank == 0 else 0, first_stream, args.full)
         elif wl.get("idle_db") is not None:
             # one frame per stream (the synthesiser's first, with its random lead-in and level), zeros behind it, then noise
             # over everything: sigma^2 = (mean square of the stream's frame) / 10^(idle_db / 10).  add_awgn_device takes its
@@ -564,7 +616,7 @@ def worker(args):
     cpu_obj = None
     parity_ok = True
     oracle_rows = {}
-    if rank == 0 and args.cpu_seconds > 0 and not dry:
+    if rank == 0 and args.full and args.cpu_seconds > 0 and not dry:
         est_rate = 7.0e6  # oracle samples/s/core
         n_cpu_streams = int(max(1, min(S, args.cpu_seconds * est_rate // N)))
         # a strided sample over the whole batch (first and last groups included)
@@ -616,12 +668,21 @@ def worker(args):
     if not dry:
         kernel_name = eng.last_kernel()
         lanes_main = eng.blk_lanes() if ("demod_blk_kernel" in kernel_name or "demod_blk6_kernel" in kernel_name) else None
+    if rank == 0 and args.dump_outputs:
+        # what the last timed call returned: every stream's byte count and 'eod' count, and the bytes of a fixed sample of
+        # streams (-1 past a stream's count: out_pitch bounds the bytes, the rest of a row is not written)
+        rows = dump_rows(S, 4 * out_pitch)
+        n_out = counts.cpu().numpy().astype(np.int64)
+        b = out.index_select(0, torch.as_tensor(rows, device="cuda")).cpu().numpy().astype(np.float32)
+        b[np.arange(out_pitch)[None, :] >= n_out[rows][:, None]] = -1.0
+        write_dump(args.dump_outputs, {"bytes": b, "bytes_rows": np.asarray(rows, np.float64),
+                                       "counts": n_out.astype(np.float64), "eod": eod.cpu().numpy().astype(np.float64)})
 
     # ---- the shader clock the device holds under this load: a one-wave probe (fskhip_clock_probe_*) started
     # first, a few more steps of the same work behind it.  Outside the timed region on purpose: the probe's wave takes a slot
     # that one workgroup of a full-device launch has to wait for.
     clock_ghz = None
-    if rank == 0 and not dry and not args.no_clock_probe:
+    if rank == 0 and not dry and args.full and not args.no_clock_probe:
         try:
             per_step_ms = elapsed / args.steps * 1e3
             k_probe = max(2, min(6, int(250.0 / max(per_step_ms, 1e-3)) + 1))
@@ -635,7 +696,7 @@ def worker(args):
 
     # ---- N > 1: the strong-scaling shape of the same job (BASELINE config #3 as written), same line -------------------
     strong = None
-    if world > 1 and not strong_only:
+    if world > 1 and not strong_only and args.full:
         first2, S2 = stream_shard(args.streams, rank, world)
         if dry:
             e2 = DryEngine(S2)
@@ -671,7 +732,7 @@ def worker(args):
 
     # ---- side measurements (rank 0, one GPU): reported in `config`, never as `value` ------------------------------
     side = {}
-    if rank == 0 and world == 1 and not args.no_side and args.precision == "f32" and cfgs is None and not dry and c5q is None:
+    if rank == 0 and world == 1 and args.full and not args.no_side and args.precision == "f32" and cfgs is None and not dry and c5q is None:
         k_side = max(2, min(args.steps, 4))
         # (0) one GPU's share of BASELINE configs #3 (65 536 streams over eight GPUs = 8 192) and #5 (16 384 over eight = 2 048):
         # the strong-scaling estimate in the driver's own record (VERDICT r03 "missing" 3).  Same signal, same length: the first
@@ -1038,7 +1099,9 @@ def worker(args):
 
 def main():
     argv = sys.argv[1:]
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    check_args(ap, args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, argv))
     world = int(os.environ.get("WORLD_SIZE", "1"))

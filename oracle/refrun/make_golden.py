@@ -6,7 +6,7 @@ TEST INFRASTRUCTURE.  Steps:
      temp dir (never into the repo);
   2. golden_harness.js runs the reference FSKCore under Node on the scenario list and dumps raw
      arrays + a manifest into the same temp dir;
-  3. this script packs the arrays into tests/golden/golden.npz (compressed) and writes
+  3. this script packs the arrays into tests/golden/golden.npz (compressed; golden_part<k>.npz when over 1 MiB) and writes
      tests/golden/manifest.json; golden_harness_next.js does the same for the SURVEY 8(f) rows (CRC-16 /
      XModem packets, ChunkedModulator, the FSKProcessor quantum loop) -> golden_next.npz + manifest_next.json;
      golden_harness_hostile.js for NaN / Inf / out-of-range / subnormal input (round 6) -> golden_hostile.npz + manifest_hostile.json.
@@ -26,6 +26,34 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
+PART_BYTES = 900000     # a committed file stays under 1 MiB: a set that compresses to more is written in parts
+
+
+def save_npz_parts(gold, npz, arrays):
+    """np.savez_compressed(gold/npz) when the set fits in PART_BYTES, else gold/<stem>_part<k>.npz, arrays packed in
+    order (tests/conftest.py load_npz reads either form); removes the other form's files.  Returns the paths written."""
+    import glob
+    import io
+    stem = npz[:-4]
+    parts, cur, cur_sz = [], {}, 0
+    for name, a in arrays.items():
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **{name: a})
+        n = len(buf.getvalue())
+        if cur and cur_sz + n > PART_BYTES:
+            parts.append(cur)
+            cur, cur_sz = {}, 0
+        cur[name] = a
+        cur_sz += n
+    parts.append(cur)
+    for old in [os.path.join(gold, npz)] + glob.glob(os.path.join(gold, stem + "_part*.npz")):
+        if os.path.exists(old):
+            os.remove(old)
+    paths = [os.path.join(gold, npz)] if len(parts) == 1 else [os.path.join(gold, "%s_part%d.npz" % (stem, k)) for k in range(len(parts))]
+    for p, part in zip(paths, parts):
+        np.savez_compressed(p, **part)
+        assert os.path.getsize(p) < 1 << 20, p
+    return paths
 
 
 def main():
@@ -55,11 +83,11 @@ def main():
                 a = np.fromfile(os.path.join(out, "%s.%s.bin" % (name, meta["dtype"])), dtype=dt)
                 assert a.size == meta["n"], name
                 arrays[name] = a
-            np.savez_compressed(os.path.join(gold, npz), **arrays)
+            paths = save_npz_parts(gold, npz, arrays)
             with open(os.path.join(gold, man_name), "w") as fh:
                 json.dump(man, fh, indent=None, separators=(",", ":"))
-            sz = os.path.getsize(os.path.join(gold, npz))
-            print("%s: wrote %d arrays, %s %.2f MB" % (harness, len(arrays), npz, sz / 1e6))
+            sz = sum(os.path.getsize(p) for p in paths)
+            print("%s: wrote %d arrays, %s in %d file(s) %.2f MB" % (harness, len(arrays), npz, len(paths), sz / 1e6))
     finally:
         if args.keep:
             print("kept", tmp)

@@ -20,7 +20,7 @@ def _run(args, env_extra=None, timeout=300):
 
 
 def test_self_launch_two_ranks_dry_engine():
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-engine", "--streams", "4096", "--seconds", "0.1"])
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-engine", "--streams", "4096", "--seconds", "0.1", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout            # ONE JSON line, rank 0's
@@ -39,6 +39,16 @@ def test_self_launch_two_ranks_dry_engine():
     assert st["Msamples_per_s"] > 0
     assert "dry-run" in d["data"]
     assert d["roofline"]["binding_bound"] in ("hbm", "valu_issue", "valu_class_priced")   # (the ceiling this run came closest to)
+
+
+def test_plain_run_is_the_headline_only():
+    """Without --full the line is the headline of the timed steps alone: no strong-scaling pass, no CPU baseline."""
+    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--dry-engine", "--streams", "2048", "--seconds", "0.05"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["config"]["ranks_reported"] == 2
+    assert "strong_scaling" not in d["config"] and d["cpu_baseline"] is None
+    assert _run(["--steps", "0", "--dry-engine"]).returncode != 0
 
 
 def test_single_rank_dry_engine_has_no_launcher_hop():

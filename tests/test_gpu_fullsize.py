@@ -690,7 +690,7 @@ def test_config5_roundtrip_modulate_awgn_demodulate_full_length():
     import subprocess
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--streams", "16384", "--steps", "1",
-                        "--warmup", "0", "--cpu-seconds", "4"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--warmup", "0", "--cpu-seconds", "4", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]      # (exit 3 = a sampled stream differed from the oracle)
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     q = line["config"]["c5_quality"]
@@ -704,6 +704,34 @@ def test_config5_roundtrip_modulate_awgn_demodulate_full_length():
     # error in any length-matched frame.  The parity claim is the oracle comparison above; these are sanity floors.
     assert q["frame_success_rate"] >= 0.4 and q["frame_delivery_rate"] >= q["frame_success_rate"], q
     assert q["ber_on_length_matched_frames"] <= 1e-4, q
+
+
+def test_bench_dump_outputs_repeat_with_and_without_full(tmp_path):
+    """bench.py --dump-outputs writes what the last timed call returned: the same with the same arguments whether or not
+    --full adds its checks around the timed steps, within 64 MB, a sampled row's bytes ending where its stream's count says."""
+    import json
+    import subprocess
+    import sys
+    dumps = []
+    for i, extra in enumerate(([], ["--full", "--no-side", "--cpu-seconds", "1"])):
+        d = tmp_path / ("run%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--streams", "4096", "--seconds", "2", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(d)] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert (line["cpu_baseline"] is None) == (not extra)
+        dumps.append({f.stem: np.load(str(f)) for f in d.glob("*.npy")})
+    a, b = dumps
+    assert sorted(a) == ["bytes", "bytes_rows", "counts", "eod"] and sorted(b) == sorted(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    rows = a["bytes_rows"].astype(np.int64)
+    n = a["counts"][rows].astype(np.int64)
+    assert a["counts"].shape == (4096,) and n.sum() > 0
+    for j in range(len(rows)):
+        assert (a["bytes"][j, :n[j]] >= 0).all() and (a["bytes"][j, n[j]:] == -1).all(), rows[j]
 
 
 def test_idle_receiver_bank_one_frame_then_a_noise_floor():

@@ -30,7 +30,7 @@ def _worker(rank, world, port, n_streams, q):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         first, count = sharding.stream_shard(n_streams, rank, world)
-        base = np.load(os.path.join(ROOT, "tests", "golden", "golden.npz"))["d_default_AB.in"]
+        base = golden().array("d_default_AB.in")
         local = []
         for s in range(first, first + count):
             x = np.zeros(base.size + 64, np.float32)
