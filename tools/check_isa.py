@@ -188,14 +188,11 @@ def blk_checks():
     problems = []
     # (round 4: plus the four bodies of demod_blk_kernel_r<write-back, time-sliced>, the kernel whose block path takes resets)
     # (round 5: plus the four of demod_blk_kernel_rp<write-back, time-sliced>: the same for per-stream tone pairs)
-    # (round 6: a -DFSK_BLK_FIVE measurement build adds the eight of demod_blk5_kernel, five waves per group, compiled for 96 VGPRs; run
-    # over such a build this check flags scratch accesses in the rare paths inside its per-tile loops and, in the write-back
-    # instantiations, a dead component of the second counter quad re-used before the wait -- one of the reasons it is not shipped)
-    found = list(re.finditer(r"^(_ZN3fsk1[6789]demod_blk5?_kernel(?:_rp?)?I\w+):[^\n]*\n", text, re.M))
-    if len(found) != 16:     # (24 in a -DFSK_BLK_FIVE measurement build)
+    found = list(re.finditer(r"^(_ZN3fsk1[689]demod_blk_kernel(?:_rp?)?I\w+):[^\n]*\n", text, re.M))
+    if len(found) != 16:
         problems.append(("demod_blk_kernel", "expected 8 + 4 + 4 kernel bodies in the ISA, found %d" % len(found)))
-    for name, n in re.findall(r"\.name:\s+(_ZN3fsk1[6789]demod_blk5?_kernel(?:_rp?)?I\w+)\s*\n(?:[^\n]*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
-        if int(n) > (96 if "demod_blk5_kernel" in name else 128):
+    for name, n in re.findall(r"\.name:\s+(_ZN3fsk1[689]demod_blk_kernel(?:_rp?)?I\w+)\s*\n(?:[^\n]*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
+        if int(n) > 128:
             problems.append((name, "%s VGPRs: more than four workgroups per CU allow" % n))
     for m in found:
         body = text[m.end():text.index(".Lfunc_end", m.end())].split("\n")
@@ -260,7 +257,7 @@ def blk_checks():
                 n_scr = sum(1 for _, x in b["lines"] if x.startswith("scratch_"))
                 if n_scr > allowed:
                     problems.append((m.group(1), "%d scratch accesses inside blk_medium's block %s (allowed: %d)" % (n_scr, b["name"], allowed)))
-        if peeks < (5 if "demod_blk5_kernel" in m.group(1) else 4):   # (the compiler duplicates the back wave's block loop: six sites in the current build)
+        if peeks < 4:   # (the compiler duplicates the back wave's block loop: six sites in the current build)
             problems.append((m.group(1), "expected at least 4 asynchronous counter reads (one per part), found %d" % peeks))
     return problems
 

@@ -59,7 +59,7 @@ if os.environ.get("VAR_STAMPS"):
     six = "blk6" in eng.last_kernel()
     f = L.lib().fskdbg_read_stamps_blk6 if six else L.lib().fskdbg_read_stamps_blk if "blk" in eng.last_kernel() else L.lib().fskdbg_read_stamps
     f.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-    a = np.zeros((7 if six else 5 if "blk5" in eng.last_kernel() else 4, 2048, 8), np.uint64)
+    a = np.zeros((7 if six else 4, 2048, 8), np.uint64)
     NW = a.shape[0]
     assert f(a.ctypes.data, a.size) == 0
     g = min(2048, (S + eng.blk_lanes() - 1) // eng.blk_lanes() if eng.blk_lanes() else (S + 63) // 64)

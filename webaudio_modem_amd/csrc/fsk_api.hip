@@ -38,16 +38,14 @@ size_t demod_fused_lds_bytes(const DemodParams &P);
 // fsk_blk.hip: four waves per group, block-batched back wave
 size_t demod_blk_lds_bytes(const DemodParams &P);
 size_t demod_blk_lds_bytes(const DemodParams &P, uint32_t y_slots);
-size_t demod_blk_lds_bytes(const DemodParams &P, uint32_t y_slots, uint32_t waves);
 bool demod_blk_applicable(const DemodParams &P);
-bool demod_blk5_built();
 hipError_t set_blk_lds_limit(const DemodParams &P);
 hipError_t launch_demod_blk(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n,
                              size_t pitch, uint8_t *out, size_t out_pitch, uint32_t *out_counts,
                              uint32_t *eod_counts, hipStream_t stream, uint32_t resident_wgs, uint32_t slice_tiles, uint32_t y_slots,
-                             uint32_t lanes, uint32_t medium, bool *sliced_out, uint32_t waves = 4u);
+                             uint32_t lanes, uint32_t medium, bool *sliced_out);
 uint32_t demod_blk_lanes(uint32_t n_streams, int device);
-void demod_blk_plan(const DemodParams &P, uint32_t groups, int device, uint32_t *y_slots, uint32_t *resident_wgs, uint32_t waves = 4u);
+void demod_blk_plan(const DemodParams &P, uint32_t groups, int device, uint32_t *y_slots, uint32_t *resident_wgs);
 uint32_t demod_blk_slices(const DemodParams &P, const DemodState &S, size_t n, uint32_t resident_wgs, uint32_t slice_tiles,
                           uint32_t *slice_tiles_out);
 size_t demod_blk_queue_words(uint32_t groups);
@@ -226,15 +224,11 @@ struct fskhip_engine {
   uint32_t blk_min_tiles = 0;    // calls with fewer whole tiles than this stay with round 2's kernels
   uint32_t blk_y_slots = 6;      // half tiles in the block kernel's y ring: as deep as the LDS allows at this batch size
   bool blk_y_pinned = false;     // "blk_y_slots" was set: "blk_lanes" leaves it alone
-  // five waves per group (demod_blk5_kernel, round 6): the front wave's two halves on a wave each.  0 never, 1 wherever the plain
-  // four-wave kernel would run ("kernel" = five-wave), 2 auto: batches of whole-wave groups that fill the device
-  uint32_t use_five = 0;
   // the exact path (fp64, fsk_demod.hip) on two waves per 64-stream group -- loads + AGC + pre-filter | the rest (SPLIT2): 0 never
   // (the default: measured SLOWER, 156 against 180 Gsamples/s at config #3 -- at two waves per SIMD the back wave has 256 registers and
   // spills 864 bytes per lane, where the one-wave kernel spreads into the accumulation registers), 1 wherever it applies
   // ("exact_waves" = 2: bit-identical, tests/test_gpu_parity.py), 2 batches of at most one group per SIMD
   uint32_t exact_split = 0;
-  uint32_t blk5_y_slots = 6, blk5_resident = 0;
   // "blk_resets": which of fsk_blk.hip's two kernels a call launches -- demod_blk_kernel_r, whose block path takes 'eod' resets
   // itself, pays where resets are frequent (an idle receiver bank: +50 %) and costs ~4 % where they are rare.  auto: by the
   // share of tiles the PREVIOUS call's back waves took off their fast loop (the kernels count; the totals come back with an
@@ -312,6 +306,17 @@ void engine_refresh_kernel_choice(fskhip_engine *e) {
   // down its per-sample path because of a lane's own span also holds a sync candidate)
   e->blk_med_now = (double)dr >= (e->blk_med_now ? 0.10 : 0.20) * (double)dt;
   e->stat_tiles = tiles; e->stat_rare = rare;
+}
+// ... and the copy that brings the totals back, behind a launch of the four- or seven-wave kernel: behind every long call, behind
+// every eighth of a run of short ones (the copy is ~3 us of the stream's time, 7 % of a 128-sample call of 65 536 streams)
+static hipError_t engine_fetch_blk_stat(fskhip_engine *e, size_t n_fast, hipStream_t st) {
+  if (e->blk_medium != 3u || !e->h_stat || !e->S.blk_stat) return hipSuccess;
+  bool fetch = n_fast >= 4096 || (++e->stat_skip & 7u) == 0u;
+  if (!fetch) {                                      // (a call being captured into a graph is replayed many times: it fetches)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    fetch = hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+  }
+  return fetch ? hipMemcpyAsync((void *)e->h_stat, e->S.blk_stat, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) : hipSuccess;
 }
 void engine_note_replayed_call(fskhip_engine *e, size_t n) {
   e->demodulated = true;
@@ -700,7 +705,6 @@ int fskhip_create(const fskhip_config *cfgs, uint32_t n_cfgs, uint32_t n_streams
     e->h_stat[0] = 0ull; e->h_stat[1] = 0ull;
     e->blk_lanes = demod_blk_lanes(n_streams, device);
     demod_blk_plan(P, (n_streams + e->blk_lanes - 1u) / e->blk_lanes, device, &e->blk_y_slots, &e->blk_resident);
-    demod_blk_plan(P, (n_streams + e->blk_lanes - 1u) / e->blk_lanes, device, &e->blk5_y_slots, &e->blk5_resident, 5u);
     if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) e->cus = 0;
     if (demod_blk6_applicable(P)) CREATE_TRY(set_blk6_lds_limit(P));
     if (e->blk_resident && e->n_blocks > e->blk_resident) {
@@ -757,12 +761,8 @@ int fskhip_set_option(fskhip_engine *e, const char *name, const char *value) {
   int rc = FSKHIP_OK;
   if (k == "kernel") {          // which whole-tile kernel fp32 lock-step calls use
     const uint32_t n_blocks = e->n_blocks;
-    e->use_six = 0u; e->use_five = 0u;
-    if (v == "five-wave") {      // (measurement builds only: -DFSK_BLK_FIVE, fsk_blk.hip)
-      if (!demod_blk5_built()) return fail(FSKHIP_E_INVALID, "fskhip_set_option(kernel): five-wave is a measurement build's kernel (-DFSK_BLK_FIVE, profiles/r06_five_wave.txt): not in this library");
-      e->use_blk = true; e->use_split = true; e->split_forced = true; e->use_five = 1u;
-    }
-    else if (v == "auto") { e->use_blk = true; e->split_forced = false; e->use_split = n_blocks < e->split_cus * 8u; e->use_six = 2u; }
+    e->use_six = 0u;
+    if (v == "auto") { e->use_blk = true; e->split_forced = false; e->use_split = n_blocks < e->split_cus * 8u; e->use_six = 2u; }
     else if (v == "auto-r04") { e->use_blk = true; e->split_forced = false; e->use_split = n_blocks < e->split_cus * 8u; }   // (round 4's choice: never seven waves)
     else if (v == "auto-r02") { e->use_blk = false; e->split_forced = false; e->use_split = n_blocks < e->split_cus * 8u; }
     else if (v == "seven-wave" || v == "six-wave") { e->use_blk = true; e->use_split = true; e->split_forced = true; e->use_six = 1u; }   // (four waves where seven do not apply; "six-wave": its first name)
@@ -979,14 +979,7 @@ static int demod_device_impl(fskhip_engine *e, float *d_samples, size_t n, size_
             HIP_TRY(launch_demod_blk6(wb, app, e->P, e->S, d_samples + head, n_fast, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st,
                                       e->blk_lanes, e->six_y_slots ? e->six_y_slots : demod_blk6_y_slots(e->P), e->six_rolemap));
             e->last_sliced = false;
-            if (e->blk_medium == 3u && e->h_stat && e->S.blk_stat) {
-              bool fetch = n_fast >= 4096 || (++e->stat_skip & 7u) == 0u;
-              if (!fetch) {
-                hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-                fetch = hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-              }
-              if (fetch) HIP_TRY(hipMemcpyAsync((void *)e->h_stat, e->S.blk_stat, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            }
+            HIP_TRY(engine_fetch_blk_stat(e, n_fast, st));
             static const char *const names6[16] = {
                 "fsk::demod_blk6_kernel<false, 64>", "fsk::demod_blk6_kernel<false, 32>", "fsk::demod_blk6_kernel<false, 16>", "fsk::demod_blk6_kernel<false, 8>",
                 "fsk::demod_blk6_kernel<true, 64>", "fsk::demod_blk6_kernel<true, 32>", "fsk::demod_blk6_kernel<true, 16>", "fsk::demod_blk6_kernel<true, 8>",
@@ -995,21 +988,9 @@ static int demod_device_impl(fskhip_engine *e, float *d_samples, size_t n, size_
                 "fsk::demod_blk6_kernel<true, 64, false>", "fsk::demod_blk6_kernel<true, 32, false>", "fsk::demod_blk6_kernel<true, 16, false>", "fsk::demod_blk6_kernel<true, 8, false>"};
             e->last_kernel = names6[(e->P.uni_cfg ? 0 : 8) + (wb ? 4 : 0) + (e->blk_lanes == 64u ? 0 : e->blk_lanes == 32u ? 1 : e->blk_lanes == 16u ? 2 : 3)];
           } else {
-          // five waves per group where the plain four-wave kernel would run (the kernels whose block path takes resets have four)
-          const bool five = e->use_five != 0u && med == 0u && e->blk5_resident != 0u && e->blk_resident == e->blk5_resident;
           HIP_TRY(launch_demod_blk(wb, app, e->P, e->S, d_samples + head, n_fast, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st,
-                                   e->blk_resident, e->blk_slice_tiles, five ? e->blk5_y_slots : e->blk_y_slots, e->blk_lanes, med, &e->last_sliced,
-                                   five ? 5u : 4u));
-          // (the totals are fetched behind every long call, behind every eighth of a run of short ones: the copy is ~3 us of
-          // the stream's time, 7 % of a 128-sample call of 65 536 streams)
-          if (e->blk_medium == 3u && e->h_stat && e->S.blk_stat) {
-            bool fetch = n_fast >= 4096 || (++e->stat_skip & 7u) == 0u;
-            if (!fetch) {                                      // (a call being captured into a graph is replayed many times: it fetches)
-              hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-              fetch = hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-            }
-            if (fetch) HIP_TRY(hipMemcpyAsync((void *)e->h_stat, e->S.blk_stat, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-          }
+                                   e->blk_resident, e->blk_slice_tiles, e->blk_y_slots, e->blk_lanes, med, &e->last_sliced));
+          HIP_TRY(engine_fetch_blk_stat(e, n_fast, st));
           static const char *const names[12] = {
               "fsk::demod_blk_kernel<false, false, false>", "fsk::demod_blk_kernel<false, false, true>",
               "fsk::demod_blk_kernel<false, true, false>", "fsk::demod_blk_kernel<false, true, true>",
@@ -1019,16 +1000,9 @@ static int demod_device_impl(fskhip_engine *e, float *d_samples, size_t n, size_
               "fsk::demod_blk_kernel_r<true, false>", "fsk::demod_blk_kernel_r<true, true>"};
           static const char *const names_rp[4] = {"fsk::demod_blk_kernel_rp<false, false>", "fsk::demod_blk_kernel_rp<false, true>",
                                                   "fsk::demod_blk_kernel_rp<true, false>", "fsk::demod_blk_kernel_rp<true, true>"};
-          static const char *const names5[8] = {
-              "fsk::demod_blk5_kernel<false, false, false>", "fsk::demod_blk5_kernel<false, false, true>",
-              "fsk::demod_blk5_kernel<false, true, false>", "fsk::demod_blk5_kernel<false, true, true>",
-              "fsk::demod_blk5_kernel<true, false, false>", "fsk::demod_blk5_kernel<true, false, true>",
-              "fsk::demod_blk5_kernel<true, true, false>", "fsk::demod_blk5_kernel<true, true, true>"};
-          if (five) e->last_kernel = names5[(wb ? 4 : 0) + (e->P.uni_cfg ? 2 : 0) + (e->last_sliced ? 1 : 0)];
-          else if (med && !e->P.uni_cfg) e->last_kernel = names_rp[(wb ? 2 : 0) + (e->last_sliced ? 1 : 0)];
-          else
-          e->last_kernel = med ? names[8 + (wb ? 2 : 0) + (e->last_sliced ? 1 : 0)]                  // <writeback, time-sliced>
-                               : names[(wb ? 4 : 0) + (e->P.uni_cfg ? 2 : 0) + (e->last_sliced ? 1 : 0)];   // <writeback, uniform, time-sliced>
+          if (med && !e->P.uni_cfg) e->last_kernel = names_rp[(wb ? 2 : 0) + (e->last_sliced ? 1 : 0)];
+          else e->last_kernel = med ? names[8 + (wb ? 2 : 0) + (e->last_sliced ? 1 : 0)]                  // <writeback, time-sliced>
+                                    : names[(wb ? 4 : 0) + (e->P.uni_cfg ? 2 : 0) + (e->last_sliced ? 1 : 0)];   // <writeback, uniform, time-sliced>
           }
         } else if (two_wave) {
           HIP_TRY(launch_demod_pipe(wb, app, e->P, e->S, d_samples + head, n_fast, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st));

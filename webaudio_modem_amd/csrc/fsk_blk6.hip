@@ -184,40 +184,17 @@ __device__ __forceinline__ float lp_step(LpLane &L, float a2, float nd, float v,
   return L.y;
 }
 
-// (front_agc / front_bp -- front_agc_bp as its two halves -- live in fsk_pipe_dev.h since round 6: fsk_blk.hip's five-wave kernel uses them too)
+// (front_agc / front_bp -- front_agc_bp as its two halves -- live in fsk_pipe_dev.h)
 
 // Every hand-off wait of this kernel is a bounded poll (FSK_SPIN, fsk_pipe_dev.h): a wave that gets nowhere in FSK_SPIN_CAP polls
 // of one wait flags the engine's hand-off fault word and ends, the waves waiting on it follow, the host reports FSKHIP_E_INTERNAL.
 #define B6_SPIN(arg) FSK_SPIN(arg, S.blk_stat)
-#ifndef FSK_B6_SLEEP
-#define FSK_B6_SLEEP 1
-#endif
-#ifndef FSK_B6_LEAN
-#define FSK_B6_LEAN 1
-#endif
-// the frame wave's own-span tiles on the block path that takes resets (blk6_medium) instead of sample by sample
-#ifndef FSK_B6_MEDIUM
-#define FSK_B6_MEDIUM 1
-#endif
-// Hand-off counters.  FSK_B6_POSTWAIT = 1: a wave waits for its own LDS writes (lgkmcnt(0)) before it writes the counter that
-// publishes them, as fsk_blk.hip does; 0: it does not -- the LDS executes a wave's instructions in order, so the counter's write
-// is performed after the data's, and a reader that has seen the counter reads after both.  The wait costs the producer ~100
-// cycles per hand-off; with only three tiles of lead allowed between the iq wave and the frame wave (kZeroLagPairs) every hand-off's
-// latency is on the ring's critical path.
-#ifndef FSK_B6_POSTWAIT
-#define FSK_B6_POSTWAIT 1
-#endif
+// Hand-off counters: a wave waits for its own LDS writes (lgkmcnt(0)) before it writes the counter that publishes them, as
+// fsk_blk.hip does.  (Not waiting is correct too -- the LDS executes a wave's instructions in order -- but gained 0.5 % at most:
+// the wait behind the post, for the counter's read-back, covers the same latency; profiles/r06_seven_wave_per_stream.txt.)
 __device__ inline void b6_post(uint32_t *p, uint32_t v) {
-#if FSK_B6_POSTWAIT
   asm volatile("s_waitcnt lgkmcnt(0)\n\tds_write_b32 %0, %1" : : "v"((uint32_t)(uintptr_t)p), "v"(v) : "memory");
-#else
-  asm volatile("ds_write_b32 %0, %1" : : "v"((uint32_t)(uintptr_t)p), "v"(v) : "memory");
-#endif
 }
-// poll period of the three waves on the x ring (x 64 cycles; the waves before it keep FSK_B6_SLEEP)
-#ifndef FSK_B6_SLEEP_RING
-#define FSK_B6_SLEEP_RING 1
-#endif
 
 // UNI = false (round 6): per-stream tone pairs.  What changes: the pre-filter wave takes its coefficients per stream
 // (front_load<false>), the iq wave rotates a per-lane phasor -- the tile's first from the exact accumulator, the other fifteen by
@@ -353,7 +330,7 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
         FSK_STAMP_W0 FSK_WAIT_BEGIN
         while (2u * t + 2u - used > 2u * kB6Stage) {
           used = lds_peek(&ctr[C6_Y]);
-          if (2u * t + 2u - used > 2u * kB6Stage) B6_SPIN(FSK_B6_SLEEP);
+          if (2u * t + 2u - used > 2u * kB6Stage) B6_SPIN(kPollSleep);
         }
         FSK_STAMP_W1
       }
@@ -403,11 +380,11 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
         FSK_STAMP_W0 FSK_WAIT_BEGIN
         while (produced < hidx + 2u) {
           produced = lds_peek(&ctr[c_in]);
-          if (produced < hidx + 2u) B6_SPIN(FSK_B6_SLEEP);
+          if (produced < hidx + 2u) B6_SPIN(kPollSleep);
         }
         while (do_bp && hidx + 1u - consumed >= NY) {         // y ring full: the frame wave (which may still need the slots'
           consumed = lds_peek(&ctr[C6_CONS]);                 // pre-filter outputs after a reset) has not released them
-          if (hidx + 1u - consumed >= NY) B6_SPIN(FSK_B6_SLEEP);
+          if (hidx + 1u - consumed >= NY) B6_SPIN(kPollSleep);
         }
         FSK_STAMP_W1
       }
@@ -486,11 +463,11 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
         FSK_STAMP_W0 FSK_WAIT_BEGIN
         while (produced < hidx + 2u) {
           produced = lds_peek(&ctr[C6_Y]);
-          if (produced < hidx + 2u) B6_SPIN(FSK_B6_SLEEP_RING);
+          if (produced < hidx + 2u) B6_SPIN(kPollSleep);
         }
         while (hidx + 2u - consumed > 2u * kB6XT) {          // x ring full: wait for the frame wave
           consumed = lds_peek(&ctr[C6_CONS]);
-          if (hidx + 2u - consumed > 2u * kB6XT) B6_SPIN(FSK_B6_SLEEP_RING);
+          if (hidx + 2u - consumed > 2u * kB6XT) B6_SPIN(kPollSleep);
         }
         FSK_STAMP_W1
       }
@@ -595,11 +572,11 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
         FSK_STAMP_W0 FSK_WAIT_BEGIN
         while (produced < hidx + 2u) {
           produced = lds_peek(&ctr[C6_IQ]);
-          if (produced < hidx + 2u) B6_SPIN(FSK_B6_SLEEP_RING);
+          if (produced < hidx + 2u) B6_SPIN(kPollSleep);
         }
         while (hidx + 2u - consumed > 2u * kB6DT) {          // a correction posted now is due kHandLag ahead: no further than that
           consumed = lds_peek(&ctr[C6_CONS]);
-          if (hidx + 2u - consumed > 2u * kB6DT) B6_SPIN(FSK_B6_SLEEP_RING);
+          if (hidx + 2u - consumed > 2u * kB6DT) B6_SPIN(kPollSleep);
         }
         FSK_STAMP_W1
       }
@@ -750,7 +727,7 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
             continue;
           }
           if (t < nt && produced >= 2u * t + 2u) break;
-          B6_SPIN(FSK_B6_SLEEP_RING);
+          B6_SPIN(kPollSleep);
         }
         FSK_STAMP_W1
       }
@@ -846,7 +823,7 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
           for (;;) {
             pw = lds_peek(&ctr[C6_P4]);
             if ((pw >> 24) == gen && (pw & 0xFFFFFFu) >= t + 2u) break;
-            B6_SPIN(FSK_B6_SLEEP_RING);
+            B6_SPIN(kPollSleep);
           }
           FSK_STAMP_W1
         }
@@ -905,7 +882,7 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
             for (;;) {
               const uint32_t pw2 = lds_peek(&ctr[C6_P4]);
               if ((pw2 >> 24) == gen && (pw2 & 0xFFFFFFu) >= t + 2u) { produced = pw2 & 0xFFFFFFu; break; }
-              B6_SPIN(FSK_B6_SLEEP_RING);
+              B6_SPIN(kPollSleep);
             }
             FSK_STAMP_W1
           }
@@ -919,7 +896,7 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
         v4f fa[4], fb[4];
         fload(fa);
         // every stream of the wave inside a frame (lanes without a stream do not count): the lean block, matched re-formed later
-        if (FSK_B6_LEAN && __builtin_amdgcn_ballot_w64(C.valid & (B.thr_eff != kStartedP)) == 0ull) {
+        if (__builtin_amdgcn_ballot_w64(C.valid & (B.thr_eff != kStartedP)) == 0ull) {
           matched_stale = true;
           for (;;) {
             int r = ftile(std::true_type(), fa, fb);
@@ -945,7 +922,7 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
             for (;;) {                                         // (P4 has produced this tile: its entry state is in the history)
               const uint32_t pw = lds_peek(&ctr[C6_P4]);
               if ((pw >> 24) == gen && (pw & 0xFFFFFFu) >= t + 2u) break;
-              B6_SPIN(FSK_B6_SLEEP_RING);
+              B6_SPIN(kPollSleep);
             }
             const v4f *ht = hist + slot_t * 2u * 64u;
             const v4f a = ht[lane], b = ht[64u + lane];
@@ -956,7 +933,7 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
         {
           uint32_t p3 = 0;
           FSK_STAMP_W0 FSK_WAIT_BEGIN
-          while ((p3 = lds_peek(&ctr[C6_X])) < t + 2u) B6_SPIN(FSK_B6_SLEEP_RING);
+          while ((p3 = lds_peek(&ctr[C6_X])) < t + 2u) B6_SPIN(kPollSleep);
           FSK_STAMP_W1
         }
         if (X.zlive != 0u) { rare_tiles++; FSK_STAMP_COUNT(1) } else { FSK_STAMP_COUNT(3) }
@@ -965,7 +942,7 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
         // block test has seen: the block path that takes resets (blk_medium's sequence, straight-line: a rare tile sample by
         // sample is ~2 200 instructions and 240 branches, 13 fast tiles' time, and nothing upstream can run ahead meanwhile)
         bool medium_done = false;
-        if (FSK_B6_MEDIUM && !amp_misaligned && __builtin_amdgcn_ballot_w64((int32_t)hardw < 0) == 0ull) {
+        if (!amp_misaligned && __builtin_amdgcn_ballot_w64((int32_t)hardw < 0) == 0ull) {
           const v4f *xt = xring + slot_t * kB6TileV4;
           const v4f *ztile = zt + ((t >> 1) & ZTM) * 8u;
           const v4f *ys0 = yring + (t % NY) * 2u * 64u, *ys1 = yring + ((t + 1u) % NY) * 2u * 64u;

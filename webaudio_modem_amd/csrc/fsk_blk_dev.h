@@ -20,6 +20,7 @@ static_assert(4u * kBlkSlots <= kZeroLagPairs, "the wave that owns the I/Q low-p
 static_assert(4u * kBlkSlots <= kOwnLag4, "the discriminator wave (up to 4 * kBlkSlots - 1 samples beyond the start of the back wave's tile) must not have reached the hand-over sample when it is posted");
 static constexpr uint32_t kBlkSlotV4 = 2 * 64;     // v4f per x-ring slot: four pair sums (I, Q) -- in place -> four (phase, magnitude)
 static constexpr uint32_t kFlushBlocks = 16;       // byte queues are flushed every this many blocks
+static constexpr uint32_t kPollSleep = 1;          // s_sleep argument (x 64 cycles) of every wave's per-tile hand-off poll
 // The y ring (wave 0 -> wave 1) may be deeper than the x ring.  With six slots everywhere the four waves hold exactly
 // three tiles between them and each tile goes round the closed chain "back wave frees a slot -> wave 0 -> 1 -> 2 -> back
 // wave": the group advances a tile per (t0 + t1 + t2 + t3) / 3, not per max(t) (measured busy cycles per sample at 8 192
@@ -83,10 +84,6 @@ __device__ inline uint32_t blk_clock(BackLane &Bn, const BackK &K, const BlkK &Q
 // The fast path of one block (a tile: eight decimated samples).  Works on copies (Bn, rp, bq, nq): the caller commits
 // them only if the returned flag word has its sign bit clear in every lane.  kv0 = pushes before the block.  hard_out:
 // the same without the 'eod' bound -- a sync candidate or a bad start / stop bit, which only the per-sample path takes.
-// LEAN (round 5): every stream of the wave is inside a frame (thr_eff = kStartedP: no sync search, fsk.ts:297), so the
-// correlator's running count cannot matter before a rare path is taken: it is not carried (seven of the vector instructions
-// per decimated sample) and the caller re-forms it from the polyphase registers when it next needs it.
-template <bool LEAN = false>
 __device__ inline uint32_t blk_fast(BackLane &Bn, const BackK &K, const BlkK &Q, uint32_t kv0, const v4f (&pa)[4],
                                     uint32_t (&rp)[kBlk], float (&am)[kBlk], uint32_t &bq, uint32_t &nq, uint32_t &hard_out) {
   const float phs[kBlk] = {pa[0].x, pa[0].z, pa[1].x, pa[1].z, pa[2].x, pa[2].z, pa[3].x, pa[3].z};
@@ -108,16 +105,14 @@ __device__ inline uint32_t blk_fast(BackLane &Bn, const BackK &K, const BlkK &Q,
     const uint32_t rold = rp[j];
     const uint32_t r = __builtin_amdgcn_alignbit(rold, nf, 31);              // syncSamplesBuffer.put(bit)
     rp[j] = r;
-    if (!LEAN) {
-      dm += (uint32_t)__builtin_popcount((r ^ K.qn) & K.mask);
-      dm -= (uint32_t)__builtin_popcount((rold ^ K.qn) & K.mask);
-      hard |= ~dm;                                                           // sign set <=> matched >= thr_eff (sync candidate)
-    }
+    dm += (uint32_t)__builtin_popcount((r ^ K.qn) & K.mask);
+    dm -= (uint32_t)__builtin_popcount((rold ^ K.qn) & K.mask);
+    hard |= ~dm;                                                             // sign set <=> matched >= thr_eff (sync candidate)
     const uint32_t silent = neg_mask(__builtin_bit_cast(uint32_t, am[j] - Bn.thr));   // fsk.ts:285
     lsr = (lsr & silent) | ((uint32_t)(j + 1) & ~silent);
     w = __builtin_amdgcn_alignbit(w, nf, 31);                                // sample 1 ends up in bit kBlk - 1
   }
-  if (!LEAN) Bn.matched = dm + Bn.thr_eff;
+  Bn.matched = dm + Bn.thr_eff;
   Bn.ls = lsr + kv0;
   // 'eod' (fsk.ts:288): no silence run inside the block is longer than the one a wholly silent block would end with
   // (eod_m1 - ((kv0 + kBlk) - ls at entry))

@@ -49,9 +49,6 @@
 #include "fsk_f64math.h"
 #include "fsk_wait.h"
 
-#ifndef FSK_FAST_WAVES
-#define FSK_FAST_WAVES 4
-#endif
 #ifndef FSK_F32_WAVES_PER_SIMD
 #define FSK_F32_WAVES_PER_SIMD 2
 #endif
@@ -716,9 +713,6 @@ __device__ inline bool block_fsm(Lane<Real> &L, const DemodParams &P, const Demo
 // precision instruction occupies the pipe for 4 cycles while a lone wave issues one instruction per ~5.7 -- two instruction
 // streams per SIMD instead of one.
 static constexpr uint32_t kPreTiles = 3;
-#ifndef FSK_SPLIT2_BLOCK
-#define FSK_SPLIT2_BLOCK 8      // decimated samples per block of the two-wave kernel's back wave (4 was tried: 736 instead of 864 bytes of spills per lane, and slower still -- 144 against 156 Gsamples/s)
-#endif
 template <typename Real, typename PolyT, bool FRAC, bool UNI, bool TRACE, bool SPLIT2 = false>
 __global__ __launch_bounds__(SPLIT2 ? 128 : 64, (sizeof(Real) == 4 ? FSK_F32_WAVES_PER_SIMD : SPLIT2 ? 2 : 1)) void demod_kernel(DemodParams P, DemodState S, float *__restrict__ samples,
                                                    size_t n, size_t pitch, int vec_ok, int writeback, int append,
@@ -938,8 +932,9 @@ __global__ __launch_bounds__(SPLIT2 ? 128 : 64, (sizeof(Real) == 4 ? FSK_F32_WAV
   // itself restates fsk.ts:278-375 for a lane without such an event: at most ONE bit decision falls into a block (they
   // are dsSPB >= 8 decimated samples apart -- the caller checks), at sample jd = bit_wait on entry.
   // Returns false if the block has to be redone.
-  // (round 6: NBD decimated samples per block -- eight, or four in the two-wave kernel, whose back wave has 256 registers)
-  constexpr int NBD = SPLIT2 ? FSK_SPLIT2_BLOCK : 8;
+  // (NBD decimated samples per block.  Four in the two-wave kernel, whose back wave has 256 registers, was tried in round 6: 736
+  // instead of 864 bytes of spills per lane, and slower still -- 144 against 156 Gsamples/s)
+  constexpr int NBD = 8;
   auto block16 = [&](const float (&x)[2 * NBD], float (&wbv)[2 * NBD]) -> bool {
     const Lane<Real> L0 = L;                                   // everything this block may touch (poly / amplitude ring / output: written at the end)
     Real amp[NBD], post[NBD];

@@ -108,7 +108,7 @@ __device__ inline void front_agc_bp(FrontLane &F, const FrontK &K, float xin, fl
   F.by2 = F.by1; F.by1 = v;
   y = v;
 }
-// front_agc_bp as its two halves (the seven-wave kernel of fsk_blk6.hip and the five-wave kernel of fsk_blk.hip give them to different waves), instruction for instruction: the AGC (fsk.ts:52-76) ...
+// front_agc_bp as its two halves (the seven-wave kernel of fsk_blk6.hip gives them to different waves), instruction for instruction: the AGC (fsk.ts:52-76) ...
 __device__ __forceinline__ float front_agc(FrontLane &F, const FrontK &K, float xin) {
   const float xv = xin * F.g;
   const float level = __builtin_fabsf(xv);
