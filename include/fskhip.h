@@ -26,7 +26,8 @@ extern "C" {
  * environment variable any more), fskhip_clock_probe_begin / _end, fskhip_debug_state.  5: fskhip_blk_lanes, option
  * "blk_lanes" (additions only).  6: kernel = seven-wave / auto-r04, options "stage_min_tiles" / "stage_y_slots" / "stage_roles"; the batched
  * IIRFilter of fskhip_next.h (additions only).  7: fskhip_get_faults (additions only).  8: FSKHIP_E_HANDOFF -- every hand-off wait of
- * the multi-wave kernels is bounded ("Hand-off waits" below; an addition: no healthy call returns it). */
+ * the multi-wave kernels is bounded ("Hand-off waits" below; an addition: no healthy call returns it); fskhip_remap_streams (an
+ * addition, same version). */
 #define FSKHIP_ABI_VERSION 8
 #define FSKHIP_MAX_PATTERN_BYTES 16
 
@@ -115,6 +116,43 @@ int fskhip_destroy(fskhip_engine *e);
  * of the old engine; the two engines must agree in stream count, precision and device.
  */
 int fskhip_carry_over(fskhip_engine *dst, const fskhip_engine *src);
+
+/*
+ * Stream remapping (ABI 8, an addition): grow, shrink, reorder or split a live batch -- the host side of the reference, which
+ * creates, drops and reorders FSKCore instances at will.  n_map == fskhip_n_streams(dst); map[i] is a stream of src (0 ..
+ * n_src-1) or -1:
+ *   map[i] >= 0  stream i of dst continues stream map[i] of src exactly as if that FSKCore had been moved: every state word
+ *                (what fskhip_debug_state returns, the fp32 free-running-frame and reset fields included), the polyphase sync
+ *                registers, the amplitude ring, the signal-quality accumulators (and whether they run: dst takes over src's
+ *                fskhip_enable_signal_quality state), the status counters (demodulationCalls,
+ *                totalSamplesProcessed, syncDetections, eodCount) and with them the fault flag of fskhip_get_faults.  A source
+ *                stream may appear more than once (independent clones); source streams not named are dropped.
+ *   map[i] == -1 stream i is new FSKCore() + configure(its config of dst): it behaves, and counts, as a freshly created engine's.
+ *                Its rings sit on the engine's grid (fskhip_debug_state shows other ring positions than a fresh engine's).
+ *                Its bytes, 'eod' events and status counters are a fresh engine's; its state words are too, bit for bit, on an
+ *                FSKHIP_PRECISION_F64 engine whose src has taken a multiple of 32 samples (the NCO phasor is re-evaluated on the
+ *                engine's 32-sample grid, fsk_params.h, as after fskhip_reset).  Elsewhere its intermediates may round differently
+ *                (fp64 within the phasor's 2e-14; fp32 to its usual bar against the reference -- an FSKHIP_PRECISION_F32 engine of
+ *                ONE shared configuration runs a new stream's I/Q low-pass in the engine's free-running frame, as after a reset).
+ * src is read only and stays usable.  The call is synchronous, like fskhip_carry_over.  Preconditions, each FSKHIP_E_INVALID
+ * with a message naming the first offending index: dst made by fskhip_create and not demodulated yet, dst != src, same
+ * precision and device, the two engines' configurations equal but for the per-stream fields (markFrequency, spaceFrequency,
+ * preFilterBandwidth) whatever the map -- an all -1 map included: dst takes over src's ring grid --, every map entry in range,
+ * and the config of dst stream i equal to that of src stream map[i] in every fskhip_config field (per stream where the configs
+ * are per stream).  A src that has reported FSKHIP_E_HANDOFF is refused with
+ * that code.  Options set on dst stay dst's own (fskhip_set_option works on dst until its first demodulate call); traces are
+ * not carried.  fskhip_processor objects (fskhip_next.h: RX rings, pending modulations) stay bound to their own engine and
+ * are not remapped.
+ * Lock step: dst takes over src's decimator phase and ring grid, so a lock-step fp32 src keeps dst on the whole-tile kernels,
+ * new streams included (an empty ring placed at the engine's grid reads nothing before its own pushes).  dst leaves lock
+ * step -- exactly as fskhip_reset of one stream does, and runs on the generic kernel, exact -- only where new streams meet
+ *   - a src mid decimator-pair (an odd number of samples so far; a map of new streams only restarts every decimator instead),
+ *   - a fractional sync-ring capacity,
+ *   - a src that is out of lock step already (then continued streams keep it too).
+ * Out of lock step an fp32 engine demodulates on its per-sample generic kernel, whose rounding is not the whole-tile kernels': its
+ * continued streams then hold the fp32 bar against the reference rather than being bit for bit the source's continuation.
+ */
+int fskhip_remap_streams(fskhip_engine *dst, const fskhip_engine *src, const int64_t *map, uint32_t n_map);
 
 uint32_t fskhip_n_streams(const fskhip_engine *e);
 

@@ -53,6 +53,8 @@ export class FSKBatch {
   getFaults(): Uint8Array;
   enableSignalQualityEstimates(on?: boolean): void;
   getSignalQualityEstimates(stream?: number): SignalQualityEstimates;
+  /** a new batch of map.length streams: stream i continues stream map[i] of this one as if moved, or is new where map[i] is -1 */
+  remap(map: ArrayLike<number>, configs?: Partial<FSKConfig> | Partial<FSKConfig>[]): FSKBatch;
   close(): void;
 }
 /** one Node process, several GPUs: one FSKBatch per device over contiguous stream blocks, calls issued together */

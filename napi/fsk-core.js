@@ -132,8 +132,9 @@ class FSKBatch {
     this.nStreams = nStreams;
     this.configs = Array.isArray(configs) ? configs.map((c) => Object.assign({}, DEFAULT_FSK_CONFIG, c))
                                           : Object.assign({}, DEFAULT_FSK_CONFIG, configs);
-    this.handle = addon.create(this.configs, nStreams, options.device || 0,
-                               options.precision === undefined ? PRECISION_F32 : options.precision);
+    this.device = options.device || 0;
+    this.precision = options.precision === undefined ? PRECISION_F32 : options.precision;
+    this.handle = addon.create(this.configs, nStreams, this.device, this.precision);
   }
   // returns {bytes: Uint8Array[S], eod: Uint32Array(S)}
   demodulateData(samples, nPerStream, pitch, writebackAgc) {
@@ -169,6 +170,29 @@ class FSKBatch {
   getFaults() { return addon.getFaults(this.handle, this.nStreams); }
   enableSignalQualityEstimates(on) { addon.enableSignalQuality(this.handle, on === undefined ? true : !!on); }
   getSignalQualityEstimates(stream) { return addon.getSignalQualityEstimates(this.handle, stream || 0); }
+  // a new FSKBatch of map.length streams: stream i continues stream map[i] of this batch as if that FSKCore had been moved
+  // (bytes, counters, rings, filter state), or is a new FSKCore where map[i] is -1; this batch is left as it is
+  // (include/fskhip.h, fskhip_remap_streams).  Configs come from this batch by the map unless given; a -1 slot needs an
+  // explicit config when this batch has per-stream configs.
+  remap(map, configs) {
+    const m = Array.from(map, Number);
+    let cfgs = configs;
+    if (cfgs === undefined) {
+      if (!Array.isArray(this.configs)) cfgs = this.configs;
+      else {
+        if (m.some((v) => v < 0)) throw new Error('FSKBatch.remap: a -1 slot needs an explicit config (per-stream configs)');
+        cfgs = m.map((v) => this.configs[v]);
+      }
+    }
+    const b = new FSKBatch(m.length, cfgs, { device: this.device, precision: this.precision });
+    try {
+      addon.remapStreams(b.handle, this.handle, m);
+    } catch (err) {
+      b.close();
+      throw err;
+    }
+    return b;
+  }
   close() { if (this.handle) { addon.destroy(this.handle); this.handle = null; } }
 }
 

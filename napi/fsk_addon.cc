@@ -392,6 +392,37 @@ static napi_value CarryOver(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// remapStreams(dst, src, map): stream i of dst continues stream map[i] of src, or starts afresh where map[i] is -1
+// (fskhip_remap_streams); map is an Array of integers, one per stream of dst
+static napi_value RemapStreams(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  fskhip_engine *dst = get_engine(env, argv[0]);
+  if (!dst) return nullptr;
+  fskhip_engine *src = get_engine(env, argv[1]);
+  if (!src) return nullptr;
+  bool is_arr = false;
+  NAPI_OK(napi_is_array(env, argv[2], &is_arr));
+  if (!is_arr) { napi_throw_type_error(env, nullptr, "remapStreams: map must be an Array of stream indices (-1: a new stream)"); return nullptr; }
+  uint32_t n = 0;
+  NAPI_OK(napi_get_array_length(env, argv[2], &n));
+  std::vector<int64_t> map(n);
+  for (uint32_t i = 0; i < n; i++) {
+    napi_value v;
+    NAPI_OK(napi_get_element(env, argv[2], i, &v));
+    double d = 0;
+    if (napi_get_value_double(env, v, &d) != napi_ok || d != (double)(int64_t)d) {
+      napi_throw_type_error(env, nullptr, "remapStreams: map entries must be integers");
+      return nullptr;
+    }
+    map[i] = (int64_t)d;
+  }
+  int rc = fskhip_remap_streams(dst, src, map.data(), n);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+
 static void set_num(napi_env env, napi_value obj, const char *k, double v);
 
 // enableSignalQuality(handle, on) / getSignalQualityEstimates(handle, stream): the opt-in estimates of include/fskhip.h
@@ -513,6 +544,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"modulatedLength", nullptr, ModulatedLength, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"reset", nullptr, Reset, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"carryOver", nullptr, CarryOver, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"remapStreams", nullptr, RemapStreams, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"enableSignalQuality", nullptr, EnableSignalQuality, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"getSignalQualityEstimates", nullptr, GetSignalQualityEstimates, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"getStatus", nullptr, GetStatus, nullptr, nullptr, nullptr, napi_default, nullptr},

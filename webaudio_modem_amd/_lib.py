@@ -92,6 +92,7 @@ _SYMBOLS = [
     ("fskhip_butterworth_bandpass", None, [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double),
                                            C.POINTER(C.c_double)]),
     ("fskhip_carry_over", C.c_int, [_P, _P]),
+    ("fskhip_remap_streams", C.c_int, [_P, _P, _P, C.c_uint32]),
     ("fskhip_enable_signal_quality", C.c_int, [_P, C.c_int]),
     ("fskhip_get_signal_quality", C.c_int, [_P, C.c_uint32, C.POINTER(SignalQuality)]),
     ("fskhip_host_alloc", C.c_int, [C.c_size_t, C.POINTER(_P)]),

@@ -72,6 +72,9 @@ hipError_t launch_awgn(float *buf, size_t n, size_t pitch, uint32_t n_streams, d
                        double *sigma, hipStream_t st);
 hipError_t launch_probe_read(const float *buf, size_t n, size_t pitch, uint32_t n_streams, float *sink, hipStream_t st);
 uint8_t host_synth_payload_byte(uint64_t seed, uint32_t stream, uint32_t frame, uint32_t i);
+// fsk_remap.hip: the state gather of fskhip_remap_streams
+hipError_t launch_remap(int precision, const RemapArgs &A, const int64_t *d_map, const DemodState &D, const DemodState &S,
+                        hipStream_t st);
 void host_synth_stream_params(uint64_t seed, uint32_t stream, uint32_t lead_max, double amp_lo, double amp_hi,
                               uint32_t *lead, double *amp);
 }  // namespace fsk
@@ -201,6 +204,8 @@ struct fskhip_engine {
   int precision = 0;
   uint32_t n_streams = 0;
   fskhip_config cfg0{};
+  std::vector<fskhip_config> cfgs;   // as given to fskhip_create: one (shared) or one per stream
+  uint32_t matched_zero = 0;         // `matched` of a stream with an all-zero bit history (init_kernel)
   DemodParams P{};
   ModParams M{};
   DemodState S{};
@@ -448,6 +453,7 @@ int fskhip_create(const fskhip_config *cfgs, uint32_t n_cfgs, uint32_t n_streams
   fskhip_engine *e = new (std::nothrow) fskhip_engine();
   if (!e) return fail(FSKHIP_E_NOMEM, "out of host memory");
   e->device = device; e->precision = precision; e->n_streams = n_streams; e->cfg0 = c0;
+  e->cfgs.assign(cfgs, cfgs + n_cfgs);
   {
     // below two waves per SIMD the one-wave-per-group kernel cannot hide its own dependency stalls; the two-wave kernel
     // gives every group two instruction streams, as long as all its workgroups' LDS tiles fit on the CUs at once.
@@ -550,6 +556,7 @@ int fskhip_create(const fskhip_config *cfgs, uint32_t n_cfgs, uint32_t n_streams
   }
   P.wide = (n_bits > 31 || frac) ? 1u : 0u;
   const uint32_t matched_zero = P.d * (uint32_t)__builtin_popcountll(~P.pat_q & P.pat_mask);
+  e->matched_zero = matched_zero;
   P.stop_pos = c0.parity == 0 ? 9 : 10;  // fsk.ts:348
   P.parity_on = c0.parity != 0;
   P.agc_on = c0.agcEnabled != 0;
@@ -738,6 +745,93 @@ int fskhip_carry_over(fskhip_engine *dst, const fskhip_engine *src) {
   dst->total_samples = src->total_samples;
   dst->base_calls = src->base_calls;
   dst->base_samples = src->base_samples;
+  return FSKHIP_OK;
+}
+
+static int handoff_check(fskhip_engine *e, bool blocking);
+
+// Every fskhip_config field (fsk.ts:5-17): what stream i of a remap's destination and the source stream it continues must share.
+static bool config_equal(const fskhip_config &a, const fskhip_config &b) {
+  return shared_fields_equal(a, b) && a.markFrequency == b.markFrequency && a.spaceFrequency == b.spaceFrequency &&
+         a.preFilterBandwidth == b.preFilterBandwidth && (a.adaptiveThreshold != 0) == (b.adaptiveThreshold != 0);
+}
+static const fskhip_config &stream_config(const fskhip_engine *e, size_t s) { return e->cfgs.size() == 1 ? e->cfgs[0] : e->cfgs[s]; }
+
+// Stream i of dst continues stream map[i] of src as if that FSKCore had been moved, or (map[i] = -1) starts as a new one
+// (include/fskhip.h).  Synchronous: every check first, then one gather launch (fsk_remap.hip), then the host-side counters.
+int fskhip_remap_streams(fskhip_engine *dst, const fskhip_engine *src, const int64_t *map, uint32_t n_map) {
+  if (n_map > 0 && !map) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: null map");
+  for (uint32_t i = 0; i < n_map; i++)
+    if (map[i] < -1) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: map[%u] = %lld (a source stream or -1)", i, (long long)map[i]);
+  if (!dst || !src) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: null engine");
+  if (dst == src) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: dst is src (remap into a new engine)");
+  if (n_map != dst->n_streams) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: n_map %u != the destination's %u streams", n_map, dst->n_streams);
+  if (dst->precision != src->precision) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: engines differ in precision (%d, %d)", dst->precision, src->precision);
+  if (dst->device != src->device) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: engines are on devices %d and %d", dst->device, src->device);
+  if (dst->demodulated) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: the destination has demodulated already (remap into a fresh engine)");
+  // One geometry for both engines, whatever the map (an all -1 map included): the gather reads src's state with dst's layout,
+  // and dst takes over src's decimator phase and ring grid.  Every field but the per-stream tone pair / pre-filter bandwidth.
+  if (!shared_fields_equal(dst->cfg0, src->cfg0) || dst->P.d != src->P.d || dst->P.amp_cap != src->P.amp_cap || dst->P.wide != src->P.wide ||
+      dst->P.frac != src->P.frac || dst->P.n_bits != src->P.n_bits || dst->P.ring_cap != src->P.ring_cap)
+    return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: the engines' configurations differ beyond mark/space/preFilterBandwidth "
+                "(sampleRate, baudRate, framing, patterns, syncThreshold, agcEnabled must be equal)");
+  uint32_t n_fresh = 0;
+  int64_t frame_row = -1;   // a continued stream's source row: its free-running I/Q frame is the one dst's continued streams share
+  for (uint32_t i = 0; i < n_map; i++) {
+    if (map[i] < 0) { n_fresh++; continue; }
+    if (map[i] >= (int64_t)src->n_streams)
+      return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: map[%u] = %lld, the source has %u streams", i, (long long)map[i], src->n_streams);
+    if (!config_equal(stream_config(dst, i), stream_config(src, (size_t)map[i])))
+      return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: the config of stream %u differs from that of source stream %lld", i, (long long)map[i]);
+    if (frame_row < 0) frame_row = map[i];
+  }
+  HIP_TRY(hipSetDevice(dst->device));
+  HIP_TRY(hipDeviceSynchronize());
+  {   // a source that has reported (or now holds) a hand-off fault: its streams stopped mid-call.  Read only: src is not written.
+    uint32_t w = src->handoff_fault;
+    if (w == 0u && src->S.blk_stat) HIP_TRY(hipMemcpy(&w, src->S.blk_stat + 2, sizeof(w), hipMemcpyDeviceToHost));
+    if (w != 0u)
+      return fail(FSKHIP_E_HANDOFF, "fskhip_remap_streams: the source's multi-wave kernel ran into its hand-off bound (fault word %u): its streams cannot be continued", w);
+  }
+
+  // Lock step (one decimator phase, one ring grid for every stream) is what the whole-tile kernels need.  A continued stream
+  // brings it along; a new one joins the grid -- unless the source streams are mid decimator-pair (a new one is not), the ring
+  // capacity is fractional, or the source has left lock step already: then new streams start at the create-time positions and
+  // the destination runs out of lock step, as after fskhip_reset of one stream mid-pair.
+  bool uniform = src->ds_uniform;
+  uint32_t parity = src->ds_parity;
+  bool gen_odd = src->gen_odd;
+  if (n_fresh == n_map) { parity = 0; gen_odd = false; }                 // only new streams: every decimator starts afresh
+  else if (n_fresh > 0 && (parity != 0 || src->P.frac)) uniform = false;
+  RemapArgs A{};
+  A.n_dst = dst->n_streams; A.n_src = src->n_streams;
+  A.d = dst->P.d; A.amp_cap = dst->P.amp_cap; A.wide = dst->P.wide; A.frac = dst->P.frac;
+  A.matched_zero = dst->matched_zero;
+  A.grid_src = (uniform && !src->P.frac) ? 1u : 0u;
+  // (fp32, one shared configuration in dst: new streams join the frame of a CONTINUED stream -- its config is dst's, unlike that of
+  // an arbitrary source row of a per-stream source, whose NCO increment and therefore frame phase may be another)
+  A.frame_src = (dst->precision == FSKHIP_PRECISION_F32 && dst->P.uni_cfg && frame_row >= 0) ? 1u : 0u;
+  A.frame_row = frame_row >= 0 ? (uint32_t)frame_row : 0u;
+  int64_t *d_map = nullptr;
+  HIP_TRY(hipMalloc((void **)&d_map, sizeof(int64_t) * n_map));
+  hipError_t err = hipMemcpy(d_map, map, sizeof(int64_t) * n_map, hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = launch_remap(dst->precision, A, d_map, dst->S, src->S, nullptr);
+  if (err == hipSuccess) err = hipDeviceSynchronize();
+  (void)hipFree(d_map);
+  if (err != hipSuccess) return fail(FSKHIP_E_HIP, "fskhip_remap_streams: %s", hipGetErrorString(err));
+
+  // host side: the engine's clocks and, per stream, the baselines its status counters are taken against (fsk.ts:131)
+  dst->calls = src->calls;
+  dst->total_samples = src->total_samples;
+  for (uint32_t i = 0; i < n_map; i++) {
+    dst->base_calls[i] = map[i] >= 0 ? src->base_calls[(size_t)map[i]] : src->calls;
+    dst->base_samples[i] = map[i] >= 0 ? src->base_samples[(size_t)map[i]] : src->total_samples;
+  }
+  dst->pushes = src->pushes;
+  dst->ds_parity = parity;
+  dst->ds_uniform = uniform;
+  dst->gen_odd = gen_odd;
+  dst->P.quality = src->P.quality;   // the signal-quality estimates belong to the streams: they go on accumulating where they did
   return FSKHIP_OK;
 }
 

@@ -173,6 +173,16 @@ struct ModParams {
                           // 0 (fp32 engines): the device library's sin(), ~1.8x faster, may differ by one f32 ulp on ~1e-9 of samples
 };
 
+// fskhip_remap_streams (fsk_remap.hip): what the gather needs besides the two engines' DemodStates and the map
+struct RemapArgs {
+  uint32_t n_dst, n_src;
+  uint32_t d, amp_cap, wide, frac;  // the engines' common geometry (equal configs)
+  uint32_t matched_zero;            // `matched` for an all-zero bit history (what configure() leaves)
+  uint32_t grid_src;                // 1: a new stream's ring positions are the source's (stream 0's: every stream's, in lock step)
+  uint32_t frame_src;               // 1 (fp32, one shared configuration): a new stream joins the engine's free-running I/Q frame
+  uint32_t frame_row;               // ... that of this source row (a continued stream's: dst's config, dst's frame)
+};
+
 // FSKProcessor + ChunkedModulator per stream (fsk-processor.ts, chunked-modulator.ts), device resident.
 // The pending signal is kept as the modulator's generator state (payload + phase + position), not as samples:
 // a slice of n samples is produced on demand and is bit-identical to the same slice of modulateData()'s output

@@ -115,11 +115,13 @@ class FSKEngine:
             if len(configs) != n_streams:
                 raise ValueError("need one config per stream")
             made = [make_config(c) for c in configs]
+            self._configs, self._config_arg = [dict(c or {}) for c in configs], None
             arr = (Config * n_streams)(*[m[0] for m in made])
             self.config = made[0][1]
             n_cfgs = n_streams
         else:
             c, self.config = make_config(configs)
+            self._configs, self._config_arg = None, dict(configs or {})
             arr = (Config * 1)(c)
             n_cfgs = 1
         h = C.c_void_p()
@@ -151,6 +153,34 @@ class FSKEngine:
     def carry_over_from(self, old):
         """what FSKCore.configure() leaves in place on a configured instance: silence threshold, debug counters"""
         _lib.check(self._L.fskhip_carry_over(self._h, old._h))
+
+    def remap_from(self, src, stream_map):
+        """fskhip_remap_streams: stream i of this (new, not yet demodulated) engine continues stream stream_map[i] of `src`
+        as if that FSKCore had been moved, or starts afresh where stream_map[i] is -1.  `src` is left as it is."""
+        m = np.ascontiguousarray(stream_map, dtype=np.int64).reshape(-1)
+        _lib.check(self._L.fskhip_remap_streams(self._h, src._h, m.ctypes.data, len(m)))
+
+    def remapped(self, stream_map, configs=None, options=None):
+        """A new engine of len(stream_map) streams whose stream i continues stream stream_map[i] of this one (-1: a new
+        FSKCore).  Its configs are taken from this engine by the map unless given; a -1 slot needs an explicit config when this
+        engine has per-stream configs.  `options` are the new engine's own (fskhip_set_option)."""
+        m = [int(v) for v in np.asarray(stream_map, dtype=np.int64).reshape(-1)]
+        if configs is None:
+            if self._configs is None:
+                configs = self._config_arg
+            else:
+                if any(v < 0 for v in m):
+                    raise ValueError("a -1 slot needs an explicit config: this engine has per-stream configs")
+                if any(v >= self.n_streams for v in m):
+                    raise ValueError("stream map entry out of range (%d streams)" % self.n_streams)
+                configs = [self._configs[v] for v in m]
+        eng = FSKEngine(len(m), configs, device=self.device, precision=self.precision, options=options)
+        try:
+            eng.remap_from(self, m)
+        except Exception:
+            eng.close()
+            raise
+        return eng
 
     def __del__(self):
         try:
