@@ -481,7 +481,7 @@ def test_fp32_vs_fp64_engines_deviation_rate_full_size():
 def test_short_odd_calls_do_not_take_the_engine_off_the_block_kernel():
     """VERDICT r03 #6.  A 6-sample call leaves the amplitude ring three pushes into a quad, a 17-sample call then leaves the
     /2 decimator mid-pair and the next buffer on a 4-byte boundary.  Round 3 then kept the engine on round 2's kernels (or
-    the per-sample kernel) for the rest of its life; now the head of the next call realigns both (fsk_api.hip) and BASELINE
+    the per-sample kernel) for the rest of its life; now the head of the next call realigns both (fsk_dispatch.hip) and BASELINE
     config #3's full-length call runs on the block kernel: its bytes are those of one call over the whole stream and of
     the oracle."""
     import webaudio_modem_amd as wm
@@ -515,7 +515,7 @@ def test_short_odd_calls_do_not_take_the_engine_off_the_block_kernel():
 @pytest.mark.parametrize("S", [64, 200])
 def test_odd_call_lengths_and_unaligned_buffers_stay_on_the_fp32_arithmetic(S):
     """Calls of odd lengths leave a decimator pair open and the next call's buffer on a 4-byte boundary: the head / tile /
-    tail dispatch (fsk_api.hip) must give exactly the bytes of one call, and of the oracle, whatever the cut."""
+    tail dispatch (fsk_dispatch.hip) must give exactly the bytes of one call, and of the oracle, whatever the cut."""
     import webaudio_modem_amd as wm
     from oracle import pyoracle as po
     N = 20011

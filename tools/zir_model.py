@@ -20,7 +20,7 @@ zero-started direct instance produces the 16 + 2 decimated samples after the res
 of the size of the wanted signal itself.  main() shows both on a noisy signal and on such a ringing tail.
 
 This script checks, in float64 and in float32, that the scheme reproduces a sample-serial implementation with real
-resets, and prints the constants the host derives (fsk_api.hip).  It is a design aid, not part of the product or tests.
+resets, and prints the constants the host derives (fsk_create.hip, derive_params).  It is a design aid, not part of the product or tests.
 """
 import math
 import numpy as np

@@ -58,6 +58,7 @@
 #include "fsk_pipe_dev.h"
 #include "fsk_blk_dev.h"
 #include "fsk_blk_sched.h"
+#include "fsk_launch.h"
 
 namespace fsk {
 

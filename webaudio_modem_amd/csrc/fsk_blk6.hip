@@ -54,6 +54,7 @@
 #include "fsk_dev.h"
 #include "fsk_pipe_dev.h"
 #include "fsk_blk_dev.h"
+#include "fsk_launch.h"
 
 namespace fsk {
 

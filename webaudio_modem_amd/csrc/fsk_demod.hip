@@ -48,6 +48,7 @@
 #include "fsk_dev.h"
 #include "fsk_f64math.h"
 #include "fsk_wait.h"
+#include "fsk_launch.h"
 
 #ifndef FSK_F32_WAVES_PER_SIMD
 #define FSK_F32_WAVES_PER_SIMD 2

@@ -1,0 +1,339 @@
+// fsk_dispatch.hip -- C ABI of libfskhip.so (include/fskhip.h): fskhip_demodulate_device / _host -- which kernels a call
+// gets, their launches, and the host-side bookkeeping the choice depends on.
+#include "fsk_engine.h"
+#include "fsk_launch.h"
+
+using namespace fsk;
+
+// everything fskhip_demodulate_device's choice of launches depends on besides its arguments
+uint32_t fsk::engine_launch_key(const fskhip_engine *e) {
+  return (e->ds_uniform ? 1u : 0u) | (e->ds_parity << 1) | (e->force_generic ? 4u : 0u) | (e->timing.on ? 8u : 0u) |
+         (e->use_split ? 32u : 0u) | (e->gen_odd ? 64u : 0u) | (e->P.quality ? 256u : 0u) |
+         (e->S.trace_stream != 0xFFFFFFFFu ? 16u : 0u) | (e->use_blk ? 512u : 0u) | ((uint32_t)(e->pushes & 3u) << 10) |
+         ((e->blk.medium == 3u ? e->blk.med_now : e->blk.medium != 0u) ? 4096u : 0u) | (e->six.use << 13);
+}
+// "blk_resets" = auto: tiles, and tiles the block path with resets took or would be given, of a sample of the groups since the
+// last look (whatever the last completed copy brought; nothing new = the choice stands).  It wins from about one tile in six on.
+void fsk::engine_refresh_kernel_choice(fskhip_engine *e) {
+  if (e->blk.medium != 3u || !e->blk.h_stat) return;
+  const unsigned long long hs = *e->blk.h_stat;
+  const uint32_t tiles = (uint32_t)hs, rare = (uint32_t)(hs >> 32);
+  const uint32_t dt = tiles - e->blk.stat_tiles, dr = rare - e->blk.stat_rare;
+  if (dt == 0u) return;
+  // (with hysteresis: the two kernels count slightly different things -- the plain one cannot tell whether a tile it sends
+  // down its per-sample path because of a lane's own span also holds a sync candidate)
+  e->blk.med_now = (double)dr >= (e->blk.med_now ? 0.10 : 0.20) * (double)dt;
+  e->blk.stat_tiles = tiles; e->blk.stat_rare = rare;
+}
+// ... and the copy that brings the totals back, behind a launch of the four- or seven-wave kernel: behind every long call, behind
+// every eighth of a run of short ones (the copy is ~3 us of the stream's time, 7 % of a 128-sample call of 65 536 streams)
+static hipError_t engine_fetch_blk_stat(fskhip_engine *e, size_t n_fast, hipStream_t st) {
+  if (e->blk.medium != 3u || !e->blk.h_stat || !e->S.blk_stat) return hipSuccess;
+  bool fetch = n_fast >= 4096 || (++e->blk.stat_skip & 7u) == 0u;
+  if (!fetch) {                                      // (a call being captured into a graph is replayed many times: it fetches)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    fetch = hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+  }
+  return fetch ? hipMemcpyAsync((void *)e->blk.h_stat, e->S.blk_stat, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+// the host-side counters after a call of n samples has been issued (calls = 1: a demodulateData() call of its own) or replayed
+static void note_call(fskhip_engine *e, size_t n, uint32_t calls) {
+  e->demodulated = true;
+  e->calls += calls;
+  e->total_samples += n;
+  e->pushes += (e->ds_parity + n) >> 1;     // (the amplitude ring's position moves with a replayed call too)
+  e->ds_parity = (e->ds_parity + (uint32_t)(n & 1)) & 1u;
+}
+void fsk::engine_note_replayed_call(fskhip_engine *e, size_t n) { note_call(e, n, 1u); }
+
+// The hand-off fault word (csrc/fsk_wait.h): a wave of a multi-wave kernel got nowhere in FSK_SPIN_CAP polls of one wait and ended
+// its launch early.  Sticky: the streams of that workgroup are mid-call, the engine is to be destroyed.  `blocking`: read the word
+// from the device (the caller has synchronised); otherwise whatever the last completed statistics copy brought (costs nothing).
+int fsk::handoff_check(fskhip_engine *e, bool blocking) {
+  if (e->handoff_fault == 0u) {
+    uint32_t w = 0;
+    if (blocking) {
+      if (e->S.blk_stat && hipMemcpy(&w, e->S.blk_stat + 2, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) w = 0;
+    } else if (e->blk.h_stat) {
+      w = (uint32_t)e->blk.h_stat[1];
+    }
+    e->handoff_fault = w;
+  }
+  if (e->handoff_fault != 0u)
+    return fail(FSKHIP_E_HANDOFF, "a hand-off wait of a multi-wave kernel ran into its bound (fault word %u, last kernel %s): destroy the engine",
+                e->handoff_fault, e->last_kernel);
+  return FSKHIP_OK;
+}
+
+// ---- one demodulate call: which kernels (plan_launches), then head -> whole tiles -> tail (issue_launches) ----------------
+namespace {
+enum TileKernel { K_GENERIC, K_SAMPLES, K_SEVEN_WAVE, K_FOUR_WAVE, K_TWO_WAVE, K_ONE_WAVE };
+struct LaunchPlan {
+  TileKernel kernel = K_GENERIC;   // K_GENERIC: all n samples on fsk_demod.hip's kernel; K_SAMPLES: all of them sample by sample (head = n)
+  size_t head = 0, n_fast = 0;     // single samples in front of the whole tiles; the whole tiles' samples (the tail is what is left)
+  uint32_t med = 0, y_slots = 0;   // four waves: "blk_resets" as this call takes it; seven waves: depth of the y ring
+  bool split2 = false;             // generic fp64 kernel on two waves per group
+};
+
+// Reads the engine and the call's arguments.  (Its one write: engine_refresh_kernel_choice, once the four-wave family is chosen.)
+LaunchPlan plan_launches(fskhip_engine *e, const float *d_samples, size_t n, size_t pitch) {
+  LaunchPlan pl;
+  // Lock-step fp32 batches with narrow integer-capacity rings never leave fsk_pipe.hip's arithmetic: a head of
+  // single samples up to an even decimator parity and a 16-byte boundary, whole 16-sample tiles, a tail of single
+  // samples -- so cutting a stream into calls of any lengths changes nothing, bit for bit.  Everything else (fp64,
+  // wide / fractional rings, streams out of lock step) is the generic kernel's.
+  if (!(n > 0 && !e->force_generic && !e->gen_odd && demod_fast_applicable(e->precision, e->ds_uniform, e->P, e->S, d_samples, pitch))) {
+    pl.split2 = e->precision == FSKHIP_PRECISION_F64 && e->ds_uniform && !e->P.wide && !e->P.frac && e->S.trace_stream == 0xFFFFFFFFu &&
+                !e->P.quality && demod_split2_lds_bytes(e->P) <= 160 * 1024 &&
+                (e->exact_split == 1u || (e->exact_split == 2u && e->cus > 0 && e->n_blocks <= 4u * (uint32_t)e->cus && n >= 64));
+    return pl;
+  }
+  const uint32_t p0 = e->ds_parity;
+  size_t head = 0, n_fast = 0;
+  bool tiles = (pitch % 4 == 0) && (uint64_t)pitch * 4u * 64u < 0x7FFFFFF0ull && (reinterpret_cast<uintptr_t>(d_samples) & 3u) == 0;
+  if (tiles) {
+    // The head: single samples (demod_tail_kernel) until the /2 decimator is at a pair boundary AND the amplitude
+    // ring's write position is a multiple of four -- what the block kernel's quad stores need (fsk_dev.h).  At most
+    // seven samples.  The tile loads that follow are 16 bytes per lane from dword-aligned addresses: a buffer that is
+    // 16-byte aligned after the head is the common case and the fastest, but nothing depends on it (VERDICT r03 #6:
+    // round 3 demanded both, so one odd-length call left an aligned device buffer on the per-sample kernel until
+    // the parity flipped back, and a call that left the ring off its quad grid kept the engine on round 2's
+    // kernels for good).
+    head = p0;                                                  // closes the open pair
+    const uint64_t at = e->pushes + ((p0 + head) >> 1);       // the ring's position after it
+    if (e->use_blk && demod_blk_applicable(e->P)) head += 2u * (size_t)((4u - (uint32_t)(at & 3u)) & 3u);
+  }
+  if (e->S.trace_stream != 0xFFFFFFFFu || e->P.quality) tiles = false;   // diagnostics (traces, quality estimates) run on the sample-granular kernel
+  if (tiles && head < n) n_fast = (n - head) & ~(size_t)15;
+  if (!n_fast) head = n;   // all of it sample by sample
+  pl.head = head; pl.n_fast = n_fast; pl.kernel = K_SAMPLES;
+  if (!n_fast) return pl;
+  const size_t blk_lds = demod_blk_lds_bytes(e->P);
+  // the block kernel stores amplitudes a quad at a time: the ring's write position at its first sample must be a
+  // multiple of four (it is unless earlier calls had odd lengths: those calls then stay with the per-sample kernels)
+  const bool quad_aligned = ((e->pushes + ((p0 + head) >> 1)) & 3u) == 0u;
+  // Batches beyond one round of resident workgroups run the block kernel persistently, in time slices; a call too
+  // short for two slices would run it in several rounds of one workgroup per group, each paying the four-wave
+  // pipeline's fill and drain, and round 2's kernels are faster there (262 144 streams x 128-sample quanta, the
+  // FSKProcessor loop: 0.195 against 0.247 ms; x 4 096 samples 384 against 370 Gsamples/s:
+  // profiles/r03_short_calls.txt)
+  const bool blk_fits = e->blk.lanes != 64u || !(e->blk.resident && e->n_blocks > e->blk.resident) ||
+                        demod_blk_slices(e->P, e->S, n_fast, e->blk.resident, e->blk.slice_tiles, nullptr) >= 2u;
+  if (e->use_blk && demod_blk_applicable(e->P) && blk_lds <= 160 * 1024 && (quad_aligned || e->split_forced) &&
+      ((blk_fits && n_fast / 16 >= e->blk.min_tiles) || e->split_forced)) {
+    engine_refresh_kernel_choice(e);
+    pl.med = e->blk.medium == 3u ? (e->blk.med_now ? 1u : 0u) : e->blk.medium;
+    // seven waves per group: every workgroup a compute unit to itself (in narrow groups -- <= 32 streams -- the stages that
+    // are not recurrences spread over the idle lanes), a uniform configuration, a call long enough to fill seven stages.
+    // Measured against the four-wave kernel: x 1.56 at 2 048 streams, x 1.48 at 4 096, x 1.42 at 8 192, x 1.13 with whole-wave
+    // groups at 16 384 (profiles/r05_lag.txt).  Idle receiver banks included: its frame wave takes own-span tiles on the
+    // block path with resets too.
+    const uint32_t six_blocks = (e->n_streams + e->blk.lanes - 1u) / e->blk.lanes;
+    const bool six = e->six.use != 0u && quad_aligned && demod_blk6_applicable(e->P) && n_fast <= demod_blk6_max_samples() &&
+                     (e->six.use == 1u || (e->cus > 0 && six_blocks <= (uint32_t)e->cus && n_fast / 16 >= e->six.min_tiles));
+    pl.kernel = six ? K_SEVEN_WAVE : K_FOUR_WAVE;
+    if (six) pl.y_slots = e->six.y_slots ? e->six.y_slots : demod_blk6_y_slots(e->P);
+    return pl;
+  }
+  const size_t wgs_per_cu = (e->n_blocks + e->split_cus - 1) / e->split_cus;
+  const size_t pipe_lds = demod_pipe_lds_bytes(e->P);
+  const bool two_wave = e->use_split && pipe_lds <= 160 * 1024 && (wgs_per_cu * pipe_lds <= 160 * 1024 || e->split_forced);
+  pl.kernel = two_wave ? K_TWO_WAVE : K_ONE_WAVE;
+  return pl;
+}
+
+// what fskhip_last_kernel reports for a call: its whole-tile kernel, or the per-sample / generic kernel of a call without tiles
+const char *kernel_name(const fskhip_engine *e, const LaunchPlan &pl, bool wb) {
+  const bool uni = e->P.uni_cfg != 0;
+  switch (pl.kernel) {
+    case K_SAMPLES: return "fsk::demod_tail_kernel";
+    case K_SEVEN_WAVE: {
+      static const char *const names6[16] = {
+          "fsk::demod_blk6_kernel<false, 64>", "fsk::demod_blk6_kernel<false, 32>", "fsk::demod_blk6_kernel<false, 16>", "fsk::demod_blk6_kernel<false, 8>",
+          "fsk::demod_blk6_kernel<true, 64>", "fsk::demod_blk6_kernel<true, 32>", "fsk::demod_blk6_kernel<true, 16>", "fsk::demod_blk6_kernel<true, 8>",
+          // (round 6: per-stream tone pairs -- <write-back, streams per workgroup, uniform = false>)
+          "fsk::demod_blk6_kernel<false, 64, false>", "fsk::demod_blk6_kernel<false, 32, false>", "fsk::demod_blk6_kernel<false, 16, false>", "fsk::demod_blk6_kernel<false, 8, false>",
+          "fsk::demod_blk6_kernel<true, 64, false>", "fsk::demod_blk6_kernel<true, 32, false>", "fsk::demod_blk6_kernel<true, 16, false>", "fsk::demod_blk6_kernel<true, 8, false>"};
+      return names6[(uni ? 0 : 8) + (wb ? 4 : 0) + (e->blk.lanes == 64u ? 0 : e->blk.lanes == 32u ? 1 : e->blk.lanes == 16u ? 2 : 3)];
+    }
+    case K_FOUR_WAVE: {
+      static const char *const names[16] = {
+          "fsk::demod_blk_kernel<false, false, false>", "fsk::demod_blk_kernel<false, false, true>",
+          "fsk::demod_blk_kernel<false, true, false>", "fsk::demod_blk_kernel<false, true, true>",
+          "fsk::demod_blk_kernel<true, false, false>", "fsk::demod_blk_kernel<true, false, true>",
+          "fsk::demod_blk_kernel<true, true, false>", "fsk::demod_blk_kernel<true, true, true>",
+          "fsk::demod_blk_kernel_r<false, false>", "fsk::demod_blk_kernel_r<false, true>",
+          "fsk::demod_blk_kernel_r<true, false>", "fsk::demod_blk_kernel_r<true, true>",
+          "fsk::demod_blk_kernel_rp<false, false>", "fsk::demod_blk_kernel_rp<false, true>",
+          "fsk::demod_blk_kernel_rp<true, false>", "fsk::demod_blk_kernel_rp<true, true>"};
+      return pl.med ? names[(uni ? 8 : 12) + (wb ? 2 : 0) + (e->last_sliced ? 1 : 0)]   // <writeback, time-sliced>: _r uniform, _rp per-stream tone pairs
+                    : names[(wb ? 4 : 0) + (uni ? 2 : 0) + (e->last_sliced ? 1 : 0)];   // <writeback, uniform, time-sliced>
+    }
+    case K_TWO_WAVE: case K_ONE_WAVE: {
+      static const char *const names2[8] = {   // <writeback, uniform>
+          "fsk::demod_pipe_kernel<false, false>", "fsk::demod_pipe_kernel<false, true>", "fsk::demod_pipe_kernel<true, false>", "fsk::demod_pipe_kernel<true, true>",
+          "fsk::demod_fused_kernel<false, false>", "fsk::demod_fused_kernel<false, true>", "fsk::demod_fused_kernel<true, false>", "fsk::demod_fused_kernel<true, true>"};
+      return names2[(pl.kernel == K_ONE_WAVE ? 4 : 0) + (wb ? 2 : 0) + (uni ? 1 : 0)];
+    }
+    case K_GENERIC: break;   // (below)
+  }
+  return pl.split2 ? "fsk::demod_kernel<double, ..., two waves>" : e->precision == FSKHIP_PRECISION_F64 ? "fsk::demod_kernel<double, ...>" : "fsk::demod_kernel<float, ...>";
+}
+
+int issue_launches(fskhip_engine *e, const LaunchPlan &pl, bool wb, bool append_first, float *d_samples, size_t n, size_t pitch,
+                   uint8_t *d_out, size_t out_pitch, uint32_t *d_out_counts, uint32_t *d_eod_counts, hipStream_t st) {
+  if (pl.kernel == K_GENERIC) {
+    e->P.nco_anchor = (uint32_t)(e->total_samples & 31u);   // (fp64: where the NCO phasor is re-evaluated; fsk_demod.hip, mix_lp)
+    HIP_TRY(launch_demod(e->precision, e->ds_uniform, wb, append_first, e->P, e->S, d_samples, n, pitch, d_out, out_pitch,
+                         d_out_counts, d_eod_counts, st, pl.split2));
+    // the generic kernel keeps an open decimator pair's partial sums in the reference's own frame: stay with it
+    // until the pair is closed
+    if (n > 0) e->gen_odd = e->precision == FSKHIP_PRECISION_F32 && ((e->ds_parity + (uint32_t)(n & 1)) & 1u) != 0;
+    return FSKHIP_OK;
+  }
+  const size_t head = pl.head, n_fast = pl.n_fast;
+  bool app = append_first;
+  if (head) {
+    HIP_TRY(launch_demod_tail(wb, app, (int)e->ds_parity, e->P, e->S, d_samples, head, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st));
+    app = true;
+  }
+  if (!n_fast) return FSKHIP_OK;
+  switch (pl.kernel) {
+    case K_SEVEN_WAVE:
+      HIP_TRY(launch_demod_blk6(wb, app, e->P, e->S, d_samples + head, n_fast, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st,
+                                e->blk.lanes, pl.y_slots, e->six.rolemap));
+      e->last_sliced = false;
+      HIP_TRY(engine_fetch_blk_stat(e, n_fast, st));
+      break;
+    case K_FOUR_WAVE:
+      HIP_TRY(launch_demod_blk(wb, app, e->P, e->S, d_samples + head, n_fast, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st,
+                               e->blk.resident, e->blk.slice_tiles, e->blk.y_slots, e->blk.lanes, pl.med, &e->last_sliced));
+      HIP_TRY(engine_fetch_blk_stat(e, n_fast, st));
+      break;
+    case K_TWO_WAVE:
+      HIP_TRY(launch_demod_pipe(wb, app, e->P, e->S, d_samples + head, n_fast, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st));
+      break;
+    default:
+      HIP_TRY(launch_demod_fused(wb, app, e->P, e->S, d_samples + head, n_fast, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st));
+  }
+  const size_t done = head + n_fast;
+  if (done < n)
+    HIP_TRY(launch_demod_tail(wb, true, 0, e->P, e->S, d_samples + done, n - done, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st));
+  return FSKHIP_OK;
+}
+
+// append_first: this launch sequence continues a call that has produced output already (a time slab of
+// fskhip_demodulate_host's pipeline); count_call: it is (the first part of) a demodulateData() call of its own
+int demod_device_impl(fskhip_engine *e, float *d_samples, size_t n, size_t pitch, uint8_t *d_out, size_t out_pitch, uint32_t *d_out_counts,
+                      uint32_t *d_eod_counts, uint32_t flags, void *hip_stream, bool append_first, bool count_call) {
+  if (!e) return fail(FSKHIP_E_NOT_CONFIGURED, "FSK demodulator not configured");
+  if (!d_out_counts || (n > 0 && !d_samples) || (out_pitch > 0 && !d_out))
+    return fail(FSKHIP_E_INVALID, "fskhip_demodulate_device: null buffer");
+  if (pitch < n) return fail(FSKHIP_E_INVALID, "pitch %zu < n_per_stream %zu", pitch, n);
+  if (!e->demod_ok) return fail(FSKHIP_E_UNSUPPORTED, "demodulator unsupported for this configuration: %s", e->demod_why.c_str());
+  if (const int hrc = handoff_check(e, false)) return hrc;
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const bool wb = (flags & FSKHIP_DEMOD_WRITEBACK_AGC) != 0;
+  if (const int rc = timing_open(e, st)) return rc;
+  e->last_kernel = "";
+  const LaunchPlan pl = plan_launches(e, d_samples, n, pitch);
+  if (const int rc = issue_launches(e, pl, wb, append_first, d_samples, n, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st)) return rc;
+  e->last_kernel = kernel_name(e, pl, wb);
+  if (const int rc = timing_close(e, st)) return rc;
+  note_call(e, n, count_call ? 1u : 0u);
+  return FSKHIP_OK;
+}
+}  // namespace
+
+extern "C" {
+int fskhip_demodulate_device(fskhip_engine *e, float *d_samples, size_t n, size_t pitch, uint8_t *d_out, size_t out_pitch,
+                             uint32_t *d_out_counts, uint32_t *d_eod_counts, uint32_t flags, void *hip_stream) {
+  return demod_device_impl(e, d_samples, n, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, flags, hip_stream, false, true);
+}
+// Host buffers in, bytes out.  A call longer than one time slab is a two-buffer pipeline over TIME: slab j+1 crosses PCIe
+// on the copy stream while slab j is demodulated on the compute stream.  Cutting along time needs no sub-batch launches,
+// and the engine gives the same bytes for any cut (the reference is a streaming state machine, fsk.ts:190-222).  The
+// copies only overlap if `samples` is page-locked (fskhip_host_alloc, or any pinned buffer of the caller); with pageable
+// memory the runtime stages each copy itself and the pipeline degrades gracefully to what one big copy costs.
+int fskhip_demodulate_host(fskhip_engine *e, float *samples, size_t n, size_t pitch, uint8_t *out, size_t out_pitch,
+                           uint32_t *out_counts, uint32_t *eod_counts, uint32_t flags) {
+  if (!e) return fail(FSKHIP_E_NOT_CONFIGURED, "FSK demodulator not configured");
+  if (!out_counts || (n > 0 && !samples) || (out_pitch > 0 && !out)) return fail(FSKHIP_E_INVALID, "null buffer");
+  if (pitch < n) return fail(FSKHIP_E_INVALID, "pitch %zu < n_per_stream %zu", pitch, n);
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t S = e->n_streams;
+  const bool wb = (flags & FSKHIP_DEMOD_WRITEBACK_AGC) != 0;
+  // slab length: ~96 MB of samples per slab, a multiple of 16 (whole tiles, even decimator parity), at least 4096
+  size_t slab = ((size_t)96 << 20) / (S * sizeof(float));
+  slab = slab < 4096 ? 4096 : slab;
+  slab &= ~(size_t)15;
+  if (e->host_slab != (size_t)-1) slab = e->host_slab & ~(size_t)15;   // fskhip_set_option("host_slab"): tests / measurements
+  const bool piped = slab > 0 && n > slab + slab / 2;
+  const size_t len0 = piped ? slab + slab / 2 : n;    // (the last slab of a pipelined call takes the remainder, < 1.5 slabs)
+  // device copies keep a row pitch that is a multiple of 4 floats so the 16-B tile loads apply.  A stream whose /2
+  // decimator is mid-pair (an earlier call had an odd length) is staged THREE floats into its row: the one sample that
+  // closes the pair then also reaches the next 16-byte boundary, and the rest of the call runs on whole tiles -- staged
+  // at the row start it would need an odd head for the parity and a multiple of four for the alignment, i.e. every
+  // later even-length call would run sample by sample (fsk_api.hip's silent performance cliff).
+  const size_t dpitch = ((len0 + 3 + 3) & ~(size_t)3) ? ((len0 + 3 + 3) & ~(size_t)3) : 4;
+  auto shift = [&]() -> size_t { return (e->precision == FSKHIP_PRECISION_F32 && e->ds_uniform && (e->ds_parity & 1u)) ? 3 : 0; };
+  int rc;
+  if ((rc = ensure(e->host.d_samples, e->host.d_samples_cap, dpitch * S)) != FSKHIP_OK) return rc;
+  if ((rc = ensure(e->host.d_out, e->host.d_out_cap, (out_pitch ? out_pitch : 1) * S)) != FSKHIP_OK) return rc;
+  if (!piped) {
+    float *stg = e->host.d_samples + shift();
+    if (n > 0)
+      HIP_TRY(hipMemcpy2DAsync(stg, dpitch * sizeof(float), samples, pitch * sizeof(float), n * sizeof(float), S,
+                               hipMemcpyHostToDevice, e->host.stream));
+    rc = fskhip_demodulate_device(e, stg, n, dpitch, e->host.d_out, out_pitch, e->host.d_counts, e->host.d_eod, flags, e->host.stream);
+    if (rc != FSKHIP_OK) return rc;
+    if (wb && n > 0)
+      HIP_TRY(hipMemcpy2DAsync(samples, pitch * sizeof(float), stg, dpitch * sizeof(float), n * sizeof(float), S,
+                               hipMemcpyDeviceToHost, e->host.stream));
+  } else {
+    if ((rc = ensure(e->host.d_samples2, e->host.d_samples2_cap, dpitch * S)) != FSKHIP_OK) return rc;
+    if (!e->host.copy_stream) {
+      HIP_TRY(hipStreamCreateWithFlags(&e->host.copy_stream, hipStreamNonBlocking));
+      for (int i = 0; i < 2; i++) {
+        HIP_TRY(hipEventCreateWithFlags(&e->host.ev_copied[i], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&e->host.ev_used_up[i], hipEventDisableTiming));
+      }
+    }
+    // on a failure inside the pipeline, let what is in flight on both streams finish before the caller's buffers go away
+#define PIPE_TRY(expr) HIP_TRY_AS(expr, #expr, false, ((void)hipStreamSynchronize(e->host.copy_stream), (void)hipStreamSynchronize(e->host.stream)))
+    float *buf[2] = {e->host.d_samples, e->host.d_samples2};
+    size_t off = 0;
+    for (size_t j = 0; off < n; j++) {
+      // the last slab takes the remainder (up to 1.5 slabs would not be worth another round trip)
+      const size_t len = (n - off > slab + slab / 2) ? slab : n - off;
+      if (len + 3 > dpitch) return fail(FSKHIP_E_INVALID, "internal: slab %zu exceeds staging pitch %zu", len, dpitch);
+      const int b = (int)(j & 1);
+      float *stg = buf[b] + shift();               // (the parity at this slab's start: slabs are multiples of 16 samples)
+      if (j >= 2) PIPE_TRY(hipStreamWaitEvent(e->host.copy_stream, e->host.ev_used_up[b], 0));   // its previous user has finished
+      PIPE_TRY(hipMemcpy2DAsync(stg, dpitch * sizeof(float), samples + off, pitch * sizeof(float), len * sizeof(float), S,
+                               hipMemcpyHostToDevice, e->host.copy_stream));
+      PIPE_TRY(hipEventRecord(e->host.ev_copied[b], e->host.copy_stream));
+      PIPE_TRY(hipStreamWaitEvent(e->host.stream, e->host.ev_copied[b], 0));
+      rc = demod_device_impl(e, stg, len, dpitch, e->host.d_out, out_pitch, e->host.d_counts, e->host.d_eod, flags, e->host.stream,
+                             /*append_first=*/j > 0, /*count_call=*/j == 0);
+      if (rc != FSKHIP_OK) { (void)hipStreamSynchronize(e->host.copy_stream); (void)hipStreamSynchronize(e->host.stream); return rc; }
+      if (wb)
+        PIPE_TRY(hipMemcpy2DAsync(samples + off, pitch * sizeof(float), stg, dpitch * sizeof(float), len * sizeof(float), S,
+                                 hipMemcpyDeviceToHost, e->host.stream));
+      PIPE_TRY(hipEventRecord(e->host.ev_used_up[b], e->host.stream));
+      off += len;
+    }
+#undef PIPE_TRY
+  }
+  if (out_pitch > 0) HIP_TRY(hipMemcpyAsync(out, e->host.d_out, out_pitch * S, hipMemcpyDeviceToHost, e->host.stream));
+  HIP_TRY(hipMemcpyAsync(out_counts, e->host.d_counts, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, e->host.stream));
+  if (eod_counts) HIP_TRY(hipMemcpyAsync(eod_counts, e->host.d_eod, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, e->host.stream));
+  HIP_TRY(hipStreamSynchronize(e->host.stream));
+  if (e->host.copy_stream) HIP_TRY(hipStreamSynchronize(e->host.copy_stream));
+  if (const int hrc = handoff_check(e, true)) return hrc;
+  for (size_t s = 0; s < S; s++)
+    if (out_counts[s] > out_pitch) return fail(FSKHIP_E_OVERFLOW, "stream %zu produced %u bytes, slab holds %zu", s, out_counts[s], out_pitch);
+  return FSKHIP_OK;
+}
+}  // extern "C"

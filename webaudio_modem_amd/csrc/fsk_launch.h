@@ -1,0 +1,68 @@
+// fsk_launch.h -- the one declaration of every host-callable function a kernel file defines.  Included by the defining
+// .hip file and by its callers (the C-ABI units), so that a signature cannot drift between them.  Not part of the ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "fsk_params.h"
+
+namespace fsk {
+// fsk_demod.hip: the generic kernel (fp64, wide / fractional rings, streams out of lock step)
+hipError_t launch_demod(int precision, bool uniform_ds, bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n, size_t pitch,
+                        uint8_t *out, size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, hipStream_t stream, bool split2 = false);
+bool demod_fast_applicable(int precision, bool uniform_even, const DemodParams &P, const DemodState &S, const float *samples, size_t pitch);
+size_t demod_split2_lds_bytes(const DemodParams &P);
+hipError_t set_demod_split2_lds_limit(size_t lds_bytes);
+hipError_t set_demod_lds_limit(size_t lds_bytes);
+size_t demod_lds_bytes(const DemodParams &P);
+// fsk_pipe.hip: free-running front / ZIR-corrected back kernels
+hipError_t launch_demod_pipe(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n, size_t pitch, uint8_t *out,
+                             size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, hipStream_t stream);
+hipError_t launch_demod_fused(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n, size_t pitch, uint8_t *out,
+                              size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, hipStream_t stream);
+hipError_t launch_demod_tail(bool writeback, bool append, int parity0, const DemodParams &P, const DemodState &S, float *samples, size_t n, size_t pitch, uint8_t *out,
+                             size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, hipStream_t stream);
+size_t demod_pipe_lds_bytes(const DemodParams &P);
+size_t demod_fused_lds_bytes(const DemodParams &P);
+hipError_t set_pipe_lds_limit(size_t pipe_bytes);
+// fsk_blk.hip: four waves per group, block-batched back wave
+size_t demod_blk_lds_bytes(const DemodParams &P);
+size_t demod_blk_lds_bytes(const DemodParams &P, uint32_t y_slots);
+bool demod_blk_applicable(const DemodParams &P);
+hipError_t set_blk_lds_limit(const DemodParams &P);
+hipError_t launch_demod_blk(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n, size_t pitch, uint8_t *out,
+                            size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, hipStream_t stream, uint32_t resident_wgs, uint32_t slice_tiles,
+                            uint32_t y_slots, uint32_t lanes, uint32_t medium, bool *sliced_out);
+uint32_t demod_blk_lanes(uint32_t n_streams, int device);
+void demod_blk_plan(const DemodParams &P, uint32_t groups, int device, uint32_t *y_slots, uint32_t *resident_wgs);
+uint32_t demod_blk_slices(const DemodParams &P, const DemodState &S, size_t n, uint32_t resident_wgs, uint32_t slice_tiles, uint32_t *slice_tiles_out);
+size_t demod_blk_queue_words(uint32_t groups);
+// fsk_blk6.hip: seven waves per group, for batches that leave every workgroup a compute unit of its own
+size_t demod_blk6_lds_bytes(const DemodParams &P, uint32_t y_slots);
+uint32_t demod_blk6_y_slots(const DemodParams &P);
+uint32_t demod_blk6_min_y_slots();
+bool demod_blk6_applicable(const DemodParams &P);
+size_t demod_blk6_max_samples();
+hipError_t set_blk6_lds_limit(const DemodParams &P);
+uint32_t demod_blk6_default_rolemap(uint32_t lanes, bool uniform);
+hipError_t launch_demod_blk6(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n, size_t pitch, uint8_t *out,
+                             size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, hipStream_t stream, uint32_t lanes, uint32_t y_slots, uint32_t rolemap);
+// fsk_mod.hip: modulator, synthetic workloads, and the FSKProcessor quantum's bookkeeping / TX kernels
+hipError_t launch_modulate(const ModParams &M, const double *coef, const uint8_t *payloads, const uint32_t *lens, size_t payload_pitch, float *out, size_t out_pitch,
+                           uint32_t *out_lens, hipStream_t st);
+hipError_t launch_synth(const ModParams &M, const double *coef, float *out, size_t n, size_t pitch, uint32_t payload_len, uint64_t seed, uint32_t lead_max, double amp_lo,
+                        double amp_hi, hipStream_t st);
+hipError_t launch_awgn(float *buf, size_t n, size_t pitch, uint32_t n_streams, double snr_db, uint64_t seed, double *sigma, hipStream_t st);
+hipError_t launch_probe_read(const float *buf, size_t n, size_t pitch, uint32_t n_streams, float *sink, hipStream_t st);
+uint8_t host_synth_payload_byte(uint64_t seed, uint32_t stream, uint32_t frame, uint32_t i);
+void host_synth_stream_params(uint64_t seed, uint32_t stream, uint32_t lead_max, double amp_lo, double amp_hi, uint32_t *lead, double *amp);
+hipError_t launch_processor_io(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out, size_t demod_pitch, const uint32_t *demod_counts,
+                               bool do_rx, float *out, size_t n_out, size_t out_pitch, bool clear_rx_on_complete, hipStream_t st);
+hipError_t launch_processor_tx_start(const ModParams &M, const ProcState &T, const uint8_t *payloads, const uint32_t *lens, size_t payload_pitch, const uint8_t *mask,
+                                     hipStream_t st);
+hipError_t launch_processor_rx_drain(const ProcState &T, uint32_t n_streams, uint8_t *out, size_t out_pitch, uint32_t *counts, hipStream_t st);
+hipError_t launch_processor_reset(const ProcState &T, uint32_t n_streams, int64_t stream, bool rx, bool tx, hipStream_t st);
+// fsk_remap.hip: the state gather of fskhip_remap_streams
+hipError_t launch_remap(int precision, const RemapArgs &A, const int64_t *d_map, const DemodState &D, const DemodState &S, hipStream_t st);
+}  // namespace fsk

@@ -13,6 +13,7 @@
 #include "fsk_fdlibm.h"
 #include "fsk_params.h"
 #include "fsk_wait.h"
+#include "fsk_launch.h"
 
 namespace fsk {
 

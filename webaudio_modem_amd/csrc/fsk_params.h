@@ -1,5 +1,5 @@
 // fsk_params.h -- launch parameters and persistent per-stream state layout shared by the host
-// API (fsk_api.hip) and the kernels (fsk_demod.hip / fsk_mod.hip).
+// API (fsk_create.hip, fsk_dispatch.hip, fsk_state.hip ...; fsk_engine.h) and the kernels (fsk_demod.hip / fsk_mod.hip).
 //
 // State is struct-of-arrays in HBM: field-major [field][stream] so that a wave (64 consecutive
 // streams) loads/stores each field with one coalesced 256-B (f32/u32) or 512-B (f64) access.

@@ -55,6 +55,7 @@
 #include "fsk_params.h"
 #include "fsk_dev.h"
 #include "fsk_pipe_dev.h"
+#include "fsk_launch.h"
 
 namespace fsk {
 // these kernels hand their state on across kernel boundaries only: plain cache policy for the PIPE_* accesses (fsk_dev.h)

@@ -9,26 +9,8 @@
 #include <string>
 #include <vector>
 
-#include "fsk_host.h"
-#include "fsk_params.h"
-
-namespace fsk {
-hipError_t launch_processor_io(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out,
-                               size_t demod_pitch, const uint32_t *demod_counts, bool do_rx, float *out, size_t n_out,
-                               size_t out_pitch, bool clear_rx_on_complete, hipStream_t st);
-hipError_t launch_processor_tx_start(const ModParams &M, const ProcState &T, const uint8_t *payloads, const uint32_t *lens,
-                                     size_t payload_pitch, const uint8_t *mask, hipStream_t st);
-hipError_t launch_processor_rx_drain(const ProcState &T, uint32_t n_streams, uint8_t *out, size_t out_pitch,
-                                     uint32_t *counts, hipStream_t st);
-hipError_t launch_processor_reset(const ProcState &T, uint32_t n_streams, int64_t stream, bool rx, bool tx, hipStream_t st);
-// engine internals the processor needs (fsk_api.hip)
-const ModParams &engine_mod_params(const fskhip_engine *e);
-const double *engine_coef(const fskhip_engine *e);
-size_t engine_max_bytes(const fskhip_engine *e, size_t n_per_stream);
-uint32_t engine_launch_key(const fskhip_engine *e);       // changes whenever the demodulator would launch differently
-void engine_refresh_kernel_choice(fskhip_engine *e);     // "blk_resets" = auto: look at the tile statistics the last completed call left
-void engine_note_replayed_call(fskhip_engine *e, size_t n);  // host-side counters of a call replayed from a graph
-}  // namespace fsk
+#include "fsk_engine.h"
+#include "fsk_launch.h"
 
 using namespace fsk;
 
@@ -66,15 +48,6 @@ int dev_alloc(T *&p, size_t n) {
   if (err != hipSuccess) return fail(FSKHIP_E_NOMEM, "hipMalloc(%zu): %s", n * sizeof(T), hipGetErrorString(err));
   return FSKHIP_OK;
 }
-template <typename T>
-int ensure(T *&p, size_t &cap, size_t need) {
-  if (need <= cap) return FSKHIP_OK;
-  if (p) (void)hipFree(p);
-  p = nullptr; cap = 0;
-  int rc = dev_alloc(p, need);
-  if (rc == FSKHIP_OK) cap = need;
-  return rc;
-}
 
 void drop_graph(fskhip_processor *p) {
   if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
@@ -88,7 +61,7 @@ int launch_quantum(fskhip_processor *p, float *d_in, size_t n_in, size_t in_pitc
     int rc = fskhip_demodulate_device(p->e, d_in, n_in, in_pitch, p->d_bytes, p->bytes_pitch, p->d_counts, p->d_eod, 0u, st);
     if (rc != FSKHIP_OK) return rc;
   }
-  HIP_TRY(launch_processor_io(engine_mod_params(p->e), engine_coef(p->e), p->T, p->d_bytes, p->bytes_pitch, p->d_counts,
+  HIP_TRY(launch_processor_io(p->e->M, p->e->S.coef, p->T, p->d_bytes, p->bytes_pitch, p->d_counts,
                               d_in != nullptr, d_out, n_out, out_pitch, (flags & FSKHIP_PROC_CLEAR_RX_ON_TX_COMPLETE) != 0, st));
   return FSKHIP_OK;
 }
@@ -117,7 +90,7 @@ int fskhip_processor_create(fskhip_engine *e, uint32_t rx_capacity, fskhip_proce
   if (rx_capacity == 0) return fail(FSKHIP_E_INVALID, "rx_capacity must be > 0");
   fskhip_processor *p = new (std::nothrow) fskhip_processor();
   if (!p) return fail(FSKHIP_E_NOMEM, "out of host memory");
-  p->e = e; p->device = engine_device(e); p->S = fskhip_n_streams(e);
+  p->e = e; p->device = e->device; p->S = fskhip_n_streams(e);
   const size_t S = p->S;
   ProcState &T = p->T;
   T.rx_cap = rx_capacity;
@@ -269,7 +242,7 @@ int fskhip_processor_modulate_host(fskhip_processor *p, const uint8_t *payloads,
   if (payload_pitch && payloads) HIP_TRY(hipMemcpy(p->d_stage, payloads, payload_pitch * S, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(p->d_u32, lens, sizeof(uint32_t) * S, hipMemcpyHostToDevice));
   if (mask) HIP_TRY(hipMemcpy(p->d_mask, mask, S, hipMemcpyHostToDevice));
-  HIP_TRY(launch_processor_tx_start(engine_mod_params(p->e), p->T, p->d_stage, p->d_u32, payload_pitch,
+  HIP_TRY(launch_processor_tx_start(p->e->M, p->T, p->d_stage, p->d_u32, payload_pitch,
                                     mask ? p->d_mask : nullptr, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   return FSKHIP_OK;

@@ -15,6 +15,7 @@
 
 #include "fsk_dev.h"
 #include "fsk_params.h"
+#include "fsk_launch.h"
 
 namespace fsk {
 
