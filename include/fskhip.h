@@ -27,7 +27,8 @@ extern "C" {
  * "blk_lanes" (additions only).  6: kernel = seven-wave / auto-r04, options "stage_min_tiles" / "stage_y_slots" / "stage_roles"; the batched
  * IIRFilter of fskhip_next.h (additions only).  7: fskhip_get_faults (additions only).  8: FSKHIP_E_HANDOFF -- every hand-off wait of
  * the multi-wave kernels is bounded ("Hand-off waits" below; an addition: no healthy call returns it); fskhip_remap_streams (an
- * addition, same version). */
+ * addition, same version); stream snapshots -- fskhip_snapshot_bytes / _streams / _info_get / _stream_config / _concat,
+ * fskhip_restore_streams (additions, same version). */
 #define FSKHIP_ABI_VERSION 8
 #define FSKHIP_MAX_PATTERN_BYTES 16
 
@@ -153,6 +154,69 @@ int fskhip_carry_over(fskhip_engine *dst, const fskhip_engine *src);
  * continued streams then hold the fp32 bar against the reference rather than being bit for bit the source's continuation.
  */
 int fskhip_remap_streams(fskhip_engine *dst, const fskhip_engine *src, const int64_t *map, uint32_t n_map);
+
+/*
+ * Stream snapshots (ABI 8, additions): a portable, host-side image of a set of streams that a fresh engine -- on any device, in any
+ * process running the same build of this library -- continues from, under fskhip_remap_streams' contract.  What the reference's
+ * host does by keeping or moving its FSKCore objects: checkpoint a live batch across a restart, move streams between GPUs, grow,
+ * shrink or rebalance a batch that is spread over several engines.
+ *
+ * The image is plain bytes (write it to a file as it is), little-endian, without pointers, every byte defined -- two snapshots of
+ * the same state are byte-identical.  It is an IMPLEMENTATION-VERSIONED format: valid for the state layout of the build that
+ * wrote it (the header carries a stamp of it, and a build with other state words refuses the image instead of misreading it);
+ * not an archival format.  Layout:
+ *   header, 352 bytes   magic "FSKS", format version, the state-layout stamp (the RF_* / IF_* word counts and a hash of the
+ *                       field names, csrc/fsk_params.h), a checksum over header and records, header / record sizes, the record
+ *                       count, the precision, whether the configs are per stream, the geometry fskhip_remap_streams compares
+ *                       (dsSPB, amplitude-ring capacity, 64-bit / fractional sync ring, pattern bits, sync-ring capacity), the
+ *                       engine-level values a destination takes over (demodulationCalls, totalSamplesProcessed, decimated
+ *                       samples pushed, decimator parity, lock-step flag, signal-quality switch, the ring-grid positions and the
+ *                       phase of the fp32 free-running I/Q frame that new streams join) and the shared fskhip_config;
+ *   n records           fixed size, stream-major, each a multiple of 16 bytes: the stream's per-stream config fields
+ *                       (markFrequency, spaceFrequency, preFilterBandwidth, adaptiveThreshold) and its status-counter
+ *                       baselines, then its amplitude ring, every state word fskhip_debug_state shows, its polyphase sync
+ *                       registers (and their `undefined` masks where the ring capacity is fractional).
+ * A host may therefore select, reorder and concatenate records with memcpy, but the header's count and checksum have to match:
+ * fskhip_snapshot_concat and fskhip_snapshot_streams' own selection are the supported ways.
+ *
+ * fskhip_snapshot_bytes     the bytes a snapshot of n_sel streams of e takes (0 for a null engine).
+ * fskhip_snapshot_streams   snapshots streams sel[0 .. n_sel) of e (sel NULL: all of them, in order; a stream may be named more
+ *                           than once) into buf -- host memory; page-locked memory (fskhip_host_alloc) makes the copy faster, it is
+ *                           not required.  Synchronises with e's outstanding work; e is read only and stays usable.  *written
+ *                           (may be NULL) = the size; FSKHIP_E_OVERFLOW, with *written = the size needed, when cap is too small;
+ *                           FSKHIP_E_HANDOFF for an engine that has reported it (as the remap refuses such a source).
+ * fskhip_snapshot_info_get  what a snapshot holds, read on the host, no device needed.  This and every call below that takes a
+ *                           snapshot validates it first -- magic, format, state-layout stamp, precision, sizes, checksum -- and
+ *                           returns FSKHIP_E_INVALID with a message naming what is wrong.
+ * fskhip_snapshot_stream_config   the fskhip_config record i ran under: a host can build the destination engine from the file
+ *                           alone (record 0 of an empty snapshot: the shared configuration).
+ * fskhip_snapshot_concat    host only: out = the records of bufs[0], then bufs[1], ... under one header.  The snapshots must be
+ *                           images of engines that could have been ONE engine: same format, precision, shared configuration and
+ *                           geometry (what the remap compares), and the same engine-level clocks -- calls, total samples, pushes,
+ *                           decimator parity, lock-step flag, ring grid, signal-quality switch and, for fp32 engines of one shared
+ *                           configuration, the phase of the free-running I/Q frame.  Shards of one sharded batch, created
+ *                           together and fed the same calls, are that.  Otherwise FSKHIP_E_INVALID naming the first field that
+ *                           differs.  FSKHIP_E_OVERFLOW / *written as above.
+ * fskhip_restore_streams    fskhip_remap_streams with the snapshot standing in for src: n_map == the streams of dst, map[i] is a
+ *                           RECORD of the snapshot or -1.  Every sentence of fskhip_remap_streams' comment holds with "src" read as
+ *                           "the engine the snapshot was taken of, at that moment" -- except the same-device precondition, which
+ *                           is dropped, and "dst != src", which has no meaning.  A refused call leaves dst as it was.
+ * Large batches cross in slabs of 8192 streams: two staging slabs on the device whatever the batch, the copy of one slab
+ * overlapping the kernel of the next.  fskhip_processor objects (fskhip_next.h) stay out of snapshots, as they stay out of a remap.
+ */
+typedef struct fskhip_snapshot_info {
+  uint32_t n_streams;
+  int32_t precision;
+  uint32_t per_stream_configs;
+  uint32_t record_bytes;
+  double demodulationCalls, totalSamplesProcessed; /* the source engine's clocks */
+} fskhip_snapshot_info;
+size_t fskhip_snapshot_bytes(const fskhip_engine *e, uint32_t n_sel);
+int fskhip_snapshot_streams(fskhip_engine *e, const int64_t *sel, uint32_t n_sel, void *buf, size_t cap, size_t *written);
+int fskhip_snapshot_info_get(const void *buf, size_t size, fskhip_snapshot_info *info);
+int fskhip_snapshot_stream_config(const void *buf, size_t size, uint32_t i, fskhip_config *cfg);
+int fskhip_snapshot_concat(const void *const *bufs, const size_t *sizes, uint32_t n, void *out, size_t cap, size_t *written);
+int fskhip_restore_streams(fskhip_engine *dst, const void *buf, size_t size, const int64_t *map, uint32_t n_map);
 
 uint32_t fskhip_n_streams(const fskhip_engine *e);
 

@@ -55,8 +55,19 @@ export class FSKBatch {
   getSignalQualityEstimates(stream?: number): SignalQualityEstimates;
   /** a new batch of map.length streams: stream i continues stream map[i] of this one as if moved, or is new where map[i] is -1 */
   remap(map: ArrayLike<number>, configs?: Partial<FSKConfig> | Partial<FSKConfig>[]): FSKBatch;
+  /** a portable image of streams `streams` (default: all, in order): plain bytes that a new batch on any device, in any process of the same build, continues from */
+  snapshot(streams?: ArrayLike<number>): Buffer;
+  /** a new batch whose stream i continues RECORD map[i] of the snapshot (-1: new; default: every record in order); precision and configs come from the snapshot unless given */
+  static fromSnapshot(buf: Uint8Array, map?: ArrayLike<number>, configs?: Partial<FSKConfig> | Partial<FSKConfig>[], device?: number): FSKBatch;
   close(): void;
 }
+export interface SnapshotInfo {
+  nStreams: number; precision: 0 | 1; perStreamConfigs: number; recordBytes: number; demodulationCalls: number; totalSamplesProcessed: number;
+}
+/** what a snapshot holds (validated on the host, no device needed) */
+export function snapshotInfo(buf: Uint8Array): SnapshotInfo;
+/** the records of several snapshots under one header; they must be images of engines that could have been one engine */
+export function snapshotConcat(bufs: Uint8Array[]): Buffer;
 /** one Node process, several GPUs: one FSKBatch per device over contiguous stream blocks, calls issued together */
 export class FSKBatchSharded {
   constructor(nStreams: number, configs: Partial<FSKConfig> | Partial<FSKConfig>[], options?: { devices?: number[]; precision?: 0 | 1 });
@@ -65,5 +76,9 @@ export class FSKBatchSharded {
   modulateData(payloads: Uint8Array[]): Float32Array[];
   reset(stream?: number): void;
   getStatus(stream?: number): FSKStatus;
+  /** one snapshot of the whole batch, records in global stream order */
+  snapshot(): Buffer;
+  /** a new sharded batch whose stream i continues GLOBAL stream map[i] of this one (-1: new), across shards and devices (default: this batch's) */
+  remap(map: ArrayLike<number>, configs?: Partial<FSKConfig> | Partial<FSKConfig>[], options?: { devices?: number[] }): FSKBatchSharded;
   close(): void;
 }

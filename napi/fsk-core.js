@@ -193,6 +193,33 @@ class FSKBatch {
     }
     return b;
   }
+  // Stream snapshots (include/fskhip.h, fskhip_snapshot_streams / fskhip_restore_streams): a Buffer holding streams `streams`
+  // of this batch (undefined: all, in order) -- plain bytes, fit for a file -- that a new batch on any device, in any process
+  // running the same build, continues from under remap()'s contract.  This batch is left as it is.
+  snapshot(streams) { return addon.snapshotStreams(this.handle, streams === undefined || streams === null ? null : Array.from(streams, Number)); }
+  // a new FSKBatch whose stream i continues RECORD map[i] of the snapshot (-1: a new FSKCore; undefined: every record in order).
+  // Precision and configs are read out of the snapshot unless configs are given (a -1 slot needs one when the snapshot's
+  // configs are per stream).
+  static fromSnapshot(buf, map, configs, device) {
+    const info = addon.snapshotInfo(buf);
+    const m = map === undefined || map === null ? Array.from({ length: info.nStreams }, (_, i) => i) : Array.from(map, Number);
+    let cfgs = configs;
+    if (cfgs === undefined || cfgs === null) {
+      if (!info.perStreamConfigs) cfgs = addon.snapshotConfig(buf, 0);
+      else {
+        if (m.some((v) => v < 0)) throw new Error('FSKBatch.fromSnapshot: a -1 slot needs an explicit config (per-stream configs)');
+        cfgs = m.map((v) => addon.snapshotConfig(buf, v));
+      }
+    }
+    const b = new FSKBatch(m.length, cfgs, { device: device || 0, precision: info.precision });
+    try {
+      addon.restoreStreams(b.handle, buf, m);
+    } catch (err) {
+      b.close();
+      throw err;
+    }
+    return b;
+  }
   close() { if (this.handle) { addon.destroy(this.handle); this.handle = null; } }
 }
 
@@ -252,7 +279,41 @@ class FSKBatchSharded {
     else { const [sh, local] = this.locate(stream); sh.batch.reset(local); }
   }
   getStatus(stream) { const [sh, local] = this.locate(stream || 0); return sh.batch.getStatus(local); }
+  // one snapshot of the whole batch, records in global stream order (fskhip_snapshot_concat of the shards' snapshots: created
+  // together and fed the same calls, they are images of what could have been one engine)
+  snapshot() {
+    const parts = this.shards.map((sh) => sh.batch.snapshot());
+    return parts.length === 1 ? parts[0] : addon.snapshotConcat(parts);
+  }
+  // a new FSKBatchSharded of map.length streams whose stream i continues GLOBAL stream map[i] of this one (-1: a new FSKCore),
+  // across shards and devices (options.devices, default: this batch's): every new shard restores its slice of the map from one
+  // snapshot of the whole batch.  This batch is left as it is.
+  remap(map, configs, options = {}) {
+    const buf = this.snapshot();
+    const info = addon.snapshotInfo(buf);
+    const m = Array.from(map, Number);
+    let cfgs = configs;
+    if (cfgs === undefined || cfgs === null) {
+      if (!info.perStreamConfigs) cfgs = addon.snapshotConfig(buf, 0);
+      else {
+        if (m.some((v) => v < 0)) throw new Error('FSKBatchSharded.remap: a -1 slot needs an explicit config (per-stream configs)');
+        cfgs = m.map((v) => addon.snapshotConfig(buf, v));
+      }
+    }
+    const devices = options.devices || this.shards.map((sh) => sh.device);
+    const next = new FSKBatchSharded(m.length, cfgs, { devices, precision: info.precision });
+    try {
+      next.shards.forEach((sh) => addon.restoreStreams(sh.batch.handle, buf, m.slice(sh.first, sh.first + sh.count)));
+    } catch (err) {
+      next.close();
+      throw err;
+    }
+    return next;
+  }
   close() { this.shards.forEach((sh) => sh.batch.close()); this.shards = []; }
 }
 
-module.exports = { FSKCore, FSKBatch, FSKBatchSharded, DEFAULT_FSK_CONFIG, Event, EventEmitter, PRECISION_F32, PRECISION_F64, addon };
+const snapshotInfo = (buf) => addon.snapshotInfo(buf);
+const snapshotConcat = (bufs) => addon.snapshotConcat(bufs);
+
+module.exports = { FSKCore, FSKBatch, FSKBatchSharded, snapshotInfo, snapshotConcat, DEFAULT_FSK_CONFIG, Event, EventEmitter, PRECISION_F32, PRECISION_F64, addon };

@@ -425,6 +425,167 @@ static napi_value RemapStreams(napi_env env, napi_callback_info info) {
 
 static void set_num(napi_env env, napi_value obj, const char *k, double v);
 
+// ---- stream snapshots (include/fskhip.h): a snapshot is a Buffer (or any Uint8Array) on this side
+static bool get_index_array(napi_env env, napi_value arr, const char *what, std::vector<int64_t> *out) {
+  bool is_arr = false;
+  if (napi_is_array(env, arr, &is_arr) != napi_ok || !is_arr) { napi_throw_type_error(env, nullptr, what); return false; }
+  uint32_t n = 0;
+  napi_get_array_length(env, arr, &n);
+  out->resize(n);
+  for (uint32_t i = 0; i < n; i++) {
+    napi_value v;
+    double d = 0;
+    if (napi_get_element(env, arr, i, &v) != napi_ok || napi_get_value_double(env, v, &d) != napi_ok || d != (double)(int64_t)d) {
+      napi_throw_type_error(env, nullptr, what);
+      return false;
+    }
+    (*out)[i] = (int64_t)d;
+  }
+  return true;
+}
+static bool get_blob(napi_env env, napi_value v, const void **data, size_t *size) {
+  bool is = false;
+  void *p = nullptr;
+  if (napi_is_buffer(env, v, &is) == napi_ok && is && napi_get_buffer_info(env, v, &p, size) == napi_ok) { *data = p; return true; }
+  if (napi_is_typedarray(env, v, &is) == napi_ok && is) {
+    napi_typedarray_type t;
+    size_t n = 0;
+    if (napi_get_typedarray_info(env, v, &t, &n, &p, nullptr, nullptr) == napi_ok && t == napi_uint8_array) { *data = p; *size = n; return true; }
+  }
+  napi_throw_type_error(env, nullptr, "a snapshot must be a Buffer or Uint8Array");
+  return false;
+}
+
+// snapshotStreams(handle, sel): Buffer with streams sel (an Array of stream indices; null / undefined: all, in order)
+static napi_value SnapshotStreams(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  fskhip_engine *e = argc >= 1 ? get_engine(env, argv[0]) : nullptr;
+  if (!e) { if (argc < 1) napi_throw_type_error(env, nullptr, "snapshotStreams(handle, sel)"); return nullptr; }
+  std::vector<int64_t> sel;
+  bool all = true;
+  if (argc >= 2) {
+    napi_valuetype t;
+    NAPI_OK(napi_typeof(env, argv[1], &t));
+    if (t != napi_undefined && t != napi_null) {
+      all = false;
+      if (!get_index_array(env, argv[1], "snapshotStreams: sel must be an Array of stream indices", &sel)) return nullptr;
+    }
+  }
+  const uint32_t n = all ? fskhip_n_streams(e) : (uint32_t)sel.size();
+  const size_t need = fskhip_snapshot_bytes(e, n);
+  void *data = nullptr;
+  napi_value buf;
+  NAPI_OK(napi_create_buffer(env, need, &data, &buf));
+  static const int64_t none = 0;
+  const int rc = fskhip_snapshot_streams(e, all ? nullptr : (sel.empty() ? &none : sel.data()), n, data, need, nullptr);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return buf;
+}
+
+// restoreStreams(dst, snapshot, map): stream i of dst continues record map[i] of the snapshot, or starts afresh where map[i] is -1
+static napi_value RestoreStreams(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (argc < 3) { napi_throw_type_error(env, nullptr, "restoreStreams(dst, snapshot, map)"); return nullptr; }
+  fskhip_engine *dst = get_engine(env, argv[0]);
+  if (!dst) return nullptr;
+  const void *data = nullptr;
+  size_t size = 0;
+  if (!get_blob(env, argv[1], &data, &size)) return nullptr;
+  std::vector<int64_t> map;
+  if (!get_index_array(env, argv[2], "restoreStreams: map must be an Array of record indices (-1: a new stream)", &map)) return nullptr;
+  const int rc = fskhip_restore_streams(dst, data, size, map.data(), (uint32_t)map.size());
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+
+// snapshotInfo(snapshot) -> {nStreams, precision, perStreamConfigs, recordBytes, demodulationCalls, totalSamplesProcessed}
+static napi_value SnapshotInfo(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const void *data = nullptr;
+  size_t size = 0;
+  if (argc < 1 || !get_blob(env, argv[0], &data, &size)) { if (argc < 1) napi_throw_type_error(env, nullptr, "snapshotInfo(snapshot)"); return nullptr; }
+  fskhip_snapshot_info si;
+  const int rc = fskhip_snapshot_info_get(data, size, &si);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  set_num(env, o, "nStreams", si.n_streams);
+  set_num(env, o, "precision", si.precision);
+  set_num(env, o, "perStreamConfigs", si.per_stream_configs);
+  set_num(env, o, "recordBytes", si.record_bytes);
+  set_num(env, o, "demodulationCalls", si.demodulationCalls);
+  set_num(env, o, "totalSamplesProcessed", si.totalSamplesProcessed);
+  return o;
+}
+
+// snapshotConfig(snapshot, i) -> the FSKConfig record i ran under
+static napi_value SnapshotConfig(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const void *data = nullptr;
+  size_t size = 0;
+  if (argc < 2 || !get_blob(env, argv[0], &data, &size)) { if (argc < 2) napi_throw_type_error(env, nullptr, "snapshotConfig(snapshot, i)"); return nullptr; }
+  uint32_t i = 0;
+  NAPI_OK(napi_get_value_uint32(env, argv[1], &i));
+  fskhip_config c;
+  const int rc = fskhip_snapshot_stream_config(data, size, i, &c);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  napi_value o, arr, v;
+  NAPI_OK(napi_create_object(env, &o));
+  set_num(env, o, "sampleRate", c.sampleRate); set_num(env, o, "baudRate", c.baudRate);
+  set_num(env, o, "markFrequency", c.markFrequency); set_num(env, o, "spaceFrequency", c.spaceFrequency);
+  set_num(env, o, "startBits", c.startBits); set_num(env, o, "stopBits", c.stopBits);
+  set_num(env, o, "syncThreshold", c.syncThreshold); set_num(env, o, "preFilterBandwidth", c.preFilterBandwidth);
+  NAPI_OK(napi_create_array_with_length(env, (size_t)c.preambleLen, &arr));
+  for (int32_t k = 0; k < c.preambleLen; k++) { napi_create_int32(env, c.preamblePattern[k], &v); napi_set_element(env, arr, (uint32_t)k, v); }
+  napi_set_named_property(env, o, "preamblePattern", arr);
+  NAPI_OK(napi_create_array_with_length(env, (size_t)c.sfdLen, &arr));
+  for (int32_t k = 0; k < c.sfdLen; k++) { napi_create_int32(env, c.sfdPattern[k], &v); napi_set_element(env, arr, (uint32_t)k, v); }
+  napi_set_named_property(env, o, "sfdPattern", arr);
+  const char *par = c.parity == 1 ? "even" : c.parity == 2 ? "odd" : "none";
+  napi_create_string_utf8(env, par, NAPI_AUTO_LENGTH, &v);
+  napi_set_named_property(env, o, "parity", v);
+  napi_get_boolean(env, c.agcEnabled != 0, &v);
+  napi_set_named_property(env, o, "agcEnabled", v);
+  napi_get_boolean(env, c.adaptiveThreshold != 0, &v);
+  napi_set_named_property(env, o, "adaptiveThreshold", v);
+  return o;
+}
+
+// snapshotConcat([snapshot, ...]) -> Buffer: the records of all of them under one header (images of what could have been one engine)
+static napi_value SnapshotConcat(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  bool is_arr = false;
+  if (argc < 1 || napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr) { napi_throw_type_error(env, nullptr, "snapshotConcat: an Array of snapshots"); return nullptr; }
+  uint32_t n = 0;
+  NAPI_OK(napi_get_array_length(env, argv[0], &n));
+  std::vector<const void *> ptrs(n);
+  std::vector<size_t> sizes(n);
+  for (uint32_t k = 0; k < n; k++) {
+    napi_value v;
+    NAPI_OK(napi_get_element(env, argv[0], k, &v));
+    if (!get_blob(env, v, &ptrs[k], &sizes[k])) return nullptr;
+  }
+  size_t need = 0;
+  int rc = fskhip_snapshot_concat(ptrs.data(), sizes.data(), n, nullptr, 0, &need);
+  if (rc != FSKHIP_E_OVERFLOW) return throw_fsk(env, rc);
+  void *data = nullptr;
+  napi_value buf;
+  NAPI_OK(napi_create_buffer(env, need, &data, &buf));
+  rc = fskhip_snapshot_concat(ptrs.data(), sizes.data(), n, data, need, nullptr);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return buf;
+}
+
 // enableSignalQuality(handle, on) / getSignalQualityEstimates(handle, stream): the opt-in estimates of include/fskhip.h
 static napi_value EnableSignalQuality(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -545,6 +706,11 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"reset", nullptr, Reset, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"carryOver", nullptr, CarryOver, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"remapStreams", nullptr, RemapStreams, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"snapshotStreams", nullptr, SnapshotStreams, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"restoreStreams", nullptr, RestoreStreams, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"snapshotInfo", nullptr, SnapshotInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"snapshotConfig", nullptr, SnapshotConfig, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"snapshotConcat", nullptr, SnapshotConcat, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"enableSignalQuality", nullptr, EnableSignalQuality, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"getSignalQualityEstimates", nullptr, GetSignalQualityEstimates, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"getStatus", nullptr, GetStatus, nullptr, nullptr, nullptr, napi_default, nullptr},

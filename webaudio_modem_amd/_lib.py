@@ -49,6 +49,12 @@ class Status(C.Structure):
     ]
 
 
+class SnapshotInfo(C.Structure):
+    """fskhip_snapshot_info (include/fskhip.h): what a stream snapshot holds"""
+    _fields_ = [("n_streams", C.c_uint32), ("precision", C.c_int32), ("per_stream_configs", C.c_uint32), ("record_bytes", C.c_uint32),
+                ("demodulationCalls", C.c_double), ("totalSamplesProcessed", C.c_double)]
+
+
 class XModemResult(C.Structure):
     """fskhip_xmodem_result (include/fskhip_next.h)."""
     _fields_ = [
@@ -93,6 +99,12 @@ _SYMBOLS = [
                                            C.POINTER(C.c_double)]),
     ("fskhip_carry_over", C.c_int, [_P, _P]),
     ("fskhip_remap_streams", C.c_int, [_P, _P, _P, C.c_uint32]),
+    ("fskhip_snapshot_bytes", C.c_size_t, [_P, C.c_uint32]),
+    ("fskhip_snapshot_streams", C.c_int, [_P, _P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fskhip_snapshot_info_get", C.c_int, [_P, C.c_size_t, C.POINTER(SnapshotInfo)]),
+    ("fskhip_snapshot_stream_config", C.c_int, [_P, C.c_size_t, C.c_uint32, C.POINTER(Config)]),
+    ("fskhip_snapshot_concat", C.c_int, [C.POINTER(_P), C.POINTER(C.c_size_t), C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fskhip_restore_streams", C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint32]),
     ("fskhip_enable_signal_quality", C.c_int, [_P, C.c_int]),
     ("fskhip_get_signal_quality", C.c_int, [_P, C.c_uint32, C.POINTER(SignalQuality)]),
     ("fskhip_host_alloc", C.c_int, [C.c_size_t, C.POINTER(_P)]),

@@ -1,5 +1,6 @@
 // fsk_create.hip -- C ABI of libfskhip.so (include/fskhip.h): configure-time parameter derivation, creating and destroying an
-// engine, and what a new engine takes over from an old one (fskhip_carry_over, the host half of fskhip_remap_streams).
+// engine, and what a new engine takes over from an old one (fskhip_carry_over, the host half of fskhip_remap_streams and what it
+// shares with fskhip_restore_streams).
 #include <new>
 
 #include "fsk_engine.h"
@@ -256,6 +257,83 @@ __global__ void init_kernel(DemodState S, uint32_t n, uint32_t matched_zero) {
 }
 }  // namespace
 
+// ---- what fskhip_remap_streams and fskhip_restore_streams (fsk_snapshot_api.hip) share: the checks, the lock-step decision and
+// the host-side counters of a destination that continues streams of a StreamSource (fsk_engine.h)
+namespace fsk {
+bool config_shared_fields_equal(const fskhip_config &a, const fskhip_config &b) { return shared_fields_equal(a, b); }
+const fskhip_config &engine_stream_config(const fskhip_engine *e, size_t s) { return stream_config(e, s); }
+
+int remap_check_map(const char *who, const char *what, const int64_t *map, uint32_t n_map) {
+  if (n_map > 0 && !map) return fail(FSKHIP_E_INVALID, "%s: null map", who);
+  for (uint32_t i = 0; i < n_map; i++)
+    if (map[i] < -1) return fail(FSKHIP_E_INVALID, "%s: map[%u] = %lld (%s or -1)", who, i, (long long)map[i], what);
+  return FSKHIP_OK;
+}
+
+// a source that has reported (or now holds) a hand-off fault: its streams stopped mid-call.  Read only: e is not written.
+// (After the caller's device synchronisation.)
+int engine_refuse_handoff(const char *who, const char *the, const fskhip_engine *e) {
+  uint32_t w = e->handoff_fault;
+  if (w == 0u && e->S.blk_stat) HIP_TRY(hipMemcpy(&w, e->S.blk_stat + 2, sizeof(w), hipMemcpyDeviceToHost));
+  if (w != 0u)
+    return fail(FSKHIP_E_HANDOFF, "%s: %s's multi-wave kernel ran into its hand-off bound (fault word %u): its streams cannot be continued", who, the, w);
+  return FSKHIP_OK;
+}
+
+int remap_check(const fskhip_engine *dst, const StreamSource &V, const int64_t *map, uint32_t n_map, RemapPlan *plan) {
+  if (n_map != dst->n_streams) return fail(FSKHIP_E_INVALID, "%s: n_map %u != the destination's %u streams", V.who, n_map, dst->n_streams);
+  if (dst->precision != V.precision) return fail(FSKHIP_E_INVALID, "%s: engines differ in precision (%d, %d)", V.who, dst->precision, V.precision);
+  if (dst->demodulated) return fail(FSKHIP_E_INVALID, "%s: the destination has demodulated already (remap into a fresh engine)", V.who);
+  // One geometry for both engines, whatever the map (an all -1 map included): the gather reads src's state with dst's layout,
+  // and dst takes over src's decimator phase and ring grid.  Every field but the per-stream tone pair / pre-filter bandwidth.
+  if (!shared_fields_equal(dst->cfg0, V.cfg0) || dst->P.d != V.d || dst->P.amp_cap != V.amp_cap || dst->P.wide != V.wide ||
+      dst->P.frac != V.frac || dst->P.n_bits != V.n_bits || dst->P.ring_cap != V.ring_cap)
+    return fail(FSKHIP_E_INVALID, "%s: the engines' configurations differ beyond mark/space/preFilterBandwidth "
+                "(sampleRate, baudRate, framing, patterns, syncThreshold, agcEnabled must be equal)", V.who);
+  uint32_t n_fresh = 0;
+  int64_t frame_row = -1;   // a continued stream's source row: its free-running I/Q frame is the one dst's continued streams share
+  for (uint32_t i = 0; i < n_map; i++) {
+    if (map[i] < 0) { n_fresh++; continue; }
+    if (map[i] >= (int64_t)V.n_streams)
+      return fail(FSKHIP_E_INVALID, "%s: map[%u] = %lld, %s has %u %s", V.who, i, (long long)map[i], V.the, V.n_streams, V.unit);
+    if (!config_equal(stream_config(dst, i), V.config(V.ctx, (size_t)map[i])))
+      return fail(FSKHIP_E_INVALID, "%s: the config of stream %u differs from that of %s %lld", V.who, i, V.item, (long long)map[i]);
+    if (frame_row < 0) frame_row = map[i];
+  }
+  // Lock step (one decimator phase, one ring grid for every stream) is what the whole-tile kernels need.  A continued stream
+  // brings it along; a new one joins the grid -- unless the source streams are mid decimator-pair (a new one is not), the ring
+  // capacity is fractional, or the source has left lock step already: then new streams start at the create-time positions and
+  // the destination runs out of lock step, as after fskhip_reset of one stream mid-pair.
+  plan->n_fresh = n_fresh;
+  plan->frame_row = frame_row;
+  plan->uniform = V.ds_uniform;
+  plan->parity = V.ds_parity;
+  plan->gen_odd = V.gen_odd;
+  if (n_fresh == n_map) { plan->parity = 0; plan->gen_odd = false; }                 // only new streams: every decimator starts afresh
+  else if (n_fresh > 0 && (V.ds_parity != 0 || V.frac)) plan->uniform = false;
+  plan->grid = plan->uniform && !V.frac;
+  // (fp32, one shared configuration in dst: new streams join the frame of a CONTINUED stream -- its config is dst's, unlike that of
+  // an arbitrary source row of a per-stream source, whose NCO increment and therefore frame phase may be another)
+  plan->frame = dst->precision == FSKHIP_PRECISION_F32 && dst->P.uni_cfg && frame_row >= 0;
+  return FSKHIP_OK;
+}
+
+// host side: the engine's clocks and, per stream, the baselines its status counters are taken against (fsk.ts:131)
+void remap_finish(fskhip_engine *dst, const StreamSource &V, const int64_t *map, uint32_t n_map, const RemapPlan &plan) {
+  dst->calls = V.calls;
+  dst->total_samples = V.total_samples;
+  for (uint32_t i = 0; i < n_map; i++) {
+    if (map[i] >= 0) V.baselines(V.ctx, (size_t)map[i], &dst->base_calls[i], &dst->base_samples[i]);
+    else { dst->base_calls[i] = V.calls; dst->base_samples[i] = V.total_samples; }
+  }
+  dst->pushes = V.pushes;
+  dst->ds_parity = plan.parity;
+  dst->ds_uniform = plan.uniform;
+  dst->gen_odd = plan.gen_odd;
+  dst->P.quality = V.quality;   // the signal-quality estimates belong to the streams: they go on accumulating where they did
+}
+}  // namespace fsk
+
 extern "C" {
 void fskhip_butterworth_lowpass(double cutoff, double sr, double b[3], double a[3]) { ref_butter_lp(cutoff, sr, b, a); }
 void fskhip_butterworth_highpass(double cutoff, double sr, double b[3], double a[3]) { ref_butter_lp_hp(true, cutoff, sr, b, a); }
@@ -409,58 +487,36 @@ int fskhip_carry_over(fskhip_engine *dst, const fskhip_engine *src) {
 // Stream i of dst continues stream map[i] of src as if that FSKCore had been moved, or (map[i] = -1) starts as a new one
 // (include/fskhip.h).  Synchronous: every check first, then one gather launch (fsk_remap.hip), then the host-side counters.
 int fskhip_remap_streams(fskhip_engine *dst, const fskhip_engine *src, const int64_t *map, uint32_t n_map) {
-  if (n_map > 0 && !map) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: null map");
-  for (uint32_t i = 0; i < n_map; i++)
-    if (map[i] < -1) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: map[%u] = %lld (a source stream or -1)", i, (long long)map[i]);
+  static const char who[] = "fskhip_remap_streams";
+  if (const int rc = remap_check_map(who, "a source stream", map, n_map)) return rc;
   if (!dst || !src) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: null engine");
   if (dst == src) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: dst is src (remap into a new engine)");
-  if (n_map != dst->n_streams) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: n_map %u != the destination's %u streams", n_map, dst->n_streams);
-  if (dst->precision != src->precision) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: engines differ in precision (%d, %d)", dst->precision, src->precision);
   if (dst->device != src->device) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: engines are on devices %d and %d", dst->device, src->device);
-  if (dst->demodulated) return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: the destination has demodulated already (remap into a fresh engine)");
-  // One geometry for both engines, whatever the map (an all -1 map included): the gather reads src's state with dst's layout,
-  // and dst takes over src's decimator phase and ring grid.  Every field but the per-stream tone pair / pre-filter bandwidth.
-  if (!shared_fields_equal(dst->cfg0, src->cfg0) || dst->P.d != src->P.d || dst->P.amp_cap != src->P.amp_cap || dst->P.wide != src->P.wide ||
-      dst->P.frac != src->P.frac || dst->P.n_bits != src->P.n_bits || dst->P.ring_cap != src->P.ring_cap)
-    return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: the engines' configurations differ beyond mark/space/preFilterBandwidth "
-                "(sampleRate, baudRate, framing, patterns, syncThreshold, agcEnabled must be equal)");
-  uint32_t n_fresh = 0;
-  int64_t frame_row = -1;   // a continued stream's source row: its free-running I/Q frame is the one dst's continued streams share
-  for (uint32_t i = 0; i < n_map; i++) {
-    if (map[i] < 0) { n_fresh++; continue; }
-    if (map[i] >= (int64_t)src->n_streams)
-      return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: map[%u] = %lld, the source has %u streams", i, (long long)map[i], src->n_streams);
-    if (!config_equal(stream_config(dst, i), stream_config(src, (size_t)map[i])))
-      return fail(FSKHIP_E_INVALID, "fskhip_remap_streams: the config of stream %u differs from that of source stream %lld", i, (long long)map[i]);
-    if (frame_row < 0) frame_row = map[i];
-  }
+  StreamSource V{};
+  V.who = who; V.the = "the source"; V.unit = "streams"; V.item = "source stream";
+  V.precision = src->precision; V.n_streams = src->n_streams; V.cfg0 = src->cfg0;
+  V.d = src->P.d; V.amp_cap = src->P.amp_cap; V.wide = src->P.wide; V.frac = src->P.frac; V.n_bits = src->P.n_bits; V.ring_cap = src->P.ring_cap;
+  V.calls = src->calls; V.total_samples = src->total_samples; V.pushes = src->pushes;
+  V.ds_parity = src->ds_parity; V.ds_uniform = src->ds_uniform; V.gen_odd = src->gen_odd; V.quality = src->P.quality;
+  V.ctx = src;
+  V.config = [](const void *ctx, size_t s) { return stream_config((const fskhip_engine *)ctx, s); };
+  V.baselines = [](const void *ctx, size_t s, uint64_t *calls, uint64_t *samples) {
+    const fskhip_engine *e = (const fskhip_engine *)ctx;
+    *calls = e->base_calls[s]; *samples = e->base_samples[s];
+  };
+  RemapPlan plan{};
+  if (const int rc = remap_check(dst, V, map, n_map, &plan)) return rc;
   HIP_TRY(hipSetDevice(dst->device));
   HIP_TRY(hipDeviceSynchronize());
-  {   // a source that has reported (or now holds) a hand-off fault: its streams stopped mid-call.  Read only: src is not written.
-    uint32_t w = src->handoff_fault;
-    if (w == 0u && src->S.blk_stat) HIP_TRY(hipMemcpy(&w, src->S.blk_stat + 2, sizeof(w), hipMemcpyDeviceToHost));
-    if (w != 0u)
-      return fail(FSKHIP_E_HANDOFF, "fskhip_remap_streams: the source's multi-wave kernel ran into its hand-off bound (fault word %u): its streams cannot be continued", w);
-  }
+  if (const int rc = engine_refuse_handoff(who, "the source", src)) return rc;
 
-  // Lock step (one decimator phase, one ring grid for every stream) is what the whole-tile kernels need.  A continued stream
-  // brings it along; a new one joins the grid -- unless the source streams are mid decimator-pair (a new one is not), the ring
-  // capacity is fractional, or the source has left lock step already: then new streams start at the create-time positions and
-  // the destination runs out of lock step, as after fskhip_reset of one stream mid-pair.
-  bool uniform = src->ds_uniform;
-  uint32_t parity = src->ds_parity;
-  bool gen_odd = src->gen_odd;
-  if (n_fresh == n_map) { parity = 0; gen_odd = false; }                 // only new streams: every decimator starts afresh
-  else if (n_fresh > 0 && (parity != 0 || src->P.frac)) uniform = false;
   RemapArgs A{};
   A.n_dst = dst->n_streams; A.n_src = src->n_streams;
   A.d = dst->P.d; A.amp_cap = dst->P.amp_cap; A.wide = dst->P.wide; A.frac = dst->P.frac;
   A.matched_zero = dst->matched_zero;
-  A.grid_src = (uniform && !src->P.frac) ? 1u : 0u;
-  // (fp32, one shared configuration in dst: new streams join the frame of a CONTINUED stream -- its config is dst's, unlike that of
-  // an arbitrary source row of a per-stream source, whose NCO increment and therefore frame phase may be another)
-  A.frame_src = (dst->precision == FSKHIP_PRECISION_F32 && dst->P.uni_cfg && frame_row >= 0) ? 1u : 0u;
-  A.frame_row = frame_row >= 0 ? (uint32_t)frame_row : 0u;
+  A.grid_src = plan.grid ? 1u : 0u;
+  A.frame_src = plan.frame ? 1u : 0u;
+  A.frame_row = plan.frame_row >= 0 ? (uint32_t)plan.frame_row : 0u;
   int64_t *d_map = nullptr;
   HIP_TRY(hipMalloc((void **)&d_map, sizeof(int64_t) * n_map));
   hipError_t err = hipMemcpy(d_map, map, sizeof(int64_t) * n_map, hipMemcpyHostToDevice);
@@ -468,19 +524,7 @@ int fskhip_remap_streams(fskhip_engine *dst, const fskhip_engine *src, const int
   if (err == hipSuccess) err = hipDeviceSynchronize();
   (void)hipFree(d_map);
   if (err != hipSuccess) return fail(FSKHIP_E_HIP, "fskhip_remap_streams: %s", hipGetErrorString(err));
-
-  // host side: the engine's clocks and, per stream, the baselines its status counters are taken against (fsk.ts:131)
-  dst->calls = src->calls;
-  dst->total_samples = src->total_samples;
-  for (uint32_t i = 0; i < n_map; i++) {
-    dst->base_calls[i] = map[i] >= 0 ? src->base_calls[(size_t)map[i]] : src->calls;
-    dst->base_samples[i] = map[i] >= 0 ? src->base_samples[(size_t)map[i]] : src->total_samples;
-  }
-  dst->pushes = src->pushes;
-  dst->ds_parity = parity;
-  dst->ds_uniform = uniform;
-  dst->gen_odd = gen_odd;
-  dst->P.quality = src->P.quality;   // the signal-quality estimates belong to the streams: they go on accumulating where they did
+  remap_finish(dst, V, map, n_map, plan);
   return FSKHIP_OK;
 }
 }  // extern "C"

@@ -109,6 +109,36 @@ uint32_t engine_launch_key(const fskhip_engine *e);          // changes whenever
 void engine_refresh_kernel_choice(fskhip_engine *e);         // "blk_resets" = auto: look at the tile statistics the last completed call left
 void engine_note_replayed_call(fskhip_engine *e, size_t n);  // host-side counters of a call replayed from a graph
 int handoff_check(fskhip_engine *e, bool blocking);
+// fsk_create.hip: what a destination engine continues streams FROM -- a live engine (fskhip_remap_streams) or a snapshot of one
+// (fskhip_restore_streams, fsk_snapshot_api.hip) -- and the checks, lock-step decision and host-side counters the two share
+struct StreamSource {
+  const char *who;                  // the entry point, for messages
+  const char *the, *unit, *item;    // "the source" / "streams" / "source stream"
+  int precision;
+  uint32_t n_streams;
+  fskhip_config cfg0;
+  uint32_t d, amp_cap, wide, frac, n_bits, ring_cap;   // the geometry both sides must share
+  uint64_t calls, total_samples, pushes;
+  uint32_t ds_parity, quality;
+  bool ds_uniform, gen_odd;
+  const void *ctx;
+  fskhip_config (*config)(const void *ctx, size_t s);
+  void (*baselines)(const void *ctx, size_t s, uint64_t *calls, uint64_t *samples);
+};
+struct RemapPlan {
+  uint32_t n_fresh;      // map entries of -1
+  int64_t frame_row;     // the first continued stream's source row, or -1
+  bool uniform, gen_odd; // what the destination's ds_uniform / gen_odd become
+  uint32_t parity;
+  bool grid;             // new streams take the source's ring positions
+  bool frame;            // new streams join the free-running I/Q frame of source row frame_row
+};
+int remap_check_map(const char *who, const char *what, const int64_t *map, uint32_t n_map);
+int remap_check(const fskhip_engine *dst, const StreamSource &V, const int64_t *map, uint32_t n_map, RemapPlan *plan);
+void remap_finish(fskhip_engine *dst, const StreamSource &V, const int64_t *map, uint32_t n_map, const RemapPlan &plan);
+int engine_refuse_handoff(const char *who, const char *the, const fskhip_engine *e);
+bool config_shared_fields_equal(const fskhip_config &a, const fskhip_config &b);
+const fskhip_config &engine_stream_config(const fskhip_engine *e, size_t s);
 // fsk_api.hip: the event pair fskhip_timing_begin / _end put around a call's launches (nothing while timing is off)
 int timing_open(fskhip_engine *e, hipStream_t st);
 int timing_close(fskhip_engine *e, hipStream_t st);

@@ -183,6 +183,26 @@ struct RemapArgs {
   uint32_t frame_row;               // ... that of this source row (a continued stream's: dst's config, dst's frame)
 };
 
+// Stream snapshots (fsk_snapshot.hip): one stream's record as the pack / unpack kernels see it -- 4-byte words from the record's
+// start, in sections of equal-sized elements, widest first so that every element is aligned to its own size and a 16-byte quad
+// of the record never splits one: the host part (written on the host: zeros here), the amplitude ring's quads, the 8-byte
+// sections (fp64 RF_* words, 64-bit polyphase registers and their `undefined` masks), the 4-byte ones (fp32 RF_* words, IF_*
+// words, 32-bit polyphase registers), zeros up to a multiple of 16 bytes.
+enum SnapKind : uint32_t { SNAP_ZERO = 0, SNAP_RF, SNAP_IF, SNAP_POLY, SNAP_POLYU, SNAP_AMP };
+struct SnapSection {
+  uint32_t kind;
+  uint32_t w0;   // first word
+  uint32_t n;    // elements
+  uint32_t e;    // words per element: 1, 2 or 4
+};
+struct SnapLayout {
+  uint32_t rec_words;   // a multiple of 4
+  uint32_t d;           // polyphase registers per stream
+  uint32_t n_sec;
+  SnapSection sec[8];
+};
+static constexpr uint32_t kSnapHostWords = 12;   // the host part of a record (fsk_snapshot_api.hip SnapRecordHost)
+
 // FSKProcessor + ChunkedModulator per stream (fsk-processor.ts, chunked-modulator.ts), device resident.
 // The pending signal is kept as the modulator's generator state (payload + phase + position), not as samples:
 // a slice of n samples is produced on demand and is bit-identical to the same slice of modulateData()'s output

@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "fsk_dev.h"
+#include "fsk_newstream.h"
 #include "fsk_params.h"
 #include "fsk_launch.h"
 
@@ -30,55 +31,44 @@ __global__ __launch_bounds__(256) void remap_kernel(RemapArgs A, const int64_t *
   const uint32_t m = cont ? (uint32_t)mi : 0u;
   const size_t nd = A.n_dst, ns = A.n_src;
 
-  // ---- state words.  A new stream: configure() (fsk.ts:101-131, 175-188) as fsk_api.hip's init_kernel writes it, its ring
-  // positions on the engine's grid when the engine stays in lock step (a ring of length 0 reads nothing before it).
+  // ---- state words.  A new stream: fsk_newstream.h -- configure()'s values, its ring positions on the engine's grid when the
+  // engine stays in lock step (the source's row 0: every stream's, in lock step), and on fp32 engines of one shared
+  // configuration the free-running I/Q frame of a continued stream's source row, A.frame_row, whose config is dst's.
   // Eight loads in flight per lane before their stores (a batch of 65 536 streams is one wave per SIMD: latency-bound)
   const Real *__restrict__ srs = (const Real *)S.rs;
   Real *__restrict__ drs = (Real *)D.rs;
+  const uint32_t *__restrict__ sis = S.is;
+  uint32_t *__restrict__ dis = D.is;
+  NewStream NS{};
+  NS.matched_zero = A.matched_zero; NS.grid = A.grid_src; NS.frame = A.frame_src;
+  if (!cont && A.grid_src) { NS.poly_phase = sis[(size_t)IF_poly_phase * ns]; NS.amp_pos = sis[(size_t)IF_amp_pos * ns]; }
+  if (!cont && A.frame_src) {
+    const size_t r = A.frame_row;
+    NS.fr0 = frame_phase(sis[(size_t)IF_nco_lo * ns + r], sis[(size_t)IF_nco_hi * ns + r], sis[(size_t)IF_fr_lo * ns + r], sis[(size_t)IF_fr_hi * ns + r]);
+  }
   for (int f0 = 0; f0 < RF_COUNT; f0 += 8) {
     Real v[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
       const int f = f0 + k;
-      const Real init = (f == RF_agc_gain || f == RF_nco_c) ? (Real)1.0 : f == RF_sil_thr ? (Real)0.01 : (Real)0;
-      const Real x = f < RF_COUNT ? srs[(size_t)f * ns + m] : init;   // (loaded for a new stream too: m = 0, in range)
-      v[k] = cont ? x : init;
+      const Real x = f < RF_COUNT ? srs[(size_t)f * ns + m] : (Real)0;   // (loaded for a new stream too: m = 0, in range)
+      v[k] = cont ? x : new_stream_real<Real>(f, NS);
     }
 #pragma unroll
     for (int k = 0; k < 8; k++)
       if (f0 + k < RF_COUNT) drs[(size_t)(f0 + k) * nd + i] = v[k];
   }
-  const uint32_t *__restrict__ sis = S.is;
-  uint32_t *__restrict__ dis = D.is;
   for (int f0 = 0; f0 < IF_COUNT; f0 += 8) {
     uint32_t v[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
       const int f = f0 + k;
-      const bool grid = (f == IF_poly_phase || f == IF_amp_pos) && A.grid_src;   // (m = 0 for a new stream)
-      const uint32_t init = f == IF_matched ? A.matched_zero : f == IF_bit_wait ? kBigWait : f == IF_zr_dph ? kHandPairs : 0u;
-      const uint32_t x = f < IF_COUNT ? sis[(size_t)f * ns + m] : init;
-      v[k] = (cont || grid) ? x : init;
+      const uint32_t x = f < IF_COUNT ? sis[(size_t)f * ns + m] : 0u;
+      v[k] = cont ? x : new_stream_int(f, NS);
     }
 #pragma unroll
     for (int k = 0; k < 8; k++)
       if (f0 + k < IF_COUNT) dis[(size_t)(f0 + k) * nd + i] = v[k];
-  }
-
-  // fp32 engines of one shared configuration keep the I/Q low-pass in ONE free-running frame (fsk_pipe_dev.h pipe_free0: NCO
-  // phase minus frame offset, wave-uniform; taken from a continued stream's source row, A.frame_row, whose config is dst's):
-  // a new stream joins it as fskhip_reset places a stream there -- its NCO at 0, its
-  // frame offset minus the frame's phase, lastPhase = 0 expressed in the frame (fsk_api.hip reset_kernel)
-  if (!cont && A.frame_src) {
-    const size_t r = A.frame_row;
-    const uint64_t acc = ((uint64_t)sis[(size_t)IF_nco_hi * ns + r] << 32) | sis[(size_t)IF_nco_lo * ns + r];
-    const uint64_t off = ((uint64_t)sis[(size_t)IF_fr_hi * ns + r] << 32) | sis[(size_t)IF_fr_lo * ns + r];
-    const uint64_t fr0 = acc - off, noff = 0ull - fr0;
-    dis[(size_t)IF_fr_lo * nd + i] = (uint32_t)noff;
-    dis[(size_t)IF_fr_hi * nd + i] = (uint32_t)(noff >> 32);
-    double ph = (double)fr0 * 5.42101086242752217e-20 * 6.283185307179586476925;
-    ph = ph > 3.14159265358979323846 ? ph - 6.283185307179586476925 : ph;
-    drs[(size_t)RF_last_phase * nd + i] = (Real)ph;
   }
 
   // ---- polyphase sync registers (and the `undefined` masks of fractional capacities)

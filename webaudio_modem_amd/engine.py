@@ -94,6 +94,54 @@ def pinned_empty(shape, dtype=np.float32):
 
 _PINNED_OWNERS = {}
 
+_PARITY_NAME = {v: k for k, v in PARITY.items()}
+
+
+def _blob(blob):
+    """a snapshot as a contiguous uint8 array (bytes, bytearray, memoryview and numpy arrays are taken without a copy)"""
+    a = blob if isinstance(blob, np.ndarray) else np.frombuffer(blob, dtype=np.uint8)
+    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+
+
+def _config_dict(c):
+    """fskhip_config -> FSKConfig dict (every field, the reference's names)"""
+    return dict(sampleRate=c.sampleRate, baudRate=c.baudRate, markFrequency=c.markFrequency, spaceFrequency=c.spaceFrequency,
+                preamblePattern=list(c.preamblePattern)[:c.preambleLen], sfdPattern=list(c.sfdPattern)[:c.sfdLen],
+                startBits=c.startBits, stopBits=c.stopBits, parity=_PARITY_NAME[c.parity], syncThreshold=c.syncThreshold,
+                agcEnabled=bool(c.agcEnabled), preFilterBandwidth=c.preFilterBandwidth, adaptiveThreshold=bool(c.adaptiveThreshold))
+
+
+def snapshot_info(blob):
+    """fskhip_snapshot_info_get: what a stream snapshot holds (validated on the host, no device needed)"""
+    b = _blob(blob)
+    info = _lib.SnapshotInfo()
+    _lib.check(_lib.lib().fskhip_snapshot_info_get(b.ctypes.data, b.nbytes, C.byref(info)))
+    return {k: getattr(info, k) for k, _ in _lib.SnapshotInfo._fields_}
+
+
+def snapshot_stream_config(blob, i):
+    """fskhip_snapshot_stream_config: the FSKConfig dict record i of a snapshot ran under"""
+    b = _blob(blob)
+    c = Config()
+    _lib.check(_lib.lib().fskhip_snapshot_stream_config(b.ctypes.data, b.nbytes, int(i), C.byref(c)))
+    return _config_dict(c)
+
+
+def snapshot_concat(blobs):
+    """fskhip_snapshot_concat: one snapshot holding the records of `blobs` in order.  They must be images of engines that
+    could have been ONE engine (shards of a sharded batch, created together and fed the same calls); refused otherwise."""
+    bs = [_blob(b) for b in blobs]
+    L = _lib.lib()
+    ptrs = (C.c_void_p * len(bs))(*[b.ctypes.data for b in bs])
+    sizes = (C.c_size_t * len(bs))(*[b.nbytes for b in bs])
+    need = C.c_size_t(0)
+    rc = L.fskhip_snapshot_concat(ptrs, sizes, len(bs), None, 0, C.byref(need))
+    if rc != _lib.E_OVERFLOW:
+        _lib.check(rc)
+    out = np.zeros(need.value, np.uint8)
+    _lib.check(L.fskhip_snapshot_concat(ptrs, sizes, len(bs), out.ctypes.data, out.nbytes, C.byref(need)))
+    return out
+
 
 # Called with (n_streams, precision) by every new FSKEngine; returns a dict of fskhip_set_option() names -> values to apply on
 # top of the `options` argument, or None.  The package sets nothing here and reads no environment variable; the test suite
@@ -177,6 +225,54 @@ class FSKEngine:
         eng = FSKEngine(len(m), configs, device=self.device, precision=self.precision, options=options)
         try:
             eng.remap_from(self, m)
+        except Exception:
+            eng.close()
+            raise
+        return eng
+
+    # ---- stream snapshots (include/fskhip.h): a portable image of streams, restored under the remap's contract ----------
+    def snapshot(self, streams=None, out=None):
+        """fskhip_snapshot_streams: a numpy uint8 array holding streams `streams` of this engine (None: all, in order; a
+        stream may be named more than once) -- plain bytes, fit for a file.  The engine is read only and stays usable.
+        `out`: a uint8 array to write into (pinned_empty(...) makes the copy faster); a view of it is returned."""
+        sel = None if streams is None else np.ascontiguousarray(streams, dtype=np.int64).reshape(-1)
+        n = self.n_streams if sel is None else len(sel)
+        need = int(self._L.fskhip_snapshot_bytes(self._h, n))
+        buf = np.zeros(need, np.uint8) if out is None else out
+        if buf.dtype != np.uint8 or not buf.flags.c_contiguous:
+            raise ValueError("out must be a contiguous uint8 array")
+        w = C.c_size_t(0)
+        _lib.check(self._L.fskhip_snapshot_streams(self._h, None if sel is None else sel.ctypes.data, n, buf.ctypes.data, buf.nbytes, C.byref(w)))
+        return buf.reshape(-1)[:w.value]
+
+    def restore_from(self, blob, stream_map):
+        """fskhip_restore_streams: stream i of this (new, not yet demodulated) engine continues RECORD stream_map[i] of the
+        snapshot `blob` as if that FSKCore had been moved here, or starts afresh where stream_map[i] is -1."""
+        b = _blob(blob)
+        m = np.ascontiguousarray(stream_map, dtype=np.int64).reshape(-1)
+        _lib.check(self._L.fskhip_restore_streams(self._h, b.ctypes.data, b.nbytes, m.ctypes.data, len(m)))
+
+    @classmethod
+    def from_snapshot(cls, blob, stream_map=None, configs=None, device=0, options=None):
+        """A new engine on `device` that continues the records of a snapshot: stream i continues record stream_map[i] (-1: a
+        new FSKCore; None: every record, in order).  Precision and configs are read out of the snapshot unless `configs` is
+        given; a -1 slot needs an explicit config when the snapshot's configs are per stream."""
+        b = _blob(blob)
+        info = snapshot_info(b)
+        m = list(range(info["n_streams"])) if stream_map is None else [int(v) for v in np.asarray(stream_map, dtype=np.int64).reshape(-1)]
+        if configs is None:
+            if not info["per_stream_configs"]:
+                configs = snapshot_stream_config(b, 0)
+            else:
+                if any(v < 0 for v in m):
+                    raise ValueError("a -1 slot needs an explicit config: the snapshot has per-stream configs")
+                if any(v >= info["n_streams"] for v in m):
+                    raise ValueError("stream map entry out of range (%d records)" % info["n_streams"])
+                known = {}
+                configs = [known.setdefault(v, snapshot_stream_config(b, v)) for v in m]
+        eng = cls(len(m), configs, device=device, precision=info["precision"], options=options)
+        try:
+            eng.restore_from(b, m)
         except Exception:
             eng.close()
             raise

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PRECISION_F32
-from .engine import FSKEngine
+from .engine import FSKEngine, snapshot_concat, snapshot_info, snapshot_stream_config
 from .sharding import all_shards
 
 
@@ -39,6 +39,7 @@ class FSKEngineSharded:
         if isinstance(configs, (list, tuple)) and len(configs) != n_streams:
             raise ValueError("need one config per stream")
         make = engine_factory or (lambda count, cfg, dev, prec: FSKEngine(count, cfg, device=dev, precision=prec))
+        self._factory = engine_factory
         self.n_streams = n_streams
         self.precision = precision
         self.devices = devices
@@ -93,6 +94,46 @@ class FSKEngineSharded:
         if err is not None:
             raise err
         return results
+
+    # ---- stream snapshots: checkpoint, grow, shrink and rebalance a sharded batch (include/fskhip.h) -------------------
+    # These need engines that implement snapshot() / restore_from(): real FSKEngines, or an engine_factory stand-in that has
+    # the two methods (stand-ins without them keep serving every other method).
+    def snapshot(self):
+        """One snapshot of the whole batch, records in global stream order: every shard's snapshot, concatenated
+        (fskhip_snapshot_concat: the shards were created together and fed the same calls, so they are images of what could
+        have been one engine)."""
+        parts = self._fan_out(lambda i, e, first, count: e.snapshot())
+        return parts[0] if len(parts) == 1 else snapshot_concat(parts)
+
+    @classmethod
+    def from_snapshot(cls, blob, stream_map=None, configs=None, devices=None, engine_factory=None):
+        """A new sharded batch whose stream i continues record stream_map[i] of the snapshot (-1: a new FSKCore; None: every
+        record in order), spread over `devices`: every shard restores its slice of the map from the one blob.  Precision and
+        configs come from the snapshot unless `configs` is given (a -1 slot needs one when the snapshot's are per stream)."""
+        info = snapshot_info(blob)
+        m = np.arange(info["n_streams"], dtype=np.int64) if stream_map is None else np.asarray(stream_map, dtype=np.int64).reshape(-1)
+        if configs is None:
+            if not info["per_stream_configs"]:
+                configs = snapshot_stream_config(blob, 0)
+            else:
+                if (m < 0).any():
+                    raise ValueError("a -1 slot needs an explicit config: the snapshot has per-stream configs")
+                known = {}
+                configs = [known.setdefault(int(v), snapshot_stream_config(blob, int(v))) for v in m]
+        new = cls(len(m), configs, devices=devices, precision=info["precision"], engine_factory=engine_factory)
+        try:
+            new._fan_out(lambda i, e, first, count: e.restore_from(blob, m[first:first + count]))
+        except Exception:
+            new.close()
+            raise
+        return new
+
+    def remapped(self, stream_map, configs=None, devices=None):
+        """A new sharded batch of len(stream_map) streams on `devices` (default: this batch's) whose stream i continues
+        GLOBAL stream stream_map[i] of this one, or starts as a new FSKCore where it is -1 -- across shards and devices: the
+        state goes through one host-side snapshot.  This batch is left as it is (close it when the new one has taken over)."""
+        return type(self).from_snapshot(self.snapshot(), stream_map, configs=configs, devices=self.devices if devices is None else devices,
+                                        engine_factory=self._factory)
 
     # ---- demodulateData / modulateData (fsk.ts:190-222, 377-424) ---------------------------------
     def demodulate_data(self, samples, writeback_agc=False):
