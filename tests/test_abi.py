@@ -196,7 +196,8 @@ def test_time_sliced_launches_hand_every_field_on_with_device_scope_policy():
     src = open(os.path.join(ROOT, "webaudio_modem_amd", "csrc", "fsk_blk.hip"), encoding="utf-8").read()
     assert "constexpr int COH = SL ? kCohSc1 : 0;" in src
     src = re.sub(r"//[^\n]*", "", src)          # (code only)
-    helpers = ["pipe_free0", "front_load", "back_load", "back_pair", "pipe_store", "ist_load", "ist_store", "back_reset"]
+    helpers = ["pipe_free0", "front_load", "back_load", "back_pair", "pipe_store", "ist_load", "ist_store", "back_reset",
+               "front_store"]
     for h in helpers:
         for m in re.finditer(r"\b%s\s*(<[^>(]*>)?\s*\(" % h, src):
             targs = m.group(1) or ""
@@ -208,6 +209,12 @@ def test_time_sliced_launches_hand_every_field_on_with_device_scope_policy():
     # the helpers that reach state through other helpers pass it down
     for inner in ("ist_store<COH>", "ist_load<COH>", "back_reset<UNI, COH>"):
         assert inner in dev, inner
+    # front_store (fsk_tile_dev.h) reaches state through the PIPE_* macros alone, under a COH of its own
+    tile = open(os.path.join(ROOT, "webaudio_modem_amd", "csrc", "fsk_tile_dev.h"), encoding="utf-8").read()
+    tile = re.sub(r"//[^\n]*", "", tile)
+    assert re.search(r"template <int COH>\s*__device__ __forceinline__ void front_store\(", tile)
+    assert "front_store<COH>(F, C)" in src
+    assert "raw_buffer_" not in tile and "__hip_atomic" not in tile
 
 
 def test_no_bit_cast_of_a_vector_element_expression():

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Static check of the compiled whole-tile demod kernels of fsk_pipe.hip and fsk_blk.hip (runs anywhere hipcc is installed, no GPU):
+"""Static check of the compiled whole-tile demod kernels of fsk_pipe.hip, fsk_blk.hip and fsk_blk6.hip (runs anywhere hipcc is
+installed, no GPU):
 the one-wave kernel's tile prefetch uses inline-asm loads whose results are only valid after a hand-placed s_waitcnt, so
 the register allocator must never spill inside that kernel (a spill store of an in-flight load result
 would save garbage); the one-wave kernel must fit 168 VGPRs (3 waves per SIMD), the two-wave kernel 128."""
@@ -11,14 +12,31 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXTRA = os.environ.get("FSK_CHECK_ISA_FLAGS", "").split()   # a measurement build's extra hipcc flags (tools/build_variant.sh)
+# csrc/Makefile's CXXFLAGS (less its warning switches) and the -fno-slp-vectorize it adds for these three files
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize"]
+_compiled = {}
+
+
+def _compile(src, mode):
+    """One hipcc run of csrc/<src> per process and mode: "asm" returns the device assembly, "resources" the compiler's
+    kernel-resource-usage remarks."""
+    if (src, mode) not in _compiled:
+        path = os.path.join(ROOT, "webaudio_modem_amd", "csrc", src)
+        with tempfile.TemporaryDirectory() as tmp:
+            cmd = ["/opt/rocm/bin/hipcc", *FLAGS, *EXTRA]
+            if mode == "asm":
+                out = os.path.join(tmp, "d.s")
+                subprocess.run(cmd + ["-S", "--cuda-device-only", "-o", out, path], capture_output=True, text=True, check=True)
+                _compiled[src, mode] = open(out).read()
+            else:
+                run = subprocess.run(cmd + ["-c", path, "-o", os.path.join(tmp, "d.o"), "-Rpass-analysis=kernel-resource-usage"],
+                                     capture_output=True, text=True, check=True)
+                _compiled[src, mode] = run.stderr
+    return _compiled[src, mode]
 
 
 def kernel_resources():
-    src = os.path.join(ROOT, "webaudio_modem_amd", "csrc", "fsk_pipe.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize", *EXTRA,
-               "-c", src, "-o", os.path.join(tmp, "d.o"), "-Rpass-analysis=kernel-resource-usage"]
-        out = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
+    out = _compile("fsk_pipe.hip", "resources")
     res, cur = {}, None
     for line in out.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
@@ -37,12 +55,7 @@ def prefetch_register_hazards():
     destination VGPRs must not be touched.  Returns a list of violations found in the fast kernels' ISA:
     any instruction after the in-loop prefetch that uses those registers without an `s_waitcnt vmcnt(0)` (the
     epilogue) or the loop-top `s_waitcnt vmcnt(8)` + ds_write (the next iteration) in between."""
-    src = os.path.join(ROOT, "webaudio_modem_amd", "csrc", "fsk_pipe.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "d.s")
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize", *EXTRA,
-                        "-S", "--cuda-device-only", "-o", asm, src], capture_output=True, text=True, check=True)
-        text = open(asm).read()
+    text = _compile("fsk_pipe.hip", "asm")
 
     def regs_of(line):
         out = set()
@@ -109,12 +122,7 @@ def pipe_prefetch_hazards(symbol=r"_ZN3fsk17demod_pipe_kernel"):
     three register sets of asm-issued tile loads in flight (unrolled by three).
     In its tile loop (everything after the prologue's `s_waitcnt vmcnt(0)` up to the epilogue's) a register of a set may
     only be read after the `s_waitcnt vmcnt(N)` placed in front of that set's ds_write_b128 staging, and only by it."""
-    src = os.path.join(ROOT, "webaudio_modem_amd", "csrc", "fsk_pipe.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "d.s")
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize", *EXTRA,
-                        "-S", "--cuda-device-only", "-o", asm, src], capture_output=True, text=True, check=True)
-        text = open(asm).read()
+    text = _compile("fsk_pipe.hip", "asm")
 
     def regs_of(line):
         out = set()
@@ -170,12 +178,7 @@ def blk_checks():
     per-sample slow path; the loops that run per tile must not: every block of the innermost loop around each of the four
     parts' asynchronous counter read (lds_peek4_begin: an asm ds_read_b128) has to be free of scratch instructions.  And
     the registers that read lands in must not be touched before a wait that covers it (lgkmcnt(0))."""
-    src = os.path.join(ROOT, "webaudio_modem_amd", "csrc", "fsk_blk.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "d.s")
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize", *EXTRA,
-                        "-S", "--cuda-device-only", "-o", asm, src], capture_output=True, text=True, check=True)
-        text = open(asm).read()
+    text = _compile("fsk_blk.hip", "asm")
 
     def regs_of(line):
         out = set()
@@ -266,11 +269,7 @@ def blk6_resources():
     """fsk_blk6.hip (seven waves per group, one workgroup per CU): eight kernel bodies <write-back, group width>, each within the
     256 VGPRs two waves per SIMD leave a wave, none with scratch memory (its frame wave keeps a register copy of the lane state
     where the four-wave kernel parks it in memory)."""
-    src = os.path.join(ROOT, "webaudio_modem_amd", "csrc", "fsk_blk6.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize", *EXTRA,
-               "-c", src, "-o", os.path.join(tmp, "d.o"), "-Rpass-analysis=kernel-resource-usage"]
-        out = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
+    out = _compile("fsk_blk6.hip", "resources")
     res, cur = {}, None
     for line in out.splitlines():
         m = re.search(r"Function Name: (\S+)", line)

@@ -419,21 +419,14 @@ __device__ __forceinline__ void demod_blk_body(
     const uint32_t in_voff = (uint32_t)((sub_row * pitch + 4u * chunk) * 4u);
     const uint32_t in_row16 = (uint32_t)(16u * pitch * 4u);
     const uint32_t st_slot = chunk * kSlotStride + sub_row;
-    // tile prefetch exactly as in demod_pipe_kernel (three register sets, hand-counted waits)
-#define BLK_BLOAD4(dst, rows16, soff)                                                                       \
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(in_voff + (rows16) * in_row16), \
-               "s"(in_rsrc), "s"(soff) : "memory")
-    auto load_tile = [&](size_t t, v4f &a, v4f &b, v4f &c, v4f &d) {
-      const uint32_t tn = (uint32_t)((t_begin + (t < n_tiles ? t : n_tiles - 1)) * kFastTile * 4u);
-      BLK_BLOAD4(a, 0u, tn); BLK_BLOAD4(b, 1u, tn); BLK_BLOAD4(c, 2u, tn); BLK_BLOAD4(d, 3u, tn);
-    };
+    // the tile prefetch of fsk_tile_dev.h, the same code as demod_pipe_kernel's; a time slice's tiles begin at tile t_begin of the call
+    auto load_tile = [&](size_t t, v4f &a, v4f &b, v4f &c, v4f &d) { tile_load(in_rsrc, in_voff, in_row16, t, n_tiles, t_begin, a, b, c, d); };
     v4f a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3;
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the state loads above are complete, the count starts clean
     load_tile(0, a0, a1, a2, a3);
     load_tile(1, b0, b1, b2, b3);
     load_tile(2, c0, c1, c2, c3);
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3),
-                 "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3) : : "memory");
+    tile_fence(a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3);
     uint32_t consumed = 0, slot_i = 0;
     // NCO phasors of the free-running frame (uniform configuration): lane j & 15 evaluates sample j of the tile from the
     // exact accumulator (v_cos / v_sin take turns), the sixteen (cos, sin) pairs go to the tile's zt slot and wave 1 reads
@@ -441,9 +434,7 @@ __device__ __forceinline__ void demod_blk_body(
     uint64_t zacc = free0 + inc * (uint64_t)(lane & 15u);
     const uint64_t inc16 = inc * 16u;
     auto do_tile = [&](uint32_t t, v4f &r0, v4f &r1, v4f &r2, v4f &r3) {
-      if (WB) asm volatile("s_waitcnt vmcnt(16)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) : : "memory");
-      else asm volatile("s_waitcnt vmcnt(8)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) : : "memory");
-      stage[st_slot] = r0; stage[st_slot + 16] = r1; stage[st_slot + 32] = r2; stage[st_slot + 48] = r3;
+      tile_stage<WB>(stage, st_slot, r0, r1, r2, r3);
       load_tile((size_t)t + 3, r0, r1, r2, r3);
       const uint32_t hidx = 2u * t;
       v4u32 cv;
@@ -496,16 +487,8 @@ __device__ __forceinline__ void demod_blk_body(
       }
     }
     FSK_STAMP_END(0)
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3),
-                 "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3) : : "memory");
-#undef BLK_BLOAD4
-    {
-      const __amdgpu_buffer_rsrc_t rs_rsrc = C.rs_rsrc;
-      const FastMem &M = C.M;
-      const uint32_t fld = C.fld;
-      PIPE_RSTORE(agc_gain, F.g);
-      PIPE_RSTORE(bp_x1, F.bx1); PIPE_RSTORE(bp_x2, F.bx2); PIPE_RSTORE(bp_y1, F.by1); PIPE_RSTORE(bp_y2, F.by2);
-    }
+    tile_fence(a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3);   // (the last prefetches are still in flight)
+    front_store<COH>(F, C);
   } else if (role == 1) {
     // ------------------------------------------------------------------------------ mixer, I/Q low-pass, pair sums
     FrontLane F;
@@ -726,8 +709,7 @@ __device__ __forceinline__ void demod_blk_body(
     BackK Ks;                                                 // the constants as scalars, for the paths that are not the fast block loop
     back_consts(Ks, P);
     if (B.dph >= kOwnPairs4) { B.qai = 0.f; B.qaq = 0.f; B.qbi = 0.f; B.qbq = 0.f; B.dph = kOwnPairs4; }   // the discriminator wave's (zr_dph is re-formed at the end)
-    BlkK Qs;
-    Qs.stop_m1 = (1u << P.stop_pos) - 1u; Qs.sh9 = P.stop_pos - 9u; Qs.ff = 0xFFu;
+    const BlkK Qs = blk_consts(P);
     BlkK Qp = Qs;
     if (!MED) asm volatile("" : "+v"(Qp.stop_m1), "+v"(Qp.sh9), "+v"(Qp.ff));
     const FastMem &M = C.M;
@@ -753,10 +735,10 @@ __device__ __forceinline__ void demod_blk_body(
     X.amp_soff = amp_soff_of(amp_pos0, amp_quad_bytes);
     const uint32_t amp_wrap = (P.amp_cap >> 2) * amp_quad_bytes;
     // the block path stores a tile's amplitudes as two whole quads: the launch must start on a quad boundary (it does
-    // unless earlier calls had odd lengths; the host then launches the per-sample kernels, fsk_api.hip) -- otherwise every
+    // unless earlier calls had odd lengths; the host then launches the per-sample kernels, fsk_dispatch.hip) -- otherwise every
     // block takes the per-sample path
     const bool amp_misaligned = (amp_pos0 & 3u) != 0u;
-    const __amdgpu_buffer_rsrc_t amp_rsrc = __builtin_amdgcn_make_buffer_rsrc(S.amp_ring, 0, (int)amp_wrap, 0x00020000);
+    const __amdgpu_buffer_rsrc_t amp_rsrc = amp_ring_rsrc(S, amp_wrap);
     const __amdgpu_buffer_rsrc_t stash_rsrc = __builtin_amdgcn_make_buffer_rsrc(S.blk_stash, 0, (int)(7u * amp_quad_bytes), 0x00020000);
     uint32_t produced = 0, slot_i = 0;                        // (x-ring slot of half tile t; even wherever a block starts)
     uint32_t pidx = 0;                                        // LDS index of the block's first polyphase register

@@ -758,8 +758,7 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
     back_load<UNI, 0>(B, K, P, S, C, stream, out_counts, eod_counts, append);
     if (B.dph >= kHandPairs) { B.qai = 0.f; B.qaq = 0.f; B.qbi = 0.f; B.qbq = 0.f; }   // the discriminator wave's
     if (!C.valid) { B.px1 = B.px2 = B.py = B.pv = 0.f; B.last_phase = 0.f; B.thf = 0.f; }   // (see `trash`)
-    BlkK Q;
-    Q.stop_m1 = (1u << P.stop_pos) - 1u; Q.sh9 = P.stop_pos - 9u; Q.ff = 0xFFu;
+    BlkK Q = blk_consts(P);
     asm volatile("" : "+v"(Q.stop_m1), "+v"(Q.sh9), "+v"(Q.ff));
     const FastMem &M = C.M;
     const uint32_t fld = C.fld, row4 = C.row4;
@@ -784,7 +783,7 @@ __global__ __launch_bounds__(64 * kB6Waves, 1) void demod_blk6_kernel(
     X.amp_soff = amp_soff_of(amp_pos0, amp_quad_bytes);
     const uint32_t amp_wrap = (P.amp_cap >> 2) * amp_quad_bytes;
     const bool amp_misaligned = (amp_pos0 & 3u) != 0u;
-    const __amdgpu_buffer_rsrc_t amp_rsrc = __builtin_amdgcn_make_buffer_rsrc(S.amp_ring, 0, (int)amp_wrap, 0x00020000);
+    const __amdgpu_buffer_rsrc_t amp_rsrc = amp_ring_rsrc(S, amp_wrap);
     uint32_t slot_t = 0;                                      // x / f ring tile of half tile t
     uint32_t pidx = 0;
     uint32_t bq = 0, nq = 0;

@@ -8,6 +8,7 @@
 #include "fsk_params.h"
 #include "fsk_dev.h"
 #include "fsk_pipe_dev.h"
+#include "fsk_tile_dev.h"
 
 namespace fsk {
 
@@ -46,6 +47,12 @@ struct BlkK {                    // block-level constants, VGPRs
   uint32_t sh9;                  // stop_pos - 9: byte = (sreg >> sh9) & 0xFF
   uint32_t ff;                   // 0xFF
 };
+// (as the parameters give them: scalars, pinned into VGPRs by the caller where its hot loop wants them there -- see back_consts)
+__device__ __forceinline__ BlkK blk_consts(const DemodParams &P) {
+  BlkK Q;
+  Q.stop_m1 = (1u << P.stop_pos) - 1u; Q.sh9 = P.stop_pos - 9u; Q.ff = 0xFFu;
+  return Q;
+}
 
 // Bit clock of one block (fsk.ts:335-341) and processByte (346-375), evaluated once from the block's eight slicer bits w
 // (sample 1 in bit kBlk - 1): a lane decides at most one bit per block, at sample jd = nextBitSampleIndex - k0.  Shared by

@@ -55,6 +55,7 @@
 #include "fsk_params.h"
 #include "fsk_dev.h"
 #include "fsk_pipe_dev.h"
+#include "fsk_tile_dev.h"
 #include "fsk_launch.h"
 
 namespace fsk {
@@ -127,28 +128,14 @@ __global__ __launch_bounds__(128) void demod_pipe_kernel(
     const uint32_t in_voff = (uint32_t)((sub_row * pitch + 4u * chunk) * 4u);
     const uint32_t in_row16 = (uint32_t)(16u * pitch * 4u);
     const uint32_t st_slot = chunk * kSlotStride + sub_row;
-    // Three tiles in flight, in three register sets used in turn (the loop is unrolled by three so that no set is ever
-    // copied).  The loads are inline asm with hand-counted waits, as in demod_fused_kernel: vmcnt counts in issue order
-    // and hipcc, which cannot see across the loop's back edge, would drain everything (vmcnt(0)) at the top of every
-    // iteration.  When a set is staged, the two sets issued after it (8 loads) may still be in flight, plus this wave's
-    // write-back stores of the two tiles in between (4 each) in the write-back variant.
-    // (rows beyond the batch read as 0: the row step rides in the bounds-checked VGPR offset)
-#define PIPE_BLOAD4(dst, rows16, soff)                                                                      \
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(in_voff + (rows16) * in_row16), \
-               "s"(in_rsrc), "s"(soff) : "memory")
-    auto load_tile = [&](size_t t, v4f &a, v4f &b, v4f &c, v4f &d) {
-      const uint32_t tn = (uint32_t)((t < n_tiles ? t : n_tiles - 1) * kFastTile * 4u);
-      PIPE_BLOAD4(a, 0u, tn); PIPE_BLOAD4(b, 1u, tn); PIPE_BLOAD4(c, 2u, tn); PIPE_BLOAD4(d, 3u, tn);
-    };
+    // three tiles in flight: the tile prefetch of fsk_tile_dev.h
+    auto load_tile = [&](size_t t, v4f &a, v4f &b, v4f &c, v4f &d) { tile_load(in_rsrc, in_voff, in_row16, t, n_tiles, 0u, a, b, c, d); };
     v4f a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3;
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the state loads above are complete, the count starts clean
     load_tile(0, a0, a1, a2, a3);
     load_tile(1, b0, b1, b2, b3);
     load_tile(2, c0, c1, c2, c3);
-    // the loop may receive the three sets in other registers than these loads were issued into: any such copy must see
-    // landed data (inside the loop tools/check_isa.py proves that nothing touches a set between issue and its wait)
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3),
-                 "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3) : : "memory");
+    tile_fence(a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3);
     // NCO phasors (uniform configuration): lane j & 15 evaluates sample j of the tile from the exact accumulator, the
     // sixteen (cos, sin) pairs are parked in LDS and read back as broadcasts
     uint64_t zacc = free0 + inc * (uint64_t)(lane & 15u);     // this lane's sample of the current tile (UNI)
@@ -156,9 +143,7 @@ __global__ __launch_bounds__(128) void demod_pipe_kernel(
     const uint64_t inc16 = inc * 16u;
     uint32_t consumed = 0, slot_i = 0;
     auto do_tile = [&](uint32_t t, v4f &r0, v4f &r1, v4f &r2, v4f &r3) {
-      if (WB) asm volatile("s_waitcnt vmcnt(16)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) : : "memory");
-      else asm volatile("s_waitcnt vmcnt(8)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) : : "memory");
-      stage[st_slot] = r0; stage[st_slot + 16] = r1; stage[st_slot + 32] = r2; stage[st_slot + 48] = r3;
+      tile_stage<WB>(stage, st_slot, r0, r1, r2, r3);
       load_tile((size_t)t + 3, r0, r1, r2, r3);
       const v4f *ztile = zt + (t & 1u) * 8u;
       float zr = 1.f, zi = 0.f;
@@ -248,21 +233,12 @@ __global__ __launch_bounds__(128) void demod_pipe_kernel(
       if (t + 2 < nt) do_tile(t + 2, c0, c1, c2, c3);
     }
     FSK_STAMP_END(0)
-    // the last prefetches are still in flight and their registers are dead to the compiler: keep them until they land
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3),
-                 "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3) : : "memory");
-#undef PIPE_BLOAD4
+    tile_fence(a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3);   // (the last prefetches are still in flight)
     // hand the final I/Q filter state to the back wave, which owns the epilogue
     fin[lane] = (v4f){F.ix1, F.ix2, F.iy, F.iv};
     fin[64u + lane] = (v4f){F.qx1, F.qx2, F.qy, F.qv};
     lds_post(&ctr[0], 2u * nt + 1u);
-    {
-      const __amdgpu_buffer_rsrc_t rs_rsrc = C.rs_rsrc;
-      const FastMem &M = C.M;
-      const uint32_t fld = C.fld;
-      PIPE_RSTORE(agc_gain, F.g);
-      PIPE_RSTORE(bp_x1, F.bx1); PIPE_RSTORE(bp_x2, F.bx2); PIPE_RSTORE(bp_y1, F.by1); PIPE_RSTORE(bp_y2, F.by2);
-    }
+    front_store<COH>(F, C);
   } else {
     // ---------------------------------------------------------------------------------------------- back
     BackLane B;
@@ -282,7 +258,7 @@ __global__ __launch_bounds__(128) void demod_pipe_kernel(
     const uint32_t amp_quad_bytes = P.n_streams * 16u;
     X.amp_soff = amp_soff_of(amp_pos0, amp_quad_bytes);
     const uint32_t amp_wrap = (P.amp_cap >> 2) * amp_quad_bytes;
-    const __amdgpu_buffer_rsrc_t amp_rsrc = __builtin_amdgcn_make_buffer_rsrc(S.amp_ring, 0, (int)amp_wrap, 0x00020000);
+    const __amdgpu_buffer_rsrc_t amp_rsrc = amp_ring_rsrc(S, amp_wrap);
     uint32_t produced = 0, slot_i = 0;
     const uint32_t nh = 2u * (uint32_t)n_tiles;             // half tiles
     FSK_STAMP_BEGIN
@@ -385,7 +361,7 @@ __global__ __launch_bounds__(64, 3) void demod_fused_kernel(
   const uint32_t amp_quad_bytes = P.n_streams * 16u;
   X.amp_soff = amp_soff_of(amp_pos0, amp_quad_bytes);
   const uint32_t amp_wrap = (P.amp_cap >> 2) * amp_quad_bytes;
-  const __amdgpu_buffer_rsrc_t amp_rsrc = __builtin_amdgcn_make_buffer_rsrc(S.amp_ring, 0, (int)amp_wrap, 0x00020000);
+  const __amdgpu_buffer_rsrc_t amp_rsrc = amp_ring_rsrc(S, amp_wrap);
 
   // tile prefetch as in the r01 kernel: inline-asm loads with a hand-counted vmcnt (each tile issues at least 8
   // VMEM operations after its prefetch -- the unconditional ring stores -- so vmcnt(8) retires exactly the loads)
@@ -542,7 +518,7 @@ __global__ __launch_bounds__(64, 2) void demod_tail_kernel(
   const uint32_t amp_quad_bytes = P.n_streams * 16u;
   X.amp_soff = amp_soff_of(amp_pos0, amp_quad_bytes);
   const uint32_t amp_wrap = (P.amp_cap >> 2) * amp_quad_bytes;
-  const __amdgpu_buffer_rsrc_t amp_rsrc = __builtin_amdgcn_make_buffer_rsrc(S.amp_ring, 0, (int)amp_wrap, 0x00020000);
+  const __amdgpu_buffer_rsrc_t amp_rsrc = amp_ring_rsrc(S, amp_wrap);
   float acc_i = parity0 ? PIPE_RLOAD(acc_i) : 0.f, acc_q = parity0 ? PIPE_RLOAD(acc_q) : 0.f;
   float *xrow = samples + (size_t)(C.row4 >> 2) * pitch;
 
