@@ -35,10 +35,10 @@ def _compile(src, mode):
     return _compiled[src, mode]
 
 
-def kernel_resources():
-    out = _compile("fsk_pipe.hip", "resources")
+def _resources(src):
+    """The compiler's resource remarks of csrc/<src>: {kernel symbol: {remark: value}}."""
     res, cur = {}, None
-    for line in out.splitlines():
+    for line in _compile(src, "resources").splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             cur = m.group(1)
@@ -50,20 +50,26 @@ def kernel_resources():
     return res
 
 
+def kernel_resources():
+    return _resources("fsk_pipe.hip")
+
+
+def regs_of(line):
+    """The VGPR numbers an ISA line names (v7, v[4:7])."""
+    out = set()
+    for m in re.finditer(r"v\[(\d+):(\d+)\]", line):
+        out |= set(range(int(m.group(1)), int(m.group(2)) + 1))
+    for m in re.finditer(r"\bv(\d+)\b", line):
+        out.add(int(m.group(1)))
+    return out
+
+
 def prefetch_register_hazards():
     """The asm-issued tile prefetch lands asynchronously: between its issue and a vmcnt wait that covers it the
     destination VGPRs must not be touched.  Returns a list of violations found in the fast kernels' ISA:
     any instruction after the in-loop prefetch that uses those registers without an `s_waitcnt vmcnt(0)` (the
     epilogue) or the loop-top `s_waitcnt vmcnt(8)` + ds_write (the next iteration) in between."""
     text = _compile("fsk_pipe.hip", "asm")
-
-    def regs_of(line):
-        out = set()
-        for m in re.finditer(r"v\[(\d+):(\d+)\]", line):
-            out |= set(range(int(m.group(1)), int(m.group(2)) + 1))
-        for m in re.finditer(r"\bv(\d+)\b", line):
-            out.add(int(m.group(1)))
-        return out
 
     problems = []
     found = list(re.finditer(r"^(_ZN3fsk18demod_fused_kernel\w+):[^\n]*\n", text, re.M))
@@ -124,14 +130,6 @@ def pipe_prefetch_hazards(symbol=r"_ZN3fsk17demod_pipe_kernel"):
     only be read after the `s_waitcnt vmcnt(N)` placed in front of that set's ds_write_b128 staging, and only by it."""
     text = _compile("fsk_pipe.hip", "asm")
 
-    def regs_of(line):
-        out = set()
-        for m in re.finditer(r"v\[(\d+):(\d+)\]", line):
-            out |= set(range(int(m.group(1)), int(m.group(2)) + 1))
-        for m in re.finditer(r"\bv(\d+)\b", line):
-            out.add(int(m.group(1)))
-        return out
-
     problems = []
     found = list(re.finditer(r"^(" + symbol + r"\w+):[^\n]*\n", text, re.M))
     if len(found) != 4:
@@ -179,14 +177,6 @@ def blk_checks():
     parts' asynchronous counter read (lds_peek4_begin: an asm ds_read_b128) has to be free of scratch instructions.  And
     the registers that read lands in must not be touched before a wait that covers it (lgkmcnt(0))."""
     text = _compile("fsk_blk.hip", "asm")
-
-    def regs_of(line):
-        out = set()
-        for m in re.finditer(r"v\[(\d+):(\d+)\]", line):
-            out |= set(range(int(m.group(1)), int(m.group(2)) + 1))
-        for m in re.finditer(r"\bv(\d+)\b", line):
-            out.add(int(m.group(1)))
-        return out
 
     problems = []
     # (round 4: plus the four bodies of demod_blk_kernel_r<write-back, time-sliced>, the kernel whose block path takes resets)
@@ -269,19 +259,8 @@ def blk6_resources():
     """fsk_blk6.hip (seven waves per group, one workgroup per CU): eight kernel bodies <write-back, group width>, each within the
     256 VGPRs two waves per SIMD leave a wave, none with scratch memory (its frame wave keeps a register copy of the lane state
     where the four-wave kernel parks it in memory)."""
-    out = _compile("fsk_blk6.hip", "resources")
-    res, cur = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
-        if m and cur:
-            res[cur][m.group(1)] = int(m.group(2))
     problems = []
-    k6 = {k: v for k, v in res.items() if "demod_blk6_kernel" in k}
+    k6 = {k: v for k, v in _resources("fsk_blk6.hip").items() if "demod_blk6_kernel" in k}
     if len(k6) != 16:     # <write-back, streams per workgroup, uniform> (round 6: per-stream tone pairs too)
         problems.append(("demod_blk6_kernel", "expected 16 kernel bodies, found %d" % len(k6)))
     for k, v in k6.items():

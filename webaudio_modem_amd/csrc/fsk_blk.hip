@@ -1045,31 +1045,24 @@ size_t demod_blk_lds_bytes(const DemodParams &P) { return demod_blk_lds_bytes(P,
 // dsSPB * 1.1 in doubles, is an integer -- fsk_api.hip)
 bool demod_blk_applicable(const DemodParams &P) { return P.d >= 8u && (P.d & 3u) == 0u && !P.wide && !P.frac; }
 
+// Every instantiation, once, in blk_index()'s order: the plain kernel <write-back, uniform, time-sliced>, then the two whose block
+// path takes resets <write-back, time-sliced> -- _r uniform, _rp per-stream tone pairs.
+typedef void (*BlkFn)(DemodParams, DemodState, float *, size_t, size_t, int, uint8_t *, size_t, uint32_t *, uint32_t *, BlkSched);
+static const KernelEntry<BlkFn> kBlkKernels[16] = {
+    FSK_K(demod_blk_kernel, false, false, false), FSK_K(demod_blk_kernel, false, true, false), FSK_K(demod_blk_kernel, true, false, false),
+    FSK_K(demod_blk_kernel, true, true, false),   FSK_K(demod_blk_kernel, false, false, true), FSK_K(demod_blk_kernel, false, true, true),
+    FSK_K(demod_blk_kernel, true, false, true),   FSK_K(demod_blk_kernel, true, true, true),
+    FSK_K(demod_blk_kernel_r, false, false),      FSK_K(demod_blk_kernel_r, false, true),      FSK_K(demod_blk_kernel_r, true, false),
+    FSK_K(demod_blk_kernel_r, true, true),        FSK_K(demod_blk_kernel_rp, false, false),    FSK_K(demod_blk_kernel_rp, false, true),
+    FSK_K(demod_blk_kernel_rp, true, false),      FSK_K(demod_blk_kernel_rp, true, true)};
+static uint32_t blk_index(bool writeback, bool uni, bool sliced, bool medium) {
+  return medium ? (uni ? 8u : 12u) + (writeback ? 2u : 0u) + (sliced ? 1u : 0u) : (sliced ? 4u : 0u) + (writeback ? 2u : 0u) + (uni ? 1u : 0u);
+}
+
 hipError_t set_blk_lds_limit(const DemodParams &P) {
-  hipError_t e = hipSuccess;
   if (demod_blk_lds_bytes(P) > 160 * 1024) return hipSuccess;
-  size_t bytes = demod_blk_lds_bytes(P, kBlkYMax);          // (every launch: y_slots is at most kBlkYMax)
-  bytes = bytes > 160 * 1024 ? 160 * 1024 : bytes;
-#define FSK_ATTR(WBV, UNIV, SLV)                                                                                 \
-  if (e == hipSuccess)                                                                                           \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&demod_blk_kernel<WBV, UNIV, SLV>),                  \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  FSK_ATTR(false, false, false) FSK_ATTR(false, true, false) FSK_ATTR(true, false, false) FSK_ATTR(true, true, false)
-  FSK_ATTR(false, false, true) FSK_ATTR(false, true, true) FSK_ATTR(true, false, true) FSK_ATTR(true, true, true)
-#undef FSK_ATTR
-#define FSK_ATTR(WBV, SLV)                                                                                       \
-  if (e == hipSuccess)                                                                                           \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&demod_blk_kernel_r<WBV, SLV>),                      \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  FSK_ATTR(false, false) FSK_ATTR(false, true) FSK_ATTR(true, false) FSK_ATTR(true, true)
-#undef FSK_ATTR
-#define FSK_ATTR(WBV, SLV)                                                                                       \
-  if (e == hipSuccess)                                                                                           \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&demod_blk_kernel_rp<WBV, SLV>),                     \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  FSK_ATTR(false, false) FSK_ATTR(false, true) FSK_ATTR(true, false) FSK_ATTR(true, true)
-#undef FSK_ATTR
-  return e;
+  const size_t bytes = demod_blk_lds_bytes(P, kBlkYMax);    // (every launch: y_slots is at most kBlkYMax)
+  return set_lds_limit(kBlkKernels, bytes > 160 * 1024 ? 160 * 1024 : bytes);
 }
 
 // How to launch a batch of `groups` on `device`: the y ring as deep as the LDS allows while every CU still holds its
@@ -1081,7 +1074,7 @@ void demod_blk_plan(const DemodParams &P, uint32_t groups, int device, uint32_t 
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) return;
   auto held = [&](uint32_t y) {
     int per_cu = 0;
-    const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(&demod_blk_kernel<false, true, true>), 256,
+    const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kBlkKernels[blk_index(false, true, true, false)].fn), 256,
                                                                        demod_blk_lds_bytes(P, y));
     if (oe != hipSuccess) return 0u;
     return per_cu > 0 ? (uint32_t)per_cu : 0u;
@@ -1101,16 +1094,6 @@ void demod_blk_plan(const DemodParams &P, uint32_t groups, int device, uint32_t 
   *y_slots = y;
   *resident_wgs = held(y) * (uint32_t)cus;
 }
-
-#ifdef FSK_ABLATE
-static void set_ablate_blk() {
-  const char *a = getenv("FSK_ABLATE");
-  const int v = a ? atoi(a) : 0;
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ablate), &v, sizeof(v));
-}
-#else
-static inline void set_ablate_blk() {}
-#endif
 
 // Time slices (see BlkSched; how a call is cut: fsk_blk_sched.h)
 size_t demod_blk_queue_words(uint32_t groups) { return 16u + (size_t)groups * (kBlkMaxSlices - 1u); }
@@ -1136,58 +1119,28 @@ uint32_t demod_blk_lanes(uint32_t n_streams, int device) {
   return 64u;
 }
 
-hipError_t launch_demod_blk(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n,
-                             size_t pitch, uint8_t *out, size_t out_pitch, uint32_t *out_counts,
-                             uint32_t *eod_counts, hipStream_t stream, uint32_t resident_wgs, uint32_t slice_tiles, uint32_t y_slots,
-                             uint32_t lanes, uint32_t medium, bool *sliced_out) {
-  lanes = (lanes == 8u || lanes == 16u || lanes == 32u) ? lanes : 64u;
+hipError_t launch_demod_blk(const DemodCall &c, const DemodParams &P, const DemodState &S, uint32_t resident_wgs, uint32_t slice_tiles, uint32_t y_slots,
+                            uint32_t lanes, uint32_t medium, const char **name) {
+  lanes = 64u >> blk_lanes_index(lanes);
   const uint32_t blocks = (P.n_streams + lanes - 1u) / lanes;
   y_slots = y_slots < kBlkSlots ? kBlkSlots : y_slots > kBlkYMax ? kBlkYMax : y_slots;
   const size_t lds = demod_blk_lds_bytes(P, y_slots);
-  set_ablate_blk();
+  set_ablate();
   BlkSched Z = {nullptr, blocks, 1u, 0u, 0u, y_slots, blk_zt_tiles(y_slots), lanes, medium};
   uint32_t st = 0;
   // (time slices are for batches beyond one round of whole-wave groups; narrow groups are never sliced -- the queue is
   // sized for 64-stream groups)
-  const uint32_t ns = lanes == 64u ? demod_blk_slices(P, S, n, resident_wgs, slice_tiles, &st) : 1u;
+  const uint32_t ns = lanes == 64u ? demod_blk_slices(P, S, c.n, resident_wgs, slice_tiles, &st) : 1u;
   const bool sliced = ns >= 2u;
   if (sliced) {
     Z.q = S.blk_q; Z.nslices = ns; Z.slice_tiles = st; Z.total = blocks * ns;
-    const hipError_t e = hipMemsetAsync(S.blk_q, 0, sizeof(uint32_t) * (16u + (size_t)blocks * (ns - 1u)), stream);
+    const hipError_t e = hipMemsetAsync(S.blk_q, 0, sizeof(uint32_t) * (16u + (size_t)blocks * (ns - 1u)), c.stream);
     if (e != hipSuccess) return e;
   }
-  if (sliced_out) *sliced_out = sliced;
-  const uint32_t grid = sliced ? resident_wgs : blocks;
-#define FSK_LAUNCH_BLK(WBV, UNIV, SLV)                                                                          \
-  hipLaunchKernelGGL((demod_blk_kernel<WBV, UNIV, SLV>), dim3(grid), dim3(256), lds, stream, P, S, samples, n, pitch, \
-                     append ? 1 : 0, out, out_pitch, out_counts, eod_counts, Z)
-  const bool uni = P.uni_cfg != 0;
-#define FSK_LAUNCH_BLKR(WBV, SLV)                                                                               \
-  hipLaunchKernelGGL((demod_blk_kernel_r<WBV, SLV>), dim3(grid), dim3(256), lds, stream, P, S, samples, n, pitch, \
-                     append ? 1 : 0, out, out_pitch, out_counts, eod_counts, Z)
-  if (uni && medium != 0u) {
-    if (sliced) { if (writeback) FSK_LAUNCH_BLKR(true, true); else FSK_LAUNCH_BLKR(false, true); }
-    else { if (writeback) FSK_LAUNCH_BLKR(true, false); else FSK_LAUNCH_BLKR(false, false); }
-    return hipGetLastError();
-  }
-#undef FSK_LAUNCH_BLKR
-#define FSK_LAUNCH_BLKRP(WBV, SLV)                                                                              \
-  hipLaunchKernelGGL((demod_blk_kernel_rp<WBV, SLV>), dim3(grid), dim3(256), lds, stream, P, S, samples, n, pitch, \
-                     append ? 1 : 0, out, out_pitch, out_counts, eod_counts, Z)
-  if (!uni && medium != 0u) {
-    if (sliced) { if (writeback) FSK_LAUNCH_BLKRP(true, true); else FSK_LAUNCH_BLKRP(false, true); }
-    else { if (writeback) FSK_LAUNCH_BLKRP(true, false); else FSK_LAUNCH_BLKRP(false, false); }
-    return hipGetLastError();
-  }
-#undef FSK_LAUNCH_BLKRP
-  if (sliced) {
-    if (writeback) { if (uni) FSK_LAUNCH_BLK(true, true, true); else FSK_LAUNCH_BLK(true, false, true); }
-    else { if (uni) FSK_LAUNCH_BLK(false, true, true); else FSK_LAUNCH_BLK(false, false, true); }
-  } else {
-    if (writeback) { if (uni) FSK_LAUNCH_BLK(true, true, false); else FSK_LAUNCH_BLK(true, false, false); }
-    else { if (uni) FSK_LAUNCH_BLK(false, true, false); else FSK_LAUNCH_BLK(false, false, false); }
-  }
-#undef FSK_LAUNCH_BLK
+  const KernelEntry<BlkFn> &k = kBlkKernels[blk_index(c.writeback, P.uni_cfg != 0, sliced, medium != 0u)];
+  hipLaunchKernelGGL(k.fn, dim3(sliced ? resident_wgs : blocks), dim3(256), lds, c.stream, P, S, c.samples, c.n, c.pitch, c.append ? 1 : 0, c.out,
+                     c.out_pitch, c.out_counts, c.eod_counts, Z);
+  *name = k.name;
   return hipGetLastError();
 }
 

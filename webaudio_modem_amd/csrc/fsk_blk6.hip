@@ -1130,21 +1130,17 @@ bool demod_blk6_applicable(const DemodParams &P) {
 // half-tile counters carry a generation in their top byte
 size_t demod_blk6_max_samples() { return ((size_t)1 << 23) * 16u - 16u; }
 
-hipError_t set_blk6_lds_limit(const DemodParams &P) {
-  hipError_t e = hipSuccess;
-  const size_t bytes = demod_blk6_lds_bytes(P, demod_blk6_y_slots(P));
-#define FSK_ATTR(WBV, LWV)                                                                                       \
-  if (e == hipSuccess)                                                                                           \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&demod_blk6_kernel<WBV, LWV, true>),                 \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);                            \
-  if (e == hipSuccess)                                                                                           \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&demod_blk6_kernel<WBV, LWV, false>),                \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  FSK_ATTR(false, 64) FSK_ATTR(false, 32) FSK_ATTR(false, 16) FSK_ATTR(false, 8)
-  FSK_ATTR(true, 64) FSK_ATTR(true, 32) FSK_ATTR(true, 16) FSK_ATTR(true, 8)
-#undef FSK_ATTR
-  return e;
-}
+// Every instantiation, once, in blk6_index()'s order: <write-back, streams per workgroup> with the uniform tone pair (UNI's default),
+// each followed by its twin for per-stream tone pairs (round 6).
+typedef void (*Blk6Fn)(DemodParams, DemodState, float *, size_t, size_t, int, uint8_t *, size_t, uint32_t *, uint32_t *, Blk6Z);
+static const KernelEntry<Blk6Fn> kBlk6Kernels[16] = {
+    FSK_K(demod_blk6_kernel, false, 64), FSK_K(demod_blk6_kernel, false, 64, false), FSK_K(demod_blk6_kernel, false, 32), FSK_K(demod_blk6_kernel, false, 32, false),
+    FSK_K(demod_blk6_kernel, false, 16), FSK_K(demod_blk6_kernel, false, 16, false), FSK_K(demod_blk6_kernel, false, 8),  FSK_K(demod_blk6_kernel, false, 8, false),
+    FSK_K(demod_blk6_kernel, true, 64),  FSK_K(demod_blk6_kernel, true, 64, false),  FSK_K(demod_blk6_kernel, true, 32),  FSK_K(demod_blk6_kernel, true, 32, false),
+    FSK_K(demod_blk6_kernel, true, 16),  FSK_K(demod_blk6_kernel, true, 16, false),  FSK_K(demod_blk6_kernel, true, 8),   FSK_K(demod_blk6_kernel, true, 8, false)};
+static uint32_t blk6_index(bool writeback, uint32_t lanes, bool uni) { return (writeback ? 8u : 0u) + 2u * blk_lanes_index(lanes) + (uni ? 0u : 1u); }
+
+hipError_t set_blk6_lds_limit(const DemodParams &P) { return set_lds_limit(kBlk6Kernels, demod_blk6_lds_bytes(P, demod_blk6_y_slots(P))); }
 
 // default part of each wave (parts: 0 loader, 1 AGC, 2 pre-filter, 3 iq, 4 post, 5 frame, 6 disc).  Waves w and w + 4 of a
 // workgroup share a SIMD (its seven waves go round the CU's four): the frame logic -- the longest instruction stream and the one
@@ -1161,33 +1157,19 @@ uint32_t demod_blk6_default_rolemap(uint32_t lanes, bool uniform) {
   return m;
 }
 
-hipError_t launch_demod_blk6(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n,
-                              size_t pitch, uint8_t *out, size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts,
-                              hipStream_t stream, uint32_t lanes, uint32_t y_slots, uint32_t rolemap) {
-  lanes = (lanes == 8u || lanes == 16u || lanes == 32u) ? lanes : 64u;
+hipError_t launch_demod_blk6(const DemodCall &c, const DemodParams &P, const DemodState &S, uint32_t lanes, uint32_t y_slots, uint32_t rolemap,
+                             const char **name) {
+  const KernelEntry<Blk6Fn> &k = kBlk6Kernels[blk6_index(c.writeback, lanes, P.uni_cfg != 0u)];
+  lanes = 64u >> blk_lanes_index(lanes);
   const uint32_t blocks = (P.n_streams + lanes - 1u) / lanes;
   const uint32_t ymax = demod_blk6_y_slots(P);
   y_slots = y_slots < kB6YMin ? kB6YMin : y_slots > ymax ? ymax : y_slots;
   y_slots &= ~1u;
   const size_t lds = demod_blk6_lds_bytes(P, y_slots);
   Blk6Z Z = {y_slots, blk6_zt_tiles(y_slots), rolemap ? rolemap : demod_blk6_default_rolemap(lanes, P.uni_cfg != 0u)};
-#define FSK_LAUNCH_B6(WBV, LWV)                                                                                      \
-  do {                                                                                                               \
-    if (P.uni_cfg != 0u)                                                                                             \
-      hipLaunchKernelGGL((demod_blk6_kernel<WBV, LWV, true>), dim3(blocks), dim3(64 * kB6Waves), lds, stream, P, S, samples, n, pitch, \
-                         append ? 1 : 0, out, out_pitch, out_counts, eod_counts, Z);                                \
-    else                                                                                                             \
-      hipLaunchKernelGGL((demod_blk6_kernel<WBV, LWV, false>), dim3(blocks), dim3(64 * kB6Waves), lds, stream, P, S, samples, n, pitch, \
-                         append ? 1 : 0, out, out_pitch, out_counts, eod_counts, Z);                                \
-  } while (0)
-  if (writeback) {
-    if (lanes == 64u) FSK_LAUNCH_B6(true, 64); else if (lanes == 32u) FSK_LAUNCH_B6(true, 32);
-    else if (lanes == 16u) FSK_LAUNCH_B6(true, 16); else FSK_LAUNCH_B6(true, 8);
-  } else {
-    if (lanes == 64u) FSK_LAUNCH_B6(false, 64); else if (lanes == 32u) FSK_LAUNCH_B6(false, 32);
-    else if (lanes == 16u) FSK_LAUNCH_B6(false, 16); else FSK_LAUNCH_B6(false, 8);
-  }
-#undef FSK_LAUNCH_B6
+  hipLaunchKernelGGL(k.fn, dim3(blocks), dim3(64 * kB6Waves), lds, c.stream, P, S, c.samples, c.n, c.pitch, c.append ? 1 : 0, c.out, c.out_pitch,
+                     c.out_counts, c.eod_counts, Z);
+  *name = k.name;
   return hipGetLastError();
 }
 

@@ -1177,51 +1177,42 @@ size_t demod_split2_lds_bytes(const DemodParams &P) {
   FSK_FOR_RT(X, float, uint64_t, true) FSK_FOR_RT(X, double, uint32_t, false)                      \
   FSK_FOR_RT(X, double, uint64_t, false) FSK_FOR_RT(X, double, uint64_t, true)
 
-// Host-side launcher (called from fsk_api.hip).  uniform_ds: every stream's downsample.counter
+// Every instantiation, once: the 24 one-wave variants with the run-time choice each serves, and the exact path on two waves per
+// group (SPLIT2).  fskhip_last_kernel reports the family by precision, not the variant.
+typedef void (*DemodFn)(DemodParams, DemodState, float *, size_t, size_t, int, int, int, uint8_t *, size_t, uint32_t *, uint32_t *);
+static const KernelEntry<DemodFn> kDemodSplit2[1] = {{&demod_kernel<double, uint32_t, false, true, false, true>, "fsk::demod_kernel<double, ..., two waves>"}};
+struct DemodVariant : KernelEntry<DemodFn> { bool f64, wide, frac, uniform_ds, trace; };
+#define FSK_VARIANT(R, T, F, U, TR) \
+  {{&demod_kernel<R, T, F, U, TR>, sizeof(R) == 8 ? "fsk::demod_kernel<double, ...>" : "fsk::demod_kernel<float, ...>"}, sizeof(R) == 8, sizeof(T) == 8, F, U, TR},
+static const DemodVariant kDemodKernels[24] = {FSK_FOR_ALL_VARIANTS(FSK_VARIANT)};
+#undef FSK_VARIANT
+static const KernelEntry<DemodFn> *demod_select(bool f64, bool wide, bool frac, bool uniform_ds, bool trace) {
+  for (const DemodVariant &v : kDemodKernels)
+    if (v.f64 == f64 && v.wide == wide && v.frac == frac && v.uniform_ds == uniform_ds && v.trace == trace) return &v;
+  return nullptr;   // (wide == false with frac == true: no such engine)
+}
+
+// Host-side launcher (called from fsk_dispatch.hip).  uniform_ds: every stream's downsample.counter
 // and ring positions are equal (true unless single streams were reset at odd sample positions).
-hipError_t launch_demod(int precision, bool uniform_ds, bool writeback, bool append, const DemodParams &P,
-                        const DemodState &S, float *samples, size_t n, size_t pitch, uint8_t *out,
-                        size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts,
-                        hipStream_t stream, bool split2) {
-  const uint32_t blocks = (P.n_streams + 63u) / 64u;
-  const size_t lds_bytes = demod_lds_bytes(P);
-  const int vec_ok = (pitch % 4 == 0) && ((reinterpret_cast<uintptr_t>(samples) & 15u) == 0);
-  int wb = writeback ? 1 : 0;
+hipError_t launch_demod(const DemodCall &c, const DemodParams &P, const DemodState &S, int precision, bool uniform_ds, bool split2, const char **name) {
+  const int vec_ok = (c.pitch % 4 == 0) && ((reinterpret_cast<uintptr_t>(c.samples) & 15u) == 0);
+  int wb = c.writeback ? 1 : 0;
 #ifdef FSK_ABLATE
   if (const char *a = getenv("FSK_ABLATE")) wb |= atoi(a) << 8;
 #endif
   const bool f64 = precision != 0, wide = P.wide != 0, frac = P.frac != 0;
   const bool trace = S.trace_stream != 0xFFFFFFFFu;
- dim3 g(blocks), b(64);
-  if (split2 && f64 && !wide && !frac && uniform_ds && !trace) {     // the exact path on two waves per group (SPLIT2)
-    hipLaunchKernelGGL((demod_kernel<double, uint32_t, false, true, false, true>), g, dim3(128), demod_split2_lds_bytes(P), stream, P, S, samples, n,
-                       pitch, vec_ok, wb, append ? 1 : 0, out, out_pitch, out_counts, eod_counts);
-    return hipGetLastError();
-  }
-#define FSK_LAUNCH(R, T, F, U, TR)                                                                 \
-  if (f64 == (sizeof(R) == 8) && wide == (sizeof(T) == 8) && frac == F && uniform_ds == U &&       \
-      trace == TR)                                                                                 \
-    hipLaunchKernelGGL((demod_kernel<R, T, F, U, TR>), g, b, lds_bytes, stream, P, S, samples, n,  \
-                       pitch, vec_ok, wb, append ? 1 : 0, out, out_pitch, out_counts, eod_counts);
-  FSK_FOR_ALL_VARIANTS(FSK_LAUNCH)
-#undef FSK_LAUNCH
+  const bool two = split2 && f64 && !wide && !frac && uniform_ds && !trace;     // the exact path on two waves per group (SPLIT2)
+  const KernelEntry<DemodFn> *k = two ? kDemodSplit2 : demod_select(f64, wide, frac, uniform_ds, trace);
+  if (!k) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k->fn, dim3((P.n_streams + 63u) / 64u), dim3(two ? 128 : 64), two ? demod_split2_lds_bytes(P) : demod_lds_bytes(P), c.stream, P, S,
+                     c.samples, c.n, c.pitch, vec_ok, wb, c.append ? 1 : 0, c.out, c.out_pitch, c.out_counts, c.eod_counts);
+  *name = k->name;
   return hipGetLastError();
 }
 
-hipError_t set_demod_split2_lds_limit(size_t lds_bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(&demod_kernel<double, uint32_t, false, true, false, true>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-}
+hipError_t set_demod_split2_lds_limit(size_t lds_bytes) { return set_lds_limit(kDemodSplit2, lds_bytes); }
 
-hipError_t set_demod_lds_limit(size_t lds_bytes) {
-  hipError_t e = hipSuccess;
-#define FSK_ATTR(R, T, F, U, TR)                                                                   \
-  if (e == hipSuccess)                                                                             \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&demod_kernel<R, T, F, U, TR>),         \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  FSK_FOR_ALL_VARIANTS(FSK_ATTR)
-#undef FSK_ATTR
-  return e;
-}
+hipError_t set_demod_lds_limit(size_t lds_bytes) { return set_lds_limit(kDemodKernels, lds_bytes); }
 
 }  // namespace fsk

@@ -142,83 +142,39 @@ LaunchPlan plan_launches(fskhip_engine *e, const float *d_samples, size_t n, siz
   return pl;
 }
 
-// what fskhip_last_kernel reports for a call: its whole-tile kernel, or the per-sample / generic kernel of a call without tiles
-const char *kernel_name(const fskhip_engine *e, const LaunchPlan &pl, bool wb) {
-  const bool uni = e->P.uni_cfg != 0;
-  switch (pl.kernel) {
-    case K_SAMPLES: return "fsk::demod_tail_kernel";
-    case K_SEVEN_WAVE: {
-      static const char *const names6[16] = {
-          "fsk::demod_blk6_kernel<false, 64>", "fsk::demod_blk6_kernel<false, 32>", "fsk::demod_blk6_kernel<false, 16>", "fsk::demod_blk6_kernel<false, 8>",
-          "fsk::demod_blk6_kernel<true, 64>", "fsk::demod_blk6_kernel<true, 32>", "fsk::demod_blk6_kernel<true, 16>", "fsk::demod_blk6_kernel<true, 8>",
-          // (round 6: per-stream tone pairs -- <write-back, streams per workgroup, uniform = false>)
-          "fsk::demod_blk6_kernel<false, 64, false>", "fsk::demod_blk6_kernel<false, 32, false>", "fsk::demod_blk6_kernel<false, 16, false>", "fsk::demod_blk6_kernel<false, 8, false>",
-          "fsk::demod_blk6_kernel<true, 64, false>", "fsk::demod_blk6_kernel<true, 32, false>", "fsk::demod_blk6_kernel<true, 16, false>", "fsk::demod_blk6_kernel<true, 8, false>"};
-      return names6[(uni ? 0 : 8) + (wb ? 4 : 0) + (e->blk.lanes == 64u ? 0 : e->blk.lanes == 32u ? 1 : e->blk.lanes == 16u ? 2 : 3)];
-    }
-    case K_FOUR_WAVE: {
-      static const char *const names[16] = {
-          "fsk::demod_blk_kernel<false, false, false>", "fsk::demod_blk_kernel<false, false, true>",
-          "fsk::demod_blk_kernel<false, true, false>", "fsk::demod_blk_kernel<false, true, true>",
-          "fsk::demod_blk_kernel<true, false, false>", "fsk::demod_blk_kernel<true, false, true>",
-          "fsk::demod_blk_kernel<true, true, false>", "fsk::demod_blk_kernel<true, true, true>",
-          "fsk::demod_blk_kernel_r<false, false>", "fsk::demod_blk_kernel_r<false, true>",
-          "fsk::demod_blk_kernel_r<true, false>", "fsk::demod_blk_kernel_r<true, true>",
-          "fsk::demod_blk_kernel_rp<false, false>", "fsk::demod_blk_kernel_rp<false, true>",
-          "fsk::demod_blk_kernel_rp<true, false>", "fsk::demod_blk_kernel_rp<true, true>"};
-      return pl.med ? names[(uni ? 8 : 12) + (wb ? 2 : 0) + (e->last_sliced ? 1 : 0)]   // <writeback, time-sliced>: _r uniform, _rp per-stream tone pairs
-                    : names[(wb ? 4 : 0) + (uni ? 2 : 0) + (e->last_sliced ? 1 : 0)];   // <writeback, uniform, time-sliced>
-    }
-    case K_TWO_WAVE: case K_ONE_WAVE: {
-      static const char *const names2[8] = {   // <writeback, uniform>
-          "fsk::demod_pipe_kernel<false, false>", "fsk::demod_pipe_kernel<false, true>", "fsk::demod_pipe_kernel<true, false>", "fsk::demod_pipe_kernel<true, true>",
-          "fsk::demod_fused_kernel<false, false>", "fsk::demod_fused_kernel<false, true>", "fsk::demod_fused_kernel<true, false>", "fsk::demod_fused_kernel<true, true>"};
-      return names2[(pl.kernel == K_ONE_WAVE ? 4 : 0) + (wb ? 2 : 0) + (uni ? 1 : 0)];
-    }
-    case K_GENERIC: break;   // (below)
-  }
-  return pl.split2 ? "fsk::demod_kernel<double, ..., two waves>" : e->precision == FSKHIP_PRECISION_F64 ? "fsk::demod_kernel<double, ...>" : "fsk::demod_kernel<float, ...>";
-}
-
-int issue_launches(fskhip_engine *e, const LaunchPlan &pl, bool wb, bool append_first, float *d_samples, size_t n, size_t pitch,
-                   uint8_t *d_out, size_t out_pitch, uint32_t *d_out_counts, uint32_t *d_eod_counts, hipStream_t st) {
+// Issues the plan's launches.  *name: what fskhip_last_kernel reports for the call -- its whole-tile kernel as the launcher named it,
+// or the per-sample / generic kernel of a call without tiles.
+int issue_launches(fskhip_engine *e, const LaunchPlan &pl, const DemodCall &call, const char **name) {
   if (pl.kernel == K_GENERIC) {
     e->P.nco_anchor = (uint32_t)(e->total_samples & 31u);   // (fp64: where the NCO phasor is re-evaluated; fsk_demod.hip, mix_lp)
-    HIP_TRY(launch_demod(e->precision, e->ds_uniform, wb, append_first, e->P, e->S, d_samples, n, pitch, d_out, out_pitch,
-                         d_out_counts, d_eod_counts, st, pl.split2));
+    HIP_TRY(launch_demod(call, e->P, e->S, e->precision, e->ds_uniform, pl.split2, name));
     // the generic kernel keeps an open decimator pair's partial sums in the reference's own frame: stay with it
     // until the pair is closed
-    if (n > 0) e->gen_odd = e->precision == FSKHIP_PRECISION_F32 && ((e->ds_parity + (uint32_t)(n & 1)) & 1u) != 0;
+    if (call.n > 0) e->gen_odd = e->precision == FSKHIP_PRECISION_F32 && ((e->ds_parity + (uint32_t)(call.n & 1)) & 1u) != 0;
     return FSKHIP_OK;
   }
   const size_t head = pl.head, n_fast = pl.n_fast;
-  bool app = append_first;
-  if (head) {
-    HIP_TRY(launch_demod_tail(wb, app, (int)e->ds_parity, e->P, e->S, d_samples, head, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st));
-    app = true;
-  }
-  if (!n_fast) return FSKHIP_OK;
+  const char *per_sample = "";   // the head's and the tail's kernel: the call's only where it has no tiles
+  if (head) HIP_TRY(launch_demod_tail(call.sub(0, head), e->P, e->S, (int)e->ds_parity, &per_sample));
+  if (!n_fast) { *name = per_sample; return FSKHIP_OK; }
+  const DemodCall tiles = call.sub(head, n_fast);
   switch (pl.kernel) {
     case K_SEVEN_WAVE:
-      HIP_TRY(launch_demod_blk6(wb, app, e->P, e->S, d_samples + head, n_fast, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st,
-                                e->blk.lanes, pl.y_slots, e->six.rolemap));
-      e->last_sliced = false;
-      HIP_TRY(engine_fetch_blk_stat(e, n_fast, st));
+      HIP_TRY(launch_demod_blk6(tiles, e->P, e->S, e->blk.lanes, pl.y_slots, e->six.rolemap, name));
+      HIP_TRY(engine_fetch_blk_stat(e, n_fast, call.stream));
       break;
     case K_FOUR_WAVE:
-      HIP_TRY(launch_demod_blk(wb, app, e->P, e->S, d_samples + head, n_fast, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st,
-                               e->blk.resident, e->blk.slice_tiles, e->blk.y_slots, e->blk.lanes, pl.med, &e->last_sliced));
-      HIP_TRY(engine_fetch_blk_stat(e, n_fast, st));
+      HIP_TRY(launch_demod_blk(tiles, e->P, e->S, e->blk.resident, e->blk.slice_tiles, e->blk.y_slots, e->blk.lanes, pl.med, name));
+      HIP_TRY(engine_fetch_blk_stat(e, n_fast, call.stream));
       break;
     case K_TWO_WAVE:
-      HIP_TRY(launch_demod_pipe(wb, app, e->P, e->S, d_samples + head, n_fast, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st));
+      HIP_TRY(launch_demod_pipe(tiles, e->P, e->S, name));
       break;
     default:
-      HIP_TRY(launch_demod_fused(wb, app, e->P, e->S, d_samples + head, n_fast, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st));
+      HIP_TRY(launch_demod_fused(tiles, e->P, e->S, name));
   }
   const size_t done = head + n_fast;
-  if (done < n)
-    HIP_TRY(launch_demod_tail(wb, true, 0, e->P, e->S, d_samples + done, n - done, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st));
+  if (done < call.n) HIP_TRY(launch_demod_tail(call.sub(done, call.n - done), e->P, e->S, 0, &per_sample));
   return FSKHIP_OK;
 }
 
@@ -238,8 +194,9 @@ int demod_device_impl(fskhip_engine *e, float *d_samples, size_t n, size_t pitch
   if (const int rc = timing_open(e, st)) return rc;
   e->last_kernel = "";
   const LaunchPlan pl = plan_launches(e, d_samples, n, pitch);
-  if (const int rc = issue_launches(e, pl, wb, append_first, d_samples, n, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st)) return rc;
-  e->last_kernel = kernel_name(e, pl, wb);
+  const char *name = "";
+  if (const int rc = issue_launches(e, pl, {wb, append_first, d_samples, n, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st}, &name)) return rc;
+  e->last_kernel = name;
   if (const int rc = timing_close(e, st)) return rc;
   note_call(e, n, count_call ? 1u : 0u);
   return FSKHIP_OK;

@@ -33,8 +33,7 @@ struct fskhip_engine {
   bool gen_odd = false;          // fp32: the last generic-kernel launch left a decimator pair open (its partial sums are in
                                  // the reference's frame, the whole-tile kernels' in the free-running one)
   bool demodulated = false;      // a demodulate call has been issued or replayed (fskhip_set_option refuses from then on)
-  const char *last_kernel = "";  // what the last fskhip_demodulate_device call launched for its whole tiles
-  bool last_sliced = false;
+  const char *last_kernel = "";  // what the last fskhip_demodulate_device call launched for its whole tiles, as the launcher named it (fsk_launch.h)
   uint32_t handoff_fault = 0;    // sticky: a kernel's hand-off wait ran into its bound (csrc/fsk_wait.h)
   bool demod_ok = true;          // false: configuration the demodulator kernels do not implement
   std::string demod_why;

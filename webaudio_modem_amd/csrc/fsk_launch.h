@@ -1,5 +1,6 @@
 // fsk_launch.h -- the one declaration of every host-callable function a kernel file defines.  Included by the defining
-// .hip file and by its callers (the C-ABI units), so that a signature cannot drift between them.  Not part of the ABI.
+// .hip file and by its callers (the C-ABI units), so that a signature cannot drift between them; and what the demodulator's
+// launchers share: the call's arguments (DemodCall) and the form of a kernel file's instantiation table (KernelEntry).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -9,21 +10,45 @@
 #include "fsk_params.h"
 
 namespace fsk {
+// What a demodulate launch takes from its call: every launch_demod_* gets one of these, then its kernel family's own arguments,
+// and says through `name` what fskhip_last_kernel reports for the kernel it chose.
+struct DemodCall {
+  bool writeback, append;   // write the AGC's output back into `samples`; the call has produced output already
+  float *samples; size_t n, pitch;
+  uint8_t *out; size_t out_pitch;
+  uint32_t *out_counts, *eod_counts;
+  hipStream_t stream;
+  // samples [first, first + len) of the call as a launch of their own (head / whole tiles / tail): behind an earlier launch it appends
+  DemodCall sub(size_t first, size_t len) const { return {writeback, append || first > 0, samples + first, len, pitch, out, out_pitch, out_counts, eod_counts, stream}; }
+};
+// One instantiation of a kernel family -- the typed kernel pointer and the name reported for it, both from one spelling of the
+// template arguments (spell them as the name has them: "false, true").  Each kernel file lists its instantiations once, in tables
+// of these beside the selector that indexes them; its LDS limit and its launcher both go through the table.
+template <typename Fn>
+struct KernelEntry { Fn fn; const char *name; };
+#define FSK_K(K, ...) {&K<__VA_ARGS__>, "fsk::" #K "<" #__VA_ARGS__ ">"}
+template <typename Entry, size_t N>
+hipError_t set_lds_limit(const Entry (&table)[N], size_t bytes) {   // every instantiation's limit of dynamic LDS
+  for (const Entry &k : table) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+// streams per workgroup of the four- and seven-wave kernels as an index: 64 / 32 / 16 / 8 -> 0..3, anything else counts as 64
+inline uint32_t blk_lanes_index(uint32_t lanes) { return lanes == 32u ? 1u : lanes == 16u ? 2u : lanes == 8u ? 3u : 0u; }
+
 // fsk_demod.hip: the generic kernel (fp64, wide / fractional rings, streams out of lock step)
-hipError_t launch_demod(int precision, bool uniform_ds, bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n, size_t pitch,
-                        uint8_t *out, size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, hipStream_t stream, bool split2 = false);
+hipError_t launch_demod(const DemodCall &c, const DemodParams &P, const DemodState &S, int precision, bool uniform_ds, bool split2, const char **name);
 bool demod_fast_applicable(int precision, bool uniform_even, const DemodParams &P, const DemodState &S, const float *samples, size_t pitch);
 size_t demod_split2_lds_bytes(const DemodParams &P);
 hipError_t set_demod_split2_lds_limit(size_t lds_bytes);
 hipError_t set_demod_lds_limit(size_t lds_bytes);
 size_t demod_lds_bytes(const DemodParams &P);
 // fsk_pipe.hip: free-running front / ZIR-corrected back kernels
-hipError_t launch_demod_pipe(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n, size_t pitch, uint8_t *out,
-                             size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, hipStream_t stream);
-hipError_t launch_demod_fused(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n, size_t pitch, uint8_t *out,
-                              size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, hipStream_t stream);
-hipError_t launch_demod_tail(bool writeback, bool append, int parity0, const DemodParams &P, const DemodState &S, float *samples, size_t n, size_t pitch, uint8_t *out,
-                             size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, hipStream_t stream);
+hipError_t launch_demod_pipe(const DemodCall &c, const DemodParams &P, const DemodState &S, const char **name);
+hipError_t launch_demod_fused(const DemodCall &c, const DemodParams &P, const DemodState &S, const char **name);
+hipError_t launch_demod_tail(const DemodCall &c, const DemodParams &P, const DemodState &S, int parity0, const char **name);
 size_t demod_pipe_lds_bytes(const DemodParams &P);
 size_t demod_fused_lds_bytes(const DemodParams &P);
 hipError_t set_pipe_lds_limit(size_t pipe_bytes);
@@ -32,9 +57,8 @@ size_t demod_blk_lds_bytes(const DemodParams &P);
 size_t demod_blk_lds_bytes(const DemodParams &P, uint32_t y_slots);
 bool demod_blk_applicable(const DemodParams &P);
 hipError_t set_blk_lds_limit(const DemodParams &P);
-hipError_t launch_demod_blk(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n, size_t pitch, uint8_t *out,
-                            size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, hipStream_t stream, uint32_t resident_wgs, uint32_t slice_tiles,
-                            uint32_t y_slots, uint32_t lanes, uint32_t medium, bool *sliced_out);
+hipError_t launch_demod_blk(const DemodCall &c, const DemodParams &P, const DemodState &S, uint32_t resident_wgs, uint32_t slice_tiles, uint32_t y_slots,
+                            uint32_t lanes, uint32_t medium, const char **name);
 uint32_t demod_blk_lanes(uint32_t n_streams, int device);
 void demod_blk_plan(const DemodParams &P, uint32_t groups, int device, uint32_t *y_slots, uint32_t *resident_wgs);
 uint32_t demod_blk_slices(const DemodParams &P, const DemodState &S, size_t n, uint32_t resident_wgs, uint32_t slice_tiles, uint32_t *slice_tiles_out);
@@ -47,8 +71,7 @@ bool demod_blk6_applicable(const DemodParams &P);
 size_t demod_blk6_max_samples();
 hipError_t set_blk6_lds_limit(const DemodParams &P);
 uint32_t demod_blk6_default_rolemap(uint32_t lanes, bool uniform);
-hipError_t launch_demod_blk6(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n, size_t pitch, uint8_t *out,
-                             size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, hipStream_t stream, uint32_t lanes, uint32_t y_slots, uint32_t rolemap);
+hipError_t launch_demod_blk6(const DemodCall &c, const DemodParams &P, const DemodState &S, uint32_t lanes, uint32_t y_slots, uint32_t rolemap, const char **name);
 // fsk_mod.hip: modulator, synthetic workloads, and the FSKProcessor quantum's bookkeeping / TX kernels
 hipError_t launch_modulate(const ModParams &M, const double *coef, const uint8_t *payloads, const uint32_t *lens, size_t payload_pitch, float *out, size_t out_pitch,
                            uint32_t *out_lens, hipStream_t st);

@@ -559,70 +559,42 @@ size_t demod_pipe_lds_bytes(const DemodParams &P) {
 }
 size_t demod_fused_lds_bytes(const DemodParams &P) { return sizeof(float4) * (4 * kSlotStride + 2 * 8) + sizeof(uint32_t) * 64u * (P.d + 1u); }
 
-hipError_t set_pipe_lds_limit(size_t pipe_bytes) {
-  hipError_t e = hipSuccess;
-#define FSK_ATTR(WBV, UNIV)                                                                                      \
-  if (e == hipSuccess)                                                                                           \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&demod_pipe_kernel<WBV, UNIV>),                       \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)pipe_bytes);
-  FSK_ATTR(false, false) FSK_ATTR(false, true) FSK_ATTR(true, false) FSK_ATTR(true, true)
-#undef FSK_ATTR
-  return e;
+// Every instantiation, once: <write-back, uniform> at pipe_index().  The sample-granular kernel is reported without its arguments.
+typedef void (*PipeFn)(DemodParams, DemodState, float *, size_t, size_t, int, uint8_t *, size_t, uint32_t *, uint32_t *);
+typedef void (*TailFn)(DemodParams, DemodState, float *, size_t, size_t, int, int, uint8_t *, size_t, uint32_t *, uint32_t *);
+static const KernelEntry<PipeFn> kPipeKernels[4] = {FSK_K(demod_pipe_kernel, false, false), FSK_K(demod_pipe_kernel, false, true),
+                                             FSK_K(demod_pipe_kernel, true, false), FSK_K(demod_pipe_kernel, true, true)};
+static const KernelEntry<PipeFn> kFusedKernels[4] = {FSK_K(demod_fused_kernel, false, false), FSK_K(demod_fused_kernel, false, true),
+                                              FSK_K(demod_fused_kernel, true, false), FSK_K(demod_fused_kernel, true, true)};
+static const char *const kTailName = "fsk::demod_tail_kernel";
+static const KernelEntry<TailFn> kTailKernels[4] = {{&demod_tail_kernel<false, false>, kTailName}, {&demod_tail_kernel<false, true>, kTailName},
+                                             {&demod_tail_kernel<true, false>, kTailName}, {&demod_tail_kernel<true, true>, kTailName}};
+static uint32_t pipe_index(bool writeback, const DemodParams &P) { return (writeback ? 2u : 0u) + (P.uni_cfg != 0 ? 1u : 0u); }
+
+hipError_t set_pipe_lds_limit(size_t pipe_bytes) { return set_lds_limit(kPipeKernels, pipe_bytes); }
+
+static hipError_t launch_tiles(const KernelEntry<PipeFn> &k, uint32_t threads, size_t lds, const DemodCall &c, const DemodParams &P, const DemodState &S,
+                               const char **name) {
+  hipLaunchKernelGGL(k.fn, dim3((P.n_streams + 63u) / 64u), dim3(threads), lds, c.stream, P, S, c.samples, c.n, c.pitch, c.append ? 1 : 0, c.out,
+                     c.out_pitch, c.out_counts, c.eod_counts);
+  *name = k.name;
+  return hipGetLastError();
 }
 
-#ifdef FSK_ABLATE
-static void set_ablate() {
-  const char *a = getenv("FSK_ABLATE");
-  const int v = a ? atoi(a) : 0;
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ablate), &v, sizeof(v));
-}
-#else
-static inline void set_ablate() {}
-#endif
-
-hipError_t launch_demod_pipe(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n,
-                             size_t pitch, uint8_t *out, size_t out_pitch, uint32_t *out_counts,
-                             uint32_t *eod_counts, hipStream_t stream) {
-  const uint32_t blocks = (P.n_streams + 63u) / 64u;
-  const size_t lds = demod_pipe_lds_bytes(P);
+hipError_t launch_demod_pipe(const DemodCall &c, const DemodParams &P, const DemodState &S, const char **name) {
   set_ablate();
-#define FSK_LAUNCH_PIPE(WBV, UNIV)                                                                          \
-  hipLaunchKernelGGL((demod_pipe_kernel<WBV, UNIV>), dim3(blocks), dim3(128), lds, stream, P, S, samples, n, pitch, \
-                     append ? 1 : 0, out, out_pitch, out_counts, eod_counts)
-  const bool uni = P.uni_cfg != 0;
-  if (writeback) { if (uni) FSK_LAUNCH_PIPE(true, true); else FSK_LAUNCH_PIPE(true, false); }
-  else { if (uni) FSK_LAUNCH_PIPE(false, true); else FSK_LAUNCH_PIPE(false, false); }
-#undef FSK_LAUNCH_PIPE
-  return hipGetLastError();
+  return launch_tiles(kPipeKernels[pipe_index(c.writeback, P)], 128, demod_pipe_lds_bytes(P), c, P, S, name);
 }
 
-hipError_t launch_demod_fused(bool writeback, bool append, const DemodParams &P, const DemodState &S, float *samples, size_t n,
-                              size_t pitch, uint8_t *out, size_t out_pitch, uint32_t *out_counts,
-                              uint32_t *eod_counts, hipStream_t stream) {
-  const uint32_t blocks = (P.n_streams + 63u) / 64u;
-  const size_t lds = demod_fused_lds_bytes(P);
-#define FSK_LAUNCH_FUSED(WBV, UNIV)                                                                          \
-  hipLaunchKernelGGL((demod_fused_kernel<WBV, UNIV>), dim3(blocks), dim3(64), lds, stream, P, S, samples, n, pitch, \
-                     append ? 1 : 0, out, out_pitch, out_counts, eod_counts)
-  const bool uni = P.uni_cfg != 0;
-  if (writeback) { if (uni) FSK_LAUNCH_FUSED(true, true); else FSK_LAUNCH_FUSED(true, false); }
-  else { if (uni) FSK_LAUNCH_FUSED(false, true); else FSK_LAUNCH_FUSED(false, false); }
-#undef FSK_LAUNCH_FUSED
-  return hipGetLastError();
+hipError_t launch_demod_fused(const DemodCall &c, const DemodParams &P, const DemodState &S, const char **name) {
+  return launch_tiles(kFusedKernels[pipe_index(c.writeback, P)], 64, demod_fused_lds_bytes(P), c, P, S, name);
 }
 
-hipError_t launch_demod_tail(bool writeback, bool append, int parity0, const DemodParams &P, const DemodState &S,
-                             float *samples, size_t n, size_t pitch, uint8_t *out, size_t out_pitch, uint32_t *out_counts,
-                             uint32_t *eod_counts, hipStream_t stream) {
-  const uint32_t blocks = (P.n_streams + 63u) / 64u;
-  const size_t lds = sizeof(uint32_t) * 64u * (P.d + 1u);
-#define FSK_LAUNCH_TAIL(WBV, UNIV)                                                                          \
-  hipLaunchKernelGGL((demod_tail_kernel<WBV, UNIV>), dim3(blocks), dim3(64), lds, stream, P, S, samples, n, pitch, \
-                     parity0, append ? 1 : 0, out, out_pitch, out_counts, eod_counts)
-  const bool uni = P.uni_cfg != 0;
-  if (writeback) { if (uni) FSK_LAUNCH_TAIL(true, true); else FSK_LAUNCH_TAIL(true, false); }
-  else { if (uni) FSK_LAUNCH_TAIL(false, true); else FSK_LAUNCH_TAIL(false, false); }
-#undef FSK_LAUNCH_TAIL
+hipError_t launch_demod_tail(const DemodCall &c, const DemodParams &P, const DemodState &S, int parity0, const char **name) {
+  const KernelEntry<TailFn> &k = kTailKernels[pipe_index(c.writeback, P)];
+  hipLaunchKernelGGL(k.fn, dim3((P.n_streams + 63u) / 64u), dim3(64), sizeof(uint32_t) * 64u * (P.d + 1u), c.stream, P, S, c.samples, c.n, c.pitch,
+                     parity0, c.append ? 1 : 0, c.out, c.out_pitch, c.out_counts, c.eod_counts);
+  *name = k.name;
   return hipGetLastError();
 }
 

@@ -22,9 +22,16 @@ namespace fsk {
 static __device__ int g_ablate;
 #define FSK_ABL_INIT const int abl_mask = __builtin_amdgcn_readfirstlane(g_ablate);
 #define FSK_ABL(w) (abl_mask & (1 << (w)))
+// host side, before a launch: this translation unit's g_ablate from the environment variable FSK_ABLATE
+static inline void set_ablate() {
+  const char *a = getenv("FSK_ABLATE");
+  const int v = a ? atoi(a) : 0;
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ablate), &v, sizeof(v));
+}
 #else
 #define FSK_ABL_INIT
 #define FSK_ABL(w) 0
+static inline void set_ablate() {}
 #endif
 
 // Wave stamps (-DFSK_STAMP builds only, tools/variants.py --stamps): every wave of the two- and three-wave kernels adds up
