@@ -28,7 +28,8 @@ extern "C" {
  * IIRFilter of fskhip_next.h (additions only).  7: fskhip_get_faults (additions only).  8: FSKHIP_E_HANDOFF -- every hand-off wait of
  * the multi-wave kernels is bounded ("Hand-off waits" below; an addition: no healthy call returns it); fskhip_remap_streams (an
  * addition, same version); stream snapshots -- fskhip_snapshot_bytes / _streams / _info_get / _stream_config / _concat,
- * fskhip_restore_streams (additions, same version). */
+ * fskhip_restore_streams (additions, same version); fskhip_processor_remap / _snapshot_bytes / _snapshot / _snapshot_info_get /
+ * _restore in fskhip_next.h (additions, same version). */
 #define FSKHIP_ABI_VERSION 8
 #define FSKHIP_MAX_PATTERN_BYTES 16
 
@@ -142,8 +143,8 @@ int fskhip_carry_over(fskhip_engine *dst, const fskhip_engine *src);
  * and the config of dst stream i equal to that of src stream map[i] in every fskhip_config field (per stream where the configs
  * are per stream).  A src that has reported FSKHIP_E_HANDOFF is refused with
  * that code.  Options set on dst stay dst's own (fskhip_set_option works on dst until its first demodulate call); traces are
- * not carried.  fskhip_processor objects (fskhip_next.h: RX rings, pending modulations) stay bound to their own engine and
- * are not remapped.
+ * not carried.  fskhip_processor objects (fskhip_next.h: RX rings, pending modulations) stay bound to their own engine; a
+ * processor created over dst continues them through fskhip_processor_remap, with the same map.
  * Lock step: dst takes over src's decimator phase and ring grid, so a lock-step fp32 src keeps dst on the whole-tile kernels,
  * new streams included (an empty ring placed at the engine's grid reads nothing before its own pushes).  dst leaves lock
  * step -- exactly as fskhip_reset of one stream does, and runs on the generic kernel, exact -- only where new streams meet
@@ -202,7 +203,7 @@ int fskhip_remap_streams(fskhip_engine *dst, const fskhip_engine *src, const int
  *                           "the engine the snapshot was taken of, at that moment" -- except the same-device precondition, which
  *                           is dropped, and "dst != src", which has no meaning.  A refused call leaves dst as it was.
  * Large batches cross in slabs of 8192 streams: two staging slabs on the device whatever the batch, the copy of one slab
- * overlapping the kernel of the next.  fskhip_processor objects (fskhip_next.h) stay out of snapshots, as they stay out of a remap.
+ * overlapping the kernel of the next.  fskhip_processor objects have an image of their own (fskhip_next.h: fskhip_processor_snapshot / _restore).
  */
 typedef struct fskhip_snapshot_info {
   uint32_t n_streams;

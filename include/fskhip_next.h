@@ -134,6 +134,71 @@ int fskhip_processor_rx_length_host(fskhip_processor *p, uint32_t *lengths);
  * FSKCore state is NOT reset (the reference does not either). */
 int fskhip_processor_reset(fskhip_processor *p, int64_t stream);
 
+/*
+ * Processor remapping and snapshots (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): the FSKProcessor row carried through the
+ * engine's lifecycle calls -- what the reference's host does by keeping or moving a whole FSKProcessor object together with its
+ * FSKCore.  fskhip_remap_streams / fskhip_snapshot_streams / fskhip_restore_streams (fskhip.h) carry the engine; these carry
+ * the processor over it.  The host makes the destination engine with those calls, creates a processor over it
+ * (fskhip_processor_create, the same rx_capacity), and moves the processor's state with the SAME map.  Synchronous host calls.
+ *
+ * fskhip_processor_remap: stream i of dst continues the processor of stream map[i] of src exactly as if that FSKProcessor
+ * object had been moved -- ring content, writeIndex, readIndex and _length verbatim; whether a modulation is pending (the
+ * empty-payload pending modulator that never completes included), its payload bytes and generator state (phase, sample
+ * position, bit cursor); the `completed` count -- or starts as new FSKProcessor() where map[i] = -1 (empty ring, nothing
+ * pending, completed 0).  A source stream may be named more than once (independent clones); those not named are dropped.
+ * src is read only and stays usable.  dst's payload store grows to what the carried payloads need; a captured quantum graph
+ * is never carried (FSKHIP_PROC_GRAPH captures afresh on dst).  FSKHIP_E_INVALID, with a message naming the first offending
+ * index or field and dst left as it was, unless: arguments non-null and dst != src; n_map == dst's stream count and every entry
+ * in range or -1; same device, equal rx_capacity; dst freshly created (no process, modulate, drain or reset call yet); the
+ * engine of dst stream i has the same fskhip_config as the engine of src stream map[i] (every field: the modulator's frame
+ * length and tones come from it, and a pending signal must continue bit for bit).
+ *
+ * A processor snapshot is a host-side image: plain little-endian bytes, no pointers, every byte defined; two snapshots of the
+ * same observable state are byte-identical.  An implementation-versioned checkpoint, not an archive.  Layout:
+ *   header, 48 bytes:  u32 magic "FSKP" (0x504B5346) | u32 format (1) | u32 header_bytes (48) | u32 record_bytes |
+ *                      u32 n_records | u32 rx_capacity | u32 payload_capacity | u32 0 |
+ *                      u64 checksum | u64 0
+ *     record_bytes = 64 + payload_capacity + rx_capacity rounded up to a multiple of 16; the image is header_bytes +
+ *     n_records x record_bytes long.  checksum: the stream snapshot's function -- over the image's little-endian u64 words w
+ *     with the checksum field taken as 0:  a += w, b += a  (mod 2^64);  checksum = a * 0x9E3779B97F4A7C15 ^ b.
+ *   records, stream-major, in selection order:
+ *     bytes  0..15   u32 writeIndex | u32 readIndex | u32 _length | u32 pendingModulation (0 / 1)
+ *     bytes 16..31   u32 completed | u32 samplePosition | u32 totalSamples (0: no signal) | u32 payload length
+ *     bytes 32..47   u32 samples into the current bit | u32 bit index | u32 current bit | u32 0
+ *     bytes 48..63   f64 phase | u64 0
+ *     then payload_capacity bytes of payload, then the ring (rx_capacity bytes, zeros up to the multiple of 16).
+ *   canonical form: ring bytes outside the live span [readIndex, readIndex + _length) (modulo rx_capacity) are zero; payload
+ *     bytes beyond the pending payload's length are zero; the seven generator words and the phase of a stream without a live
+ *     signal (not pending, or pending with totalSamples 0) are zero; payload_capacity is the longest pending payload among the
+ *     selected streams rounded up to 16 -- not whatever the source's payload store had grown to.
+ *
+ * fskhip_processor_snapshot_bytes  the bytes a snapshot of the selected streams takes (it depends on their pending payloads, so
+ *                           it takes the selection, not its size; synchronises with p's work).  0 for a null processor.
+ * fskhip_processor_snapshot write streams sel[0 .. n_sel) of p (sel NULL: all, in order; a stream may be named more than once)
+ *                           into buf.  Synchronises with p's outstanding work; p is read only and stays usable.  *written (may
+ *                           be NULL) receives the size; cap too small: FSKHIP_E_OVERFLOW, *written = the size needed.
+ * fskhip_processor_snapshot_info_get  what an image holds -- on the host, no device needed -- after validating it: magic,
+ *                           format, sizes, checksum, and every record's index words against the capacities.  Each flaw is
+ *                           FSKHIP_E_INVALID with a message that names it.
+ * fskhip_processor_restore  fskhip_processor_remap with the image standing in for src: map[i] names a RECORD, or is -1.  The
+ *                           same-device condition is dropped.  The config condition cannot be checked from the image and is
+ *                           the caller's duty: restore dst's engine from the stream snapshot taken at the same moment, with the
+ *                           same map (fskhip_restore_streams checks the configs).  Every other precondition of the remap
+ *                           applies; everything is validated before anything is written, a refused call leaves dst as it was.
+ * Large batches cross in slabs of 8192 streams, as stream snapshots do.  None of these calls returns -8.
+ */
+typedef struct fskhip_processor_snapshot_info {
+  uint32_t n_streams;          /* records in the image */
+  uint32_t rx_capacity;
+  uint32_t payload_capacity;   /* payload bytes per record */
+  uint32_t record_bytes;
+} fskhip_processor_snapshot_info;
+int fskhip_processor_remap(fskhip_processor *dst, const fskhip_processor *src, const int64_t *map, uint32_t n_map);
+size_t fskhip_processor_snapshot_bytes(const fskhip_processor *p, const int64_t *sel, uint32_t n_sel);
+int fskhip_processor_snapshot(fskhip_processor *p, const int64_t *sel, uint32_t n_sel, void *buf, size_t cap, size_t *written);
+int fskhip_processor_snapshot_info_get(const void *buf, size_t size, fskhip_processor_snapshot_info *info);
+int fskhip_processor_restore(fskhip_processor *dst, const void *buf, size_t size, const int64_t *map, uint32_t n_map);
+
 /* ---------------------------------------------------------------------------------------------------
  * FIR half of src/dsp/filters.ts: FIRFilter (112-167) batched over streams, and the windowed-sinc designs
  * (243-314) + FilterFactory.createFIR* (346-368).

@@ -1,8 +1,11 @@
 // Typings of napi/fsk-processor.js and napi/chunked-modulator.js (src/webaudio/processors/fsk-processor.ts,
 // src/webaudio/chunked-modulator.ts on the device).
-import { FSKBatch, FSKCore, FSKStatus } from './fsk-core';
+import { FSKBatch, FSKConfig, FSKCore, FSKStatus } from './fsk-core';
 export declare const PROC_CLEAR_RX_ON_TX_COMPLETE: 1;
 export declare const PROC_GRAPH: 2;
+/** FSKProcessorBatch.snapshot(): the FSKBatch's stream snapshot and the processors' own image */
+export interface ProcessorBatchSnapshot { engine: Buffer; processor: Buffer; }
+export declare function processorSnapshotInfo(buf: Uint8Array): { nStreams: number; rxCapacity: number; payloadCapacity: number; recordBytes: number };
 export declare class FSKProcessorBatch {
   constructor(batch: FSKBatch, options?: { rxCapacity?: number; clearRxOnTxComplete?: boolean; useGraph?: boolean });
   readonly nStreams: number;
@@ -16,6 +19,11 @@ export declare class FSKProcessorBatch {
   rxLengths(): Uint32Array;
   reset(stream?: number): void;
   status(stream?: number): FSKStatus & { demodulatedBufferLength: number; pendingModulation: boolean; fskCoreReady: boolean; processDemodulationCallCount: number };
+  /** a new batch whose stream i continues stream map[i] of this one (FSKCore, ring, pending modulation), -1: a new stream */
+  remap(map: ArrayLike<number>, configs?: Partial<FSKConfig> | Partial<FSKConfig>[]): FSKProcessorBatch;
+  snapshot(streams?: ArrayLike<number>): ProcessorBatchSnapshot;
+  static fromSnapshot(snap: ProcessorBatchSnapshot, map?: ArrayLike<number>, configs?: Partial<FSKConfig> | Partial<FSKConfig>[], device?: number,
+    options?: { clearRxOnTxComplete?: boolean; useGraph?: boolean }): FSKProcessorBatch;
   close(): void;
 }
 export interface ChunkResult { signal: Float32Array; isComplete: boolean; samplesConsumed: number; totalSamples: number; }

@@ -2,9 +2,11 @@
 // FSKProcessorBatch: S instances of the reference's FSKProcessor (src/webaudio/processors/fsk-processor.ts) on one
 // GPU.  process(inputs, nOut) is process() for every stream in one call: demodulated bytes go into per-stream RX
 // rings on the device, pending modulations are fed from the device; modulate / demodulate / reset / status mirror
-// the worklet's message handlers (without the waiting: callers poll).
+// the worklet's message handlers (without the waiting: callers poll).  remap / snapshot / fromSnapshot carry the rings and
+// pending modulations along with the batch's streams (FSKBatch.remap / snapshot / fromSnapshot underneath).
 const path = require('path');
 const addon = require(path.join(__dirname, 'fsk_addon.node'));
+const { FSKBatch } = require(path.join(__dirname, 'fsk-core.js'));
 const PROC_CLEAR_RX_ON_TX_COMPLETE = 1, PROC_GRAPH = 2;
 
 class FSKProcessorBatch {
@@ -18,6 +20,50 @@ class FSKProcessorBatch {
     this.processDemodulationCallCount = 0;
   }
   close() { if (this.handle) { addon.processorDestroy(this.handle); this.handle = null; } }
+
+  _options() {
+    return { rxCapacity: this.rxCapacity, clearRxOnTxComplete: !!(this.flags & PROC_CLEAR_RX_ON_TX_COMPLETE), useGraph: !!(this.flags & PROC_GRAPH) };
+  }
+  // a new FSKProcessorBatch of map.length streams whose stream i continues stream map[i] of this one -- its FSKCore (FSKBatch.remap)
+  // and its FSKProcessor: ring, pending modulation, completed count -- or starts as a new one where map[i] is -1.  The new
+  // processor batch owns its FSKBatch (close both); this one is left as it is.  processDemodulationCallCount is carried.
+  remap(map, configs) {
+    const m = Array.from(map, Number);
+    const batch = this.batch.remap(m, configs);
+    let next = null;
+    try {
+      next = new FSKProcessorBatch(batch, this._options());
+      addon.processorRemap(next.handle, this.handle, m);
+    } catch (err) {
+      if (next) next.close();
+      batch.close();
+      throw err;
+    }
+    next.processDemodulationCallCount = this.processDemodulationCallCount;
+    return next;
+  }
+  // {engine, processor}: the FSKBatch's snapshot and the processors' own image, two Buffers taken at one moment
+  snapshot(streams) {
+    const sel = streams === undefined || streams === null ? null : Array.from(streams, Number);
+    return { engine: this.batch.snapshot(sel), processor: addon.processorSnapshot(this.handle, sel) };
+  }
+  // a new FSKProcessorBatch whose stream i continues RECORD map[i] of both images (-1: a new stream; undefined: every record in
+  // order).  options: useGraph, clearRxOnTxComplete; rxCapacity is the image's.  processDemodulationCallCount starts at 0.
+  static fromSnapshot(snap, map, configs, device, options = {}) {
+    const info = addon.processorSnapshotInfo(snap.processor);
+    const m = map === undefined || map === null ? Array.from({ length: info.nStreams }, (_, i) => i) : Array.from(map, Number);
+    const batch = FSKBatch.fromSnapshot(snap.engine, m, configs, device);
+    let next = null;
+    try {
+      next = new FSKProcessorBatch(batch, Object.assign({}, options, { rxCapacity: info.rxCapacity }));
+      addon.processorRestore(next.handle, snap.processor, m);
+    } catch (err) {
+      if (next) next.close();
+      batch.close();
+      throw err;
+    }
+    return next;
+  }
 
   // process(inputs, outputs) fsk-processor.ts:152-167.  inputs: Float32Array [S][nIn] or null; returns Float32Array [S][nOut] or null
   process(inputs, nIn, nOut) {
@@ -54,4 +100,5 @@ class FSKProcessorBatch {
       fskCoreReady: true, processDemodulationCallCount: this.processDemodulationCallCount }, this.batch.getStatus(stream));
   }
 }
-module.exports = { FSKProcessorBatch, PROC_CLEAR_RX_ON_TX_COMPLETE, PROC_GRAPH };
+const processorSnapshotInfo = (buf) => addon.processorSnapshotInfo(buf);
+module.exports = { FSKProcessorBatch, processorSnapshotInfo, PROC_CLEAR_RX_ON_TX_COMPLETE, PROC_GRAPH };

@@ -11,6 +11,8 @@
 //   processorModulate(handle, payloads: Uint8Array, lens: Uint32Array, pitch, mask: Uint8Array|null)
 //   processorTxState(handle) -> {pos, total, pending, completed};  processorRxLength(handle) -> Uint32Array
 //   processorDrain(handle, capacity) -> {out, outPitch, counts};  processorReset(handle, stream)
+//   processorRemap(dst, src, map: number[]);  processorSnapshot(handle, sel: number[]|null) -> Buffer
+//   processorRestore(dst, snapshot: Uint8Array, map: number[]);  processorSnapshotInfo(snapshot) -> {nStreams, rxCapacity, payloadCapacity, recordBytes}
 //   sincLowpass/sincHighpass(cutoff, sampleRate, numTaps), sincBandpass(center, bandwidth, sampleRate, numTaps) -> Float64Array
 //   firCreate(taps: Float64Array, nStreams, device, precision) -> handle;  firDestroy(handle)
 //   firProcess(handle, input: Float32Array, n, pitch, nStreams) -> Float32Array;  firReset(handle, stream)
@@ -287,6 +289,92 @@ napi_value ProcessorReset(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// ---- processor remap / snapshots (include/fskhip_next.h): a snapshot is a Buffer (or any Uint8Array) on this side
+bool index_array(napi_env env, napi_value arr, const char *what, std::vector<int64_t> *out) {
+  bool is_arr = false;
+  if (napi_is_array(env, arr, &is_arr) != napi_ok || !is_arr) { napi_throw_type_error(env, nullptr, what); return false; }
+  uint32_t n = 0;
+  napi_get_array_length(env, arr, &n);
+  out->resize(n);
+  for (uint32_t i = 0; i < n; i++) {
+    napi_value v;
+    double d = 0;
+    if (napi_get_element(env, arr, i, &v) != napi_ok || napi_get_value_double(env, v, &d) != napi_ok || d != (double)(int64_t)d) {
+      napi_throw_type_error(env, nullptr, what);
+      return false;
+    }
+    (*out)[i] = (int64_t)d;
+  }
+  return true;
+}
+
+napi_value ProcessorRemap(napi_env env, napi_callback_info info) {
+  ARGS(3);
+  Proc *dst = get_proc(env, argv[0]);
+  if (!dst) return nullptr;
+  Proc *src = get_proc(env, argv[1]);
+  if (!src) return nullptr;
+  std::vector<int64_t> map;
+  if (!index_array(env, argv[2], "processorRemap: map must be an Array of integer stream indices (-1: a new stream)", &map)) return nullptr;
+  static const int64_t none = 0;
+  int rc = fskhip_processor_remap(dst->p, src->p, map.empty() ? &none : map.data(), (uint32_t)map.size());
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+
+napi_value ProcessorSnapshot(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  Proc *h = get_proc(env, argv[0]);
+  if (!h) return nullptr;
+  std::vector<int64_t> sel;
+  napi_valuetype t;
+  NAPI_OK(napi_typeof(env, argv[1], &t));
+  const bool all = t == napi_undefined || t == napi_null;
+  if (!all && !index_array(env, argv[1], "processorSnapshot: sel must be an Array of integer stream indices", &sel)) return nullptr;
+  static const int64_t none = 0;
+  const int64_t *sp = all ? nullptr : (sel.empty() ? &none : sel.data());
+  const uint32_t n = all ? h->S : (uint32_t)sel.size();
+  size_t need = 0;
+  int rc = fskhip_processor_snapshot(h->p, sp, n, nullptr, 0, &need);   // (the size: it depends on the pending payloads)
+  if (rc != FSKHIP_E_OVERFLOW) return throw_fsk(env, rc);
+  void *data = nullptr;
+  napi_value buf;
+  NAPI_OK(napi_create_buffer(env, need, &data, &buf));
+  rc = fskhip_processor_snapshot(h->p, sp, n, data, need, nullptr);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return buf;
+}
+
+napi_value ProcessorRestore(napi_env env, napi_callback_info info) {
+  ARGS(3);
+  Proc *dst = get_proc(env, argv[0]);
+  if (!dst) return nullptr;
+  void *data; size_t size;
+  if (!typed(env, argv[1], napi_uint8_array, &data, &size)) return nullptr;
+  std::vector<int64_t> map;
+  if (!index_array(env, argv[2], "processorRestore: map must be an Array of integer record indices (-1: a new stream)", &map)) return nullptr;
+  static const int64_t none = 0;
+  int rc = fskhip_processor_restore(dst->p, data, size, map.empty() ? &none : map.data(), (uint32_t)map.size());
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+
+napi_value ProcessorSnapshotInfo(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  void *data; size_t size;
+  if (!typed(env, argv[0], napi_uint8_array, &data, &size)) return nullptr;
+  fskhip_processor_snapshot_info si;
+  int rc = fskhip_processor_snapshot_info_get(data, size, &si);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  set_u32(env, o, "nStreams", si.n_streams);
+  set_u32(env, o, "rxCapacity", si.rx_capacity);
+  set_u32(env, o, "payloadCapacity", si.payload_capacity);
+  set_u32(env, o, "recordBytes", si.record_bytes);
+  return o;
+}
+
 // ---- FIR ------------------------------------------------------------------------------------------------
 napi_value sinc_result(napi_env env, int n, const std::vector<double> &t) {
   if (n < 0) return throw_fsk(env, n);
@@ -449,6 +537,10 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"processorRxLength", nullptr, ProcessorRxLength, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorDrain", nullptr, ProcessorDrain, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorReset", nullptr, ProcessorReset, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"processorRemap", nullptr, ProcessorRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"processorSnapshot", nullptr, ProcessorSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"processorRestore", nullptr, ProcessorRestore, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"processorSnapshotInfo", nullptr, ProcessorSnapshotInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"sincLowpass", nullptr, SincLowpass, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"sincHighpass", nullptr, SincHighpass, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"sincBandpass", nullptr, SincBandpass, nullptr, nullptr, nullptr, napi_default, nullptr},

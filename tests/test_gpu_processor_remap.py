@@ -1,0 +1,467 @@
+"""FSKProcessorBatch through remap, snapshot and restore on the GPU (include/fskhip_next.h: fskhip_processor_remap /
+_snapshot / _restore): a processor row -- RX ring, pending modulation, completed count -- must continue exactly as if the
+reference's FSKProcessor object had been moved, cloned or newly created.  Checked against the CPU oracle over a random
+schedule with three remaps, against the golden runs captured from the real FSKProcessor, and image against image."""
+import copy
+import ctypes as C
+import hashlib
+
+import numpy as np
+import pytest
+
+from conftest import golden_next
+
+pytestmark = pytest.mark.gpu
+
+CFG = dict(baudRate=1200, markFrequency=1200, spaceFrequency=2200)
+
+
+def _rng(seed):
+    return np.random.default_rng(seed)
+
+
+def _tracked_oracle(cfg, rx_capacity):
+    """A ProcessorOracle whose copy.deepcopy is an independent clone.  The oracle's FSKCore lives behind a C handle that cannot be
+    copied, so the clone is a new oracle that replays the original's calls."""
+    from oracle import next_oracle as no
+    from oracle import pyoracle as po
+
+    class Tracked(no.ProcessorOracle):
+        def __init__(self):
+            super().__init__(po.OracleCore(cfg), rx_capacity=rx_capacity)
+            self.log = []
+
+        def modulate(self, data):
+            self.log.append(("modulate", bytes(data)))
+            return super().modulate(data)
+
+        def process(self, inp, n_out):
+            self.log.append(("process", None if inp is None else np.array(inp, np.float32), n_out))
+            return super().process(inp, n_out)
+
+        def demodulate(self):
+            self.log.append(("demodulate",))
+            return super().demodulate()
+
+        def __deepcopy__(self, memo):
+            twin = Tracked()
+            for op in self.log:
+                getattr(twin, op[0])(*op[1:])
+            return twin
+
+    return Tracked()
+
+
+def _frame_row(r, length, first):
+    """an RX input row: silence, then from sample `first` on (plus a random even lead) one frame of 20..60 bytes"""
+    from oracle import pyoracle as po
+    row = np.zeros(length, np.float32)
+    sig = po.OracleCore(CFG).modulate(r.integers(0, 256, int(r.integers(20, 61)), dtype=np.uint8).tobytes())
+    at = first + int(r.integers(0, 200)) * 2
+    k = max(0, min(len(sig), length - at))
+    row[at:at + k] = sig[:k]
+    return row
+
+
+# the three remaps of the schedule, by quantum: the batch shrinks, grows with new streams, is permuted with clones
+def _maps(r):
+    shrink = np.sort(r.choice(70, 50, replace=False)).astype(np.int64)
+    grow = np.concatenate([np.arange(50), -np.ones(14)]).astype(np.int64)
+    r.shuffle(grow)
+    perm = r.integers(0, 64, 64).astype(np.int64)          # with replacement: some sources twice, some dropped
+    assert len(set(perm)) < 64
+    return {175: shrink, 240: grow, 300: perm}
+
+
+def _run_schedule(use_graph, how):
+    """test_processor_batch_random_schedule_matches_oracle's schedule (70 streams, 128-sample quanta, rx_capacity 48, fp64, masked
+    modulations, drains) with three remaps; how = "remap": FSKProcessorBatch.remapped, "snapshot": snapshot -> close ->
+    from_snapshot.  Returns a digest of every output, drain and counter."""
+    import webaudio_modem_amd as wm
+    S, Q, n, cap = 70, 420, 128, 48
+    r = _rng(0xF1B)
+    maps = _maps(_rng(0x3A9))
+    eng = wm.FSKEngine(S, CFG, precision=wm.PRECISION_F64)
+    proc = wm.FSKProcessorBatch(eng, rx_capacity=cap, use_graph=use_graph)
+    oracles = [_tracked_oracle(CFG, cap) for _ in range(S)]
+    x = np.stack([_frame_row(r, Q * n, 0) for _ in range(S)])
+    tx_at = set(int(q) for q in r.choice(np.arange(5, 400), 9, replace=False)) | {165, 171, 236, 296}
+    drain_at = {100, 250, 330, 419}
+    digest = hashlib.sha256()
+    for q in range(Q):
+        if q in maps:
+            m = maps[q]
+            if q == 175:   # what the first remap must carry: signals under way, rings that hold bytes across the wrap
+                st = proc.tx_state()
+                assert np.count_nonzero(st["pendingModulation"] & (st["samplePosition"] > 0)) >= 5
+                assert sum(1 for o in oracles if o.ring.length > 0 and o.ring.r + o.ring.length > cap) >= 5
+            if how == "remap":
+                nxt = proc.remapped(m)
+                assert list(proc.rx_lengths()) == [o.ring.length for o in oracles]    # the source stays usable, unchanged
+                proc.close()
+                eng.close()
+            else:
+                snap = proc.snapshot()
+                assert isinstance(snap.engine, bytes) and isinstance(snap.processor, bytes)
+                proc.close()
+                eng.close()
+                nxt = wm.FSKProcessorBatch.from_snapshot(snap, m, use_graph=use_graph)
+            proc, eng = nxt, nxt.engine
+            seen, moved = set(), []
+            for v in m:
+                v = int(v)
+                moved.append(_tracked_oracle(CFG, cap) if v < 0 else copy.deepcopy(oracles[v]) if v in seen else oracles[v])
+                seen.add(v)
+            oracles = moved
+            x = np.stack([x[v] if v >= 0 else _frame_row(r, Q * n, q * n) for v in m])
+            S = len(m)
+            assert proc.n_streams == S and list(proc.rx_lengths()) == [o.ring.length for o in oracles]
+            assert list(proc.tx_state()["completed"]) == [o.completed for o in oracles]
+        if q in tx_at:
+            pend = proc.tx_state()["pendingModulation"]
+            assert list(pend) == [o.pending is not None for o in oracles]
+            mask = (r.random(S) < 0.4) & ~pend
+            payloads = [r.integers(0, 256, int(r.integers(0, 12)), dtype=np.uint8).tobytes() for _ in range(S)]
+            proc.modulate(payloads, mask=list(mask))
+            for s in range(S):
+                if mask[s]:
+                    oracles[s].modulate(payloads[s])
+        out = proc.process(x[:, q * n:(q + 1) * n], n)
+        digest.update(out.tobytes())
+        for s in range(S):
+            want = oracles[s].process(x[s, q * n:(q + 1) * n], n)
+            assert np.array_equal(out[s], want), (q, s)
+        if q in drain_at:
+            got = proc.demodulate()
+            for s in range(S):
+                assert got[s] == oracles[s].demodulate(), (q, s)
+                digest.update(got[s])
+        if q % 47 == 0 or q in maps:
+            lens = proc.rx_lengths()
+            assert list(lens) == [o.ring.length for o in oracles], q
+            digest.update(lens.tobytes())
+    st = proc.tx_state()
+    assert list(st["completed"]) == [o.completed for o in oracles]
+    assert sum(st["completed"]) > 20
+    digest.update(st["completed"].tobytes())
+    proc.close()
+    eng.close()
+    return digest.hexdigest()
+
+
+_DIGESTS = {}
+
+
+def _digest(use_graph, how):
+    if (use_graph, how) not in _DIGESTS:
+        _DIGESTS[use_graph, how] = _run_schedule(use_graph, how)
+    return _DIGESTS[use_graph, how]
+
+
+@pytest.mark.parametrize("use_graph", [False, True], ids=["launches", "graph"])
+def test_random_schedule_with_remaps_matches_oracle(use_graph):
+    _digest(use_graph, "remap")
+
+
+@pytest.mark.parametrize("use_graph", [False, True], ids=["launches", "graph"])
+def test_random_schedule_with_snapshot_restore_matches_oracle_and_remap(use_graph):
+    assert _digest(use_graph, "snapshot") == _digest(use_graph, "remap")
+
+
+# ---------------------------------------------------------------- images ----------------
+def _feed(proc, x, q0, q1, n=128):
+    for q in range(q0, q1):
+        proc.process(x[:, q * n:(q + 1) * n], n)
+
+
+def test_images_are_deterministic_and_canonical():
+    import webaudio_modem_amd as wm
+    S, n, cap = 40, 128, 48
+    r = _rng(0xCA11)
+    x = np.stack([_frame_row(r, 200 * n, 0) for _ in range(S)])
+    last = [r.integers(0, 256, int(r.integers(1, 12)), dtype=np.uint8).tobytes() for _ in range(S)]
+    mask = [s % 3 != 0 for s in range(S)]
+    images, batches = [], []
+    for history in ("plain", "other"):
+        eng = wm.FSKEngine(S, CFG, precision=wm.PRECISION_F64)
+        proc = wm.FSKProcessorBatch(eng, rx_capacity=cap, clear_rx_on_tx_complete=False)
+        # an earlier modulation, cancelled by reset(): the other history's payload is longer, so its payload store is wider and
+        # holds stale bytes behind every later payload; it also drains along the way, so its rings were read at other places
+        proc.modulate([bytes([s]) * (100 if history == "other" else 30) for s in range(S)])
+        _feed(proc, x, 0, 30)
+        if history == "other":
+            proc.demodulate()
+        _feed(proc, x, 30, 60)
+        proc.demodulate()
+        proc.reset()
+        proc.modulate(last, mask=mask)
+        _feed(proc, x, 60, 75)
+        a, b = proc.snapshot(), proc.snapshot()
+        assert a.processor == b.processor and a.engine == b.engine              # two snapshots of one state
+        images.append(a)
+        batches.append((proc, eng))
+    st = batches[0][0].tx_state()
+    assert np.count_nonzero(st["pendingModulation"] & (st["samplePosition"] > 0)) >= 10 and batches[0][0].rx_lengths().max() > 0
+    assert batches[1][0].tx_state()["completed"].tolist() == st["completed"].tolist()
+    assert images[0].processor == images[1].processor                           # same observable state, another history
+    info = wm.processor_snapshot_info(images[0].processor)
+    assert info["n_streams"] == S and info["rx_capacity"] == cap
+    assert info["payload_capacity"] == 16 and info["record_bytes"] == 64 + 16 + 48   # the longest PENDING payload (<= 11 bytes), not the store's pitch
+    # a restored batch's snapshot is the image it came from (identity map), in both images
+    back = wm.FSKProcessorBatch.from_snapshot(images[0], clear_rx_on_tx_complete=False)
+    again = back.snapshot()
+    assert again.processor == images[0].processor
+    # a selection is the matching records, the payload capacity its own
+    idx = [s for s in range(S) if not mask[s]][:5]
+    part = batches[0][0].snapshot(idx)
+    assert wm.processor_snapshot_info(part.processor)["payload_capacity"] == 0
+    rb = info["record_bytes"]
+    for k, s in enumerate(idx):
+        whole = images[0].processor[48 + s * rb:48 + (s + 1) * rb]
+        assert part.processor[48 + k * (rb - 16):48 + (k + 1) * (rb - 16)] == whole[:64] + whole[64 + 16:]
+    back.engine.close()
+    back.close()
+    for proc, eng in batches:
+        proc.close()
+        eng.close()
+
+
+def test_remap_equals_restore_word_for_word():
+    import webaudio_modem_amd as wm
+    S, n, cap = 90, 128, 48
+    r = _rng(0xE0E0)
+    x = np.stack([_frame_row(r, 160 * n, 0) for _ in range(S)])
+    eng = wm.FSKEngine(S, CFG, precision=wm.PRECISION_F64)
+    src = wm.FSKProcessorBatch(eng, rx_capacity=cap)
+    _feed(src, x, 0, 70)
+    src.modulate([r.integers(0, 256, int(r.integers(0, 40)), dtype=np.uint8).tobytes() for _ in range(S)], mask=list(r.random(S) < 0.6))
+    _feed(src, x, 70, 80)
+    m = r.integers(-1, S, 75).astype(np.int64)
+    a = src.remapped(m)
+    b = wm.FSKProcessorBatch.from_snapshot(src.snapshot(), m)
+    ta, tb = a.tx_state(), b.tx_state()
+    assert np.count_nonzero(ta["pendingModulation"]) > 10 and np.count_nonzero(ta["totalSamples"] == 0) > 0
+    for k in ("samplePosition", "totalSamples", "pendingModulation", "completed"):
+        assert np.array_equal(ta[k], tb[k]), k
+    assert np.array_equal(a.rx_lengths(), b.rx_lengths()) and a.rx_lengths().max() > 0
+    assert a.snapshot().processor == b.snapshot().processor
+    xm = np.stack([x[v] if v >= 0 else np.zeros(x.shape[1], np.float32) for v in m])
+    for q in range(80, 120):
+        oa, ob = a.process(xm[:, q * n:(q + 1) * n], n), b.process(xm[:, q * n:(q + 1) * n], n)
+        assert np.array_equal(oa, ob), q
+        if q == 85:
+            assert a.demodulate() == b.demodulate()
+    assert a.demodulate() == b.demodulate()
+    assert np.array_equal(a.tx_state()["completed"], b.tx_state()["completed"])
+    for p in (a, b, src):
+        p.engine.close()
+        p.close()
+
+
+# ---------------------------------------------------------------- golden runs of the real FSKProcessor ----------------
+@pytest.mark.parametrize("name", [r["name"] for r in golden_next().manifest["processor"]])
+def test_golden_processor_runs_survive_an_identity_remap(name):
+    import webaudio_modem_amd as wm
+    from oracle import pyoracle as po
+    from test_oracle_next import rx_run_input
+    g = golden_next()
+    run = next(r for r in g.manifest["processor"] if r["name"] == name)
+    S = 3
+    eng = wm.FSKEngine(S, run["config"], precision=wm.PRECISION_F64)
+
+    def remap(proc):
+        nxt = proc.remapped(np.arange(S))
+        proc.engine.close()
+        proc.close()
+        return nxt
+
+    if run["kind"] == "rx":
+        proc = wm.FSKProcessorBatch(eng, rx_capacity=run["ring_capacity"])
+        buf = rx_run_input(lambda: po.OracleCore(run["config"]), run)
+        drains = {d["quantum"]: d["bytes"] for d in run["drains"]}
+        probe = dict(map(tuple, run["length_probe"]))
+        for q in range(run["quanta"]):
+            if q == run["quanta"] // 2:
+                proc = remap(proc)
+            proc.process(np.tile(buf[q * 128:(q + 1) * 128], (S, 1)), 0)
+            if q in drains:
+                for got in proc.demodulate():
+                    assert list(got) == drains[q], (name, q)
+            if q in probe and q % 64 == 0:
+                assert list(proc.rx_lengths()) == [probe[q]] * S, (name, q)
+        for got in proc.demodulate():
+            assert list(got) == drains[run["quanta"]]
+    else:
+        proc = wm.FSKProcessorBatch(eng)
+        direct = po.OracleCore(run["config"]).modulate(bytes(run["payload"]))
+        outs, complete_at = [], -1
+        for q in range(run["quanta"]):
+            if q == run["start_quantum"]:
+                proc.modulate([bytes(run["payload"])] * S)
+            if q == (run["start_quantum"] + run["complete_at"]) // 2:
+                st = proc.tx_state()
+                assert all(st["pendingModulation"]) and all(0 < p < run["total"] for p in st["samplePosition"])    # inside the signal
+                proc = remap(proc)
+            before = proc.tx_state()["completed"].copy()
+            outs.append(proc.process(None, 128))
+            if proc.tx_state()["completed"][0] != before[0]:
+                complete_at = q
+        assert complete_at == run["complete_at"]
+        out = np.concatenate(outs, axis=1)
+        want = np.zeros(out.shape[1], np.float32)
+        k = run["start_quantum"] * 128
+        want[k:k + len(direct)] = direct
+        for s in range(S):
+            assert np.array_equal(out[s], want), (name, s)
+        assert not any(proc.tx_state()["pendingModulation"])
+    proc.engine.close()
+    proc.close()
+
+
+def test_fp32_pending_signal_continues_as_the_engines_modulator():
+    """fp32 engines generate with the device's sin(): the reference signal is the same engine's fskhip_modulate output."""
+    import webaudio_modem_amd as wm
+    S, n = 70, 128
+    r = _rng(0xF32)
+    eng = wm.FSKEngine(S, CFG, precision=wm.PRECISION_F32)
+    payloads = [r.integers(0, 256, int(r.integers(1, 30)), dtype=np.uint8).tobytes() for _ in range(S)]
+    direct = eng.modulate_data(payloads)
+    proc = wm.FSKProcessorBatch(eng)
+    proc.modulate(payloads)
+    outs = [proc.process(None, n) for _ in range(9)]
+    m = r.permutation(S).astype(np.int64)
+    nxt = proc.remapped(m)
+    outs_after = [nxt.process(None, n) for _ in range(120)]
+    a, b = np.concatenate(outs, axis=1), np.concatenate(outs_after, axis=1)
+    for i, v in enumerate(m):
+        sig = np.asarray(direct[v], np.float32)
+        want = np.zeros(a.shape[1] + b.shape[1], np.float32)
+        want[:len(sig)] = sig
+        assert np.array_equal(a[v], want[:a.shape[1]]), v
+        assert np.array_equal(b[i], want[a.shape[1]:]), (i, v)          # the same slice of the same engine's signal, across the remap
+    assert list(nxt.tx_state()["completed"]) == [1] * S
+    for p in (proc, nxt):
+        p.engine.close()
+        p.close()
+
+
+# ---------------------------------------------------------------- refusals ----------------
+def test_preconditions_are_refused_and_leave_both_sides_as_they_were():
+    import webaudio_modem_amd as wm
+    from webaudio_modem_amd import _lib
+    L = _lib.lib()
+    S, n, cap = 12, 128, 48
+    r = _rng(0xBAD)
+    x = np.stack([_frame_row(r, 80 * n, 0) for _ in range(S)])
+    cfgs = [dict(CFG, markFrequency=1200 + 10 * s) for s in range(S)]
+    eng = wm.FSKEngine(S, cfgs, precision=wm.PRECISION_F64)
+    src = wm.FSKProcessorBatch(eng, rx_capacity=cap)
+    src.modulate([b"payload!"] * S)
+    _feed(src, x, 0, 60)
+    before = (src.rx_lengths().copy(), {k: v.copy() for k, v in src.tx_state().items()}, src.snapshot().processor)
+    assert before[0].max() > 0
+    image = before[2]
+    blob = np.frombuffer(image, np.uint8)
+
+    def remap(dst, m):
+        a = np.ascontiguousarray(m, np.int64)
+        rc = L.fskhip_processor_remap(dst._h, src._h, a.ctypes.data, len(a))
+        return rc, L.fskhip_last_error().decode()
+
+    def restore(dst, m):
+        a = np.ascontiguousarray(m, np.int64)
+        rc = L.fskhip_processor_restore(dst._h, blob.ctypes.data, blob.nbytes, a.ctypes.data, len(a))
+        return rc, L.fskhip_last_error().decode()
+
+    ident = np.arange(S)
+    deng = wm.FSKEngine(S, cfgs, precision=wm.PRECISION_F64)
+    for call, the in ((remap, "the source has 12 streams"), (restore, "the snapshot has 12 records")):
+        fn = "fskhip_processor_remap" if call is remap else "fskhip_processor_restore"
+        dst = wm.FSKProcessorBatch(deng, rx_capacity=cap)
+        rc, msg = call(dst, ident[:-1])
+        assert rc == _lib.E_INVALID and "n_map 11" in msg and fn in msg, msg
+        bad = ident.copy()
+        bad[7] = S
+        rc, msg = call(dst, bad)
+        assert rc == _lib.E_INVALID and "map[7] = 12" in msg and the in msg, msg
+        bad[3] = -2
+        rc, msg = call(dst, bad)
+        assert rc == _lib.E_INVALID and "map[3] = -2" in msg, msg
+        other = wm.FSKProcessorBatch(deng, rx_capacity=64)
+        rc, msg = call(other, ident)
+        assert rc == _lib.E_INVALID and "rx_capacity" in msg and "64" in msg and "48" in msg, msg
+        other.close()
+        if call is remap:
+            swapped = ident.copy()
+            swapped[[4, 5]] = [5, 4]
+            rc, msg = call(dst, swapped)
+            assert rc == _lib.E_INVALID and "config of stream 4" in msg and "source stream 5" in msg, msg
+            assert L.fskhip_processor_remap(src._h, src._h, ident.ctypes.data, S) == _lib.E_INVALID
+            assert "same processor" in L.fskhip_last_error().decode()
+        # after every refusal dst still works as a fresh processor ...
+        assert not dst.rx_lengths().any() and not dst.tx_state()["pendingModulation"].any() and not dst.tx_state()["completed"].any()
+        used = wm.FSKProcessorBatch(deng, rx_capacity=cap)
+        used.reset()
+        rc, msg = call(used, ident)
+        assert rc == _lib.E_INVALID and "used already" in msg, msg
+        used.close()
+        # ... and takes the state once the call is right
+        rc, msg = call(dst, ident)
+        assert rc == 0, msg
+        assert np.array_equal(dst.rx_lengths(), before[0]) and dst.snapshot().processor == image
+        dst.close()
+    # src is unchanged
+    assert np.array_equal(src.rx_lengths(), before[0])
+    for k, v in src.tx_state().items():
+        assert np.array_equal(v, before[1][k]), k
+    assert src.snapshot().processor == image
+    small = (C.c_char * 64)()
+    w = C.c_size_t(0)
+    assert L.fskhip_processor_snapshot(src._h, None, 0, small, 64, C.byref(w)) == _lib.E_OVERFLOW and w.value == len(image)
+    assert L.fskhip_processor_snapshot_bytes(src._h, None, 0) == len(image)
+    src.close()
+    eng.close()
+    deng.close()
+
+
+# ---------------------------------------------------------------- size ----------------
+def test_65536_streams_random_permutation_half_full_rings():
+    import webaudio_modem_amd as wm
+    from oracle import pyoracle as po
+    S, cap, n = 65536, 1024, 128
+    r = _rng(0x10000)
+    eng = wm.FSKEngine(S, CFG, precision=wm.PRECISION_F32)
+    src = wm.FSKProcessorBatch(eng, rx_capacity=cap, clear_rx_on_tx_complete=False)
+    # 64 groups of streams hear the same two 255-byte frames, group g a byte time (400 samples) later than group g - 1, to the
+    # end; one drain on the way, inside the first frame, takes a byte less from every later group: rings about half full, of 64
+    # different lengths, whose live spans start at 64 different places
+    frames = [po.OracleCore(CFG).modulate(bytes((37 * k + j) & 0xFF for j in range(255))) for k in range(2)]
+    line = np.concatenate([np.zeros(512, np.float32)] + [np.concatenate([f, np.zeros(800, np.float32)]) for f in frames] + [np.zeros(66 * 400, np.float32)])
+    quanta = len(line) // n
+    padded = np.concatenate([np.zeros(64 * 400, np.float32), line])
+    group = (np.arange(S) % 64).astype(np.int64)
+    for q in range(quanta):
+        rows = np.stack([padded[(64 - g) * 400 + q * n:(64 - g) * 400 + (q + 1) * n] for g in range(64)])
+        src.process(rows[group], 0)
+        if q == quanta // 8:
+            src.demodulate()
+    lens = src.rx_lengths()
+    assert lens.max() <= cap and np.median(lens) >= cap // 4 and len(set(lens.tolist())) > 32
+    src.modulate([bytes([s & 0xFF, (s >> 8) & 0xFF, 0x5A]) for s in range(S)], mask=list(r.random(S) < 0.5))
+    src.process(None, n)
+    m = r.permutation(S).astype(np.int64)
+    dst = src.remapped(m)
+    ts, td = src.tx_state(), dst.tx_state()
+    for k in ("samplePosition", "totalSamples", "pendingModulation", "completed"):
+        assert np.array_equal(td[k], ts[k][m]), k
+    assert np.array_equal(dst.rx_lengths(), lens[m])
+    sample = r.choice(S, 200, replace=False)
+    out_s, out_d = src.process(None, n), dst.process(None, n)
+    got_s, got_d = src.demodulate(), dst.demodulate()
+    for i in sample:
+        assert got_d[i] == got_s[m[i]] and len(got_d[i]) == lens[m[i]], i
+        assert np.array_equal(out_d[i], out_s[m[i]]), i
+    assert sum(len(got_d[i]) for i in sample) > 200 * cap // 4
+    for p in (src, dst):
+        p.engine.close()
+        p.close()

@@ -55,6 +55,11 @@ class SnapshotInfo(C.Structure):
                 ("demodulationCalls", C.c_double), ("totalSamplesProcessed", C.c_double)]
 
 
+class ProcessorSnapshotInfo(C.Structure):
+    """fskhip_processor_snapshot_info (include/fskhip_next.h): what a processor snapshot holds"""
+    _fields_ = [("n_streams", C.c_uint32), ("rx_capacity", C.c_uint32), ("payload_capacity", C.c_uint32), ("record_bytes", C.c_uint32)]
+
+
 class XModemResult(C.Structure):
     """fskhip_xmodem_result (include/fskhip_next.h)."""
     _fields_ = [
@@ -140,6 +145,11 @@ _SYMBOLS = [
     ("fskhip_processor_rx_drain_host", C.c_int, [_P, _P, C.c_size_t, _P]),
     ("fskhip_processor_rx_length_host", C.c_int, [_P, _P]),
     ("fskhip_processor_reset", C.c_int, [_P, C.c_int64]),
+    ("fskhip_processor_remap", C.c_int, [_P, _P, _P, C.c_uint32]),
+    ("fskhip_processor_snapshot_bytes", C.c_size_t, [_P, _P, C.c_uint32]),
+    ("fskhip_processor_snapshot", C.c_int, [_P, _P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fskhip_processor_snapshot_info_get", C.c_int, [_P, C.c_size_t, C.POINTER(ProcessorSnapshotInfo)]),
+    ("fskhip_processor_restore", C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint32]),
     ("fskhip_sinc_lowpass", C.c_int, [C.c_double, C.c_double, C.c_uint32, _P]),
     ("fskhip_sinc_highpass", C.c_int, [C.c_double, C.c_double, C.c_uint32, _P]),
     ("fskhip_sinc_bandpass", C.c_int, [C.c_double, C.c_double, C.c_double, C.c_uint32, _P]),

@@ -261,6 +261,7 @@ __global__ void init_kernel(DemodState S, uint32_t n, uint32_t matched_zero) {
 // the host-side counters of a destination that continues streams of a StreamSource (fsk_engine.h)
 namespace fsk {
 bool config_shared_fields_equal(const fskhip_config &a, const fskhip_config &b) { return shared_fields_equal(a, b); }
+bool config_all_fields_equal(const fskhip_config &a, const fskhip_config &b) { return config_equal(a, b); }
 const fskhip_config &engine_stream_config(const fskhip_engine *e, size_t s) { return stream_config(e, s); }
 
 int remap_check_map(const char *who, const char *what, const int64_t *map, uint32_t n_map) {

@@ -137,6 +137,7 @@ int remap_check(const fskhip_engine *dst, const StreamSource &V, const int64_t *
 void remap_finish(fskhip_engine *dst, const StreamSource &V, const int64_t *map, uint32_t n_map, const RemapPlan &plan);
 int engine_refuse_handoff(const char *who, const char *the, const fskhip_engine *e);
 bool config_shared_fields_equal(const fskhip_config &a, const fskhip_config &b);
+bool config_all_fields_equal(const fskhip_config &a, const fskhip_config &b);   // what a continued stream and its source must share
 const fskhip_config &engine_stream_config(const fskhip_engine *e, size_t s);
 // fsk_api.hip: the event pair fskhip_timing_begin / _end put around a call's launches (nothing while timing is off)
 int timing_open(fskhip_engine *e, hipStream_t st);

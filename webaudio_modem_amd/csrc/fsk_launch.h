@@ -98,4 +98,13 @@ hipError_t launch_snap_pack(const SnapLayout &L, const DemodState &S, uint32_t n
                             hipStream_t st);
 hipError_t launch_snap_unpack(int precision, const SnapLayout &L, const DemodState &D, uint32_t n_dst, const int64_t *d_map, uint32_t rec_first, uint32_t rec_count,
                               bool fresh_too, const NewStream &N, const void *d_in, hipStream_t st);
+// fsk_processor_remap.hip: FSKProcessor state (ProcState) between processors and stream-major records (ProcImage).
+// gather: stream i of D continues stream d_map[i] of S, or starts as a created one where d_map[i] = -1.
+// unpack: the same from the slab I of an image's records; streams whose record is in another slab are left alone, new ones are
+// written where fresh_too (a restore runs it once per slab).  pack: records [0, I.count) of d_out, canonical.
+// max_payload: *d_out = the longest pending payload among streams d_idx[0 .. n) (null: 0 .. n - 1; entries < 0 skipped).
+hipError_t launch_processor_gather(const ProcState &D, uint32_t n_dst, const int64_t *d_map, const ProcState &S, hipStream_t st);
+hipError_t launch_processor_unpack(const ProcState &D, uint32_t n_dst, const int64_t *d_map, const ProcImage &I, bool fresh_too, hipStream_t st);
+hipError_t launch_processor_pack(const ProcState &S, const int64_t *d_sel, const ProcImage &I, void *d_out, hipStream_t st);
+hipError_t launch_processor_max_payload(const ProcState &S, const int64_t *d_idx, uint32_t n, uint32_t *d_out, hipStream_t st);
 }  // namespace fsk

@@ -221,6 +221,18 @@ struct ProcState {
   uint32_t *tx_completed;
 };
 
+// Processor snapshots (fsk_processor_remap.hip, include/fskhip_next.h): a slab of stream-major records on the device.  A record:
+// kProcRecFixed bytes of words -- rx_w rx_r rx_len tx_pending | tx_completed tx_pos tx_len tx_n_payload | tx_in_bit tx_bit_idx
+// tx_cur_bit 0 | tx_phase (8 bytes) 0 0 --, then pay_cap bytes of payload, then ring_pitch bytes of ring (rx_cap rounded up to 16).
+static constexpr uint32_t kProcRecFixed = 64;
+struct ProcImage {
+  const uint8_t *rec;      // record 0 of the slab (16-byte aligned)
+  uint32_t rec_bytes;      // kProcRecFixed + pay_cap + ring_pitch
+  uint32_t pay_cap;        // a multiple of 16
+  uint32_t ring_pitch;     // a multiple of 16
+  uint32_t first, count;   // the slab holds records [first, first + count) of the image (pack: streams sel[first ..])
+};
+
 // fp32 free-running frame (fsk_pipe.hip): the front end zeroes a stream's I/Q low-pass kZeroLagPairs decimated samples
 // after a resetState() -- far enough for the wave that owns the low-pass to learn of the reset in time, however far it runs
 // ahead of the wave with the frame logic (at most six half tiles = 24 decimated samples in fsk_blk.hip, four half tiles in

@@ -11,48 +11,11 @@
 
 #include "fsk_engine.h"
 #include "fsk_launch.h"
+#include "fsk_proc.h"
 
 using namespace fsk;
 
-struct fskhip_processor {
-  fskhip_engine *e = nullptr;
-  int device = 0;
-  uint32_t S = 0;
-  ProcState T{};
-  // demodulator outputs of the current quantum
-  uint8_t *d_bytes = nullptr; size_t bytes_pitch = 0;
-  uint32_t *d_counts = nullptr, *d_eod = nullptr;
-  // staging for the _host entry points
-  hipStream_t stream = nullptr;
-  float *d_in = nullptr; size_t d_in_cap = 0;
-  float *d_out = nullptr; size_t d_out_cap = 0;
-  uint8_t *d_stage = nullptr; size_t d_stage_cap = 0;
-  uint32_t *d_u32 = nullptr;   // [4][S] scratch
-  uint8_t *d_mask = nullptr;
-  // captured quantum
-  hipGraphExec_t graph_exec = nullptr;
-  struct Key {
-    float *in; size_t n_in, in_pitch; float *out; size_t n_out, out_pitch; uint32_t flags; hipStream_t st; uint32_t ekey;
-    bool operator==(const Key &o) const {
-      return in == o.in && n_in == o.n_in && in_pitch == o.in_pitch && out == o.out && n_out == o.n_out &&
-             out_pitch == o.out_pitch && flags == o.flags && st == o.st && ekey == o.ekey;
-    }
-  } graph_key{};
-};
-
 namespace {
-
-template <typename T>
-int dev_alloc(T *&p, size_t n) {
-  hipError_t err = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
-  if (err != hipSuccess) return fail(FSKHIP_E_NOMEM, "hipMalloc(%zu): %s", n * sizeof(T), hipGetErrorString(err));
-  return FSKHIP_OK;
-}
-
-void drop_graph(fskhip_processor *p) {
-  if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
-  p->graph_exec = nullptr;
-}
 
 // the launches of one quantum, in stream order
 int launch_quantum(fskhip_processor *p, float *d_in, size_t n_in, size_t in_pitch, float *d_out, size_t n_out,
@@ -67,6 +30,26 @@ int launch_quantum(fskhip_processor *p, float *d_in, size_t n_in, size_t in_pitc
 }
 
 }  // namespace
+
+namespace fsk {
+int processor_grow_payload(fskhip_processor *p, size_t max_len) {
+  if (max_len <= p->T.tx_payload_pitch) return FSKHIP_OK;
+  const size_t S = p->S;
+  const size_t np = (max_len + 63) & ~(size_t)63;
+  uint8_t *nbuf = nullptr;
+  int rc = dev_alloc(nbuf, np * S);
+  if (rc != FSKHIP_OK) return rc;
+  HIP_TRY(hipMemset(nbuf, 0, np * S));
+  if (p->T.tx_payload) {
+    HIP_TRY(hipMemcpy2D(nbuf, np, p->T.tx_payload, p->T.tx_payload_pitch, p->T.tx_payload_pitch, S, hipMemcpyDeviceToDevice));
+    (void)hipFree(p->T.tx_payload);
+  }
+  p->T.tx_payload = nbuf;
+  p->T.tx_payload_pitch = np;
+  drop_graph(p);  // the captured launch holds the old pointer
+  return FSKHIP_OK;
+}
+}  // namespace fsk
 
 extern "C" {
 
@@ -133,6 +116,7 @@ int fskhip_processor_process_device(fskhip_processor *p, float *d_in, size_t n_i
   if (!p) return fail(FSKHIP_E_INVALID, "null processor");
   if (d_in && in_pitch < n_in) return fail(FSKHIP_E_INVALID, "in_pitch %zu < n_in %zu", in_pitch, n_in);
   if (d_out && out_pitch < n_out) return fail(FSKHIP_E_INVALID, "out_pitch %zu < n_out %zu", out_pitch, n_out);
+  p->used = true;
   if (d_in && !fskhip_demod_supported(p->e)) {
     // let the engine produce its own loud message
     return fskhip_demodulate_device(p->e, d_in, n_in, in_pitch, p->d_bytes, p->bytes_pitch, p->d_counts, p->d_eod, 0u, hip_stream);
@@ -210,6 +194,7 @@ int fskhip_processor_modulate_host(fskhip_processor *p, const uint8_t *payloads,
                                    const uint8_t *mask) {
   if (!p) return fail(FSKHIP_E_INVALID, "null processor");
   if (!lens) return fail(FSKHIP_E_INVALID, "null lens");
+  p->used = true;
   HIP_TRY(hipSetDevice(p->device));
   HIP_TRY(hipDeviceSynchronize());
   const size_t S = p->S;
@@ -223,20 +208,7 @@ int fskhip_processor_modulate_host(fskhip_processor *p, const uint8_t *payloads,
     if (lens[s] && !payloads) return fail(FSKHIP_E_INVALID, "null payloads");
     if (lens[s] > max_len) max_len = lens[s];
   }
-  if (max_len > p->T.tx_payload_pitch) {  // grow the payload store, keeping the pending rows
-    const size_t np = (max_len + 63) & ~(size_t)63;
-    uint8_t *nbuf = nullptr;
-    int rc = dev_alloc(nbuf, np * S);
-    if (rc != FSKHIP_OK) return rc;
-    HIP_TRY(hipMemset(nbuf, 0, np * S));
-    if (p->T.tx_payload) {
-      HIP_TRY(hipMemcpy2D(nbuf, np, p->T.tx_payload, p->T.tx_payload_pitch, p->T.tx_payload_pitch, S, hipMemcpyDeviceToDevice));
-      (void)hipFree(p->T.tx_payload);
-    }
-    p->T.tx_payload = nbuf;
-    p->T.tx_payload_pitch = np;
-    drop_graph(p);  // the captured launch holds the old pointer
-  }
+  if (const int grc = processor_grow_payload(p, max_len)) return grc;
   int rc;
   if ((rc = ensure(p->d_stage, p->d_stage_cap, (payload_pitch ? payload_pitch : 1) * S)) != FSKHIP_OK) return rc;
   if (payload_pitch && payloads) HIP_TRY(hipMemcpy(p->d_stage, payloads, payload_pitch * S, hipMemcpyHostToDevice));
@@ -267,6 +239,7 @@ int fskhip_processor_tx_state_host(fskhip_processor *p, uint32_t *pos, uint32_t 
 int fskhip_processor_rx_drain_host(fskhip_processor *p, uint8_t *out, size_t out_pitch, uint32_t *counts) {
   if (!p) return fail(FSKHIP_E_INVALID, "null processor");
   if (!counts || (out_pitch && !out)) return fail(FSKHIP_E_INVALID, "null buffer");
+  p->used = true;
   HIP_TRY(hipSetDevice(p->device));
   HIP_TRY(hipDeviceSynchronize());
   const size_t S = p->S;
@@ -291,6 +264,7 @@ int fskhip_processor_rx_length_host(fskhip_processor *p, uint32_t *lengths) {
 int fskhip_processor_reset(fskhip_processor *p, int64_t stream) {
   if (!p) return fail(FSKHIP_E_INVALID, "null processor");
   if (stream >= (int64_t)p->S) return fail(FSKHIP_E_INVALID, "stream out of range");
+  p->used = true;
   HIP_TRY(hipSetDevice(p->device));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(launch_processor_reset(p->T, p->S, stream, true, true, nullptr));

@@ -4,9 +4,12 @@
   `modulateData(bytes)` of `FSKCore` (the GPU modulator);
 * `FSKProcessorBatch` -- S instances of src/webaudio/processors/fsk-processor.ts on one GPU: `process()` once per
   quantum for all streams (RX byte rings and pending modulations stay on the device), `modulate`, `demodulate`,
-  `reset`, `status`.
+  `reset`, `status`; and the batch's lifecycle -- `remapped`, `snapshot`, `from_snapshot` -- which carries the rings and
+  pending modulations along with the engine's streams.
 """
 import ctypes as C
+
+import collections
 
 import numpy as np
 
@@ -58,6 +61,18 @@ class ChunkedModulator:
         self.samplePosition = 0
 
 
+# What FSKProcessorBatch.snapshot() returns: the engine's stream snapshot and the processor's own image, taken at one moment.
+ProcessorBatchSnapshot = collections.namedtuple("ProcessorBatchSnapshot", ["engine", "processor"])
+
+
+def processor_snapshot_info(blob):
+    """fskhip_processor_snapshot_info_get: what a processor snapshot holds (validated on the host, no device needed)"""
+    b = np.ascontiguousarray(blob if isinstance(blob, np.ndarray) else np.frombuffer(blob, dtype=np.uint8)).view(np.uint8).reshape(-1)
+    info = _lib.ProcessorSnapshotInfo()
+    _lib.check(_lib.lib().fskhip_processor_snapshot_info_get(b.ctypes.data, b.nbytes, C.byref(info)))
+    return {k: getattr(info, k) for k, _ in _lib.ProcessorSnapshotInfo._fields_}
+
+
 class FSKProcessorBatch:
     """S FSKProcessors over one FSKEngine.  rx_capacity 1024 is the reference's demodulatedBuffer size
     (fsk-processor.ts:84); clear_rx_on_tx_complete mirrors its 'modulate' handler (228-235)."""
@@ -83,6 +98,68 @@ class FSKProcessorBatch:
             self.close()
         except Exception:
             pass
+
+    # ---- lifecycle: the processors follow their FSKCores through a remap / a snapshot (include/fskhip_next.h) -------
+    def _like(self, engine):
+        return FSKProcessorBatch(engine, rx_capacity=self.rx_capacity, clear_rx_on_tx_complete=bool(self.flags & PROC_CLEAR_RX_ON_TX_COMPLETE),
+                                 use_graph=bool(self.flags & PROC_GRAPH))
+
+    def remapped(self, stream_map, configs=None, options=None):
+        """A new batch of len(stream_map) streams whose stream i continues stream stream_map[i] of this one -- FSKCore
+        (engine.remapped) and FSKProcessor (fskhip_processor_remap: ring, pending modulation, completed count) -- or starts
+        as a new FSKProcessor where stream_map[i] is -1.  The new batch owns its engine (close both); this batch stays
+        usable.  processDemodulationCallCount is carried."""
+        m = np.ascontiguousarray(stream_map, dtype=np.int64).reshape(-1)
+        eng = self.engine.remapped(m, configs=configs, options=options)
+        try:
+            nxt = self._like(eng)
+        except Exception:
+            eng.close()
+            raise
+        try:
+            _lib.check(self._L.fskhip_processor_remap(nxt._h, self._h, m.ctypes.data, len(m)))
+        except Exception:
+            nxt.close()
+            eng.close()
+            raise
+        nxt.processDemodulationCallCount = self.processDemodulationCallCount
+        return nxt
+
+    def snapshot(self, streams=None):
+        """The pair of images of streams `streams` (None: all, in order): .engine (FSKEngine.snapshot) and .processor
+        (fskhip_processor_snapshot), both `bytes`.  The batch is read only and stays usable."""
+        sel = None if streams is None else np.ascontiguousarray(streams, dtype=np.int64).reshape(-1)
+        n = self.n_streams if sel is None else len(sel)
+        sel_p = None if sel is None else sel.ctypes.data
+        need = int(self._L.fskhip_processor_snapshot_bytes(self._h, sel_p, n))
+        buf = np.zeros(max(need, 1), np.uint8)
+        w = C.c_size_t(0)
+        _lib.check(self._L.fskhip_processor_snapshot(self._h, sel_p, n, buf.ctypes.data, need, C.byref(w)))
+        return ProcessorBatchSnapshot(engine=self.engine.snapshot(streams).tobytes(), processor=buf[:w.value].tobytes())
+
+    @classmethod
+    def from_snapshot(cls, snap, stream_map=None, configs=None, device=0, options=None, clear_rx_on_tx_complete=True, use_graph=False):
+        """A new batch on `device` that continues the records of a snapshot() pair: stream i continues record stream_map[i]
+        of both images (-1: a new FSKCore and FSKProcessor; None: every record, in order).  The engine is made by
+        FSKEngine.from_snapshot, which checks the configs; rx_capacity is the image's.  The host counter
+        processDemodulationCallCount is not part of an image and starts at 0."""
+        from .engine import FSKEngine
+        info = processor_snapshot_info(snap.processor)
+        m = np.arange(info["n_streams"], dtype=np.int64) if stream_map is None else np.ascontiguousarray(stream_map, dtype=np.int64).reshape(-1)
+        eng = FSKEngine.from_snapshot(snap.engine, stream_map=m, configs=configs, device=device, options=options)
+        try:
+            nxt = cls(eng, rx_capacity=info["rx_capacity"], clear_rx_on_tx_complete=clear_rx_on_tx_complete, use_graph=use_graph)
+        except Exception:
+            eng.close()
+            raise
+        try:
+            b = np.frombuffer(snap.processor, dtype=np.uint8)
+            _lib.check(nxt._L.fskhip_processor_restore(nxt._h, b.ctypes.data, b.nbytes, m.ctypes.data, len(m)))
+        except Exception:
+            nxt.close()
+            eng.close()
+            raise
+        return nxt
 
     # ---- process(inputs, outputs) fsk-processor.ts:152-167 -----------------------------------------
     def process(self, inputs=None, n_out=0):
