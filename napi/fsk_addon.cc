@@ -3,6 +3,8 @@
 // This is the FFI a reference maintainer would add: FSKCore / FSKProcessor keep their
 // TypeScript signatures and call these functions; nothing here computes DSP.  Built directly against
 // /usr/include/node/node_api.h with g++ (no node-gyp download), linked to libfskhip.so.
+// What an entry point is spelled with -- ARGS_UPTO, u32 / i32, make_typed, index_array, set_num, throw_fsk -- is addon_util.h's,
+// shared with fsk_addon_next.cc; this file adds the FSKConfig conversion, the busy-engine bookkeeping and get_blob.
 //
 // JS surface (all synchronous; errors throw with the C library's message):
 //   create(configs: object | object[], nStreams, device, precision) -> handle
@@ -15,30 +17,11 @@
 //   getStatus(handle, stream) -> {ready, frameStarted, globalSampleCounter, ...}
 //   demodSupported(handle) -> boolean
 //   deviceCount() -> number
-#include <node_api.h>
-
-#include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "../include/fskhip.h"
-
-#define NAPI_OK(call)                                                        \
-  do {                                                                       \
-    if ((call) != napi_ok) {                                                 \
-      napi_throw_error(env, nullptr, "N-API call failed: " #call);           \
-      return nullptr;                                                        \
-    }                                                                        \
-  } while (0)
-
-static napi_value throw_fsk(napi_env env, int rc) {
-  char code[16];
-  snprintf(code, sizeof(code), "%d", rc);
-  napi_throw_error(env, code, fskhip_last_error());
-  return nullptr;
-}
+#include "addon_util.h"
 
 static bool get_number(napi_env env, napi_value obj, const char *key, double *out) {
   bool has = false;
@@ -117,28 +100,19 @@ static bool is_busy(const fskhip_engine *e) {
   return false;
 }
 static fskhip_engine *get_engine(napi_env env, napi_value v) {
-  void *p = nullptr;
-  if (napi_get_value_external(env, v, &p) != napi_ok || !p) {
-    napi_throw_error(env, nullptr, "FSK modulator not configured");
-    return nullptr;
-  }
-  if (is_busy((fskhip_engine *)p)) {
+  fskhip_engine *e = (fskhip_engine *)external(env, v, "FSK modulator not configured");
+  if (e && is_busy(e)) {
     napi_throw_error(env, nullptr, "an asynchronous call is already in flight on this engine");
     return nullptr;
   }
-  return (fskhip_engine *)p;
+  return e;
 }
 
 static napi_value Create(napi_env env, napi_callback_info info) {
-  size_t argc = 4;
-  napi_value argv[4];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(4);
   if (argc < 4) { napi_throw_type_error(env, nullptr, "create(configs, nStreams, device, precision)"); return nullptr; }
-  uint32_t n_streams = 0;
-  int32_t device = 0, precision = 0;
-  napi_get_value_uint32(env, argv[1], &n_streams);
-  napi_get_value_int32(env, argv[2], &device);
-  napi_get_value_int32(env, argv[3], &precision);
+  const uint32_t n_streams = u32(env, argv[1]);
+  const int32_t device = i32(env, argv[2]), precision = i32(env, argv[3]);
   std::vector<fskhip_config> cfgs;
   bool is_arr = false;
   napi_is_array(env, argv[0], &is_arr);
@@ -164,9 +138,7 @@ static napi_value Create(napi_env env, napi_callback_info info) {
 }
 
 static napi_value Destroy(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(1);
   void *p = nullptr;
   if (argc == 1 && napi_get_value_external(env, argv[0], &p) == napi_ok && p) {
     if (is_busy((fskhip_engine *)p)) g_doomed.push_back((fskhip_engine *)p);   // destroyed by demod_complete
@@ -175,50 +147,60 @@ static napi_value Destroy(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
-static napi_value make_typed(napi_env env, napi_typedarray_type t, size_t count, size_t elem, void **data) {
-  napi_value ab, ta;
-  if (napi_create_arraybuffer(env, count * elem, data, &ab) != napi_ok) return nullptr;
-  if (napi_create_typedarray(env, t, count, ab, 0, &ta) != napi_ok) return nullptr;
-  return ta;
-}
-
 // demodulateData (fsk.ts:190-222) for every stream.  The input Float32Array is BORROWED for the call
 // (napi_get_typedarray_info, never retained); with flags & 1 it is overwritten with the AGC-scaled
 // samples like the reference does (fsk.ts:55).
-static napi_value Demodulate(napi_env env, napi_callback_info info) {
-  size_t argc = 5;
-  napi_value argv[5];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  fskhip_engine *e = get_engine(env, argv[0]);
-  if (!e) return nullptr;
+// What demodulate and demodulateAsync share: one call's arguments, validated, and its outputs, allocated ...
+struct DemodCall {
+  fskhip_engine *e = nullptr;
+  float *samples = nullptr;
+  uint8_t *out = nullptr;
+  uint32_t *counts = nullptr, *eod = nullptr;
+  uint32_t n = 0, pitch = 0, flags = 0;
+  size_t out_pitch = 0;
+};
+struct DemodArrays { napi_value samples, out, counts, eod; };
+static DemodCall *demod_prepare(napi_env env, napi_callback_info info, DemodCall *c, DemodArrays *a) {   // (nullptr: thrown)
+  ARGS_UPTO(5);
+  c->e = get_engine(env, argv[0]);
+  if (!c->e) return nullptr;
   napi_typedarray_type tt;
   size_t len = 0;
   void *data = nullptr;
   NAPI_OK(napi_get_typedarray_info(env, argv[1], &tt, &len, &data, nullptr, nullptr));
   if (tt != napi_float32_array) { napi_throw_type_error(env, nullptr, "samples must be a Float32Array"); return nullptr; }
-  uint32_t n = 0, pitch = 0, flags = 0;
-  napi_get_value_uint32(env, argv[2], &n);
-  napi_get_value_uint32(env, argv[3], &pitch);
-  napi_get_value_uint32(env, argv[4], &flags);
-  const uint32_t S = fskhip_n_streams(e);
-  if (pitch < n || (size_t)pitch * (S ? S - 1 : 0) + n > len) { napi_throw_range_error(env, nullptr, "samples too short"); return nullptr; }
-  const size_t out_pitch = fskhip_max_bytes(e, n);  // the library's own bound (a byte needs >= 8 bit times of samplesPerBit samples)
+  c->samples = (float *)data;
+  c->n = u32(env, argv[2]); c->pitch = u32(env, argv[3]); c->flags = u32(env, argv[4]);
+  const uint32_t S = fskhip_n_streams(c->e);
+  if (c->pitch < c->n || (size_t)c->pitch * (S ? S - 1 : 0) + c->n > len) { napi_throw_range_error(env, nullptr, "samples too short"); return nullptr; }
+  c->out_pitch = fskhip_max_bytes(c->e, c->n);  // the library's own bound (a byte needs >= 8 bit times of samplesPerBit samples)
   void *out = nullptr, *counts = nullptr, *eod = nullptr;
-  napi_value out_v = make_typed(env, napi_uint8_array, out_pitch * S, 1, &out);
-  napi_value cnt_v = make_typed(env, napi_uint32_array, S, 4, &counts);
-  napi_value eod_v = make_typed(env, napi_uint32_array, S, 4, &eod);
-  if (!out_v || !cnt_v || !eod_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
-  int rc = fskhip_demodulate_host(e, (float *)data, n, pitch, (uint8_t *)out, out_pitch, (uint32_t *)counts,
-                                  (uint32_t *)eod, flags);
-  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
-  napi_value res, op;
+  a->samples = argv[1];
+  a->out = make_typed(env, napi_uint8_array, c->out_pitch * S, 1, &out);
+  a->counts = make_typed(env, napi_uint32_array, S, 4, &counts);
+  a->eod = make_typed(env, napi_uint32_array, S, 4, &eod);
+  if (!a->out || !a->counts || !a->eod) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  c->out = (uint8_t *)out; c->counts = (uint32_t *)counts; c->eod = (uint32_t *)eod;
+  return c;
+}
+// ... and the object both hand back
+static napi_value demod_result(napi_env env, size_t out_pitch, napi_value out_v, napi_value cnt_v, napi_value eod_v) {
+  napi_value res;
   NAPI_OK(napi_create_object(env, &res));
-  napi_create_uint32(env, (uint32_t)out_pitch, &op);
   napi_set_named_property(env, res, "out", out_v);
-  napi_set_named_property(env, res, "outPitch", op);
+  set_u32(env, res, "outPitch", (uint32_t)out_pitch);
   napi_set_named_property(env, res, "counts", cnt_v);
   napi_set_named_property(env, res, "eod", eod_v);
   return res;
+}
+
+static napi_value Demodulate(napi_env env, napi_callback_info info) {
+  DemodCall c;
+  DemodArrays a;
+  if (!demod_prepare(env, info, &c, &a)) return nullptr;
+  int rc = fskhip_demodulate_host(c.e, c.samples, c.n, c.pitch, c.out, c.out_pitch, c.counts, c.eod, c.flags);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return demod_result(env, c.out_pitch, a.out, a.counts, a.eod);
 }
 
 // demodulateAsync: the same call on a libuv worker thread, for batches big enough to matter to the event loop
@@ -228,39 +210,29 @@ struct DemodWork {
   napi_async_work work = nullptr;
   napi_deferred deferred = nullptr;
   napi_ref in_ref = nullptr, out_ref = nullptr, cnt_ref = nullptr, eod_ref = nullptr;
-  fskhip_engine *e = nullptr;
-  float *samples = nullptr;
-  uint8_t *out = nullptr;
-  uint32_t *counts = nullptr, *eod = nullptr;
-  uint32_t n = 0, pitch = 0, flags = 0;
-  size_t out_pitch = 0;
+  DemodCall c;
   int rc = 0;
   std::string err;
 };
 static void demod_execute(napi_env, void *data) {
   DemodWork *w = (DemodWork *)data;
-  w->rc = fskhip_demodulate_host(w->e, w->samples, w->n, w->pitch, w->out, w->out_pitch, w->counts, w->eod, w->flags);
+  const DemodCall &c = w->c;
+  w->rc = fskhip_demodulate_host(c.e, c.samples, c.n, c.pitch, c.out, c.out_pitch, c.counts, c.eod, c.flags);
   if (w->rc != FSKHIP_OK) w->err = fskhip_last_error();  // thread-local: read it on the thread that failed
 }
 static void demod_complete(napi_env env, napi_status, void *data) {
   DemodWork *w = (DemodWork *)data;
   for (size_t i = 0; i < g_busy.size(); i++)
-    if (g_busy[i] == w->e) { g_busy.erase(g_busy.begin() + i); break; }
+    if (g_busy[i] == w->c.e) { g_busy.erase(g_busy.begin() + i); break; }
   bool doomed = false;
   for (size_t i = 0; i < g_doomed.size(); i++)
-    if (g_doomed[i] == w->e) { g_doomed.erase(g_doomed.begin() + i); doomed = true; break; }
+    if (g_doomed[i] == w->c.e) { g_doomed.erase(g_doomed.begin() + i); doomed = true; break; }
   if (w->rc == FSKHIP_OK) {
-    napi_value res, out_v, cnt_v, eod_v, op;
-    napi_create_object(env, &res);
+    napi_value out_v, cnt_v, eod_v;
     napi_get_reference_value(env, w->out_ref, &out_v);
     napi_get_reference_value(env, w->cnt_ref, &cnt_v);
     napi_get_reference_value(env, w->eod_ref, &eod_v);
-    napi_create_uint32(env, (uint32_t)w->out_pitch, &op);
-    napi_set_named_property(env, res, "out", out_v);
-    napi_set_named_property(env, res, "outPitch", op);
-    napi_set_named_property(env, res, "counts", cnt_v);
-    napi_set_named_property(env, res, "eod", eod_v);
-    napi_resolve_deferred(env, w->deferred, res);
+    napi_resolve_deferred(env, w->deferred, demod_result(env, w->c.out_pitch, out_v, cnt_v, eod_v));
   } else {
     napi_value msg, errv;
     napi_create_string_utf8(env, w->err.c_str(), NAPI_AUTO_LENGTH, &msg);
@@ -272,53 +244,32 @@ static void demod_complete(napi_env env, napi_status, void *data) {
   napi_delete_reference(env, w->cnt_ref);
   napi_delete_reference(env, w->eod_ref);
   napi_delete_async_work(env, w->work);
-  if (doomed) fskhip_destroy(w->e);   // destroy() was called while the worker held the engine
+  if (doomed) fskhip_destroy(w->c.e);   // destroy() was called while the worker held the engine
   delete w;
 }
 
 static napi_value DemodulateAsync(napi_env env, napi_callback_info info) {
-  size_t argc = 5;
-  napi_value argv[5];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  fskhip_engine *e = get_engine(env, argv[0]);
-  if (!e) return nullptr;
-  napi_typedarray_type tt;
-  size_t len = 0;
-  void *data = nullptr;
-  NAPI_OK(napi_get_typedarray_info(env, argv[1], &tt, &len, &data, nullptr, nullptr));
-  if (tt != napi_float32_array) { napi_throw_type_error(env, nullptr, "samples must be a Float32Array"); return nullptr; }
+  DemodCall c;
+  DemodArrays a;
+  if (!demod_prepare(env, info, &c, &a)) return nullptr;
   DemodWork *w = new DemodWork();
-  w->e = e; w->samples = (float *)data;
-  napi_get_value_uint32(env, argv[2], &w->n);
-  napi_get_value_uint32(env, argv[3], &w->pitch);
-  napi_get_value_uint32(env, argv[4], &w->flags);
-  const uint32_t S = fskhip_n_streams(e);
-  if (w->pitch < w->n || (size_t)w->pitch * (S ? S - 1 : 0) + w->n > len) { delete w; napi_throw_range_error(env, nullptr, "samples too short"); return nullptr; }
-  w->out_pitch = fskhip_max_bytes(e, w->n);
-  void *out = nullptr, *counts = nullptr, *eod = nullptr;
-  napi_value out_v = make_typed(env, napi_uint8_array, w->out_pitch * S, 1, &out);
-  napi_value cnt_v = make_typed(env, napi_uint32_array, S, 4, &counts);
-  napi_value eod_v = make_typed(env, napi_uint32_array, S, 4, &eod);
-  if (!out_v || !cnt_v || !eod_v) { delete w; napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
-  w->out = (uint8_t *)out; w->counts = (uint32_t *)counts; w->eod = (uint32_t *)eod;
-  napi_create_reference(env, argv[1], 1, &w->in_ref);
-  napi_create_reference(env, out_v, 1, &w->out_ref);
-  napi_create_reference(env, cnt_v, 1, &w->cnt_ref);
-  napi_create_reference(env, eod_v, 1, &w->eod_ref);
+  w->c = c;
+  napi_create_reference(env, a.samples, 1, &w->in_ref);
+  napi_create_reference(env, a.out, 1, &w->out_ref);
+  napi_create_reference(env, a.counts, 1, &w->cnt_ref);
+  napi_create_reference(env, a.eod, 1, &w->eod_ref);
   napi_value promise, name;
   napi_create_promise(env, &w->deferred, &promise);
   napi_create_string_utf8(env, "fskhip_demodulate", NAPI_AUTO_LENGTH, &name);
   napi_create_async_work(env, nullptr, name, demod_execute, demod_complete, w, &w->work);
-  g_busy.push_back(e);
+  g_busy.push_back(c.e);
   napi_queue_async_work(env, w->work);
   return promise;
 }
 
 // modulateData (fsk.ts:377-424) for every stream
 static napi_value Modulate(napi_env env, napi_callback_info info) {
-  size_t argc = 4;
-  napi_value argv[4];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(4);
   fskhip_engine *e = get_engine(env, argv[0]);
   if (!e) return nullptr;
   napi_typedarray_type tt;
@@ -328,8 +279,7 @@ static napi_value Modulate(napi_env env, napi_callback_info info) {
   if (tt != napi_uint8_array) { napi_throw_type_error(env, nullptr, "payloads must be a Uint8Array"); return nullptr; }
   NAPI_OK(napi_get_typedarray_info(env, argv[2], &tt, &llen, &ldata, nullptr, nullptr));
   if (tt != napi_uint32_array) { napi_throw_type_error(env, nullptr, "lens must be a Uint32Array"); return nullptr; }
-  uint32_t ppitch = 0;
-  napi_get_value_uint32(env, argv[3], &ppitch);
+  const uint32_t ppitch = u32(env, argv[3]);
   const uint32_t S = fskhip_n_streams(e);
   if (llen < S || plen < (size_t)ppitch * S) { napi_throw_range_error(env, nullptr, "payloads/lens too short"); return nullptr; }
   uint32_t max_len = 0;
@@ -343,32 +293,25 @@ static napi_value Modulate(napi_env env, napi_callback_info info) {
   int rc = fskhip_modulate_host(e, (const uint8_t *)pdata, (const uint32_t *)ldata, ppitch, (float *)out, out_pitch,
                                 (uint32_t *)olens);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
-  napi_value res, op;
+  napi_value res;
   NAPI_OK(napi_create_object(env, &res));
-  napi_create_uint32(env, (uint32_t)out_pitch, &op);
   napi_set_named_property(env, res, "out", out_v);
-  napi_set_named_property(env, res, "outPitch", op);
+  set_u32(env, res, "outPitch", (uint32_t)out_pitch);
   napi_set_named_property(env, res, "lens", len_v);
   return res;
 }
 
 static napi_value ModulatedLength(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(2);
   fskhip_engine *e = get_engine(env, argv[0]);
   if (!e) return nullptr;
-  uint32_t n = 0;
-  napi_get_value_uint32(env, argv[1], &n);
   napi_value r;
-  napi_create_double(env, (double)fskhip_modulated_length(e, n), &r);
+  napi_create_double(env, (double)fskhip_modulated_length(e, u32(env, argv[1])), &r);
   return r;
 }
 
 static napi_value Reset(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(2);
   fskhip_engine *e = get_engine(env, argv[0]);
   if (!e) return nullptr;
   int64_t s = -1;
@@ -380,9 +323,7 @@ static napi_value Reset(napi_env env, napi_callback_info info) {
 
 // carryOver(dst, src): what FSKCore.configure() leaves in place on a configured instance (fskhip_carry_over)
 static napi_value CarryOver(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(2);
   fskhip_engine *dst = get_engine(env, argv[0]);
   if (!dst) return nullptr;
   fskhip_engine *src = get_engine(env, argv[1]);
@@ -395,54 +336,19 @@ static napi_value CarryOver(napi_env env, napi_callback_info info) {
 // remapStreams(dst, src, map): stream i of dst continues stream map[i] of src, or starts afresh where map[i] is -1
 // (fskhip_remap_streams); map is an Array of integers, one per stream of dst
 static napi_value RemapStreams(napi_env env, napi_callback_info info) {
-  size_t argc = 3;
-  napi_value argv[3];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(3);
   fskhip_engine *dst = get_engine(env, argv[0]);
   if (!dst) return nullptr;
   fskhip_engine *src = get_engine(env, argv[1]);
   if (!src) return nullptr;
-  bool is_arr = false;
-  NAPI_OK(napi_is_array(env, argv[2], &is_arr));
-  if (!is_arr) { napi_throw_type_error(env, nullptr, "remapStreams: map must be an Array of stream indices (-1: a new stream)"); return nullptr; }
-  uint32_t n = 0;
-  NAPI_OK(napi_get_array_length(env, argv[2], &n));
-  std::vector<int64_t> map(n);
-  for (uint32_t i = 0; i < n; i++) {
-    napi_value v;
-    NAPI_OK(napi_get_element(env, argv[2], i, &v));
-    double d = 0;
-    if (napi_get_value_double(env, v, &d) != napi_ok || d != (double)(int64_t)d) {
-      napi_throw_type_error(env, nullptr, "remapStreams: map entries must be integers");
-      return nullptr;
-    }
-    map[i] = (int64_t)d;
-  }
-  int rc = fskhip_remap_streams(dst, src, map.data(), n);
+  std::vector<int64_t> map;
+  if (!index_array(env, argv[2], "remapStreams: map must be an Array of stream indices (-1: a new stream)", &map, "remapStreams: map entries must be integers")) return nullptr;
+  int rc = fskhip_remap_streams(dst, src, map.data(), (uint32_t)map.size());
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   return nullptr;
 }
 
-static void set_num(napi_env env, napi_value obj, const char *k, double v);
-
 // ---- stream snapshots (include/fskhip.h): a snapshot is a Buffer (or any Uint8Array) on this side
-static bool get_index_array(napi_env env, napi_value arr, const char *what, std::vector<int64_t> *out) {
-  bool is_arr = false;
-  if (napi_is_array(env, arr, &is_arr) != napi_ok || !is_arr) { napi_throw_type_error(env, nullptr, what); return false; }
-  uint32_t n = 0;
-  napi_get_array_length(env, arr, &n);
-  out->resize(n);
-  for (uint32_t i = 0; i < n; i++) {
-    napi_value v;
-    double d = 0;
-    if (napi_get_element(env, arr, i, &v) != napi_ok || napi_get_value_double(env, v, &d) != napi_ok || d != (double)(int64_t)d) {
-      napi_throw_type_error(env, nullptr, what);
-      return false;
-    }
-    (*out)[i] = (int64_t)d;
-  }
-  return true;
-}
 static bool get_blob(napi_env env, napi_value v, const void **data, size_t *size) {
   bool is = false;
   void *p = nullptr;
@@ -458,37 +364,25 @@ static bool get_blob(napi_env env, napi_value v, const void **data, size_t *size
 
 // snapshotStreams(handle, sel): Buffer with streams sel (an Array of stream indices; null / undefined: all, in order)
 static napi_value SnapshotStreams(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(2);
   fskhip_engine *e = argc >= 1 ? get_engine(env, argv[0]) : nullptr;
   if (!e) { if (argc < 1) napi_throw_type_error(env, nullptr, "snapshotStreams(handle, sel)"); return nullptr; }
   std::vector<int64_t> sel;
-  bool all = true;
-  if (argc >= 2) {
-    napi_valuetype t;
-    NAPI_OK(napi_typeof(env, argv[1], &t));
-    if (t != napi_undefined && t != napi_null) {
-      all = false;
-      if (!get_index_array(env, argv[1], "snapshotStreams: sel must be an Array of stream indices", &sel)) return nullptr;
-    }
-  }
+  const bool all = nullish(env, argv[1]);
+  if (!all && !index_array(env, argv[1], "snapshotStreams: sel must be an Array of stream indices", &sel)) return nullptr;
   const uint32_t n = all ? fskhip_n_streams(e) : (uint32_t)sel.size();
   const size_t need = fskhip_snapshot_bytes(e, n);
   void *data = nullptr;
   napi_value buf;
   NAPI_OK(napi_create_buffer(env, need, &data, &buf));
-  static const int64_t none = 0;
-  const int rc = fskhip_snapshot_streams(e, all ? nullptr : (sel.empty() ? &none : sel.data()), n, data, need, nullptr);
+  const int rc = fskhip_snapshot_streams(e, index_data(sel, all), n, data, need, nullptr);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   return buf;
 }
 
 // restoreStreams(dst, snapshot, map): stream i of dst continues record map[i] of the snapshot, or starts afresh where map[i] is -1
 static napi_value RestoreStreams(napi_env env, napi_callback_info info) {
-  size_t argc = 3;
-  napi_value argv[3];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(3);
   if (argc < 3) { napi_throw_type_error(env, nullptr, "restoreStreams(dst, snapshot, map)"); return nullptr; }
   fskhip_engine *dst = get_engine(env, argv[0]);
   if (!dst) return nullptr;
@@ -496,7 +390,7 @@ static napi_value RestoreStreams(napi_env env, napi_callback_info info) {
   size_t size = 0;
   if (!get_blob(env, argv[1], &data, &size)) return nullptr;
   std::vector<int64_t> map;
-  if (!get_index_array(env, argv[2], "restoreStreams: map must be an Array of record indices (-1: a new stream)", &map)) return nullptr;
+  if (!index_array(env, argv[2], "restoreStreams: map must be an Array of record indices (-1: a new stream)", &map)) return nullptr;
   const int rc = fskhip_restore_streams(dst, data, size, map.data(), (uint32_t)map.size());
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   return nullptr;
@@ -504,9 +398,7 @@ static napi_value RestoreStreams(napi_env env, napi_callback_info info) {
 
 // snapshotInfo(snapshot) -> {nStreams, precision, perStreamConfigs, recordBytes, demodulationCalls, totalSamplesProcessed}
 static napi_value SnapshotInfo(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(1);
   const void *data = nullptr;
   size_t size = 0;
   if (argc < 1 || !get_blob(env, argv[0], &data, &size)) { if (argc < 1) napi_throw_type_error(env, nullptr, "snapshotInfo(snapshot)"); return nullptr; }
@@ -526,9 +418,7 @@ static napi_value SnapshotInfo(napi_env env, napi_callback_info info) {
 
 // snapshotConfig(snapshot, i) -> the FSKConfig record i ran under
 static napi_value SnapshotConfig(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(2);
   const void *data = nullptr;
   size_t size = 0;
   if (argc < 2 || !get_blob(env, argv[0], &data, &size)) { if (argc < 2) napi_throw_type_error(env, nullptr, "snapshotConfig(snapshot, i)"); return nullptr; }
@@ -552,18 +442,14 @@ static napi_value SnapshotConfig(napi_env env, napi_callback_info info) {
   const char *par = c.parity == 1 ? "even" : c.parity == 2 ? "odd" : "none";
   napi_create_string_utf8(env, par, NAPI_AUTO_LENGTH, &v);
   napi_set_named_property(env, o, "parity", v);
-  napi_get_boolean(env, c.agcEnabled != 0, &v);
-  napi_set_named_property(env, o, "agcEnabled", v);
-  napi_get_boolean(env, c.adaptiveThreshold != 0, &v);
-  napi_set_named_property(env, o, "adaptiveThreshold", v);
+  set_bool(env, o, "agcEnabled", c.agcEnabled != 0);
+  set_bool(env, o, "adaptiveThreshold", c.adaptiveThreshold != 0);
   return o;
 }
 
 // snapshotConcat([snapshot, ...]) -> Buffer: the records of all of them under one header (images of what could have been one engine)
 static napi_value SnapshotConcat(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(1);
   bool is_arr = false;
   if (argc < 1 || napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr) { napi_throw_type_error(env, nullptr, "snapshotConcat: an Array of snapshots"); return nullptr; }
   uint32_t n = 0;
@@ -588,9 +474,7 @@ static napi_value SnapshotConcat(napi_env env, napi_callback_info info) {
 
 // enableSignalQuality(handle, on) / getSignalQualityEstimates(handle, stream): the opt-in estimates of include/fskhip.h
 static napi_value EnableSignalQuality(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(2);
   fskhip_engine *e = get_engine(env, argv[0]);
   if (!e) return nullptr;
   bool on = true;
@@ -600,15 +484,11 @@ static napi_value EnableSignalQuality(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 static napi_value GetSignalQualityEstimates(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(2);
   fskhip_engine *e = get_engine(env, argv[0]);
   if (!e) return nullptr;
-  uint32_t stream = 0;
-  if (argc > 1) napi_get_value_uint32(env, argv[1], &stream);
   fskhip_signal_quality q;
-  int rc = fskhip_get_signal_quality(e, stream, &q);
+  int rc = fskhip_get_signal_quality(e, u32(env, argv[1]), &q);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   napi_value obj;
   NAPI_OK(napi_create_object(env, &obj));
@@ -619,28 +499,13 @@ static napi_value GetSignalQualityEstimates(napi_env env, napi_callback_info inf
   return obj;
 }
 
-static void set_num(napi_env env, napi_value obj, const char *k, double v) {
-  napi_value n;
-  napi_create_double(env, v, &n);
-  napi_set_named_property(env, obj, k, n);
-}
-static void set_bool(napi_env env, napi_value obj, const char *k, bool v) {
-  napi_value n;
-  napi_get_boolean(env, v, &n);
-  napi_set_named_property(env, obj, k, n);
-}
-
 // getStatus() (fsk.ts:481-493)
 static napi_value GetStatus(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(2);
   fskhip_engine *e = get_engine(env, argv[0]);
   if (!e) return nullptr;
-  uint32_t s = 0;
-  napi_get_value_uint32(env, argv[1], &s);
   fskhip_status st;
-  int rc = fskhip_get_status(e, s, &st);
+  int rc = fskhip_get_status(e, u32(env, argv[1]), &st);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   napi_value o;
   NAPI_OK(napi_create_object(env, &o));
@@ -660,13 +525,10 @@ static napi_value GetStatus(napi_env env, napi_callback_info info) {
 
 // getFaults(handle) -> Uint8Array[nStreams]: 1 = the stream's filter state is no longer finite (include/fskhip.h, fskhip_get_faults)
 static napi_value GetFaults(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(2);
   fskhip_engine *e = get_engine(env, argv[0]);
   if (!e) return nullptr;
-  uint32_t n = 0;
-  napi_get_value_uint32(env, argv[1], &n);
+  const uint32_t n = u32(env, argv[1]);
   void *data = nullptr;
   napi_value ab, arr;
   NAPI_OK(napi_create_arraybuffer(env, n, &data, &ab));
@@ -677,9 +539,7 @@ static napi_value GetFaults(napi_env env, napi_callback_info info) {
 }
 
 static napi_value DemodSupported(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  ARGS_UPTO(1);
   fskhip_engine *e = get_engine(env, argv[0]);
   if (!e) return nullptr;
   napi_value r;

@@ -1,6 +1,7 @@
 // fsk_addon_next.cc -- N-API binding of include/fskhip_next.h (CRC-16 / XModem packets, the FSKProcessor streaming
 // contract, batched FIR), part of fsk_addon.node.  Same rules as fsk_addon.cc: typed arrays are borrowed for the
 // call, results are fresh arrays, errors throw with the C library's message, nothing here computes.
+// The helpers the entry points are spelled with (ARGS, typed, u32, index_array, ...) are addon_util.h's.
 //
 // JS surface added to the addon:
 //   crc16(data: Uint8Array, pitch, lens: Uint32Array, device) -> Uint16Array
@@ -18,59 +19,14 @@
 //   firProcess(handle, input: Float32Array, n, pitch, nStreams) -> Float32Array;  firReset(handle, stream)
 //   iirCreate(b, a: Float64Array, nStreams, device, precision) -> handle; iirProcess(handle, Float32Array | Float64Array, n, pitch, nStreams);
 //   iirCoefficients(handle), iirReset(handle, stream), iirDestroy(handle); butterworth(kind, f, bandwidth, sampleRate) -> [b0 b1 b2 a0 a1 a2]
-#include <node_api.h>
-
-#include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "../include/fskhip_next.h"
-
-#define NAPI_OK(call)                                                        \
-  do {                                                                       \
-    if ((call) != napi_ok) {                                                 \
-      napi_throw_error(env, nullptr, "N-API call failed: " #call);           \
-      return nullptr;                                                        \
-    }                                                                        \
-  } while (0)
+#include "addon_util.h"
 
 namespace {
 
-napi_value throw_fsk(napi_env env, int rc) {
-  char code[16];
-  snprintf(code, sizeof(code), "%d", rc);
-  napi_throw_error(env, code, fskhip_last_error());
-  return nullptr;
-}
-napi_value make_typed(napi_env env, napi_typedarray_type t, size_t count, size_t elem, void **data) {
-  napi_value ab, ta;
-  if (napi_create_arraybuffer(env, count * elem, data, &ab) != napi_ok) return nullptr;
-  if (napi_create_typedarray(env, t, count, ab, 0, &ta) != napi_ok) return nullptr;
-  return ta;
-}
-// borrows a typed array of the given type; null/undefined -> data = nullptr when `optional`
-bool typed(napi_env env, napi_value v, napi_typedarray_type want, void **data, size_t *len, bool optional = false) {
-  napi_valuetype vt;
-  napi_typeof(env, v, &vt);
-  if (optional && (vt == napi_null || vt == napi_undefined)) { *data = nullptr; *len = 0; return true; }
-  bool is = false;
-  napi_is_typedarray(env, v, &is);
-  napi_typedarray_type tt;
-  if (!is || napi_get_typedarray_info(env, v, &tt, len, data, nullptr, nullptr) != napi_ok || tt != want) {
-    napi_throw_type_error(env, nullptr, "wrong typed array argument");
-    return false;
-  }
-  return true;
-}
-uint32_t u32(napi_env env, napi_value v) { uint32_t x = 0; napi_get_value_uint32(env, v, &x); return x; }
-int32_t i32(napi_env env, napi_value v) { int32_t x = 0; napi_get_value_int32(env, v, &x); return x; }
-double f64(napi_env env, napi_value v) { double x = 0; napi_get_value_double(env, v, &x); return x; }
-void *external(napi_env env, napi_value v, const char *what) {
-  void *p = nullptr;
-  if (napi_get_value_external(env, v, &p) != napi_ok || !p) { napi_throw_error(env, nullptr, what); return nullptr; }
-  return p;
-}
 // FIR / IIR filter handles: the external owns a box, so that close() can empty it (a later call throws instead of touching freed
 // memory) and a filter that is never close()d is destroyed when the garbage collector drops the handle
 struct FilterBox { void *p; bool iir; };
@@ -97,18 +53,6 @@ void filter_box_close(napi_env env, napi_value v) {
   FilterBox *b = (FilterBox *)q;
   if (b->p) { if (b->iir) fskhip_iir_destroy((fskhip_iir *)b->p); else fskhip_fir_destroy((fskhip_fir *)b->p); b->p = nullptr; }
 }
-void set_u32(napi_env env, napi_value obj, const char *k, uint32_t v) {
-  napi_value n;
-  napi_create_uint32(env, v, &n);
-  napi_set_named_property(env, obj, k, n);
-}
-
-#define ARGS(n)                                                              \
-  size_t argc = n;                                                           \
-  napi_value argv[n];                                                        \
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));       \
-  if (argc < n) { napi_throw_type_error(env, nullptr, "too few arguments"); return nullptr; }
-
 napi_value Crc16(napi_env env, napi_callback_info info) {
   ARGS(4);
   void *data, *lens; size_t dlen, llen;
@@ -290,24 +234,6 @@ napi_value ProcessorReset(napi_env env, napi_callback_info info) {
 }
 
 // ---- processor remap / snapshots (include/fskhip_next.h): a snapshot is a Buffer (or any Uint8Array) on this side
-bool index_array(napi_env env, napi_value arr, const char *what, std::vector<int64_t> *out) {
-  bool is_arr = false;
-  if (napi_is_array(env, arr, &is_arr) != napi_ok || !is_arr) { napi_throw_type_error(env, nullptr, what); return false; }
-  uint32_t n = 0;
-  napi_get_array_length(env, arr, &n);
-  out->resize(n);
-  for (uint32_t i = 0; i < n; i++) {
-    napi_value v;
-    double d = 0;
-    if (napi_get_element(env, arr, i, &v) != napi_ok || napi_get_value_double(env, v, &d) != napi_ok || d != (double)(int64_t)d) {
-      napi_throw_type_error(env, nullptr, what);
-      return false;
-    }
-    (*out)[i] = (int64_t)d;
-  }
-  return true;
-}
-
 napi_value ProcessorRemap(napi_env env, napi_callback_info info) {
   ARGS(3);
   Proc *dst = get_proc(env, argv[0]);
@@ -316,8 +242,7 @@ napi_value ProcessorRemap(napi_env env, napi_callback_info info) {
   if (!src) return nullptr;
   std::vector<int64_t> map;
   if (!index_array(env, argv[2], "processorRemap: map must be an Array of integer stream indices (-1: a new stream)", &map)) return nullptr;
-  static const int64_t none = 0;
-  int rc = fskhip_processor_remap(dst->p, src->p, map.empty() ? &none : map.data(), (uint32_t)map.size());
+  int rc = fskhip_processor_remap(dst->p, src->p, index_data(map), (uint32_t)map.size());
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   return nullptr;
 }
@@ -327,12 +252,9 @@ napi_value ProcessorSnapshot(napi_env env, napi_callback_info info) {
   Proc *h = get_proc(env, argv[0]);
   if (!h) return nullptr;
   std::vector<int64_t> sel;
-  napi_valuetype t;
-  NAPI_OK(napi_typeof(env, argv[1], &t));
-  const bool all = t == napi_undefined || t == napi_null;
+  const bool all = nullish(env, argv[1]);
   if (!all && !index_array(env, argv[1], "processorSnapshot: sel must be an Array of integer stream indices", &sel)) return nullptr;
-  static const int64_t none = 0;
-  const int64_t *sp = all ? nullptr : (sel.empty() ? &none : sel.data());
+  const int64_t *sp = index_data(sel, all);
   const uint32_t n = all ? h->S : (uint32_t)sel.size();
   size_t need = 0;
   int rc = fskhip_processor_snapshot(h->p, sp, n, nullptr, 0, &need);   // (the size: it depends on the pending payloads)
@@ -353,8 +275,7 @@ napi_value ProcessorRestore(napi_env env, napi_callback_info info) {
   if (!typed(env, argv[1], napi_uint8_array, &data, &size)) return nullptr;
   std::vector<int64_t> map;
   if (!index_array(env, argv[2], "processorRestore: map must be an Array of integer record indices (-1: a new stream)", &map)) return nullptr;
-  static const int64_t none = 0;
-  int rc = fskhip_processor_restore(dst->p, data, size, map.empty() ? &none : map.data(), (uint32_t)map.size());
+  int rc = fskhip_processor_restore(dst->p, data, size, index_data(map), (uint32_t)map.size());
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   return nullptr;
 }

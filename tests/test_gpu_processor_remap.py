@@ -424,6 +424,72 @@ def test_preconditions_are_refused_and_leave_both_sides_as_they_were():
     deng.close()
 
 
+# ---------------------------------------------------------------- slab boundaries ----------------
+SLAB = 8192          # fsk_stage.h kSnapSlab: records per staging slab
+
+
+def test_remap_equals_restore_across_slab_boundaries():
+    """2 x 8 192 + 1 streams: three slabs with a last one of a single record, the smallest batch at which a slab has to wait for the
+    staging buffer of the slab two before it, on the way out and on the way in.  Then a selection of exactly one slab, and one
+    of no records at all (a restore of none still creates the new processors).  Each time a batch restored from the images
+    and one made by src.remapped() with the same map are the same batch: every word of tx_state, every ring length, image
+    against image, and every stream's output and ring bytes over the quanta that follow."""
+    import webaudio_modem_amd as wm
+    S, n, cap, quanta = 2 * SLAB + 1, 128, 48, 24
+    r = _rng(0x51AB)
+    rows = np.stack([_frame_row(r, (quanta + 4) * n, 0) for _ in range(64)])     # stream s hears row s % 64 ...
+    group = (np.arange(S) % 64).astype(np.int64)
+    eng = wm.FSKEngine(S, CFG, precision=wm.PRECISION_F32)
+    src = wm.FSKProcessorBatch(eng, rx_capacity=cap)
+    for q in range(quanta):
+        src.process(rows[group, q * n:(q + 1) * n], 0)
+    lens = src.rx_lengths()
+    assert lens.max() > 0
+    # ... and sends a payload of its own: no two records are the same
+    src.modulate([bytes([s & 0xFF, s >> 8]) + bytes(s % 23) for s in range(S)], mask=[s % 5 != 0 for s in range(S)])
+    src.process(None, n)
+    ts = src.tx_state()
+
+    def check(snap, n_records, rec_map, src_map):
+        """rec_map names records of the images, src_map the same streams in src"""
+        assert wm.processor_snapshot_info(snap.processor)["n_streams"] == n_records
+        a = src.remapped(src_map)
+        b = wm.FSKProcessorBatch.from_snapshot(snap, rec_map)
+        old = src_map >= 0
+        ta, tb = a.tx_state(), b.tx_state()
+        for k in ("samplePosition", "totalSamples", "pendingModulation", "completed"):
+            assert np.array_equal(ta[k], tb[k]), k
+            assert np.array_equal(tb[k][old], ts[k][src_map[old]]), k
+            assert not tb[k][~old].any(), k
+        assert np.array_equal(a.rx_lengths(), b.rx_lengths()) and np.array_equal(b.rx_lengths()[old], lens[src_map[old]])
+        sa, sb = a.snapshot(), b.snapshot()
+        assert sa.processor == sb.processor and sa.engine == sb.engine
+        xin = np.where(old[:, None], rows[group[np.maximum(src_map, 0)]], 0).astype(np.float32)
+        for q in range(quanta, quanta + 4):
+            oa, ob = a.process(xin[:, q * n:(q + 1) * n], n), b.process(xin[:, q * n:(q + 1) * n], n)
+            assert np.array_equal(oa, ob), q
+        assert a.demodulate() == b.demodulate()
+        assert np.array_equal(a.tx_state()["completed"], b.tx_state()["completed"])
+        for p in (a, b):
+            p.engine.close()
+            p.close()
+
+    # three slabs, the last ragged: every record, shuffled, 40 slots new
+    m = r.permutation(S).astype(np.int64)
+    m[r.choice(S, 40, replace=False)] = -1
+    check(src.snapshot(), S, m, m)
+    # exactly one slab, out and in: a selection that reorders, restored in another order with 9 slots new
+    sel = r.permutation(S)[:SLAB].astype(np.int64)
+    m = r.permutation(SLAB).astype(np.int64)
+    m[r.choice(SLAB, 9, replace=False)] = -1
+    check(src.snapshot(sel), SLAB, m, np.where(m >= 0, sel[np.maximum(m, 0)], -1))
+    # no records: new processors only
+    m = -np.ones(70, np.int64)
+    check(src.snapshot([]), 0, m, m)
+    src.engine.close()
+    src.close()
+
+
 # ---------------------------------------------------------------- size ----------------
 def test_65536_streams_random_permutation_half_full_rings():
     import webaudio_modem_amd as wm

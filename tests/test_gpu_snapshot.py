@@ -505,3 +505,59 @@ def test_snapshot_full_size_random_permutation(prec):
         ctrl.device_free(b)
     dst.close()
     ctrl.close()
+
+
+# ---- 8. the staging pipeline's slab boundaries --------------------------------------------------------------------------------
+SLAB = 8192          # fsk_stage.h kSnapSlab: records per staging slab
+
+
+@pytest.mark.parametrize("kind", ["uniform", "per-stream"])
+@pytest.mark.parametrize("prec", [0, 1])
+def test_restore_equals_remap_across_slab_boundaries(prec, kind):
+    """2 x 8 192 + 1 streams: three slabs with a last one of a single record, the smallest batch at which a slab has to wait for the
+    staging buffer of the slab two before it, on the way out and on the way in.  Then a selection of exactly one slab, and one
+    of no records at all (a restore of none still creates the new streams).  Each time a destination restored from the image
+    and one made by src.remapped() with the same map are the same engine: image against image over every word of every
+    stream, state words at the slab edges and a strided sample, and every stream's output of one more call."""
+    wm = _wm()
+    S, n, cut = 2 * SLAB + 1, 600, 300
+    rng = np.random.default_rng(17 + prec)
+    x = R._signals(R._cfgs(kind, S), S, n, seed=19, lead_max=100)
+    src = wm.FSKEngine(S, R._cfgs(kind, S), precision=_prec(prec))
+    src.demodulate_data(x[:, :cut])
+
+    def check(blob, n_records, rec_map, src_map):
+        """rec_map names records of the blob, src_map the same streams in src"""
+        assert wm.snapshot_info(blob)["n_streams"] == n_records
+        dcfg = None if kind == "uniform" else [R._cfg(kind, int(v) if v >= 0 else i) for i, v in enumerate(src_map)]
+        a = src.remapped(src_map, configs=dcfg)
+        b = wm.FSKEngine.from_snapshot(blob, rec_map, configs=dcfg)
+        n_dst = len(src_map)
+        edges = [i for i in (0, 1, SLAB - 1, SLAB, SLAB + 1, 2 * SLAB - 1, 2 * SLAB) if i < n_dst]
+        sample = sorted(set(edges) | set(range(0, n_dst, 127)))
+        din = np.where((src_map >= 0)[:, None], x[np.maximum(src_map, 0), cut:], 0).astype(np.float32)
+        for step in range(2):
+            assert np.array_equal(a.snapshot(), b.snapshot()), step
+            for i in sample:
+                assert R._same_state(R._state(a, i), R._state(b, i)), (step, i)
+                assert a.get_status(i) == b.get_status(i), (step, i)
+            if step == 0:
+                (ab, ae), (bb, be) = a.demodulate_data(din), b.demodulate_data(din)
+                assert ab == bb and np.array_equal(ae, be)
+                assert a.last_kernel() == b.last_kernel()
+        a.close()
+        b.close()
+
+    # three slabs, the last ragged: every record, shuffled, 40 slots new
+    m = rng.permutation(S).astype(np.int64)
+    m[rng.choice(S, 40, replace=False)] = -1
+    check(src.snapshot(), S, m, m)
+    # exactly one slab, out and in: a selection that reorders, restored in another order with 9 slots new
+    sel = rng.permutation(S)[:SLAB].astype(np.int64)
+    m = rng.permutation(SLAB).astype(np.int64)
+    m[rng.choice(SLAB, 9, replace=False)] = -1
+    check(src.snapshot(sel), SLAB, m, np.where(m >= 0, sel[np.maximum(m, 0)], -1))
+    # no records: new streams only
+    m = -np.ones(70, np.int64)
+    check(src.snapshot([]), 0, m, m)
+    src.close()

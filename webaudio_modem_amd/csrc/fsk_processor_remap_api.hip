@@ -2,7 +2,8 @@
 // (fskhip_processor_snapshot_bytes / _snapshot / _snapshot_info_get, fskhip_processor_restore).  They carry the FSKProcessor row
 // -- RX rings, pending modulations, `completed` counts -- where fskhip_remap_streams and the stream snapshots carry the FSKCore
 // below it.  The image's format is documented in the header; this file is its only reader and writer.  Kernels:
-// fsk_processor_remap.hip; slab staging and checksum: fsk_stage.h, shared with the stream snapshots.
+// fsk_processor_remap.hip; the frame of an image (checksum, open front and back, selection and room checks) and the slab
+// pipelines: fsk_stage.h, shared with the stream snapshots.
 #include <algorithm>
 #include <vector>
 
@@ -32,14 +33,6 @@ static_assert(sizeof(ProcHeader) == 48 && sizeof(ProcHeader) % 16 == 0, "ProcHea
 uint32_t ring_pitch_of(uint32_t rx_capacity) { return (rx_capacity + 15u) & ~15u; }
 uint32_t record_bytes_of(uint32_t rx_capacity, uint32_t pay_cap) { return kProcRecFixed + pay_cap + ring_pitch_of(rx_capacity); }
 
-uint64_t proc_checksum(ProcHeader h, const void *records, size_t bytes) {
-  h.checksum = 0;
-  SnapSum s;
-  snap_sum(s, &h, sizeof(h));
-  snap_sum(s, records, bytes);
-  return snap_sum_value(s);
-}
-
 // a validated image: the header (copied: the caller's bytes need no alignment) and the records
 struct ProcSnap {
   ProcHeader h;
@@ -47,24 +40,15 @@ struct ProcSnap {
 };
 
 int proc_open(const char *who, const void *buf, size_t size, ProcSnap *s) {
-  if (!buf) return fail(FSKHIP_E_INVALID, "%s: null snapshot", who);
-  if (size < sizeof(ProcHeader)) return fail(FSKHIP_E_INVALID, "%s: %zu bytes are fewer than a processor snapshot header's %zu", who, size, sizeof(ProcHeader));
   ProcHeader &h = s->h;
-  std::memcpy(&h, buf, sizeof(h));
-  if (h.magic != kProcMagic) return fail(FSKHIP_E_INVALID, "%s: not a processor snapshot (magic 0x%08x, expected 0x%08x)", who, h.magic, kProcMagic);
-  if (h.format != kProcFormat) return fail(FSKHIP_E_INVALID, "%s: processor snapshot format %u, this library reads format %u", who, h.format, kProcFormat);
-  if (h.header_bytes != sizeof(ProcHeader)) return fail(FSKHIP_E_INVALID, "%s: header_bytes %u, expected %zu", who, h.header_bytes, sizeof(ProcHeader));
+  if (const int rc = image_open_front(who, "processor snapshot", buf, size, kProcMagic, kProcFormat, &h)) return rc;
   if (h.rx_capacity == 0 || h.rx_capacity > (1u << 30)) return fail(FSKHIP_E_INVALID, "%s: rx_capacity %u in the snapshot", who, h.rx_capacity);
   if ((h.payload_capacity & 15u) != 0u || h.payload_capacity > (1u << 30))
     return fail(FSKHIP_E_INVALID, "%s: payload_capacity %u in the snapshot (a multiple of 16)", who, h.payload_capacity);
   if (h.record_bytes != record_bytes_of(h.rx_capacity, h.payload_capacity))
     return fail(FSKHIP_E_INVALID, "%s: record_bytes %u, but rx_capacity %u and payload_capacity %u make records of %u bytes", who, h.record_bytes, h.rx_capacity,
                 h.payload_capacity, record_bytes_of(h.rx_capacity, h.payload_capacity));
-  if (size != sizeof(ProcHeader) + (size_t)h.n_records * h.record_bytes)
-    return fail(FSKHIP_E_INVALID, "%s: %zu bytes do not match n_records x record_bytes (%zu + %u x %u)", who, size, sizeof(ProcHeader), h.n_records, h.record_bytes);
-  s->rec = (const unsigned char *)buf + sizeof(ProcHeader);
-  const uint64_t c = proc_checksum(h, s->rec, size - sizeof(ProcHeader));
-  if (c != h.checksum) return fail(FSKHIP_E_INVALID, "%s: checksum %016llx, the bytes sum to %016llx (a damaged snapshot)", who, (unsigned long long)h.checksum, (unsigned long long)c);
+  if (const int rc = image_open_back(who, "n_records", buf, size, h, h.n_records, &s->rec)) return rc;
   // the words a kernel would index with: inside the ring, inside the record's payload
   for (uint32_t r = 0; r < h.n_records; r++) {
     uint32_t w[8];
@@ -91,12 +75,6 @@ int max_pending_payload(const char *who, const fskhip_processor *p, const int64_
   if (d_idx) (void)hipFree(d_idx);
   if (d_out) (void)hipFree(d_out);
   if (err != hipSuccess) return fail(FSKHIP_E_HIP, "%s: %s", who, hipGetErrorString(err));
-  return FSKHIP_OK;
-}
-
-int check_sel(const char *who, const fskhip_processor *p, const int64_t *sel, uint32_t n_sel) {
-  for (uint32_t i = 0; sel && i < n_sel; i++)
-    if (sel[i] < 0 || sel[i] >= (int64_t)p->S) return fail(FSKHIP_E_INVALID, "%s: sel[%u] = %lld, the processor has %u streams", who, i, (long long)sel[i], p->S);
   return FSKHIP_OK;
 }
 
@@ -143,7 +121,7 @@ size_t fskhip_processor_snapshot_bytes(const fskhip_processor *p, const int64_t 
   static const char who[] = "fskhip_processor_snapshot_bytes";
   if (!p) return 0;
   if (!sel) n_sel = p->S;
-  if (check_sel(who, p, sel, n_sel)) return 0;
+  if (check_sel(who, "processor", sel, n_sel, p->S)) return 0;
   if (hipSetDevice(p->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 0;
   uint32_t max_pay = 0;
   if (max_pending_payload(who, p, sel, n_sel, &max_pay)) return 0;
@@ -154,46 +132,28 @@ int fskhip_processor_snapshot(fskhip_processor *p, const int64_t *sel, uint32_t 
   static const char who[] = "fskhip_processor_snapshot";
   if (!p) return fail(FSKHIP_E_INVALID, "%s: null processor", who);
   if (!sel) n_sel = p->S;
-  if (const int rc = check_sel(who, p, sel, n_sel)) return rc;
+  if (const int rc = check_sel(who, "processor", sel, n_sel, p->S)) return rc;
   HIP_TRY(hipSetDevice(p->device));
   HIP_TRY(hipDeviceSynchronize());
   uint32_t max_pay = 0;
   if (const int rc = max_pending_payload(who, p, sel, n_sel, &max_pay)) return rc;
   const uint32_t pay_cap = (max_pay + 15u) & ~15u;
   const size_t rec_bytes = record_bytes_of(p->T.rx_cap, pay_cap), need = sizeof(ProcHeader) + (size_t)n_sel * rec_bytes;
-  if (written) *written = need;
-  if (!buf || cap < need) return fail(FSKHIP_E_OVERFLOW, "%s: a snapshot of %u streams takes %zu bytes, the buffer has %zu", who, n_sel, need, buf ? cap : (size_t)0);
+  if (const int rc = check_room(who, n_sel, need, buf, cap, written)) return rc;
 
-  ProcHeader h;
-  std::memset(&h, 0, sizeof(h));
-  h.magic = kProcMagic; h.format = kProcFormat; h.header_bytes = sizeof(ProcHeader); h.record_bytes = (uint32_t)rec_bytes;
+  ProcHeader h = image_header<ProcHeader>(kProcMagic, kProcFormat, rec_bytes);
   h.n_records = n_sel; h.rx_capacity = p->T.rx_cap; h.payload_capacity = pay_cap;
   unsigned char *rec = (unsigned char *)buf + sizeof(ProcHeader);
   SnapSum sum;
   snap_sum(sum, &h, sizeof(h));   // (checksum field still 0)
 
-  // slab k: pack on the processor's stream, its copy on the copy stream; the host sums slab k - 1 while slab k is on its way
-  Stage st;
-  const uint32_t slab = std::min<uint32_t>(kSnapSlab, std::max<uint32_t>(n_sel, 1u));
-  SNAP_HIP(st.open((size_t)slab * rec_bytes, sel, sel ? n_sel : 0));
-  const uint32_t n_slabs = (n_sel + slab - 1) / slab;
-  auto finish = [&](uint32_t k) {
-    const uint32_t a = k * slab, b = std::min(n_sel, a + slab);
-    snap_sum(sum, rec + (size_t)a * rec_bytes, (size_t)(b - a) * rec_bytes);
-  };
-  for (uint32_t k = 0; k < n_slabs; k++) {
-    const int b = (int)(k & 1u);
-    const uint32_t first = k * slab, count = std::min(n_sel - first, slab);
+  const auto pack = [&](const int64_t *d_sel, uint32_t first, uint32_t count, void *d_buf, hipStream_t stream) {
     const ProcImage I{nullptr, (uint32_t)rec_bytes, pay_cap, ring_pitch_of(p->T.rx_cap), first, count};
-    if (k >= 2) SNAP_HIP(hipStreamWaitEvent(p->stream, st.ev_copy[b], 0));
-    SNAP_HIP(launch_processor_pack(p->T, st.d_idx, I, st.buf[b], p->stream));
-    SNAP_HIP(hipEventRecord(st.ev_kernel[b], p->stream));
-    SNAP_HIP(hipStreamWaitEvent(st.copy, st.ev_kernel[b], 0));
-    SNAP_HIP(hipMemcpyAsync(rec + (size_t)first * rec_bytes, st.buf[b], (size_t)count * rec_bytes, hipMemcpyDeviceToHost, st.copy));
-    SNAP_HIP(hipEventRecord(st.ev_copy[b], st.copy));
-    if (k >= 1) { SNAP_HIP(hipEventSynchronize(st.ev_copy[b ^ 1])); finish(k - 1); }
-  }
-  if (n_slabs) { SNAP_HIP(hipEventSynchronize(st.ev_copy[(n_slabs - 1) & 1u])); finish(n_slabs - 1); }
+    return launch_processor_pack(p->T, d_sel, I, d_buf, stream);
+  };
+  // the host's part of a slab that has arrived: the checksum
+  const auto finish = [&](uint32_t a, uint32_t b) { snap_sum(sum, rec + (size_t)a * rec_bytes, (size_t)(b - a) * rec_bytes); };
+  if (const int rc = stage_records_out(who, p->stream, sel, n_sel, rec_bytes, rec, pack, finish)) return rc;
   h.checksum = snap_sum_value(sum);
   std::memcpy(buf, &h, sizeof(h));
   return FSKHIP_OK;
@@ -223,28 +183,11 @@ int fskhip_processor_restore(fskhip_processor *dst, const void *buf, size_t size
   if (const int rc = processor_grow_payload(dst, h.payload_capacity)) return rc;
   if (n_map == 0) return FSKHIP_OK;
 
-  // slab k of the records crosses to the device on the copy stream while slab k - 1 is unpacked on the processor's own; every
-  // launch covers all of dst and serves the streams whose record is in its slab (new streams: the first)
-  Stage st;
-  const uint32_t slab = std::min<uint32_t>(kSnapSlab, std::max<uint32_t>(h.n_records, 1u));
-  SNAP_HIP(st.open((size_t)slab * h.record_bytes, map, n_map));
-  const uint32_t n_slabs = std::max<uint32_t>(1u, (h.n_records + slab - 1) / slab);
-  for (uint32_t k = 0; k < n_slabs; k++) {
-    const int b = (int)(k & 1u);
-    const uint32_t first = k * slab, count = h.n_records > first ? std::min(h.n_records - first, slab) : 0u;
-    if (count) {
-      if (k >= 2) SNAP_HIP(hipStreamWaitEvent(st.copy, st.ev_kernel[b], 0));
-      SNAP_HIP(hipMemcpyAsync(st.buf[b], s.rec + (size_t)first * h.record_bytes, (size_t)count * h.record_bytes, hipMemcpyHostToDevice, st.copy));
-      SNAP_HIP(hipEventRecord(st.ev_copy[b], st.copy));
-      SNAP_HIP(hipStreamWaitEvent(dst->stream, st.ev_copy[b], 0));
-    }
-    const ProcImage I{(const uint8_t *)st.buf[b], h.record_bytes, h.payload_capacity, ring_pitch_of(h.rx_capacity), first, count};
-    SNAP_HIP(launch_processor_unpack(dst->T, dst->S, st.d_idx, I, k == 0, dst->stream));
-    SNAP_HIP(hipEventRecord(st.ev_kernel[b], dst->stream));
-  }
-  SNAP_HIP(hipStreamSynchronize(dst->stream));
-  SNAP_HIP(hipDeviceSynchronize());
-  return FSKHIP_OK;
+  const auto unpack = [&](const int64_t *d_map, uint32_t first, uint32_t count, bool fresh_too, void *d_buf, hipStream_t stream) {
+    const ProcImage I{(const uint8_t *)d_buf, h.record_bytes, h.payload_capacity, ring_pitch_of(h.rx_capacity), first, count};
+    return launch_processor_unpack(dst->T, dst->S, d_map, I, fresh_too, stream);
+  };
+  return stage_records_in(who, dst->stream, map, n_map, s.rec, h.n_records, h.record_bytes, unpack);
 }
 
 }  // extern "C"

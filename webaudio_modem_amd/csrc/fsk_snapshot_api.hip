@@ -2,7 +2,9 @@
 // of streams -- one SnapHeader, then fixed-size stream-major records -- that fskhip_restore_streams continues from under
 // fskhip_remap_streams' contract, on any device and in any process running this build.  The format is documented in the
 // header; this file is its only reader and writer.  The pack / unpack kernels are fsk_snapshot.hip's; the checks, the
-// lock-step decision and the host-side counters are the remap's own (fsk_create.hip, fsk_engine.h).
+// lock-step decision and the host-side counters are the remap's own (fsk_create.hip, fsk_engine.h); the frame of an image
+// (checksum, open front and back, selection and room checks) and the slab pipelines are fsk_stage.h's, shared with the
+// processor snapshots.
 #include <algorithm>
 
 #include "fsk_engine.h"
@@ -65,14 +67,6 @@ uint64_t fields_hash() {
   return h;
 }
 
-uint64_t snap_checksum(SnapHeader h, const void *records, size_t bytes) {
-  h.checksum = 0;
-  SnapSum s;
-  snap_sum(s, &h, sizeof(h));
-  snap_sum(s, records, bytes);
-  return snap_sum_value(s);
-}
-
 SnapConfig pack_config(const fskhip_config &c) {
   SnapConfig o;
   std::memset(&o, 0, sizeof(o));
@@ -125,31 +119,22 @@ struct Snap {
   }
 };
 
-int snap_open(const char *who, const void *buf, size_t size, Snap *s, bool sum = true) {
-  if (!buf) return fail(FSKHIP_E_INVALID, "%s: null snapshot", who);
-  if (size < sizeof(SnapHeader)) return fail(FSKHIP_E_INVALID, "%s: %zu bytes are fewer than a snapshot header's %zu", who, size, sizeof(SnapHeader));
+int snap_open(const char *who, const void *buf, size_t size, Snap *s) {
   SnapHeader &h = s->h;
-  std::memcpy(&h, buf, sizeof(h));
-  if (h.magic != kSnapMagic) return fail(FSKHIP_E_INVALID, "%s: not a snapshot (magic 0x%08x, expected 0x%08x)", who, h.magic, kSnapMagic);
-  if (h.format != kSnapFormat) return fail(FSKHIP_E_INVALID, "%s: snapshot format %u, this library reads format %u", who, h.format, kSnapFormat);
-  if (h.rf_count != RF_COUNT || h.if_count != IF_COUNT || h.fields_hash != fields_hash())
-    return fail(FSKHIP_E_INVALID, "%s: the snapshot's state layout (%u + %u words, stamp %016llx) is another build's (%d + %d words, stamp %016llx)", who, h.rf_count,
-                h.if_count, (unsigned long long)h.fields_hash, (int)RF_COUNT, (int)IF_COUNT, (unsigned long long)fields_hash());
-  if (h.header_bytes != sizeof(SnapHeader)) return fail(FSKHIP_E_INVALID, "%s: header_bytes %u, expected %zu", who, h.header_bytes, sizeof(SnapHeader));
+  const auto stamp = [&] {
+    if (h.rf_count != RF_COUNT || h.if_count != IF_COUNT || h.fields_hash != fields_hash())
+      return fail(FSKHIP_E_INVALID, "%s: the snapshot's state layout (%u + %u words, stamp %016llx) is another build's (%d + %d words, stamp %016llx)", who, h.rf_count,
+                  h.if_count, (unsigned long long)h.fields_hash, (int)RF_COUNT, (int)IF_COUNT, (unsigned long long)fields_hash());
+    return (int)FSKHIP_OK;
+  };
+  if (const int rc = image_open_front(who, "snapshot", buf, size, kSnapMagic, kSnapFormat, &h, stamp)) return rc;
   if (h.precision != FSKHIP_PRECISION_F32 && h.precision != FSKHIP_PRECISION_F64) return fail(FSKHIP_E_INVALID, "%s: unknown precision %d in the snapshot", who, h.precision);
   if (h.amp_cap != 8u * h.d || h.d == 0 || h.d > (1u << 20) || h.wide > 1 || h.frac > 1 || (h.frac && !h.wide))
     return fail(FSKHIP_E_INVALID, "%s: inconsistent geometry in the snapshot (d %u, amp_cap %u, wide %u, frac %u)", who, h.d, h.amp_cap, h.wide, h.frac);
   s->L = snap_layout(h.precision, h.d, h.amp_cap, h.wide, h.frac);
   if (h.record_bytes != 4u * s->L.rec_words)
     return fail(FSKHIP_E_INVALID, "%s: record_bytes %u, but this geometry and precision make records of %u bytes", who, h.record_bytes, 4u * s->L.rec_words);
-  if (size != sizeof(SnapHeader) + (size_t)h.n_streams * h.record_bytes)
-    return fail(FSKHIP_E_INVALID, "%s: %zu bytes do not match n_streams x record_bytes (%zu + %u x %u)", who, size, sizeof(SnapHeader), h.n_streams, h.record_bytes);
-  s->rec = (const unsigned char *)buf + sizeof(SnapHeader);
-  if (sum) {
-    const uint64_t c = snap_checksum(h, s->rec, size - sizeof(SnapHeader));
-    if (c != h.checksum) return fail(FSKHIP_E_INVALID, "%s: checksum %016llx, the bytes sum to %016llx (a damaged snapshot)", who, (unsigned long long)h.checksum, (unsigned long long)c);
-  }
-  return FSKHIP_OK;
+  return image_open_back(who, "n_streams", buf, size, h, h.n_streams, &s->rec);
 }
 
 }  // namespace
@@ -166,20 +151,17 @@ int fskhip_snapshot_streams(fskhip_engine *e, const int64_t *sel, uint32_t n_sel
   static const char who[] = "fskhip_snapshot_streams";
   if (!e) return fail(FSKHIP_E_INVALID, "%s: null engine", who);
   if (!sel) n_sel = e->n_streams;
-  for (uint32_t i = 0; sel && i < n_sel; i++)
-    if (sel[i] < 0 || sel[i] >= (int64_t)e->n_streams) return fail(FSKHIP_E_INVALID, "%s: sel[%u] = %lld, the engine has %u streams", who, i, (long long)sel[i], e->n_streams);
+  if (const int rc = check_sel(who, "engine", sel, n_sel, e->n_streams)) return rc;
   const SnapLayout L = snap_layout(e->precision, e->P.d, e->P.amp_cap, e->P.wide, e->P.frac);
   const size_t rec_bytes = 4u * (size_t)L.rec_words, need = sizeof(SnapHeader) + (size_t)n_sel * rec_bytes;
-  if (written) *written = need;
-  if (!buf || cap < need) return fail(FSKHIP_E_OVERFLOW, "%s: a snapshot of %u streams takes %zu bytes, the buffer has %zu", who, n_sel, need, buf ? cap : (size_t)0);
+  if (const int rc = check_room(who, n_sel, need, buf, cap, written)) return rc;
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipDeviceSynchronize());
   if (const int rc = engine_refuse_handoff(who, "the engine", e)) return rc;
 
-  SnapHeader h;
-  std::memset(&h, 0, sizeof(h));
-  h.magic = kSnapMagic; h.format = kSnapFormat; h.rf_count = RF_COUNT; h.if_count = IF_COUNT; h.fields_hash = fields_hash();
-  h.header_bytes = sizeof(SnapHeader); h.record_bytes = (uint32_t)rec_bytes; h.n_streams = n_sel; h.precision = e->precision;
+  SnapHeader h = image_header<SnapHeader>(kSnapMagic, kSnapFormat, rec_bytes);
+  h.rf_count = RF_COUNT; h.if_count = IF_COUNT; h.fields_hash = fields_hash();
+  h.n_streams = n_sel; h.precision = e->precision;
   h.per_stream_configs = e->cfgs.size() == 1 ? 0u : 1u;
   h.d = e->P.d; h.amp_cap = e->P.amp_cap; h.wide = e->P.wide; h.frac = e->P.frac; h.n_bits = e->P.n_bits; h.ring_cap = e->P.ring_cap;
   h.ds_parity = e->ds_parity; h.ds_uniform = e->ds_uniform ? 1u : 0u; h.gen_odd = e->gen_odd ? 1u : 0u; h.quality = e->P.quality;
@@ -197,14 +179,11 @@ int fskhip_snapshot_streams(fskhip_engine *e, const int64_t *sel, uint32_t n_sel
   SnapSum sum;
   snap_sum(sum, &h, sizeof(h));   // (checksum field still 0)
 
-  // slab k: pack on the engine's stream, its copy on the copy stream; the host finishes slab k - 1 (the records' host parts, the
-  // checksum) while slab k is on its way
-  Stage st;
-  const uint32_t slab = std::min<uint32_t>(kSnapSlab, std::max<uint32_t>(n_sel, 1u));
-  SNAP_HIP(st.open((size_t)slab * rec_bytes, sel, sel ? n_sel : 0));
-  const uint32_t n_slabs = (n_sel + slab - 1) / slab;
-  auto finish = [&](uint32_t k) {
-    const uint32_t a = k * slab, b = std::min(n_sel, a + slab);
+  const auto pack = [&](const int64_t *d_sel, uint32_t first, uint32_t count, void *d_buf, hipStream_t stream) {
+    return launch_snap_pack(L, e->S, e->n_streams, d_sel, first, count, d_buf, stream);
+  };
+  // the host's part of a slab that has arrived: the records' host parts, the checksum
+  const auto finish = [&](uint32_t a, uint32_t b) {
     for (uint32_t r = a; r < b; r++) {
       const size_t s = sel ? (size_t)sel[r] : r;
       const fskhip_config &c = engine_stream_config(e, s);
@@ -217,18 +196,7 @@ int fskhip_snapshot_streams(fskhip_engine *e, const int64_t *sel, uint32_t n_sel
     }
     snap_sum(sum, rec + (size_t)a * rec_bytes, (size_t)(b - a) * rec_bytes);
   };
-  for (uint32_t k = 0; k < n_slabs; k++) {
-    const int b = (int)(k & 1u);
-    const uint32_t first = k * slab, count = std::min(n_sel - first, slab);
-    if (k >= 2) SNAP_HIP(hipStreamWaitEvent(e->host.stream, st.ev_copy[b], 0));
-    SNAP_HIP(launch_snap_pack(L, e->S, e->n_streams, st.d_idx, first, count, st.buf[b], e->host.stream));
-    SNAP_HIP(hipEventRecord(st.ev_kernel[b], e->host.stream));
-    SNAP_HIP(hipStreamWaitEvent(st.copy, st.ev_kernel[b], 0));
-    SNAP_HIP(hipMemcpyAsync(rec + (size_t)first * rec_bytes, st.buf[b], (size_t)count * rec_bytes, hipMemcpyDeviceToHost, st.copy));
-    SNAP_HIP(hipEventRecord(st.ev_copy[b], st.copy));
-    if (k >= 1) { SNAP_HIP(hipEventSynchronize(st.ev_copy[b ^ 1])); finish(k - 1); }
-  }
-  if (n_slabs) { SNAP_HIP(hipEventSynchronize(st.ev_copy[(n_slabs - 1) & 1u])); finish(n_slabs - 1); }
+  if (const int rc = stage_records_out(who, e->host.stream, sel, n_sel, rec_bytes, rec, pack, finish)) return rc;
   h.checksum = snap_sum_value(sum);
   std::memcpy(buf, &h, sizeof(h));
   return FSKHIP_OK;
@@ -306,7 +274,7 @@ int fskhip_snapshot_concat(const void *const *bufs, const size_t *sizes, uint32_
     if (bytes) std::memmove(rec + at, ss[k].rec, bytes);
     at += bytes;
   }
-  h.checksum = snap_checksum(h, rec, at);
+  h.checksum = image_checksum(h, rec, at);
   std::memcpy(out, &h, sizeof(h));
   return FSKHIP_OK;
 }
@@ -343,26 +311,10 @@ int fskhip_restore_streams(fskhip_engine *dst, const void *buf, size_t size, con
     const size_t r = (size_t)plan.frame_row;
     N.fr0 = frame_phase(s.int_word(r, IF_nco_lo), s.int_word(r, IF_nco_hi), s.int_word(r, IF_fr_lo), s.int_word(r, IF_fr_hi));
   }
-  // slab k of the records crosses to the device on the copy stream while slab k - 1 is unpacked on the engine's own; every launch
-  // covers all of dst and serves the streams whose record is in its slab (new streams: the first)
-  Stage st;
-  const uint32_t slab = std::min<uint32_t>(kSnapSlab, std::max<uint32_t>(h.n_streams, 1u));
-  SNAP_HIP(st.open((size_t)slab * h.record_bytes, map, n_map));
-  const uint32_t n_slabs = std::max<uint32_t>(1u, (h.n_streams + slab - 1) / slab);
-  for (uint32_t k = 0; k < n_slabs; k++) {
-    const int b = (int)(k & 1u);
-    const uint32_t first = k * slab, count = h.n_streams > first ? std::min(h.n_streams - first, slab) : 0u;
-    if (count) {
-      if (k >= 2) SNAP_HIP(hipStreamWaitEvent(st.copy, st.ev_kernel[b], 0));
-      SNAP_HIP(hipMemcpyAsync(st.buf[b], s.rec + (size_t)first * h.record_bytes, (size_t)count * h.record_bytes, hipMemcpyHostToDevice, st.copy));
-      SNAP_HIP(hipEventRecord(st.ev_copy[b], st.copy));
-      SNAP_HIP(hipStreamWaitEvent(dst->host.stream, st.ev_copy[b], 0));
-    }
-    SNAP_HIP(launch_snap_unpack(dst->precision, s.L, dst->S, dst->n_streams, st.d_idx, first, count, k == 0, N, st.buf[b], dst->host.stream));
-    SNAP_HIP(hipEventRecord(st.ev_kernel[b], dst->host.stream));
-  }
-  SNAP_HIP(hipStreamSynchronize(dst->host.stream));
-  SNAP_HIP(hipDeviceSynchronize());
+  const auto unpack = [&](const int64_t *d_map, uint32_t first, uint32_t count, bool fresh_too, void *d_buf, hipStream_t stream) {
+    return launch_snap_unpack(dst->precision, s.L, dst->S, dst->n_streams, d_map, first, count, fresh_too, N, d_buf, stream);
+  };
+  if (const int rc = stage_records_in(who, dst->host.stream, map, n_map, s.rec, h.n_streams, h.record_bytes, unpack)) return rc;
   remap_finish(dst, V, map, n_map, plan);
   return FSKHIP_OK;
 }

@@ -1,5 +1,8 @@
-// fsk_stage.h -- what the two image writers share (fsk_snapshot_api.hip: stream snapshots; fsk_processor_remap_api.hip: processor
-// snapshots): the checksum over an image, and the staging that carries records across PCIe in slabs.  Not part of the ABI.
+// fsk_stage.h -- what the two image formats share (fsk_snapshot_api.hip: stream snapshots; fsk_processor_remap_api.hip: processor
+// snapshots), each once: the checksum over an image, the frame every image has (the front and the back of opening one, the
+// common header fields, the writers' selection and room checks), and the two slab pipelines that carry records across PCIe --
+// stage_records_out for the writers, stage_records_in for the restores.  The formats keep their own headers, geometry checks
+// and kernels; no event chain is spelled anywhere else.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -59,6 +62,69 @@ struct Stage {
   }
 };
 
+// ---- the frame of an image: `H` is a format's header, which begins magic, format and has header_bytes, record_bytes, checksum ----
+template <class H>
+uint64_t image_checksum(H h, const void *records, size_t bytes) {
+  h.checksum = 0;
+  SnapSum s;
+  snap_sum(s, &h, sizeof(h));
+  snap_sum(s, records, bytes);
+  return snap_sum_value(s);
+}
+
+// a writer's header: zeroed (every byte of an image is defined), the frame's fields set; the format fills in the rest
+template <class H>
+H image_header(uint32_t magic, uint32_t format, size_t rec_bytes) {
+  H h;
+  std::memset(&h, 0, sizeof(h));
+  h.magic = magic; h.format = format; h.header_bytes = sizeof(H); h.record_bytes = (uint32_t)rec_bytes;
+  return h;
+}
+
+// The front of opening an image, `noun` being what the messages call it: null, shorter than a header, magic, format,
+// header_bytes.  The header is copied to *h (the caller's bytes need no alignment).  `stamp`: a format's check that goes
+// between format and header_bytes (which build wrote the image), returning a code.
+template <class H, class Stamp>
+int image_open_front(const char *who, const char *noun, const void *buf, size_t size, uint32_t magic, uint32_t format, H *h, Stamp stamp) {
+  if (!buf) return fail(FSKHIP_E_INVALID, "%s: null snapshot", who);
+  if (size < sizeof(H)) return fail(FSKHIP_E_INVALID, "%s: %zu bytes are fewer than a %s header's %zu", who, size, noun, sizeof(H));
+  std::memcpy(h, buf, sizeof(H));
+  if (h->magic != magic) return fail(FSKHIP_E_INVALID, "%s: not a %s (magic 0x%08x, expected 0x%08x)", who, noun, h->magic, magic);
+  if (h->format != format) return fail(FSKHIP_E_INVALID, "%s: %s format %u, this library reads format %u", who, noun, h->format, format);
+  if (const int rc = stamp()) return rc;
+  if (h->header_bytes != sizeof(H)) return fail(FSKHIP_E_INVALID, "%s: header_bytes %u, expected %zu", who, h->header_bytes, sizeof(H));
+  return FSKHIP_OK;
+}
+template <class H>
+int image_open_front(const char *who, const char *noun, const void *buf, size_t size, uint32_t magic, uint32_t format, H *h) {
+  return image_open_front(who, noun, buf, size, magic, format, h, [] { return (int)FSKHIP_OK; });
+}
+
+// The back, after the format's own geometry checks have vouched for record_bytes: the size is the header and n records
+// (`count_name`: the header's name for n), and the bytes sum to the checksum.  *rec: the first record.
+template <class H>
+int image_open_back(const char *who, const char *count_name, const void *buf, size_t size, const H &h, uint32_t n, const unsigned char **rec) {
+  if (size != sizeof(H) + (size_t)n * h.record_bytes)
+    return fail(FSKHIP_E_INVALID, "%s: %zu bytes do not match %s x record_bytes (%zu + %u x %u)", who, size, count_name, sizeof(H), n, h.record_bytes);
+  *rec = (const unsigned char *)buf + sizeof(H);
+  const uint64_t c = image_checksum(h, *rec, size - sizeof(H));
+  if (c != h.checksum) return fail(FSKHIP_E_INVALID, "%s: checksum %016llx, the bytes sum to %016llx (a damaged snapshot)", who, (unsigned long long)h.checksum, (unsigned long long)c);
+  return FSKHIP_OK;
+}
+
+// what the writers ask of a selection (`noun`: "engine" / "processor", which has n_streams) ...
+inline int check_sel(const char *who, const char *noun, const int64_t *sel, uint32_t n_sel, uint32_t n_streams) {
+  for (uint32_t i = 0; sel && i < n_sel; i++)
+    if (sel[i] < 0 || sel[i] >= (int64_t)n_streams) return fail(FSKHIP_E_INVALID, "%s: sel[%u] = %lld, the %s has %u streams", who, i, (long long)sel[i], noun, n_streams);
+  return FSKHIP_OK;
+}
+// ... and of the caller's buffer: *written is the size needed, whether or not the image fits
+inline int check_room(const char *who, uint32_t n_sel, size_t need, const void *buf, size_t cap, size_t *written) {
+  if (written) *written = need;
+  if (!buf || cap < need) return fail(FSKHIP_E_OVERFLOW, "%s: a snapshot of %u streams takes %zu bytes, the buffer has %zu", who, n_sel, need, buf ? cap : (size_t)0);
+  return FSKHIP_OK;
+}
+
 }  // namespace fsk
 
 // a HIP call inside a slab pipeline (`who` names the entry point): on failure the device is drained before the staging goes away
@@ -67,3 +133,62 @@ struct Stage {
     const hipError_t _e = (expr);                                                                      \
     if (_e != hipSuccess) { (void)hipDeviceSynchronize(); return fail(FSKHIP_E_HIP, "%s: %s: %s", who, #expr, hipGetErrorString(_e)); } \
   } while (0)
+
+namespace fsk {
+
+// ---- the slab pipelines.  Both own the Stage, the slab size and the event chain; a format brings its launches as callables
+// that return hipError_t.  `stream` is the owner's (the engine's, the processor's); the copies run on Stage::copy beside it.
+
+// Records out: records [0, n) of rec_bytes each -- record r being row idx[r] of the owner, or row r where idx is null -- to the
+// host at `rec`.  Slab k: pack(d_idx, first, count, d_buf, stream) on the owner's stream, then its copy on the copy stream;
+// finish(first_record, end_record) is the host's part for a slab that has arrived, run for slab k - 1 while slab k is on its way.
+template <class Pack, class Finish>
+int stage_records_out(const char *who, hipStream_t stream, const int64_t *idx, uint32_t n, size_t rec_bytes, unsigned char *rec, Pack pack, Finish finish) {
+  Stage st;
+  const uint32_t slab = std::min<uint32_t>(kSnapSlab, std::max<uint32_t>(n, 1u));
+  SNAP_HIP(st.open((size_t)slab * rec_bytes, idx, idx ? n : 0));
+  const uint32_t n_slabs = (n + slab - 1) / slab;
+  auto arrived = [&](uint32_t k) { finish(k * slab, std::min(n, k * slab + slab)); };
+  for (uint32_t k = 0; k < n_slabs; k++) {
+    const int b = (int)(k & 1u);
+    const uint32_t first = k * slab, count = std::min(n - first, slab);
+    if (k >= 2) SNAP_HIP(hipStreamWaitEvent(stream, st.ev_copy[b], 0));   // buffer b is free once slab k - 2 has left it
+    SNAP_HIP(pack(st.d_idx, first, count, st.buf[b], stream));
+    SNAP_HIP(hipEventRecord(st.ev_kernel[b], stream));
+    SNAP_HIP(hipStreamWaitEvent(st.copy, st.ev_kernel[b], 0));
+    SNAP_HIP(hipMemcpyAsync(rec + (size_t)first * rec_bytes, st.buf[b], (size_t)count * rec_bytes, hipMemcpyDeviceToHost, st.copy));
+    SNAP_HIP(hipEventRecord(st.ev_copy[b], st.copy));
+    if (k >= 1) { SNAP_HIP(hipEventSynchronize(st.ev_copy[b ^ 1])); arrived(k - 1); }
+  }
+  if (n_slabs) { SNAP_HIP(hipEventSynchronize(st.ev_copy[(n_slabs - 1) & 1u])); arrived(n_slabs - 1); }
+  return FSKHIP_OK;
+}
+
+// Records in: the n records at `rec` to the device, for a destination whose row i takes record map[i] (-1: a fresh row).  Slab k
+// crosses on the copy stream while slab k - 1 is unpacked on the owner's: unpack(d_map, first, count, fresh_too, d_buf, stream)
+// covers all of the destination and serves the rows whose record is in [first, first + count) -- and the fresh rows where
+// fresh_too, which is the first launch; there is a first launch even for no records.  Returns with the device idle.
+template <class Unpack>
+int stage_records_in(const char *who, hipStream_t stream, const int64_t *map, uint32_t n_map, const unsigned char *rec, uint32_t n, size_t rec_bytes, Unpack unpack) {
+  Stage st;
+  const uint32_t slab = std::min<uint32_t>(kSnapSlab, std::max<uint32_t>(n, 1u));
+  SNAP_HIP(st.open((size_t)slab * rec_bytes, map, n_map));
+  const uint32_t n_slabs = std::max<uint32_t>(1u, (n + slab - 1) / slab);
+  for (uint32_t k = 0; k < n_slabs; k++) {
+    const int b = (int)(k & 1u);
+    const uint32_t first = k * slab, count = n > first ? std::min(n - first, slab) : 0u;
+    if (count) {
+      if (k >= 2) SNAP_HIP(hipStreamWaitEvent(st.copy, st.ev_kernel[b], 0));   // buffer b is free once slab k - 2 is unpacked
+      SNAP_HIP(hipMemcpyAsync(st.buf[b], rec + (size_t)first * rec_bytes, (size_t)count * rec_bytes, hipMemcpyHostToDevice, st.copy));
+      SNAP_HIP(hipEventRecord(st.ev_copy[b], st.copy));
+      SNAP_HIP(hipStreamWaitEvent(stream, st.ev_copy[b], 0));
+    }
+    SNAP_HIP(unpack(st.d_idx, first, count, k == 0, st.buf[b], stream));
+    SNAP_HIP(hipEventRecord(st.ev_kernel[b], stream));
+  }
+  SNAP_HIP(hipStreamSynchronize(stream));
+  SNAP_HIP(hipDeviceSynchronize());
+  return FSKHIP_OK;
+}
+
+}  // namespace fsk

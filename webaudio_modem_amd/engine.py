@@ -103,6 +103,11 @@ def _blob(blob):
     return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
 
 
+def _struct_dict(st):
+    """a ctypes struct as a dict of its fields"""
+    return {k: getattr(st, k) for k, _ in st._fields_}
+
+
 def _config_dict(c):
     """fskhip_config -> FSKConfig dict (every field, the reference's names)"""
     return dict(sampleRate=c.sampleRate, baudRate=c.baudRate, markFrequency=c.markFrequency, spaceFrequency=c.spaceFrequency,
@@ -116,7 +121,7 @@ def snapshot_info(blob):
     b = _blob(blob)
     info = _lib.SnapshotInfo()
     _lib.check(_lib.lib().fskhip_snapshot_info_get(b.ctypes.data, b.nbytes, C.byref(info)))
-    return {k: getattr(info, k) for k, _ in _lib.SnapshotInfo._fields_}
+    return _struct_dict(info)
 
 
 def snapshot_stream_config(blob, i):
@@ -141,6 +146,27 @@ def snapshot_concat(blobs):
     out = np.zeros(need.value, np.uint8)
     _lib.check(L.fskhip_snapshot_concat(ptrs, sizes, len(bs), out.ctypes.data, out.nbytes, C.byref(need)))
     return out
+
+
+def _snapshot_plan(blob, stream_map, configs, range_error=True):
+    """What every from_snapshot starts with: (snapshot_info(blob), the map as an int64 array, the configs).  stream_map None
+    is every record in order.  configs None: read out of the snapshot -- the shared one, or record by record through the
+    map, where a -1 slot has none to take.  An entry past the records raises ValueError here if range_error; else it is left
+    to the library's refusal."""
+    info = snapshot_info(blob)
+    n = info["n_streams"]
+    m = np.arange(n, dtype=np.int64) if stream_map is None else np.asarray(stream_map, dtype=np.int64).reshape(-1)
+    if configs is None:
+        if not info["per_stream_configs"]:
+            configs = snapshot_stream_config(blob, 0)
+        else:
+            if (m < 0).any():
+                raise ValueError("a -1 slot needs an explicit config: the snapshot has per-stream configs")
+            if range_error and (m >= n).any():
+                raise ValueError("stream map entry out of range (%d records)" % n)
+            known = {}
+            configs = [known.setdefault(v, snapshot_stream_config(blob, v)) for v in m.tolist()]
+    return info, m, configs
 
 
 # Called with (n_streams, precision) by every new FSKEngine; returns a dict of fskhip_set_option() names -> values to apply on
@@ -258,18 +284,7 @@ class FSKEngine:
         new FSKCore; None: every record, in order).  Precision and configs are read out of the snapshot unless `configs` is
         given; a -1 slot needs an explicit config when the snapshot's configs are per stream."""
         b = _blob(blob)
-        info = snapshot_info(b)
-        m = list(range(info["n_streams"])) if stream_map is None else [int(v) for v in np.asarray(stream_map, dtype=np.int64).reshape(-1)]
-        if configs is None:
-            if not info["per_stream_configs"]:
-                configs = snapshot_stream_config(b, 0)
-            else:
-                if any(v < 0 for v in m):
-                    raise ValueError("a -1 slot needs an explicit config: the snapshot has per-stream configs")
-                if any(v >= info["n_streams"] for v in m):
-                    raise ValueError("stream map entry out of range (%d records)" % info["n_streams"])
-                known = {}
-                configs = [known.setdefault(v, snapshot_stream_config(b, v)) for v in m]
+        info, m, configs = _snapshot_plan(b, stream_map, configs)
         eng = cls(len(m), configs, device=device, precision=info["precision"], options=options)
         try:
             eng.restore_from(b, m)

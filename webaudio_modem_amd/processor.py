@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PROC_CLEAR_RX_ON_TX_COMPLETE, PROC_GRAPH  # noqa: F401
+from .engine import FSKEngine, _blob, _struct_dict
 
 
 class ChunkedModulator:
@@ -67,10 +68,10 @@ ProcessorBatchSnapshot = collections.namedtuple("ProcessorBatchSnapshot", ["engi
 
 def processor_snapshot_info(blob):
     """fskhip_processor_snapshot_info_get: what a processor snapshot holds (validated on the host, no device needed)"""
-    b = np.ascontiguousarray(blob if isinstance(blob, np.ndarray) else np.frombuffer(blob, dtype=np.uint8)).view(np.uint8).reshape(-1)
+    b = _blob(blob)
     info = _lib.ProcessorSnapshotInfo()
     _lib.check(_lib.lib().fskhip_processor_snapshot_info_get(b.ctypes.data, b.nbytes, C.byref(info)))
-    return {k: getattr(info, k) for k, _ in _lib.ProcessorSnapshotInfo._fields_}
+    return _struct_dict(info)
 
 
 class FSKProcessorBatch:
@@ -143,7 +144,6 @@ class FSKProcessorBatch:
         of both images (-1: a new FSKCore and FSKProcessor; None: every record, in order).  The engine is made by
         FSKEngine.from_snapshot, which checks the configs; rx_capacity is the image's.  The host counter
         processDemodulationCallCount is not part of an image and starts at 0."""
-        from .engine import FSKEngine
         info = processor_snapshot_info(snap.processor)
         m = np.arange(info["n_streams"], dtype=np.int64) if stream_map is None else np.ascontiguousarray(stream_map, dtype=np.int64).reshape(-1)
         eng = FSKEngine.from_snapshot(snap.engine, stream_map=m, configs=configs, device=device, options=options)
@@ -153,7 +153,7 @@ class FSKProcessorBatch:
             eng.close()
             raise
         try:
-            b = np.frombuffer(snap.processor, dtype=np.uint8)
+            b = _blob(snap.processor)
             _lib.check(nxt._L.fskhip_processor_restore(nxt._h, b.ctypes.data, b.nbytes, m.ctypes.data, len(m)))
         except Exception:
             nxt.close()

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PRECISION_F32
-from .engine import FSKEngine, snapshot_concat, snapshot_info, snapshot_stream_config
+from .engine import FSKEngine, snapshot_concat, _snapshot_plan
 from .sharding import all_shards
 
 
@@ -110,16 +110,7 @@ class FSKEngineSharded:
         """A new sharded batch whose stream i continues record stream_map[i] of the snapshot (-1: a new FSKCore; None: every
         record in order), spread over `devices`: every shard restores its slice of the map from the one blob.  Precision and
         configs come from the snapshot unless `configs` is given (a -1 slot needs one when the snapshot's are per stream)."""
-        info = snapshot_info(blob)
-        m = np.arange(info["n_streams"], dtype=np.int64) if stream_map is None else np.asarray(stream_map, dtype=np.int64).reshape(-1)
-        if configs is None:
-            if not info["per_stream_configs"]:
-                configs = snapshot_stream_config(blob, 0)
-            else:
-                if (m < 0).any():
-                    raise ValueError("a -1 slot needs an explicit config: the snapshot has per-stream configs")
-                known = {}
-                configs = [known.setdefault(int(v), snapshot_stream_config(blob, int(v))) for v in m]
+        info, m, configs = _snapshot_plan(blob, stream_map, configs, range_error=False)   # (an entry past the records: the library refuses it)
         new = cls(len(m), configs, devices=devices, precision=info["precision"], engine_factory=engine_factory)
         try:
             new._fan_out(lambda i, e, first, count: e.restore_from(blob, m[first:first + count]))
