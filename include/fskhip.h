@@ -29,7 +29,8 @@ extern "C" {
  * the multi-wave kernels is bounded ("Hand-off waits" below; an addition: no healthy call returns it); fskhip_remap_streams (an
  * addition, same version); stream snapshots -- fskhip_snapshot_bytes / _streams / _info_get / _stream_config / _concat,
  * fskhip_restore_streams (additions, same version); fskhip_processor_remap / _snapshot_bytes / _snapshot / _snapshot_info_get /
- * _restore in fskhip_next.h (additions, same version). */
+ * _restore in fskhip_next.h (additions, same version); capture formats -- FSKHIP_SAMPLES_* / FSKHIP_LAYOUT_*, fskhip_sample_bytes,
+ * fskhip_ingest_device, fskhip_demodulate_host_fmt (additions, same version). */
 #define FSKHIP_ABI_VERSION 8
 #define FSKHIP_MAX_PATTERN_BYTES 16
 
@@ -262,6 +263,47 @@ int fskhip_demodulate_host(fskhip_engine *e, float *samples, size_t n_per_stream
 int fskhip_demodulate_device(fskhip_engine *e, float *d_samples, size_t n_per_stream, size_t pitch,
                              uint8_t *d_out, size_t out_pitch, uint32_t *d_out_counts,
                              uint32_t *d_eod_counts, uint32_t flags, void *hip_stream);
+
+/*
+ * Capture formats (ABI 8, additions): what sound cards, WAV files, RTP gateways and telephone trunks deliver, widened to the
+ * float32 [stream][sample] rows above ON THE DEVICE, so that 2 or 1 bytes per sample cross PCIe instead of 4.  Every value is an
+ * integer of at most 16 bits times 2^-15, i.e. exact in float32:
+ *   FSKHIP_SAMPLES_F32    4 B  the float itself (a copy, or a transpose only)
+ *   FSKHIP_SAMPLES_S16    2 B  little-endian, signed: (float)x * (1.0f / 32768) (WebAudio's convention)
+ *   FSKHIP_SAMPLES_MULAW  1 B  G.711 mu-law: u = ~b; mag = ((((u & 15) << 3) + 0x84) << ((u >> 4) & 7)) - 0x84;
+ *                              v = (u & 0x80) ? -mag : mag; v / 32768.0f (range +-32124)
+ *   FSKHIP_SAMPLES_ALAW   1 B  G.711 A-law: a = b ^ 0x55; e = (a >> 4) & 7; m = a & 15;
+ *                              mag = e ? ((m << 4) + 0x108) << (e - 1) : (m << 4) + 8; v = (a & 0x80) ? mag : -mag; v / 32768.0f
+ *                              (range +-32256)
+ *   FSKHIP_LAYOUT_STREAM_MAJOR  element (s, t) at s * src_pitch + t, src_pitch >= n_per_stream: the shape of fskhip_demodulate_*
+ *   FSKHIP_LAYOUT_SAMPLE_MAJOR  element (s, t) at t * src_pitch + s, src_pitch >= n_streams: interleaved capture frames
+ * Pitches are in elements.
+ * fskhip_sample_bytes         4, 2, 1, 1; 0 for an unknown format.
+ * fskhip_ingest_device        d_dst[s * dst_pitch + t] = value of element (s, t) of d_src for t < n_per_stream, nothing else is
+ *                             written; on the current device, asynchronous on `hip_stream`, like fskhip_crc16_device.  d_src needs
+ *                             the alignment of its element only, d_dst that of a float, any pitches (dst_pitch >= n_per_stream).  A
+ *                             host with device-resident capture buffers converts into a float buffer of its own and calls
+ *                             fskhip_demodulate_device as before.  n_streams == 0 or n_per_stream == 0: FSKHIP_OK, nothing
+ *                             launched.  FSKHIP_E_INVALID: unknown format or layout, a null or misaligned pointer with work to
+ *                             do, a pitch that is too small.
+ * fskhip_demodulate_host_fmt  fskhip_demodulate_host's contract for `samples` (host memory, read only) in any format and layout:
+ *                             the narrow samples cross PCIe in the same time slabs (option "host_slab", in samples), the device
+ *                             widens each slab, and the demodulators run on exactly the floats a host-side conversion would
+ *                             have handed to fskhip_demodulate_host -- same bytes, counts and state.  A time slab of a
+ *                             sample-major source is one contiguous range of frames and crosses as ONE copy, columns beyond
+ *                             n_streams included (a shard of a wider capture passes its first column and the full frame pitch).
+ *                             FSKHIP_SAMPLES_F32 in stream-major layout IS fskhip_demodulate_host.  FSKHIP_DEMOD_WRITEBACK_AGC
+ *                             with any other format or layout is FSKHIP_E_INVALID (there is nothing of the caller's to write
+ *                             floats back into) and leaves the engine as it was.
+ */
+enum { FSKHIP_SAMPLES_F32 = 0, FSKHIP_SAMPLES_S16 = 1, FSKHIP_SAMPLES_MULAW = 2, FSKHIP_SAMPLES_ALAW = 3 };
+enum { FSKHIP_LAYOUT_STREAM_MAJOR = 0, FSKHIP_LAYOUT_SAMPLE_MAJOR = 1 };
+size_t fskhip_sample_bytes(int format);
+int fskhip_ingest_device(const void *d_src, int format, int layout, uint32_t n_streams, size_t n_per_stream,
+                         size_t src_pitch, float *d_dst, size_t dst_pitch, void *hip_stream);
+int fskhip_demodulate_host_fmt(fskhip_engine *e, const void *samples, int format, int layout, size_t n_per_stream,
+                               size_t src_pitch, uint8_t *out, size_t out_pitch, uint32_t *out_counts,
+                               uint32_t *eod_counts, uint32_t flags);
 
 /*
  * modulateData(bytes) (fsk.ts:377-424) for every stream.  Stream s modulates

@@ -41,11 +41,19 @@ export interface SignalQualityEstimates {
   snr: number; ber: number; eyeOpening: number; phaseJitter: number; frequencyOffset: number;
   signalLevel: number; noiseFloor: number; frames: number; bytes: number;
 }
+export type SampleArray = Int16Array | Uint8Array | Float32Array;
+export type SampleFormat = 'f32' | 's16' | 'mulaw' | 'alaw' | 0 | 1 | 2 | 3;
+export type SampleLayout = 'stream' | 'sample' | 0 | 1;
+export const SAMPLE_FORMATS: { f32: 0; s16: 1; mulaw: 2; alaw: 3 };
+export const SAMPLE_LAYOUTS: { stream: 0; sample: 1 };
 export class FSKBatch {
   constructor(nStreams: number, configs: Partial<FSKConfig> | Partial<FSKConfig>[], options?: { device?: number; precision?: 0 | 1 });
   demodulateData(samples: Float32Array, nPerStream: number, pitch?: number, writebackAgc?: boolean): { bytes: Uint8Array[]; eod: Uint32Array };
   /** the same on a libuv worker thread (N-API async work); one call in flight per batch */
   demodulateDataAsync(samples: Float32Array, nPerStream: number, pitch?: number, writebackAgc?: boolean): Promise<{ bytes: Uint8Array[]; eod: Uint32Array }>;
+  /** demodulateData for capture samples as they arrive: Int16Array ('s16'), G.711 Uint8Array ('mulaw' | 'alaw') or Float32Array ('f32'); layout 'stream' = [S][pitch], 'sample' = interleaved frames [nPerStream][pitch >= S] */
+  demodulateSamples(samples: SampleArray, format: SampleFormat, layout: SampleLayout | undefined, nPerStream: number, pitch?: number): { bytes: Uint8Array[]; eod: Uint32Array };
+  demodulateSamplesAsync(samples: SampleArray, format: SampleFormat, layout: SampleLayout | undefined, nPerStream: number, pitch?: number): Promise<{ bytes: Uint8Array[]; eod: Uint32Array }>;
   modulateData(payloads: Uint8Array[]): Float32Array[];
   reset(stream?: number): void;
   getStatus(stream?: number): FSKStatus;
@@ -73,6 +81,8 @@ export class FSKBatchSharded {
   constructor(nStreams: number, configs: Partial<FSKConfig> | Partial<FSKConfig>[], options?: { devices?: number[]; precision?: 0 | 1 });
   readonly shards: { first: number; count: number; device: number; batch: FSKBatch }[];
   demodulateData(samples: Float32Array, nPerStream: number, pitch?: number, writebackAgc?: boolean): Promise<{ bytes: Uint8Array[]; eod: Uint32Array }>;
+  /** FSKBatch.demodulateSamples over the shards, no host copy: a shard takes a row block ('stream') or a column block with the full frame pitch ('sample') */
+  demodulateSamples(samples: SampleArray, format: SampleFormat, layout: SampleLayout | undefined, nPerStream: number, pitch?: number): Promise<{ bytes: Uint8Array[]; eod: Uint32Array }>;
   modulateData(payloads: Uint8Array[]): Float32Array[];
   reset(stream?: number): void;
   getStatus(stream?: number): FSKStatus;

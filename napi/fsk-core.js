@@ -126,6 +126,20 @@ class FSKCore extends EventEmitter {
   }
 }
 
+// capture formats and layouts (include/fskhip.h: FSKHIP_SAMPLES_* / FSKHIP_LAYOUT_*), by name or by value
+const SAMPLE_FORMATS = { f32: 0, s16: 1, mulaw: 2, alaw: 3 };
+const SAMPLE_LAYOUTS = { stream: 0, sample: 1 };
+function sampleFormat(f) {
+  const v = typeof f === 'string' ? SAMPLE_FORMATS[f.toLowerCase()] : f;
+  if (!(v >= 0 && v <= 3)) throw new TypeError('unknown sample format ' + f);
+  return v;
+}
+function sampleLayout(l) {
+  const v = l === undefined || l === null ? 0 : typeof l === 'string' ? SAMPLE_LAYOUTS[l.toLowerCase()] : l;
+  if (v !== 0 && v !== 1) throw new TypeError('unknown layout ' + l);
+  return v;
+}
+
 // S independent FSKCore instances in one engine: samples are [S][N] stream-major Float32Array.
 class FSKBatch {
   constructor(nStreams, configs, options = {}) {
@@ -147,6 +161,23 @@ class FSKBatch {
   // touched until it settles, and one call may be in flight per batch
   async demodulateDataAsync(samples, nPerStream, pitch, writebackAgc) {
     const r = await addon.demodulateAsync(this.handle, samples, nPerStream, pitch || nPerStream, writebackAgc ? DEMOD_WRITEBACK_AGC : 0);
+    const bytes = [];
+    for (let s = 0; s < this.nStreams; s++) bytes.push(r.out.slice(s * r.outPitch, s * r.outPitch + r.counts[s]));
+    return { bytes, eod: r.eod };
+  }
+  // demodulateData for capture samples as they arrive (include/fskhip.h, fskhip_demodulate_host_fmt): an Int16Array ('s16'), a
+  // Uint8Array of G.711 codes ('mulaw' / 'alaw') or a Float32Array ('f32'); layout 'stream' = [S][pitch], 'sample' = interleaved
+  // frames [nPerStream][pitch >= S].  The narrow samples cross PCIe and are widened on the device.  Returns {bytes, eod}.
+  demodulateSamples(samples, format, layout, nPerStream, pitch) {
+    const lay = sampleLayout(layout);
+    const r = addon.demodulateSamples(this.handle, samples, sampleFormat(format), lay, nPerStream, pitch || (lay ? this.nStreams : nPerStream));
+    const bytes = [];
+    for (let s = 0; s < this.nStreams; s++) bytes.push(r.out.slice(s * r.outPitch, s * r.outPitch + r.counts[s]));
+    return { bytes, eod: r.eod };
+  }
+  async demodulateSamplesAsync(samples, format, layout, nPerStream, pitch) {
+    const lay = sampleLayout(layout);
+    const r = await addon.demodulateSamplesAsync(this.handle, samples, sampleFormat(format), lay, nPerStream, pitch || (lay ? this.nStreams : nPerStream));
     const bytes = [];
     for (let s = 0; s < this.nStreams; s++) bytes.push(r.out.slice(s * r.outPitch, s * r.outPitch + r.counts[s]));
     return { bytes, eod: r.eod };
@@ -268,6 +299,18 @@ class FSKBatchSharded {
     parts.forEach((r, i) => { r.bytes.forEach((b) => bytes.push(b)); eod.set(r.eod, this.shards[i].first); });
     return { bytes, eod };
   }
+  // FSKBatch.demodulateSamples over the shards, without a host copy: a shard's streams are a row block of a stream-major
+  // array, and a COLUMN block of interleaved frames -- the array from its first column on, with the full frame pitch
+  async demodulateSamples(samples, format, layout, nPerStream, pitch) {
+    const lay = sampleLayout(layout);
+    const p = pitch || (lay ? this.nStreams : nPerStream);
+    const parts = await Promise.all(this.shards.map((sh) =>
+      sh.batch.demodulateSamplesAsync(lay ? samples.subarray(sh.first) : samples.subarray(sh.first * p, (sh.first + sh.count) * p), format, lay, nPerStream, p)));
+    const bytes = [];
+    const eod = new Uint32Array(this.nStreams);
+    parts.forEach((r, i) => { r.bytes.forEach((b) => bytes.push(b)); eod.set(r.eod, this.shards[i].first); });
+    return { bytes, eod };
+  }
   modulateData(payloads) {
     if (payloads.length !== this.nStreams) throw new Error('need one payload per stream');
     let out = [];
@@ -316,4 +359,4 @@ class FSKBatchSharded {
 const snapshotInfo = (buf) => addon.snapshotInfo(buf);
 const snapshotConcat = (bufs) => addon.snapshotConcat(bufs);
 
-module.exports = { FSKCore, FSKBatch, FSKBatchSharded, snapshotInfo, snapshotConcat, DEFAULT_FSK_CONFIG, Event, EventEmitter, PRECISION_F32, PRECISION_F64, addon };
+module.exports = { FSKCore, FSKBatch, FSKBatchSharded, SAMPLE_FORMATS, SAMPLE_LAYOUTS, snapshotInfo, snapshotConcat, DEFAULT_FSK_CONFIG, Event, EventEmitter, PRECISION_F32, PRECISION_F64, addon };

@@ -11,6 +11,8 @@
 //   destroy(handle)
 //   demodulate(handle, samples: Float32Array, nPerStream, pitch, flags) -> {out: Uint8Array, outPitch, counts: Uint32Array, eod: Uint32Array}
 //   demodulateAsync(... same ...) -> Promise of the same object; runs on a libuv worker thread
+//   demodulateSamples(handle, samples: Int16Array | Uint8Array | Float32Array, format, layout, nPerStream, pitch) -> the same object:
+//     capture samples as they arrive (FSKHIP_SAMPLES_* / FSKHIP_LAYOUT_*, fskhip_demodulate_host_fmt); demodulateSamplesAsync likewise
 //   modulate(handle, payloads: Uint8Array, lens: Uint32Array, payloadPitch) -> {out: Float32Array, outPitch, lens: Uint32Array}
 //   modulatedLength(handle, nBytes) -> number
 //   reset(handle, stream)            stream < 0: all
@@ -153,26 +155,42 @@ static napi_value Destroy(napi_env env, napi_callback_info info) {
 // What demodulate and demodulateAsync share: one call's arguments, validated, and its outputs, allocated ...
 struct DemodCall {
   fskhip_engine *e = nullptr;
-  float *samples = nullptr;
+  void *samples = nullptr;
+  int32_t format = FSKHIP_SAMPLES_F32, layout = FSKHIP_LAYOUT_STREAM_MAJOR;   // (as they are: fskhip_demodulate_host's own call)
   uint8_t *out = nullptr;
   uint32_t *counts = nullptr, *eod = nullptr;
   uint32_t n = 0, pitch = 0, flags = 0;
   size_t out_pitch = 0;
 };
 struct DemodArrays { napi_value samples, out, counts, eod; };
-static DemodCall *demod_prepare(napi_env env, napi_callback_info info, DemodCall *c, DemodArrays *a) {   // (nullptr: thrown)
-  ARGS_UPTO(5);
+// fmt: the arguments of demodulateSamples (handle, samples, format, layout, nPerStream, pitch) instead of demodulate's
+static DemodCall *demod_prepare(napi_env env, napi_callback_info info, DemodCall *c, DemodArrays *a, bool fmt = false) {   // (nullptr: thrown)
+  ARGS_UPTO(6);
   c->e = get_engine(env, argv[0]);
   if (!c->e) return nullptr;
   napi_typedarray_type tt;
   size_t len = 0;
   void *data = nullptr;
   NAPI_OK(napi_get_typedarray_info(env, argv[1], &tt, &len, &data, nullptr, nullptr));
-  if (tt != napi_float32_array) { napi_throw_type_error(env, nullptr, "samples must be a Float32Array"); return nullptr; }
-  c->samples = (float *)data;
-  c->n = u32(env, argv[2]); c->pitch = u32(env, argv[3]); c->flags = u32(env, argv[4]);
+  if (fmt) {
+    c->format = i32(env, argv[2]); c->layout = i32(env, argv[3]);
+    c->n = u32(env, argv[4]); c->pitch = u32(env, argv[5]);
+    const napi_typedarray_type want = c->format == FSKHIP_SAMPLES_F32 ? napi_float32_array : c->format == FSKHIP_SAMPLES_S16 ? napi_int16_array : napi_uint8_array;
+    if (!fskhip_sample_bytes(c->format) || (c->layout != FSKHIP_LAYOUT_STREAM_MAJOR && c->layout != FSKHIP_LAYOUT_SAMPLE_MAJOR)) {
+      napi_throw_type_error(env, nullptr, "unknown sample format or layout");
+      return nullptr;
+    }
+    if (tt != want) { napi_throw_type_error(env, nullptr, "samples must be the format's typed array: Float32Array, Int16Array or (G.711) Uint8Array"); return nullptr; }
+  } else {
+    if (tt != napi_float32_array) { napi_throw_type_error(env, nullptr, "samples must be a Float32Array"); return nullptr; }
+    c->n = u32(env, argv[2]); c->pitch = u32(env, argv[3]); c->flags = u32(env, argv[4]);
+  }
+  c->samples = data;
   const uint32_t S = fskhip_n_streams(c->e);
-  if (c->pitch < c->n || (size_t)c->pitch * (S ? S - 1 : 0) + c->n > len) { napi_throw_range_error(env, nullptr, "samples too short"); return nullptr; }
+  // the last row (stream-major) / the last frame (sample-major) may end with its own samples
+  const bool frames = c->layout == FSKHIP_LAYOUT_SAMPLE_MAJOR;
+  const size_t rows = frames ? c->n : S, cols = frames ? S : c->n;
+  if (c->pitch < cols || (rows && (size_t)c->pitch * (rows - 1) + cols > len)) { napi_throw_range_error(env, nullptr, "samples too short"); return nullptr; }
   c->out_pitch = fskhip_max_bytes(c->e, c->n);  // the library's own bound (a byte needs >= 8 bit times of samplesPerBit samples)
   void *out = nullptr, *counts = nullptr, *eod = nullptr;
   a->samples = argv[1];
@@ -194,14 +212,20 @@ static napi_value demod_result(napi_env env, size_t out_pitch, napi_value out_v,
   return res;
 }
 
-static napi_value Demodulate(napi_env env, napi_callback_info info) {
+// (format F32 in stream-major layout IS fskhip_demodulate_host, write-back flag included: include/fskhip.h)
+static int demod_run(const DemodCall &c) {
+  return fskhip_demodulate_host_fmt(c.e, c.samples, c.format, c.layout, c.n, c.pitch, c.out, c.out_pitch, c.counts, c.eod, c.flags);
+}
+static napi_value demodulate_sync(napi_env env, napi_callback_info info, bool fmt) {
   DemodCall c;
   DemodArrays a;
-  if (!demod_prepare(env, info, &c, &a)) return nullptr;
-  int rc = fskhip_demodulate_host(c.e, c.samples, c.n, c.pitch, c.out, c.out_pitch, c.counts, c.eod, c.flags);
+  if (!demod_prepare(env, info, &c, &a, fmt)) return nullptr;
+  int rc = demod_run(c);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   return demod_result(env, c.out_pitch, a.out, a.counts, a.eod);
 }
+static napi_value Demodulate(napi_env env, napi_callback_info info) { return demodulate_sync(env, info, false); }
+static napi_value DemodulateSamples(napi_env env, napi_callback_info info) { return demodulate_sync(env, info, true); }
 
 // demodulateAsync: the same call on a libuv worker thread, for batches big enough to matter to the event loop
 // (SURVEY 8b "Threading").  Output arrays are created up front on the JS thread; the input Float32Array is
@@ -217,7 +241,7 @@ struct DemodWork {
 static void demod_execute(napi_env, void *data) {
   DemodWork *w = (DemodWork *)data;
   const DemodCall &c = w->c;
-  w->rc = fskhip_demodulate_host(c.e, c.samples, c.n, c.pitch, c.out, c.out_pitch, c.counts, c.eod, c.flags);
+  w->rc = demod_run(c);
   if (w->rc != FSKHIP_OK) w->err = fskhip_last_error();  // thread-local: read it on the thread that failed
 }
 static void demod_complete(napi_env env, napi_status, void *data) {
@@ -248,10 +272,10 @@ static void demod_complete(napi_env env, napi_status, void *data) {
   delete w;
 }
 
-static napi_value DemodulateAsync(napi_env env, napi_callback_info info) {
+static napi_value demodulate_async(napi_env env, napi_callback_info info, bool fmt) {
   DemodCall c;
   DemodArrays a;
-  if (!demod_prepare(env, info, &c, &a)) return nullptr;
+  if (!demod_prepare(env, info, &c, &a, fmt)) return nullptr;
   DemodWork *w = new DemodWork();
   w->c = c;
   napi_create_reference(env, a.samples, 1, &w->in_ref);
@@ -266,6 +290,8 @@ static napi_value DemodulateAsync(napi_env env, napi_callback_info info) {
   napi_queue_async_work(env, w->work);
   return promise;
 }
+static napi_value DemodulateAsync(napi_env env, napi_callback_info info) { return demodulate_async(env, info, false); }
+static napi_value DemodulateSamplesAsync(napi_env env, napi_callback_info info) { return demodulate_async(env, info, true); }
 
 // modulateData (fsk.ts:377-424) for every stream
 static napi_value Modulate(napi_env env, napi_callback_info info) {
@@ -561,6 +587,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"destroy", nullptr, Destroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"demodulate", nullptr, Demodulate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"demodulateAsync", nullptr, DemodulateAsync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"demodulateSamples", nullptr, DemodulateSamples, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"demodulateSamplesAsync", nullptr, DemodulateSamplesAsync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"modulate", nullptr, Modulate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"modulatedLength", nullptr, ModulatedLength, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"reset", nullptr, Reset, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -17,6 +17,8 @@ PROC_CLEAR_RX_ON_TX_COMPLETE, PROC_GRAPH = 1, 2
 XM_NEED_MORE, XM_EOT, XM_TRUNCATED, XM_INVALID_SEQUENCE, XM_INVALID_CRC, XM_UNEXPECTED_SEQUENCE = 0, 1, 2, 3, 4, 5
 PRECISION_F32, PRECISION_F64 = 0, 1
 DEMOD_WRITEBACK_AGC = 1
+SAMPLES_F32, SAMPLES_S16, SAMPLES_MULAW, SAMPLES_ALAW = 0, 1, 2, 3
+LAYOUT_STREAM_MAJOR, LAYOUT_SAMPLE_MAJOR = 0, 1
 
 
 class Config(C.Structure):
@@ -81,6 +83,9 @@ _SYMBOLS = [
     ("fskhip_blk_lanes", C.c_uint32, [_P]),
     ("fskhip_demodulate_host", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_uint32]),
     ("fskhip_demodulate_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_uint32, _P]),
+    ("fskhip_sample_bytes", C.c_size_t, [C.c_int]),
+    ("fskhip_ingest_device", C.c_int, [_P, C.c_int, C.c_int, C.c_uint32, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P]),
+    ("fskhip_demodulate_host_fmt", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_uint32]),
     ("fskhip_modulated_length", C.c_size_t, [_P, C.c_size_t]),
     ("fskhip_modulate_host", C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
     ("fskhip_modulate_device", C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t, _P, _P]),

@@ -1,5 +1,5 @@
-// fsk_dispatch.hip -- C ABI of libfskhip.so (include/fskhip.h): fskhip_demodulate_device / _host -- which kernels a call
-// gets, their launches, and the host-side bookkeeping the choice depends on.
+// fsk_dispatch.hip -- C ABI of libfskhip.so (include/fskhip.h): fskhip_demodulate_device / _host / _host_fmt -- which kernels a call
+// gets, their launches, the host-side bookkeeping the choice depends on, and the host forms' copy / compute pipeline.
 #include "fsk_engine.h"
 #include "fsk_launch.h"
 
@@ -201,26 +201,24 @@ int demod_device_impl(fskhip_engine *e, float *d_samples, size_t n, size_t pitch
   note_call(e, n, count_call ? 1u : 0u);
   return FSKHIP_OK;
 }
-}  // namespace
-
-extern "C" {
-int fskhip_demodulate_device(fskhip_engine *e, float *d_samples, size_t n, size_t pitch, uint8_t *d_out, size_t out_pitch,
-                             uint32_t *d_out_counts, uint32_t *d_eod_counts, uint32_t flags, void *hip_stream) {
-  return demod_device_impl(e, d_samples, n, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, flags, hip_stream, false, true);
-}
-// Host buffers in, bytes out.  A call longer than one time slab is a two-buffer pipeline over TIME: slab j+1 crosses PCIe
-// on the copy stream while slab j is demodulated on the compute stream.  Cutting along time needs no sub-batch launches,
-// and the engine gives the same bytes for any cut (the reference is a streaming state machine, fsk.ts:190-222).  The
-// copies only overlap if `samples` is page-locked (fskhip_host_alloc, or any pinned buffer of the caller); with pageable
-// memory the runtime stages each copy itself and the pipeline degrades gracefully to what one big copy costs.
-int fskhip_demodulate_host(fskhip_engine *e, float *samples, size_t n, size_t pitch, uint8_t *out, size_t out_pitch,
-                           uint32_t *out_counts, uint32_t *eod_counts, uint32_t flags) {
+// fskhip_demodulate_host (format F32, stream-major: `samples` is the caller's float*, staged as it is and written back into where
+// FSKHIP_DEMOD_WRITEBACK_AGC asks) and fskhip_demodulate_host_fmt (anything else: the samples cross PCIe as they are, into a narrow
+// staging slab, and fsk_ingest.hip's kernel widens them into the float staging tile on the compute stream).  One time pipeline:
+// the same slab lengths in samples, the same two streams and events.
+int demod_host_impl(fskhip_engine *e, const void *samples_, int format, int layout, size_t n, size_t pitch, uint8_t *out, size_t out_pitch,
+                    uint32_t *out_counts, uint32_t *eod_counts, uint32_t flags) {
   if (!e) return fail(FSKHIP_E_NOT_CONFIGURED, "FSK demodulator not configured");
-  if (!out_counts || (n > 0 && !samples) || (out_pitch > 0 && !out)) return fail(FSKHIP_E_INVALID, "null buffer");
-  if (pitch < n) return fail(FSKHIP_E_INVALID, "pitch %zu < n_per_stream %zu", pitch, n);
-  HIP_TRY(hipSetDevice(e->device));
+  if (!out_counts || (n > 0 && !samples_) || (out_pitch > 0 && !out)) return fail(FSKHIP_E_INVALID, "null buffer");
   const size_t S = e->n_streams;
+  const bool direct = format == FSKHIP_SAMPLES_F32 && layout == FSKHIP_LAYOUT_STREAM_MAJOR;
+  const bool frames = layout == FSKHIP_LAYOUT_SAMPLE_MAJOR;
+  if (!frames && pitch < n) return fail(FSKHIP_E_INVALID, "pitch %zu < n_per_stream %zu", pitch, n);
+  if (frames && pitch < S) return fail(FSKHIP_E_INVALID, "frame pitch %zu < n_streams %zu", pitch, S);
   const bool wb = (flags & FSKHIP_DEMOD_WRITEBACK_AGC) != 0;
+  if (wb && !direct) return fail(FSKHIP_E_INVALID, "FSKHIP_DEMOD_WRITEBACK_AGC needs float samples in stream-major layout: there is nothing to write floats back into");
+  HIP_TRY(hipSetDevice(e->device));
+  float *const samples = direct ? (float *)const_cast<void *>(samples_) : nullptr;
+  const size_t esz = ingest_sample_bytes(format);
   // slab length: ~96 MB of samples per slab, a multiple of 16 (whole tiles, even decimator parity), at least 4096
   size_t slab = ((size_t)96 << 20) / (S * sizeof(float));
   slab = slab < 4096 ? 4096 : slab;
@@ -235,21 +233,38 @@ int fskhip_demodulate_host(fskhip_engine *e, float *samples, size_t n, size_t pi
   // later even-length call would run sample by sample (fsk_api.hip's silent performance cliff).
   const size_t dpitch = ((len0 + 3 + 3) & ~(size_t)3) ? ((len0 + 3 + 3) & ~(size_t)3) : 4;
   auto shift = [&]() -> size_t { return (e->precision == FSKHIP_PRECISION_F32 && e->ds_uniform && (e->ds_parity & 1u)) ? 3 : 0; };
+  // the narrow staging slabs: rows of 16-byte-aligned pitch (stream-major), or the slab's frames as they are (sample-major)
+  const size_t npitch = frames ? pitch : (len0 + 15) & ~(size_t)15;
+  const size_t nbytes = (frames ? len0 * pitch : S * npitch) * esz;
+  // samples [off, off + len) of every stream: host -> staging slab b, on `st` (direct: straight into the float tile `stg`)
+  auto stage_in = [&](int b, float *stg, size_t off, size_t len, hipStream_t st) -> hipError_t {
+    if (direct) return hipMemcpy2DAsync(stg, dpitch * sizeof(float), samples + off, pitch * sizeof(float), len * sizeof(float), S, hipMemcpyHostToDevice, st);
+    const uint8_t *from = (const uint8_t *)samples_ + off * (frames ? pitch : 1) * esz;
+    if (frames) return hipMemcpyAsync(e->host.d_narrow[b], from, ((len - 1) * pitch + S) * esz, hipMemcpyHostToDevice, st);   // (the last frame: its S columns only)
+    return hipMemcpy2DAsync(e->host.d_narrow[b], npitch * esz, from, pitch * esz, len * esz, S, hipMemcpyHostToDevice, st);
+  };
+  // ... and from there into the float tile, on the compute stream (direct: they are there already)
+  auto widen = [&](int b, float *stg, size_t len) -> hipError_t {
+    return direct ? hipSuccess : launch_ingest(e->host.d_narrow[b], format, layout, (uint32_t)S, len, npitch, stg, dpitch, e->host.stream);
+  };
   int rc;
   if ((rc = ensure(e->host.d_samples, e->host.d_samples_cap, dpitch * S)) != FSKHIP_OK) return rc;
   if ((rc = ensure(e->host.d_out, e->host.d_out_cap, (out_pitch ? out_pitch : 1) * S)) != FSKHIP_OK) return rc;
+  if (!direct && n > 0 && (rc = ensure(e->host.d_narrow[0], e->host.d_narrow_cap[0], nbytes)) != FSKHIP_OK) return rc;
   if (!piped) {
     float *stg = e->host.d_samples + shift();
-    if (n > 0)
-      HIP_TRY(hipMemcpy2DAsync(stg, dpitch * sizeof(float), samples, pitch * sizeof(float), n * sizeof(float), S,
-                               hipMemcpyHostToDevice, e->host.stream));
-    rc = fskhip_demodulate_device(e, stg, n, dpitch, e->host.d_out, out_pitch, e->host.d_counts, e->host.d_eod, flags, e->host.stream);
+    if (n > 0) {
+      HIP_TRY(stage_in(0, stg, 0, n, e->host.stream));
+      HIP_TRY(widen(0, stg, n));
+    }
+    rc = demod_device_impl(e, stg, n, dpitch, e->host.d_out, out_pitch, e->host.d_counts, e->host.d_eod, flags, e->host.stream, false, true);
     if (rc != FSKHIP_OK) return rc;
     if (wb && n > 0)
       HIP_TRY(hipMemcpy2DAsync(samples, pitch * sizeof(float), stg, dpitch * sizeof(float), n * sizeof(float), S,
                                hipMemcpyDeviceToHost, e->host.stream));
   } else {
     if ((rc = ensure(e->host.d_samples2, e->host.d_samples2_cap, dpitch * S)) != FSKHIP_OK) return rc;
+    if (!direct && (rc = ensure(e->host.d_narrow[1], e->host.d_narrow_cap[1], nbytes)) != FSKHIP_OK) return rc;
     if (!e->host.copy_stream) {
       HIP_TRY(hipStreamCreateWithFlags(&e->host.copy_stream, hipStreamNonBlocking));
       for (int i = 0; i < 2; i++) {
@@ -268,10 +283,10 @@ int fskhip_demodulate_host(fskhip_engine *e, float *samples, size_t n, size_t pi
       const int b = (int)(j & 1);
       float *stg = buf[b] + shift();               // (the parity at this slab's start: slabs are multiples of 16 samples)
       if (j >= 2) PIPE_TRY(hipStreamWaitEvent(e->host.copy_stream, e->host.ev_used_up[b], 0));   // its previous user has finished
-      PIPE_TRY(hipMemcpy2DAsync(stg, dpitch * sizeof(float), samples + off, pitch * sizeof(float), len * sizeof(float), S,
-                               hipMemcpyHostToDevice, e->host.copy_stream));
+      PIPE_TRY(stage_in(b, stg, off, len, e->host.copy_stream));
       PIPE_TRY(hipEventRecord(e->host.ev_copied[b], e->host.copy_stream));
       PIPE_TRY(hipStreamWaitEvent(e->host.stream, e->host.ev_copied[b], 0));
+      PIPE_TRY(widen(b, stg, len));
       rc = demod_device_impl(e, stg, len, dpitch, e->host.d_out, out_pitch, e->host.d_counts, e->host.d_eod, flags, e->host.stream,
                              /*append_first=*/j > 0, /*count_call=*/j == 0);
       if (rc != FSKHIP_OK) { (void)hipStreamSynchronize(e->host.copy_stream); (void)hipStreamSynchronize(e->host.stream); return rc; }
@@ -292,5 +307,28 @@ int fskhip_demodulate_host(fskhip_engine *e, float *samples, size_t n, size_t pi
   for (size_t s = 0; s < S; s++)
     if (out_counts[s] > out_pitch) return fail(FSKHIP_E_OVERFLOW, "stream %zu produced %u bytes, slab holds %zu", s, out_counts[s], out_pitch);
   return FSKHIP_OK;
+}
+}  // namespace
+
+extern "C" {
+int fskhip_demodulate_device(fskhip_engine *e, float *d_samples, size_t n, size_t pitch, uint8_t *d_out, size_t out_pitch,
+                             uint32_t *d_out_counts, uint32_t *d_eod_counts, uint32_t flags, void *hip_stream) {
+  return demod_device_impl(e, d_samples, n, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, flags, hip_stream, false, true);
+}
+// Host buffers in, bytes out.  A call longer than one time slab is a two-buffer pipeline over TIME: slab j+1 crosses PCIe
+// on the copy stream while slab j is demodulated on the compute stream.  Cutting along time needs no sub-batch launches,
+// and the engine gives the same bytes for any cut (the reference is a streaming state machine, fsk.ts:190-222).  The
+// copies only overlap if `samples` is page-locked (fskhip_host_alloc, or any pinned buffer of the caller); with pageable
+// memory the runtime stages each copy itself and the pipeline degrades gracefully to what one big copy costs.
+int fskhip_demodulate_host(fskhip_engine *e, float *samples, size_t n, size_t pitch, uint8_t *out, size_t out_pitch,
+                           uint32_t *out_counts, uint32_t *eod_counts, uint32_t flags) {
+  return demod_host_impl(e, samples, FSKHIP_SAMPLES_F32, FSKHIP_LAYOUT_STREAM_MAJOR, n, pitch, out, out_pitch, out_counts, eod_counts, flags);
+}
+// ... and the same for samples in any capture format and layout (include/fskhip.h), read only
+int fskhip_demodulate_host_fmt(fskhip_engine *e, const void *samples, int format, int layout, size_t n, size_t src_pitch, uint8_t *out,
+                               size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, uint32_t flags) {
+  if (!ingest_sample_bytes(format)) return fail(FSKHIP_E_INVALID, "fskhip_demodulate_host_fmt: unknown sample format %d", format);
+  if (layout != FSKHIP_LAYOUT_STREAM_MAJOR && layout != FSKHIP_LAYOUT_SAMPLE_MAJOR) return fail(FSKHIP_E_INVALID, "fskhip_demodulate_host_fmt: unknown layout %d", layout);
+  return demod_host_impl(e, samples, format, layout, n, src_pitch, out, out_pitch, out_counts, eod_counts, flags);
 }
 }  // extern "C"

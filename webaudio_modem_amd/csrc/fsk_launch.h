@@ -98,6 +98,10 @@ hipError_t launch_snap_pack(const SnapLayout &L, const DemodState &S, uint32_t n
                             hipStream_t st);
 hipError_t launch_snap_unpack(int precision, const SnapLayout &L, const DemodState &D, uint32_t n_dst, const int64_t *d_map, uint32_t rec_first, uint32_t rec_count,
                               bool fresh_too, const NewStream &N, const void *d_in, hipStream_t st);
+// fsk_ingest.hip: capture formats (FSKHIP_SAMPLES_*) and layouts (FSKHIP_LAYOUT_*) -> float32 [stream][dst_pitch], exact.  The caller
+// has checked the arguments (fskhip_ingest_device); nothing is launched for an empty batch.  ingest_sample_bytes: 0 = unknown format.
+size_t ingest_sample_bytes(int format);
+hipError_t launch_ingest(const void *d_src, int format, int layout, uint32_t n_streams, size_t n, size_t src_pitch, float *d_dst, size_t dst_pitch, hipStream_t st);
 // fsk_processor_remap.hip: FSKProcessor state (ProcState) between processors and stream-major records (ProcImage).
 // gather: stream i of D continues stream d_map[i] of S, or starts as a created one where d_map[i] = -1.
 // unpack: the same from the slab I of an image's records; streams whose record is in another slab are left alone, new ones are

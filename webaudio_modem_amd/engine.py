@@ -169,6 +169,70 @@ def _snapshot_plan(blob, stream_map, configs, range_error=True):
     return info, m, configs
 
 
+# capture formats and layouts by name (include/fskhip.h: FSKHIP_SAMPLES_* / FSKHIP_LAYOUT_*)
+SAMPLE_FORMATS = {"f32": _lib.SAMPLES_F32, "s16": _lib.SAMPLES_S16, "mulaw": _lib.SAMPLES_MULAW, "alaw": _lib.SAMPLES_ALAW}
+SAMPLE_LAYOUTS = {"stream": _lib.LAYOUT_STREAM_MAJOR, "sample": _lib.LAYOUT_SAMPLE_MAJOR}
+_FORMAT_DTYPE = {_lib.SAMPLES_F32: np.float32, _lib.SAMPLES_S16: np.int16, _lib.SAMPLES_MULAW: np.uint8, _lib.SAMPLES_ALAW: np.uint8}
+
+
+def _format_code(fmt):
+    if isinstance(fmt, str):
+        if fmt.lower() not in SAMPLE_FORMATS:
+            raise ValueError("unknown sample format %r (one of %s)" % (fmt, ", ".join(SAMPLE_FORMATS)))
+        return SAMPLE_FORMATS[fmt.lower()]
+    return int(fmt)
+
+
+def _layout_code(layout):
+    if isinstance(layout, str):
+        if layout.lower() not in SAMPLE_LAYOUTS:
+            raise ValueError("unknown layout %r (one of %s)" % (layout, ", ".join(SAMPLE_LAYOUTS)))
+        return SAMPLE_LAYOUTS[layout.lower()]
+    return int(layout)
+
+
+def sample_args(samples, fmt=None, layout="stream"):
+    """What fskhip_demodulate_host_fmt takes for a numpy array of capture samples: (array, format, layout, streams, samples per
+    stream, pitch in elements).  fmt None: by the dtype -- float32 is "f32", int16 "s16"; uint8 needs "mulaw" or "alaw" said.
+    layout "stream": the array is [S, N]; "sample": [N, S], interleaved frames.  A view whose rows are a block of a wider array
+    (a shard of it) is taken as it is, with the wider array's pitch; anything else that is not contiguous is copied."""
+    a = np.asarray(samples)
+    if fmt is None:
+        if a.dtype == np.float32:
+            fmt = _lib.SAMPLES_F32
+        elif a.dtype == np.int16:
+            fmt = _lib.SAMPLES_S16
+        elif a.dtype == np.uint8:
+            raise ValueError("uint8 samples need fmt='mulaw' or fmt='alaw'")
+        else:
+            raise ValueError("no sample format for dtype %s: float32, int16 or uint8 (G.711)" % a.dtype)
+    code, lay = _format_code(fmt), _layout_code(layout)
+    if code not in _FORMAT_DTYPE:
+        raise ValueError("unknown sample format %r" % (fmt,))
+    if lay not in (_lib.LAYOUT_STREAM_MAJOR, _lib.LAYOUT_SAMPLE_MAJOR):
+        raise ValueError("unknown layout %r" % (layout,))
+    if a.dtype != _FORMAT_DTYPE[code]:
+        raise ValueError("format %r takes %s samples, got %s" % (fmt, np.dtype(_FORMAT_DTYPE[code]).name, a.dtype))
+    if a.ndim == 1:
+        a = a.reshape(1, -1) if lay == _lib.LAYOUT_STREAM_MAJOR else a.reshape(-1, 1)
+    if a.ndim != 2:
+        raise ValueError("samples must be a 2-D array")
+    isz = a.dtype.itemsize
+    rows, cols = a.shape
+    if not (cols <= 1 or a.strides[1] == isz) or not (rows <= 1 or (a.strides[0] % isz == 0 and a.strides[0] >= cols * isz)):
+        a = np.ascontiguousarray(a)
+    pitch = a.strides[0] // isz if rows > 1 else cols
+    S, N = (rows, cols) if lay == _lib.LAYOUT_STREAM_MAJOR else (cols, rows)
+    return a, code, lay, S, N, max(pitch, cols, 1)
+
+
+def ingest_device(d_src, fmt, layout, n_streams, n_per_stream, src_pitch, d_dst, dst_pitch, stream=None):
+    """fskhip_ingest_device: device pointers (ints); widens capture samples into float32 [n_streams][dst_pitch] on the current
+    device, asynchronously on `stream` (a hipStream_t handle or None)."""
+    _lib.check(_lib.lib().fskhip_ingest_device(d_src, _format_code(fmt), _layout_code(layout), n_streams, n_per_stream, src_pitch,
+                                               d_dst, dst_pitch, stream))
+
+
 # Called with (n_streams, precision) by every new FSKEngine; returns a dict of fskhip_set_option() names -> values to apply on
 # top of the `options` argument, or None.  The package sets nothing here and reads no environment variable; the test suite
 # (tests/conftest.py) and the measurement tools (tools/envopts.py) install a hook that maps their FSKHIP_* variables.
@@ -335,6 +399,21 @@ class FSKEngine:
             counts.ctypes.data, eod.ctypes.data, flags))
         if writeback_agc and x is not samples:
             np.copyto(samples, x.reshape(samples.shape))
+        return [out[s, :counts[s]].tobytes() for s in range(S)], eod
+
+    def demodulate_samples(self, samples, fmt=None, layout="stream", out_pitch=None):
+        """demodulate_data for capture samples as they arrive (fskhip_demodulate_host_fmt): int16 PCM, G.711 bytes (uint8 with
+        fmt="mulaw" / "alaw") or float32, [S, N] (layout="stream") or interleaved frames [N, S] (layout="sample").  The narrow
+        samples cross PCIe and are widened on the device.  Returns what demodulate_data returns."""
+        x, code, lay, S, N, pitch = sample_args(samples, fmt, layout)
+        if S != self.n_streams:
+            raise ValueError("expected %d streams, got %d" % (self.n_streams, S))
+        opitch = out_pitch or self.max_bytes(N)
+        out = np.zeros((S, opitch), dtype=np.uint8)
+        counts = np.zeros(S, dtype=np.uint32)
+        eod = np.zeros(S, dtype=np.uint32)
+        _lib.check(self._L.fskhip_demodulate_host_fmt(self._h, x.ctypes.data, code, lay, N, pitch, out.ctypes.data, opitch,
+                                                      counts.ctypes.data, eod.ctypes.data, 0))
         return [out[s, :counts[s]].tobytes() for s in range(S)], eod
 
     def demodulate_device(self, d_samples, n_per_stream, pitch, d_out, out_pitch, d_counts, d_eod=None,

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PRECISION_F32
-from .engine import FSKEngine, snapshot_concat, _snapshot_plan
+from .engine import FSKEngine, snapshot_concat, _snapshot_plan, sample_args
 from .sharding import all_shards
 
 
@@ -142,6 +142,21 @@ class FSKEngineSharded:
             eod.append(np.asarray(c, dtype=np.uint32))
         if writeback_agc and x is not samples:
             np.copyto(samples, x.reshape(np.shape(samples)))
+        return out, (np.concatenate(eod) if eod else np.zeros(0, np.uint32))
+
+    def demodulate_samples(self, samples, fmt=None, layout="stream", out_pitch=None):
+        """FSKEngine.demodulate_samples over the shards.  No host copy: a shard's streams are a row block of a stream-major
+        array, and a COLUMN block of interleaved frames -- its first column's address and the full frame pitch."""
+        x, code, lay, S, _N, _pitch = sample_args(samples, fmt, layout)
+        if S != self.n_streams:
+            raise ValueError("expected %d streams, got %d" % (self.n_streams, S))
+        sample_major = lay == _lib.LAYOUT_SAMPLE_MAJOR
+        parts = self._fan_out(lambda i, e, first, count: e.demodulate_samples(
+            x[:, first:first + count] if sample_major else x[first:first + count], fmt=code, layout=lay, out_pitch=out_pitch))
+        out, eod = [], []
+        for o, c in parts:
+            out.extend(o)
+            eod.append(np.asarray(c, dtype=np.uint32))
         return out, (np.concatenate(eod) if eod else np.zeros(0, np.uint32))
 
     def modulate_data(self, payloads):
