@@ -394,12 +394,8 @@ int fskhip_create(const fskhip_config *cfgs, uint32_t n_cfgs, uint32_t n_streams
   if (!e) return fail(FSKHIP_E_NOMEM, "out of host memory");
   e->device = device; e->precision = precision; e->n_streams = n_streams; e->cfg0 = c0;
   e->cfgs.assign(cfgs, cfgs + n_cfgs);
-  // below two waves per SIMD the one-wave-per-group kernel cannot hide its own dependency stalls; the two-wave kernel
-  // gives every group two instruction streams, as long as all its workgroups' LDS tiles fit on the CUs at once.
-  // (Round 2's choice; since round 3 the four-wave kernel takes every call it applies to.)
   if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) e->cus = 0;
   e->split_cus = e->cus > 0 ? (uint32_t)e->cus : 256u;
-  e->use_split = (n_streams + 63) / 64 < e->split_cus * 8u;  // < 2 waves per SIMD (4 SIMDs per CU)
   std::vector<double> coef;   // per-stream constants [CF_COUNT][n_streams]
   std::vector<uint64_t> inc;  // NCO increments [n_streams]
   if (const int rc = derive_params(cfgs, n_cfgs, e, coef, inc)) { delete e; return rc; }

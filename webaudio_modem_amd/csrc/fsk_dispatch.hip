@@ -1,16 +1,16 @@
-// fsk_dispatch.hip -- C ABI of libfskhip.so (include/fskhip.h): fskhip_demodulate_device / _host / _host_fmt -- which kernels a call
-// gets, their launches, the host-side bookkeeping the choice depends on, and the host forms' copy / compute pipeline.
+// fsk_dispatch.hip -- C ABI of libfskhip.so (include/fskhip.h): fskhip_demodulate_device / _host / _host_fmt -- the facts the choice
+// of a call's kernels depends on (the choice itself: fsk_plan.h), their launches, the host-side bookkeeping, and the host forms'
+// copy / compute pipeline.
 #include "fsk_engine.h"
 #include "fsk_launch.h"
 
 using namespace fsk;
 
-// everything fskhip_demodulate_device's choice of launches depends on besides its arguments
+// everything fskhip_demodulate_device's choice of launches depends on besides its arguments (bits 8 and 16: fsk_processor.hip)
 uint32_t fsk::engine_launch_key(const fskhip_engine *e) {
   return (e->ds_uniform ? 1u : 0u) | (e->ds_parity << 1) | (e->force_generic ? 4u : 0u) | (e->timing.on ? 8u : 0u) |
-         (e->use_split ? 32u : 0u) | (e->gen_odd ? 64u : 0u) | (e->P.quality ? 256u : 0u) |
-         (e->S.trace_stream != 0xFFFFFFFFu ? 16u : 0u) | (e->use_blk ? 512u : 0u) | ((uint32_t)(e->pushes & 3u) << 10) |
-         ((e->blk.medium == 3u ? e->blk.med_now : e->blk.medium != 0u) ? 4096u : 0u) | (e->six.use << 13);
+         (e->S.trace_stream != 0xFFFFFFFFu ? 16u : 0u) | (e->gen_odd ? 64u : 0u) | (e->P.quality ? 256u : 0u) | ((uint32_t)(e->pushes & 3u) << 10) |
+         ((e->blk.medium == 3u ? e->blk.med_now : e->blk.medium != 0u) ? 4096u : 0u) | ((uint32_t)e->policy << 13);
 }
 // "blk_resets" = auto: tiles, and tiles the block path with resets took or would be given, of a sample of the groups since the
 // last look (whatever the last completed copy brought; nothing new = the choice stands).  It wins from about one tile in six on.
@@ -65,81 +65,27 @@ int fsk::handoff_check(fskhip_engine *e, bool blocking) {
   return FSKHIP_OK;
 }
 
-// ---- one demodulate call: which kernels (plan_launches), then head -> whole tiles -> tail (issue_launches) ----------------
+// ---- one demodulate call: which kernels (plan_facts -> fsk_plan.h's plan_launches), then head -> whole tiles -> tail (issue_launches) ----
 namespace {
-enum TileKernel { K_GENERIC, K_SAMPLES, K_SEVEN_WAVE, K_FOUR_WAVE, K_TWO_WAVE, K_ONE_WAVE };
-struct LaunchPlan {
-  TileKernel kernel = K_GENERIC;   // K_GENERIC: all n samples on fsk_demod.hip's kernel; K_SAMPLES: all of them sample by sample (head = n)
-  size_t head = 0, n_fast = 0;     // single samples in front of the whole tiles; the whole tiles' samples (the tail is what is left)
-  uint32_t med = 0, y_slots = 0;   // four waves: "blk_resets" as this call takes it; seven waves: depth of the y ring
-  bool split2 = false;             // generic fp64 kernel on two waves per group
-};
-
-// Reads the engine and the call's arguments.  (Its one write: engine_refresh_kernel_choice, once the four-wave family is chosen.)
-LaunchPlan plan_launches(fskhip_engine *e, const float *d_samples, size_t n, size_t pitch) {
-  LaunchPlan pl;
-  // Lock-step fp32 batches with narrow integer-capacity rings never leave fsk_pipe.hip's arithmetic: a head of
-  // single samples up to an even decimator parity and a 16-byte boundary, whole 16-sample tiles, a tail of single
-  // samples -- so cutting a stream into calls of any lengths changes nothing, bit for bit.  Everything else (fp64,
-  // wide / fractional rings, streams out of lock step) is the generic kernel's.
-  if (!(n > 0 && !e->force_generic && !e->gen_odd && demod_fast_applicable(e->precision, e->ds_uniform, e->P, e->S, d_samples, pitch))) {
-    pl.split2 = e->precision == FSKHIP_PRECISION_F64 && e->ds_uniform && !e->P.wide && !e->P.frac && e->S.trace_stream == 0xFFFFFFFFu &&
-                !e->P.quality && demod_split2_lds_bytes(e->P) <= 160 * 1024 &&
-                (e->exact_split == 1u || (e->exact_split == 2u && e->cus > 0 && e->n_blocks <= 4u * (uint32_t)e->cus && n >= 64));
-    return pl;
-  }
-  const uint32_t p0 = e->ds_parity;
-  size_t head = 0, n_fast = 0;
-  bool tiles = (pitch % 4 == 0) && (uint64_t)pitch * 4u * 64u < 0x7FFFFFF0ull && (reinterpret_cast<uintptr_t>(d_samples) & 3u) == 0;
-  if (tiles) {
-    // The head: single samples (demod_tail_kernel) until the /2 decimator is at a pair boundary AND the amplitude
-    // ring's write position is a multiple of four -- what the block kernel's quad stores need (fsk_dev.h).  At most
-    // seven samples.  The tile loads that follow are 16 bytes per lane from dword-aligned addresses: a buffer that is
-    // 16-byte aligned after the head is the common case and the fastest, but nothing depends on it (VERDICT r03 #6:
-    // round 3 demanded both, so one odd-length call left an aligned device buffer on the per-sample kernel until
-    // the parity flipped back, and a call that left the ring off its quad grid kept the engine on round 2's
-    // kernels for good).
-    head = p0;                                                  // closes the open pair
-    const uint64_t at = e->pushes + ((p0 + head) >> 1);       // the ring's position after it
-    if (e->use_blk && demod_blk_applicable(e->P)) head += 2u * (size_t)((4u - (uint32_t)(at & 3u)) & 3u);
-  }
-  if (e->S.trace_stream != 0xFFFFFFFFu || e->P.quality) tiles = false;   // diagnostics (traces, quality estimates) run on the sample-granular kernel
-  if (tiles && head < n) n_fast = (n - head) & ~(size_t)15;
-  if (!n_fast) head = n;   // all of it sample by sample
-  pl.head = head; pl.n_fast = n_fast; pl.kernel = K_SAMPLES;
-  if (!n_fast) return pl;
-  const size_t blk_lds = demod_blk_lds_bytes(e->P);
-  // the block kernel stores amplitudes a quad at a time: the ring's write position at its first sample must be a
-  // multiple of four (it is unless earlier calls had odd lengths: those calls then stay with the per-sample kernels)
-  const bool quad_aligned = ((e->pushes + ((p0 + head) >> 1)) & 3u) == 0u;
-  // Batches beyond one round of resident workgroups run the block kernel persistently, in time slices; a call too
-  // short for two slices would run it in several rounds of one workgroup per group, each paying the four-wave
-  // pipeline's fill and drain, and round 2's kernels are faster there (262 144 streams x 128-sample quanta, the
-  // FSKProcessor loop: 0.195 against 0.247 ms; x 4 096 samples 384 against 370 Gsamples/s:
-  // profiles/r03_short_calls.txt)
-  const bool blk_fits = e->blk.lanes != 64u || !(e->blk.resident && e->n_blocks > e->blk.resident) ||
-                        demod_blk_slices(e->P, e->S, n_fast, e->blk.resident, e->blk.slice_tiles, nullptr) >= 2u;
-  if (e->use_blk && demod_blk_applicable(e->P) && blk_lds <= 160 * 1024 && (quad_aligned || e->split_forced) &&
-      ((blk_fits && n_fast / 16 >= e->blk.min_tiles) || e->split_forced)) {
-    engine_refresh_kernel_choice(e);
-    pl.med = e->blk.medium == 3u ? (e->blk.med_now ? 1u : 0u) : e->blk.medium;
-    // seven waves per group: every workgroup a compute unit to itself (in narrow groups -- <= 32 streams -- the stages that
-    // are not recurrences spread over the idle lanes), a uniform configuration, a call long enough to fill seven stages.
-    // Measured against the four-wave kernel: x 1.56 at 2 048 streams, x 1.48 at 4 096, x 1.42 at 8 192, x 1.13 with whole-wave
-    // groups at 16 384 (profiles/r05_lag.txt).  Idle receiver banks included: its frame wave takes own-span tiles on the
-    // block path with resets too.
-    const uint32_t six_blocks = (e->n_streams + e->blk.lanes - 1u) / e->blk.lanes;
-    const bool six = e->six.use != 0u && quad_aligned && demod_blk6_applicable(e->P) && n_fast <= demod_blk6_max_samples() &&
-                     (e->six.use == 1u || (e->cus > 0 && six_blocks <= (uint32_t)e->cus && n_fast / 16 >= e->six.min_tiles));
-    pl.kernel = six ? K_SEVEN_WAVE : K_FOUR_WAVE;
-    if (six) pl.y_slots = e->six.y_slots ? e->six.y_slots : demod_blk6_y_slots(e->P);
-    return pl;
-  }
-  const size_t wgs_per_cu = (e->n_blocks + e->split_cus - 1) / e->split_cus;
-  const size_t pipe_lds = demod_pipe_lds_bytes(e->P);
-  const bool two_wave = e->use_split && pipe_lds <= 160 * 1024 && (wgs_per_cu * pipe_lds <= 160 * 1024 || e->split_forced);
-  pl.kernel = two_wave ? K_TWO_WAVE : K_ONE_WAVE;
-  return pl;
+// What plan_launches reads, from the engine and the call's arguments: the one place that asks the kernel files what applies.
+PlanFacts plan_facts(const fskhip_engine *e, const float *d_samples, size_t n, size_t pitch) {
+  PlanFacts f{};
+  f.policy = e->policy;
+  f.f64 = e->precision == FSKHIP_PRECISION_F64; f.lock_step = e->ds_uniform;
+  f.fast = demod_fast_applicable(e->precision, e->ds_uniform, e->P, e->S, d_samples, 0);   // (the pitch's bound is the planner's)
+  f.ds_parity = e->ds_parity; f.ring_pos = (uint32_t)(e->pushes & 3u);
+  f.gen_odd = e->gen_odd; f.force_generic = e->force_generic; f.diagnostics = e->S.trace_stream != 0xFFFFFFFFu || e->P.quality;
+  f.n = n; f.pitch = pitch; f.ptr_low = (uint32_t)(reinterpret_cast<uintptr_t>(d_samples) & 3u);
+  f.n_streams = e->n_streams; f.n_blocks = e->n_blocks; f.cus = e->cus > 0 ? (uint32_t)e->cus : 0u; f.split_cus = e->split_cus;
+  f.wide_or_frac = e->P.wide || e->P.frac; f.exact_split = e->exact_split;
+  if (f.f64) f.split2_lds = f.wide_or_frac ? 0 : demod_split2_lds_bytes(e->P);
+  if (!f.fast) return f;   // (the whole-tile kernels' facts: lock-step fp32 engines only)
+  f.blk_applicable = demod_blk_applicable(e->P); f.blk_queue = e->S.blk_q != nullptr; f.blk_lds = demod_blk_lds_bytes(e->P);
+  f.blk_lanes = e->blk.lanes; f.blk_resident = e->blk.resident; f.blk_slice_tiles = e->blk.slice_tiles; f.blk_min_tiles = e->blk.min_tiles;
+  f.six_applicable = demod_blk6_applicable(e->P); f.six_max_samples = demod_blk6_max_samples(); f.six_min_tiles = e->six.min_tiles;
+  f.six_y_pinned = e->six.y_slots; f.six_y_default = f.six_applicable ? demod_blk6_y_slots(e->P) : 0u;
+  f.pipe_lds = demod_pipe_lds_bytes(e->P);
+  return f;
 }
 
 // Issues the plan's launches.  *name: what fskhip_last_kernel reports for the call -- its whole-tile kernel as the launcher named it,
@@ -193,7 +139,11 @@ int demod_device_impl(fskhip_engine *e, float *d_samples, size_t n, size_t pitch
   const bool wb = (flags & FSKHIP_DEMOD_WRITEBACK_AGC) != 0;
   if (const int rc = timing_open(e, st)) return rc;
   e->last_kernel = "";
-  const LaunchPlan pl = plan_launches(e, d_samples, n, pitch);
+  LaunchPlan pl = plan_launches(plan_facts(e, d_samples, n, pitch));
+  if (pl.kernel == K_FOUR_WAVE || pl.kernel == K_SEVEN_WAVE) {   // (only then: auto's hysteresis depends on when it is consulted)
+    engine_refresh_kernel_choice(e);
+    pl.med = e->blk.medium == 3u ? (e->blk.med_now ? 1u : 0u) : e->blk.medium;
+  }
   const char *name = "";
   if (const int rc = issue_launches(e, pl, {wb, append_first, d_samples, n, pitch, d_out, out_pitch, d_out_counts, d_eod_counts, st}, &name)) return rc;
   e->last_kernel = name;
@@ -226,13 +176,9 @@ int demod_host_impl(fskhip_engine *e, const void *samples_, int format, int layo
   if (e->host_slab != (size_t)-1) slab = e->host_slab & ~(size_t)15;   // fskhip_set_option("host_slab"): tests / measurements
   const bool piped = slab > 0 && n > slab + slab / 2;
   const size_t len0 = piped ? slab + slab / 2 : n;    // (the last slab of a pipelined call takes the remainder, < 1.5 slabs)
-  // device copies keep a row pitch that is a multiple of 4 floats so the 16-B tile loads apply.  A stream whose /2
-  // decimator is mid-pair (an earlier call had an odd length) is staged THREE floats into its row: the one sample that
-  // closes the pair then also reaches the next 16-byte boundary, and the rest of the call runs on whole tiles -- staged
-  // at the row start it would need an odd head for the parity and a multiple of four for the alignment, i.e. every
-  // later even-length call would run sample by sample (fsk_api.hip's silent performance cliff).
+  // device copies keep a row pitch that is a multiple of 4 floats, with room for host_stage_shift's three (fsk_plan.h)
   const size_t dpitch = ((len0 + 3 + 3) & ~(size_t)3) ? ((len0 + 3 + 3) & ~(size_t)3) : 4;
-  auto shift = [&]() -> size_t { return (e->precision == FSKHIP_PRECISION_F32 && e->ds_uniform && (e->ds_parity & 1u)) ? 3 : 0; };
+  auto shift = [&]() -> size_t { return host_stage_shift(e->precision == FSKHIP_PRECISION_F64, e->ds_uniform, e->ds_parity); };
   // the narrow staging slabs: rows of 16-byte-aligned pitch (stream-major), or the slab's frames as they are (sample-major)
   const size_t npitch = frames ? pitch : (len0 + 15) & ~(size_t)15;
   const size_t nbytes = (frames ? len0 * pitch : S * npitch) * esz;

@@ -8,6 +8,7 @@
 
 #include "fsk_host.h"
 #include "fsk_params.h"
+#include "fsk_plan.h"
 
 struct fskhip_engine {
   int device = 0;
@@ -40,11 +41,8 @@ struct fskhip_engine {
   uint32_t trace_cap = 0;
   // what fskhip_set_option() can change (tests and measurements; none changes a result)
   bool force_generic = false;    // "force_generic": never a whole-tile kernel
-  bool use_split = false;        // two waves per 64-stream group (demod_pipe_kernel): batches of fewer than two waves per SIMD
-  uint32_t split_cus = 256;
-  bool split_forced = false;     // "kernel" pinned one: skip the residency checks too
-  bool use_blk = true;           // four waves per group with the block-batched back wave (demod_blk_kernel, fsk_blk.hip): the default
-                                 // wherever it applies (dsSPB a multiple of 4, >= 8)
+  fsk::KernelPolicy policy = fsk::KernelPolicy::AUTO;   // "kernel": which whole-tile kernels fp32 lock-step calls may use (fsk_plan.h)
+  uint32_t split_cus = 256;      // compute units the two-wave kernel's residency rule counts with (cus, or 256 where unknown)
   // the exact path (fp64, fsk_demod.hip) on two waves per 64-stream group -- loads + AGC + pre-filter | the rest (SPLIT2): 0 never
   // (the default: measured SLOWER, 156 against 180 Gsamples/s at config #3 -- at two waves per SIMD the back wave has 256 registers and
   // spills 864 bytes per lane, where the one-wave kernel spreads into the accumulation registers), 1 wherever it applies
@@ -71,7 +69,6 @@ struct fskhip_engine {
   // seven waves per group (demod_blk6_kernel, fsk_blk6.hip): the whole-tile kernel of batches small enough to give every workgroup a
   // compute unit of its own (uniform configurations, calls of at least min_tiles tiles)
   struct Six {
-    uint32_t use = 2;            // 0 never, 1 wherever it applies ("kernel" = seven-wave), 2 auto
     uint32_t min_tiles = 8;      // shorter calls stay on the four-wave kernel (one 128-sample quantum is already 1.13 x faster on seven waves, profiles/r05_lag.txt)
     uint32_t y_slots = 0;        // 0 = as deep as the LDS allows
     uint32_t rolemap = 0;        // 0 = the default placement of the seven parts on a workgroup's waves

@@ -7,7 +7,7 @@
 // Every value is an integer of at most 16 bits times 2^-15: the float is exact, and the tests compare bit for bit.
 //
 //   stream-major   no LDS.  A row is a head of single elements up to the first 16-byte boundary of its DESTINATION (the host
-//                  path hands over rows that start three floats into an aligned one, fsk_dispatch.hip's shift()), quads of
+//                  path hands over rows that start three floats into an aligned one, host_stage_shift, fsk_plan.h), quads of
 //                  four elements -- one float4 store per quad, fed by one 16- / 8- / 4-byte load where the source lines up
 //                  with its own quad size behind that head and by four element loads where it does not --, and a tail of
 //                  single elements.  A lane issues the loads of kIngestQuads quads before it converts the first, and

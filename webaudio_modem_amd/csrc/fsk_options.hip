@@ -24,18 +24,13 @@ int fskhip_set_option(fskhip_engine *e, const char *name, const char *value) {
     return FSKHIP_OK;
   };
   uint64_t x = 0; int rc;
-  if (k == "kernel") {          // which whole-tile kernel fp32 lock-step calls use
-    const uint32_t n_blocks = e->n_blocks;
-    e->six.use = 0u;
-    if (v == "auto") { e->use_blk = true; e->split_forced = false; e->use_split = n_blocks < e->split_cus * 8u; e->six.use = 2u; }
-    else if (v == "auto-r04") { e->use_blk = true; e->split_forced = false; e->use_split = n_blocks < e->split_cus * 8u; }   // (round 4's choice: never seven waves)
-    else if (v == "auto-r02") { e->use_blk = false; e->split_forced = false; e->use_split = n_blocks < e->split_cus * 8u; }
-    else if (v == "seven-wave" || v == "six-wave") { e->use_blk = true; e->use_split = true; e->split_forced = true; e->six.use = 1u; }   // (four waves where seven do not apply; "six-wave": its first name)
-    else if (v == "four-wave") { e->use_blk = true; e->use_split = true; e->split_forced = true; }
-    else if (v == "two-wave") { e->use_blk = false; e->use_split = true; e->split_forced = true; }
-    else if (v == "one-wave") { e->use_blk = false; e->use_split = false; e->split_forced = true; }
-    else return fail(FSKHIP_E_INVALID, "fskhip_set_option(kernel): '%s' is none of auto, auto-r04, auto-r02, seven-wave, four-wave, two-wave, one-wave", value);
-    return FSKHIP_OK;
+  if (k == "kernel") {          // which whole-tile kernel fp32 lock-step calls use ("six-wave": the seven-wave kernel's first name)
+    static const struct { const char *name; KernelPolicy policy; } kPolicies[] = {
+        {"auto", KernelPolicy::AUTO},           {"auto-r04", KernelPolicy::AUTO_R04},    {"auto-r02", KernelPolicy::AUTO_R02}, {"seven-wave", KernelPolicy::SEVEN_WAVE},
+        {"six-wave", KernelPolicy::SEVEN_WAVE}, {"four-wave", KernelPolicy::FOUR_WAVE}, {"two-wave", KernelPolicy::TWO_WAVE}, {"one-wave", KernelPolicy::ONE_WAVE}};
+    for (const auto &p : kPolicies)
+      if (v == p.name) { e->policy = p.policy; return FSKHIP_OK; }
+    return fail(FSKHIP_E_INVALID, "fskhip_set_option(kernel): '%s' is none of auto, auto-r04, auto-r02, seven-wave, four-wave, two-wave, one-wave", value);
   }
   if (k == "blk_resets") {      // 1: the four-wave kernel's block path takes resets (default), 0: such blocks go sample by sample
     if (v == "auto") { e->blk.medium = 3u; return FSKHIP_OK; }
@@ -75,7 +70,7 @@ int fskhip_set_option(fskhip_engine *e, const char *name, const char *value) {
     if (!blk) return FSKHIP_OK;                       // (the four-wave kernel does not apply to this engine: nothing to tune)
     if (k == "blk_y_slots") {
       if ((rc = number(6, 28, &x)) != FSKHIP_OK) return rc;
-      if (demod_blk_lds_bytes(e->P, (uint32_t)x) > 160 * 1024)
+      if (demod_blk_lds_bytes(e->P, (uint32_t)x) > kLdsLimit)
         return fail(FSKHIP_E_INVALID, "fskhip_set_option(blk_y_slots): %s slots need %zu B of LDS (> 160 KiB) at dsSPB %u", value,
                     demod_blk_lds_bytes(e->P, (uint32_t)x), e->P.d);
       e->blk.y_slots = (uint32_t)x;
