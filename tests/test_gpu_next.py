@@ -464,3 +464,69 @@ def test_iir_batch_matches_oracle():
         o.process_buffer(x[6])
         assert np.array_equal(y2[6].view(np.uint32), o.process_buffer(x[6, :300]).view(np.uint32))     # stream 6 carried on
         f.close()
+
+
+# ---- the filters' _host calls: row pitches on both sides, growth and re-use of the staging slabs ----------------------------------
+ROWS_S, ROWS_N, ROWS_SENTINEL = 65, (5, 64, 7), -12345.0       # a second wave with one lane; not a whole vector, a growth, a shorter call
+
+
+def _rows_through_host(call, h, x, pitched):
+    """x [S, sum(ROWS_N)] through three consecutive _host calls on handle h.  pitched: the host arrays are views of wider ones
+    (in_pitch = n + 3, out_pitch = n + 1) whose other columns hold a sentinel, which must still be there afterwards."""
+    from webaudio_modem_amd import _lib
+    outs, off = [], 0
+    for n in ROWS_N:
+        ip, op = (n + 3, n + 1) if pitched else (n, n)
+        xin, out = np.full((ROWS_S, ip), ROWS_SENTINEL, x.dtype), np.full((ROWS_S, op), ROWS_SENTINEL, x.dtype)
+        xin[:, :n] = x[:, off:off + n]
+        _lib.check(call(h, xin.ctypes.data, n, ip, out.ctypes.data, op))
+        assert np.all(out[:, n:] == ROWS_SENTINEL) and np.all(xin[:, n:] == ROWS_SENTINEL), n
+        assert np.array_equal(xin[:, :n], x[:, off:off + n])
+        outs.append(out[:, :n].copy())
+        off += n
+    return np.concatenate(outs, axis=1)
+
+
+@pytest.mark.parametrize("kind", ["fir-f64", "fir-f32", "iir-float", "iir-double"])
+def test_filter_host_calls_with_pitches_and_regrowth(kind):
+    """fskhip_fir_process_host (fp64 and fp32 engines, 5 taps) and fskhip_iir_process_host / _f64_host (order 2), 65 streams,
+    calls of 5, 64 and 7 samples on one handle: host rows wider than n on both sides give, bit for bit, what contiguous arrays
+    give on a second handle (the same kernel: no tolerance), nothing outside the n columns is written, and the first run is
+    the oracle's -- bit for bit on the fp64 engines, within 1e-5 of full scale on the fp32 FIR (this module's bar)."""
+    import ctypes as C
+    import webaudio_modem_amd as wm
+    from webaudio_modem_amd import _lib
+    from oracle import pyoracle as po
+    L = _lib.lib()
+    r = _rng(0x9175)
+    dtype = np.float64 if kind == "iir-double" else np.float32
+    bits = np.uint64 if kind == "iir-double" else np.uint32
+    x = (r.random((ROWS_S, sum(ROWS_N))) * 2 - 1).astype(dtype)
+    if kind.startswith("fir"):
+        taps = list(r.random(5) - 0.5)
+        prec = wm.PRECISION_F64 if kind == "fir-f64" else wm.PRECISION_F32
+        create = lambda h: L.fskhip_fir_create(0, (C.c_double * 5)(*taps), 5, ROWS_S, prec, C.byref(h))   # noqa: E731
+        call, destroy = L.fskhip_fir_process_host, L.fskhip_fir_destroy
+        oracle = lambda s: po.FIR(taps).process_buffer(x[s])                                               # noqa: E731
+    else:
+        b, a = list(r.random(3) - 0.5), [1.25, -0.3, 0.2]
+        create = lambda h: L.fskhip_iir_create(0, (C.c_double * 3)(*b), 3, (C.c_double * 3)(*a), 3, ROWS_S, wm.PRECISION_F64, C.byref(h))   # noqa: E731
+        call, destroy = (L.fskhip_iir_process_f64_host if kind == "iir-double" else L.fskhip_iir_process_host), L.fskhip_iir_destroy
+
+        def oracle(s):
+            o = po.IIR(b, a)
+            return np.array([o.process(float(v)) for v in x[s]]) if kind == "iir-double" else o.process_buffer(x[s])
+    got = []
+    for pitched in (True, False):
+        h = C.c_void_p()
+        _lib.check(create(h))
+        try:
+            got.append(_rows_through_host(call, h, x, pitched))
+        finally:
+            destroy(h)
+    assert np.array_equal(got[0].view(bits), got[1].view(bits))
+    want = np.stack([oracle(s) for s in range(ROWS_S)])
+    if kind == "fir-f32":
+        assert np.max(np.abs(got[0] - want)) <= 1e-5 * max(1.0, float(np.max(np.abs(want))))
+    else:
+        assert np.array_equal(got[0].view(bits), want.astype(dtype).view(bits))

@@ -1,4 +1,4 @@
-// fsk_api.hip -- C ABI of libfskhip.so (include/fskhip.h): the error string, memory helpers, timing, the clock probe and the
+// fsk_api.hip -- C ABI of libfskhip.so (include/fskhip.h): the error string, device selection (fsk_host.h), memory helpers, timing, the clock probe and the
 // modulator / synthetic-signal entry points (the rest: fsk_create, fsk_options, fsk_dispatch, fsk_state).  No torch types, no CPU fallback.
 #include <cstdarg>
 
@@ -16,6 +16,14 @@ int fsk::fail(int code, const char *fmt, ...) {
   va_end(ap);
   g_err = buf;
   return code;
+}
+int fsk::select_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(FSKHIP_E_NO_DEVICE, "no HIP device available (the engine has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(FSKHIP_E_NO_DEVICE, "device %d out of range (%d devices)", device, ndev);
+  if (hipSetDevice(device) != hipSuccess) return fail(FSKHIP_E_NO_DEVICE, "hipSetDevice(%d) failed", device);
+  return FSKHIP_OK;
 }
 
 namespace {

@@ -384,11 +384,7 @@ int fskhip_create(const fskhip_config *cfgs, uint32_t n_cfgs, uint32_t n_streams
     if (!shared_fields_equal(c0, cfgs[i]))
       return fail(FSKHIP_E_UNSUPPORTED, "per-stream configs may differ only in mark/space/preFilterBandwidth (stream %u)", i);
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(FSKHIP_E_NO_DEVICE, "no HIP device available (the engine has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(FSKHIP_E_NO_DEVICE, "device %d out of range (%d devices)", device, ndev);
-  if (hipSetDevice(device) != hipSuccess) return fail(FSKHIP_E_NO_DEVICE, "hipSetDevice(%d) failed", device);
+  if (const int rc = select_device(device)) return rc;
 
   fskhip_engine *e = new (std::nothrow) fskhip_engine();
   if (!e) return fail(FSKHIP_E_NOMEM, "out of host memory");

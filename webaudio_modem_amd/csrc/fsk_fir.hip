@@ -12,7 +12,7 @@
 #include <new>
 #include <vector>
 
-#include "fsk_host.h"
+#include "fsk_filter_host.h"
 
 namespace fsk {
 namespace {
@@ -138,33 +138,31 @@ int sinc_highpass(double cutoff, double sampleRate, uint32_t n_taps, std::vector
 
 using namespace fsk;
 
-struct fskhip_fir {
-  int device = 0;
-  int precision = 0;
-  uint32_t n_taps = 0, S = 0;
+struct fskhip_fir : FilterHost {
+  uint32_t n_taps = 0;
   double *d_taps = nullptr;   // coefficients as given (fp64 path)
   float *d_taps32 = nullptr;  // rounded once on the host (fp32 path)
   float *hist[2] = {nullptr, nullptr};  // ping-pong: [cur] is read by the next call
   int cur = 0;
-  hipStream_t stream = nullptr;
-  float *d_in = nullptr, *d_out = nullptr; size_t d_in_cap = 0, d_out_cap = 0;
 };
+
+// fskhip_sinc_lowpass / _highpass: the checks and the copy out around one of the two designs
+static int sinc_taps(int (*design)(double, double, uint32_t, std::vector<double> &), const char *who, double cutoff, double sampleRate,
+                     uint32_t n_taps, double *taps) {
+  if (!taps || n_taps == 0) return fail(FSKHIP_E_INVALID, "%s: bad argument", who);
+  std::vector<double> c;
+  const int n = design(cutoff, sampleRate, n_taps, c);
+  for (int i = 0; i < n; i++) taps[i] = c[i];
+  return n;
+}
 
 extern "C" {
 
 int fskhip_sinc_lowpass(double cutoff, double sampleRate, uint32_t n_taps, double *taps) {
-  if (!taps || n_taps == 0) return fail(FSKHIP_E_INVALID, "fskhip_sinc_lowpass: bad argument");
-  std::vector<double> c;
-  const int n = sinc_lowpass(cutoff, sampleRate, n_taps, c);
-  for (int i = 0; i < n; i++) taps[i] = c[i];
-  return n;
+  return sinc_taps(sinc_lowpass, "fskhip_sinc_lowpass", cutoff, sampleRate, n_taps, taps);
 }
 int fskhip_sinc_highpass(double cutoff, double sampleRate, uint32_t n_taps, double *taps) {
-  if (!taps || n_taps == 0) return fail(FSKHIP_E_INVALID, "fskhip_sinc_highpass: bad argument");
-  std::vector<double> c;
-  const int n = sinc_highpass(cutoff, sampleRate, n_taps, c);
-  for (int i = 0; i < n; i++) taps[i] = c[i];
-  return n;
+  return sinc_taps(sinc_highpass, "fskhip_sinc_highpass", cutoff, sampleRate, n_taps, taps);
 }
 int fskhip_sinc_bandpass(double center, double bandwidth, double sampleRate, uint32_t n_taps, double *taps) {  // filters.ts:296-314
   if (!taps || n_taps == 0) return fail(FSKHIP_E_INVALID, "fskhip_sinc_bandpass: bad argument");
@@ -184,12 +182,7 @@ uint32_t fskhip_fir_streams(const fskhip_fir *f) { return f ? f->S : 0u; }
 
 int fskhip_fir_destroy(fskhip_fir *f) {
   if (!f) return FSKHIP_OK;
-  (void)hipSetDevice(f->device);
-  (void)hipDeviceSynchronize();
-  void *bufs[] = {f->d_taps, f->d_taps32, f->hist[0], f->hist[1], f->d_in, f->d_out};
-  for (void *b : bufs)
-    if (b) (void)hipFree(b);
-  if (f->stream) (void)hipStreamDestroy(f->stream);
+  filter_close(*f, {f->d_taps, f->d_taps32, f->hist[0], f->hist[1]});
   delete f;
   return FSKHIP_OK;
 }
@@ -198,11 +191,7 @@ int fskhip_fir_create(int device, const double *taps, uint32_t n_taps, uint32_t 
   if (!taps || !out || n_taps == 0 || n_streams == 0) return fail(FSKHIP_E_INVALID, "fskhip_fir_create: null/zero argument");
   if (precision != FSKHIP_PRECISION_F32 && precision != FSKHIP_PRECISION_F64) return fail(FSKHIP_E_INVALID, "unknown precision %d", precision);
   if (n_taps > 4096) return fail(FSKHIP_E_UNSUPPORTED, "%u taps do not fit the LDS tile (max 4096)", n_taps);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(FSKHIP_E_NO_DEVICE, "no HIP device available (the engine has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(FSKHIP_E_NO_DEVICE, "device %d out of range (%d devices)", device, ndev);
-  if (hipSetDevice(device) != hipSuccess) return fail(FSKHIP_E_NO_DEVICE, "hipSetDevice(%d) failed", device);
+  if (const int rc = select_device(device)) return rc;
   fskhip_fir *f = new (std::nothrow) fskhip_fir();
   if (!f) return fail(FSKHIP_E_NOMEM, "out of host memory");
   f->device = device; f->precision = precision; f->n_taps = n_taps; f->S = n_streams;
@@ -219,14 +208,7 @@ int fskhip_fir_create(int device, const double *taps, uint32_t n_taps, uint32_t 
   }
   if (err == hipSuccess) err = hipMemset(f->hist[0], 0, hsz);
   if (err == hipSuccess) err = hipMemset(f->hist[1], 0, hsz);
-  if (err == hipSuccess) err = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking);
-  if (err == hipSuccess) err = hipDeviceSynchronize();
-  if (err != hipSuccess) {
-    fskhip_fir_destroy(f);
-    return fail(err == hipErrorOutOfMemory ? FSKHIP_E_NOMEM : FSKHIP_E_HIP, "fskhip_fir_create: %s", hipGetErrorString(err));
-  }
-  *out = f;
-  return FSKHIP_OK;
+  return filter_open(f, err, "fskhip_fir_create", fskhip_fir_destroy, out);
 }
 
 int fskhip_fir_process_device(fskhip_fir *f, const float *d_in, size_t n, size_t in_pitch, float *d_out, size_t out_pitch,
@@ -261,38 +243,12 @@ int fskhip_fir_process_device(fskhip_fir *f, const float *d_in, size_t n, size_t
 }
 
 int fskhip_fir_process_host(fskhip_fir *f, const float *in, size_t n, size_t in_pitch, float *out, size_t out_pitch) {
-  if (!f) return fail(FSKHIP_E_INVALID, "null filter");
-  if (n == 0) return FSKHIP_OK;
-  if (!in || !out) return fail(FSKHIP_E_INVALID, "fskhip_fir_process_host: null buffer");
-  if (in_pitch < n || out_pitch < n) return fail(FSKHIP_E_INVALID, "pitch < n_per_stream");
-  HIP_TRY(hipSetDevice(f->device));
-  const size_t dp = (n + 3) & ~(size_t)3, S = f->S;
-  auto ensure = [&](float *&p, size_t &cap, size_t need) -> int {
-    if (need <= cap) return FSKHIP_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    hipError_t err = hipMalloc((void **)&p, need * sizeof(float));
-    if (err != hipSuccess) return fail(FSKHIP_E_NOMEM, "hipMalloc(%zu): %s", need * sizeof(float), hipGetErrorString(err));
-    cap = need;
-    return FSKHIP_OK;
-  };
-  int rc;
-  if ((rc = ensure(f->d_in, f->d_in_cap, dp * S)) != FSKHIP_OK) return rc;
-  if ((rc = ensure(f->d_out, f->d_out_cap, dp * S)) != FSKHIP_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(f->d_in, dp * sizeof(float), in, in_pitch * sizeof(float), n * sizeof(float), S,
-                           hipMemcpyHostToDevice, f->stream));
-  if ((rc = fskhip_fir_process_device(f, f->d_in, n, dp, f->d_out, dp, f->stream)) != FSKHIP_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(out, out_pitch * sizeof(float), f->d_out, dp * sizeof(float), n * sizeof(float), S,
-                           hipMemcpyDeviceToHost, f->stream));
-  HIP_TRY(hipStreamSynchronize(f->stream));
-  return FSKHIP_OK;
+  return filter_rows_host(f, "fskhip_fir_process_host: null buffer", "pitch < n_per_stream", in, n, in_pitch, out, out_pitch,
+                          [=](const float *d_in, float *d_out, size_t dp, hipStream_t st) { return fskhip_fir_process_device(f, d_in, n, dp, d_out, dp, st); });
 }
 
 int fskhip_fir_reset(fskhip_fir *f, int64_t stream) {
-  if (!f) return fail(FSKHIP_E_INVALID, "null filter");
-  if (stream >= (int64_t)f->S) return fail(FSKHIP_E_INVALID, "stream out of range");
-  HIP_TRY(hipSetDevice(f->device));
-  HIP_TRY(hipDeviceSynchronize());
+  if (const int rc = filter_reset_begin(f, stream)) return rc;
   if (f->n_taps > 1) {
     const size_t total = (size_t)f->S * (f->n_taps - 1);
     hipLaunchKernelGGL(fir_reset_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, f->hist[f->cur],

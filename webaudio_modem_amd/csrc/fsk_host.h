@@ -1,4 +1,7 @@
-// fsk_host.h -- host-side helpers shared by the C-ABI translation units of libfskhip.so (not part of the ABI).
+// fsk_host.h -- host-side helpers shared by the C-ABI translation units of libfskhip.so (not part of the ABI): the error
+// string, device selection, device allocation (dev_alloc, and ensure for scratch that grows) and the HIP_TRY macros.  What only
+// some units share lives beside them: fsk_filter_host.h (the two filters' handles and _host calls), fsk_stage.h (image frames
+// and the slab pipelines of the snapshot units), fsk_proc.h (struct fskhip_processor).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +11,16 @@
 namespace fsk {
 // records the thread-local message fskhip_last_error() returns and hands `code` back
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+// makes `device` current for a create call or a handle-less _host call: FSKHIP_E_NO_DEVICE where there is no device, the index
+// is out of range or hipSetDevice refuses it (fsk_api.hip)
+int select_device(int device);
+// a device buffer of n elements (of one where n is 0)
+template <typename T>
+int dev_alloc(T *&p, size_t n) {
+  hipError_t err = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
+  if (err != hipSuccess) return fail(FSKHIP_E_NOMEM, "hipMalloc(%zu): %s", n * sizeof(T), hipGetErrorString(err));
+  return FSKHIP_OK;
+}
 // a device scratch buffer that only grows: at least `need` elements (its old contents are not kept)
 template <typename T>
 int ensure(T *&p, size_t &cap, size_t need) {

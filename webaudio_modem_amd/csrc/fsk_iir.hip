@@ -17,7 +17,7 @@
 #include <new>
 #include <vector>
 
-#include "fsk_host.h"
+#include "fsk_filter_host.h"
 
 namespace fsk {
 namespace {
@@ -186,14 +186,9 @@ __global__ void iir_reset_kernel(Real *hx, Real *hy, uint32_t n_streams, int64_t
 
 using namespace fsk;
 
-struct fskhip_iir {
-  int device = 0;
-  int precision = 0;
-  uint32_t S = 0;
+struct fskhip_iir : FilterHost {
   IirCoef C{};
   void *hx = nullptr, *hy = nullptr;   // [kIirMax][S] Real: x[n-1-i], y[n-1-i]
-  hipStream_t stream = nullptr;
-  void *d_in = nullptr, *d_out = nullptr; size_t d_in_cap = 0, d_out_cap = 0;   // staging of the _host entry points (bytes)
 };
 
 template <typename IO>
@@ -235,44 +230,16 @@ static int iir_process_device(fskhip_iir *f, const IO *d_in, size_t n, size_t in
   return FSKHIP_OK;
 }
 
-template <typename IO>
-static int iir_process_host(fskhip_iir *f, const IO *in, size_t n, size_t in_pitch, IO *out, size_t out_pitch, const char *who) {
-  if (!f) return fail(FSKHIP_E_INVALID, "null filter");
-  if (n == 0) return FSKHIP_OK;
-  if (!in || !out) return fail(FSKHIP_E_INVALID, "%s: null buffer", who);
-  if (in_pitch < n || out_pitch < n) return fail(FSKHIP_E_INVALID, "%s: pitch < n_per_stream", who);
-  HIP_TRY(hipSetDevice(f->device));
-  constexpr size_t VN = 16 / sizeof(IO);
-  const size_t dp = (n + VN - 1) / VN * VN, S = f->S;
-  auto ensure = [&](void *&p, size_t &cap, size_t need) -> int {
-    if (need <= cap) return FSKHIP_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    hipError_t err = hipMalloc(&p, need);
-    if (err != hipSuccess) return fail(FSKHIP_E_NOMEM, "hipMalloc(%zu): %s", need, hipGetErrorString(err));
-    cap = need;
-    return FSKHIP_OK;
-  };
-  int rc;
-  if ((rc = ensure(f->d_in, f->d_in_cap, dp * S * sizeof(IO))) != FSKHIP_OK) return rc;
-  if ((rc = ensure(f->d_out, f->d_out_cap, dp * S * sizeof(IO))) != FSKHIP_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(f->d_in, dp * sizeof(IO), in, in_pitch * sizeof(IO), n * sizeof(IO), S, hipMemcpyHostToDevice, f->stream));
-  if ((rc = iir_process_device<IO>(f, (const IO *)f->d_in, n, dp, (IO *)f->d_out, dp, f->stream, who)) != FSKHIP_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(out, out_pitch * sizeof(IO), f->d_out, dp * sizeof(IO), n * sizeof(IO), S, hipMemcpyDeviceToHost, f->stream));
-  HIP_TRY(hipStreamSynchronize(f->stream));
-  return FSKHIP_OK;
-}
+// the two _host entry points: `who`, and its two refusals spelled out
+#define FSK_IIR_HOST(IO, who)                                                                                              \
+  filter_rows_host(f, who ": null buffer", who ": pitch < n_per_stream", in, n, in_pitch, out, out_pitch,                    \
+                   [=](const IO *d_in, IO *d_out, size_t dp, hipStream_t st) { return iir_process_device<IO>(f, d_in, n, dp, d_out, dp, st, who); })
 
 extern "C" {
 
 int fskhip_iir_destroy(fskhip_iir *f) {
   if (!f) return FSKHIP_OK;
-  (void)hipSetDevice(f->device);
-  (void)hipDeviceSynchronize();
-  void *bufs[] = {f->hx, f->hy, f->d_in, f->d_out};
-  for (void *b : bufs)
-    if (b) (void)hipFree(b);
-  if (f->stream) (void)hipStreamDestroy(f->stream);
+  filter_close(*f, {f->hx, f->hy});
   delete f;
   return FSKHIP_OK;
 }
@@ -287,11 +254,7 @@ int fskhip_iir_create(int device, const double *b, uint32_t nb, const double *a,
   if (precision != FSKHIP_PRECISION_F32 && precision != FSKHIP_PRECISION_F64) return fail(FSKHIP_E_INVALID, "unknown precision %d", precision);
   if (nb > (uint32_t)kIirMax + 1u || na > (uint32_t)kIirMax + 1u)
     return fail(FSKHIP_E_UNSUPPORTED, "IIR order %u: the batched kernel keeps up to %d past inputs and outputs in registers", (nb > na ? nb : na) - 1u, kIirMax);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(FSKHIP_E_NO_DEVICE, "no HIP device available (the engine has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(FSKHIP_E_NO_DEVICE, "device %d out of range (%d devices)", device, ndev);
-  if (hipSetDevice(device) != hipSuccess) return fail(FSKHIP_E_NO_DEVICE, "hipSetDevice(%d) failed", device);
+  if (const int rc = select_device(device)) return rc;
   fskhip_iir *f = new (std::nothrow) fskhip_iir();
   if (!f) return fail(FSKHIP_E_NOMEM, "out of host memory");
   f->device = device; f->precision = precision; f->S = n_streams;
@@ -310,14 +273,7 @@ int fskhip_iir_create(int device, const double *b, uint32_t nb, const double *a,
   if (err == hipSuccess) err = hipMalloc(&f->hy, hsz);
   if (err == hipSuccess) err = hipMemset(f->hx, 0, hsz);
   if (err == hipSuccess) err = hipMemset(f->hy, 0, hsz);
-  if (err == hipSuccess) err = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking);
-  if (err == hipSuccess) err = hipDeviceSynchronize();
-  if (err != hipSuccess) {
-    fskhip_iir_destroy(f);
-    return fail(err == hipErrorOutOfMemory ? FSKHIP_E_NOMEM : FSKHIP_E_HIP, "fskhip_iir_create: %s", hipGetErrorString(err));
-  }
-  *out = f;
-  return FSKHIP_OK;
+  return filter_open(f, err, "fskhip_iir_create", fskhip_iir_destroy, out);
 }
 
 uint32_t fskhip_iir_streams(const fskhip_iir *f) { return f ? f->S : 0u; }
@@ -334,20 +290,18 @@ int fskhip_iir_process_device(fskhip_iir *f, const float *d_in, size_t n, size_t
   return iir_process_device<float>(f, d_in, n, in_pitch, d_out, out_pitch, hip_stream, "fskhip_iir_process_device");
 }
 int fskhip_iir_process_host(fskhip_iir *f, const float *in, size_t n, size_t in_pitch, float *out, size_t out_pitch) {
-  return iir_process_host<float>(f, in, n, in_pitch, out, out_pitch, "fskhip_iir_process_host");
+  return FSK_IIR_HOST(float, "fskhip_iir_process_host");
 }
 int fskhip_iir_process_f64_device(fskhip_iir *f, const double *d_in, size_t n, size_t in_pitch, double *d_out, size_t out_pitch, void *hip_stream) {
   return iir_process_device<double>(f, d_in, n, in_pitch, d_out, out_pitch, hip_stream, "fskhip_iir_process_f64_device");
 }
 int fskhip_iir_process_f64_host(fskhip_iir *f, const double *in, size_t n, size_t in_pitch, double *out, size_t out_pitch) {
-  return iir_process_host<double>(f, in, n, in_pitch, out, out_pitch, "fskhip_iir_process_f64_host");
+  return FSK_IIR_HOST(double, "fskhip_iir_process_f64_host");
 }
+#undef FSK_IIR_HOST
 
 int fskhip_iir_reset(fskhip_iir *f, int64_t stream) {
-  if (!f) return fail(FSKHIP_E_INVALID, "null filter");
-  if (stream >= (int64_t)f->S) return fail(FSKHIP_E_INVALID, "stream out of range");
-  HIP_TRY(hipSetDevice(f->device));
-  HIP_TRY(hipDeviceSynchronize());
+  if (const int rc = filter_reset_begin(f, stream)) return rc;
   const size_t total = (size_t)f->S * kIirMax;
   if (f->precision == FSKHIP_PRECISION_F64)
     hipLaunchKernelGGL(iir_reset_kernel<double>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, (double *)f->hx, (double *)f->hy, f->S, stream);

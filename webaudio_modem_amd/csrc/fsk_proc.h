@@ -1,5 +1,5 @@
 // fsk_proc.h -- struct fskhip_processor and what the two C-ABI units over it share (fsk_processor.hip: the streaming contract;
-// fsk_processor_remap_api.hip: remap, snapshot, restore).  Not part of the ABI.
+// fsk_processor_remap_api.hip: remap, snapshot, restore); its buffers come from fsk_host.h's dev_alloc.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,13 +33,6 @@ struct fskhip_processor {
 };
 
 namespace fsk {
-
-template <typename T>
-int dev_alloc(T *&p, size_t n) {
-  hipError_t err = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
-  if (err != hipSuccess) return fail(FSKHIP_E_NOMEM, "hipMalloc(%zu): %s", n * sizeof(T), hipGetErrorString(err));
-  return FSKHIP_OK;
-}
 
 inline void drop_graph(fskhip_processor *p) {
   if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);

@@ -322,23 +322,11 @@ struct DevBufs {
   }
   template <typename T>
   int alloc(T *&p, size_t n) {
-    void *q = nullptr;
-    hipError_t err = hipMalloc(&q, (n ? n : 1) * sizeof(T));
-    if (err != hipSuccess) return fail(FSKHIP_E_NOMEM, "hipMalloc(%zu): %s", n * sizeof(T), hipGetErrorString(err));
-    ptrs.push_back(q);
-    p = (T *)q;
-    return FSKHIP_OK;
+    const int rc = dev_alloc(p, n);
+    if (rc == FSKHIP_OK) ptrs.push_back(p);
+    return rc;
   }
 };
-
-int select_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(FSKHIP_E_NO_DEVICE, "no HIP device available (the engine has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(FSKHIP_E_NO_DEVICE, "device %d out of range (%d devices)", device, ndev);
-  if (hipSetDevice(device) != hipSuccess) return fail(FSKHIP_E_NO_DEVICE, "hipSetDevice(%d) failed", device);
-  return FSKHIP_OK;
-}
 
 }  // namespace
 }  // namespace fsk
