@@ -30,7 +30,8 @@ extern "C" {
  * addition, same version); stream snapshots -- fskhip_snapshot_bytes / _streams / _info_get / _stream_config / _concat,
  * fskhip_restore_streams (additions, same version); fskhip_processor_remap / _snapshot_bytes / _snapshot / _snapshot_info_get /
  * _restore in fskhip_next.h (additions, same version); capture formats -- FSKHIP_SAMPLES_* / FSKHIP_LAYOUT_*, fskhip_sample_bytes,
- * fskhip_ingest_device, fskhip_demodulate_host_fmt (additions, same version). */
+ * fskhip_ingest_device, fskhip_demodulate_host_fmt (additions, same version); the same formats out -- fskhip_egress_device,
+ * fskhip_modulate_host_fmt (additions, same version). */
 #define FSKHIP_ABI_VERSION 8
 #define FSKHIP_MAX_PATTERN_BYTES 16
 
@@ -304,6 +305,46 @@ int fskhip_ingest_device(const void *d_src, int format, int layout, uint32_t n_s
 int fskhip_demodulate_host_fmt(fskhip_engine *e, const void *samples, int format, int layout, size_t n_per_stream,
                                size_t src_pitch, uint8_t *out, size_t out_pitch, uint32_t *out_counts,
                                uint32_t *eod_counts, uint32_t flags);
+
+/*
+ * The same formats OUT (ABI 8, additions): the modulator's float32 [stream][sample] rows narrowed ON THE DEVICE into what a trunk, an
+ * RTP gateway or an interleaved playback buffer takes, so that 2 or 1 bytes per sample cross PCIe instead of 4.  The enums above
+ * stay as they are; a float x becomes
+ *   FSKHIP_SAMPLES_S16    v = clamp(rne(x * 32768.0f), -32768, 32767): rne = round to nearest, ties to even (rintf in the default
+ *                         rounding mode); NaN gives 0, +-Inf and everything out of range saturate.  x * 32768 is exact in float32
+ *                         for every normal x, so v is defined bit for bit.
+ *   FSKHIP_SAMPLES_MULAW  the G.711 encoder on that v: m = v >> 2 (arithmetic); neg = m < 0; m = min(|m|, 8158) + 33;
+ *                         seg = floor(log2 m) - 5; code = ((seg << 4) | ((m >> (seg + 1)) & 15)) ^ (neg ? 0x7F : 0xFF)
+ *   FSKHIP_SAMPLES_ALAW   the G.711 encoder on that v: m = v >> 3 (arithmetic); neg = m < 0; m = neg ? -m - 1 : m;
+ *                         seg = max(floor(log2 max(m, 1)) - 4, 0); code = ((seg << 4) | ((m >> (seg < 2 ? 1 : seg)) & 15)) ^ (neg ? 0x55 : 0xD5)
+ *   FSKHIP_SAMPLES_F32    the float itself, bit for bit (a copy, or a transpose only)
+ * These are the standard encoders (Python's audioop.lin2ulaw / lin2alaw on all 65 536 values of v), not "the nearest entry of the
+ * decode table", from which they differ on about a thousand values of v each.  With the decoders above, decode(encode(decode(b)))
+ * == decode(b) for all 256 codes of both laws; only mu-law code 127 (negative zero) re-encodes to another code, 0xFF.
+ * Silence -- what x = 0 gives -- is s16 0, mu-law 0xFF, A-law 0xD5, f32 0.0f.
+ * fskhip_egress_device        element (s, t) of d_dst (FSKHIP_LAYOUT_STREAM_MAJOR: at s * dst_pitch + t, dst_pitch >= n_per_stream;
+ *                             FSKHIP_LAYOUT_SAMPLE_MAJOR: at t * dst_pitch + s, dst_pitch >= n_streams; pitches in elements) = the
+ *                             encoding of d_src[s * src_pitch + t] (float32, src_pitch >= n_per_stream) for s < n_streams,
+ *                             t < n_per_stream; nothing else is written.  d_lens (device, n_streams words, may be NULL): where
+ *                             given, elements with t >= d_lens[s] are written as the format's silence instead of a conversion of
+ *                             whatever the source row holds there -- ragged signal lengths (fskhip_modulate_device's d_out_lens)
+ *                             thus make whole interleaved frames.  On the current device, asynchronous on `hip_stream`, like
+ *                             fskhip_ingest_device.  d_dst needs the alignment of its element only, d_src and d_lens that of their
+ *                             4-byte words; any pitches.  n_streams == 0 or n_per_stream == 0: FSKHIP_OK, nothing launched.
+ *                             FSKHIP_E_INVALID (before any device call): unknown format or layout, a null or misaligned pointer
+ *                             with work to do, a pitch that is too small.
+ * fskhip_modulate_host_fmt    fskhip_modulate_host's contract with `out` (host memory) in `format` / `layout`: n_per_stream samples
+ *                             of every stream, stream s silent from out_lens[s] on.  Stream-major: rows of n_per_stream elements
+ *                             at dst_pitch >= n_per_stream; sample-major: n_per_stream frames of n_streams elements at dst_pitch
+ *                             >= n_streams, columns beyond n_streams of a wider frame untouched (a shard of a wider playback buffer
+ *                             passes its first column and the full frame pitch).  The floats are those fskhip_modulate_host
+ *                             returns: FSKHIP_SAMPLES_F32 stream-major is byte for byte its output for t < out_lens[s].
+ *                             out_lens[s] > n_per_stream: FSKHIP_E_OVERFLOW, as there.
+ */
+int fskhip_egress_device(const float *d_src, size_t src_pitch, const uint32_t *d_lens, uint32_t n_streams, size_t n_per_stream,
+                         int format, int layout, void *d_dst, size_t dst_pitch, void *hip_stream);
+int fskhip_modulate_host_fmt(fskhip_engine *e, const uint8_t *payloads, const uint32_t *lens, size_t payload_pitch, int format,
+                             int layout, void *out, size_t n_per_stream, size_t dst_pitch, uint32_t *out_lens);
 
 /*
  * modulateData(bytes) (fsk.ts:377-424) for every stream.  Stream s modulates

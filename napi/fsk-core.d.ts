@@ -55,6 +55,8 @@ export class FSKBatch {
   demodulateSamples(samples: SampleArray, format: SampleFormat, layout: SampleLayout | undefined, nPerStream: number, pitch?: number): { bytes: Uint8Array[]; eod: Uint32Array };
   demodulateSamplesAsync(samples: SampleArray, format: SampleFormat, layout: SampleLayout | undefined, nPerStream: number, pitch?: number): Promise<{ bytes: Uint8Array[]; eod: Uint32Array }>;
   modulateData(payloads: Uint8Array[]): Float32Array[];
+  /** modulateData into playback samples, quantised on the device: 's16' Int16Array, 'mulaw' | 'alaw' Uint8Array, 'f32' Float32Array; layout 'stream' = [S][pitch], 'sample' = interleaved frames [nPerStream][pitch >= S]; nPerStream undefined: the longest signal; stream s is the format's silence from lens[s] on */
+  modulateSamples(payloads: Uint8Array[], format: SampleFormat, layout?: SampleLayout, nPerStream?: number, pitch?: number, out?: SampleArray): { samples: SampleArray; lens: Uint32Array; nPerStream: number; pitch: number };
   reset(stream?: number): void;
   getStatus(stream?: number): FSKStatus;
   /** 1 = the stream absorbed a NaN / Inf sample (dead from there on, like the reference's instance) or, fp32 engines, a sample beyond their range */
@@ -84,6 +86,8 @@ export class FSKBatchSharded {
   /** FSKBatch.demodulateSamples over the shards, no host copy: a shard takes a row block ('stream') or a column block with the full frame pitch ('sample') */
   demodulateSamples(samples: SampleArray, format: SampleFormat, layout: SampleLayout | undefined, nPerStream: number, pitch?: number): Promise<{ bytes: Uint8Array[]; eod: Uint32Array }>;
   modulateData(payloads: Uint8Array[]): Float32Array[];
+  /** FSKBatch.modulateSamples over the shards into ONE array, no host copy: a shard writes a row block ('stream') or a column block at the full frame pitch ('sample') */
+  modulateSamples(payloads: Uint8Array[], format: SampleFormat, layout?: SampleLayout, nPerStream?: number, pitch?: number, out?: SampleArray): { samples: SampleArray; lens: Uint32Array; nPerStream: number; pitch: number };
   reset(stream?: number): void;
   getStatus(stream?: number): FSKStatus;
   /** one snapshot of the whole batch, records in global stream order */

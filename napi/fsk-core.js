@@ -194,6 +194,24 @@ class FSKBatch {
     for (let s = 0; s < this.nStreams; s++) out.push(r.out.slice(s * r.outPitch, s * r.outPitch + r.lens[s]));
     return out;
   }
+  // modulateData into playback samples as a trunk or a sound card takes them (include/fskhip.h, fskhip_modulate_host_fmt): an
+  // Int16Array ('s16'), a Uint8Array of G.711 codes ('mulaw' / 'alaw') or a Float32Array ('f32'); layout 'stream' = [S][pitch],
+  // 'sample' = interleaved frames [nPerStream][pitch >= S].  Quantised on the device: the narrow samples are what crosses PCIe.
+  // nPerStream undefined: the longest signal's length.  `out`: the typed array to write into (a new one otherwise).  Returns
+  // {samples, lens, nPerStream, pitch}: stream s is the format's silence from lens[s] on.
+  modulateSamples(payloads, format, layout, nPerStream, pitch, out) {
+    if (payloads.length !== this.nStreams) throw new Error('need one payload per stream');
+    const lay = sampleLayout(layout), fmt = sampleFormat(format);
+    let ppitch = 1;
+    payloads.forEach((p) => { ppitch = Math.max(ppitch, p.length); });
+    const flat = new Uint8Array(ppitch * this.nStreams);
+    const lens = new Uint32Array(this.nStreams);
+    payloads.forEach((p, s) => { flat.set(p, s * ppitch); lens[s] = p.length; });
+    const n = nPerStream === undefined || nPerStream === null ? addon.modulatedLength(this.handle, Math.max(0, ...lens)) : nPerStream;
+    const p = pitch || (lay ? this.nStreams : n);
+    const r = addon.modulateSamples(this.handle, flat, lens, ppitch, fmt, lay, n, p, out === undefined ? null : out);
+    return { samples: r.out, lens: r.lens, nPerStream: n, pitch: p };
+  }
   reset(stream) { addon.reset(this.handle, stream === undefined ? -1 : stream); }
   getStatus(stream) { return addon.getStatus(this.handle, stream || 0); }
   // Uint8Array[nStreams]: 1 = the stream absorbed a NaN / Inf sample (the reference's instance is dead from there on too, and the engine
@@ -316,6 +334,31 @@ class FSKBatchSharded {
     let out = [];
     for (const sh of this.shards) out = out.concat(sh.batch.modulateData(payloads.slice(sh.first, sh.first + sh.count)));
     return out;
+  }
+  // FSKBatch.modulateSamples over the shards: ONE typed array for the whole batch and no host copy -- a shard writes its row block of
+  // a stream-major array, or its COLUMN block of the interleaved frames: the array from its first column on, at the full frame pitch
+  modulateSamples(payloads, format, layout, nPerStream, pitch, out) {
+    if (payloads.length !== this.nStreams) throw new Error('need one payload per stream');
+    const lay = sampleLayout(layout), fmt = sampleFormat(format);
+    let longest = 0;
+    payloads.forEach((p) => { longest = Math.max(longest, p.length); });
+    const n = nPerStream === undefined || nPerStream === null ? addon.modulatedLength(this.shards[0].batch.handle, longest) : nPerStream;
+    const p = pitch || (lay ? this.nStreams : n);
+    const rows = lay ? n : this.nStreams, cols = lay ? this.nStreams : n;
+    if (p < cols) throw new RangeError('samples too short');
+    const need = rows ? p * (rows - 1) + cols : 0;
+    let samples = out;
+    if (samples === undefined || samples === null) {
+      samples = new [Float32Array, Int16Array, Uint8Array, Uint8Array][fmt](need);
+      if (fmt >= 2) samples.fill(fmt === 2 ? 0xff : 0xd5);   // (the pitch's padding: silence, like the rest)
+    }
+    if (samples.length < need) throw new RangeError('samples too short');
+    const lens = new Uint32Array(this.nStreams);
+    for (const sh of this.shards) {
+      const view = lay ? samples.subarray(sh.first) : samples.subarray(sh.first * p, (sh.first + sh.count - 1) * p + n);
+      lens.set(sh.batch.modulateSamples(payloads.slice(sh.first, sh.first + sh.count), fmt, lay, n, p, view).lens, sh.first);
+    }
+    return { samples, lens, nPerStream: n, pitch: p };
   }
   reset(stream) {
     if (stream === undefined || stream < 0) this.shards.forEach((sh) => sh.batch.reset());

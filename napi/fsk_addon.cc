@@ -13,6 +13,8 @@
 //   demodulateAsync(... same ...) -> Promise of the same object; runs on a libuv worker thread
 //   demodulateSamples(handle, samples: Int16Array | Uint8Array | Float32Array, format, layout, nPerStream, pitch) -> the same object:
 //     capture samples as they arrive (FSKHIP_SAMPLES_* / FSKHIP_LAYOUT_*, fskhip_demodulate_host_fmt); demodulateSamplesAsync likewise
+//   modulateSamples(handle, payloads, lens, payloadPitch, format, layout, nPerStream, pitch, out | null) -> {out, lens}: the same formats
+//     out (fskhip_modulate_host_fmt)
 //   modulate(handle, payloads: Uint8Array, lens: Uint32Array, payloadPitch) -> {out: Float32Array, outPitch, lens: Uint32Array}
 //   modulatedLength(handle, nBytes) -> number
 //   reset(handle, stream)            stream < 0: all
@@ -327,6 +329,59 @@ static napi_value Modulate(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// modulateSamples(handle, payloads: Uint8Array, lens: Uint32Array, payloadPitch, format, layout, nPerStream, pitch, out | null) ->
+// {out, lens}: modulateData into playback samples (fskhip_modulate_host_fmt) -- an Int16Array, a G.711 Uint8Array or a Float32Array,
+// stream-major [S][pitch] or interleaved frames [nPerStream][pitch >= S].  `out`: the caller's array of that type (a shard passes
+// the frames from its first column on), written in place; null: a new one.  Argument checks as demodulateSamples makes them.
+static napi_value ModulateSamples(napi_env env, napi_callback_info info) {
+  ARGS_UPTO(9);
+  fskhip_engine *e = get_engine(env, argv[0]);
+  if (!e) return nullptr;
+  napi_typedarray_type tt;
+  size_t plen = 0, llen = 0, olen = 0;
+  void *pdata = nullptr, *ldata = nullptr, *out = nullptr, *olens = nullptr;
+  NAPI_OK(napi_get_typedarray_info(env, argv[1], &tt, &plen, &pdata, nullptr, nullptr));
+  if (tt != napi_uint8_array) { napi_throw_type_error(env, nullptr, "payloads must be a Uint8Array"); return nullptr; }
+  NAPI_OK(napi_get_typedarray_info(env, argv[2], &tt, &llen, &ldata, nullptr, nullptr));
+  if (tt != napi_uint32_array) { napi_throw_type_error(env, nullptr, "lens must be a Uint32Array"); return nullptr; }
+  const uint32_t ppitch = u32(env, argv[3]);
+  const int32_t format = i32(env, argv[4]), layout = i32(env, argv[5]);
+  const uint32_t n = u32(env, argv[6]), pitch = u32(env, argv[7]);
+  const uint32_t S = fskhip_n_streams(e);
+  if (llen < S || plen < (size_t)ppitch * S) { napi_throw_range_error(env, nullptr, "payloads/lens too short"); return nullptr; }
+  const size_t esz = fskhip_sample_bytes(format);
+  if (!esz || (layout != FSKHIP_LAYOUT_STREAM_MAJOR && layout != FSKHIP_LAYOUT_SAMPLE_MAJOR)) {
+    napi_throw_type_error(env, nullptr, "unknown sample format or layout");
+    return nullptr;
+  }
+  const napi_typedarray_type want = format == FSKHIP_SAMPLES_F32 ? napi_float32_array : format == FSKHIP_SAMPLES_S16 ? napi_int16_array : napi_uint8_array;
+  // the last row (stream-major) / the last frame (sample-major) may end with its own samples
+  const bool frames = layout == FSKHIP_LAYOUT_SAMPLE_MAJOR;
+  const size_t rows = frames ? n : S, cols = frames ? S : n;
+  const size_t need = rows ? (size_t)pitch * (rows - 1) + cols : 0;
+  napi_value out_v = argv[8];
+  if (argc < 9 || nullish(env, argv[8])) {
+    if (pitch < cols) { napi_throw_range_error(env, nullptr, "samples too short"); return nullptr; }
+    out_v = make_typed(env, want, need, esz, &out);
+    if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+    if (format == FSKHIP_SAMPLES_MULAW || format == FSKHIP_SAMPLES_ALAW)   // (the pitch's padding: silence, like the rest)
+      memset(out, format == FSKHIP_SAMPLES_MULAW ? 0xFF : 0xD5, need);
+  } else {
+    NAPI_OK(napi_get_typedarray_info(env, argv[8], &tt, &olen, &out, nullptr, nullptr));
+    if (tt != want) { napi_throw_type_error(env, nullptr, "samples must be the format's typed array: Float32Array, Int16Array or (G.711) Uint8Array"); return nullptr; }
+    if (pitch < cols || need > olen) { napi_throw_range_error(env, nullptr, "samples too short"); return nullptr; }
+  }
+  napi_value len_v = make_typed(env, napi_uint32_array, S, 4, &olens);
+  if (!len_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  int rc = fskhip_modulate_host_fmt(e, (const uint8_t *)pdata, (const uint32_t *)ldata, ppitch, format, layout, out, n, pitch, (uint32_t *)olens);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  napi_value res;
+  NAPI_OK(napi_create_object(env, &res));
+  napi_set_named_property(env, res, "out", out_v);
+  napi_set_named_property(env, res, "lens", len_v);
+  return res;
+}
+
 static napi_value ModulatedLength(napi_env env, napi_callback_info info) {
   ARGS_UPTO(2);
   fskhip_engine *e = get_engine(env, argv[0]);
@@ -589,6 +644,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"demodulateAsync", nullptr, DemodulateAsync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"demodulateSamples", nullptr, DemodulateSamples, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"demodulateSamplesAsync", nullptr, DemodulateSamplesAsync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"modulateSamples", nullptr, ModulateSamples, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"modulate", nullptr, Modulate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"modulatedLength", nullptr, ModulatedLength, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"reset", nullptr, Reset, nullptr, nullptr, nullptr, napi_default, nullptr},

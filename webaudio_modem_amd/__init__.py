@@ -4,7 +4,7 @@ Everything that computes goes through libfskhip.so (hand-written HIP for gfx950,
 include/fskhip.h).  There is no CPU path in this package.
 """
 from ._lib import FskHipError, PRECISION_F32, PRECISION_F64, DEMOD_WRITEBACK_AGC, LIB_PATH  # noqa: F401
-from .engine import FSKEngine, DEFAULT_FSK_CONFIG, make_config, pinned_empty, snapshot_info, snapshot_stream_config, snapshot_concat, ingest_device, SAMPLE_FORMATS, SAMPLE_LAYOUTS  # noqa: F401
+from .engine import FSKEngine, DEFAULT_FSK_CONFIG, make_config, pinned_empty, snapshot_info, snapshot_stream_config, snapshot_concat, ingest_device, egress_device, SAMPLE_FORMATS, SAMPLE_LAYOUTS  # noqa: F401
 from .fsk_core import FSKCore, Event, EventEmitter  # noqa: F401
 from .filters import FilterDesign, FilterFactory, FIRFilter, FIRFilterBatch, IIRFilter, IIRFilterBatch  # noqa: F401
 from .processor import ChunkedModulator, FSKProcessorBatch, ProcessorBatchSnapshot, processor_snapshot_info  # noqa: F401
@@ -14,4 +14,4 @@ from .sharded import FSKEngineSharded  # noqa: F401
 
 __all__ = ["FSKEngine", "FSKEngineSharded", "FSKCore", "FilterDesign", "FilterFactory", "FIRFilter", "FIRFilterBatch", "IIRFilter", "IIRFilterBatch", "ChunkedModulator",
            "FSKProcessorBatch", "ProcessorBatchSnapshot", "processor_snapshot_info", "CRC16", "XModemPacket", "ControlType", "crc16_batch", "serialize_batch", "scan_bursts",
-           "DEFAULT_FSK_CONFIG", "snapshot_info", "snapshot_stream_config", "snapshot_concat", "ingest_device", "SAMPLE_FORMATS", "SAMPLE_LAYOUTS", "FskHipError", "PRECISION_F32", "PRECISION_F64"]
+           "DEFAULT_FSK_CONFIG", "snapshot_info", "snapshot_stream_config", "snapshot_concat", "ingest_device", "egress_device", "SAMPLE_FORMATS", "SAMPLE_LAYOUTS", "FskHipError", "PRECISION_F32", "PRECISION_F64"]

@@ -86,6 +86,8 @@ _SYMBOLS = [
     ("fskhip_sample_bytes", C.c_size_t, [C.c_int]),
     ("fskhip_ingest_device", C.c_int, [_P, C.c_int, C.c_int, C.c_uint32, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P]),
     ("fskhip_demodulate_host_fmt", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_uint32]),
+    ("fskhip_egress_device", C.c_int, [_P, C.c_size_t, _P, C.c_uint32, C.c_size_t, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    ("fskhip_modulate_host_fmt", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, _P, C.c_size_t, C.c_size_t, _P]),
     ("fskhip_modulated_length", C.c_size_t, [_P, C.c_size_t]),
     ("fskhip_modulate_host", C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
     ("fskhip_modulate_device", C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t, _P, _P]),

@@ -127,6 +127,48 @@ int fskhip_modulate_host(fskhip_engine *e, const uint8_t *payloads, const uint32
     if (out_lens[s] > out_pitch) return fail(FSKHIP_E_OVERFLOW, "stream %zu needs %u samples, slab holds %zu", s, out_lens[s], out_pitch);
   return FSKHIP_OK;
 }
+// ... and the same into any capture format and layout (include/fskhip.h): the floats stay on the device, fsk_egress.hip's kernel narrows
+// them -- silence from the modulator's own d_out_lens on -- into a staging buffer kept with the engine, and the narrow samples cross
+// PCIe in one 2-D copy: rows of n elements (stream-major), or n frames of n_streams elements (sample-major: the staging frames are
+// packed, the caller's may be wider and keep their other columns)
+int fskhip_modulate_host_fmt(fskhip_engine *e, const uint8_t *payloads, const uint32_t *lens, size_t payload_pitch, int format, int layout, void *out, size_t n,
+                             size_t dst_pitch, uint32_t *out_lens) {
+  const size_t esz = ingest_sample_bytes(format);
+  if (!esz) return fail(FSKHIP_E_INVALID, "fskhip_modulate_host_fmt: unknown sample format %d", format);
+  if (layout != FSKHIP_LAYOUT_STREAM_MAJOR && layout != FSKHIP_LAYOUT_SAMPLE_MAJOR) return fail(FSKHIP_E_INVALID, "fskhip_modulate_host_fmt: unknown layout %d", layout);
+  if (!e) return fail(FSKHIP_E_NOT_CONFIGURED, "FSK modulator not configured");
+  if (!lens || !out_lens || (n > 0 && !out)) return fail(FSKHIP_E_INVALID, "null buffer");
+  const size_t S = e->n_streams;
+  const bool frames = layout == FSKHIP_LAYOUT_SAMPLE_MAJOR;
+  if (!frames && dst_pitch < n) return fail(FSKHIP_E_INVALID, "dst_pitch %zu < n_per_stream %zu", dst_pitch, n);
+  if (frames && dst_pitch < S) return fail(FSKHIP_E_INVALID, "frame pitch %zu < n_streams %zu", dst_pitch, S);
+  if ((reinterpret_cast<uintptr_t>(out) & (esz - 1u)) != 0) return fail(FSKHIP_E_INVALID, "out is not aligned to its element size");
+  for (size_t s = 0; s < S; s++)
+    if (lens[s] > payload_pitch) return fail(FSKHIP_E_INVALID, "lens[%zu] = %u exceeds payload_pitch %zu", s, lens[s], payload_pitch);
+  HIP_TRY(hipSetDevice(e->device));
+  const EgressStage g = egress_stage(S, n, esz, frames);
+  int rc;
+  if ((rc = ensure(e->host.d_samples, e->host.d_samples_cap, (g.fpitch ? g.fpitch : 4) * S)) != FSKHIP_OK) return rc;
+  if ((rc = ensure(e->host.d_payloads, e->host.d_payloads_cap, (payload_pitch ? payload_pitch : 1) * S)) != FSKHIP_OK) return rc;
+  if (n > 0 && (rc = ensure(e->host.d_egress, e->host.d_egress_cap, g.bytes)) != FSKHIP_OK) return rc;
+  if (payload_pitch > 0 && payloads)
+    HIP_TRY(hipMemcpyAsync(e->host.d_payloads, payloads, payload_pitch * S, hipMemcpyHostToDevice, e->host.stream));
+  HIP_TRY(hipMemcpyAsync(e->host.d_lens, lens, sizeof(uint32_t) * S, hipMemcpyHostToDevice, e->host.stream));
+  rc = fskhip_modulate_device(e, e->host.d_payloads, e->host.d_lens, payload_pitch, e->host.d_samples, g.fpitch, e->host.d_counts, e->host.stream);
+  if (rc != FSKHIP_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(out_lens, e->host.d_counts, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, e->host.stream));
+  if (n > 0) {
+    const hipError_t err = launch_egress(e->host.d_samples, g.fpitch, e->host.d_counts, (uint32_t)S, n, format, layout, e->host.d_egress, g.npitch, e->host.stream);
+    if (err == hipErrorInvalidValue) return fail(FSKHIP_E_INVALID, "fskhip_modulate_host_fmt: %zu streams x %zu samples are more workgroups than one launch takes", S, n);
+    HIP_TRY(err);
+    HIP_TRY(hipMemcpy2DAsync(out, dst_pitch * esz, e->host.d_egress, g.npitch * esz, g.row_bytes, g.rows, hipMemcpyDeviceToHost, e->host.stream));
+  }
+  HIP_TRY(hipStreamSynchronize(e->host.stream));
+  if (const int hrc = handoff_check(e, true)) return hrc;
+  for (size_t s = 0; s < S; s++)
+    if (out_lens[s] > n) return fail(FSKHIP_E_OVERFLOW, "stream %zu needs %u samples, slab holds %zu", s, out_lens[s], n);
+  return FSKHIP_OK;
+}
 int fskhip_synth_device(fskhip_engine *e, float *d_out, size_t n, size_t pitch, uint32_t payload_len, uint64_t seed,
                         uint32_t lead_max, double amp_lo, double amp_hi, void *hip_stream) {
   if (!e) return fail(FSKHIP_E_NOT_CONFIGURED, "not configured");

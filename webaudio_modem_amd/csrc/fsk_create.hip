@@ -353,7 +353,7 @@ int fskhip_destroy(fskhip_engine *e) {
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
   void *bufs[] = {e->S.rs, e->S.is, e->S.poly, e->S.amp_ring, (void *)e->S.coef, (void *)e->S.nco_inc, e->host.d_samples,
-                  e->host.d_samples2, e->host.d_narrow[0], e->host.d_narrow[1], e->host.d_out, e->host.d_counts, e->host.d_eod, e->host.d_lens, e->host.d_payloads, e->d_status, e->d_sigma,
+                  e->host.d_samples2, e->host.d_narrow[0], e->host.d_narrow[1], e->host.d_egress, e->host.d_out, e->host.d_counts, e->host.d_eod, e->host.d_lens, e->host.d_payloads, e->d_status, e->d_sigma,
                   e->S.trace_amp, e->S.trace_post, e->S.trace_bit, e->S.trace_n, e->S.poly_u, e->S.cu_ctr, e->S.blk_q, e->S.blk_stash, e->S.blk_stat, e->d_clock};
   for (void *b : bufs)
     if (b) (void)hipFree(b);

@@ -79,6 +79,7 @@ struct fskhip_engine {
     float *d_samples2 = nullptr; size_t d_samples2_cap = 0;   // second time slab of fskhip_demodulate_host's pipeline
     hipStream_t copy_stream = nullptr;                        // its H2D stream
     uint8_t *d_narrow[2] = {nullptr, nullptr}; size_t d_narrow_cap[2] = {0, 0};   // fskhip_demodulate_host_fmt: the samples as they crossed PCIe, per time slab
+    uint8_t *d_egress = nullptr; size_t d_egress_cap = 0;     // fskhip_modulate_host_fmt: the samples as they cross PCIe
     hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_used_up[2] = {nullptr, nullptr};
     uint8_t *d_out = nullptr; size_t d_out_cap = 0;
     uint32_t *d_counts = nullptr, *d_eod = nullptr, *d_lens = nullptr;

@@ -102,6 +102,11 @@ hipError_t launch_snap_unpack(int precision, const SnapLayout &L, const DemodSta
 // has checked the arguments (fskhip_ingest_device); nothing is launched for an empty batch.  ingest_sample_bytes: 0 = unknown format.
 size_t ingest_sample_bytes(int format);
 hipError_t launch_ingest(const void *d_src, int format, int layout, uint32_t n_streams, size_t n, size_t src_pitch, float *d_dst, size_t dst_pitch, hipStream_t st);
+// fsk_egress.hip: float32 [stream][src_pitch] -> the same formats and layouts, narrowed (include/fskhip.h: the encoders).  d_lens (may
+// be null): elements from d_lens[s] on are the format's silence.  The caller has checked the arguments (fskhip_egress_device); nothing
+// is launched for an empty batch.
+hipError_t launch_egress(const float *d_src, size_t src_pitch, const uint32_t *d_lens, uint32_t n_streams, size_t n, int format, int layout, void *d_dst,
+                         size_t dst_pitch, hipStream_t st);
 // fsk_processor_remap.hip: FSKProcessor state (ProcState) between processors and stream-major records (ProcImage).
 // gather: stream i of D continues stream d_map[i] of S, or starts as a created one where d_map[i] = -1.
 // unpack: the same from the slab I of an image's records; streams whose record is in another slab are left alone, new ones are

@@ -66,6 +66,26 @@ inline size_t host_stage_shift(bool f64, bool lock_step, uint32_t ds_parity) {
   return (!f64 && lock_step && (plan_head(ds_parity, 0, false) & 1u)) ? 3 : 0;
 }
 
+// fskhip_modulate_host_fmt's staging (fsk_api.hip): the float rows the modulator writes, the narrow buffer fsk_egress.hip's kernel
+// fills, and the ONE 2-D copy that brings it to the host -- of `rows` rows of `row_bytes` bytes, npitch * esz apart on the device.
+// Stream-major rows start on 16-byte boundaries (the kernel's vector path from element 0); sample-major frames are packed, n_streams
+// elements each, whatever frame pitch the caller's buffer has.
+struct EgressStage {
+  size_t fpitch;             // floats per row of the float staging: a multiple of 4
+  size_t npitch;             // elements per row (stream-major) or frame (sample-major) of the narrow staging
+  size_t bytes;              // of the narrow staging
+  size_t rows, row_bytes;    // the copy's geometry
+};
+inline EgressStage egress_stage(size_t n_streams, size_t n, size_t esz, bool frames) {
+  EgressStage g;
+  g.fpitch = (n + 3) & ~(size_t)3;
+  g.npitch = frames ? n_streams : ((n * esz + 15) & ~(size_t)15) / esz;
+  g.rows = frames ? n : n_streams;
+  g.row_bytes = (frames ? n_streams : n) * esz;
+  g.bytes = g.rows * g.npitch * esz;
+  return g;
+}
+
 // Lock-step fp32 batches with narrow integer-capacity rings never leave fsk_pipe.hip's arithmetic: a head of single samples,
 // whole 16-sample tiles, a tail of single samples -- so cutting a stream into calls of any lengths changes nothing, bit for bit.
 // Everything else (fp64, wide / fractional rings, streams out of lock step, an open pair the generic kernel left) is the

@@ -233,6 +233,47 @@ def ingest_device(d_src, fmt, layout, n_streams, n_per_stream, src_pitch, d_dst,
                                                d_dst, dst_pitch, stream))
 
 
+def egress_device(d_src, src_pitch, d_lens, n_streams, n_per_stream, fmt, layout, d_dst, dst_pitch, stream=None):
+    """fskhip_egress_device: device pointers (ints); narrows float32 [n_streams][src_pitch] into samples of `fmt` in `layout` on the
+    current device, asynchronously on `stream` (a hipStream_t handle or None).  d_lens (or None): per-stream lengths; a stream is
+    the format's silence from its length on."""
+    _lib.check(_lib.lib().fskhip_egress_device(d_src, src_pitch, d_lens, n_streams, n_per_stream, _format_code(fmt), _layout_code(layout),
+                                               d_dst, dst_pitch, stream))
+
+
+def payload_args(payloads):
+    """What the modulate calls take for a list of bytes-like payloads: (uint8 [S, pitch] array, uint32 lengths, pitch)"""
+    lens = np.array([len(p) for p in payloads], dtype=np.uint32)
+    ppitch = max(1, int(lens.max())) if len(lens) else 1
+    pay = np.zeros((len(payloads), ppitch), dtype=np.uint8)
+    for s, p in enumerate(payloads):
+        if len(p):
+            pay[s, :len(p)] = np.frombuffer(bytes(p), dtype=np.uint8)
+    return pay, lens, ppitch
+
+
+def samples_out(fmt, layout, n_streams, n_per_stream, out=None):
+    """The array FSKEngine.modulate_samples writes: (array, format, layout, pitch in elements).  out None: a new one of the format's
+    dtype (SAMPLE_FORMATS), [S, n] (layout "stream") or [n, S] (layout "sample").  Otherwise `out` itself, which must have that
+    dtype and shape and unit stride along its rows; its rows may be a block of a wider array (a shard's column block of
+    interleaved frames): the wider array's pitch is passed on and nothing is copied."""
+    code, lay = _format_code(fmt), _layout_code(layout)
+    if code not in _FORMAT_DTYPE:
+        raise ValueError("unknown sample format %r" % (fmt,))
+    if lay not in (_lib.LAYOUT_STREAM_MAJOR, _lib.LAYOUT_SAMPLE_MAJOR):
+        raise ValueError("unknown layout %r" % (layout,))
+    shape = (n_streams, n_per_stream) if lay == _lib.LAYOUT_STREAM_MAJOR else (n_per_stream, n_streams)
+    if out is None:
+        out = np.zeros(shape, _FORMAT_DTYPE[code])
+    if not isinstance(out, np.ndarray) or out.dtype != _FORMAT_DTYPE[code] or out.shape != shape or not out.flags.writeable:
+        raise ValueError("out must be a writeable %s array of shape %r" % (np.dtype(_FORMAT_DTYPE[code]).name, shape))
+    isz = out.dtype.itemsize
+    rows, cols = shape
+    if not (cols <= 1 or out.strides[1] == isz) or not (rows <= 1 or (out.strides[0] % isz == 0 and out.strides[0] >= cols * isz)):
+        raise ValueError("out must have contiguous rows at a constant pitch")
+    return out, code, lay, max(out.strides[0] // isz if rows > 1 else cols, cols, 1)
+
+
 # Called with (n_streams, precision) by every new FSKEngine; returns a dict of fskhip_set_option() names -> values to apply on
 # top of the `options` argument, or None.  The package sets nothing here and reads no environment variable; the test suite
 # (tests/conftest.py) and the measurement tools (tools/envopts.py) install a hook that maps their FSKHIP_* variables.
@@ -431,18 +472,29 @@ class FSKEngine:
         if len(payloads) != self.n_streams:
             raise ValueError("need one payload per stream")
         S = self.n_streams
-        lens = np.array([len(p) for p in payloads], dtype=np.uint32)
-        ppitch = max(1, int(lens.max()))
-        pay = np.zeros((S, ppitch), dtype=np.uint8)
-        for s, p in enumerate(payloads):
-            if len(p):
-                pay[s, :len(p)] = np.frombuffer(bytes(p), dtype=np.uint8)
+        pay, lens, ppitch = payload_args(payloads)
         opitch = max(4, self.modulated_length(int(lens.max())))
         out = np.zeros((S, opitch), dtype=np.float32)
         out_lens = np.zeros(S, dtype=np.uint32)
         _lib.check(self._L.fskhip_modulate_host(self._h, pay.ctypes.data, lens.ctypes.data, ppitch, out.ctypes.data,
                                                 opitch, out_lens.ctypes.data))
         return [out[s, :out_lens[s]].copy() for s in range(S)]
+
+    def modulate_samples(self, payloads, fmt, layout="stream", n_per_stream=None, out=None):
+        """modulate_data into playback samples as a trunk or a sound card takes them (fskhip_modulate_host_fmt): fmt "s16", "mulaw",
+        "alaw" or "f32", [S, n] (layout="stream") or interleaved frames [n, S] (layout="sample"); quantised on the device, so the
+        narrow samples are what crosses PCIe.  n_per_stream None: the longest signal's length.  Returns (samples, lens): stream s
+        is the format's silence from lens[s] on.  `out`: the array to write into (samples_out)."""
+        if len(payloads) != self.n_streams:
+            raise ValueError("need one payload per stream")
+        S = self.n_streams
+        pay, lens, ppitch = payload_args(payloads)
+        n = self.modulated_length(int(lens.max())) if n_per_stream is None else int(n_per_stream)
+        out, code, lay, pitch = samples_out(fmt, layout, S, n, out)
+        out_lens = np.zeros(S, dtype=np.uint32)
+        _lib.check(self._L.fskhip_modulate_host_fmt(self._h, pay.ctypes.data, lens.ctypes.data, ppitch, code, lay, out.ctypes.data, n, pitch,
+                                                    out_lens.ctypes.data))
+        return out, out_lens
 
     def modulate_device(self, d_payloads, d_lens, payload_pitch, d_out, out_pitch, d_out_lens, stream=None):
         _lib.check(self._L.fskhip_modulate_device(self._h, d_payloads, d_lens, payload_pitch, d_out, out_pitch,

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PRECISION_F32
-from .engine import FSKEngine, snapshot_concat, _snapshot_plan, sample_args
+from .engine import FSKEngine, snapshot_concat, _snapshot_plan, sample_args, samples_out
 from .sharding import all_shards
 
 
@@ -164,6 +164,20 @@ class FSKEngineSharded:
             raise ValueError("need one payload per stream")
         parts = self._fan_out(lambda i, e, first, count: e.modulate_data(payloads[first:first + count]))
         return [sig for p in parts for sig in p]
+
+    def modulate_samples(self, payloads, fmt, layout="stream", n_per_stream=None, out=None):
+        """FSKEngine.modulate_samples over the shards: ONE array for the whole batch and no host copy -- every shard writes its row
+        block of a stream-major array, or its COLUMN block of the interleaved frames at the full frame pitch."""
+        if len(payloads) != self.n_streams:
+            raise ValueError("need one payload per stream")
+        if n_per_stream is None:   # (one signal length per payload size: the fields it depends on are shared by every stream)
+            n_per_stream = self.engines[0].modulated_length(max((len(p) for p in payloads), default=0))
+        n = int(n_per_stream)
+        out, code, lay, _pitch = samples_out(fmt, layout, self.n_streams, n, out)
+        sample_major = lay == _lib.LAYOUT_SAMPLE_MAJOR
+        parts = self._fan_out(lambda i, e, first, count: e.modulate_samples(
+            payloads[first:first + count], code, lay, n_per_stream=n, out=out[:, first:first + count] if sample_major else out[first:first + count])[1])
+        return out, (np.concatenate([np.asarray(p, dtype=np.uint32) for p in parts]) if parts else np.zeros(0, np.uint32))
 
     # ---- reset / getStatus -----------------------------------------------------------------------
     def reset(self, stream=-1):
