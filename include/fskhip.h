@@ -31,7 +31,8 @@ extern "C" {
  * fskhip_restore_streams (additions, same version); fskhip_processor_remap / _snapshot_bytes / _snapshot / _snapshot_info_get /
  * _restore in fskhip_next.h (additions, same version); capture formats -- FSKHIP_SAMPLES_* / FSKHIP_LAYOUT_*, fskhip_sample_bytes,
  * fskhip_ingest_device, fskhip_demodulate_host_fmt (additions, same version); the same formats out -- fskhip_egress_device,
- * fskhip_modulate_host_fmt (additions, same version). */
+ * fskhip_modulate_host_fmt (additions, same version); the compacted RX drain -- fskhip_processor_rx_drain_sparse_host / _device in
+ * fskhip_next.h (additions, same version). */
 #define FSKHIP_ABI_VERSION 8
 #define FSKHIP_MAX_PATTERN_BYTES 16
 

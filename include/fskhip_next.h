@@ -128,6 +128,34 @@ int fskhip_processor_tx_state_host(fskhip_processor *p, uint32_t *pos, uint32_t 
 /* the 'demodulate' request without the wait (fsk-processor.ts:117-138): remove everything buffered.  counts[s]
  * is the number of bytes removed into out[s*out_pitch ...] (out_pitch >= rx_capacity never overflows). */
 int fskhip_processor_rx_drain_host(fskhip_processor *p, uint8_t *out, size_t out_pitch, uint32_t *counts);
+/*
+ * The same request for the receivers that hold bytes only (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): a compacted drain.
+ * What crosses to the caller is the live bytes and two words per selected stream, not n_streams x out_pitch.
+ *   selected    stream s is selected when (mask == NULL || mask[s]) and its ring holds at least max(min_len, 1) bytes: min_len lets
+ *               a host wait for a whole packet header, or a whole packet, before it pays for a stream.  The selected streams are
+ *               listed in ascending order: streams[0 .. n_active).
+ *   CSR layout  offsets has n_active + 1 entries -- the caller provides cap_streams + 1 words --, offsets[0] = 0,
+ *               offsets[n_active] = n_bytes; the bytes of streams[i] are data[offsets[i] .. offsets[i+1]), oldest first, tightly
+ *               packed: exactly what fskhip_processor_rx_drain_host would have returned for that stream.
+ *   the rings   the dense drain's effect, for the selected streams only: readIndex advanced by _length modulo the capacity,
+ *               _length = 0, writeIndex and the ring bytes untouched.  A stream that is not selected is not touched in any word.
+ *   overflow    atomic: if n_active > cap_streams or n_bytes > cap_bytes the call returns FSKHIP_E_OVERFLOW with *n_active and
+ *               *n_bytes set to the true sizes and drains NOTHING -- every ring is as it was, the host calls again with room.
+ *               Both caps 0 with null lists is therefore a size query.
+ *   _device     asynchronous on `hip_stream`, pointers on the processor's device; d_totals takes three words: n_active, n_bytes,
+ *               and 1 if the rings were drained, 0 if a cap was too small (the packing kernel reads the totals and stands down
+ *               as a whole; the lists are then undefined).  It uses scratch kept with the processor: one such call at a time.
+ * FSKHIP_E_INVALID before any device call, in this order: null n_active or n_bytes (_host) / null d_totals (_device); a null
+ * streams or offsets with cap_streams != 0, a null data with cap_bytes != 0; a null processor.  FSKHIP_E_UNSUPPORTED when
+ * n_streams x rx_capacity exceeds 2^32 - 1 (offsets are 32-bit).  Like the dense drain it makes the processor a used one
+ * (fskhip_processor_remap wants a fresh destination), and it is never part of the captured quantum graph.  Never returns -8.
+ */
+int fskhip_processor_rx_drain_sparse_host(fskhip_processor *p, const uint8_t *mask, uint32_t min_len, uint32_t *streams,
+                                          uint32_t *offsets, uint32_t cap_streams, uint8_t *data, size_t cap_bytes,
+                                          uint32_t *n_active, uint32_t *n_bytes);
+int fskhip_processor_rx_drain_sparse_device(fskhip_processor *p, const uint8_t *d_mask, uint32_t min_len, uint32_t *d_streams,
+                                            uint32_t *d_offsets, uint32_t cap_streams, uint8_t *d_data, size_t cap_bytes,
+                                            uint32_t *d_totals, void *hip_stream);
 /* demodulatedBufferLength of the 'status' reply (fsk-processor.ts:246). */
 int fskhip_processor_rx_length_host(fskhip_processor *p, uint32_t *lengths);
 /* reset() (fsk-processor.ts:140-146): RX ring cleared, pending modulation dropped; stream < 0 = all.  The

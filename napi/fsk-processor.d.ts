@@ -16,6 +16,9 @@ export declare class FSKProcessorBatch {
   txState(): { pos: Uint32Array; total: Uint32Array; pending: Uint8Array; completed: Uint32Array };
   /** 'demodulate' without the wait: everything buffered, per stream */
   demodulate(): Uint8Array[];
+  /** the same for the streams that hold at least max(minLen, 1) bytes (and mask[s]) only, in ascending order: the bytes of
+   *  streams[i] are data.subarray(offsets[i], offsets[i + 1]); streams not listed keep their rings */
+  rxDrainSparse(options?: { mask?: ArrayLike<boolean | number> | null; minLen?: number }): { streams: Uint32Array; offsets: Uint32Array; data: Uint8Array };
   rxLengths(): Uint32Array;
   reset(stream?: number): void;
   status(stream?: number): FSKStatus & { demodulatedBufferLength: number; pendingModulation: boolean; fskCoreReady: boolean; processDemodulationCallCount: number };

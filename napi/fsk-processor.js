@@ -92,6 +92,21 @@ class FSKProcessorBatch {
     for (let s = 0; s < this.nStreams; s++) out.push(r.out.slice(s * r.outPitch, s * r.outPitch + r.counts[s]));
     return out;
   }
+  // the same for the streams that hold bytes only: {streams, offsets, data} -- the streams with at least max(minLen, 1) buffered
+  // bytes (and mask[s], where a mask is given) in ascending order; the bytes of streams[i] are data.subarray(offsets[i], offsets[i + 1]).
+  // Streams not listed keep their rings.
+  rxDrainSparse(options = {}) {
+    if (options === null || typeof options !== 'object') throw new TypeError('rxDrainSparse: options must be an object {mask, minLen}');
+    const { mask, minLen = 1 } = options;
+    if (!Number.isInteger(minLen) || minLen < 0 || minLen > 0xffffffff) throw new RangeError('rxDrainSparse: minLen must be an integer in [0, 2^32)');
+    let m = null;
+    if (mask !== undefined && mask !== null) {
+      if (!Array.isArray(mask) && !ArrayBuffer.isView(mask)) throw new TypeError('rxDrainSparse: mask must be an array of nStreams booleans');
+      if (mask.length !== this.nStreams) throw new RangeError('rxDrainSparse: mask must have one entry per stream (' + this.nStreams + ')');
+      m = Uint8Array.from(mask, (b) => (b ? 1 : 0));
+    }
+    return addon.processorDrainSparse(this.handle, m, minLen);
+  }
   rxLengths() { return addon.processorRxLength(this.handle); }
   reset(stream = -1) { addon.processorReset(this.handle, stream); }
   status(stream = 0) {               // the 'status' reply (240-253)

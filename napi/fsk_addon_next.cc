@@ -12,6 +12,7 @@
 //   processorModulate(handle, payloads: Uint8Array, lens: Uint32Array, pitch, mask: Uint8Array|null)
 //   processorTxState(handle) -> {pos, total, pending, completed};  processorRxLength(handle) -> Uint32Array
 //   processorDrain(handle, capacity) -> {out, outPitch, counts};  processorReset(handle, stream)
+//   processorDrainSparse(handle, mask: Uint8Array|null, minLen) -> {streams: Uint32Array, offsets: Uint32Array, data: Uint8Array}
 //   processorRemap(dst, src, map: number[]);  processorSnapshot(handle, sel: number[]|null) -> Buffer
 //   processorRestore(dst, snapshot: Uint8Array, map: number[]);  processorSnapshotInfo(snapshot) -> {nStreams, rxCapacity, payloadCapacity, recordBytes}
 //   sincLowpass/sincHighpass(cutoff, sampleRate, numTaps), sincBandpass(center, bandwidth, sampleRate, numTaps) -> Float64Array
@@ -219,6 +220,38 @@ napi_value ProcessorDrain(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, o, "out", out_v);
   napi_set_named_property(env, o, "counts", cnt_v);
   set_u32(env, o, "outPitch", cap);
+  return o;
+}
+
+// the compacted drain: sized with a query call (an overflowing call drains nothing), then drained into arrays of exactly that size
+napi_value ProcessorDrainSparse(napi_env env, napi_callback_info info) {
+  ARGS(3);
+  Proc *h = get_proc(env, argv[0]);
+  if (!h) return nullptr;
+  void *mask; size_t mlen;
+  if (!typed(env, argv[1], napi_uint8_array, &mask, &mlen, true)) return nullptr;
+  if (mask && mlen != h->S) { napi_throw_range_error(env, nullptr, "processorDrainSparse: mask must have one entry per stream"); return nullptr; }
+  const uint32_t min_len = u32(env, argv[2]);
+  uint32_t n_active = 0, n_bytes = 0;
+  int rc = fskhip_processor_rx_drain_sparse_host(h->p, (const uint8_t *)mask, min_len, nullptr, nullptr, 0, nullptr, 0, &n_active, &n_bytes);
+  if (rc != FSKHIP_OK && rc != FSKHIP_E_OVERFLOW) return throw_fsk(env, rc);
+  void *streams, *offsets, *data;
+  napi_value str_v = make_typed(env, napi_uint32_array, n_active, 4, &streams);
+  napi_value off_v = make_typed(env, napi_uint32_array, (size_t)n_active + 1, 4, &offsets);
+  napi_value dat_v = make_typed(env, napi_uint8_array, n_bytes, 1, &data);
+  if (!str_v || !off_v || !dat_v) { napi_throw_error(env, nullptr, "processorDrainSparse: out of memory"); return nullptr; }
+  if (rc == FSKHIP_E_OVERFLOW) {
+    rc = fskhip_processor_rx_drain_sparse_host(h->p, (const uint8_t *)mask, min_len, (uint32_t *)streams, (uint32_t *)offsets, n_active, (uint8_t *)data,
+                                               n_bytes, &n_active, &n_bytes);
+    if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  } else {
+    *(uint32_t *)offsets = 0u;
+  }
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "streams", str_v);
+  napi_set_named_property(env, o, "offsets", off_v);
+  napi_set_named_property(env, o, "data", dat_v);
   return o;
 }
 
@@ -457,6 +490,7 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"processorTxState", nullptr, ProcessorTxState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRxLength", nullptr, ProcessorRxLength, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorDrain", nullptr, ProcessorDrain, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"processorDrainSparse", nullptr, ProcessorDrainSparse, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorReset", nullptr, ProcessorReset, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRemap", nullptr, ProcessorRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorSnapshot", nullptr, ProcessorSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},

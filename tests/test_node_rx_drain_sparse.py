@@ -1,0 +1,36 @@
+"""FSKProcessorBatch.rxDrainSparse (napi/fsk-processor.js -> N-API -> fskhip_processor_rx_drain_sparse_host):
+tests/js/rx_drain_sparse_test.js -- its argument checks without a device, and on the GPU its result against rxDrain's on a clone."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+NODE = shutil.which("node")
+JS = os.path.join(ROOT, "tests", "js", "rx_drain_sparse_test.js")
+
+
+def _build():
+    import __graft_entry__ as ge
+    ge.build()
+    if not os.path.exists(os.path.join(ROOT, "napi", "fsk_addon.node")):
+        pytest.skip("N-API addon not built (no node headers)")
+
+
+@pytest.mark.skipif(NODE is None, reason="node not installed")
+def test_node_rx_drain_sparse_argument_checks():
+    _build()
+    out = subprocess.run([NODE, JS, "cpu"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "js rx drain sparse cpu tests ok" in out.stdout
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(NODE is None, reason="node not installed")
+def test_node_rx_drain_sparse_equals_dense_drain_on_a_clone():
+    _build()
+    out = subprocess.run([NODE, JS, "gpu"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "js rx drain sparse gpu tests ok" in out.stdout

@@ -150,6 +150,8 @@ _SYMBOLS = [
     ("fskhip_processor_modulate_host", C.c_int, [_P, _P, _P, C.c_size_t, _P]),
     ("fskhip_processor_tx_state_host", C.c_int, [_P, _P, _P, _P, _P]),
     ("fskhip_processor_rx_drain_host", C.c_int, [_P, _P, C.c_size_t, _P]),
+    ("fskhip_processor_rx_drain_sparse_host", C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_size_t, _P, _P]),
+    ("fskhip_processor_rx_drain_sparse_device", C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_size_t, _P, _P]),
     ("fskhip_processor_rx_length_host", C.c_int, [_P, _P]),
     ("fskhip_processor_reset", C.c_int, [_P, C.c_int64]),
     ("fskhip_processor_remap", C.c_int, [_P, _P, _P, C.c_uint32]),

@@ -116,4 +116,13 @@ hipError_t launch_processor_gather(const ProcState &D, uint32_t n_dst, const int
 hipError_t launch_processor_unpack(const ProcState &D, uint32_t n_dst, const int64_t *d_map, const ProcImage &I, bool fresh_too, hipStream_t st);
 hipError_t launch_processor_pack(const ProcState &S, const int64_t *d_sel, const ProcImage &I, void *d_out, hipStream_t st);
 hipError_t launch_processor_max_payload(const ProcState &S, const int64_t *d_idx, uint32_t n, uint32_t *d_out, hipStream_t st);
+// fsk_drain.hip: the compacted RX drain (fskhip_processor_rx_drain_sparse_*).  The caller has checked the arguments.
+// size: count + scan -- d_pairs (drain_sparse_pair_words(n_streams) words of scratch) takes each workgroup's exclusive
+// {stream, byte} position, d_totals {n_active, n_bytes, 1 if both fit the caps else 0}.
+// pack: given those, and only where d_totals[2] is 1, writes the lists and the bytes and advances the selected rings.
+size_t drain_sparse_pair_words(uint32_t n_streams);
+hipError_t launch_drain_sparse_size(const ProcState &T, uint32_t n_streams, const uint8_t *d_mask, uint32_t min_len, uint32_t cap_streams, uint64_t cap_bytes,
+                                    uint32_t *d_pairs, uint32_t *d_totals, hipStream_t st);
+hipError_t launch_drain_sparse_pack(const ProcState &T, uint32_t n_streams, const uint8_t *d_mask, uint32_t min_len, const uint32_t *d_pairs,
+                                    const uint32_t *d_totals, uint32_t *d_streams, uint32_t *d_offsets, uint8_t *d_data, hipStream_t st);
 }  // namespace fsk

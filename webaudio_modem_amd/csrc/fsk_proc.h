@@ -19,7 +19,8 @@ struct fskhip_processor {
   float *d_in = nullptr; size_t d_in_cap = 0;
   float *d_out = nullptr; size_t d_out_cap = 0;
   uint8_t *d_stage = nullptr; size_t d_stage_cap = 0;
-  uint32_t *d_u32 = nullptr;   // [4][S] scratch
+  uint32_t *d_u32 = nullptr;   // [4][S] + 4 words of scratch (the 4: the sparse drain's totals behind its workgroup pairs)
+  uint32_t *d_lists = nullptr; size_t d_lists_cap = 0;   // the sparse drain's streams[] and offsets[] on their way to the host
   uint8_t *d_mask = nullptr;
   // captured quantum
   hipGraphExec_t graph_exec = nullptr;

@@ -60,7 +60,7 @@ int fskhip_processor_destroy(fskhip_processor *p) {
   drop_graph(p);
   void *bufs[] = {p->T.rx_buf, p->T.rx_w, p->T.rx_r, p->T.rx_len, p->T.tx_payload, p->T.tx_phase, p->T.tx_pos, p->T.tx_len,
                   p->T.tx_in_bit, p->T.tx_bit_idx, p->T.tx_cur_bit, p->T.tx_n_payload, p->T.tx_pending, p->T.tx_completed,
-                  p->d_bytes, p->d_counts, p->d_eod, p->d_in, p->d_out, p->d_stage, p->d_u32, p->d_mask};
+                  p->d_bytes, p->d_counts, p->d_eod, p->d_in, p->d_out, p->d_stage, p->d_u32, p->d_mask, p->d_lists};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   if (p->stream) (void)hipStreamDestroy(p->stream);
@@ -90,7 +90,7 @@ int fskhip_processor_create(fskhip_engine *e, uint32_t rx_capacity, fskhip_proce
   PROC_TRY(dev_alloc(T.tx_pos, S)); PROC_TRY(dev_alloc(T.tx_len, S)); PROC_TRY(dev_alloc(T.tx_in_bit, S));
   PROC_TRY(dev_alloc(T.tx_bit_idx, S)); PROC_TRY(dev_alloc(T.tx_cur_bit, S)); PROC_TRY(dev_alloc(T.tx_n_payload, S));
   PROC_TRY(dev_alloc(T.tx_pending, S)); PROC_TRY(dev_alloc(T.tx_completed, S));
-  PROC_TRY(dev_alloc(p->d_counts, S)); PROC_TRY(dev_alloc(p->d_eod, S)); PROC_TRY(dev_alloc(p->d_u32, 4 * S));
+  PROC_TRY(dev_alloc(p->d_counts, S)); PROC_TRY(dev_alloc(p->d_eod, S)); PROC_TRY(dev_alloc(p->d_u32, 4 * S + 4));
   PROC_TRY(dev_alloc(p->d_mask, S));
 #undef PROC_TRY
   if (rc == FSKHIP_OK) {
@@ -250,6 +250,73 @@ int fskhip_processor_rx_drain_host(fskhip_processor *p, uint8_t *out, size_t out
   if (out_pitch) HIP_TRY(hipMemcpy(out, p->d_stage, out_pitch * S, hipMemcpyDeviceToHost));
   for (size_t s = 0; s < S; s++)
     if (counts[s] > out_pitch) return fail(FSKHIP_E_OVERFLOW, "stream %zu held %u bytes, slab holds %zu", s, counts[s], out_pitch);
+  return FSKHIP_OK;
+}
+
+// what both forms of the sparse drain refuse before they touch the device, in the header's order
+static int sparse_drain_refusal(const char *fn, const fskhip_processor *p, const void *totals, const char *totals_name, const void *streams,
+                                const void *offsets, uint32_t cap_streams, const void *data, size_t cap_bytes) {
+  if (!totals) return fail(FSKHIP_E_INVALID, "%s: null %s", fn, totals_name);
+  if (cap_streams && (!streams || !offsets)) return fail(FSKHIP_E_INVALID, "%s: null streams or offsets with cap_streams %u", fn, cap_streams);
+  if (cap_bytes && !data) return fail(FSKHIP_E_INVALID, "%s: null data with cap_bytes %zu", fn, cap_bytes);
+  if (!p) return fail(FSKHIP_E_INVALID, "null processor");
+  if ((uint64_t)p->S * p->T.rx_cap > 0xFFFFFFFFull)
+    return fail(FSKHIP_E_UNSUPPORTED, "%s: %u streams x rx_capacity %u exceed the 32-bit offsets", fn, p->S, p->T.rx_cap);
+  return FSKHIP_OK;
+}
+
+int fskhip_processor_rx_drain_sparse_host(fskhip_processor *p, const uint8_t *mask, uint32_t min_len, uint32_t *streams,
+                                          uint32_t *offsets, uint32_t cap_streams, uint8_t *data, size_t cap_bytes,
+                                          uint32_t *n_active, uint32_t *n_bytes) {
+  static const char fn[] = "fskhip_processor_rx_drain_sparse_host";
+  if (const int rc = sparse_drain_refusal(fn, p, n_active && n_bytes ? (const void *)n_active : nullptr, "n_active or n_bytes", streams, offsets,
+                                          cap_streams, data, cap_bytes))
+    return rc;
+  p->used = true;
+  *n_active = 0u; *n_bytes = 0u;
+  const size_t S = p->S;
+  if (S == 0) {
+    if (offsets) offsets[0] = 0u;
+    return FSKHIP_OK;
+  }
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (mask) HIP_TRY(hipMemcpy(p->d_mask, mask, S, hipMemcpyHostToDevice));
+  const uint8_t *d_mask = mask ? p->d_mask : nullptr;
+  uint32_t *d_totals = p->d_u32 + 4 * S;
+  HIP_TRY(launch_drain_sparse_size(p->T, p->S, d_mask, min_len, cap_streams, cap_bytes, p->d_u32, d_totals, nullptr));
+  uint32_t totals[2] = {0u, 0u};
+  HIP_TRY(hipMemcpy(totals, d_totals, sizeof(totals), hipMemcpyDeviceToHost));
+  *n_active = totals[0]; *n_bytes = totals[1];
+  if (totals[0] > cap_streams || totals[1] > cap_bytes)
+    return fail(FSKHIP_E_OVERFLOW, "%u streams hold %u bytes, the lists hold %u streams and %zu bytes (nothing was drained)", totals[0], totals[1],
+                cap_streams, cap_bytes);
+  if (totals[0] == 0u) {   // nothing selected: nothing to pack
+    if (offsets) offsets[0] = 0u;
+    return FSKHIP_OK;
+  }
+  int rc;   // staging for what is there, not for n_streams x rx_capacity
+  if ((rc = ensure(p->d_stage, p->d_stage_cap, (size_t)totals[1])) != FSKHIP_OK) return rc;
+  if ((rc = ensure(p->d_lists, p->d_lists_cap, 2 * (size_t)totals[0] + 1)) != FSKHIP_OK) return rc;
+  uint32_t *d_streams = p->d_lists, *d_offsets = p->d_lists + totals[0];
+  HIP_TRY(launch_drain_sparse_pack(p->T, p->S, d_mask, min_len, p->d_u32, d_totals, d_streams, d_offsets, p->d_stage, nullptr));
+  HIP_TRY(hipMemcpy(streams, d_streams, sizeof(uint32_t) * totals[0], hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(offsets, d_offsets, sizeof(uint32_t) * ((size_t)totals[0] + 1), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(data, p->d_stage, totals[1], hipMemcpyDeviceToHost));
+  return FSKHIP_OK;
+}
+
+int fskhip_processor_rx_drain_sparse_device(fskhip_processor *p, const uint8_t *d_mask, uint32_t min_len, uint32_t *d_streams,
+                                            uint32_t *d_offsets, uint32_t cap_streams, uint8_t *d_data, size_t cap_bytes,
+                                            uint32_t *d_totals, void *hip_stream) {
+  if (const int rc = sparse_drain_refusal("fskhip_processor_rx_drain_sparse_device", p, d_totals, "d_totals", d_streams, d_offsets, cap_streams, d_data,
+                                          cap_bytes))
+    return rc;
+  p->used = true;
+  HIP_TRY(hipSetDevice(p->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_TRY(launch_drain_sparse_size(p->T, p->S, d_mask, min_len, cap_streams, cap_bytes, p->d_u32, d_totals, st));
+  HIP_TRY(launch_drain_sparse_pack(p->T, p->S, d_mask, min_len, p->d_u32, d_totals, d_streams, d_offsets, d_data, st));
   return FSKHIP_OK;
 }
 

@@ -218,6 +218,35 @@ class FSKProcessorBatch:
         _lib.check(self._L.fskhip_processor_rx_drain_host(self._h, out.ctypes.data, self.rx_capacity, counts.ctypes.data))
         return [out[s, :counts[s]].tobytes() for s in range(self.n_streams)]
 
+    def demodulate_sparse(self, mask=None, min_len=1):
+        """The same for the streams that hold bytes only (fskhip_processor_rx_drain_sparse_host): (streams, offsets, data) --
+        the streams with at least max(min_len, 1) buffered bytes (and mask[s], where a mask is given) in ascending order, and
+        their bytes in CSR form: those of streams[i] are data[offsets[i]:offsets[i + 1]], oldest first.  uint32, uint32
+        (one entry more than streams) and uint8 arrays of exactly the returned sizes.  Streams not listed keep their rings."""
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask, dtype=bool).reshape(-1).astype(np.uint8))
+            if len(m) != self.n_streams:
+                raise ValueError("mask must have one entry per stream")
+        m_p = None if m is None else m.ctypes.data
+        na, nb = C.c_uint32(0), C.c_uint32(0)
+        # a size query first: an overflowing call drains nothing, so the second call finds what the first one counted
+        rc = self._L.fskhip_processor_rx_drain_sparse_host(self._h, m_p, min_len, None, None, 0, None, 0, C.byref(na), C.byref(nb))
+        if rc != _lib.E_OVERFLOW:
+            _lib.check(rc)
+        streams = np.zeros(na.value, np.uint32)
+        offsets = np.zeros(na.value + 1, np.uint32)
+        data = np.zeros(nb.value, np.uint8)
+        if rc == _lib.E_OVERFLOW:
+            _lib.check(self._L.fskhip_processor_rx_drain_sparse_host(self._h, m_p, min_len, streams.ctypes.data, offsets.ctypes.data, na.value,
+                                                                     data.ctypes.data, nb.value, C.byref(na), C.byref(nb)))
+        return streams, offsets, data
+
+    def demodulate_active(self, mask=None, min_len=1):
+        """demodulate_sparse as {stream: bytes} of the streams that held any."""
+        streams, offsets, data = self.demodulate_sparse(mask=mask, min_len=min_len)
+        return {int(s): data[offsets[i]:offsets[i + 1]].tobytes() for i, s in enumerate(streams)}
+
     def rx_lengths(self):
         lens = np.zeros(self.n_streams, dtype=np.uint32)
         _lib.check(self._L.fskhip_processor_rx_length_host(self._h, lens.ctypes.data))
