@@ -32,7 +32,8 @@ extern "C" {
  * _restore in fskhip_next.h (additions, same version); capture formats -- FSKHIP_SAMPLES_* / FSKHIP_LAYOUT_*, fskhip_sample_bytes,
  * fskhip_ingest_device, fskhip_demodulate_host_fmt (additions, same version); the same formats out -- fskhip_egress_device,
  * fskhip_modulate_host_fmt (additions, same version); the compacted RX drain -- fskhip_processor_rx_drain_sparse_host / _device in
- * fskhip_next.h (additions, same version). */
+ * fskhip_next.h (additions, same version); the resident XModem receiver -- fskhip_xmodem_rx_* in fskhip_next.h (additions, same
+ * version). */
 #define FSKHIP_ABI_VERSION 8
 #define FSKHIP_MAX_PATTERN_BYTES 16
 

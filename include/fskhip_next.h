@@ -228,6 +228,72 @@ int fskhip_processor_snapshot_info_get(const void *buf, size_t size, fskhip_proc
 int fskhip_processor_restore(fskhip_processor *dst, const void *buf, size_t size, const int64_t *map, uint32_t n_map);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The resident XModem receiver (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): XModemTransport's receive grammar run on the
+ * device over a processor's RX rings, in place.  fskhip_xmodem_scan_* judges a recorded burst and charges a packet cut by the
+ * burst's end as FSKHIP_XM_TRUNCATED; on a live line the rest of that packet arrives a quantum later.  A receiver keeps what a
+ * host would otherwise carry by hand between polls -- expectedSequence and the two running counters per stream -- takes only
+ * whole grammar steps out of the rings, and returns the accepted payloads plus one result record for every stream where
+ * something happened, in the compacted drain's CSR form.  Raw demodulated bytes do not cross to the host.  The control plane
+ * stays with the host: each record says which control bytes the reference would have sent (one ACK per accepted or duplicate
+ * packet, a NAK on an error status, the final ACK on FSKHIP_XM_EOT); retries and timeouts are the host's.
+ *
+ * State per stream, kept with this handle and NOT in the processor (its images and remaps do not carry it): `expected`
+ * (receive.expectedSequence, starts at 1), `packets` and `dropped` (running statistics.packetsReceived / packetsDropped, start
+ * at 0, counted as in fskhip_xmodem_result).  fskhip_xmodem_rx_reset is initializeReceive() (xmodem.ts:221-225) for one stream
+ * or all (stream < 0): expected = 1 and nothing else -- not the ring, not the counters; what a host calls after FSKHIP_XM_EOT.
+ * state_get / state_set carry the three arrays ([n_streams] each, any pointer may be NULL) across a remap or a restore with the
+ * host's own map; state_set wants every expected[] in 1..255, else FSKHIP_E_INVALID naming the first bad stream, nothing set.
+ * create, reset, state_get and state_set synchronise with the processor's outstanding work.  The processor must outlive every
+ * poll, reset and state call of the receiver; fskhip_xmodem_rx_destroy alone may follow the processor's destruction.
+ *
+ * One poll, for every SELECTED stream -- (mask == NULL || mask[s]) and a ring that holds at least one byte.  L = the live bytes,
+ * oldest first ([readIndex, readIndex + _length) modulo the capacity), e = expected[s], scan = fskhip_xmodem_scan_*'s grammar:
+ *   1. R = scan(L, e).
+ *   2. R.status == FSKHIP_XM_TRUNCATED -- an incomplete packet waits: with c the position of that packet's SOH (R.consumed - 1
+ *      before the three header bytes are in, R.consumed - 4 after), the result is R' = scan(L[:c], e) -- FSKHIP_XM_NEED_MORE,
+ *      consumed = c, error fields -1 -- and c bytes leave the ring: the packet stays at its front, SOH included, for a later
+ *      poll.  FSKHIP_XM_TRUNCATED is never reported by a poll.
+ *   3. R.status is INVALID_SEQUENCE, INVALID_CRC or UNEXPECTED_SEQUENCE -- an error ends the scan and clears the ring: R' = R
+ *      and all of L leaves (the reference's receive.buffer = [] before its NAK, xmodem.ts:256-259); R'.consumed keeps the
+ *      grammar's value, the end of the offending step.
+ *   4. otherwise (NEED_MORE or EOT) R' = R and R.consumed bytes leave; bytes behind an EOT stay in the ring.
+ *   5. the ring: readIndex advances by the bytes that leave, modulo the capacity, _length shrinks by them; writeIndex and the
+ *      ring bytes are untouched.  A stream that is not selected is not touched in any word.
+ *   6. the state: expected[s] = R'.expected_after; packets[s] += R'.packets; dropped[s] += R'.dropped.
+ *   7. the stream is LISTED when R'.status != FSKHIP_XM_NEED_MORE or R'.packets + R'.dropped > 0 -- when the host has
+ *      something to send.  A stream whose poll only swallowed line noise between packets is advanced but not listed.
+ * Output: the listed streams in ascending order in streams[0 .. n_events); results[i] = R' of streams[i]; offsets has
+ * n_events + 1 entries (the caller provides cap_streams + 1 words), offsets[n_events] = n_bytes; the assembled payload of
+ * streams[i] is data[offsets[i] .. offsets[i+1]) -- accepted packets only, in order, no duplicates, nothing of a packet whose
+ * CRC failed --, tightly packed.
+ * Overflow, as the compacted drain: if n_events > cap_streams or n_bytes > cap_bytes the call returns FSKHIP_E_OVERFLOW with
+ * the true sizes and changes NOTHING -- no ring word and no receiver state of any stream, swallowed noise included.  Both caps 0
+ * with null lists is therefore a size query.  _device is asynchronous on `hip_stream`, pointers on the processor's device;
+ * d_totals takes three words: n_events, n_bytes, and 1 if the poll was committed, 0 if it stood down (the lists are then
+ * undefined).  The handle keeps scratch: one poll at a time per handle.
+ * FSKHIP_E_INVALID before any device call, in this order: null n_events or n_bytes (_host) / null d_totals (_device); a null
+ * streams, results or offsets with cap_streams != 0; a null data with cap_bytes != 0; a null receiver.  create refuses a null
+ * processor or a null out.  FSKHIP_E_UNSUPPORTED when n_streams x rx_capacity exceeds 2^32 - 1.  A poll makes the processor a
+ * used one, as a drain does, and is never part of the captured quantum graph.  None of these calls returns -8.
+ * There is no minimum rx_capacity: a packet that cannot fit its ring waits at the ring's front until the ring's own
+ * overwrite-oldest rule pushes it out, exactly as RingBuffer.put would (utils.ts:38-48); rx_capacity >= 261 holds any packet.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct fskhip_xmodem_rx fskhip_xmodem_rx;
+
+int fskhip_xmodem_rx_create(fskhip_processor *p, fskhip_xmodem_rx **out);
+int fskhip_xmodem_rx_destroy(fskhip_xmodem_rx *r);
+int fskhip_xmodem_rx_reset(fskhip_xmodem_rx *r, int64_t stream);
+int fskhip_xmodem_rx_state_get(fskhip_xmodem_rx *r, uint32_t *expected, uint32_t *packets, uint32_t *dropped);
+int fskhip_xmodem_rx_state_set(fskhip_xmodem_rx *r, const uint32_t *expected, const uint32_t *packets,
+                               const uint32_t *dropped);
+int fskhip_xmodem_rx_poll_host(fskhip_xmodem_rx *r, const uint8_t *mask, uint32_t *streams, fskhip_xmodem_result *results,
+                               uint32_t *offsets, uint32_t cap_streams, uint8_t *data, size_t cap_bytes, uint32_t *n_events,
+                               uint32_t *n_bytes);
+int fskhip_xmodem_rx_poll_device(fskhip_xmodem_rx *r, const uint8_t *d_mask, uint32_t *d_streams,
+                                 fskhip_xmodem_result *d_results, uint32_t *d_offsets, uint32_t cap_streams, uint8_t *d_data,
+                                 size_t cap_bytes, uint32_t *d_totals, void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * FIR half of src/dsp/filters.ts: FIRFilter (112-167) batched over streams, and the windowed-sinc designs
  * (243-314) + FilterFactory.createFIR* (346-368).
  * ------------------------------------------------------------------------------------------------- */

@@ -13,6 +13,9 @@
 //   processorTxState(handle) -> {pos, total, pending, completed};  processorRxLength(handle) -> Uint32Array
 //   processorDrain(handle, capacity) -> {out, outPitch, counts};  processorReset(handle, stream)
 //   processorDrainSparse(handle, mask: Uint8Array|null, minLen) -> {streams: Uint32Array, offsets: Uint32Array, data: Uint8Array}
+//   xmodemRxCreate(processor) -> handle;  xmodemRxDestroy(handle);  xmodemRxReset(handle, stream)
+//   xmodemRxPoll(handle, mask: Uint8Array|null) -> {streams: Uint32Array, results: Int32Array[10*n], offsets: Uint32Array, data: Uint8Array}
+//   xmodemRxState(handle) -> {expected, packets, dropped: Uint32Array};  xmodemRxSetState(handle, expected|null, packets|null, dropped|null)
 //   processorRemap(dst, src, map: number[]);  processorSnapshot(handle, sel: number[]|null) -> Buffer
 //   processorRestore(dst, snapshot: Uint8Array, map: number[]);  processorSnapshotInfo(snapshot) -> {nStreams, rxCapacity, payloadCapacity, recordBytes}
 //   sincLowpass/sincHighpass(cutoff, sampleRate, numTaps), sincBandpass(center, bandwidth, sampleRate, numTaps) -> Float64Array
@@ -266,6 +269,113 @@ napi_value ProcessorReset(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// ---- the resident XModem receiver (include/fskhip_next.h: fskhip_xmodem_rx_*) over a processor handle.  The external owns a box, as
+// the filters' do: close() empties it, and a receiver that is never closed is destroyed with its handle (destroy does not read the processor)
+struct XmRx { fskhip_xmodem_rx *r; uint32_t S; };
+void xm_rx_finalize(napi_env, void *data, void *) {
+  XmRx *h = (XmRx *)data;
+  if (h->r) fskhip_xmodem_rx_destroy(h->r);
+  delete h;
+}
+XmRx *get_xm_rx(napi_env env, napi_value v) {
+  XmRx *h = (XmRx *)external(env, v, "receiver destroyed");
+  if (h && !h->r) { napi_throw_error(env, nullptr, "receiver destroyed"); return nullptr; }
+  return h;
+}
+napi_value XmodemRxCreate(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  Proc *p = get_proc(env, argv[0]);
+  if (!p) return nullptr;
+  fskhip_xmodem_rx *r = nullptr;
+  int rc = fskhip_xmodem_rx_create(p->p, &r);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  XmRx *h = new XmRx{r, p->S};
+  napi_value ext;
+  if (napi_create_external(env, h, xm_rx_finalize, nullptr, &ext) != napi_ok) { xm_rx_finalize(env, h, nullptr); napi_throw_error(env, nullptr, "xmodemRxCreate: no handle"); return nullptr; }
+  return ext;
+}
+napi_value XmodemRxDestroy(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  void *q = nullptr;
+  if (napi_get_value_external(env, argv[0], &q) == napi_ok && q) {
+    XmRx *h = (XmRx *)q;
+    if (h->r) fskhip_xmodem_rx_destroy(h->r);
+    h->r = nullptr;
+  }
+  return nullptr;
+}
+// sized with a query call (an overflowing poll changes nothing), then polled into arrays of exactly that size
+napi_value XmodemRxPoll(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  XmRx *h = get_xm_rx(env, argv[0]);
+  if (!h) return nullptr;
+  void *mask; size_t mlen;
+  if (!typed(env, argv[1], napi_uint8_array, &mask, &mlen, true)) return nullptr;
+  if (mask && mlen != h->S) { napi_throw_range_error(env, nullptr, "xmodemRxPoll: mask must have one entry per stream"); return nullptr; }
+  uint32_t n_events = 0, n_bytes = 0;
+  int rc = fskhip_xmodem_rx_poll_host(h->r, (const uint8_t *)mask, nullptr, nullptr, nullptr, 0, nullptr, 0, &n_events, &n_bytes);
+  if (rc != FSKHIP_OK && rc != FSKHIP_E_OVERFLOW) return throw_fsk(env, rc);
+  void *streams, *results, *offsets, *data;
+  napi_value str_v = make_typed(env, napi_uint32_array, n_events, 4, &streams);
+  napi_value res_v = make_typed(env, napi_int32_array, 10 * (size_t)n_events, 4, &results);
+  napi_value off_v = make_typed(env, napi_uint32_array, (size_t)n_events + 1, 4, &offsets);
+  napi_value dat_v = make_typed(env, napi_uint8_array, n_bytes, 1, &data);
+  if (!str_v || !res_v || !off_v || !dat_v) { napi_throw_error(env, nullptr, "xmodemRxPoll: out of memory"); return nullptr; }
+  if (rc == FSKHIP_E_OVERFLOW) {
+    rc = fskhip_xmodem_rx_poll_host(h->r, (const uint8_t *)mask, (uint32_t *)streams, (fskhip_xmodem_result *)results, (uint32_t *)offsets, n_events,
+                                    (uint8_t *)data, n_bytes, &n_events, &n_bytes);
+    if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  } else {
+    *(uint32_t *)offsets = 0u;
+  }
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "streams", str_v);
+  napi_set_named_property(env, o, "results", res_v);
+  napi_set_named_property(env, o, "offsets", off_v);
+  napi_set_named_property(env, o, "data", dat_v);
+  return o;
+}
+napi_value XmodemRxReset(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  XmRx *h = get_xm_rx(env, argv[0]);
+  if (!h) return nullptr;
+  int64_t s = -1;
+  napi_get_value_int64(env, argv[1], &s);
+  int rc = fskhip_xmodem_rx_reset(h->r, s);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+napi_value XmodemRxState(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  XmRx *h = get_xm_rx(env, argv[0]);
+  if (!h) return nullptr;
+  void *e, *p, *d;
+  napi_value e_v = make_typed(env, napi_uint32_array, h->S, 4, &e), p_v = make_typed(env, napi_uint32_array, h->S, 4, &p);
+  napi_value d_v = make_typed(env, napi_uint32_array, h->S, 4, &d);
+  int rc = fskhip_xmodem_rx_state_get(h->r, (uint32_t *)e, (uint32_t *)p, (uint32_t *)d);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "expected", e_v);
+  napi_set_named_property(env, o, "packets", p_v);
+  napi_set_named_property(env, o, "dropped", d_v);
+  return o;
+}
+napi_value XmodemRxSetState(napi_env env, napi_callback_info info) {
+  ARGS(4);
+  XmRx *h = get_xm_rx(env, argv[0]);
+  if (!h) return nullptr;
+  void *a[3]; size_t n[3];
+  for (int i = 0; i < 3; i++) {
+    if (!typed(env, argv[1 + i], napi_uint32_array, &a[i], &n[i], true)) return nullptr;
+    if (a[i] && n[i] != h->S) { napi_throw_range_error(env, nullptr, "xmodemRxSetState: state arrays must have one entry per stream"); return nullptr; }
+  }
+  int rc = fskhip_xmodem_rx_state_set(h->r, (const uint32_t *)a[0], (const uint32_t *)a[1], (const uint32_t *)a[2]);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+
 // ---- processor remap / snapshots (include/fskhip_next.h): a snapshot is a Buffer (or any Uint8Array) on this side
 napi_value ProcessorRemap(napi_env env, napi_callback_info info) {
   ARGS(3);
@@ -492,6 +602,12 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"processorDrain", nullptr, ProcessorDrain, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorDrainSparse", nullptr, ProcessorDrainSparse, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorReset", nullptr, ProcessorReset, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRxCreate", nullptr, XmodemRxCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRxDestroy", nullptr, XmodemRxDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRxPoll", nullptr, XmodemRxPoll, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRxReset", nullptr, XmodemRxReset, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRxState", nullptr, XmodemRxState, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRxSetState", nullptr, XmodemRxSetState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRemap", nullptr, ProcessorRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorSnapshot", nullptr, ProcessorSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRestore", nullptr, ProcessorRestore, nullptr, nullptr, nullptr, napi_default, nullptr},

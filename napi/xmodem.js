@@ -1,7 +1,8 @@
 'use strict';
 // CRC16 / XModemPacket / ControlType with the reference's surface (src/utils/crc16.ts, src/transports/xmodem/packet.ts,
 // types.ts), plus the batch forms and scanBursts -- the receive checks of XModemTransport (xmodem.ts:233-320) applied
-// to recorded bursts.  Everything that COMPUTES does so in libfskhip.so through the N-API addon (no JavaScript CRC here); the one
+// to recorded bursts -- and XModemReceiverBatch, the same grammar resident on the device over the RX rings of an
+// FSKProcessorBatch.  Everything that COMPUTES does so in libfskhip.so through the N-API addon (no JavaScript CRC here); the one
 // method that only lays bytes out is XModemPacket.serialize(packet): packet.ts:44-54 writes the fields of the packet OBJECT as
 // they are -- checksum included, whatever it holds (the reference's tests serialise packets with a wrong one) -- so it cannot go
 // through serializeBatch, which computes the CRC.
@@ -65,6 +66,9 @@ class XModemPacket {                            // packet.ts:17-66
 }
 
 // bursts: array of Uint8Array (what the demodulator returned per stream); expected: starting expectedSequence per stream
+const resultOf = (q) => ({ status: q[0], statusName: XM_STATUS[q[0]], error: XM_ERRORS[q[0]] || null, expectedAfter: q[1], packets: q[2], dropped: q[3],
+  consumed: q[4], errSeq: q[6], errLen: q[7], crcRx: q[8], crcCalc: q[9] });
+
 function scanBursts(bursts, expected, device = 0) {
   if (!bursts.length) return [];
   const p = packRows(bursts);
@@ -72,9 +76,56 @@ function scanBursts(bursts, expected, device = 0) {
   const r = addon.xmodemScan(p.slab, p.pitch, p.lens, exp, device);
   return bursts.map((_, i) => {
     const q = r.results.subarray(i * 10, i * 10 + 10);
-    return { status: q[0], statusName: XM_STATUS[q[0]], error: XM_ERRORS[q[0]] || null, expectedAfter: q[1], packets: q[2], dropped: q[3],
-      consumed: q[4], errSeq: q[6], errLen: q[7], crcRx: q[8], crcCalc: q[9], data: r.data.slice(i * r.dataPitch, i * r.dataPitch + q[5]) };
+    return Object.assign(resultOf(q), { data: r.data.slice(i * r.dataPitch, i * r.dataPitch + q[5]) });
   });
 }
 
-module.exports = { CRC16, XModemPacket, ControlType, PacketConstants, crc16Batch, serializeBatch, scanBursts };
+// The receive side of XModemTransport for every stream of an FSKProcessorBatch (fsk-processor.js), resident on the device
+// (fskhip_xmodem_rx_*).  poll() walks the RX rings in place and takes whole packets out of them; a packet that has only partly arrived
+// waits in its ring, an error clears the ring, bytes behind an EOT stay.  expectedSequence and the running packetsReceived /
+// packetsDropped live with this object.  Sending ACK / NAK, retries and timeouts are the caller's.  Close it before its processor.
+function stateArray(name, a, n) {
+  if (a === undefined || a === null) return null;
+  if (!Array.isArray(a) && !ArrayBuffer.isView(a)) throw new TypeError('setState: ' + name + ' must be an array of nStreams integers');
+  if (a.length !== n) throw new RangeError('setState: ' + name + ' must have one entry per stream (' + n + ')');
+  for (const v of a) if (!Number.isInteger(v) || v < 0 || v > 0xffffffff) throw new RangeError('setState: ' + name + ' must hold integers in [0, 2^32)');
+  return Uint32Array.from(a);
+}
+class XModemReceiverBatch {
+  constructor(processor) {
+    if (processor === null || typeof processor !== 'object' || !Number.isInteger(processor.nStreams)) throw new TypeError('XModemReceiverBatch: processor must be an FSKProcessorBatch');
+    this.processor = processor;
+    this.nStreams = processor.nStreams;
+    this.handle = addon.xmodemRxCreate(processor.handle);
+  }
+  close() { if (this.handle) { addon.xmodemRxDestroy(this.handle); this.handle = null; } }
+  // {streams, results, offsets, data}: the streams with an event in ascending order, one result each (scanBursts' fields, `data`
+  // the accepted payload of that stream), and the same payloads in CSR form: data.subarray(offsets[i], offsets[i + 1])
+  poll(options = {}) {
+    if (options === null || typeof options !== 'object') throw new TypeError('poll: options must be an object {mask}');
+    const { mask } = options;
+    let m = null;
+    if (mask !== undefined && mask !== null) {
+      if (!Array.isArray(mask) && !ArrayBuffer.isView(mask)) throw new TypeError('poll: mask must be an array of nStreams booleans');
+      if (mask.length !== this.nStreams) throw new RangeError('poll: mask must have one entry per stream (' + this.nStreams + ')');
+      m = Uint8Array.from(mask, (b) => (b ? 1 : 0));
+    }
+    const r = addon.xmodemRxPoll(this.handle, m);
+    const results = Array.from(r.streams, (_, i) =>
+      Object.assign(resultOf(r.results.subarray(i * 10, i * 10 + 10)), { data: r.data.slice(r.offsets[i], r.offsets[i + 1]) }));
+    return { streams: r.streams, results, offsets: r.offsets, data: r.data };
+  }
+  // initializeReceive() (xmodem.ts:221-225): expectedSequence = 1 for one stream, or all (-1)
+  reset(stream = -1) {
+    if (!Number.isInteger(stream)) throw new TypeError('reset: stream must be an integer (-1: all)');
+    addon.xmodemRxReset(this.handle, stream);
+  }
+  state() { return addon.xmodemRxState(this.handle); }                 // {expected, packets, dropped}: Uint32Array per stream
+  setState(state) {                                                     // what state() returned, or any part of it (expected: 1..255)
+    if (state === null || typeof state !== 'object') throw new TypeError('setState: state must be an object {expected, packets, dropped}');
+    const n = this.nStreams;
+    addon.xmodemRxSetState(this.handle, stateArray('expected', state.expected, n), stateArray('packets', state.packets, n), stateArray('dropped', state.dropped, n));
+  }
+}
+
+module.exports = { XModemReceiverBatch, CRC16, XModemPacket, ControlType, PacketConstants, crc16Batch, serializeBatch, scanBursts };

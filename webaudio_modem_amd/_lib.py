@@ -159,6 +159,13 @@ _SYMBOLS = [
     ("fskhip_processor_snapshot", C.c_int, [_P, _P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("fskhip_processor_snapshot_info_get", C.c_int, [_P, C.c_size_t, C.POINTER(ProcessorSnapshotInfo)]),
     ("fskhip_processor_restore", C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint32]),
+    ("fskhip_xmodem_rx_create", C.c_int, [_P, C.POINTER(_P)]),
+    ("fskhip_xmodem_rx_destroy", C.c_int, [_P]),
+    ("fskhip_xmodem_rx_reset", C.c_int, [_P, C.c_int64]),
+    ("fskhip_xmodem_rx_state_get", C.c_int, [_P, _P, _P, _P]),
+    ("fskhip_xmodem_rx_state_set", C.c_int, [_P, _P, _P, _P]),
+    ("fskhip_xmodem_rx_poll_host", C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, C.c_size_t, _P, _P]),
+    ("fskhip_xmodem_rx_poll_device", C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, C.c_size_t, _P, _P]),
     ("fskhip_sinc_lowpass", C.c_int, [C.c_double, C.c_double, C.c_uint32, _P]),
     ("fskhip_sinc_highpass", C.c_int, [C.c_double, C.c_double, C.c_uint32, _P]),
     ("fskhip_sinc_bandpass", C.c_int, [C.c_double, C.c_double, C.c_double, C.c_uint32, _P]),

@@ -21,6 +21,7 @@
 
 #include "fsk_launch.h"
 #include "fsk_params.h"
+#include "fsk_pick_dev.h"
 
 namespace fsk {
 
@@ -28,46 +29,13 @@ namespace {
 
 constexpr uint32_t kInFlight = 4;   // ring passes whose loads are issued before the first store
 
-struct SpanJob { uint32_t src, start, len, dst; };   // bytes [start, start + len) modulo the capacity of ring src -> data[dst ..]
-
-// inclusive prefix sum over the wave
-__device__ __forceinline__ uint32_t wave_scan(uint32_t x, uint32_t lane) {
-#pragma unroll
-  for (uint32_t o = 1; o < 64u; o <<= 1) {
-    const uint32_t t = (uint32_t)__shfl_up((int)x, o, 64);
-    if (lane >= o) x += t;
-  }
-  return x;
-}
-
-// What a lane learns about its stream s = blockIdx.x * 256 + threadIdx.x: whether it is selected, and where the workgroup's
-// selected streams / bytes before it end (pos_s, pos_b) out of the workgroup's totals (tot_s, tot_b).
-struct Pick {
-  bool sel;
-  uint32_t len, pos_s, pos_b, tot_s, tot_b;
-};
+// the drain's selection -- mask[s] and at least max(min_len, 1) bytes -- and byte count -- the whole ring content -- through the
+// shared in-workgroup scan (fsk_pick_dev.h)
 __device__ __forceinline__ Pick pick_and_scan(const uint32_t *__restrict__ rx_len, const uint8_t *__restrict__ mask, uint32_t n_streams, uint32_t min_len,
                                               uint32_t (*ws)[2]) {
-  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-  Pick P;
-  P.len = s < n_streams ? rx_len[s] : 0u;
-  P.sel = s < n_streams && P.len >= max(min_len, 1u) && (!mask || mask[s] != 0);
-  const uint32_t b = P.sel ? P.len : 0u;
-  const uint64_t vote = __builtin_amdgcn_ballot_w64(P.sel);
-  const uint32_t incl = wave_scan(b, lane);
-  if (lane == 63u) { ws[wv][0] = (uint32_t)__builtin_popcountll(vote); ws[wv][1] = incl; }
-  __syncthreads();
-  P.pos_s = (uint32_t)__builtin_popcountll(vote & ((1ull << lane) - 1ull));
-  P.pos_b = incl - b;
-  P.tot_s = 0u; P.tot_b = 0u;
-#pragma unroll
-  for (uint32_t w = 0; w < 4u; w++) {
-    const uint32_t cs = ws[w][0], cb = ws[w][1];
-    if (w < wv) { P.pos_s += cs; P.pos_b += cb; }
-    P.tot_s += cs; P.tot_b += cb;
-  }
-  return P;
+  const uint32_t len = s < n_streams ? rx_len[s] : 0u;
+  return pick_scan(s < n_streams && len >= max(min_len, 1u) && (!mask || mask[s] != 0), len, ws);
 }
 
 __global__ __launch_bounds__(256) void drain_count_kernel(const uint32_t *__restrict__ rx_len, const uint8_t *__restrict__ mask, uint32_t n_streams,
@@ -104,12 +72,6 @@ __global__ __launch_bounds__(256) void drain_scan_kernel(uint2 *__restrict__ pai
     totals[1] = carry_b;
     totals[2] = carry_s <= cap_streams && (uint64_t)carry_b <= cap_bytes ? 1u : 0u;
   }
-}
-
-__device__ __forceinline__ uint32_t lanes_per_span(uint32_t longest) {
-  uint32_t l = 1u;
-  while (l < longest && l < 64u) l <<= 1;
-  return l;
 }
 
 __global__ __launch_bounds__(256) void drain_pack_kernel(ProcState T, const uint8_t *__restrict__ mask, uint32_t n_streams, uint32_t min_len,
@@ -175,6 +137,11 @@ uint32_t groups_of(uint32_t n_streams) { return n_streams ? (n_streams + 255u) /
 
 }  // namespace
 
+hipError_t launch_drain_totals(uint32_t *d_pairs, uint32_t n_pairs, uint32_t cap_streams, uint64_t cap_bytes, uint32_t *d_totals, hipStream_t st) {
+  hipLaunchKernelGGL(drain_scan_kernel, dim3(1), dim3(256), 0, st, (uint2 *)d_pairs, n_pairs, cap_streams, cap_bytes, d_totals);
+  return hipGetLastError();
+}
+
 size_t drain_sparse_pair_words(uint32_t n_streams) { return 2u * (size_t)groups_of(n_streams); }
 
 hipError_t launch_drain_sparse_size(const ProcState &T, uint32_t n_streams, const uint8_t *d_mask, uint32_t min_len, uint32_t cap_streams, uint64_t cap_bytes,
@@ -183,8 +150,7 @@ hipError_t launch_drain_sparse_size(const ProcState &T, uint32_t n_streams, cons
   hipLaunchKernelGGL(drain_count_kernel, dim3(groups), dim3(256), 0, st, T.rx_len, d_mask, n_streams, min_len, (uint2 *)d_pairs);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(drain_scan_kernel, dim3(1), dim3(256), 0, st, (uint2 *)d_pairs, groups, cap_streams, cap_bytes, d_totals);
-  return hipGetLastError();
+  return launch_drain_totals(d_pairs, groups, cap_streams, cap_bytes, d_totals, st);
 }
 
 hipError_t launch_drain_sparse_pack(const ProcState &T, uint32_t n_streams, const uint8_t *d_mask, uint32_t min_len, const uint32_t *d_pairs,

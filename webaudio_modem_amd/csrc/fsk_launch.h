@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/fskhip_next.h"
 #include "fsk_newstream.h"
 #include "fsk_params.h"
 
@@ -120,9 +121,24 @@ hipError_t launch_processor_max_payload(const ProcState &S, const int64_t *d_idx
 // size: count + scan -- d_pairs (drain_sparse_pair_words(n_streams) words of scratch) takes each workgroup's exclusive
 // {stream, byte} position, d_totals {n_active, n_bytes, 1 if both fit the caps else 0}.
 // pack: given those, and only where d_totals[2] is 1, writes the lists and the bytes and advances the selected rings.
+// totals: the scan half on its own, for any list of n_pairs workgroup pairs (the resident XModem receiver reduces its own).
 size_t drain_sparse_pair_words(uint32_t n_streams);
+hipError_t launch_drain_totals(uint32_t *d_pairs, uint32_t n_pairs, uint32_t cap_streams, uint64_t cap_bytes, uint32_t *d_totals, hipStream_t st);
 hipError_t launch_drain_sparse_size(const ProcState &T, uint32_t n_streams, const uint8_t *d_mask, uint32_t min_len, uint32_t cap_streams, uint64_t cap_bytes,
                                     uint32_t *d_pairs, uint32_t *d_totals, hipStream_t st);
 hipError_t launch_drain_sparse_pack(const ProcState &T, uint32_t n_streams, const uint8_t *d_mask, uint32_t min_len, const uint32_t *d_pairs,
                                     const uint32_t *d_totals, uint32_t *d_streams, uint32_t *d_offsets, uint8_t *d_data, hipStream_t st);
+// fsk_xmodem_rx.hip: the resident XModem receiver (fskhip_xmodem_rx_poll_*).  The caller has checked the arguments.
+// XmRxState: the receiver's per-stream state.  XmRxScratch: per stream the poll's result R', the bytes to take out of the ring and
+// two flag bits; xmodem_rx_pair_words(n_streams) words of workgroup pairs.
+// scan: walks the selected rings, fills the scratch and nothing else, then the totals {n_events, n_bytes, 1 if both fit the caps}.
+// commit: given those, and only where d_totals[2] is 1, writes the lists, the results and the payloads, advances the rings and
+// updates the state.
+struct XmRxState { uint32_t *expected, *packets, *dropped; };
+struct XmRxScratch { fskhip_xmodem_result *res; uint32_t *removed, *flags, *pairs; };
+size_t xmodem_rx_pair_words(uint32_t n_streams);
+hipError_t launch_xmodem_rx_scan(const ProcState &T, uint32_t n_streams, const uint8_t *d_mask, const XmRxState &X, const XmRxScratch &W, uint32_t cap_streams,
+                                 uint64_t cap_bytes, uint32_t *d_totals, hipStream_t st);
+hipError_t launch_xmodem_rx_commit(const ProcState &T, uint32_t n_streams, const XmRxState &X, const XmRxScratch &W, const uint32_t *d_totals, uint32_t *d_streams,
+                                   fskhip_xmodem_result *d_results, uint32_t *d_offsets, uint8_t *d_data, hipStream_t st);
 }  // namespace fsk

@@ -10,26 +10,19 @@
 #include <vector>
 
 #include "fsk_host.h"
+#include "fsk_xmodem_scan.h"
 
 namespace fsk {
 namespace {
 
-constexpr uint32_t kSOH = 0x01, kEOT = 0x04;  // types.ts:29-34
+using namespace xm;   // the receive grammar and the CRC step: fsk_xmodem_scan.h
+
 constexpr int kBlock = 256;
 
-// table[i] = CRC of the single byte i from a zero register: the 8 shift/xor steps of crc16.ts:25-33
+// the workgroup's copy of the CRC table (fsk_xmodem_scan.h: crc_table_entry)
 __device__ __forceinline__ void build_crc_table(uint32_t *table) {
-  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) {
-    uint32_t c = i << 8;
-#pragma unroll
-    for (int k = 0; k < 8; k++) c = (c & 0x8000u) ? ((c << 1) ^ 0x1021u) : (c << 1);
-    table[i] = c & 0xFFFFu;
-  }
+  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) table[i] = crc_table_entry(i);
   __syncthreads();
-}
-// crc ^= byte << 8, then 8 steps == one table step on the high byte
-__device__ __forceinline__ uint32_t crc_step(const uint32_t *table, uint32_t crc, uint32_t byte) {
-  return ((crc << 8) & 0xFFFFu) ^ table[((crc >> 8) ^ byte) & 0xFFu];
 }
 
 // Sequential byte reader over one row: a dword at a time when the row is 4-byte aligned.
@@ -93,153 +86,6 @@ __global__ __launch_bounds__(kBlock) void serialize_kernel(const uint8_t *payloa
   o[5 + len] = (uint8_t)(crc & 0xFFu);
   out_lens[r] = len + 6;
 }
-
-// per-byte state machine of the receive grammar; every lane walks its own burst front to back
-enum : uint32_t { ST_IDLE, ST_SEQ, ST_NSEQ, ST_LEN, ST_PAYLOAD, ST_CRC_HI, ST_CRC_LO, ST_DONE };
-
-struct Scan {
-  uint32_t state, status, expected;
-  uint32_t seq, nseq, len, k, crc, rx, start;
-  uint32_t packets, dropped, consumed, data_len;
-  int32_t err_seq, err_len, crc_rx, crc_calc;
-  bool accept;
-  uint32_t word;  // payload bytes on their way to data[]: stored a dword at a time where the row allows it
-
-  __device__ __forceinline__ void init(uint32_t expected_seq) {
-    state = ST_IDLE; status = FSKHIP_XM_NEED_MORE; expected = expected_seq;
-    seq = nseq = len = k = crc = rx = start = 0;
-    packets = dropped = consumed = data_len = 0;
-    err_seq = err_len = crc_rx = crc_calc = -1;
-    accept = false;
-    word = 0;
-  }
-
-  // assembleData (xmodem.ts:322-333): byte `off` of the stream's assembled payload.  Tentative until the packet's CRC
-  // has matched -- only data[0 .. data_len) is meaningful afterwards.  With a 4-byte aligned row the bytes are merged
-  // into dwords (one store per 4 bytes); a partial dword is flushed bytewise when its packet ends.
-  template <bool DW>
-  __device__ __forceinline__ void put(uint8_t *drow, size_t data_pitch, uint32_t off, uint32_t b, bool last) {
-    if (!drow || (size_t)off >= data_pitch) return;
-    if (!DW) { drow[off] = (uint8_t)b; return; }
-    const uint32_t sh = (off & 3u) * 8u;
-    word = (word & ~(0xFFu << sh)) | (b << sh);
-    if ((off & 3u) == 3u && (size_t)off < data_pitch) {
-      // full dword: bytes before this packet's first byte inside it were written by an earlier flush and are in `word`
-      *reinterpret_cast<uint32_t *>(drow + (off & ~3u)) = word;
-    } else if (last) {
-      for (uint32_t q = off & ~3u; q <= off; q++) drow[q] = (uint8_t)(word >> ((q & 3u) * 8u));
-    }
-  }
-
-  template <bool DW>
-  __device__ __forceinline__ void byte(const uint32_t *table, uint32_t b, uint32_t pos, uint8_t *drow, size_t data_pitch) {
-    switch (state) {
-      case ST_IDLE:  // xmodem.ts:238-252
-        if (b == kEOT) {
-          status = FSKHIP_XM_EOT;
-          state = ST_DONE;
-        } else if (b == kSOH) {
-          start = pos;
-          state = ST_SEQ;
-        }
-        consumed = pos + 1;
-        break;
-      case ST_SEQ:
-        seq = b;
-        state = ST_NSEQ;
-        break;
-      case ST_NSEQ:
-        nseq = b;
-        state = ST_LEN;
-        break;
-      case ST_LEN: {  // xmodem.ts:266-274, 278, 309, 315
-        len = b;
-        const uint32_t prev = expected == 1 ? 255u : expected - 1;
-        if (seq + nseq != 255u) {
-          status = FSKHIP_XM_INVALID_SEQUENCE;
-        } else if (seq == expected) {
-          accept = true;
-        } else if (seq == prev) {
-          accept = false;
-        } else {
-          status = FSKHIP_XM_UNEXPECTED_SEQUENCE;
-        }
-        if (status != FSKHIP_XM_NEED_MORE) {
-          err_seq = (int32_t)seq;
-          err_len = (int32_t)len;
-          dropped++;
-          consumed = pos + 1;
-          state = ST_DONE;
-        } else {
-          k = 0;
-          crc = 0xFFFFu;
-          state = len ? ST_PAYLOAD : ST_CRC_HI;
-        }
-        break;
-      }
-      case ST_PAYLOAD:
-        if (accept) {
-          put<DW>(drow, data_pitch, data_len + k, b, k + 1 == len);
-          crc = crc_step(table, crc, b);
-        }
-        if (++k == len) state = ST_CRC_HI;
-        break;
-      case ST_CRC_HI:
-        rx = b << 8;
-        state = ST_CRC_LO;
-        break;
-      case ST_CRC_LO:
-        rx |= b;
-        consumed = pos + 1;
-        state = ST_IDLE;
-        if (accept) {
-          packets++;        // statistics.packetsReceived: counted once the payload is in, before the CRC check (xmodem.ts:280)
-          if (rx != crc) {  // xmodem.ts:287-291
-            status = FSKHIP_XM_INVALID_CRC;
-            err_seq = (int32_t)seq;
-            err_len = (int32_t)len;
-            crc_rx = (int32_t)rx;
-            crc_calc = (int32_t)crc;
-            dropped++;
-            state = ST_DONE;
-          } else {  // xmodem.ts:293-303
-            data_len += len;
-            expected = (expected % 255u) + 1;
-          }
-        } else {
-          dropped++;  // duplicate: consumed and ignored (xmodem.ts:309-314)
-        }
-        break;
-      default:
-        break;
-    }
-  }
-
-  __device__ __forceinline__ void finish(fskhip_xmodem_result *out) {
-    if (state != ST_IDLE && state != ST_DONE) {  // ran out of bytes inside a packet (the reference's wait times out)
-      status = FSKHIP_XM_TRUNCATED;
-      // what waitForBytes has taken out of the receive buffer by then (xmodem.ts:475-499): SOH, and the three header
-      // bytes once they were all there -- pinned to the real XModemTransport by tests/golden/manifest_next.json
-      consumed = state >= ST_PAYLOAD ? start + 4u : start + 1u;
-      if (state >= ST_PAYLOAD) {
-        err_seq = (int32_t)seq;
-        err_len = (int32_t)len;
-      }
-    }
-    fskhip_xmodem_result r;
-    r.status = status;
-    r.expected_after = expected;
-    r.packets = packets;
-    r.dropped = dropped;
-    r.consumed = consumed;
-    r.data_len = data_len;
-    r.err_seq = err_seq;
-    r.err_len = err_len;
-    r.crc_rx = crc_rx;
-    r.crc_calc = crc_calc;
-    *out = r;
-  }
-};
 
 // any layout: every lane walks its own row
 template <bool ALIGNED>

@@ -1,7 +1,8 @@
 """CRC-16 and XModem packets above the C ABI (include/fskhip_next.h): the reference's `CRC16`
 (src/utils/crc16.ts) and `XModemPacket` (src/transports/xmodem/packet.ts) with the same names, argument meaning
 and error texts, plus the batch forms that actually feed a GPU and `scan_bursts`, the receive checks of
-XModemTransport (src/transports/xmodem/xmodem.ts:233-320) applied to the bytes a demodulate call returned.
+XModemTransport (src/transports/xmodem/xmodem.ts:233-320) applied to the bytes a demodulate call returned; and
+`XModemReceiverBatch`, the same grammar resident on the device over the RX rings of an `FSKProcessorBatch`.
 Everything computes in libfskhip.so; there is no CPU path here.
 """
 import ctypes as C
@@ -133,3 +134,91 @@ def scan_bursts(bursts, expected, device=0, data_pitch=None):
         d["data"] = data[i, :d["data_len"]].tobytes()
         out.append(d)
     return out
+
+
+# fskhip_xmodem_result as a numpy record: the ten words, in order
+RESULT_DTYPE = np.dtype([(k, "<u4" if t is C.c_uint32 else "<i4") for k, t in XModemResult._fields_])
+
+
+class XModemReceiverBatch:
+    """The receive side of XModemTransport for every stream of an FSKProcessorBatch, resident on the device
+    (fskhip_xmodem_rx_*): a poll walks the RX rings in place, takes whole packets out of them and returns the accepted
+    payloads and one result record per stream with something to answer -- an incomplete packet waits in its ring for
+    the next poll.  expectedSequence and the running packetsReceived / packetsDropped live with this object.  Sending
+    ACK / NAK, retries and timeouts are the caller's.  The processor must outlive it."""
+
+    def __init__(self, processor):
+        self.processor = processor
+        self._L = _lib.lib()
+        self.n_streams = processor.n_streams
+        h = C.c_void_p()
+        _lib.check(self._L.fskhip_xmodem_rx_create(processor._h, C.byref(h)))
+        self._h = h
+        self._cap_streams, self._cap_bytes = 0, 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.fskhip_xmodem_rx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def poll(self, mask=None):
+        """(streams, results, offsets, data): the streams with an event, ascending (uint32); their result records
+        (RESULT_DTYPE); CSR offsets (uint32, len(streams) + 1); the accepted payload bytes (uint8) -- those of streams[i]
+        are data[offsets[i]:offsets[i + 1]].  The lists are sized to the last poll's and grown on overflow: an
+        overflowing call changes nothing and reports the true sizes."""
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8)
+        if m is not None and m.shape != (self.n_streams,):
+            raise ValueError("mask must have one entry per stream")
+        m_p = None if m is None else m.ctypes.data
+        ne, nb = C.c_uint32(0), C.c_uint32(0)
+        while True:
+            cs, cb = self._cap_streams, self._cap_bytes
+            streams, offsets = np.zeros(cs, np.uint32), np.zeros(cs + 1, np.uint32)
+            results, data = np.zeros(cs, RESULT_DTYPE), np.zeros(cb, np.uint8)
+            rc = self._L.fskhip_xmodem_rx_poll_host(self._h, m_p, streams.ctypes.data if cs else None, results.ctypes.data if cs else None,
+                                                    offsets.ctypes.data if cs else None, cs, data.ctypes.data if cb else None, cb,
+                                                    C.byref(ne), C.byref(nb))
+            if rc != _lib.E_OVERFLOW:
+                _lib.check(rc)
+                break
+            self._cap_streams, self._cap_bytes = max(cs, ne.value), max(cb, nb.value)
+        n = ne.value
+        return streams[:n], results[:n], offsets[:n + 1], data[:nb.value]
+
+    def poll_active(self, mask=None):
+        """{stream: (result dict, payload bytes)} of one poll; the dict has scan_bursts' keys"""
+        streams, results, offsets, data = self.poll(mask)
+        out = {}
+        for i, s in enumerate(streams):
+            d = {k: int(results[i][k]) for k in RESULT_DTYPE.names}
+            d["status_name"] = STATUS_NAMES[d["status"]]
+            d["error"] = STATUS_ERRORS.get(d["status"])
+            out[int(s)] = (d, data[offsets[i]:offsets[i + 1]].tobytes())
+        return out
+
+    def reset(self, stream=-1):
+        """initializeReceive() (xmodem.ts:221-225): expectedSequence = 1 for one stream, or all"""
+        _lib.check(self._L.fskhip_xmodem_rx_reset(self._h, int(stream)))
+
+    def state(self):
+        """{"expected", "packets", "dropped"}: uint32 arrays, one entry per stream"""
+        out = {k: np.zeros(self.n_streams, np.uint32) for k in ("expected", "packets", "dropped")}
+        _lib.check(self._L.fskhip_xmodem_rx_state_get(self._h, out["expected"].ctypes.data, out["packets"].ctypes.data, out["dropped"].ctypes.data))
+        return out
+
+    def set_state(self, expected=None, packets=None, dropped=None):
+        """what state() returned, or any part of it (expected: 1..255)"""
+        arrs = []
+        for a in (expected, packets, dropped):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.uint32)
+                if a.shape != (self.n_streams,):
+                    raise ValueError("state arrays must have one entry per stream")
+            arrs.append(a)
+        _lib.check(self._L.fskhip_xmodem_rx_state_set(self._h, *[None if a is None else a.ctypes.data for a in arrs]))
