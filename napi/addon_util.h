@@ -6,6 +6,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "../include/fskhip.h"
@@ -69,6 +70,21 @@ static inline bool typed(napi_env env, napi_value v, napi_typedarray_type want, 
     return false;
   }
   return true;
+}
+
+// the capture formats (FSKHIP_SAMPLES_* / FSKHIP_LAYOUT_*): whether the pair is one (throws a TypeError where not), the typed array
+// a format's samples come in, and the fill of a fresh G.711 array with the format's silence (the other formats' is the zero
+// a fresh array holds)
+static inline bool sample_format_ok(napi_env env, int32_t format, int32_t layout) {
+  if (fskhip_sample_bytes(format) && (layout == FSKHIP_LAYOUT_STREAM_MAJOR || layout == FSKHIP_LAYOUT_SAMPLE_MAJOR)) return true;
+  napi_throw_type_error(env, nullptr, "unknown sample format or layout");
+  return false;
+}
+static inline napi_typedarray_type sample_array_type(int32_t format) {
+  return format == FSKHIP_SAMPLES_F32 ? napi_float32_array : format == FSKHIP_SAMPLES_S16 ? napi_int16_array : napi_uint8_array;
+}
+static inline void fill_silence(int32_t format, void *out, size_t count) {
+  if (format == FSKHIP_SAMPLES_MULAW || format == FSKHIP_SAMPLES_ALAW) memset(out, format == FSKHIP_SAMPLES_MULAW ? 0xFF : 0xD5, count);
 }
 
 // an Array of integers; throws `what` as a TypeError when it is no Array, `what_entry` (default: `what`) at an entry that is no integer

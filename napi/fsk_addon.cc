@@ -177,12 +177,8 @@ static DemodCall *demod_prepare(napi_env env, napi_callback_info info, DemodCall
   if (fmt) {
     c->format = i32(env, argv[2]); c->layout = i32(env, argv[3]);
     c->n = u32(env, argv[4]); c->pitch = u32(env, argv[5]);
-    const napi_typedarray_type want = c->format == FSKHIP_SAMPLES_F32 ? napi_float32_array : c->format == FSKHIP_SAMPLES_S16 ? napi_int16_array : napi_uint8_array;
-    if (!fskhip_sample_bytes(c->format) || (c->layout != FSKHIP_LAYOUT_STREAM_MAJOR && c->layout != FSKHIP_LAYOUT_SAMPLE_MAJOR)) {
-      napi_throw_type_error(env, nullptr, "unknown sample format or layout");
-      return nullptr;
-    }
-    if (tt != want) { napi_throw_type_error(env, nullptr, "samples must be the format's typed array: Float32Array, Int16Array or (G.711) Uint8Array"); return nullptr; }
+    if (!sample_format_ok(env, c->format, c->layout)) return nullptr;
+    if (tt != sample_array_type(c->format)) { napi_throw_type_error(env, nullptr, "samples must be the format's typed array: Float32Array, Int16Array or (G.711) Uint8Array"); return nullptr; }
   } else {
     if (tt != napi_float32_array) { napi_throw_type_error(env, nullptr, "samples must be a Float32Array"); return nullptr; }
     c->n = u32(env, argv[2]); c->pitch = u32(env, argv[3]); c->flags = u32(env, argv[4]);
@@ -349,12 +345,9 @@ static napi_value ModulateSamples(napi_env env, napi_callback_info info) {
   const uint32_t n = u32(env, argv[6]), pitch = u32(env, argv[7]);
   const uint32_t S = fskhip_n_streams(e);
   if (llen < S || plen < (size_t)ppitch * S) { napi_throw_range_error(env, nullptr, "payloads/lens too short"); return nullptr; }
+  if (!sample_format_ok(env, format, layout)) return nullptr;
   const size_t esz = fskhip_sample_bytes(format);
-  if (!esz || (layout != FSKHIP_LAYOUT_STREAM_MAJOR && layout != FSKHIP_LAYOUT_SAMPLE_MAJOR)) {
-    napi_throw_type_error(env, nullptr, "unknown sample format or layout");
-    return nullptr;
-  }
-  const napi_typedarray_type want = format == FSKHIP_SAMPLES_F32 ? napi_float32_array : format == FSKHIP_SAMPLES_S16 ? napi_int16_array : napi_uint8_array;
+  const napi_typedarray_type want = sample_array_type(format);
   // the last row (stream-major) / the last frame (sample-major) may end with its own samples
   const bool frames = layout == FSKHIP_LAYOUT_SAMPLE_MAJOR;
   const size_t rows = frames ? n : S, cols = frames ? S : n;
@@ -364,8 +357,7 @@ static napi_value ModulateSamples(napi_env env, napi_callback_info info) {
     if (pitch < cols) { napi_throw_range_error(env, nullptr, "samples too short"); return nullptr; }
     out_v = make_typed(env, want, need, esz, &out);
     if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
-    if (format == FSKHIP_SAMPLES_MULAW || format == FSKHIP_SAMPLES_ALAW)   // (the pitch's padding: silence, like the rest)
-      memset(out, format == FSKHIP_SAMPLES_MULAW ? 0xFF : 0xD5, need);
+    fill_silence(format, out, need);   // (the pitch's padding: silence, like the rest)
   } else {
     NAPI_OK(napi_get_typedarray_info(env, argv[8], &tt, &olen, &out, nullptr, nullptr));
     if (tt != want) { napi_throw_type_error(env, nullptr, "samples must be the format's typed array: Float32Array, Int16Array or (G.711) Uint8Array"); return nullptr; }

@@ -1,5 +1,5 @@
 """The encode direction of the capture formats without a GPU (include/fskhip.h: fskhip_egress_device, fskhip_modulate_host_fmt): the
-numpy reference the GPU tests use (tests/egress_ref.py) against Python's audioop for every 16-bit value, the fixed point through the
+numpy reference the GPU tests use (tests/samples_ref.py) against Python's audioop for every 16-bit value, the fixed point through the
 decoders for every code, the s16 rule at its edges, the staging geometry of the host call (csrc/fsk_plan.h: egress_stage, compiled
 here with g++), the Python argument checks and -- with no device -- the loud failure of the compute entry points."""
 import os
@@ -9,8 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
-import egress_ref as er
-import ingest_ref as ir
+import samples_ref as er
+import samples_ref as ir
 
 from conftest import ROOT
 

@@ -1,24 +1,24 @@
 """The encode direction of the capture formats on the GPU (include/fskhip.h: fskhip_egress_device, fskhip_modulate_host_fmt;
-csrc/fsk_egress.hip).
+csrc/fsk_samples.hip).
 
-  * the egress kernel against numpy (tests/egress_ref.py, held against audioop in test_egress_cpu.py), BIT FOR BIT, for every format x
+  * the egress kernel against numpy (tests/samples_ref.py, held against audioop in test_egress_cpu.py), BIT FOR BIT, for every format x
     layout: every value k / 32768, the rounding ties, the edges of the float range, stream counts and lengths around the 64 x 64 tile,
     the 16-byte vector and the per-workgroup span, every destination offset within 16 bytes, every source offset within a float4,
     pitches wider than the rows, with and without ragged per-stream lengths -- and the whole destination compared, sentinels
     included: nothing else is written;
-  * FSKEngine.modulate_samples == egress_ref.encode of what fskhip_modulate_host returns, silence from lens[s] on, fp32 and fp64
+  * FSKEngine.modulate_samples == samples_ref.encode of what fskhip_modulate_host returns, silence from lens[s] on, fp32 and fp64
     engines, ragged payloads, one, two and three 64-stream groups; the overflow refusal;
   * the round trip modulate_samples -> demodulate_samples through every trunk format and layout;
   * two engines writing their column blocks of one array of interleaved frames."""
 import numpy as np
 import pytest
 
-import egress_ref as er
+import samples_ref as er
 
 pytestmark = [pytest.mark.gpu]
 
 BELL = dict(baudRate=1200, markFrequency=1200, spaceFrequency=2200)
-SPAN = 8192                                   # elements of a row per workgroup of the stream-major kernel (csrc/fsk_egress.hip: kEgressSpan)
+SPAN = 8192                                   # elements of a row per workgroup of the stream-major kernel (csrc/fsk_samples.hip: kEgressSpan)
 STREAMS = (1, 63, 64, 65, 130)
 LENGTHS = (1, 3, 4, 5, 15, 16, 17, 63, 64, 65, SPAN + 7)
 CORE = {(S, n) for S in (1, 65) for n in (5, 17, 65, SPAN + 7)}   # shapes that take EVERY destination offset x source offset
@@ -230,7 +230,7 @@ def _payload(s):
 @pytest.mark.parametrize("fmt", ["s16", "mulaw", "alaw"])
 def test_round_trip_through_the_trunk_formats(fmt, layout):
     """Bell 202 at 48 kHz, 65 streams, one 16-byte frame each, no stream excused.  The payload list was fixed after running the same
-    chain on the CPU: oracle.pyoracle modulate -> egress_ref.encode -> ingest_ref.decode -> oracle demodulate returns every one of
+    chain on the CPU: oracle.pyoracle modulate -> samples_ref.encode -> samples_ref.decode -> oracle demodulate returns every one of
     these 65 payloads exactly through s16, mu-law and A-law (and f32), with the signal as modulateData returns it and with 1000
     further samples of encoded silence behind it; none had to be dropped."""
     wm = _wm()

@@ -1,6 +1,6 @@
-"""Capture formats on the GPU (include/fskhip.h: fskhip_ingest_device, fskhip_demodulate_host_fmt; csrc/fsk_ingest.hip).
+"""Capture formats on the GPU (include/fskhip.h: fskhip_ingest_device, fskhip_demodulate_host_fmt; csrc/fsk_samples.hip).
 
-  * the ingest kernel against numpy (tests/ingest_ref.py, held against audioop in test_ingest_cpu.py), BIT FOR BIT -- every value is
+  * the ingest kernel against numpy (tests/samples_ref.py, held against audioop in test_ingest_cpu.py), BIT FOR BIT -- every value is
     an integer of at most 16 bits times 2^-15, exact in float32 -- for every format x layout, stream counts and lengths around
     the 64 x 64 tile and the four-element quad, every source and destination alignment, pitches that are no multiple of four;
     and nothing written outside [0, n) of a row;
@@ -12,7 +12,7 @@
 import numpy as np
 import pytest
 
-import ingest_ref as ir
+import samples_ref as ir
 
 pytestmark = [pytest.mark.gpu]
 
@@ -21,6 +21,8 @@ MARGIN = 8                         # floats in front of and behind the destinati
 BELL = dict(baudRate=1200, markFrequency=1200, spaceFrequency=2200)
 STREAMS = (1, 3, 64, 65, 130)
 LENGTHS = (0, 1, 3, 15, 16, 17, 63, 64, 65, 257)
+CHUNK = 4096                       # samples of a row per workgroup of the stream-major kernel (csrc/fsk_samples.hip: kIngestChunk)
+LONG_STREAMS = (1, 3)              # the batches that also take rows of CHUNK + 7 samples, stream-major: workgroups c > 0 at every alignment
 
 
 def _wm():
@@ -88,7 +90,7 @@ def test_ingest_kernel_bit_for_bit(eng, fmt, layout):
     launches = 0
     try:
         for S in STREAMS:
-            for n in LENGTHS:
+            for n in LENGTHS + ((CHUNK + 7,) if layout == "stream" and S in LONG_STREAMS else ()):
                 # pitches that are no multiple of four, and 16-element-aligned ones (every row on the wide path when the offsets are 0)
                 for src_pitch, dst_pitch in (((n + 1) if layout == "stream" else (S + 2), n + 1),
                                              (((n + 15) & ~15) if layout == "stream" else ((S + 15) & ~15), max((n + 3) & ~3, 4))):
@@ -106,7 +108,7 @@ def test_ingest_kernel_bit_for_bit(eng, fmt, layout):
                             launches += 1
     finally:
         dev.close()
-    assert launches == len(STREAMS) * len(LENGTHS) * 2 * 16
+    assert launches == (len(STREAMS) * len(LENGTHS) + (len(LONG_STREAMS) if layout == "stream" else 0)) * 2 * 16
 
 
 @pytest.mark.parametrize("layout", ["stream", "sample"])

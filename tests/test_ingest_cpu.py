@@ -1,12 +1,12 @@
 """Capture formats without a GPU (include/fskhip.h: fskhip_sample_bytes, fskhip_ingest_device, fskhip_demodulate_host_fmt): the element
-sizes, the numpy decode reference the GPU tests use (tests/ingest_ref.py) against Python's audioop for every code, the argument
+sizes, the numpy decode reference the GPU tests use (tests/samples_ref.py) against Python's audioop for every code, the argument
 checks that need no device, and -- with no device -- the loud failure of the two compute entry points."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import ingest_ref as ir
+import samples_ref as ir
 
 
 @pytest.fixture(scope="module")

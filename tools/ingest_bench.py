@@ -66,7 +66,7 @@ class Hip:
 
 
 def host_rows(a, wm, emit):
-    import ingest_ref as ir
+    import samples_ref as ir
     from webaudio_modem_amd import _lib
     L = _lib.lib()
     S, N = a.host_streams, a.samples
@@ -131,7 +131,7 @@ def host_rows(a, wm, emit):
 
 
 def kernel_rows(a, wm, emit):
-    import ingest_ref as ir
+    import samples_ref as ir
     hip = Hip()
     S, N = a.kernel_streams, a.samples
     eng = wm.FSKEngine(1, {})

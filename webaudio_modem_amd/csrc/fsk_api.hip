@@ -127,15 +127,14 @@ int fskhip_modulate_host(fskhip_engine *e, const uint8_t *payloads, const uint32
     if (out_lens[s] > out_pitch) return fail(FSKHIP_E_OVERFLOW, "stream %zu needs %u samples, slab holds %zu", s, out_lens[s], out_pitch);
   return FSKHIP_OK;
 }
-// ... and the same into any capture format and layout (include/fskhip.h): the floats stay on the device, fsk_egress.hip's kernel narrows
+// ... and the same into any capture format and layout (include/fskhip.h): the floats stay on the device, fsk_samples.hip's egress kernel narrows
 // them -- silence from the modulator's own d_out_lens on -- into a staging buffer kept with the engine, and the narrow samples cross
 // PCIe in one 2-D copy: rows of n elements (stream-major), or n frames of n_streams elements (sample-major: the staging frames are
 // packed, the caller's may be wider and keep their other columns)
 int fskhip_modulate_host_fmt(fskhip_engine *e, const uint8_t *payloads, const uint32_t *lens, size_t payload_pitch, int format, int layout, void *out, size_t n,
                              size_t dst_pitch, uint32_t *out_lens) {
-  const size_t esz = ingest_sample_bytes(format);
-  if (!esz) return fail(FSKHIP_E_INVALID, "fskhip_modulate_host_fmt: unknown sample format %d", format);
-  if (layout != FSKHIP_LAYOUT_STREAM_MAJOR && layout != FSKHIP_LAYOUT_SAMPLE_MAJOR) return fail(FSKHIP_E_INVALID, "fskhip_modulate_host_fmt: unknown layout %d", layout);
+  if (const int rc = check_sample_format("fskhip_modulate_host_fmt", format, layout)) return rc;
+  const size_t esz = sample_bytes(format);
   if (!e) return fail(FSKHIP_E_NOT_CONFIGURED, "FSK modulator not configured");
   if (!lens || !out_lens || (n > 0 && !out)) return fail(FSKHIP_E_INVALID, "null buffer");
   const size_t S = e->n_streams;

@@ -153,7 +153,7 @@ int demod_device_impl(fskhip_engine *e, float *d_samples, size_t n, size_t pitch
 }
 // fskhip_demodulate_host (format F32, stream-major: `samples` is the caller's float*, staged as it is and written back into where
 // FSKHIP_DEMOD_WRITEBACK_AGC asks) and fskhip_demodulate_host_fmt (anything else: the samples cross PCIe as they are, into a narrow
-// staging slab, and fsk_ingest.hip's kernel widens them into the float staging tile on the compute stream).  One time pipeline:
+// staging slab, and fsk_samples.hip's ingest kernel widens them into the float staging tile on the compute stream).  One time pipeline:
 // the same slab lengths in samples, the same two streams and events.
 int demod_host_impl(fskhip_engine *e, const void *samples_, int format, int layout, size_t n, size_t pitch, uint8_t *out, size_t out_pitch,
                     uint32_t *out_counts, uint32_t *eod_counts, uint32_t flags) {
@@ -168,7 +168,7 @@ int demod_host_impl(fskhip_engine *e, const void *samples_, int format, int layo
   if (wb && !direct) return fail(FSKHIP_E_INVALID, "FSKHIP_DEMOD_WRITEBACK_AGC needs float samples in stream-major layout: there is nothing to write floats back into");
   HIP_TRY(hipSetDevice(e->device));
   float *const samples = direct ? (float *)const_cast<void *>(samples_) : nullptr;
-  const size_t esz = ingest_sample_bytes(format);
+  const size_t esz = sample_bytes(format);
   // slab length: ~96 MB of samples per slab, a multiple of 16 (whole tiles, even decimator parity), at least 4096
   size_t slab = ((size_t)96 << 20) / (S * sizeof(float));
   slab = slab < 4096 ? 4096 : slab;
@@ -273,8 +273,7 @@ int fskhip_demodulate_host(fskhip_engine *e, float *samples, size_t n, size_t pi
 // ... and the same for samples in any capture format and layout (include/fskhip.h), read only
 int fskhip_demodulate_host_fmt(fskhip_engine *e, const void *samples, int format, int layout, size_t n, size_t src_pitch, uint8_t *out,
                                size_t out_pitch, uint32_t *out_counts, uint32_t *eod_counts, uint32_t flags) {
-  if (!ingest_sample_bytes(format)) return fail(FSKHIP_E_INVALID, "fskhip_demodulate_host_fmt: unknown sample format %d", format);
-  if (layout != FSKHIP_LAYOUT_STREAM_MAJOR && layout != FSKHIP_LAYOUT_SAMPLE_MAJOR) return fail(FSKHIP_E_INVALID, "fskhip_demodulate_host_fmt: unknown layout %d", layout);
+  if (const int rc = check_sample_format("fskhip_demodulate_host_fmt", format, layout)) return rc;
   return demod_host_impl(e, samples, format, layout, n, src_pitch, out, out_pitch, out_counts, eod_counts, flags);
 }
 }  // extern "C"

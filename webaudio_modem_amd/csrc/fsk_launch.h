@@ -99,11 +99,14 @@ hipError_t launch_snap_pack(const SnapLayout &L, const DemodState &S, uint32_t n
                             hipStream_t st);
 hipError_t launch_snap_unpack(int precision, const SnapLayout &L, const DemodState &D, uint32_t n_dst, const int64_t *d_map, uint32_t rec_first, uint32_t rec_count,
                               bool fresh_too, const NewStream &N, const void *d_in, hipStream_t st);
-// fsk_ingest.hip: capture formats (FSKHIP_SAMPLES_*) and layouts (FSKHIP_LAYOUT_*) -> float32 [stream][dst_pitch], exact.  The caller
-// has checked the arguments (fskhip_ingest_device); nothing is launched for an empty batch.  ingest_sample_bytes: 0 = unknown format.
-size_t ingest_sample_bytes(int format);
+// fsk_samples.hip: the capture formats (FSKHIP_SAMPLES_*) and layouts (FSKHIP_LAYOUT_*).  sample_bytes: 0 = unknown format.
+// check_sample_format: FSKHIP_OK, or the refusal of a format or layout that is none, with `who` in front, that every entry point taking the pair gives.
+size_t sample_bytes(int format);
+int check_sample_format(const char *who, int format, int layout);
+// ingest: those -> float32 [stream][dst_pitch], exact.  The caller has checked the arguments (fskhip_ingest_device); nothing is
+// launched for an empty batch.
 hipError_t launch_ingest(const void *d_src, int format, int layout, uint32_t n_streams, size_t n, size_t src_pitch, float *d_dst, size_t dst_pitch, hipStream_t st);
-// fsk_egress.hip: float32 [stream][src_pitch] -> the same formats and layouts, narrowed (include/fskhip.h: the encoders).  d_lens (may
+// egress: float32 [stream][src_pitch] -> the same formats and layouts, narrowed (include/fskhip.h: the encoders).  d_lens (may
 // be null): elements from d_lens[s] on are the format's silence.  The caller has checked the arguments (fskhip_egress_device); nothing
 // is launched for an empty batch.
 hipError_t launch_egress(const float *d_src, size_t src_pitch, const uint32_t *d_lens, uint32_t n_streams, size_t n, int format, int layout, void *d_dst,

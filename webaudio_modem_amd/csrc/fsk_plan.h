@@ -66,7 +66,7 @@ inline size_t host_stage_shift(bool f64, bool lock_step, uint32_t ds_parity) {
   return (!f64 && lock_step && (plan_head(ds_parity, 0, false) & 1u)) ? 3 : 0;
 }
 
-// fskhip_modulate_host_fmt's staging (fsk_api.hip): the float rows the modulator writes, the narrow buffer fsk_egress.hip's kernel
+// fskhip_modulate_host_fmt's staging (fsk_api.hip): the float rows the modulator writes, the narrow buffer fsk_samples.hip's egress kernel
 // fills, and the ONE 2-D copy that brings it to the host -- of `rows` rows of `row_bytes` bytes, npitch * esz apart on the device.
 // Stream-major rows start on 16-byte boundaries (the kernel's vector path from element 0); sample-major frames are packed, n_streams
 // elements each, whatever frame pitch the caller's buffer has.

@@ -175,20 +175,26 @@ SAMPLE_LAYOUTS = {"stream": _lib.LAYOUT_STREAM_MAJOR, "sample": _lib.LAYOUT_SAMP
 _FORMAT_DTYPE = {_lib.SAMPLES_F32: np.float32, _lib.SAMPLES_S16: np.int16, _lib.SAMPLES_MULAW: np.uint8, _lib.SAMPLES_ALAW: np.uint8}
 
 
-def _format_code(fmt):
-    if isinstance(fmt, str):
-        if fmt.lower() not in SAMPLE_FORMATS:
-            raise ValueError("unknown sample format %r (one of %s)" % (fmt, ", ".join(SAMPLE_FORMATS)))
-        return SAMPLE_FORMATS[fmt.lower()]
-    return int(fmt)
+def _sample_codes(fmt, layout, numbers_as_they_are=False):
+    """(format, layout) as the library's numbers, from names (SAMPLE_FORMATS / SAMPLE_LAYOUTS, any case) or numbers.
+    numbers_as_they_are: a number that is no format or layout is passed on, for the library to refuse."""
+    code = SAMPLE_FORMATS.get(fmt.lower()) if isinstance(fmt, str) else int(fmt)
+    lay = SAMPLE_LAYOUTS.get(layout.lower()) if isinstance(layout, str) else int(layout)
+    if code not in _FORMAT_DTYPE and not (numbers_as_they_are and code is not None):
+        raise ValueError("unknown sample format %r (one of %s)" % (fmt, ", ".join(SAMPLE_FORMATS)))
+    if lay not in SAMPLE_LAYOUTS.values() and not (numbers_as_they_are and lay is not None):
+        raise ValueError("unknown layout %r (one of %s)" % (layout, ", ".join(SAMPLE_LAYOUTS)))
+    return code, lay
 
 
-def _layout_code(layout):
-    if isinstance(layout, str):
-        if layout.lower() not in SAMPLE_LAYOUTS:
-            raise ValueError("unknown layout %r (one of %s)" % (layout, ", ".join(SAMPLE_LAYOUTS)))
-        return SAMPLE_LAYOUTS[layout.lower()]
-    return int(layout)
+def _row_pitch(a):
+    """the pitch in elements of a 2-D array whose rows are contiguous and lie at one constant pitch of whole elements, at least a
+    row apart (a block of rows or of columns of a wider array is one); None for any other"""
+    isz = a.dtype.itemsize
+    rows, cols = a.shape
+    if not (cols <= 1 or a.strides[1] == isz) or not (rows <= 1 or (a.strides[0] % isz == 0 and a.strides[0] >= cols * isz)):
+        return None
+    return max(a.strides[0] // isz if rows > 1 else cols, cols, 1)
 
 
 def sample_args(samples, fmt=None, layout="stream"):
@@ -206,30 +212,23 @@ def sample_args(samples, fmt=None, layout="stream"):
             raise ValueError("uint8 samples need fmt='mulaw' or fmt='alaw'")
         else:
             raise ValueError("no sample format for dtype %s: float32, int16 or uint8 (G.711)" % a.dtype)
-    code, lay = _format_code(fmt), _layout_code(layout)
-    if code not in _FORMAT_DTYPE:
-        raise ValueError("unknown sample format %r" % (fmt,))
-    if lay not in (_lib.LAYOUT_STREAM_MAJOR, _lib.LAYOUT_SAMPLE_MAJOR):
-        raise ValueError("unknown layout %r" % (layout,))
+    code, lay = _sample_codes(fmt, layout)
     if a.dtype != _FORMAT_DTYPE[code]:
         raise ValueError("format %r takes %s samples, got %s" % (fmt, np.dtype(_FORMAT_DTYPE[code]).name, a.dtype))
     if a.ndim == 1:
         a = a.reshape(1, -1) if lay == _lib.LAYOUT_STREAM_MAJOR else a.reshape(-1, 1)
     if a.ndim != 2:
         raise ValueError("samples must be a 2-D array")
-    isz = a.dtype.itemsize
-    rows, cols = a.shape
-    if not (cols <= 1 or a.strides[1] == isz) or not (rows <= 1 or (a.strides[0] % isz == 0 and a.strides[0] >= cols * isz)):
+    if _row_pitch(a) is None:
         a = np.ascontiguousarray(a)
-    pitch = a.strides[0] // isz if rows > 1 else cols
-    S, N = (rows, cols) if lay == _lib.LAYOUT_STREAM_MAJOR else (cols, rows)
-    return a, code, lay, S, N, max(pitch, cols, 1)
+    S, N = a.shape if lay == _lib.LAYOUT_STREAM_MAJOR else a.shape[::-1]
+    return a, code, lay, S, N, _row_pitch(a)
 
 
 def ingest_device(d_src, fmt, layout, n_streams, n_per_stream, src_pitch, d_dst, dst_pitch, stream=None):
     """fskhip_ingest_device: device pointers (ints); widens capture samples into float32 [n_streams][dst_pitch] on the current
     device, asynchronously on `stream` (a hipStream_t handle or None)."""
-    _lib.check(_lib.lib().fskhip_ingest_device(d_src, _format_code(fmt), _layout_code(layout), n_streams, n_per_stream, src_pitch,
+    _lib.check(_lib.lib().fskhip_ingest_device(d_src, *_sample_codes(fmt, layout, True), n_streams, n_per_stream, src_pitch,
                                                d_dst, dst_pitch, stream))
 
 
@@ -237,7 +236,7 @@ def egress_device(d_src, src_pitch, d_lens, n_streams, n_per_stream, fmt, layout
     """fskhip_egress_device: device pointers (ints); narrows float32 [n_streams][src_pitch] into samples of `fmt` in `layout` on the
     current device, asynchronously on `stream` (a hipStream_t handle or None).  d_lens (or None): per-stream lengths; a stream is
     the format's silence from its length on."""
-    _lib.check(_lib.lib().fskhip_egress_device(d_src, src_pitch, d_lens, n_streams, n_per_stream, _format_code(fmt), _layout_code(layout),
+    _lib.check(_lib.lib().fskhip_egress_device(d_src, src_pitch, d_lens, n_streams, n_per_stream, *_sample_codes(fmt, layout, True),
                                                d_dst, dst_pitch, stream))
 
 
@@ -257,21 +256,15 @@ def samples_out(fmt, layout, n_streams, n_per_stream, out=None):
     dtype (SAMPLE_FORMATS), [S, n] (layout "stream") or [n, S] (layout "sample").  Otherwise `out` itself, which must have that
     dtype and shape and unit stride along its rows; its rows may be a block of a wider array (a shard's column block of
     interleaved frames): the wider array's pitch is passed on and nothing is copied."""
-    code, lay = _format_code(fmt), _layout_code(layout)
-    if code not in _FORMAT_DTYPE:
-        raise ValueError("unknown sample format %r" % (fmt,))
-    if lay not in (_lib.LAYOUT_STREAM_MAJOR, _lib.LAYOUT_SAMPLE_MAJOR):
-        raise ValueError("unknown layout %r" % (layout,))
+    code, lay = _sample_codes(fmt, layout)
     shape = (n_streams, n_per_stream) if lay == _lib.LAYOUT_STREAM_MAJOR else (n_per_stream, n_streams)
     if out is None:
         out = np.zeros(shape, _FORMAT_DTYPE[code])
     if not isinstance(out, np.ndarray) or out.dtype != _FORMAT_DTYPE[code] or out.shape != shape or not out.flags.writeable:
         raise ValueError("out must be a writeable %s array of shape %r" % (np.dtype(_FORMAT_DTYPE[code]).name, shape))
-    isz = out.dtype.itemsize
-    rows, cols = shape
-    if not (cols <= 1 or out.strides[1] == isz) or not (rows <= 1 or (out.strides[0] % isz == 0 and out.strides[0] >= cols * isz)):
+    if _row_pitch(out) is None:
         raise ValueError("out must have contiguous rows at a constant pitch")
-    return out, code, lay, max(out.strides[0] // isz if rows > 1 else cols, cols, 1)
+    return out, code, lay, _row_pitch(out)
 
 
 # Called with (n_streams, precision) by every new FSKEngine; returns a dict of fskhip_set_option() names -> values to apply on
