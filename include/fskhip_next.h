@@ -294,6 +294,113 @@ int fskhip_xmodem_rx_poll_device(fskhip_xmodem_rx *r, const uint8_t *d_mask, uin
                                  size_t cap_bytes, uint32_t *d_totals, void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The resident XModem sender (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): XModemTransport.sendData() (xmodem.ts:69-184) for
+ * every stream of a processor, with the files, the packet building and the wait's grammar on the device.  The receiver above
+ * split the protocol loop -- grammar on the device, timers with the host -- and this is the same split for the send side: a poll
+ * looks into the RX rings for the control byte a wait is waiting for, and where one arrived it builds the next packet (or the
+ * EOT) on the device and hands it to the processor's modulator, as fskhip_processor_modulate_host would.  No ring byte, no
+ * fragment and no packet crosses to the host; what comes back is one event per stream where something happened.  The host keeps
+ * the timers: a wait that has lasted too long is ended by naming the stream in the poll's abort mask.
+ *
+ * What a poll is.  Every wait of the reference's sender calls dataChannel.demodulate(), which returns EVERYTHING buffered; the
+ * wait looks at that one reply and throws the rest of it away (waitForControlByte returns the first of ACK / NAK / EOT in the
+ * reply, xmodem.ts:413-418; waitForACK succeeds if the reply holds an ACK anywhere, 448-452).  One poll of a ring is one such
+ * reply.  The result therefore depends on WHEN the poll happens -- two control bytes found by one poll are one reply, the second
+ * is lost; found by two polls they are two replies -- exactly as the reference's result depends on when its message arrives.
+ * Unlike the receiver there is NO cut-invariance here, and none is claimed or tested.
+ *
+ * State per stream, kept with this handle and NOT in the processor (its images and remaps do not carry it): state (FSKHIP_XT_*),
+ * sequence (send.sequence, 1..255), fragment_index, retries (the counter local to withRetry, xmodem.ts:608: it restarts at 0 for
+ * every fragment; send.retries plays no part on the send path), packets_sent (statistics.packetsSent: data packets and the EOT)
+ * and retransmitted (statistics.packetsRetransmitted); and the stream's file, in one packed store on the device.
+ *
+ * fskhip_xmodem_tx_create   max_payload_size is config.maxPayloadSize, 1..255 (the reference's default is 128), max_retries is
+ *                           config.maxRetries (the reference's default is 10).  Grows the processor's payload store to hold
+ *                           max_payload_size + 6 bytes, so that no poll allocates; synchronises with the processor's work.
+ * fskhip_xmodem_tx_send_host  sendData(data) for the streams with (mask == NULL || mask[s]): the file of stream s is
+ *                           data[offsets[s] .. offsets[s+1]) (offsets has n_streams + 1 entries; those of unselected streams are
+ *                           not looked at, except that every selected stream needs offsets[s] <= offsets[s+1]).  ensureIdle first:
+ *                           if any selected stream is not FSKHIP_XT_IDLE the call returns FSKHIP_E_BUSY with the reference's text,
+ *                           'Transport busy: sendData cannot start while in SENDING_WAIT_ACK state' (the state's own name:
+ *                           SENDING_WAIT_NAK, SENDING_WAIT_ACK or SENDING_WAIT_FINAL_ACK) followed by ' (stream N)', and starts
+ *                           nothing.  Then initializeSend: sequence 1, fragment_index 0, retries 0, n_fragments =
+ *                           max(1, ceil(len / max_payload_size)) -- an empty file is ONE empty fragment --, state WAIT_NAK.
+ *                           Nothing is transmitted yet.  A stream's earlier file is replaced; the store is compacted when it has
+ *                           to grow.  FSKHIP_E_UNSUPPORTED if the files together would exceed 2^32 - 1 bytes.
+ * fskhip_xmodem_tx_reset    reset() (xmodem.ts:370-383) for one stream or all (stream < 0): FSKHIP_XT_IDLE, sequence 1,
+ *                           fragment_index 0, retries 0, the file dropped (n_fragments 0), and -- as super.reset() does -- both
+ *                           counters 0.  The ring and a pending modulation are left alone.
+ * fskhip_xmodem_tx_state_get / _state_set  the six arrays ([n_streams] each, any pointer may be NULL), to carry a sender across
+ *                           a remap or a restore: send_host on the new handle, then state_set.  state_set validates everything
+ *                           before it sets anything, with the values given taking the place of the current ones: state <= 3,
+ *                           sequence in 1..255, and for a stream in WAIT_NAK or WAIT_ACK fragment_index < n_fragments (so a file
+ *                           must have been given); FSKHIP_E_INVALID names the first bad stream.
+ * create, send_host, reset, state_get and state_set synchronise with the processor's outstanding work.  The processor must outlive
+ * every call but fskhip_xmodem_tx_destroy.
+ *
+ * One poll.  A stream is SELECTED when (mask == NULL || mask[s]) and its state is not FSKHIP_XT_IDLE.  It follows the first of
+ * rules 1-3 that applies, and within rule 3 the first branch that matches:
+ *   1. abort[s] (abort may be NULL: none): status ABORTED, state IDLE.  This is the wait's timeout: its signal is aborted, every
+ *      wait throws, withRetry and waitForInitialNAK do not retry an abort (xmodem.ts:115, 617), sendData fails with 'Operation
+ *      aborted' ('Operation aborted at sendData' in the first wait).  The ring and any pending modulation are left alone (the
+ *      reference has no cancel).  The "standalone mode" branch and the EOT retry of the reference are not reachable this way, so
+ *      the device needs no timer and retransmits no EOT.
+ *   2. the processor's tx_pending[s] != 0: nothing happens, the stream is not listed and its ring is not touched -- the reference
+ *      is still inside `await modulate()` and is not waiting yet.
+ *   3. otherwise L = the live ring bytes, oldest first, is the reply.  ALL of L leaves the ring: readIndex advances by _length
+ *      modulo the capacity, _length = 0; writeIndex and the ring bytes are untouched.  An empty L is a legal, empty reply.
+ *      WAIT_NAK       c = the first ACK / NAK / EOT of L.  NAK: fragment 0 (fragment_index) is transmitted, state WAIT_ACK.  ACK or
+ *                     EOT: returned and skipped, same state (control = c).  None: nothing.
+ *      WAIT_ACK       c as above.  ACK: retries = 0, fragment_index++, sequence = sequence % 255 + 1; the next fragment is
+ *                     transmitted, or after the last one EOT is, and the state is WAIT_FINAL_ACK.  NAK: retransmitted++; then
+ *                     ++retries > max_retries ends the transfer -- status MAX_RETRIES, state IDLE, nothing sent ('Timeout - max
+ *                     retries exceeded') --, otherwise retransmitted++ again (an answered NAK counts twice, xmodem.ts:146, 155)
+ *                     and the same fragment is transmitted again.  EOT: ignored, the wait goes on (control = EOT).
+ *      WAIT_FINAL_ACK an ACK anywhere in L: status DONE, state IDLE, control = ACK.  Anything else, the echo of the sender's own
+ *                     EOT and a NAK included, is ignored (control = -1).
+ *      Every transmission counts in packets_sent.  A transmission is the 'modulate' request of that stream: the packet
+ *      SOH seq ~seq len payload crc_hi crc_lo (CRC-16 of the payload only), or the single byte 0x04, built on the device and
+ *      started as fskhip_processor_modulate_host starts it; tx_pending was 0, so it cannot be busy.
+ * The event: status, state_after, control (the byte the wait returned, else -1), sent_len (bytes handed to the modulator: 0, 1
+ * for EOT, len + 6 for a packet), and sequence, fragment_index, n_fragments, retries after the poll (retries is max_retries + 1
+ * after MAX_RETRIES).  A stream is LISTED when status != PROGRESS, or sent_len != 0, or control != -1.  A stream whose reply held
+ * only other bytes is drained and not listed.  A stream that is not selected is not touched in any word.
+ * Output: the listed streams in ascending order in streams[0 .. n_events), events[i] that of streams[i].
+ * Overflow, as the receiver's: if n_events > cap_streams the call returns FSKHIP_E_OVERFLOW with the true count and changes
+ * NOTHING -- no ring word, no sender word, no modulation.  cap_streams 0 with null lists is therefore a size query.  _device is
+ * asynchronous on `hip_stream`, pointers on the processor's device; d_totals takes three words: n_events, 0, and 1 if the poll
+ * was committed, 0 if it stood down (the lists are then undefined).  The handle keeps scratch: one poll at a time per handle.
+ * FSKHIP_E_INVALID before any device call, in this order.  poll: null n_events (_host) / null d_totals (_device); a null streams or
+ * events with cap_streams != 0; a null sender.  create: a null processor or a null out; max_payload_size outside 1..255.
+ * send_host: null offsets; a null sender; then, stream by stream, offsets[s] > offsets[s+1], a file with null data, a stream that
+ * is busy (FSKHIP_E_BUSY).  state_get, state_set, reset: a null sender (reset: then a stream out of range).  A poll makes the
+ * processor a used one, as a drain does, and is never part of the captured quantum graph.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct fskhip_xmodem_tx fskhip_xmodem_tx;
+enum { FSKHIP_XT_IDLE = 0, FSKHIP_XT_WAIT_NAK = 1, FSKHIP_XT_WAIT_ACK = 2, FSKHIP_XT_WAIT_FINAL_ACK = 3 };   /* state */
+enum { FSKHIP_XT_PROGRESS = 0, FSKHIP_XT_DONE = 1, FSKHIP_XT_MAX_RETRIES = 2, FSKHIP_XT_ABORTED = 3 };        /* status */
+typedef struct fskhip_xmodem_tx_event {
+  uint32_t status, state_after;
+  int32_t  control;        /* the byte that the wait returned (0x06 / 0x15 / 0x04), else -1 */
+  uint32_t sent_len;       /* bytes handed to the modulator by this poll: 0, 1 (EOT) or len + 6 */
+  uint32_t sequence, fragment_index, n_fragments, retries;   /* after the poll */
+} fskhip_xmodem_tx_event;
+
+int fskhip_xmodem_tx_create(fskhip_processor *p, uint32_t max_payload_size, uint32_t max_retries, fskhip_xmodem_tx **out);
+int fskhip_xmodem_tx_destroy(fskhip_xmodem_tx *t);
+int fskhip_xmodem_tx_send_host(fskhip_xmodem_tx *t, const uint8_t *mask, const uint64_t *offsets, const uint8_t *data);
+int fskhip_xmodem_tx_poll_host(fskhip_xmodem_tx *t, const uint8_t *mask, const uint8_t *abort, uint32_t *streams,
+                               fskhip_xmodem_tx_event *events, uint32_t cap_streams, uint32_t *n_events);
+int fskhip_xmodem_tx_poll_device(fskhip_xmodem_tx *t, const uint8_t *d_mask, const uint8_t *d_abort, uint32_t *d_streams,
+                                 fskhip_xmodem_tx_event *d_events, uint32_t cap_streams, uint32_t *d_totals, void *hip_stream);
+int fskhip_xmodem_tx_state_get(fskhip_xmodem_tx *t, uint32_t *state, uint32_t *sequence, uint32_t *fragment_index,
+                               uint32_t *retries, uint32_t *packets_sent, uint32_t *retransmitted);
+int fskhip_xmodem_tx_state_set(fskhip_xmodem_tx *t, const uint32_t *state, const uint32_t *sequence,
+                               const uint32_t *fragment_index, const uint32_t *retries, const uint32_t *packets_sent,
+                               const uint32_t *retransmitted);
+int fskhip_xmodem_tx_reset(fskhip_xmodem_tx *t, int64_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * FIR half of src/dsp/filters.ts: FIRFilter (112-167) batched over streams, and the windowed-sinc designs
  * (243-314) + FilterFactory.createFIR* (346-368).
  * ------------------------------------------------------------------------------------------------- */

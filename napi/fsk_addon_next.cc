@@ -16,6 +16,10 @@
 //   xmodemRxCreate(processor) -> handle;  xmodemRxDestroy(handle);  xmodemRxReset(handle, stream)
 //   xmodemRxPoll(handle, mask: Uint8Array|null) -> {streams: Uint32Array, results: Int32Array[10*n], offsets: Uint32Array, data: Uint8Array}
 //   xmodemRxState(handle) -> {expected, packets, dropped: Uint32Array};  xmodemRxSetState(handle, expected|null, packets|null, dropped|null)
+//   xmodemTxCreate(processor, maxPayloadSize, maxRetries) -> handle;  xmodemTxDestroy(handle);  xmodemTxReset(handle, stream)
+//   xmodemTxSend(handle, mask: Uint8Array|null, offsets: Uint32Array[nStreams + 1], data: Uint8Array)
+//   xmodemTxPoll(handle, mask: Uint8Array|null, abort: Uint8Array|null) -> {streams: Uint32Array, events: Int32Array[8*n]}
+//   xmodemTxState(handle) -> {state, sequence, fragmentIndex, retries, packetsSent, retransmitted: Uint32Array};  xmodemTxSetState(handle, the six|null)
 //   processorRemap(dst, src, map: number[]);  processorSnapshot(handle, sel: number[]|null) -> Buffer
 //   processorRestore(dst, snapshot: Uint8Array, map: number[]);  processorSnapshotInfo(snapshot) -> {nStreams, rxCapacity, payloadCapacity, recordBytes}
 //   sincLowpass/sincHighpass(cutoff, sampleRate, numTaps), sincBandpass(center, bandwidth, sampleRate, numTaps) -> Float64Array
@@ -376,6 +380,129 @@ napi_value XmodemRxSetState(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// ---- the resident XModem sender (include/fskhip_next.h: fskhip_xmodem_tx_*) over a processor handle, boxed as the receiver is
+struct XmTx { fskhip_xmodem_tx *t; uint32_t S; };
+void xm_tx_finalize(napi_env, void *data, void *) {
+  XmTx *h = (XmTx *)data;
+  if (h->t) fskhip_xmodem_tx_destroy(h->t);
+  delete h;
+}
+XmTx *get_xm_tx(napi_env env, napi_value v) {
+  XmTx *h = (XmTx *)external(env, v, "sender destroyed");
+  if (h && !h->t) { napi_throw_error(env, nullptr, "sender destroyed"); return nullptr; }
+  return h;
+}
+napi_value XmodemTxCreate(napi_env env, napi_callback_info info) {
+  ARGS(3);
+  Proc *p = get_proc(env, argv[0]);
+  if (!p) return nullptr;
+  uint32_t max_payload = 0, max_retries = 0;
+  napi_get_value_uint32(env, argv[1], &max_payload);
+  napi_get_value_uint32(env, argv[2], &max_retries);
+  fskhip_xmodem_tx *t = nullptr;
+  int rc = fskhip_xmodem_tx_create(p->p, max_payload, max_retries, &t);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  XmTx *h = new XmTx{t, p->S};
+  napi_value ext;
+  if (napi_create_external(env, h, xm_tx_finalize, nullptr, &ext) != napi_ok) { xm_tx_finalize(env, h, nullptr); napi_throw_error(env, nullptr, "xmodemTxCreate: no handle"); return nullptr; }
+  return ext;
+}
+napi_value XmodemTxDestroy(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  void *q = nullptr;
+  if (napi_get_value_external(env, argv[0], &q) == napi_ok && q) {
+    XmTx *h = (XmTx *)q;
+    if (h->t) fskhip_xmodem_tx_destroy(h->t);
+    h->t = nullptr;
+  }
+  return nullptr;
+}
+napi_value XmodemTxSend(napi_env env, napi_callback_info info) {
+  ARGS(4);
+  XmTx *h = get_xm_tx(env, argv[0]);
+  if (!h) return nullptr;
+  void *mask, *off, *data; size_t mlen, olen, dlen;
+  if (!typed(env, argv[1], napi_uint8_array, &mask, &mlen, true) || !typed(env, argv[2], napi_uint32_array, &off, &olen) ||
+      !typed(env, argv[3], napi_uint8_array, &data, &dlen))
+    return nullptr;
+  if (mask && mlen != h->S) { napi_throw_range_error(env, nullptr, "xmodemTxSend: mask must have one entry per stream"); return nullptr; }
+  if (olen != (size_t)h->S + 1) { napi_throw_range_error(env, nullptr, "xmodemTxSend: offsets must have nStreams + 1 entries"); return nullptr; }
+  std::vector<uint64_t> offsets(olen);
+  for (size_t i = 0; i < olen; i++) {
+    offsets[i] = ((const uint32_t *)off)[i];
+    if (offsets[i] > dlen) { napi_throw_range_error(env, nullptr, "xmodemTxSend: an offset lies behind the data"); return nullptr; }
+  }
+  int rc = fskhip_xmodem_tx_send_host(h->t, (const uint8_t *)mask, offsets.data(), (const uint8_t *)data);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+// sized with a query call (an overflowing poll changes nothing), then polled into arrays of exactly that size
+napi_value XmodemTxPoll(napi_env env, napi_callback_info info) {
+  ARGS(3);
+  XmTx *h = get_xm_tx(env, argv[0]);
+  if (!h) return nullptr;
+  void *mask, *abort_; size_t mlen, alen;
+  if (!typed(env, argv[1], napi_uint8_array, &mask, &mlen, true) || !typed(env, argv[2], napi_uint8_array, &abort_, &alen, true)) return nullptr;
+  if ((mask && mlen != h->S) || (abort_ && alen != h->S)) { napi_throw_range_error(env, nullptr, "xmodemTxPoll: mask and abort must have one entry per stream"); return nullptr; }
+  uint32_t n_events = 0;
+  int rc = fskhip_xmodem_tx_poll_host(h->t, (const uint8_t *)mask, (const uint8_t *)abort_, nullptr, nullptr, 0, &n_events);
+  if (rc != FSKHIP_OK && rc != FSKHIP_E_OVERFLOW) return throw_fsk(env, rc);
+  void *streams, *events;
+  napi_value str_v = make_typed(env, napi_uint32_array, n_events, 4, &streams);
+  napi_value ev_v = make_typed(env, napi_int32_array, 8 * (size_t)n_events, 4, &events);
+  if (!str_v || !ev_v) { napi_throw_error(env, nullptr, "xmodemTxPoll: out of memory"); return nullptr; }
+  if (rc == FSKHIP_E_OVERFLOW) {
+    rc = fskhip_xmodem_tx_poll_host(h->t, (const uint8_t *)mask, (const uint8_t *)abort_, (uint32_t *)streams, (fskhip_xmodem_tx_event *)events, n_events, &n_events);
+    if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  }
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "streams", str_v);
+  napi_set_named_property(env, o, "events", ev_v);
+  return o;
+}
+napi_value XmodemTxReset(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  XmTx *h = get_xm_tx(env, argv[0]);
+  if (!h) return nullptr;
+  int64_t s = -1;
+  napi_get_value_int64(env, argv[1], &s);
+  int rc = fskhip_xmodem_tx_reset(h->t, s);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+const char *const kXmTxWords[6] = {"state", "sequence", "fragmentIndex", "retries", "packetsSent", "retransmitted"};
+napi_value XmodemTxState(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  XmTx *h = get_xm_tx(env, argv[0]);
+  if (!h) return nullptr;
+  void *a[6]; napi_value v[6];
+  for (int i = 0; i < 6; i++) {
+    v[i] = make_typed(env, napi_uint32_array, h->S, 4, &a[i]);
+    if (!v[i]) { napi_throw_error(env, nullptr, "xmodemTxState: out of memory"); return nullptr; }
+  }
+  int rc = fskhip_xmodem_tx_state_get(h->t, (uint32_t *)a[0], (uint32_t *)a[1], (uint32_t *)a[2], (uint32_t *)a[3], (uint32_t *)a[4], (uint32_t *)a[5]);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  for (int i = 0; i < 6; i++) napi_set_named_property(env, o, kXmTxWords[i], v[i]);
+  return o;
+}
+napi_value XmodemTxSetState(napi_env env, napi_callback_info info) {
+  ARGS(7);
+  XmTx *h = get_xm_tx(env, argv[0]);
+  if (!h) return nullptr;
+  void *a[6]; size_t n[6];
+  for (int i = 0; i < 6; i++) {
+    if (!typed(env, argv[1 + i], napi_uint32_array, &a[i], &n[i], true)) return nullptr;
+    if (a[i] && n[i] != h->S) { napi_throw_range_error(env, nullptr, "xmodemTxSetState: state arrays must have one entry per stream"); return nullptr; }
+  }
+  int rc = fskhip_xmodem_tx_state_set(h->t, (const uint32_t *)a[0], (const uint32_t *)a[1], (const uint32_t *)a[2], (const uint32_t *)a[3], (const uint32_t *)a[4],
+                                      (const uint32_t *)a[5]);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+
 // ---- processor remap / snapshots (include/fskhip_next.h): a snapshot is a Buffer (or any Uint8Array) on this side
 napi_value ProcessorRemap(napi_env env, napi_callback_info info) {
   ARGS(3);
@@ -608,6 +735,13 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"xmodemRxReset", nullptr, XmodemRxReset, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"xmodemRxState", nullptr, XmodemRxState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"xmodemRxSetState", nullptr, XmodemRxSetState, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTxCreate", nullptr, XmodemTxCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTxDestroy", nullptr, XmodemTxDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTxSend", nullptr, XmodemTxSend, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTxPoll", nullptr, XmodemTxPoll, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTxReset", nullptr, XmodemTxReset, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTxState", nullptr, XmodemTxState, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTxSetState", nullptr, XmodemTxSetState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRemap", nullptr, ProcessorRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorSnapshot", nullptr, ProcessorSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRestore", nullptr, ProcessorRestore, nullptr, nullptr, nullptr, napi_default, nullptr},

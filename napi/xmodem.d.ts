@@ -46,3 +46,34 @@ export declare class XModemReceiverBatch {
   setState(state: { expected?: ArrayLike<number> | null; packets?: ArrayLike<number> | null; dropped?: ArrayLike<number> | null }): void;
   close(): void;
 }
+
+/** fskhip_xmodem_tx_event of one stream */
+export interface SenderEvent {
+  status: number; statusName: 'progress' | 'done' | 'max_retries' | 'aborted';
+  /** what sendData() would have thrown ('Operation aborted at sendData' where the abort ended the first wait), or null */
+  error: string | null;
+  stateAfter: number; stateName: string;
+  /** the byte the wait returned (0x06 / 0x15 / 0x04), else -1 */
+  control: number;
+  /** bytes handed to the modulator by this poll: 0, 1 (EOT) or len + 6 */
+  sentLen: number;
+  sequence: number; fragmentIndex: number; nFragments: number; retries: number;
+}
+export interface SenderState {
+  state: Uint32Array; sequence: Uint32Array; fragmentIndex: Uint32Array; retries: Uint32Array; packetsSent: Uint32Array; retransmitted: Uint32Array;
+}
+/** XModemTransport.sendData() for every stream of an FSKProcessorBatch, resident on the device (fskhip_xmodem_tx_*) */
+export declare class XModemSenderBatch {
+  constructor(processor: { handle: unknown; nStreams: number }, options?: { maxPayloadSize?: number; maxRetries?: number });
+  readonly nStreams: number;
+  readonly maxPayloadSize: number;
+  readonly maxRetries: number;
+  send(files: ArrayLike<ArrayLike<number> | null>, options?: { mask?: ArrayLike<boolean | number> | null }): void;
+  /** one demodulate() reply per waiting stream; abort: the streams whose wait has timed out */
+  poll(options?: { mask?: ArrayLike<boolean | number> | null; abort?: ArrayLike<boolean | number> | null }): { streams: Uint32Array; events: SenderEvent[] };
+  /** reset(): IDLE, sequence 1, the file dropped, the counters 0, for one stream or all (-1) */
+  reset(stream?: number): void;
+  state(): SenderState;
+  setState(state: { [K in keyof SenderState]?: ArrayLike<number> | null }): void;
+  close(): void;
+}

@@ -128,4 +128,77 @@ class XModemReceiverBatch {
   }
 }
 
-module.exports = { XModemReceiverBatch, CRC16, XModemPacket, ControlType, PacketConstants, crc16Batch, serializeBatch, scanBursts };
+// The send side of XModemTransport for every stream of an FSKProcessorBatch, resident on the device (fskhip_xmodem_tx_*): send() hands
+// each stream a file, poll() takes what each waiting stream's RX ring holds as ONE demodulate() reply and, where the control byte a wait
+// is waiting for has arrived, builds the next packet (or the EOT) on the device and starts its modulation.  What a poll finds depends
+// on when it happens, as in the reference.  The timers are the caller's: poll({abort}) ends the waits that have lasted too long.
+const TX_STATES = ['IDLE', 'SENDING_WAIT_NAK', 'SENDING_WAIT_ACK', 'SENDING_WAIT_FINAL_ACK'];
+const TX_STATUS = ['progress', 'done', 'max_retries', 'aborted'];
+const TX_ERRORS = [null, null, 'Timeout - max retries exceeded', 'Operation aborted'];
+const TX_WORDS = ['state', 'sequence', 'fragmentIndex', 'retries', 'packetsSent', 'retransmitted'];
+function boolArray(who, name, a, n) {
+  if (a === undefined || a === null) return null;
+  if (!Array.isArray(a) && !ArrayBuffer.isView(a)) throw new TypeError(who + ': ' + name + ' must be an array of nStreams booleans');
+  if (a.length !== n) throw new RangeError(who + ': ' + name + ' must have one entry per stream (' + n + ')');
+  return Uint8Array.from(a, (b) => (b ? 1 : 0));
+}
+class XModemSenderBatch {
+  constructor(processor, options = {}) {
+    if (processor === null || typeof processor !== 'object' || !Number.isInteger(processor.nStreams)) throw new TypeError('XModemSenderBatch: processor must be an FSKProcessorBatch');
+    if (options === null || typeof options !== 'object') throw new TypeError('XModemSenderBatch: options must be an object {maxPayloadSize, maxRetries}');
+    const { maxPayloadSize = 128, maxRetries = 10 } = options;
+    if (!Number.isInteger(maxPayloadSize) || maxPayloadSize < 1 || maxPayloadSize > 255) throw new RangeError('XModemSenderBatch: maxPayloadSize must be an integer in 1..255');
+    if (!Number.isInteger(maxRetries) || maxRetries < 0 || maxRetries > 0xffffffff) throw new RangeError('XModemSenderBatch: maxRetries must be an integer in [0, 2^32)');
+    this.processor = processor;
+    this.nStreams = processor.nStreams;
+    this.maxPayloadSize = maxPayloadSize;
+    this.maxRetries = maxRetries;
+    this.handle = addon.xmodemTxCreate(processor.handle, maxPayloadSize, maxRetries);
+  }
+  close() { if (this.handle) { addon.xmodemTxDestroy(this.handle); this.handle = null; } }
+  // sendData(files[s]) for every stream, or those of options.mask (the other entries are ignored).  Nothing is transmitted yet; a stream
+  // that is still sending throws the reference's 'Transport busy' text and nothing is started.
+  send(files, options = {}) {
+    if (!Array.isArray(files)) throw new TypeError('send: files must be an array of nStreams byte arrays');
+    if (files.length !== this.nStreams) throw new RangeError('send: files must have one entry per stream (' + this.nStreams + ')');
+    if (options === null || typeof options !== 'object') throw new TypeError('send: options must be an object {mask}');
+    const m = boolArray('send', 'mask', options.mask, this.nStreams);
+    const rows = files.map((f, s) => {
+      if (m && !m[s]) return new Uint8Array(0);
+      if (!Array.isArray(f) && !ArrayBuffer.isView(f)) throw new TypeError('send: files[' + s + '] must be a byte array');
+      return Uint8Array.from(f);
+    });
+    const offsets = new Uint32Array(this.nStreams + 1);
+    let total = 0;
+    rows.forEach((r, s) => { offsets[s] = total; total += r.length; });
+    if (total > 0xffffffff) throw new RangeError('send: the files together exceed 2^32 - 1 bytes');
+    offsets[this.nStreams] = total;
+    const data = new Uint8Array(total);
+    rows.forEach((r, s) => data.set(r, offsets[s]));
+    addon.xmodemTxSend(this.handle, m, offsets, data);
+  }
+  // {streams, events}: the streams where something happened in ascending order, and one event each
+  poll(options = {}) {
+    if (options === null || typeof options !== 'object') throw new TypeError('poll: options must be an object {mask, abort}');
+    const m = boolArray('poll', 'mask', options.mask, this.nStreams), a = boolArray('poll', 'abort', options.abort, this.nStreams);
+    const r = addon.xmodemTxPoll(this.handle, m, a);
+    const events = Array.from(r.streams, (_, i) => {
+      const q = r.events.subarray(i * 8, i * 8 + 8);
+      return { status: q[0], statusName: TX_STATUS[q[0]], error: TX_ERRORS[q[0]], stateAfter: q[1], stateName: TX_STATES[q[1]], control: q[2], sentLen: q[3],
+        sequence: q[4], fragmentIndex: q[5], nFragments: q[6], retries: q[7] };
+    });
+    return { streams: r.streams, events };
+  }
+  // reset() (xmodem.ts:370-383) for one stream, or all (-1): IDLE, sequence 1, the file dropped, the counters 0
+  reset(stream = -1) {
+    if (!Number.isInteger(stream)) throw new TypeError('reset: stream must be an integer (-1: all)');
+    addon.xmodemTxReset(this.handle, stream);
+  }
+  state() { return addon.xmodemTxState(this.handle); }   // {state, sequence, fragmentIndex, retries, packetsSent, retransmitted}: Uint32Array per stream
+  setState(state) {                                       // what state() returned, or any part of it, after send() on this object
+    if (state === null || typeof state !== 'object') throw new TypeError('setState: state must be an object {' + TX_WORDS.join(', ') + '}');
+    addon.xmodemTxSetState(this.handle, ...TX_WORDS.map((k) => stateArray(k, state[k], this.nStreams)));
+  }
+}
+
+module.exports = { XModemReceiverBatch, XModemSenderBatch, CRC16, XModemPacket, ControlType, PacketConstants, crc16Batch, serializeBatch, scanBursts };

@@ -144,4 +144,32 @@ hipError_t launch_xmodem_rx_scan(const ProcState &T, uint32_t n_streams, const u
                                  uint64_t cap_bytes, uint32_t *d_totals, hipStream_t st);
 hipError_t launch_xmodem_rx_commit(const ProcState &T, uint32_t n_streams, const XmRxState &X, const XmRxScratch &W, const uint32_t *d_totals, uint32_t *d_streams,
                                    fskhip_xmodem_result *d_results, uint32_t *d_offsets, uint8_t *d_data, hipStream_t st);
+// fsk_xmodem_tx.hip: the resident XModem sender (fskhip_xmodem_tx_poll_*).  The caller has checked the arguments.
+// XmTxState: the sender's per-stream words, each stream's file as [file_off, file_off + file_len) of the packed store, and the two
+// settings.  XmTxScratch: per stream the poll's event and flag word; xmodem_tx_pair_words(n_streams) words of workgroup pairs; the
+// staging slab [n_streams][slab_pitch] (rows 16-byte aligned, slab_pitch >= max_payload + 6) with its lengths and mask, in the
+// form launch_processor_tx_start takes.
+// step: decides every selected stream's transition into the scratch, clears tx_mask and nothing else, then the totals
+// {n_events, 0, 1 if they fit cap_streams}.  commit: given those, and only where d_totals[2] is 1, writes the lists, builds the
+// packets into the slab (tx_lens / tx_mask set for the streams that transmit), empties the rings that gave their reply and updates
+// the words; the caller launches launch_processor_tx_start(M, T, slab, tx_lens, slab_pitch, tx_mask) behind it.
+// repack: the files of the streams with keep[s] from one packed store into another (old_off -> new_off).
+struct XmTxState {
+  uint32_t *state, *sequence, *index, *n_fragments, *retries, *sent, *retransmitted, *file_off, *file_len;
+  const uint8_t *store;
+  uint32_t max_payload, max_retries;
+};
+struct XmTxScratch {
+  fskhip_xmodem_tx_event *ev;
+  uint32_t *flags, *pairs;
+  uint8_t *slab; uint32_t slab_pitch;
+  uint32_t *tx_lens; uint8_t *tx_mask;
+};
+size_t xmodem_tx_pair_words(uint32_t n_streams);
+hipError_t launch_xmodem_tx_step(const ProcState &T, uint32_t n_streams, const uint8_t *d_mask, const uint8_t *d_abort, const XmTxState &X, const XmTxScratch &W,
+                                 uint32_t cap_streams, uint32_t *d_totals, hipStream_t st);
+hipError_t launch_xmodem_tx_commit(const ProcState &T, uint32_t n_streams, const XmTxState &X, const XmTxScratch &W, const uint32_t *d_totals, uint32_t *d_streams,
+                                   fskhip_xmodem_tx_event *d_events, hipStream_t st);
+hipError_t launch_xmodem_tx_repack(const uint8_t *d_old_store, const uint32_t *d_old_off, const uint32_t *d_new_off, const uint32_t *d_lens, const uint8_t *d_keep,
+                                   uint32_t n_streams, uint8_t *d_new_store, hipStream_t st);
 }  // namespace fsk

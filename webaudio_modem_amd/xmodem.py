@@ -2,7 +2,8 @@
 (src/utils/crc16.ts) and `XModemPacket` (src/transports/xmodem/packet.ts) with the same names, argument meaning
 and error texts, plus the batch forms that actually feed a GPU and `scan_bursts`, the receive checks of
 XModemTransport (src/transports/xmodem/xmodem.ts:233-320) applied to the bytes a demodulate call returned; and
-`XModemReceiverBatch`, the same grammar resident on the device over the RX rings of an `FSKProcessorBatch`.
+`XModemReceiverBatch`, the same grammar resident on the device over the RX rings of an `FSKProcessorBatch`, and
+`XModemSenderBatch`, `sendData()` for every stream of one: files, packets and the waits' grammar on the device.
 Everything computes in libfskhip.so; there is no CPU path here.
 """
 import ctypes as C
@@ -10,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import XModemTxEvent, XT_IDLE, XT_WAIT_NAK, XT_WAIT_ACK, XT_WAIT_FINAL_ACK, XT_PROGRESS, XT_DONE, XT_MAX_RETRIES, XT_ABORTED  # noqa: F401
 from ._lib import XModemResult, XM_NEED_MORE, XM_EOT, XM_TRUNCATED, XM_INVALID_SEQUENCE, XM_INVALID_CRC, \
     XM_UNEXPECTED_SEQUENCE  # noqa: F401
 
@@ -222,3 +224,120 @@ class XModemReceiverBatch:
                     raise ValueError("state arrays must have one entry per stream")
             arrs.append(a)
         _lib.check(self._L.fskhip_xmodem_rx_state_set(self._h, *[None if a is None else a.ctypes.data for a in arrs]))
+
+
+# fskhip_xmodem_tx_event as a numpy record: the eight words, in order
+TX_EVENT_DTYPE = np.dtype([(k, "<u4" if t is C.c_uint32 else "<i4") for k, t in XModemTxEvent._fields_])
+TX_STATE_NAMES = {XT_IDLE: "IDLE", XT_WAIT_NAK: "SENDING_WAIT_NAK", XT_WAIT_ACK: "SENDING_WAIT_ACK", XT_WAIT_FINAL_ACK: "SENDING_WAIT_FINAL_ACK"}
+TX_STATUS_NAMES = {XT_PROGRESS: "progress", XT_DONE: "done", XT_MAX_RETRIES: "max_retries", XT_ABORTED: "aborted"}
+# what sendData() throws where a poll ends with that status (xmodem.ts:116, 618, 622); an abort in the first wait: TX_ERROR_FIRST_WAIT
+TX_STATUS_ERRORS = {XT_MAX_RETRIES: "Timeout - max retries exceeded", XT_ABORTED: "Operation aborted"}
+TX_ERROR_FIRST_WAIT = "Operation aborted at sendData"
+TX_WORDS = ("state", "sequence", "fragment_index", "retries", "packets_sent", "retransmitted")
+
+
+class XModemSenderBatch:
+    """The send side of XModemTransport for every stream of an FSKProcessorBatch, resident on the device (fskhip_xmodem_tx_*):
+    `send` hands each stream a file, a `poll` takes what each waiting stream's RX ring holds as one demodulate() reply, and where
+    the control byte a wait is waiting for has arrived it builds the next packet (or the EOT) on the device and starts its
+    modulation on the processor.  One poll is one reply, so what a poll finds depends on when it happens, as it does in the
+    reference.  The timers are the caller's: a wait that has lasted too long is ended through `abort`.  The processor must
+    outlive it."""
+
+    def __init__(self, processor, max_payload_size=128, max_retries=10):
+        self.processor = processor
+        self._L = _lib.lib()
+        self.n_streams = processor.n_streams
+        self.max_payload_size, self.max_retries = max_payload_size, max_retries
+        h = C.c_void_p()
+        _lib.check(self._L.fskhip_xmodem_tx_create(processor._h, max_payload_size, max_retries, C.byref(h)))
+        self._h = h
+        self._cap_streams = 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.fskhip_xmodem_tx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _mask(self, mask, name="mask"):
+        if mask is None:
+            return None
+        m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8)
+        if m.shape != (self.n_streams,):
+            raise ValueError("%s must have one entry per stream" % name)
+        return m
+
+    def send(self, files, mask=None):
+        """sendData(files[s]) for every stream (or those of `mask`; the other entries are ignored and may be None): the files go to
+        the device, the streams wait for the receiver's first NAK.  Nothing is transmitted yet.  A stream that is still sending
+        raises RuntimeError with the reference's 'Transport busy' text, and nothing is started."""
+        if len(files) != self.n_streams:
+            raise ValueError("need one file per stream")
+        m = self._mask(mask)
+        rows = [bytes(f) if (m is None or m[s]) and f is not None else b"" for s, f in enumerate(files)]
+        offsets = np.zeros(self.n_streams + 1, np.uint64)
+        offsets[1:] = np.cumsum([len(r) for r in rows], dtype=np.uint64)
+        data = np.frombuffer(b"".join(rows), np.uint8)
+        rc = self._L.fskhip_xmodem_tx_send_host(self._h, None if m is None else m.ctypes.data, offsets.ctypes.data, data.ctypes.data if len(data) else None)
+        if rc == _lib.E_BUSY:
+            raise RuntimeError(self._L.fskhip_last_error().decode("utf-8", "replace"))
+        _lib.check(rc)
+
+    def poll(self, mask=None, abort=None):
+        """(streams, events): the streams where something happened, ascending (uint32), and their event records
+        (TX_EVENT_DTYPE).  abort: the streams whose wait has timed out.  The lists are sized to the last poll's and grown on
+        overflow: an overflowing call changes nothing and reports the true count."""
+        m, a = self._mask(mask), self._mask(abort, "abort")
+        ne = C.c_uint32(0)
+        while True:
+            cs = self._cap_streams
+            streams, events = np.zeros(cs, np.uint32), np.zeros(cs, TX_EVENT_DTYPE)
+            rc = self._L.fskhip_xmodem_tx_poll_host(self._h, None if m is None else m.ctypes.data, None if a is None else a.ctypes.data,
+                                                    streams.ctypes.data if cs else None, events.ctypes.data if cs else None, cs, C.byref(ne))
+            if rc != _lib.E_OVERFLOW:
+                _lib.check(rc)
+                break
+            self._cap_streams = max(cs, ne.value)
+        return streams[:ne.value], events[:ne.value]
+
+    def poll_active(self, mask=None, abort=None):
+        """{stream: event dict} of one poll; the dict has the record's words plus status_name, state_name and error (the text
+        sendData() would have thrown, or None)"""
+        streams, events = self.poll(mask, abort)
+        out = {}
+        for s, e in zip(streams, events):
+            d = {k: int(e[k]) for k in TX_EVENT_DTYPE.names}
+            d["status_name"], d["state_name"] = TX_STATUS_NAMES[d["status"]], TX_STATE_NAMES[d["state_after"]]
+            d["error"] = TX_STATUS_ERRORS.get(d["status"])
+            out[int(s)] = d
+        return out
+
+    def reset(self, stream=-1):
+        """reset() (xmodem.ts:370-383) for one stream, or all: IDLE, sequence 1, the file dropped, the counters 0"""
+        _lib.check(self._L.fskhip_xmodem_tx_reset(self._h, int(stream)))
+
+    def state(self):
+        """{"state", "sequence", "fragment_index", "retries", "packets_sent", "retransmitted"}: uint32 arrays, one entry per stream"""
+        out = {k: np.zeros(self.n_streams, np.uint32) for k in TX_WORDS}
+        _lib.check(self._L.fskhip_xmodem_tx_state_get(self._h, *[out[k].ctypes.data for k in TX_WORDS]))
+        return out
+
+    def set_state(self, **words):
+        """what state() returned, or any part of it, after send() on this handle (validated as a whole before anything is set)"""
+        arrs = []
+        for k in TX_WORDS:
+            a = words.pop(k, None)
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.uint32)
+                if a.shape != (self.n_streams,):
+                    raise ValueError("state arrays must have one entry per stream")
+            arrs.append(a)
+        if words:
+            raise TypeError("unknown state words: %s" % ", ".join(sorted(words)))
+        _lib.check(self._L.fskhip_xmodem_tx_state_set(self._h, *[None if a is None else a.ctypes.data for a in arrs]))
