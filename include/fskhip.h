@@ -33,7 +33,8 @@ extern "C" {
  * fskhip_ingest_device, fskhip_demodulate_host_fmt (additions, same version); the same formats out -- fskhip_egress_device,
  * fskhip_modulate_host_fmt (additions, same version); the compacted RX drain -- fskhip_processor_rx_drain_sparse_host / _device in
  * fskhip_next.h (additions, same version); the resident XModem receiver -- fskhip_xmodem_rx_* in fskhip_next.h (additions, same
- * version). */
+ * version); the streaming quantum in the capture formats -- fskhip_processor_process_fmt_host / _device in fskhip_next.h (additions,
+ * same version). */
 #define FSKHIP_ABI_VERSION 8
 #define FSKHIP_MAX_PATTERN_BYTES 16
 

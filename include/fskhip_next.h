@@ -113,6 +113,38 @@ int fskhip_processor_process_host(fskhip_processor *p, float *in, size_t n_in, s
                                   size_t n_out, size_t out_pitch, uint32_t flags);
 
 /*
+ * process() with either side in a capture format and layout (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): what a trunk or an RTP
+ * gateway delivers and takes -- 16-bit PCM, G.711 mu-law / A-law or floats, stream-major or as interleaved frames
+ * [sample][channel] -- goes in and comes out as it is, so a quantum crosses PCIe in 1, 2 or 4 bytes per sample and the host neither
+ * widens nor transposes.  Formats and layouts are fskhip.h's FSKHIP_SAMPLES_* and FSKHIP_LAYOUT_*, with its formulas, silence
+ * values and pitch rules: pitches are in elements; FSKHIP_LAYOUT_STREAM_MAJOR has element (s, t) at s * pitch + t and needs
+ * pitch >= n; FSKHIP_LAYOUT_SAMPLE_MAJOR has it at t * pitch + s and needs pitch >= n_streams, and the columns from n_streams on
+ * of a wider frame are neither read nor written.  The contract is fskhip_processor_process_*'s: either side may be NULL, zero
+ * lengths are legal, the two flags mean what they mean there.
+ *   RX  the processor and its engine end in exactly the state fskhip_processor_process_* leaves when handed the floats
+ *       decode(d_in): every ring byte and word, every engine state word, the counters, a decimator left mid-pair by an odd n_in.
+ *       (One ingest launch widens the quantum into a float tile kept with the processor; the demodulators run on that.)
+ *   TX  element (s, t) of d_out is encode(x), x the float fskhip_processor_process_* writes at (s, t) -- the format's silence where
+ *       that zero-fills --, and every generator and completion word ends as there.  (The kernel that generates the samples encodes
+ *       and stores them: no float tile, no second launch.)
+ * FSKHIP_SAMPLES_F32 in stream-major layout on both sides IS fskhip_processor_process_*.  With FSKHIP_PROC_GRAPH the quantum is
+ * one linear capture on the caller's stream; formats and layouts are part of what a replay must match.  The _host form keeps
+ * narrow staging with the processor: a stream-major side crosses as one 2-D copy of narrow rows, a sample-major side as one copy
+ * of n frames (out: n_streams elements per frame, the caller's other columns stay as they are; in: at the caller's frame pitch, so
+ * the columns from n_streams on of a wider input frame cross the link with the rest -- the host reads them, the device ignores
+ * them: a caller whose frames are much wider than the batch pays for them on PCIe), all on the processor's stream with one
+ * synchronise at the end.  FSKHIP_E_INVALID before any device call, in this order: a null processor; an unknown format or
+ * layout (the input side first, whether or not the side is NULL); a pitch that is too small (of a side that is not NULL); a
+ * pointer that is not aligned to its element.
+ */
+int fskhip_processor_process_fmt_device(fskhip_processor *p, const void *d_in, int in_format, int in_layout, size_t n_in,
+                                        size_t in_pitch, void *d_out, int out_format, int out_layout, size_t n_out,
+                                        size_t out_pitch, uint32_t flags, void *hip_stream);
+int fskhip_processor_process_fmt_host(fskhip_processor *p, const void *in, int in_format, int in_layout, size_t n_in,
+                                      size_t in_pitch, void *out, int out_format, int out_layout, size_t n_out, size_t out_pitch,
+                                      uint32_t flags);
+
+/*
  * The 'modulate' request (fsk-processor.ts:87-113) for the streams with mask[s] != 0 (mask NULL = all):
  * pendingModulation = new ChunkedModulator(fskCore); startModulation(payload) (chunked-modulator.ts:31-39:
  * the whole signal is generated now; an EMPTY payload leaves the stream with a pending modulator that never

@@ -402,4 +402,4 @@ class FSKBatchSharded {
 const snapshotInfo = (buf) => addon.snapshotInfo(buf);
 const snapshotConcat = (bufs) => addon.snapshotConcat(bufs);
 
-module.exports = { FSKCore, FSKBatch, FSKBatchSharded, SAMPLE_FORMATS, SAMPLE_LAYOUTS, snapshotInfo, snapshotConcat, DEFAULT_FSK_CONFIG, Event, EventEmitter, PRECISION_F32, PRECISION_F64, addon };
+module.exports = { FSKCore, FSKBatch, FSKBatchSharded, SAMPLE_FORMATS, SAMPLE_LAYOUTS, sampleFormat, sampleLayout, snapshotInfo, snapshotConcat, DEFAULT_FSK_CONFIG, Event, EventEmitter, PRECISION_F32, PRECISION_F64, addon };

@@ -1,6 +1,6 @@
 // Typings of napi/fsk-processor.js and napi/chunked-modulator.js (src/webaudio/processors/fsk-processor.ts,
 // src/webaudio/chunked-modulator.ts on the device).
-import { FSKBatch, FSKConfig, FSKCore, FSKStatus } from './fsk-core';
+import { FSKBatch, FSKConfig, FSKCore, FSKStatus, SampleArray, SampleFormat, SampleLayout } from './fsk-core';
 export declare const PROC_CLEAR_RX_ON_TX_COMPLETE: 1;
 export declare const PROC_GRAPH: 2;
 /** FSKProcessorBatch.snapshot(): the FSKBatch's stream snapshot and the processors' own image */
@@ -11,6 +11,10 @@ export declare class FSKProcessorBatch {
   readonly nStreams: number;
   /** process(inputs, outputs) for every stream: inputs [S][nIn] or null; returns [S][nOut] or null */
   process(inputs: Float32Array | null, nIn: number, nOut: number): Float32Array | null;
+  /** process() with either side in a capture format and layout: 'stream' = [S][pitch >= n], 'sample' = interleaved frames [n][pitch >= S];
+   *  returns the output format's typed array (null when nOut is 0); state and output are process()'s on the decoded floats */
+  processSamples(inputs: SampleArray | null, input?: { format?: SampleFormat; layout?: SampleLayout; nIn?: number; pitch?: number },
+    output?: { format?: SampleFormat; layout?: SampleLayout; nOut?: number; pitch?: number }): SampleArray | null;
   /** 'modulate': throws 'Modulation already in progress' when a selected stream still has one */
   modulate(payloads: Uint8Array[], mask?: boolean[]): void;
   txState(): { pos: Uint32Array; total: Uint32Array; pending: Uint8Array; completed: Uint32Array };

@@ -6,7 +6,7 @@
 // pending modulations along with the batch's streams (FSKBatch.remap / snapshot / fromSnapshot underneath).
 const path = require('path');
 const addon = require(path.join(__dirname, 'fsk_addon.node'));
-const { FSKBatch } = require(path.join(__dirname, 'fsk-core.js'));
+const { FSKBatch, sampleFormat, sampleLayout } = require(path.join(__dirname, 'fsk-core.js'));
 const PROC_CLEAR_RX_ON_TX_COMPLETE = 1, PROC_GRAPH = 2;
 
 class FSKProcessorBatch {
@@ -69,6 +69,30 @@ class FSKProcessorBatch {
   process(inputs, nIn, nOut) {
     if (inputs) this.processDemodulationCallCount++;
     return addon.processorProcess(this.handle, inputs || null, inputs ? nIn : 0, inputs ? nIn : 0, nOut || 0, this.flags);
+  }
+  // process() with either side in a capture format and layout (fskhip_processor_process_fmt_host): inputs is the input format's typed
+  // array -- Float32Array 'f32', Int16Array 's16', Uint8Array 'mulaw' / 'alaw' -- or null, input = {format, layout, nIn, pitch},
+  // output = {format, layout, nOut, pitch}; layout 'stream' = [S][pitch >= n], 'sample' = interleaved frames [n][pitch >= S]; format
+  // defaults to 'f32', layout to 'stream', pitch to the packed one.  Returns the output format's typed array, or null when nOut is 0.
+  // The samples cross PCIe as they are; state and output are those of process() on the decoded floats, the output encoded.
+  processSamples(inputs, input = {}, output = {}) {
+    if (input === null || typeof input !== 'object' || output === null || typeof output !== 'object') {
+      throw new TypeError('processSamples: input and output must be objects {format, layout, nIn | nOut, pitch}');
+    }
+    const inFmt = sampleFormat(input.format === undefined ? 'f32' : input.format), inLay = sampleLayout(input.layout);
+    const outFmt = sampleFormat(output.format === undefined ? 'f32' : output.format), outLay = sampleLayout(output.layout);
+    const count = (v, what) => {
+      const n = v === undefined ? 0 : v;
+      if (!Number.isInteger(n) || n < 0 || n > 0xffffffff) throw new RangeError('processSamples: ' + what + ' must be an integer in [0, 2^32)');
+      return n;
+    };
+    const has = inputs !== undefined && inputs !== null;
+    if (has && !ArrayBuffer.isView(inputs)) throw new TypeError('processSamples: inputs must be a typed array or null');
+    const nIn = has ? count(input.nIn, 'nIn') : 0, nOut = count(output.nOut, 'nOut');
+    const inPitch = count(input.pitch, 'input pitch') || (inLay ? this.nStreams : nIn);
+    const outPitch = count(output.pitch, 'output pitch') || (outLay ? this.nStreams : nOut);
+    if (has) this.processDemodulationCallCount++;      // (as process() counts: behind the argument checks, in front of the call)
+    return addon.processorProcessSamples(this.handle, has ? inputs : null, inFmt, inLay, nIn, inPitch, outFmt, outLay, nOut, outPitch, this.flags);
   }
   // 'modulate' (87-113): payloads = array of S Uint8Array; mask = optional array of S booleans
   modulate(payloads, mask) {

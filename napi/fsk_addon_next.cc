@@ -9,6 +9,8 @@
 //   xmodemScan(bytes: Uint8Array, pitch, counts: Uint32Array, expected: Uint32Array, device) -> {data, dataPitch, results: Int32Array[10*S]}
 //   processorCreate(engine, rxCapacity) -> handle;  processorDestroy(handle)
 //   processorProcess(handle, input: Float32Array|null, nIn, inPitch, nOut, flags) -> Float32Array|null
+//   processorProcessSamples(handle, input: Float32Array|Int16Array|Uint8Array|null, inFormat, inLayout, nIn, inPitch, outFormat, outLayout,
+//     nOut, outPitch, flags) -> the output format's typed array | null: the same with either side in a capture format and layout
 //   processorModulate(handle, payloads: Uint8Array, lens: Uint32Array, pitch, mask: Uint8Array|null)
 //   processorTxState(handle) -> {pos, total, pending, completed};  processorRxLength(handle) -> Uint32Array
 //   processorDrain(handle, capacity) -> {out, outPitch, counts};  processorReset(handle, stream)
@@ -164,6 +166,44 @@ napi_value ProcessorProcess(napi_env env, napi_callback_info info) {
   napi_value out_v = nullptr;
   if (n_out) out_v = make_typed(env, napi_float32_array, (size_t)n_out * h->S, 4, &out);
   int rc = fskhip_processor_process_host(h->p, (float *)in, n_in, in_pitch, (float *)out, n_out, n_out, flags);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  if (!out_v) napi_get_null(env, &out_v);
+  return out_v;
+}
+
+// elements a [rows][pitch] array of rows x cols samples needs (the last row may end with its own samples); -1: pitch < cols
+static inline int64_t samples_needed(int32_t layout, uint32_t S, uint32_t n, uint32_t pitch) {
+  const size_t rows = layout == FSKHIP_LAYOUT_SAMPLE_MAJOR ? n : S, cols = layout == FSKHIP_LAYOUT_SAMPLE_MAJOR ? S : n;
+  if (pitch < cols) return -1;
+  return rows ? (int64_t)pitch * (int64_t)(rows - 1) + (int64_t)cols : 0;
+}
+
+// process() with either side in a capture format and layout (fskhip_processor_process_fmt_host): the input is the input format's
+// typed array or null, the result a new array of the output format's type, [S][outPitch] or [nOut][outPitch >= S] (its padding the
+// format's silence), or null when nOut is 0
+napi_value ProcessorProcessSamples(napi_env env, napi_callback_info info) {
+  ARGS(11);
+  const int32_t in_format = i32(env, argv[2]), in_layout = i32(env, argv[3]), out_format = i32(env, argv[6]), out_layout = i32(env, argv[7]);
+  if (!sample_format_ok(env, in_format, in_layout) || !sample_format_ok(env, out_format, out_layout)) return nullptr;
+  Proc *h = get_proc(env, argv[0]);
+  if (!h) return nullptr;
+  void *in; size_t ilen;
+  if (!typed(env, argv[1], sample_array_type(in_format), &in, &ilen, true)) return nullptr;
+  const uint32_t n_in = u32(env, argv[4]), in_pitch = u32(env, argv[5]), n_out = u32(env, argv[8]), out_pitch = u32(env, argv[9]), flags = u32(env, argv[10]);
+  if (in) {
+    const int64_t need = samples_needed(in_layout, h->S, n_in, in_pitch);
+    if (need < 0 || (size_t)need > ilen) { napi_throw_range_error(env, nullptr, "input too short"); return nullptr; }
+  }
+  void *out = nullptr;
+  napi_value out_v = nullptr;
+  if (n_out) {
+    const int64_t need = samples_needed(out_layout, h->S, n_out, out_pitch);
+    if (need < 0) { napi_throw_range_error(env, nullptr, "output pitch too small"); return nullptr; }
+    out_v = make_typed(env, sample_array_type(out_format), (size_t)need, fskhip_sample_bytes(out_format), &out);
+    if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+    fill_silence(out_format, out, (size_t)need);
+  }
+  int rc = fskhip_processor_process_fmt_host(h->p, in, in_format, in_layout, n_in, in_pitch, out, out_format, out_layout, n_out, out_pitch, flags);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   if (!out_v) napi_get_null(env, &out_v);
   return out_v;
@@ -723,6 +763,7 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"processorCreate", nullptr, ProcessorCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorDestroy", nullptr, ProcessorDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorProcess", nullptr, ProcessorProcess, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"processorProcessSamples", nullptr, ProcessorProcessSamples, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorModulate", nullptr, ProcessorModulate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorTxState", nullptr, ProcessorTxState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRxLength", nullptr, ProcessorRxLength, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -157,6 +157,8 @@ _SYMBOLS = [
     ("fskhip_processor_destroy", C.c_int, [_P]),
     ("fskhip_processor_process_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_uint32, _P]),
     ("fskhip_processor_process_host", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_uint32]),
+    ("fskhip_processor_process_fmt_device", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, _P]),
+    ("fskhip_processor_process_fmt_host", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32]),
     ("fskhip_processor_modulate_host", C.c_int, [_P, _P, _P, C.c_size_t, _P]),
     ("fskhip_processor_tx_state_host", C.c_int, [_P, _P, _P, _P, _P]),
     ("fskhip_processor_rx_drain_host", C.c_int, [_P, _P, C.c_size_t, _P]),

@@ -84,6 +84,10 @@ uint8_t host_synth_payload_byte(uint64_t seed, uint32_t stream, uint32_t frame, 
 void host_synth_stream_params(uint64_t seed, uint32_t stream, uint32_t lead_max, double amp_lo, double amp_hi, uint32_t *lead, double *amp);
 hipError_t launch_processor_io(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out, size_t demod_pitch, const uint32_t *demod_counts,
                                bool do_rx, float *out, size_t n_out, size_t out_pitch, bool clear_rx_on_complete, hipStream_t st);
+// the same quantum with `out` in a capture format and layout (FSKHIP_SAMPLES_* / FSKHIP_LAYOUT_*, checked by the caller; out_pitch in
+// elements): one launch, the kernel encodes behind its generator.  float32 stream-major is launch_processor_io.
+hipError_t launch_processor_io_fmt(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out, size_t demod_pitch, const uint32_t *demod_counts,
+                                   bool do_rx, void *out, int format, int layout, size_t n_out, size_t out_pitch, bool clear_rx_on_complete, hipStream_t st);
 hipError_t launch_processor_tx_start(const ModParams &M, const ProcState &T, const uint8_t *payloads, const uint32_t *lens, size_t payload_pitch, const uint8_t *mask,
                                      hipStream_t st);
 hipError_t launch_processor_rx_drain(const ProcState &T, uint32_t n_streams, uint8_t *out, size_t out_pitch, uint32_t *counts, hipStream_t st);

@@ -14,6 +14,7 @@
 #include "fsk_params.h"
 #include "fsk_wait.h"
 #include "fsk_launch.h"
+#include "fsk_samples_dev.h"
 
 namespace fsk {
 
@@ -551,6 +552,132 @@ __global__ __launch_bounds__(64) void processor_io_kernel(ModParams M, const dou
   if (rx_dirty && valid) { T.rx_w[stream] = w; T.rx_r[stream] = r; T.rx_len[stream] = len; }
 }
 
+// The same quantum with the output in a capture format and layout (fskhip_processor_process_fmt_*; FMT / LAYOUT: include/fskhip.h's
+// FSKHIP_SAMPLES_* / FSKHIP_LAYOUT_*): processor_io_kernel's bookkeeping and generator, statement for statement, and behind the
+// generator SampleFmt<FMT>::encode -- element (s, t) of `out_` is the code of the float that kernel writes there, its zero fill the
+// format's silence.  The codes leave the registers for `out_` themselves: no float tile in HBM, no second launch.
+//   sample-major   [sample][channel] frames: a lane is a stream, so a wave instruction stores 64 consecutive elements of one frame;
+//                  columns from n_streams on are not written.
+//   stream-major   the lane packs its row's 32 codes of a tile into kTile * sizeof(element) / 4 words of LDS (rows an odd number of
+//                  words apart: every bank once per half wave); the wave then stores them as 16-byte vectors, 16 / 32 rows of
+//                  64 / 32 contiguous bytes per instruction (16-bit / G.711), or -- where the base or the pitch is off the 16-byte
+//                  grid (vec_ok = 0) -- as single elements, two rows of 32 consecutive ones per instruction.  float32 in this layout
+//                  is processor_io_kernel itself.
+template <bool EXACT, int FMT, int LAYOUT>
+__global__ __launch_bounds__(64) void processor_io_fmt_kernel(ModParams M, const double *__restrict__ coef, ProcState T,
+                                                              const uint8_t *__restrict__ demod_out, size_t demod_pitch,
+                                                              const uint32_t *__restrict__ demod_counts, int do_rx,
+                                                              void *__restrict__ out_, size_t n_out, size_t out_pitch,
+                                                              int vec_ok, uint32_t clear_rx_on_complete) {
+  static_assert(FMT != FSKHIP_SAMPLES_F32 || LAYOUT != FSKHIP_LAYOUT_STREAM_MAJOR, "float32 stream-major is processor_io_kernel");
+  using F = SampleFmt<FMT>;
+  const uint32_t lane = threadIdx.x;
+  const uint32_t stream = blockIdx.x * 64u + lane;
+  const bool valid = stream < M.n_streams;
+  const uint32_t row = valid ? stream : M.n_streams - 1;
+  const size_t ns = M.n_streams;
+
+  uint32_t w = T.rx_w[row], r = T.rx_r[row], len = T.rx_len[row];
+  bool rx_dirty = false;
+  if (do_rx && valid) {
+    uint32_t cnt = demod_counts[stream];
+    if ((size_t)cnt > demod_pitch) cnt = (uint32_t)demod_pitch;
+    const uint8_t *src = demod_out + (size_t)stream * demod_pitch;
+    uint8_t *ring = T.rx_buf + (size_t)stream * T.rx_cap;
+    for (uint32_t i = 0; i < cnt; i++) {  // put(): overwrite the oldest when full
+      ring[w] = src[i];
+      w = w + 1 == T.rx_cap ? 0u : w + 1;
+      if (len < T.rx_cap) len++;
+      else r = r + 1 == T.rx_cap ? 0u : r + 1;
+    }
+    rx_dirty = cnt != 0;
+  }
+
+  if (out_ != nullptr && n_out > 0) {
+    const uint32_t flen = T.tx_len[row];
+    const bool active = valid && T.tx_pending[row] != 0u && flen > 0u && T.tx_pos[row] < flen;
+    const uint8_t *prow = T.tx_payload + (size_t)row * T.tx_payload_pitch;
+    auto pb = [&](uint32_t i) -> uint8_t { return prow[i]; };
+    FrameGen G;
+    G.start(M, coef[(size_t)CF_mark_w * ns + row], coef[(size_t)CF_space_w * ns + row], T.tx_n_payload[row]);
+    if (active) {
+      G.phase = T.tx_phase[row]; G.pos = T.tx_pos[row]; G.in_bit = T.tx_in_bit[row];
+      G.bit_idx = T.tx_bit_idx[row]; G.cur_bit = T.tx_cur_bit[row];
+    } else {
+      G.pos = G.frame_len;  // nothing to emit: zeros
+    }
+    typename F::Bits *const out = (typename F::Bits *)out_;
+    constexpr uint32_t kEsz = (uint32_t)sizeof(typename F::Bits);
+    constexpr uint32_t kWords = (uint32_t)kTile * kEsz / 4u;          // words of codes per row of a tile
+    constexpr uint32_t kRowPitch = kWords + 1u;                       // odd
+    __shared__ uint32_t codes[LAYOUT == FSKHIP_LAYOUT_STREAM_MAJOR ? 64u * kRowPitch : 1u];
+    for (size_t t0 = 0; t0 < n_out; t0 += kTile) {
+      if constexpr (LAYOUT == FSKHIP_LAYOUT_STREAM_MAJOR) __syncthreads();   // (the tile's readers of the round before)
+      for (uint32_t c = 0; c < (uint32_t)kChunks; c++) {
+        const size_t base = t0 + 4u * c;
+        const float4 v = frame_next4<EXACT>(G, M, pb, base + 0 < n_out, base + 1 < n_out, base + 2 < n_out, base + 3 < n_out);
+        const float o[4] = {v.x, v.y, v.z, v.w};
+        uint32_t k[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) k[j] = F::encode(o[j]);
+        if constexpr (LAYOUT == FSKHIP_LAYOUT_SAMPLE_MAJOR) {
+#pragma unroll
+          for (int j = 0; j < 4; j++)
+            if (valid && base + j < n_out) out[(base + j) * out_pitch + stream] = (typename F::Bits)k[j];
+        } else if constexpr (kEsz == 2) {
+          codes[lane * kRowPitch + 2u * c] = k[0] | (k[1] << 16);
+          codes[lane * kRowPitch + 2u * c + 1u] = k[2] | (k[3] << 16);
+        } else {
+          codes[lane * kRowPitch + c] = k[0] | (k[1] << 8) | (k[2] << 16) | (k[3] << 24);
+        }
+      }
+      if constexpr (LAYOUT == FSKHIP_LAYOUT_STREAM_MAJOR) {
+        __syncthreads();
+        constexpr uint32_t kVecEls = 16u / kEsz;                      // elements of a 16-byte vector
+        if (vec_ok) {
+          constexpr uint32_t kLanesPerRow = kWords / 4u, kRowsPerStore = 64u / kLanesPerRow;
+          const uint32_t sub_row = lane / kLanesPerRow, q = lane % kLanesPerRow;
+#pragma unroll
+          for (uint32_t i = 0; i < kLanesPerRow; i++) {
+            const uint32_t lr = kRowsPerStore * i + sub_row;
+            const uint32_t rr = blockIdx.x * 64u + lr;
+            const size_t c0 = t0 + (size_t)kVecEls * q;
+            if (rr >= M.n_streams || c0 >= n_out) continue;
+            const uint32_t *src = &codes[lr * kRowPitch + 4u * q];
+            typename F::Bits *dst = out + (size_t)rr * out_pitch + c0;
+            if (c0 + kVecEls <= n_out) {
+              *reinterpret_cast<uint4 *>(dst) = make_uint4(src[0], src[1], src[2], src[3]);
+            } else {   // the row's last, partial vector
+              for (uint32_t e = 0; c0 + e < n_out; e++) dst[e] = (typename F::Bits)(src[e * kEsz / 4u] >> (8u * ((e * kEsz) & 3u)));
+            }
+          }
+        } else {
+          const uint32_t half = lane >> 5, e = lane & 31u;
+          const size_t col = t0 + e;
+#pragma unroll 4
+          for (uint32_t i = 0; i < 32u; i++) {
+            const uint32_t lr = 2u * i + half;
+            const uint32_t rr = blockIdx.x * 64u + lr;
+            if (rr < M.n_streams && col < n_out)
+              out[(size_t)rr * out_pitch + col] = (typename F::Bits)(codes[lr * kRowPitch + e * kEsz / 4u] >> (8u * ((e * kEsz) & 3u)));
+          }
+        }
+      }
+    }
+    if (active) {
+      if (G.pos >= flen) {  // isComplete: ChunkedModulator.reset() + pendingModulation = null
+        T.tx_pos[stream] = 0u; T.tx_len[stream] = 0u; T.tx_pending[stream] = 0u;
+        T.tx_completed[stream] += 1u;
+        if (clear_rx_on_complete) { w = 0u; r = 0u; len = 0u; rx_dirty = true; }
+      } else {
+        T.tx_phase[stream] = G.phase; T.tx_pos[stream] = G.pos; T.tx_in_bit[stream] = G.in_bit;
+        T.tx_bit_idx[stream] = G.bit_idx; T.tx_cur_bit[stream] = G.cur_bit;
+      }
+    }
+  }
+  if (rx_dirty && valid) { T.rx_w[stream] = w; T.rx_r[stream] = r; T.rx_len[stream] = len; }
+}
+
 // startModulation() for the selected streams: take the payload, arm the generator at sample 0
 __global__ void processor_tx_start_kernel(ModParams M, ProcState T, const uint8_t *__restrict__ payloads,
                                           const uint32_t *__restrict__ lens, size_t payload_pitch,
@@ -612,6 +739,27 @@ hipError_t launch_processor_io(const ModParams &M, const double *coef, const Pro
   else
     hipLaunchKernelGGL(processor_io_kernel<false>, dim3(blocks), dim3(64), 0, st, M, coef, T, demod_out, demod_pitch,
                        demod_counts, do_rx ? 1 : 0, out, n_out, out_pitch, vec_ok, clear_rx_on_complete ? 1u : 0u);
+  return hipGetLastError();
+}
+// every format-writing instantiation, once: [exact sine][format][layout] in the order of include/fskhip.h's enums; float32
+// stream-major is processor_io_kernel's
+#define FSK_IO_FMT_ROW(EXACT, FMT) {FSK_K(processor_io_fmt_kernel, EXACT, FMT, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(processor_io_fmt_kernel, EXACT, FMT, FSKHIP_LAYOUT_SAMPLE_MAJOR)}
+#define FSK_IO_FMT_KERNELS(EXACT)                                                                                                   \
+  {{{nullptr, nullptr}, FSK_K(processor_io_fmt_kernel, EXACT, FSKHIP_SAMPLES_F32, FSKHIP_LAYOUT_SAMPLE_MAJOR)}, FSK_IO_FMT_ROW(EXACT, FSKHIP_SAMPLES_S16), \
+   FSK_IO_FMT_ROW(EXACT, FSKHIP_SAMPLES_MULAW), FSK_IO_FMT_ROW(EXACT, FSKHIP_SAMPLES_ALAW)}
+using IoFmtFn = void (*)(ModParams, const double *, ProcState, const uint8_t *, size_t, const uint32_t *, int, void *, size_t, size_t, int, uint32_t);
+static const KernelEntry<IoFmtFn> kIoFmtKernels[2][4][2] = {FSK_IO_FMT_KERNELS(false), FSK_IO_FMT_KERNELS(true)};
+
+hipError_t launch_processor_io_fmt(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out,
+                                   size_t demod_pitch, const uint32_t *demod_counts, bool do_rx, void *out, int format, int layout,
+                                   size_t n_out, size_t out_pitch, bool clear_rx_on_complete, hipStream_t st) {
+  if (format == FSKHIP_SAMPLES_F32 && layout == FSKHIP_LAYOUT_STREAM_MAJOR)
+    return launch_processor_io(M, coef, T, demod_out, demod_pitch, demod_counts, do_rx, (float *)out, n_out, out_pitch, clear_rx_on_complete, st);
+  const uint32_t blocks = (M.n_streams + 63u) / 64u;
+  const size_t esz = sample_bytes(format);
+  const int vec_ok = out && (out_pitch * esz % 16 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15u) == 0);
+  hipLaunchKernelGGL(kIoFmtKernels[M.exact_sin ? 1 : 0][format][layout].fn, dim3(blocks), dim3(64), 0, st, M, coef, T, demod_out, demod_pitch,
+                     demod_counts, do_rx ? 1 : 0, out, n_out, out_pitch, vec_ok, clear_rx_on_complete ? 1u : 0u);
   return hipGetLastError();
 }
 hipError_t launch_processor_tx_start(const ModParams &M, const ProcState &T, const uint8_t *payloads, const uint32_t *lens,

@@ -60,7 +60,7 @@ int fskhip_processor_destroy(fskhip_processor *p) {
   drop_graph(p);
   void *bufs[] = {p->T.rx_buf, p->T.rx_w, p->T.rx_r, p->T.rx_len, p->T.tx_payload, p->T.tx_phase, p->T.tx_pos, p->T.tx_len,
                   p->T.tx_in_bit, p->T.tx_bit_idx, p->T.tx_cur_bit, p->T.tx_n_payload, p->T.tx_pending, p->T.tx_completed,
-                  p->d_bytes, p->d_counts, p->d_eod, p->d_in, p->d_out, p->d_stage, p->d_u32, p->d_mask, p->d_lists};
+                  p->d_bytes, p->d_counts, p->d_eod, p->d_in, p->d_out, p->d_stage, p->d_u32, p->d_mask, p->d_lists, p->d_fin, p->d_nin, p->d_nout};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   if (p->stream) (void)hipStreamDestroy(p->stream);
@@ -123,47 +123,10 @@ int fskhip_processor_process_device(fskhip_processor *p, float *d_in, size_t n_i
   }
   HIP_TRY(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)hip_stream;
-  if (d_in) {  // byte slab of this quantum: grown outside any capture
-    const size_t need = engine_max_bytes(p->e, n_in);
-    if (need > p->bytes_pitch) {
-      HIP_TRY(hipDeviceSynchronize());
-      drop_graph(p);
-      if (p->d_bytes) (void)hipFree(p->d_bytes);
-      p->d_bytes = nullptr; p->bytes_pitch = 0;
-      int rc = dev_alloc(p->d_bytes, need * p->S);
-      if (rc != FSKHIP_OK) return rc;
-      p->bytes_pitch = need;
-    }
-  }
-  // timing events / the trace capture are per-launch host decisions: no replay while either is armed
-  engine_refresh_kernel_choice(p->e);
-  if (engine_launch_key(p->e) & (8u | 16u)) flags &= ~FSKHIP_PROC_GRAPH;
-  if (!(flags & FSKHIP_PROC_GRAPH)) return launch_quantum(p, d_in, n_in, in_pitch, d_out, n_out, out_pitch, flags, st);
-
-  if (!st) return fail(FSKHIP_E_INVALID, "FSKHIP_PROC_GRAPH needs an explicit stream (the null stream cannot be captured)");
-  fskhip_processor::Key key{d_in, n_in, in_pitch, d_out, n_out, out_pitch, flags, st, engine_launch_key(p->e)};
-  if (!p->graph_exec || !(key == p->graph_key)) {
-    drop_graph(p);
-    hipGraph_t graph = nullptr;
-    HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    int rc = launch_quantum(p, d_in, n_in, in_pitch, d_out, n_out, out_pitch, flags, st);
-    hipError_t cerr = hipStreamEndCapture(st, &graph);
-    if (rc != FSKHIP_OK) {
-      if (graph) (void)hipGraphDestroy(graph);
-      return rc;
-    }
-    if (cerr != hipSuccess) return fail(FSKHIP_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(cerr));
-    hipError_t ierr = hipGraphInstantiate(&p->graph_exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ierr != hipSuccess) { p->graph_exec = nullptr; return fail(FSKHIP_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ierr)); }
-    p->graph_key = key;
-    // the capture itself already did the host-side accounting of one call; it launched nothing
-    HIP_TRY(hipGraphLaunch(p->graph_exec, st));
-    return FSKHIP_OK;
-  }
-  if (d_in) engine_note_replayed_call(p->e, n_in);
-  HIP_TRY(hipGraphLaunch(p->graph_exec, st));
-  return FSKHIP_OK;
+  if (d_in)   // byte slab of this quantum
+    if (const int rc = grow_byte_slab(p, n_in)) return rc;
+  return run_quantum(p, {d_in, n_in, in_pitch, d_out, n_out, out_pitch, flags, st, 0u}, d_in != nullptr,
+                     [&](uint32_t f) { return launch_quantum(p, d_in, n_in, in_pitch, d_out, n_out, out_pitch, f, st); });
 }
 
 int fskhip_processor_process_host(fskhip_processor *p, float *in, size_t n_in, size_t in_pitch, float *out, size_t n_out,

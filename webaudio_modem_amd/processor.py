@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import PROC_CLEAR_RX_ON_TX_COMPLETE, PROC_GRAPH  # noqa: F401
-from .engine import FSKEngine, _blob, _struct_dict
+from .engine import FSKEngine, _blob, _struct_dict, _sample_codes, sample_args, samples_out
 
 
 class ChunkedModulator:
@@ -182,6 +182,36 @@ class FSKProcessorBatch:
     def process_device(self, d_in, n_in, in_pitch, d_out, n_out, out_pitch, stream=None, flags=None):
         _lib.check(self._L.fskhip_processor_process_device(self._h, d_in, n_in, in_pitch, d_out, n_out, out_pitch,
                                                            self.flags if flags is None else flags, stream))
+
+    def process_samples(self, inputs=None, in_fmt="f32", in_layout="stream", n_out=0, out_fmt="f32", out_layout="stream"):
+        """process() with either side in a capture format (SAMPLE_FORMATS: "f32", "s16", "mulaw", "alaw") and layout
+        (SAMPLE_LAYOUTS: "stream" = [S, n], "sample" = [n, S], interleaved frames): fskhip_processor_process_fmt_host.  inputs: an
+        array of in_fmt's dtype in in_layout's shape (rows may be a block of a wider array, whose other columns are ignored), or
+        None; returns an array of out_fmt's dtype, [S, n_out] or [n_out, S] (None when n_out == 0).  The samples cross PCIe as
+        they are; the state ends as process() leaves it on the decoded floats, the output is process()'s, encoded."""
+        in_code, in_lay = _sample_codes(in_fmt, in_layout)
+        out_code, out_lay = _sample_codes(out_fmt, out_layout)      # (every argument check comes before the call is counted)
+        x, n_in, in_pitch = None, 0, 0
+        if inputs is not None:
+            x, in_code, in_lay, S, n_in, in_pitch = sample_args(inputs, in_fmt, in_layout)
+            if in_pitch is None:      # (an array without elements has no strides to speak of: its rows are packed)
+                in_pitch = max(x.shape[1], 1)
+            if S != self.n_streams:
+                raise ValueError("inputs must be [n_streams, n] (layout 'stream') or [n, n_streams] (layout 'sample')")
+            self.processDemodulationCallCount += 1
+        out, out_pitch = None, 0
+        if n_out:
+            out, out_code, out_lay, out_pitch = samples_out(out_fmt, out_layout, self.n_streams, int(n_out))
+        _lib.check(self._L.fskhip_processor_process_fmt_host(
+            self._h, x.ctypes.data if x is not None else None, in_code, in_lay, n_in, in_pitch,
+            out.ctypes.data if out is not None else None, out_code, out_lay, int(n_out), out_pitch, self.flags))
+        return out
+
+    def process_samples_device(self, d_in, in_fmt, in_layout, n_in, in_pitch, d_out, out_fmt, out_layout, n_out, out_pitch, stream=None, flags=None):
+        """fskhip_processor_process_fmt_device: device pointers (ints or None), pitches in elements, asynchronous on `stream`"""
+        _lib.check(self._L.fskhip_processor_process_fmt_device(self._h, d_in, *_sample_codes(in_fmt, in_layout, True), n_in, in_pitch,
+                                                               d_out, *_sample_codes(out_fmt, out_layout, True), n_out, out_pitch,
+                                                               self.flags if flags is None else flags, stream))
 
     # ---- 'modulate' fsk-processor.ts:87-113 ------------------------------------------------------------
     def modulate(self, payloads, mask=None):
