@@ -433,6 +433,129 @@ int fskhip_xmodem_tx_state_set(fskhip_xmodem_tx *t, const uint32_t *state, const
 int fskhip_xmodem_tx_reset(fskhip_xmodem_tx *t, int64_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The resident XModem file receiver (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): XModemTransport.receiveData()
+ * (xmodem.ts:186-335) for every stream of a processor.  fskhip_xmodem_rx above runs the receive grammar and leaves ACK / NAK,
+ * the retry counter and the file to the host; this handle keeps all of them on the device, with the split the sender uses:
+ * grammar, state, file and transmissions on the device, the timers with the host, as masks.  During a transfer only events
+ * cross to the host, one record per stream where something happened; the assembled file is read once, at the end.
+ * fskhip_xmodem_rx is unchanged and stays the tool for a host that wants the bytes poll by poll.
+ *
+ * State per stream, kept with this handle and NOT in the processor: state (FSKHIP_XR_*, the reference's RECEIVING_* names),
+ * expected (receive.expectedSequence, 1..255), retries (send.retries, which receiveAllPackets counts), file_len,
+ * packets_received and dropped (statistics.packetsReceived / packetsDropped, counted as fskhip_xmodem_result counts them),
+ * packets_sent (every control byte transmitted); and the stream's file, a row of file_capacity bytes on the device.
+ *
+ * fskhip_xmodem_recv_create   file_capacity: bytes of file store per stream; max_retries: config.maxRetries.  Grows the
+ *                             processor's payload store to hold 1 byte where needed and sizes the _host form's
+ *                             staging for n_streams events, so that no poll allocates.
+ *                             FSKHIP_E_UNSUPPORTED when n_streams x file_capacity or n_streams x rx_capacity exceeds 2^32 - 1.
+ * fskhip_xmodem_recv_start_host  receiveData() up to its first wait for the streams with (mask == NULL || mask[s]).  ensureIdle
+ *                             first: if any selected stream is not FSKHIP_XR_IDLE the call returns FSKHIP_E_BUSY with the
+ *                             reference's text, 'Transport busy: receiveData cannot start while in RECEIVING_WAIT_BLOCK state'
+ *                             (the state's own name) followed by ' (stream N)', and starts nothing.  If a selected stream has
+ *                             tx_pending != 0: FSKHIP_E_BUSY, 'Modulation already in progress (stream N)', nothing started.
+ *                             Then initializeReceive (xmodem.ts:221-225): expected 1, file length 0, retries 0.  The RX ring
+ *                             is NOT cleared: the reference clears only its own receive.buffer, and what the channel buffered
+ *                             before the call is still delivered.  Then the NAK byte is started on the processor exactly as
+ *                             fskhip_processor_modulate_host starts it, packets_sent++, state FSKHIP_XR_SEND_NAK.
+ * fskhip_xmodem_recv_reset    reset() (xmodem.ts:370-383) for one stream or all (stream < 0): IDLE, expected 1, retries 0, file
+ *                             length 0, the three counters 0.  The ring and a pending modulation are left alone.
+ * fskhip_xmodem_recv_state_get / _state_set  the seven arrays ([n_streams] each, any pointer may be NULL): state, expected,
+ *                             retries, file_len, packets_received, dropped, packets_sent.  state_set validates everything before
+ *                             it sets anything and names the first bad stream: state <= FSKHIP_XR_SEND_ACK, expected in 1..255,
+ *                             file_len <= file_capacity.
+ * fskhip_xmodem_recv_files_host  the assembled files of streams sel[0 .. n_sel) in CSR form: offsets has n_sel + 1 entries, the
+ *                             file of sel[i] is data[offsets[i] .. offsets[i+1]).  Packed on the device into one contiguous
+ *                             buffer, which crosses in one copy.  *n_bytes takes the true size; cap_bytes too small returns
+ *                             FSKHIP_E_OVERFLOW and copies nothing (offsets are still written), so cap_bytes 0 is a size query.
+ *                             Does not change the receiver.  The partial file of a transfer that failed stays readable until
+ *                             the next start or reset.
+ * fskhip_xmodem_recv_files_set_host  puts files back (file_len included), to carry a receiver across a remap or a restore:
+ *                             files_set_host first, then state_set.  Refuses a file longer than file_capacity.
+ * All of these synchronise with the processor's outstanding work.  The processor must outlive every call but _destroy.
+ * The device cannot see a modulation end: SEND_NAK and SEND_ACK become WAIT_BLOCK LAZILY, at the first poll that finds
+ * tx_pending == 0 -- state_get may report SEND_* after the control byte has gone out.
+ *
+ * One poll.  A stream is SELECTED when (mask == NULL || mask[s]) and its state is not FSKHIP_XR_IDLE.  It follows the first of
+ * rules 1-3 that applies (mask, timeout and abort may each be NULL: all, none, none):
+ *   1. abort[s]: status ABORTED, state IDLE -- the external signal or reset(): checkAbort ends in 'Operation aborted'.  The ring
+ *      and any pending modulation are left alone; the partial file stays.
+ *   2. the processor's tx_pending[s] != 0: nothing happens, no word is touched, the stream is not listed -- the reference is
+ *      inside `await sendControl()`, where no timer runs; timeout[s] is ignored.
+ *   3. otherwise a SEND_* state becomes WAIT_BLOCK, and with L = the live ring bytes, oldest first, the receive grammar
+ *      (fskhip_xmodem_scan_host's) runs from expected[s] and STOPS AT THE FIRST STEP THAT OWES A REPLY: the reference awaits
+ *      each control byte's modulation before it reads on, so one poll makes at most one transmission per stream.
+ *      accepted packet  (CRC matches) payload appended to the file, expected = expected % 255 + 1, retries = 0,
+ *                       packets_received++, the bytes through the packet's end leave the ring, ACK is transmitted, state
+ *                       SEND_ACK.  If the payload would not fit in file_capacity: status FILE_FULL, state IDLE, nothing
+ *                       transmitted, no counter moves and the packet stays in the ring (line noise in front of its SOH has left).
+ *                       The reference has no such limit: this is the resident store's own.
+ *      duplicate        (the previous sequence) dropped++, its bytes leave, ACK is transmitted; the state stays WAIT_BLOCK
+ *                       and retries is untouched (xmodem.ts:309-314).
+ *      error            INVALID_SEQUENCE, INVALID_CRC or UNEXPECTED_SEQUENCE: the counters move as fskhip_xmodem_result
+ *                       counts them, ALL of L leaves the ring; then ++retries > max_retries ends the transfer -- status
+ *                       MAX_RETRIES, state IDLE, nothing sent ('Receive failed after max retries: ...') --, otherwise NAK is
+ *                       transmitted.
+ *      EOT              where a packet could start: the bytes through it leave, those behind it stay; ACK is transmitted,
+ *                       status DONE, state IDLE.  An empty file is a legal result.
+ *      no such step     line noise in front of an incomplete packet leaves, the packet stays at the ring's front, SOH included.
+ *                       With timeout[s] the wait's timer has fired: the whole ring is cleared and the ++retries rule above
+ *                       follows (NAK or MAX_RETRIES).  A timeout flag on a stream that had a reply-owing step is ignored.
+ *      Every transmission counts in packets_sent; each is one byte, built on the device and started as
+ *      fskhip_processor_modulate_host starts it (tx_pending was 0, so it cannot be busy).
+ * The event: status, state_after, control (the byte transmitted, else -1), step (the FSKHIP_XM_* status of the grammar step;
+ * NEED_MORE for an accepted packet, a duplicate and a bare timeout), seq and len of the packet concerned (else -1),
+ * accepted_len (bytes appended by this poll), file_len, expected and retries after the poll (retries is max_retries + 1 after
+ * MAX_RETRIES), crc_rx / crc_calc as in fskhip_xmodem_result.  A stream is LISTED when status != PROGRESS or something was
+ * transmitted.  A stream whose poll only swallowed noise is advanced and not listed.  A stream that is not selected is not
+ * touched in any word.  Output: the listed streams ascending in streams[0 .. n_events), events[i] that of streams[i].
+ * Overflow: if n_events > cap_streams the call returns FSKHIP_E_OVERFLOW with the true count and changes NOTHING -- no ring
+ * word, no receiver word, no file byte, no modulation.  cap_streams 0 with null lists is therefore a size query.  _device is
+ * asynchronous on `hip_stream`, pointers on the processor's device; d_totals takes three words: n_events, 0, and 1 if the poll
+ * was committed, 0 if it stood down.  The handle keeps scratch: one poll at a time per handle.
+ * What is invariant: while no error, timeout or abort occurs (duplicates allowed), the sequence of transmissions, the file and
+ * every word at quiescence do not depend on where polls fall or on how the bytes were split between them.  Once an error has
+ * cleared the ring the result depends on what had arrived at poll time, as it does in the reference.
+ * FSKHIP_E_INVALID before any device call, in this order.  poll: null n_events (_host) / null d_totals (_device); a null streams
+ * or events with cap_streams != 0; a null receiver.  create: a null processor or a null out.  start_host, state_get, state_set,
+ * reset: a null receiver (reset: then a stream out of range).  files_host: null n_bytes; a null sel or offsets with n_sel != 0;
+ * a null data with cap_bytes != 0; a null receiver; a sel entry out of range.  files_set_host: a null sel, offsets with
+ * n_sel != 0; a null receiver; then, entry by entry, a sel out of range, offsets[i] > offsets[i+1], a file longer than
+ * file_capacity, a file with null data.  A poll makes the processor a used one and is never part of the captured quantum graph.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct fskhip_xmodem_recv fskhip_xmodem_recv;
+enum { FSKHIP_XR_IDLE = 0, FSKHIP_XR_SEND_NAK = 1, FSKHIP_XR_WAIT_BLOCK = 2, FSKHIP_XR_SEND_ACK = 3 };   /* state */
+enum { FSKHIP_XR_PROGRESS = 0, FSKHIP_XR_DONE = 1, FSKHIP_XR_MAX_RETRIES = 2, FSKHIP_XR_ABORTED = 3, FSKHIP_XR_FILE_FULL = 4 };   /* status */
+typedef struct fskhip_xmodem_recv_event {
+  uint32_t status, state_after;
+  int32_t  control;        /* the byte transmitted by this poll (0x06 / 0x15), else -1 */
+  uint32_t step;           /* FSKHIP_XM_* of the grammar step */
+  int32_t  seq, len;       /* of the packet concerned, else -1 */
+  uint32_t accepted_len;   /* bytes appended to the file by this poll */
+  uint32_t file_len, expected, retries;   /* after the poll */
+  int32_t  crc_rx, crc_calc;
+} fskhip_xmodem_recv_event;
+
+int fskhip_xmodem_recv_create(fskhip_processor *p, uint32_t file_capacity, uint32_t max_retries, fskhip_xmodem_recv **out);
+int fskhip_xmodem_recv_destroy(fskhip_xmodem_recv *r);
+int fskhip_xmodem_recv_start_host(fskhip_xmodem_recv *r, const uint8_t *mask);
+int fskhip_xmodem_recv_poll_host(fskhip_xmodem_recv *r, const uint8_t *mask, const uint8_t *timeout, const uint8_t *abort,
+                                 uint32_t *streams, fskhip_xmodem_recv_event *events, uint32_t cap_streams, uint32_t *n_events);
+int fskhip_xmodem_recv_poll_device(fskhip_xmodem_recv *r, const uint8_t *d_mask, const uint8_t *d_timeout, const uint8_t *d_abort,
+                                   uint32_t *d_streams, fskhip_xmodem_recv_event *d_events, uint32_t cap_streams,
+                                   uint32_t *d_totals, void *hip_stream);
+int fskhip_xmodem_recv_state_get(fskhip_xmodem_recv *r, uint32_t *state, uint32_t *expected, uint32_t *retries, uint32_t *file_len,
+                                 uint32_t *packets_received, uint32_t *dropped, uint32_t *packets_sent);
+int fskhip_xmodem_recv_state_set(fskhip_xmodem_recv *r, const uint32_t *state, const uint32_t *expected, const uint32_t *retries,
+                                 const uint32_t *file_len, const uint32_t *packets_received, const uint32_t *dropped,
+                                 const uint32_t *packets_sent);
+int fskhip_xmodem_recv_reset(fskhip_xmodem_recv *r, int64_t stream);
+int fskhip_xmodem_recv_files_host(fskhip_xmodem_recv *r, const uint32_t *sel, uint32_t n_sel, uint64_t *offsets, uint8_t *data,
+                                  size_t cap_bytes, uint64_t *n_bytes);
+int fskhip_xmodem_recv_files_set_host(fskhip_xmodem_recv *r, const uint32_t *sel, uint32_t n_sel, const uint64_t *offsets,
+                                      const uint8_t *data);
+
+/* ---------------------------------------------------------------------------------------------------
  * FIR half of src/dsp/filters.ts: FIRFilter (112-167) batched over streams, and the windowed-sinc designs
  * (243-314) + FilterFactory.createFIR* (346-368).
  * ------------------------------------------------------------------------------------------------- */

@@ -22,6 +22,12 @@
 //   xmodemTxSend(handle, mask: Uint8Array|null, offsets: Uint32Array[nStreams + 1], data: Uint8Array)
 //   xmodemTxPoll(handle, mask: Uint8Array|null, abort: Uint8Array|null) -> {streams: Uint32Array, events: Int32Array[8*n]}
 //   xmodemTxState(handle) -> {state, sequence, fragmentIndex, retries, packetsSent, retransmitted: Uint32Array};  xmodemTxSetState(handle, the six|null)
+//   xmodemRecvCreate(processor, fileCapacity, maxRetries) -> handle;  xmodemRecvDestroy(handle);  xmodemRecvReset(handle, stream)
+//   xmodemRecvStart(handle, mask: Uint8Array|null)
+//   xmodemRecvPoll(handle, mask, timeout, abort: Uint8Array|null) -> {streams: Uint32Array, events: Int32Array[12*n]}
+//   xmodemRecvFiles(handle, sel: Uint32Array) -> {offsets: Float64Array[n + 1], data: Uint8Array}
+//   xmodemRecvSetFiles(handle, sel: Uint32Array, offsets: Uint32Array[n + 1], data: Uint8Array)
+//   xmodemRecvState(handle) -> {state, expected, retries, fileLen, packetsReceived, dropped, packetsSent: Uint32Array};  xmodemRecvSetState(handle, the seven|null)
 //   processorRemap(dst, src, map: number[]);  processorSnapshot(handle, sel: number[]|null) -> Buffer
 //   processorRestore(dst, snapshot: Uint8Array, map: number[]);  processorSnapshotInfo(snapshot) -> {nStreams, rxCapacity, payloadCapacity, recordBytes}
 //   sincLowpass/sincHighpass(cutoff, sampleRate, numTaps), sincBandpass(center, bandwidth, sampleRate, numTaps) -> Float64Array
@@ -543,6 +549,168 @@ napi_value XmodemTxSetState(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// ---- the resident XModem file receiver (include/fskhip_next.h: fskhip_xmodem_recv_*) over a processor handle, boxed as the sender is
+struct XmRecv { fskhip_xmodem_recv *r; uint32_t S; };
+void xm_recv_finalize(napi_env, void *data, void *) {
+  XmRecv *h = (XmRecv *)data;
+  if (h->r) fskhip_xmodem_recv_destroy(h->r);
+  delete h;
+}
+XmRecv *get_xm_recv(napi_env env, napi_value v) {
+  XmRecv *h = (XmRecv *)external(env, v, "receiver destroyed");
+  if (h && !h->r) { napi_throw_error(env, nullptr, "receiver destroyed"); return nullptr; }
+  return h;
+}
+napi_value XmodemRecvCreate(napi_env env, napi_callback_info info) {
+  ARGS(3);
+  Proc *p = get_proc(env, argv[0]);
+  if (!p) return nullptr;
+  uint32_t file_capacity = 0, max_retries = 0;
+  napi_get_value_uint32(env, argv[1], &file_capacity);
+  napi_get_value_uint32(env, argv[2], &max_retries);
+  fskhip_xmodem_recv *r = nullptr;
+  int rc = fskhip_xmodem_recv_create(p->p, file_capacity, max_retries, &r);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  XmRecv *h = new XmRecv{r, p->S};
+  napi_value ext;
+  if (napi_create_external(env, h, xm_recv_finalize, nullptr, &ext) != napi_ok) { xm_recv_finalize(env, h, nullptr); napi_throw_error(env, nullptr, "xmodemRecvCreate: no handle"); return nullptr; }
+  return ext;
+}
+napi_value XmodemRecvDestroy(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  void *q = nullptr;
+  if (napi_get_value_external(env, argv[0], &q) == napi_ok && q) {
+    XmRecv *h = (XmRecv *)q;
+    if (h->r) fskhip_xmodem_recv_destroy(h->r);
+    h->r = nullptr;
+  }
+  return nullptr;
+}
+napi_value XmodemRecvStart(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  XmRecv *h = get_xm_recv(env, argv[0]);
+  if (!h) return nullptr;
+  void *mask; size_t mlen;
+  if (!typed(env, argv[1], napi_uint8_array, &mask, &mlen, true)) return nullptr;
+  if (mask && mlen != h->S) { napi_throw_range_error(env, nullptr, "xmodemRecvStart: mask must have one entry per stream"); return nullptr; }
+  int rc = fskhip_xmodem_recv_start_host(h->r, (const uint8_t *)mask);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+// sized with a query call (an overflowing poll changes nothing), then polled into arrays of exactly that size
+napi_value XmodemRecvPoll(napi_env env, napi_callback_info info) {
+  ARGS(4);
+  XmRecv *h = get_xm_recv(env, argv[0]);
+  if (!h) return nullptr;
+  void *m[3]; size_t len[3];
+  for (int i = 0; i < 3; i++) {
+    if (!typed(env, argv[1 + i], napi_uint8_array, &m[i], &len[i], true)) return nullptr;
+    if (m[i] && len[i] != h->S) { napi_throw_range_error(env, nullptr, "xmodemRecvPoll: mask, timeout and abort must have one entry per stream"); return nullptr; }
+  }
+  uint32_t n_events = 0;
+  int rc = fskhip_xmodem_recv_poll_host(h->r, (const uint8_t *)m[0], (const uint8_t *)m[1], (const uint8_t *)m[2], nullptr, nullptr, 0, &n_events);
+  if (rc != FSKHIP_OK && rc != FSKHIP_E_OVERFLOW) return throw_fsk(env, rc);
+  void *streams, *events;
+  napi_value str_v = make_typed(env, napi_uint32_array, n_events, 4, &streams);
+  napi_value ev_v = make_typed(env, napi_int32_array, 12 * (size_t)n_events, 4, &events);
+  if (!str_v || !ev_v) { napi_throw_error(env, nullptr, "xmodemRecvPoll: out of memory"); return nullptr; }
+  if (rc == FSKHIP_E_OVERFLOW) {
+    rc = fskhip_xmodem_recv_poll_host(h->r, (const uint8_t *)m[0], (const uint8_t *)m[1], (const uint8_t *)m[2], (uint32_t *)streams, (fskhip_xmodem_recv_event *)events,
+                                      n_events, &n_events);
+    if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  }
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "streams", str_v);
+  napi_set_named_property(env, o, "events", ev_v);
+  return o;
+}
+napi_value XmodemRecvReset(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  XmRecv *h = get_xm_recv(env, argv[0]);
+  if (!h) return nullptr;
+  int64_t s = -1;
+  napi_get_value_int64(env, argv[1], &s);
+  int rc = fskhip_xmodem_recv_reset(h->r, s);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+// sized with a query call (a cap that is too small copies nothing), then read into an array of exactly that size
+napi_value XmodemRecvFiles(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  XmRecv *h = get_xm_recv(env, argv[0]);
+  if (!h) return nullptr;
+  void *sel; size_t n_sel;
+  if (!typed(env, argv[1], napi_uint32_array, &sel, &n_sel)) return nullptr;
+  if (n_sel > 0xFFFFFFFFull) { napi_throw_range_error(env, nullptr, "xmodemRecvFiles: too many streams"); return nullptr; }
+  std::vector<uint64_t> offsets(n_sel + 1, 0u);
+  uint64_t n_bytes = 0;
+  int rc = fskhip_xmodem_recv_files_host(h->r, (const uint32_t *)sel, (uint32_t)n_sel, offsets.data(), nullptr, 0, &n_bytes);
+  if (rc != FSKHIP_OK && rc != FSKHIP_E_OVERFLOW) return throw_fsk(env, rc);
+  void *data, *off;
+  napi_value data_v = make_typed(env, napi_uint8_array, (size_t)n_bytes, 1, &data);
+  napi_value off_v = make_typed(env, napi_float64_array, n_sel + 1, 8, &off);
+  if (!data_v || !off_v) { napi_throw_error(env, nullptr, "xmodemRecvFiles: out of memory"); return nullptr; }
+  if (rc == FSKHIP_E_OVERFLOW) {
+    rc = fskhip_xmodem_recv_files_host(h->r, (const uint32_t *)sel, (uint32_t)n_sel, offsets.data(), (uint8_t *)data, (size_t)n_bytes, &n_bytes);
+    if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  }
+  for (size_t i = 0; i <= n_sel; i++) ((double *)off)[i] = (double)offsets[i];
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "offsets", off_v);
+  napi_set_named_property(env, o, "data", data_v);
+  return o;
+}
+napi_value XmodemRecvSetFiles(napi_env env, napi_callback_info info) {
+  ARGS(4);
+  XmRecv *h = get_xm_recv(env, argv[0]);
+  if (!h) return nullptr;
+  void *sel, *off, *data; size_t n_sel, olen, dlen;
+  if (!typed(env, argv[1], napi_uint32_array, &sel, &n_sel) || !typed(env, argv[2], napi_uint32_array, &off, &olen) || !typed(env, argv[3], napi_uint8_array, &data, &dlen))
+    return nullptr;
+  if (olen != n_sel + 1 || n_sel > 0xFFFFFFFFull) { napi_throw_range_error(env, nullptr, "xmodemRecvSetFiles: offsets must have one entry per selected stream and one more"); return nullptr; }
+  std::vector<uint64_t> offsets(olen);
+  for (size_t i = 0; i < olen; i++) {
+    offsets[i] = ((const uint32_t *)off)[i];
+    if (offsets[i] > dlen) { napi_throw_range_error(env, nullptr, "xmodemRecvSetFiles: an offset lies behind the data"); return nullptr; }
+  }
+  int rc = fskhip_xmodem_recv_files_set_host(h->r, (const uint32_t *)sel, (uint32_t)n_sel, offsets.data(), (const uint8_t *)data);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+const char *const kXmRecvWords[7] = {"state", "expected", "retries", "fileLen", "packetsReceived", "dropped", "packetsSent"};
+napi_value XmodemRecvState(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  XmRecv *h = get_xm_recv(env, argv[0]);
+  if (!h) return nullptr;
+  void *a[7]; napi_value v[7];
+  for (int i = 0; i < 7; i++) {
+    v[i] = make_typed(env, napi_uint32_array, h->S, 4, &a[i]);
+    if (!v[i]) { napi_throw_error(env, nullptr, "xmodemRecvState: out of memory"); return nullptr; }
+  }
+  int rc = fskhip_xmodem_recv_state_get(h->r, (uint32_t *)a[0], (uint32_t *)a[1], (uint32_t *)a[2], (uint32_t *)a[3], (uint32_t *)a[4], (uint32_t *)a[5], (uint32_t *)a[6]);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  for (int i = 0; i < 7; i++) napi_set_named_property(env, o, kXmRecvWords[i], v[i]);
+  return o;
+}
+napi_value XmodemRecvSetState(napi_env env, napi_callback_info info) {
+  ARGS(8);
+  XmRecv *h = get_xm_recv(env, argv[0]);
+  if (!h) return nullptr;
+  void *a[7]; size_t n[7];
+  for (int i = 0; i < 7; i++) {
+    if (!typed(env, argv[1 + i], napi_uint32_array, &a[i], &n[i], true)) return nullptr;
+    if (a[i] && n[i] != h->S) { napi_throw_range_error(env, nullptr, "xmodemRecvSetState: state arrays must have one entry per stream"); return nullptr; }
+  }
+  int rc = fskhip_xmodem_recv_state_set(h->r, (const uint32_t *)a[0], (const uint32_t *)a[1], (const uint32_t *)a[2], (const uint32_t *)a[3], (const uint32_t *)a[4],
+                                        (const uint32_t *)a[5], (const uint32_t *)a[6]);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+
 // ---- processor remap / snapshots (include/fskhip_next.h): a snapshot is a Buffer (or any Uint8Array) on this side
 napi_value ProcessorRemap(napi_env env, napi_callback_info info) {
   ARGS(3);
@@ -783,6 +951,15 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"xmodemTxReset", nullptr, XmodemTxReset, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"xmodemTxState", nullptr, XmodemTxState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"xmodemTxSetState", nullptr, XmodemTxSetState, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRecvCreate", nullptr, XmodemRecvCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRecvDestroy", nullptr, XmodemRecvDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRecvStart", nullptr, XmodemRecvStart, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRecvPoll", nullptr, XmodemRecvPoll, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRecvReset", nullptr, XmodemRecvReset, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRecvFiles", nullptr, XmodemRecvFiles, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRecvSetFiles", nullptr, XmodemRecvSetFiles, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRecvState", nullptr, XmodemRecvState, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRecvSetState", nullptr, XmodemRecvSetState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRemap", nullptr, ProcessorRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorSnapshot", nullptr, ProcessorSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRestore", nullptr, ProcessorRestore, nullptr, nullptr, nullptr, napi_default, nullptr},

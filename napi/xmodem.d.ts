@@ -77,3 +77,43 @@ export declare class XModemSenderBatch {
   setState(state: { [K in keyof SenderState]?: ArrayLike<number> | null }): void;
   close(): void;
 }
+
+/** fskhip_xmodem_recv_event of one stream */
+export interface FileReceiverEvent {
+  status: number; statusName: 'progress' | 'done' | 'max_retries' | 'aborted' | 'file_full';
+  /** what receiveData() would have thrown (the start of its text), or null */
+  error: string | null;
+  stateAfter: number; stateName: string;
+  /** the byte transmitted by this poll (0x06 / 0x15), else -1 */
+  control: number;
+  /** the FSKHIP_XM_* status of the grammar step */
+  step: number; stepName: string;
+  /** of the packet concerned, else -1 */
+  seq: number; len: number;
+  /** bytes appended to the file by this poll */
+  acceptedLen: number;
+  fileLen: number; expected: number; retries: number; crcRx: number; crcCalc: number;
+}
+export interface FileReceiverState {
+  state: Uint32Array; expected: Uint32Array; retries: Uint32Array; fileLen: Uint32Array; packetsReceived: Uint32Array; dropped: Uint32Array; packetsSent: Uint32Array;
+}
+/** XModemTransport.receiveData() for every stream of an FSKProcessorBatch, resident on the device (fskhip_xmodem_recv_*) */
+export declare class XModemFileReceiverBatch {
+  constructor(processor: { handle: unknown; nStreams: number }, options?: { fileCapacity?: number; maxRetries?: number });
+  readonly nStreams: number;
+  readonly fileCapacity: number;
+  readonly maxRetries: number;
+  /** receiveData() up to its first wait: the initial NAK is modulated */
+  start(options?: { mask?: ArrayLike<boolean | number> | null }): void;
+  /** at most one reply-owing step per waiting stream; timeout: the streams whose wait's timer has fired; abort: the streams to abort */
+  poll(options?: { mask?: ArrayLike<boolean | number> | null; timeout?: ArrayLike<boolean | number> | null; abort?: ArrayLike<boolean | number> | null }):
+    { streams: Uint32Array; events: FileReceiverEvent[] };
+  /** the assembled files of `streams` (default: all) */
+  files(streams?: ArrayLike<number> | null): Uint8Array[];
+  setFiles(files: ArrayLike<ArrayLike<number> | null>, options?: { mask?: ArrayLike<boolean | number> | null }): void;
+  /** reset(): IDLE, expected 1, retries 0, an empty file, the counters 0, for one stream or all (-1) */
+  reset(stream?: number): void;
+  state(): FileReceiverState;
+  setState(state: { [K in keyof FileReceiverState]?: ArrayLike<number> | null }): void;
+  close(): void;
+}

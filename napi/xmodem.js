@@ -201,4 +201,90 @@ class XModemSenderBatch {
   }
 }
 
-module.exports = { XModemReceiverBatch, XModemSenderBatch, CRC16, XModemPacket, ControlType, PacketConstants, crc16Batch, serializeBatch, scanBursts };
+// receiveData() of XModemTransport for every stream of an FSKProcessorBatch, resident on the device (fskhip_xmodem_recv_*): start() sends
+// the initial NAK, poll() walks each waiting stream's RX ring up to the first step of the receive grammar that owes a reply, appends an
+// accepted payload to the stream's file on the device, counts retries and starts the ACK or NAK on the processor.  Only events come back;
+// files() reads the assembled files once, at the end.  The timers are the caller's: poll({timeout}) names the streams whose wait's timer
+// has fired, poll({abort}) the streams to abort.
+const RECV_STATES = ['IDLE', 'RECEIVING_SEND_NAK', 'RECEIVING_WAIT_BLOCK', 'RECEIVING_SEND_ACK'];
+const RECV_STATUS = ['progress', 'done', 'max_retries', 'aborted', 'file_full'];
+const RECV_ERRORS = [null, null, 'Receive failed after max retries', 'Operation aborted', 'File store full'];
+const RECV_WORDS = ['state', 'expected', 'retries', 'fileLen', 'packetsReceived', 'dropped', 'packetsSent'];
+class XModemFileReceiverBatch {
+  constructor(processor, options = {}) {
+    if (processor === null || typeof processor !== 'object' || !Number.isInteger(processor.nStreams)) throw new TypeError('XModemFileReceiverBatch: processor must be an FSKProcessorBatch');
+    if (options === null || typeof options !== 'object') throw new TypeError('XModemFileReceiverBatch: options must be an object {fileCapacity, maxRetries}');
+    const { fileCapacity = 65536, maxRetries = 10 } = options;
+    if (!Number.isInteger(fileCapacity) || fileCapacity < 0 || fileCapacity > 0xffffffff) throw new RangeError('XModemFileReceiverBatch: fileCapacity must be an integer in [0, 2^32)');
+    if (!Number.isInteger(maxRetries) || maxRetries < 0 || maxRetries > 0xffffffff) throw new RangeError('XModemFileReceiverBatch: maxRetries must be an integer in [0, 2^32)');
+    this.processor = processor;
+    this.nStreams = processor.nStreams;
+    this.fileCapacity = fileCapacity;
+    this.maxRetries = maxRetries;
+    this.handle = addon.xmodemRecvCreate(processor.handle, fileCapacity, maxRetries);
+  }
+  close() { if (this.handle) { addon.xmodemRecvDestroy(this.handle); this.handle = null; } }
+  // receiveData() up to its first wait for every stream, or those of options.mask: the initial NAK is modulated.  A stream that is still
+  // receiving, or whose processor is mid-modulation, throws the reference's text and nothing is started.
+  start(options = {}) {
+    if (options === null || typeof options !== 'object') throw new TypeError('start: options must be an object {mask}');
+    addon.xmodemRecvStart(this.handle, boolArray('start', 'mask', options.mask, this.nStreams));
+  }
+  // {streams, events}: the streams where something happened in ascending order, and one event each
+  poll(options = {}) {
+    if (options === null || typeof options !== 'object') throw new TypeError('poll: options must be an object {mask, timeout, abort}');
+    const n = this.nStreams;
+    const r = addon.xmodemRecvPoll(this.handle, boolArray('poll', 'mask', options.mask, n), boolArray('poll', 'timeout', options.timeout, n), boolArray('poll', 'abort', options.abort, n));
+    const events = Array.from(r.streams, (_, i) => {
+      const q = r.events.subarray(i * 12, i * 12 + 12);
+      return { status: q[0], statusName: RECV_STATUS[q[0]], error: RECV_ERRORS[q[0]], stateAfter: q[1], stateName: RECV_STATES[q[1]], control: q[2], step: q[3],
+        stepName: XM_STATUS[q[3]], seq: q[4], len: q[5], acceptedLen: q[6], fileLen: q[7], expected: q[8], retries: q[9], crcRx: q[10], crcCalc: q[11] };
+    });
+    return { streams: r.streams, events };
+  }
+  _sel(who, streams) {
+    if (streams === undefined || streams === null) return Uint32Array.from({ length: this.nStreams }, (_, i) => i);
+    if (!Array.isArray(streams) && !ArrayBuffer.isView(streams)) throw new TypeError(who + ': streams must be an array of stream indices');
+    for (const s of streams) if (!Number.isInteger(s) || s < 0 || s >= this.nStreams) throw new RangeError(who + ': streams must hold integers in [0, ' + this.nStreams + ')');
+    return Uint32Array.from(streams);
+  }
+  // the assembled files of `streams` (default: all), one Uint8Array each: packed on the device, one copy
+  files(streams) {
+    const sel = this._sel('files', streams);
+    const r = addon.xmodemRecvFiles(this.handle, sel);
+    return Array.from(sel, (_, i) => r.data.slice(r.offsets[i], r.offsets[i + 1]));
+  }
+  // puts files back (one per stream; those of options.mask, the other entries are ignored): before setState, to carry a receiver across a remap
+  setFiles(files, options = {}) {
+    if (!Array.isArray(files)) throw new TypeError('setFiles: files must be an array of nStreams byte arrays');
+    if (files.length !== this.nStreams) throw new RangeError('setFiles: files must have one entry per stream (' + this.nStreams + ')');
+    if (options === null || typeof options !== 'object') throw new TypeError('setFiles: options must be an object {mask}');
+    const m = boolArray('setFiles', 'mask', options.mask, this.nStreams);
+    const sel = [], rows = [];
+    files.forEach((f, s) => {
+      if (m && !m[s]) return;
+      if (!Array.isArray(f) && !ArrayBuffer.isView(f)) throw new TypeError('setFiles: files[' + s + '] must be a byte array');
+      sel.push(s); rows.push(Uint8Array.from(f));
+    });
+    const offsets = new Uint32Array(sel.length + 1);
+    let total = 0;
+    rows.forEach((r, i) => { offsets[i] = total; total += r.length; });
+    if (total > 0xffffffff) throw new RangeError('setFiles: the files together exceed 2^32 - 1 bytes');
+    offsets[sel.length] = total;
+    const data = new Uint8Array(total);
+    rows.forEach((r, i) => data.set(r, offsets[i]));
+    addon.xmodemRecvSetFiles(this.handle, Uint32Array.from(sel), offsets, data);
+  }
+  // reset() (xmodem.ts:370-383) for one stream, or all (-1): IDLE, expected 1, retries 0, an empty file, the counters 0
+  reset(stream = -1) {
+    if (!Number.isInteger(stream)) throw new TypeError('reset: stream must be an integer (-1: all)');
+    addon.xmodemRecvReset(this.handle, stream);
+  }
+  state() { return addon.xmodemRecvState(this.handle); }   // {state, expected, retries, fileLen, packetsReceived, dropped, packetsSent}: Uint32Array per stream
+  setState(state) {                                         // what state() returned, or any part of it
+    if (state === null || typeof state !== 'object') throw new TypeError('setState: state must be an object {' + RECV_WORDS.join(', ') + '}');
+    addon.xmodemRecvSetState(this.handle, ...RECV_WORDS.map((k) => stateArray(k, state[k], this.nStreams)));
+  }
+}
+
+module.exports = { XModemReceiverBatch, XModemSenderBatch, XModemFileReceiverBatch, CRC16, XModemPacket, ControlType, PacketConstants, crc16Batch, serializeBatch, scanBursts };

@@ -17,6 +17,8 @@ PROC_CLEAR_RX_ON_TX_COMPLETE, PROC_GRAPH = 1, 2
 XM_NEED_MORE, XM_EOT, XM_TRUNCATED, XM_INVALID_SEQUENCE, XM_INVALID_CRC, XM_UNEXPECTED_SEQUENCE = 0, 1, 2, 3, 4, 5
 XT_IDLE, XT_WAIT_NAK, XT_WAIT_ACK, XT_WAIT_FINAL_ACK = 0, 1, 2, 3
 XT_PROGRESS, XT_DONE, XT_MAX_RETRIES, XT_ABORTED = 0, 1, 2, 3
+XR_IDLE, XR_SEND_NAK, XR_WAIT_BLOCK, XR_SEND_ACK = 0, 1, 2, 3
+XR_PROGRESS, XR_DONE, XR_MAX_RETRIES, XR_ABORTED, XR_FILE_FULL = 0, 1, 2, 3, 4
 PRECISION_F32, PRECISION_F64 = 0, 1
 DEMOD_WRITEBACK_AGC = 1
 SAMPLES_F32, SAMPLES_S16, SAMPLES_MULAW, SAMPLES_ALAW = 0, 1, 2, 3
@@ -78,6 +80,15 @@ class XModemTxEvent(C.Structure):
     _fields_ = [
         ("status", C.c_uint32), ("state_after", C.c_uint32), ("control", C.c_int32), ("sent_len", C.c_uint32),
         ("sequence", C.c_uint32), ("fragment_index", C.c_uint32), ("n_fragments", C.c_uint32), ("retries", C.c_uint32),
+    ]
+
+
+class XModemRecvEvent(C.Structure):
+    """fskhip_xmodem_recv_event (include/fskhip_next.h)."""
+    _fields_ = [
+        ("status", C.c_uint32), ("state_after", C.c_uint32), ("control", C.c_int32), ("step", C.c_uint32),
+        ("seq", C.c_int32), ("len", C.c_int32), ("accepted_len", C.c_uint32), ("file_len", C.c_uint32),
+        ("expected", C.c_uint32), ("retries", C.c_uint32), ("crc_rx", C.c_int32), ("crc_calc", C.c_int32),
     ]
 
 
@@ -186,6 +197,16 @@ _SYMBOLS = [
     ("fskhip_xmodem_tx_state_get", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     ("fskhip_xmodem_tx_state_set", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     ("fskhip_xmodem_tx_reset", C.c_int, [_P, C.c_int64]),
+    ("fskhip_xmodem_recv_create", C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    ("fskhip_xmodem_recv_destroy", C.c_int, [_P]),
+    ("fskhip_xmodem_recv_start_host", C.c_int, [_P, _P]),
+    ("fskhip_xmodem_recv_poll_host", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
+    ("fskhip_xmodem_recv_poll_device", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P]),
+    ("fskhip_xmodem_recv_state_get", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    ("fskhip_xmodem_recv_state_set", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    ("fskhip_xmodem_recv_reset", C.c_int, [_P, C.c_int64]),
+    ("fskhip_xmodem_recv_files_host", C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_size_t, _P]),
+    ("fskhip_xmodem_recv_files_set_host", C.c_int, [_P, _P, C.c_uint32, _P, _P]),
     ("fskhip_sinc_lowpass", C.c_int, [C.c_double, C.c_double, C.c_uint32, _P]),
     ("fskhip_sinc_highpass", C.c_int, [C.c_double, C.c_double, C.c_uint32, _P]),
     ("fskhip_sinc_bandpass", C.c_int, [C.c_double, C.c_double, C.c_double, C.c_uint32, _P]),

@@ -1,9 +1,12 @@
 // fsk_host.h -- host-side helpers shared by the C-ABI translation units of libfskhip.so (not part of the ABI): the error
-// string, device selection, device allocation (dev_alloc, and ensure for scratch that grows) and the HIP_TRY macros.  What only
+// string, device selection, device allocation (dev_alloc, and ensure for scratch that grows), the HIP_TRY macros and, behind them,
+// the per-stream word arrays of the resident XModem handles (fill_words, get_words, put_words).  What only
 // some units share lives beside them: fsk_filter_host.h (the two filters' handles and _host calls), fsk_stage.h (image frames
 // and the slab pipelines of the snapshot units), fsk_proc.h (struct fskhip_processor).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <vector>
 
 #include "../../include/fskhip.h"
 #include "../../include/fskhip_next.h"
@@ -44,3 +47,24 @@ int ensure(T *&p, size_t &cap, size_t need) {
     }                                                                                                                  \
   } while (0)
 #define HIP_TRY(expr) HIP_TRY_AS(expr, #expr, false, (void)0)
+
+namespace fsk {
+// per-stream uint32 words on the device, as the three resident XModem handles keep them: n words set to `value`; n words to the
+// host; n words from the host (a null `host` leaves them as they are).  Synchronous copies on the null stream.
+inline int fill_words(uint32_t *d, size_t n, uint32_t value) {
+  if (!n) return FSKHIP_OK;
+  if (value == 0u) { HIP_TRY(hipMemset(d, 0, sizeof(uint32_t) * n)); return FSKHIP_OK; }
+  const std::vector<uint32_t> host(n, value);
+  HIP_TRY(hipMemcpy(d, host.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+  return FSKHIP_OK;
+}
+inline int get_words(std::vector<uint32_t> &host, const uint32_t *d, size_t n) {
+  host.resize(n);
+  if (n) HIP_TRY(hipMemcpy(host.data(), d, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+  return FSKHIP_OK;
+}
+inline int put_words(uint32_t *d, const uint32_t *host, size_t n) {
+  if (n && host) HIP_TRY(hipMemcpy(d, host, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+  return FSKHIP_OK;
+}
+}  // namespace fsk

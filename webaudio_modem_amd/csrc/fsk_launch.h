@@ -176,4 +176,34 @@ hipError_t launch_xmodem_tx_commit(const ProcState &T, uint32_t n_streams, const
                                    fskhip_xmodem_tx_event *d_events, hipStream_t st);
 hipError_t launch_xmodem_tx_repack(const uint8_t *d_old_store, const uint32_t *d_old_off, const uint32_t *d_new_off, const uint32_t *d_lens, const uint8_t *d_keep,
                                    uint32_t n_streams, uint8_t *d_new_store, hipStream_t st);
+// fsk_xmodem_recv.hip: the resident XModem file receiver (fskhip_xmodem_recv_poll_*).  The caller has checked the arguments.
+// XmRecvState: the receiver's per-stream words, the file rows [n_streams][file_cap] and the two settings.  XmRecvScratch: per
+// stream the poll's event, flag word, the bytes to take out of the ring and where the accepted payload starts among the live ring
+// bytes; xmodem_recv_pair_words(n_streams) words of workgroup pairs; the staging slab [n_streams][slab_pitch] with its lengths
+// and mask, in the form launch_processor_tx_start takes.
+// step: decides every selected stream's transition into the scratch, clears tx_mask and nothing else, then the totals
+// {n_events, 0, 1 if they fit cap_streams}.  commit: given those, and only where d_totals[2] is 1, writes the lists, appends the
+// accepted payloads to the file rows, advances the rings, updates the words and puts the control bytes into the slab (tx_lens /
+// tx_mask set for the streams that transmit); the caller launches launch_processor_tx_start(M, T, slab, tx_lens, slab_pitch,
+// tx_mask) behind it.
+// files: pack -- the file rows of streams d_sel[0 .. n_sel) into d_packed at d_offsets (n_sel + 1 entries); otherwise the other
+// way, file_len set to each file's length.
+struct XmRecvState {
+  uint32_t *state, *expected, *retries, *file_len, *packets, *dropped, *sent;
+  uint8_t *files;
+  uint32_t file_cap, max_retries;
+};
+struct XmRecvScratch {
+  fskhip_xmodem_recv_event *ev;
+  uint32_t *flags, *removed, *span, *pairs;
+  uint8_t *slab; uint32_t slab_pitch;
+  uint32_t *tx_lens; uint8_t *tx_mask;
+};
+size_t xmodem_recv_pair_words(uint32_t n_streams);
+hipError_t launch_xmodem_recv_step(const ProcState &T, uint32_t n_streams, const uint8_t *d_mask, const uint8_t *d_timeout, const uint8_t *d_abort,
+                                   const XmRecvState &X, const XmRecvScratch &W, uint32_t cap_streams, uint32_t *d_totals, hipStream_t st);
+hipError_t launch_xmodem_recv_commit(const ProcState &T, uint32_t n_streams, const XmRecvState &X, const XmRecvScratch &W, const uint32_t *d_totals,
+                                     uint32_t *d_streams, fskhip_xmodem_recv_event *d_events, hipStream_t st);
+hipError_t launch_xmodem_recv_files(bool pack, const XmRecvState &X, const uint32_t *d_sel, const uint64_t *d_offsets, uint32_t n_sel, uint8_t *d_packed,
+                                    hipStream_t st);
 }  // namespace fsk

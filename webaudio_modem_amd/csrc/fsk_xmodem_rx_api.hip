@@ -41,14 +41,6 @@ int poll_refusal(const char *fn, const fskhip_xmodem_rx *r, const void *totals, 
   return FSKHIP_OK;
 }
 
-int fill_words(uint32_t *d, size_t n, uint32_t value) {
-  if (!n) return FSKHIP_OK;
-  if (value == 0u) { HIP_TRY(hipMemset(d, 0, sizeof(uint32_t) * n)); return FSKHIP_OK; }
-  const std::vector<uint32_t> host(n, value);
-  HIP_TRY(hipMemcpy(d, host.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-  return FSKHIP_OK;
-}
-
 }  // namespace
 
 extern "C" {

@@ -157,6 +157,12 @@ struct Scan {
 
   FSK_XM_FN bool inside_packet() const { return state != ST_IDLE && state != ST_DONE; }
 
+  // The one-reply mode (the resident receiveData(), fsk_xmodem_recv_step.h): the reference awaits the modulation of each ACK /
+  // NAK before it reads on (xmodem.ts:242, 259, 307, 314), so a walk in this mode feeds bytes only while owes_reply() is false.
+  // True once a step has ended that the receiver answers: an accepted packet or a duplicate (ACK), an error (NAK), an EOT (ACK).
+  // A walk that stops there has seen at most one such step: seq / len / start are that packet's, packets + dropped its count.
+  FSK_XM_FN bool owes_reply() const { return state == ST_DONE || packets + dropped > 0u; }
+
   FSK_XM_FN void store(fskhip_xmodem_result *out) const {
     fskhip_xmodem_result r;
     r.status = status;

@@ -47,25 +47,6 @@ int poll_refusal(const char *fn, const fskhip_xmodem_tx *t, const void *totals, 
   return FSKHIP_OK;
 }
 
-int fill_words(uint32_t *d, size_t n, uint32_t value) {
-  if (!n) return FSKHIP_OK;
-  if (value == 0u) { HIP_TRY(hipMemset(d, 0, sizeof(uint32_t) * n)); return FSKHIP_OK; }
-  const std::vector<uint32_t> host(n, value);
-  HIP_TRY(hipMemcpy(d, host.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-  return FSKHIP_OK;
-}
-
-int get_words(std::vector<uint32_t> &host, const uint32_t *d, size_t n) {
-  host.resize(n);
-  if (n) HIP_TRY(hipMemcpy(host.data(), d, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-  return FSKHIP_OK;
-}
-
-int put_words(uint32_t *d, const uint32_t *host, size_t n) {
-  if (n && host) HIP_TRY(hipMemcpy(d, host, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-  return FSKHIP_OK;
-}
-
 // the store holds `live` bytes of files that stay and is about to take `incoming` more at its end: where they do not fit behind
 // `used`, the files that stay move to the front of a new, larger store
 int make_room(fskhip_xmodem_tx *t, const std::vector<uint8_t> &stays, uint64_t live, uint64_t incoming) {

@@ -3,7 +3,8 @@
 and error texts, plus the batch forms that actually feed a GPU and `scan_bursts`, the receive checks of
 XModemTransport (src/transports/xmodem/xmodem.ts:233-320) applied to the bytes a demodulate call returned; and
 `XModemReceiverBatch`, the same grammar resident on the device over the RX rings of an `FSKProcessorBatch`, and
-`XModemSenderBatch`, `sendData()` for every stream of one: files, packets and the waits' grammar on the device.
+`XModemSenderBatch`, `sendData()` for every stream of one: files, packets and the waits' grammar on the device, and
+`XModemFileReceiverBatch`, `receiveData()` for every stream of one: grammar, ACK / NAK, retries and the file on the device.
 Everything computes in libfskhip.so; there is no CPU path here.
 """
 import ctypes as C
@@ -12,6 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import XModemTxEvent, XT_IDLE, XT_WAIT_NAK, XT_WAIT_ACK, XT_WAIT_FINAL_ACK, XT_PROGRESS, XT_DONE, XT_MAX_RETRIES, XT_ABORTED  # noqa: F401
+from ._lib import XModemRecvEvent, XR_IDLE, XR_SEND_NAK, XR_WAIT_BLOCK, XR_SEND_ACK, XR_PROGRESS, XR_DONE, XR_MAX_RETRIES, XR_ABORTED, XR_FILE_FULL  # noqa: F401
 from ._lib import XModemResult, XM_NEED_MORE, XM_EOT, XM_TRUNCATED, XM_INVALID_SEQUENCE, XM_INVALID_CRC, \
     XM_UNEXPECTED_SEQUENCE  # noqa: F401
 
@@ -341,3 +343,145 @@ class XModemSenderBatch:
         if words:
             raise TypeError("unknown state words: %s" % ", ".join(sorted(words)))
         _lib.check(self._L.fskhip_xmodem_tx_state_set(self._h, *[None if a is None else a.ctypes.data for a in arrs]))
+
+
+# fskhip_xmodem_recv_event as a numpy record: the twelve words, in order
+RECV_EVENT_DTYPE = np.dtype([(k, "<u4" if t is C.c_uint32 else "<i4") for k, t in XModemRecvEvent._fields_])
+RECV_STATE_NAMES = {XR_IDLE: "IDLE", XR_SEND_NAK: "RECEIVING_SEND_NAK", XR_WAIT_BLOCK: "RECEIVING_WAIT_BLOCK", XR_SEND_ACK: "RECEIVING_SEND_ACK"}
+RECV_STATUS_NAMES = {XR_PROGRESS: "progress", XR_DONE: "done", XR_MAX_RETRIES: "max_retries", XR_ABORTED: "aborted", XR_FILE_FULL: "file_full"}
+# what receiveData() throws where a poll ends with that status (xmodem.ts:235, 256); FILE_FULL is the resident store's own limit
+RECV_STATUS_ERRORS = {XR_MAX_RETRIES: "Receive failed after max retries", XR_ABORTED: "Operation aborted", XR_FILE_FULL: "File store full"}
+RECV_WORDS = ("state", "expected", "retries", "file_len", "packets_received", "dropped", "packets_sent")
+
+
+class XModemFileReceiverBatch:
+    """receiveData() of XModemTransport for every stream of an FSKProcessorBatch, resident on the device (fskhip_xmodem_recv_*):
+    `start` sends the initial NAK, a `poll` walks each waiting stream's RX ring up to the first step of the receive grammar that
+    owes a reply, appends an accepted payload to the stream's file on the device, counts retries and starts the ACK or NAK on the
+    processor.  Only events come back; `files` reads the assembled files once, at the end.  The timers are the caller's: a wait
+    that has lasted too long is named in `timeout`, an external abort in `abort`.  The processor must outlive it."""
+
+    def __init__(self, processor, file_capacity=65536, max_retries=10):
+        self.processor = processor
+        self._L = _lib.lib()
+        self.n_streams = processor.n_streams
+        self.file_capacity, self.max_retries = file_capacity, max_retries
+        h = C.c_void_p()
+        _lib.check(self._L.fskhip_xmodem_recv_create(processor._h, file_capacity, max_retries, C.byref(h)))
+        self._h = h
+        self._cap_streams = 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.fskhip_xmodem_recv_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _mask(self, mask, name="mask"):
+        if mask is None:
+            return None
+        m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8)
+        if m.shape != (self.n_streams,):
+            raise ValueError("%s must have one entry per stream" % name)
+        return m
+
+    def _sel(self, streams):
+        sel = np.arange(self.n_streams, dtype=np.uint32) if streams is None else np.ascontiguousarray(streams, dtype=np.uint32)
+        if sel.ndim != 1:
+            raise ValueError("streams must be a list of stream indices")
+        return sel
+
+    def start(self, mask=None):
+        """receiveData() up to its first wait for every stream (or those of `mask`): expected 1, an empty file, retries 0, and the
+        initial NAK is modulated.  A stream that is still receiving, or whose processor is mid-modulation, raises RuntimeError
+        with the reference's text, and nothing is started."""
+        m = self._mask(mask)
+        rc = self._L.fskhip_xmodem_recv_start_host(self._h, None if m is None else m.ctypes.data)
+        if rc == _lib.E_BUSY:
+            raise RuntimeError(self._L.fskhip_last_error().decode("utf-8", "replace"))
+        _lib.check(rc)
+
+    def poll(self, mask=None, timeout=None, abort=None):
+        """(streams, events): the streams where something happened, ascending (uint32), and their event records
+        (RECV_EVENT_DTYPE).  timeout: the streams whose wait's timer has fired; abort: the streams to abort.  The lists are sized
+        to the last poll's and grown on overflow: an overflowing call changes nothing and reports the true count."""
+        m, t, a = self._mask(mask), self._mask(timeout, "timeout"), self._mask(abort, "abort")
+        ne = C.c_uint32(0)
+        while True:
+            cs = self._cap_streams
+            streams, events = np.zeros(cs, np.uint32), np.zeros(cs, RECV_EVENT_DTYPE)
+            rc = self._L.fskhip_xmodem_recv_poll_host(self._h, *[None if x is None else x.ctypes.data for x in (m, t, a)],
+                                                      streams.ctypes.data if cs else None, events.ctypes.data if cs else None, cs, C.byref(ne))
+            if rc != _lib.E_OVERFLOW:
+                _lib.check(rc)
+                break
+            self._cap_streams = max(cs, ne.value)
+        return streams[:ne.value], events[:ne.value]
+
+    def poll_active(self, mask=None, timeout=None, abort=None):
+        """{stream: event dict} of one poll; the dict has the record's words plus status_name, state_name and error (the text
+        receiveData() would have thrown, or None)"""
+        streams, events = self.poll(mask, timeout, abort)
+        out = {}
+        for s, e in zip(streams, events):
+            d = {k: int(e[k]) for k in RECV_EVENT_DTYPE.names}
+            d["status_name"], d["state_name"] = RECV_STATUS_NAMES[d["status"]], RECV_STATE_NAMES[d["state_after"]]
+            d["error"] = RECV_STATUS_ERRORS.get(d["status"])
+            out[int(s)] = d
+        return out
+
+    def files(self, streams=None):
+        """the assembled files of `streams` (default: all), a list of bytes: packed on the device, one copy"""
+        sel = self._sel(streams)
+        offsets, nb = np.zeros(len(sel) + 1, np.uint64), C.c_uint64(0)
+        sel_p = sel.ctypes.data if len(sel) else None
+        rc = self._L.fskhip_xmodem_recv_files_host(self._h, sel_p, len(sel), offsets.ctypes.data, None, 0, C.byref(nb))   # the size
+        if rc != _lib.E_OVERFLOW:
+            _lib.check(rc)
+        data = np.zeros(nb.value, np.uint8)
+        if nb.value:
+            _lib.check(self._L.fskhip_xmodem_recv_files_host(self._h, sel_p, len(sel), offsets.ctypes.data, data.ctypes.data, data.nbytes, C.byref(nb)))
+        return [data[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in range(len(sel))]
+
+    def set_files(self, files, mask=None):
+        """puts files back (one per stream; those of `mask`, the other entries are ignored and may be None): before set_state, to
+        carry a receiver across a remap or a restore"""
+        if len(files) != self.n_streams:
+            raise ValueError("need one file per stream")
+        m = self._mask(mask)
+        sel = np.array([s for s in range(self.n_streams) if m is None or m[s]], np.uint32)
+        rows = [bytes(files[s]) for s in sel]
+        offsets = np.zeros(len(sel) + 1, np.uint64)
+        offsets[1:] = np.cumsum([len(r) for r in rows], dtype=np.uint64)
+        data = np.frombuffer(b"".join(rows), np.uint8)
+        _lib.check(self._L.fskhip_xmodem_recv_files_set_host(self._h, sel.ctypes.data if len(sel) else None, len(sel), offsets.ctypes.data,
+                                                             data.ctypes.data if len(data) else None))
+
+    def reset(self, stream=-1):
+        """reset() (xmodem.ts:370-383) for one stream, or all: IDLE, expected 1, retries 0, an empty file, the counters 0"""
+        _lib.check(self._L.fskhip_xmodem_recv_reset(self._h, int(stream)))
+
+    def state(self):
+        """{"state", "expected", "retries", "file_len", "packets_received", "dropped", "packets_sent"}: uint32 arrays, one entry per stream"""
+        out = {k: np.zeros(self.n_streams, np.uint32) for k in RECV_WORDS}
+        _lib.check(self._L.fskhip_xmodem_recv_state_get(self._h, *[out[k].ctypes.data for k in RECV_WORDS]))
+        return out
+
+    def set_state(self, **words):
+        """what state() returned, or any part of it (validated as a whole before anything is set)"""
+        arrs = []
+        for k in RECV_WORDS:
+            a = words.pop(k, None)
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.uint32)
+                if a.shape != (self.n_streams,):
+                    raise ValueError("state arrays must have one entry per stream")
+            arrs.append(a)
+        if words:
+            raise TypeError("unknown state words: %s" % ", ".join(sorted(words)))
+        _lib.check(self._L.fskhip_xmodem_recv_state_set(self._h, *[None if a is None else a.ctypes.data for a in arrs]))
