@@ -269,7 +269,8 @@ int fskhip_processor_restore(fskhip_processor *dst, const void *buf, size_t size
  * stays with the host: each record says which control bytes the reference would have sent (one ACK per accepted or duplicate
  * packet, a NAK on an error status, the final ACK on FSKHIP_XM_EOT); retries and timeouts are the host's.
  *
- * State per stream, kept with this handle and NOT in the processor (its images and remaps do not carry it): `expected`
+ * State per stream, kept with this handle and NOT in the processor (its images and remaps do not carry it; fskhip_xmodem_rx_remap,
+ * _snapshot and _restore below do): `expected`
  * (receive.expectedSequence, starts at 1), `packets` and `dropped` (running statistics.packetsReceived / packetsDropped, start
  * at 0, counted as in fskhip_xmodem_result).  fskhip_xmodem_rx_reset is initializeReceive() (xmodem.ts:221-225) for one stream
  * or all (stream < 0): expected = 1 and nothing else -- not the ring, not the counters; what a host calls after FSKHIP_XM_EOT.
@@ -341,7 +342,8 @@ int fskhip_xmodem_rx_poll_device(fskhip_xmodem_rx *r, const uint8_t *d_mask, uin
  * is lost; found by two polls they are two replies -- exactly as the reference's result depends on when its message arrives.
  * Unlike the receiver there is NO cut-invariance here, and none is claimed or tested.
  *
- * State per stream, kept with this handle and NOT in the processor (its images and remaps do not carry it): state (FSKHIP_XT_*),
+ * State per stream, kept with this handle and NOT in the processor (its images and remaps do not carry it; fskhip_xmodem_tx_remap,
+ * _snapshot and _restore below do): state (FSKHIP_XT_*),
  * sequence (send.sequence, 1..255), fragment_index, retries (the counter local to withRetry, xmodem.ts:608: it restarts at 0 for
  * every fragment; send.retries plays no part on the send path), packets_sent (statistics.packetsSent: data packets and the EOT)
  * and retransmitted (statistics.packetsRetransmitted); and the stream's file, in one packed store on the device.
@@ -440,7 +442,8 @@ int fskhip_xmodem_tx_reset(fskhip_xmodem_tx *t, int64_t stream);
  * cross to the host, one record per stream where something happened; the assembled file is read once, at the end.
  * fskhip_xmodem_rx is unchanged and stays the tool for a host that wants the bytes poll by poll.
  *
- * State per stream, kept with this handle and NOT in the processor: state (FSKHIP_XR_*, the reference's RECEIVING_* names),
+ * State per stream, kept with this handle and NOT in the processor (fskhip_xmodem_recv_remap, _snapshot and _restore below carry
+ * it): state (FSKHIP_XR_*, the reference's RECEIVING_* names),
  * expected (receive.expectedSequence, 1..255), retries (send.retries, which receiveAllPackets counts), file_len,
  * packets_received and dropped (statistics.packetsReceived / packetsDropped, counted as fskhip_xmodem_result counts them),
  * packets_sent (every control byte transmitted); and the stream's file, a row of file_capacity bytes on the device.
@@ -554,6 +557,94 @@ int fskhip_xmodem_recv_files_host(fskhip_xmodem_recv *r, const uint32_t *sel, ui
                                   size_t cap_bytes, uint64_t *n_bytes);
 int fskhip_xmodem_recv_files_set_host(fskhip_xmodem_recv *r, const uint32_t *sel, uint32_t n_sel, const uint64_t *offsets,
                                       const uint8_t *data);
+
+/* ---------------------------------------------------------------------------------------------------
+ * The resident XModem handles through remap, snapshot and restore (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): what the
+ * reference's host does by keeping or moving a whole XModemTransport object with its FSKProcessor.  The engine is carried by
+ * fskhip_remap_streams / fskhip_snapshot_streams / fskhip_restore_streams, the processor over it by fskhip_processor_remap /
+ * _snapshot / _restore; the host then creates a FRESH XModem handle over the destination processor and moves the handle's state
+ * with the SAME map through the calls below.  They never touch the processor.  The words, the sender's packed file store and the
+ * file receiver's rows move on the device; no file passes through host memory on a remap, and an image crosses PCIe once.
+ * state_get / state_set, send_host and files_host / files_set_host stay as they are.  Synchronous host calls; none returns -8.
+ *
+ * _remap: stream i of dst continues the handle state of stream map[i] of src exactly as if that stream's XModemTransport object
+ * had been moved: every state word verbatim (the file receiver's SEND_* states included: they go on turning into WAIT_BLOCK lazily,
+ * the processor remap carries tx_pending), and the stream's file with it.  Where map[i] = -1 the stream starts as a new transport --
+ *   rx    expected 1, counters 0
+ *   tx    IDLE, sequence 1, fragment_index 0, retries 0, counters 0, no file
+ *   recv  IDLE, expected 1, retries 0, file_len 0, counters 0.
+ * A source stream may be named more than once: independent clones, their files copied once per clone.  Source streams that are not
+ * named are dropped.  src is read only and stays usable.  Which file bytes move: the sender's file whenever the handle holds one,
+ * whatever the stream's state (a later state_set may use it), into a store built densely, in stream order, with no dead bytes; of
+ * a file receiver's row exactly file_len bytes, for IDLE streams too (the partial file of a failed transfer stays readable) --
+ * row bytes beyond file_len are unspecified in dst.
+ * FSKHIP_E_INVALID, with a message naming the first offending index or field and dst left as it was -- everything is validated
+ * before anything is written -- unless: the arguments are non-null and dst != src; n_map == dst's stream count and every entry is
+ * in range or -1; dst and src are on the same device; dst is freshly created (rx: no poll, reset or state_set call yet; tx: no
+ * send, poll, reset or state_set; recv: no start, poll, reset, state_set or files_set); tx: max_payload_size is equal on both
+ * handles (the fragment boundaries of a running transfer depend on it); recv: every carried file_len <= dst's file_capacity (the
+ * capacity may otherwise differ).  max_retries is the new handle's own and is not compared.  tx: carried files, clones counted,
+ * that together exceed 2^32 - 1 bytes: FSKHIP_E_UNSUPPORTED.
+ * A handle that has been remapped or restored into is STILL fresh: these calls write every stream of dst, so a second remap or
+ * restore into the same handle is accepted and replaces the first as a whole (the sender's store included); only the calls listed
+ * above end freshness.  Refusals (FSKHIP_E_INVALID, FSKHIP_E_UNSUPPORTED) write nothing.  A call that fails later, with FSKHIP_E_HIP or
+ * FSKHIP_E_NOMEM from the device, may leave dst's words partly written: destroy such a handle and create a new one.
+ *
+ * An XModem snapshot is a host-side image: plain little-endian bytes, no pointers, every byte defined; two snapshots of the same
+ * observable state are byte-identical, whatever the sender's store looked like inside (file order, dead bytes, past compactions).
+ * An implementation-versioned checkpoint, not an archive.  Three parts, in this order:
+ *   header, 48 bytes:  u32 magic "FSKX" (0x584B5346) | u32 format (1) | u32 header_bytes (48) | u32 kind (1 rx, 2 tx, 3 recv) |
+ *                      u32 n_records | u32 record_words (rx 4, tx 8, recv 8) | u32 param0 | u32 param1 |
+ *                      u64 checksum | u64 file_bytes
+ *     param0 / param1: 0 / 0 (rx), max_payload_size / max_retries (tx), file_capacity / max_retries (recv).  file_bytes: the sum of
+ *     the records' file lengths (0 for rx).  checksum: the processor snapshot's function over the image's u64 words, with the
+ *     checksum field taken as 0.
+ *   word table, n_records x record_words u32, one record per selected stream, in selection order:
+ *     rx    expected, packets, dropped, 0
+ *     tx    state, sequence, fragment_index, retries, packets_sent, retransmitted, file_len, has_file
+ *     recv  state, expected, retries, file_len, packets_received, dropped, packets_sent, 0
+ *   the files, concatenated tightly in record order (file_bytes in all), then zero padding to a multiple of 16.
+ * The whole image is 48 + 4 x n_records x record_words + file_bytes rounded up to 16 bytes long.
+ *
+ * fskhip_xmodem_snapshot_info_get  what an image holds -- on the host, no device needed -- after validating ALL of it; each flaw is
+ *                           FSKHIP_E_INVALID with a message that names it: magic, format, header_bytes, kind, record_words
+ *                           against the kind; the size against the formula above; the checksum; the records' file_len summing
+ *                           to file_bytes; padding and reserved words zero; and per record -- rx: expected in 1..255; tx: param0
+ *                           in 1..255, state <= 3, sequence in 1..255, has_file 0 or 1, file_len 0 where has_file is 0, and in
+ *                           WAIT_NAK or WAIT_ACK a file held with fragment_index < max(1, ceil(file_len / param0)); recv:
+ *                           state <= 3, expected in 1..255, file_len <= param0.
+ * _snapshot_bytes           the bytes a snapshot of the selected streams takes (it depends on their files, so it takes the
+ *                           selection).  0 for a null handle.
+ * _snapshot                 write streams sel[0 .. n_sel) (sel NULL: all, in order; a stream may be named more than once) into buf.
+ *                           Synchronises with the processor's outstanding work; the handle is read only and stays usable.  *written
+ *                           (may be NULL) receives the size; cap too small: FSKHIP_E_OVERFLOW with *written = the size needed and
+ *                           nothing written, so cap 0 is a size query.
+ * _restore                  _remap with the image standing in for src: map[i] names a RECORD, or is -1.  The same-device condition is
+ *                           dropped; the image's kind must be the handle's; every other precondition applies with the image's
+ *                           param0 in the place of src's; nothing is written before the whole image and map have passed.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct fskhip_xmodem_snapshot_info {
+  uint32_t kind;        /* 1 rx, 2 tx, 3 recv */
+  uint32_t n_streams;   /* records in the image */
+  uint32_t param0, param1;
+  uint64_t file_bytes;
+} fskhip_xmodem_snapshot_info;
+int fskhip_xmodem_snapshot_info_get(const void *buf, size_t size, fskhip_xmodem_snapshot_info *info);
+
+int fskhip_xmodem_rx_remap(fskhip_xmodem_rx *dst, const fskhip_xmodem_rx *src, const int64_t *map, uint32_t n_map);
+size_t fskhip_xmodem_rx_snapshot_bytes(const fskhip_xmodem_rx *r, const int64_t *sel, uint32_t n_sel);
+int fskhip_xmodem_rx_snapshot(fskhip_xmodem_rx *r, const int64_t *sel, uint32_t n_sel, void *buf, size_t cap, size_t *written);
+int fskhip_xmodem_rx_restore(fskhip_xmodem_rx *dst, const void *buf, size_t size, const int64_t *map, uint32_t n_map);
+
+int fskhip_xmodem_tx_remap(fskhip_xmodem_tx *dst, const fskhip_xmodem_tx *src, const int64_t *map, uint32_t n_map);
+size_t fskhip_xmodem_tx_snapshot_bytes(const fskhip_xmodem_tx *t, const int64_t *sel, uint32_t n_sel);
+int fskhip_xmodem_tx_snapshot(fskhip_xmodem_tx *t, const int64_t *sel, uint32_t n_sel, void *buf, size_t cap, size_t *written);
+int fskhip_xmodem_tx_restore(fskhip_xmodem_tx *dst, const void *buf, size_t size, const int64_t *map, uint32_t n_map);
+
+int fskhip_xmodem_recv_remap(fskhip_xmodem_recv *dst, const fskhip_xmodem_recv *src, const int64_t *map, uint32_t n_map);
+size_t fskhip_xmodem_recv_snapshot_bytes(const fskhip_xmodem_recv *r, const int64_t *sel, uint32_t n_sel);
+int fskhip_xmodem_recv_snapshot(fskhip_xmodem_recv *r, const int64_t *sel, uint32_t n_sel, void *buf, size_t cap, size_t *written);
+int fskhip_xmodem_recv_restore(fskhip_xmodem_recv *dst, const void *buf, size_t size, const int64_t *map, uint32_t n_map);
 
 /* ---------------------------------------------------------------------------------------------------
  * FIR half of src/dsp/filters.ts: FIRFilter (112-167) batched over streams, and the windowed-sinc designs

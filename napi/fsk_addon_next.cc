@@ -28,6 +28,8 @@
 //   xmodemRecvFiles(handle, sel: Uint32Array) -> {offsets: Float64Array[n + 1], data: Uint8Array}
 //   xmodemRecvSetFiles(handle, sel: Uint32Array, offsets: Uint32Array[n + 1], data: Uint8Array)
 //   xmodemRecvState(handle) -> {state, expected, retries, fileLen, packetsReceived, dropped, packetsSent: Uint32Array};  xmodemRecvSetState(handle, the seven|null)
+//   xmodem{Rx,Tx,Recv}Remap(dst, src, map: number[]);  xmodem{Rx,Tx,Recv}Snapshot(handle, sel: number[]|null) -> Buffer
+//   xmodem{Rx,Tx,Recv}Restore(dst, snapshot: Uint8Array, map: number[]);  xmodemSnapshotInfo(snapshot) -> {kind, nStreams, param0, param1, fileBytes}
 //   processorRemap(dst, src, map: number[]);  processorSnapshot(handle, sel: number[]|null) -> Buffer
 //   processorRestore(dst, snapshot: Uint8Array, map: number[]);  processorSnapshotInfo(snapshot) -> {nStreams, rxCapacity, payloadCapacity, recordBytes}
 //   sincLowpass/sincHighpass(cutoff, sampleRate, numTaps), sincBandpass(center, bandwidth, sampleRate, numTaps) -> Float64Array
@@ -774,6 +776,73 @@ napi_value ProcessorSnapshotInfo(napi_env env, napi_callback_info info) {
   return o;
 }
 
+// ---- the resident XModem handles through remap / snapshot / restore (include/fskhip_next.h): one spelling for the three kinds
+#define XM_LIFECYCLE(Name, Box, get, field, kind)                                                                                   \
+  napi_value Xmodem##Name##Remap(napi_env env, napi_callback_info info) {                                                            \
+    ARGS(3);                                                                                                                         \
+    Box *dst = get(env, argv[0]);                                                                                                    \
+    if (!dst) return nullptr;                                                                                                        \
+    Box *src = get(env, argv[1]);                                                                                                    \
+    if (!src) return nullptr;                                                                                                        \
+    std::vector<int64_t> map;                                                                                                        \
+    if (!index_array(env, argv[2], "xmodem" #Name "Remap: map must be an Array of integer stream indices (-1: a new stream)", &map)) return nullptr; \
+    int rc = fskhip_xmodem_##kind##_remap(dst->field, src->field, index_data(map), (uint32_t)map.size());                            \
+    if (rc != FSKHIP_OK) return throw_fsk(env, rc);                                                                                  \
+    return nullptr;                                                                                                                  \
+  }                                                                                                                                  \
+  napi_value Xmodem##Name##Snapshot(napi_env env, napi_callback_info info) {                                                         \
+    ARGS(2);                                                                                                                         \
+    Box *h = get(env, argv[0]);                                                                                                      \
+    if (!h) return nullptr;                                                                                                          \
+    std::vector<int64_t> sel;                                                                                                        \
+    const bool all = nullish(env, argv[1]);                                                                                          \
+    if (!all && !index_array(env, argv[1], "xmodem" #Name "Snapshot: sel must be an Array of integer stream indices", &sel)) return nullptr; \
+    const int64_t *sp = index_data(sel, all);                                                                                        \
+    const uint32_t n = all ? h->S : (uint32_t)sel.size();                                                                            \
+    size_t need = 0;                                                                                                                 \
+    int rc = fskhip_xmodem_##kind##_snapshot(h->field, sp, n, nullptr, 0, &need);   /* (the size: it depends on the files) */        \
+    if (rc != FSKHIP_E_OVERFLOW) return throw_fsk(env, rc);                                                                          \
+    void *data = nullptr;                                                                                                            \
+    napi_value buf;                                                                                                                  \
+    NAPI_OK(napi_create_buffer(env, need, &data, &buf));                                                                             \
+    rc = fskhip_xmodem_##kind##_snapshot(h->field, sp, n, data, need, nullptr);                                                      \
+    if (rc != FSKHIP_OK) return throw_fsk(env, rc);                                                                                  \
+    return buf;                                                                                                                      \
+  }                                                                                                                                  \
+  napi_value Xmodem##Name##Restore(napi_env env, napi_callback_info info) {                                                          \
+    ARGS(3);                                                                                                                         \
+    Box *dst = nullish(env, argv[0]) ? nullptr : get(env, argv[0]);                                                                  \
+    if (!dst && !nullish(env, argv[0])) return nullptr;                                                                              \
+    void *data; size_t size;                                                                                                         \
+    if (!typed(env, argv[1], napi_uint8_array, &data, &size)) return nullptr;                                                        \
+    std::vector<int64_t> map;                                                                                                        \
+    if (!index_array(env, argv[2], "xmodem" #Name "Restore: map must be an Array of integer record indices (-1: a new stream)", &map)) return nullptr; \
+    int rc = fskhip_xmodem_##kind##_restore(dst ? dst->field : nullptr, data, size, index_data(map), (uint32_t)map.size());          \
+    if (rc != FSKHIP_OK) return throw_fsk(env, rc);                                                                                  \
+    return nullptr;                                                                                                                  \
+  }
+XM_LIFECYCLE(Rx, XmRx, get_xm_rx, r, rx)
+XM_LIFECYCLE(Tx, XmTx, get_xm_tx, t, tx)
+XM_LIFECYCLE(Recv, XmRecv, get_xm_recv, r, recv)
+#undef XM_LIFECYCLE
+
+napi_value XmodemSnapshotInfo(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  void *data; size_t size;
+  if (!typed(env, argv[0], napi_uint8_array, &data, &size)) return nullptr;
+  fskhip_xmodem_snapshot_info si;
+  int rc = fskhip_xmodem_snapshot_info_get(data, size, &si);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  set_u32(env, o, "kind", si.kind);
+  set_u32(env, o, "nStreams", si.n_streams);
+  set_u32(env, o, "param0", si.param0);
+  set_u32(env, o, "param1", si.param1);
+  set_num(env, o, "fileBytes", (double)si.file_bytes);
+  return o;
+}
+
 // ---- FIR ------------------------------------------------------------------------------------------------
 napi_value sinc_result(napi_env env, int n, const std::vector<double> &t) {
   if (n < 0) return throw_fsk(env, n);
@@ -964,6 +1033,16 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"processorSnapshot", nullptr, ProcessorSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRestore", nullptr, ProcessorRestore, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorSnapshotInfo", nullptr, ProcessorSnapshotInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRxRemap", nullptr, XmodemRxRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRxSnapshot", nullptr, XmodemRxSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRxRestore", nullptr, XmodemRxRestore, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTxRemap", nullptr, XmodemTxRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTxSnapshot", nullptr, XmodemTxSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTxRestore", nullptr, XmodemTxRestore, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRecvRemap", nullptr, XmodemRecvRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRecvSnapshot", nullptr, XmodemRecvSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemRecvRestore", nullptr, XmodemRecvRestore, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemSnapshotInfo", nullptr, XmodemSnapshotInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"sincLowpass", nullptr, SincLowpass, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"sincHighpass", nullptr, SincHighpass, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"sincBandpass", nullptr, SincBandpass, nullptr, nullptr, nullptr, napi_default, nullptr},

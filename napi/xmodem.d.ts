@@ -45,6 +45,12 @@ export declare class XModemReceiverBatch {
   state(): ReceiverState;
   setState(state: { expected?: ArrayLike<number> | null; packets?: ArrayLike<number> | null; dropped?: ArrayLike<number> | null }): void;
   close(): void;
+  /** a new object over `processor` (the destination the engine and the processor were remapped into with the same map): stream i continues stream map[i], file included; -1 starts a new transport */
+  remap(processor: object, map: ArrayLike<number>): XModemReceiverBatch;
+  /** the image of `streams` (default: all, in order): words and files */
+  snapshot(streams?: ArrayLike<number> | null): Buffer;
+  /** a new object over `processor` continuing the records of a snapshot(); its parameters are the image's unless overridden */
+  static fromSnapshot(processor: object, buf: Uint8Array, map?: ArrayLike<number> | null): XModemReceiverBatch;
 }
 
 /** fskhip_xmodem_tx_event of one stream */
@@ -76,6 +82,12 @@ export declare class XModemSenderBatch {
   state(): SenderState;
   setState(state: { [K in keyof SenderState]?: ArrayLike<number> | null }): void;
   close(): void;
+  /** a new object over `processor` (the destination the engine and the processor were remapped into with the same map): stream i continues stream map[i], file included; -1 starts a new transport */
+  remap(processor: object, map: ArrayLike<number>): XModemSenderBatch;
+  /** the image of `streams` (default: all, in order): words and files */
+  snapshot(streams?: ArrayLike<number> | null): Buffer;
+  /** a new object over `processor` continuing the records of a snapshot(); its parameters are the image's unless overridden */
+  static fromSnapshot(processor: object, buf: Uint8Array, map?: ArrayLike<number> | null, options?: { maxRetries?: number }): XModemSenderBatch;
 }
 
 /** fskhip_xmodem_recv_event of one stream */
@@ -116,4 +128,13 @@ export declare class XModemFileReceiverBatch {
   state(): FileReceiverState;
   setState(state: { [K in keyof FileReceiverState]?: ArrayLike<number> | null }): void;
   close(): void;
+  /** a new object over `processor` (the destination the engine and the processor were remapped into with the same map): stream i continues stream map[i], file included; -1 starts a new transport */
+  remap(processor: object, map: ArrayLike<number>): XModemFileReceiverBatch;
+  /** the image of `streams` (default: all, in order): words and files */
+  snapshot(streams?: ArrayLike<number> | null): Buffer;
+  /** a new object over `processor` continuing the records of a snapshot(); its parameters are the image's unless overridden */
+  static fromSnapshot(processor: object, buf: Uint8Array, map?: ArrayLike<number> | null, options?: { fileCapacity?: number; maxRetries?: number }): XModemFileReceiverBatch;
 }
+export interface XModemSnapshotInfo { kind: 1 | 2 | 3; nStreams: number; param0: number; param1: number; fileBytes: number; }
+/** what an XModem snapshot holds, after validating all of it on the host */
+export declare function xmodemSnapshotInfo(buf: Uint8Array): XModemSnapshotInfo;

@@ -287,4 +287,36 @@ class XModemFileReceiverBatch {
   }
 }
 
-module.exports = { XModemReceiverBatch, XModemSenderBatch, XModemFileReceiverBatch, CRC16, XModemPacket, ControlType, PacketConstants, crc16Batch, serializeBatch, scanBursts };
+// remap / snapshot / fromSnapshot of the three resident classes: the handle's state follows its streams with the map the engine and
+// the processor were carried with (fskhip_xmodem_{rx,tx,recv}_remap / _snapshot / _restore).  `like(processor)` makes a new object
+// with this one's parameters over the destination processor; `made(processor, info, options)` one with an image's.
+const XM_KINDS = { 1: 'rx', 2: 'tx', 3: 'recv' };
+function xmodemSnapshotInfo(buf) { return addon.xmodemSnapshotInfo(buf); }
+function lifecycle(Class, kind, fns, like, made) {
+  Class.prototype.remap = function remap(processor, map) {
+    const next = like(this, processor);
+    try { fns.remap(next.handle, this.handle, Array.from(map)); } catch (e) { next.close(); throw e; }
+    return next;
+  };
+  Class.prototype.snapshot = function snapshot(streams) {
+    return fns.snapshot(this.handle, streams === undefined || streams === null ? null : Array.from(streams));
+  };
+  Class.fromSnapshot = function fromSnapshot(processor, buf, map, options = {}) {
+    const info = xmodemSnapshotInfo(buf);
+    if (XM_KINDS[info.kind] !== kind) throw new TypeError(`${Class.name}.fromSnapshot: the snapshot is of kind '${XM_KINDS[info.kind]}', not '${kind}'`);
+    const m = map === undefined || map === null ? Array.from({ length: info.nStreams }, (_, i) => i) : Array.from(map);
+    const next = made(processor, info, options);
+    try { fns.restore(next.handle, buf, m); } catch (e) { next.close(); throw e; }
+    return next;
+  };
+}
+lifecycle(XModemReceiverBatch, 'rx', { remap: addon.xmodemRxRemap, snapshot: addon.xmodemRxSnapshot, restore: addon.xmodemRxRestore },
+  (self, p) => new XModemReceiverBatch(p), (p) => new XModemReceiverBatch(p));
+lifecycle(XModemSenderBatch, 'tx', { remap: addon.xmodemTxRemap, snapshot: addon.xmodemTxSnapshot, restore: addon.xmodemTxRestore },
+  (self, p) => new XModemSenderBatch(p, { maxPayloadSize: self.maxPayloadSize, maxRetries: self.maxRetries }),
+  (p, info, o) => new XModemSenderBatch(p, Object.assign({ maxPayloadSize: info.param0, maxRetries: info.param1 }, o)));
+lifecycle(XModemFileReceiverBatch, 'recv', { remap: addon.xmodemRecvRemap, snapshot: addon.xmodemRecvSnapshot, restore: addon.xmodemRecvRestore },
+  (self, p) => new XModemFileReceiverBatch(p, { fileCapacity: self.fileCapacity, maxRetries: self.maxRetries }),
+  (p, info, o) => new XModemFileReceiverBatch(p, Object.assign({ fileCapacity: info.param0, maxRetries: info.param1 }, o)));
+
+module.exports = { xmodemSnapshotInfo, XModemReceiverBatch, XModemSenderBatch, XModemFileReceiverBatch, CRC16, XModemPacket, ControlType, PacketConstants, crc16Batch, serializeBatch, scanBursts };

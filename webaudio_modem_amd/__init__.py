@@ -8,7 +8,7 @@ from .engine import FSKEngine, DEFAULT_FSK_CONFIG, make_config, pinned_empty, sn
 from .fsk_core import FSKCore, Event, EventEmitter  # noqa: F401
 from .filters import FilterDesign, FilterFactory, FIRFilter, FIRFilterBatch, IIRFilter, IIRFilterBatch  # noqa: F401
 from .processor import ChunkedModulator, FSKProcessorBatch, ProcessorBatchSnapshot, processor_snapshot_info  # noqa: F401
-from .xmodem import CRC16, XModemPacket, ControlType, crc16_batch, serialize_batch, scan_bursts, XModemReceiverBatch, XModemSenderBatch, XModemFileReceiverBatch  # noqa: F401
+from .xmodem import CRC16, XModemPacket, ControlType, crc16_batch, serialize_batch, scan_bursts, XModemReceiverBatch, XModemSenderBatch, XModemFileReceiverBatch, xmodem_snapshot_info  # noqa: F401
 from . import sharding  # noqa: F401
 from .sharded import FSKEngineSharded  # noqa: F401
 

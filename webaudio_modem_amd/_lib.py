@@ -66,6 +66,11 @@ class ProcessorSnapshotInfo(C.Structure):
     _fields_ = [("n_streams", C.c_uint32), ("rx_capacity", C.c_uint32), ("payload_capacity", C.c_uint32), ("record_bytes", C.c_uint32)]
 
 
+class XModemSnapshotInfo(C.Structure):
+    """fskhip_xmodem_snapshot_info (include/fskhip_next.h): what an XModem snapshot holds"""
+    _fields_ = [("kind", C.c_uint32), ("n_streams", C.c_uint32), ("param0", C.c_uint32), ("param1", C.c_uint32), ("file_bytes", C.c_uint64)]
+
+
 class XModemResult(C.Structure):
     """fskhip_xmodem_result (include/fskhip_next.h)."""
     _fields_ = [
@@ -207,6 +212,19 @@ _SYMBOLS = [
     ("fskhip_xmodem_recv_reset", C.c_int, [_P, C.c_int64]),
     ("fskhip_xmodem_recv_files_host", C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_size_t, _P]),
     ("fskhip_xmodem_recv_files_set_host", C.c_int, [_P, _P, C.c_uint32, _P, _P]),
+    ("fskhip_xmodem_snapshot_info_get", C.c_int, [_P, C.c_size_t, C.POINTER(XModemSnapshotInfo)]),
+    ("fskhip_xmodem_rx_remap", C.c_int, [_P, _P, _P, C.c_uint32]),
+    ("fskhip_xmodem_rx_snapshot_bytes", C.c_size_t, [_P, _P, C.c_uint32]),
+    ("fskhip_xmodem_rx_snapshot", C.c_int, [_P, _P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fskhip_xmodem_rx_restore", C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint32]),
+    ("fskhip_xmodem_tx_remap", C.c_int, [_P, _P, _P, C.c_uint32]),
+    ("fskhip_xmodem_tx_snapshot_bytes", C.c_size_t, [_P, _P, C.c_uint32]),
+    ("fskhip_xmodem_tx_snapshot", C.c_int, [_P, _P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fskhip_xmodem_tx_restore", C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint32]),
+    ("fskhip_xmodem_recv_remap", C.c_int, [_P, _P, _P, C.c_uint32]),
+    ("fskhip_xmodem_recv_snapshot_bytes", C.c_size_t, [_P, _P, C.c_uint32]),
+    ("fskhip_xmodem_recv_snapshot", C.c_int, [_P, _P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fskhip_xmodem_recv_restore", C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint32]),
     ("fskhip_sinc_lowpass", C.c_int, [C.c_double, C.c_double, C.c_uint32, _P]),
     ("fskhip_sinc_highpass", C.c_int, [C.c_double, C.c_double, C.c_uint32, _P]),
     ("fskhip_sinc_bandpass", C.c_int, [C.c_double, C.c_double, C.c_double, C.c_uint32, _P]),

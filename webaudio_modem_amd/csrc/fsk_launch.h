@@ -206,4 +206,29 @@ hipError_t launch_xmodem_recv_commit(const ProcState &T, uint32_t n_streams, con
                                      uint32_t *d_streams, fskhip_xmodem_recv_event *d_events, hipStream_t st);
 hipError_t launch_xmodem_recv_files(bool pack, const XmRecvState &X, const uint32_t *d_sel, const uint64_t *d_offsets, uint32_t n_sel, uint8_t *d_packed,
                                     hipStream_t st);
+// fsk_xmodem_remap.hip: the three resident XModem handles carried through remap, snapshot and restore (fskhip_xmodem_*_remap /
+// _snapshot / _restore).  The caller has checked the arguments.
+// XmWords: a handle's per-stream word arrays in the order of its image record, and what a new stream holds in each.
+// gather: stream i of D takes the words of stream d_map[i] of S -- or, where S is null, words [0, D.n) of record d_map[i] of d_table
+// (record_words words per record) --, the fresh values where d_map[i] = -1.  pack: record r of d_table = the words of stream
+// d_sel[r] of S (null: r), zeros behind them; flag7: word 7 is stored as 0 / 1 (the sender's has_file from its fragment count).
+// XmSpan: one file's move, byte offsets into the two bases.  copy: every span, byte-exact, any length and alignment; max_len: the
+// longest span (how many workgroups share one).
+// recv_plan: the spans of a file receiver's remap -- row d_map[i] of the source (file_len bytes) to row i --, in d_bad[0] the first
+// i whose file exceeds dst_cap (else 0xFFFFFFFF) and in d_bad[1] the longest carried file.  file_offsets: d_offsets[r] = the bytes of the files of streams d_sel[0 .. r)
+// (null: 0 .. r), n + 1 entries; d_sums: xmodem_offsets_scratch_words(n) 64-bit words, of which the last two end as the total and
+// the longest file.  recv_spans: with those, the spans of a
+// snapshot -- row d_sel[r] to d_offsets[r] of the image's file area.
+struct XmWords { uint32_t *a[8]; uint32_t fresh[8]; uint32_t n; };
+struct XmSpan { uint64_t src, dst, len; };
+hipError_t launch_xmodem_words_gather(const XmWords &D, uint32_t n_dst, const int64_t *d_map, const XmWords *S, const uint32_t *d_table, uint32_t record_words,
+                                      hipStream_t st);
+hipError_t launch_xmodem_words_pack(const XmWords &S, const int64_t *d_sel, uint32_t n, uint32_t record_words, bool flag7, uint32_t *d_table, hipStream_t st);
+hipError_t launch_xmodem_span_copy(const uint8_t *d_src, uint8_t *d_dst, const XmSpan *d_spans, uint32_t n_spans, uint64_t max_len, hipStream_t st);
+hipError_t launch_xmodem_recv_plan(const uint32_t *d_src_len, uint32_t src_cap, uint32_t dst_cap, const int64_t *d_map, uint32_t n_dst, XmSpan *d_spans,
+                                   uint32_t *d_bad, hipStream_t st);
+size_t xmodem_offsets_scratch_words(uint32_t n);
+hipError_t launch_xmodem_file_offsets(const uint32_t *d_len, const int64_t *d_sel, uint32_t n, uint64_t *d_offsets, uint64_t *d_sums, hipStream_t st);
+hipError_t launch_xmodem_recv_spans(const uint32_t *d_len, uint32_t cap, const int64_t *d_sel, uint32_t n, const uint64_t *d_offsets, XmSpan *d_spans,
+                                    hipStream_t st);
 }  // namespace fsk

@@ -1,5 +1,5 @@
 // fsk_stage.h -- what the two image formats share (fsk_snapshot_api.hip: stream snapshots; fsk_processor_remap_api.hip: processor
-// snapshots), each once: the checksum over an image, the frame every image has (the front and the back of opening one, the
+// snapshots), each once: the checksum over an image (fsk_snapsum.h), the frame every image has (the front and the back of opening one, the
 // common header fields, the writers' selection and room checks), and the two slab pipelines that carry records across PCIe --
 // stage_records_out for the writers, stage_records_in for the restores.  The formats keep their own headers, geometry checks
 // and kernels; no event chain is spelled anywhere else.  Not part of the ABI.
@@ -11,25 +11,11 @@
 #include <cstring>
 
 #include "fsk_host.h"
+#include "fsk_snapsum.h"
 
 namespace fsk {
 
 constexpr uint32_t kSnapSlab = 8192;           // streams per staging slab: two slabs of ~9 MB on the device, whatever the batch
-
-// Running position-dependent sum over little-endian 64-bit words (sizes here are multiples of 8): a = sum of words, b = sum of
-// the running a.  Two adds per 8 bytes -- it runs at memory speed, which a byte-wise hash of a 66 MB image would not.
-struct SnapSum { uint64_t a = 0, b = 0; };
-inline void snap_sum(SnapSum &s, const void *p, size_t bytes) {
-  const unsigned char *c = (const unsigned char *)p;
-  uint64_t a = s.a, b = s.b;
-  for (size_t i = 0; i + 8 <= bytes; i += 8) {
-    uint64_t w;
-    std::memcpy(&w, c + i, 8);
-    a += w; b += a;
-  }
-  s.a = a; s.b = b;
-}
-inline uint64_t snap_sum_value(const SnapSum &s) { return s.a * 0x9E3779B97F4A7C15ull ^ s.b; }
 
 // two staging buffers on the device, a copy stream beside the owner's own, and the events that chain slab k's copy and kernel
 struct Stage {

@@ -12,23 +12,9 @@
 #include "fsk_host.h"
 #include "fsk_launch.h"
 #include "fsk_proc.h"
+#include "fsk_xmodem_handles.h"
 
 using namespace fsk;
-
-struct fskhip_xmodem_recv {
-  fskhip_processor *p = nullptr;
-  int device = 0;   // the processor's, kept here: destroy does not read the processor, which may be gone by then
-  XmRecvState X{};
-  XmRecvScratch W{};
-  uint32_t *d_totals = nullptr;
-  // staging for the _host forms
-  uint8_t *d_mask = nullptr, *d_timeout = nullptr, *d_abort = nullptr;
-  uint32_t *d_streams = nullptr;               // [n_streams] each, from create: no poll allocates
-  fskhip_xmodem_recv_event *d_events = nullptr;
-  uint32_t *d_sel = nullptr; size_t d_sel_cap = 0;
-  uint64_t *d_offsets = nullptr; size_t d_offsets_cap = 0;
-  uint8_t *d_packed = nullptr; size_t d_packed_cap = 0;
-};
 
 namespace {
 
@@ -135,7 +121,7 @@ int fskhip_xmodem_recv_start_host(fskhip_xmodem_recv *r, const uint8_t *mask) {
   if ((rc = get_words(expected, r->X.expected, S)) != FSKHIP_OK || (rc = get_words(retries, r->X.retries, S)) != FSKHIP_OK ||
       (rc = get_words(file_len, r->X.file_len, S)) != FSKHIP_OK || (rc = get_words(sent, r->X.sent, S)) != FSKHIP_OK)
     return rc;
-  p->used = true;
+  p->used = true; r->used = true;
   std::vector<uint8_t> slab(S * r->W.slab_pitch, 0), tx_mask(S, 0);
   std::vector<uint32_t> lens(S, 0u);
   for (size_t s = 0; s < S; s++) {
@@ -160,6 +146,7 @@ int fskhip_xmodem_recv_reset(fskhip_xmodem_recv *r, int64_t stream) {
   if (stream >= (int64_t)r->p->S) return fail(FSKHIP_E_INVALID, "stream out of range");
   HIP_TRY(hipSetDevice(r->p->device));
   HIP_TRY(hipDeviceSynchronize());
+  r->used = true;
   const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? r->p->S : 1;
   uint32_t *zero[] = {r->X.state, r->X.retries, r->X.file_len, r->X.packets, r->X.dropped, r->X.sent};
   for (uint32_t *z : zero)
@@ -196,6 +183,7 @@ int fskhip_xmodem_recv_state_set(fskhip_xmodem_recv *r, const uint32_t *state, c
   }
   HIP_TRY(hipSetDevice(r->p->device));
   HIP_TRY(hipDeviceSynchronize());
+  r->used = true;
   int rc;
   if ((rc = put_words(r->X.state, state, S)) != FSKHIP_OK || (rc = put_words(r->X.expected, expected, S)) != FSKHIP_OK ||
       (rc = put_words(r->X.retries, retries, S)) != FSKHIP_OK || (rc = put_words(r->X.file_len, file_len, S)) != FSKHIP_OK ||
@@ -249,6 +237,7 @@ int fskhip_xmodem_recv_files_set_host(fskhip_xmodem_recv *r, const uint32_t *sel
                   (unsigned long long)(offsets[i + 1] - offsets[i]), r->X.file_cap);
     if (offsets[i + 1] > offsets[i] && !data) return fail(FSKHIP_E_INVALID, "%s: null data", fn);
   }
+  r->used = true;
   if (!n_sel) return FSKHIP_OK;
   HIP_TRY(hipSetDevice(r->p->device));
   HIP_TRY(hipDeviceSynchronize());
@@ -269,7 +258,7 @@ int fskhip_xmodem_recv_poll_host(fskhip_xmodem_recv *r, const uint8_t *mask, con
                                  fskhip_xmodem_recv_event *events, uint32_t cap_streams, uint32_t *n_events) {
   if (const int rc = poll_refusal("fskhip_xmodem_recv_poll_host", r, n_events, "n_events", streams, events, cap_streams)) return rc;
   fskhip_processor *p = r->p;
-  p->used = true;
+  p->used = true; r->used = true;
   *n_events = 0u;
   const size_t S = p->S;
   if (S == 0) return FSKHIP_OK;
@@ -301,7 +290,7 @@ int fskhip_xmodem_recv_poll_device(fskhip_xmodem_recv *r, const uint8_t *d_mask,
                                    fskhip_xmodem_recv_event *d_events, uint32_t cap_streams, uint32_t *d_totals, void *hip_stream) {
   if (const int rc = poll_refusal("fskhip_xmodem_recv_poll_device", r, d_totals, "d_totals", d_streams, d_events, cap_streams)) return rc;
   fskhip_processor *p = r->p;
-  p->used = true;
+  p->used = true; r->used = true;
   HIP_TRY(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)hip_stream;
   HIP_TRY(launch_xmodem_recv_step(p->T, p->S, d_mask, d_timeout, d_abort, r->X, r->W, cap_streams, d_totals, st));

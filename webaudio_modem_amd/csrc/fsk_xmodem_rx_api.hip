@@ -10,21 +10,9 @@
 #include "fsk_host.h"
 #include "fsk_launch.h"
 #include "fsk_proc.h"
+#include "fsk_xmodem_handles.h"
 
 using namespace fsk;
-
-struct fskhip_xmodem_rx {
-  fskhip_processor *p = nullptr;
-  int device = 0;   // the processor's, kept here: destroy does not read the processor, which may be gone by then
-  XmRxState X{};
-  XmRxScratch W{};
-  uint32_t *d_totals = nullptr;
-  // staging for the _host form
-  uint8_t *d_mask = nullptr;
-  uint32_t *d_lists = nullptr; size_t d_lists_cap = 0;            // streams[] and offsets[]
-  fskhip_xmodem_result *d_results = nullptr; size_t d_results_cap = 0;
-  uint8_t *d_data = nullptr; size_t d_data_cap = 0;
-};
 
 namespace {
 
@@ -93,6 +81,7 @@ int fskhip_xmodem_rx_reset(fskhip_xmodem_rx *r, int64_t stream) {
   if (stream >= (int64_t)r->p->S) return fail(FSKHIP_E_INVALID, "stream out of range");
   HIP_TRY(hipSetDevice(r->p->device));
   HIP_TRY(hipDeviceSynchronize());
+  r->used = true;
   const int rc = stream < 0 ? fill_words(r->X.expected, r->p->S, 1u) : fill_words(r->X.expected + stream, 1, 1u);
   if (rc != FSKHIP_OK) return rc;
   HIP_TRY(hipDeviceSynchronize());
@@ -118,6 +107,7 @@ int fskhip_xmodem_rx_state_set(fskhip_xmodem_rx *r, const uint32_t *expected, co
         return fail(FSKHIP_E_INVALID, "fskhip_xmodem_rx_state_set: expected[%u] = %u is not a sequence number (1-255)", s, expected[s]);
   HIP_TRY(hipSetDevice(r->p->device));
   HIP_TRY(hipDeviceSynchronize());
+  r->used = true;
   const size_t bytes = sizeof(uint32_t) * r->p->S;
   if (expected && bytes) HIP_TRY(hipMemcpy(r->X.expected, expected, bytes, hipMemcpyHostToDevice));
   if (packets && bytes) HIP_TRY(hipMemcpy(r->X.packets, packets, bytes, hipMemcpyHostToDevice));
@@ -133,7 +123,7 @@ int fskhip_xmodem_rx_poll_host(fskhip_xmodem_rx *r, const uint8_t *mask, uint32_
                                   cap_streams, data, cap_bytes))
     return rc;
   fskhip_processor *p = r->p;
-  p->used = true;
+  p->used = true; r->used = true;
   *n_events = 0u; *n_bytes = 0u;
   const size_t S = p->S;
   if (S == 0) {
@@ -174,7 +164,7 @@ int fskhip_xmodem_rx_poll_device(fskhip_xmodem_rx *r, const uint8_t *d_mask, uin
   if (const int rc = poll_refusal("fskhip_xmodem_rx_poll_device", r, d_totals, "d_totals", d_streams, d_results, d_offsets, cap_streams, d_data, cap_bytes))
     return rc;
   fskhip_processor *p = r->p;
-  p->used = true;
+  p->used = true; r->used = true;
   HIP_TRY(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)hip_stream;
   HIP_TRY(launch_xmodem_rx_scan(p->T, p->S, d_mask, r->X, r->W, cap_streams, cap_bytes, d_totals, st));

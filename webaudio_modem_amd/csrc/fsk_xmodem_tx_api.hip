@@ -13,26 +13,10 @@
 #include "fsk_host.h"
 #include "fsk_launch.h"
 #include "fsk_proc.h"
+#include "fsk_xmodem_handles.h"
 #include "fsk_xmodem_tx_step.h"
 
 using namespace fsk;
-
-struct fskhip_xmodem_tx {
-  fskhip_processor *p = nullptr;
-  int device = 0;   // the processor's, kept here: destroy does not read the processor, which may be gone by then
-  XmTxState X{};
-  XmTxScratch W{};
-  uint32_t *d_totals = nullptr;
-  // the packed file store: files are appended at `used`; a replaced file's bytes stay behind until the store is compacted
-  uint8_t *d_store = nullptr; size_t store_cap = 0, store_used = 0;
-  std::vector<uint32_t> h_off, h_len;   // each stream's file (h_len 0 and h_has 0: none)
-  std::vector<uint8_t> h_has;
-  uint32_t *d_new_off = nullptr; uint8_t *d_keep = nullptr;   // the compaction's arguments
-  // staging for the _host form
-  uint8_t *d_mask = nullptr, *d_abort = nullptr;
-  uint32_t *d_streams = nullptr; size_t d_streams_cap = 0;
-  fskhip_xmodem_tx_event *d_events = nullptr; size_t d_events_cap = 0;
-};
 
 namespace {
 
@@ -161,6 +145,7 @@ int fskhip_xmodem_tx_send_host(fskhip_xmodem_tx *t, const uint8_t *mask, const u
   }
   if (live + incoming > 0xFFFFFFFFull)
     return fail(FSKHIP_E_UNSUPPORTED, "%s: the files would take %llu bytes, the store's offsets are 32-bit", fn, (unsigned long long)(live + incoming));
+  t->used = true;
   if ((rc = make_room(t, stays, live, incoming)) != FSKHIP_OK) return rc;
   if ((rc = get_words(sequence, t->X.sequence, S)) != FSKHIP_OK || (rc = get_words(index, t->X.index, S)) != FSKHIP_OK ||
       (rc = get_words(n_fragments, t->X.n_fragments, S)) != FSKHIP_OK || (rc = get_words(retries, t->X.retries, S)) != FSKHIP_OK)
@@ -194,6 +179,7 @@ int fskhip_xmodem_tx_reset(fskhip_xmodem_tx *t, int64_t stream) {
   if (stream >= (int64_t)t->p->S) return fail(FSKHIP_E_INVALID, "stream out of range");
   HIP_TRY(hipSetDevice(t->p->device));
   HIP_TRY(hipDeviceSynchronize());
+  t->used = true;
   const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? t->p->S : 1;
   uint32_t *zero[] = {t->X.state, t->X.index, t->X.n_fragments, t->X.retries, t->X.sent, t->X.retransmitted, t->X.file_off, t->X.file_len};
   for (uint32_t *z : zero)
@@ -238,6 +224,7 @@ int fskhip_xmodem_tx_state_set(fskhip_xmodem_tx *t, const uint32_t *state, const
     if ((st == FSKHIP_XT_WAIT_NAK || st == FSKHIP_XT_WAIT_ACK) && idx >= n_frag)
       return fail(FSKHIP_E_INVALID, "%s: stream %zu waits to send fragment %u of %u", fn, s, idx, n_frag);
   }
+  t->used = true;
   if ((rc = put_words(t->X.state, state, S)) != FSKHIP_OK || (rc = put_words(t->X.sequence, sequence, S)) != FSKHIP_OK ||
       (rc = put_words(t->X.index, fragment_index, S)) != FSKHIP_OK || (rc = put_words(t->X.retries, retries, S)) != FSKHIP_OK ||
       (rc = put_words(t->X.sent, packets_sent, S)) != FSKHIP_OK || (rc = put_words(t->X.retransmitted, retransmitted, S)) != FSKHIP_OK)
@@ -250,7 +237,7 @@ int fskhip_xmodem_tx_poll_host(fskhip_xmodem_tx *t, const uint8_t *mask, const u
                                uint32_t cap_streams, uint32_t *n_events) {
   if (const int rc = poll_refusal("fskhip_xmodem_tx_poll_host", t, n_events, "n_events", streams, events, cap_streams)) return rc;
   fskhip_processor *p = t->p;
-  p->used = true;
+  p->used = true; t->used = true;
   *n_events = 0u;
   const size_t S = p->S;
   if (S == 0) return FSKHIP_OK;
@@ -282,7 +269,7 @@ int fskhip_xmodem_tx_poll_device(fskhip_xmodem_tx *t, const uint8_t *d_mask, con
                                  uint32_t cap_streams, uint32_t *d_totals, void *hip_stream) {
   if (const int rc = poll_refusal("fskhip_xmodem_tx_poll_device", t, d_totals, "d_totals", d_streams, d_events, cap_streams)) return rc;
   fskhip_processor *p = t->p;
-  p->used = true;
+  p->used = true; t->used = true;
   HIP_TRY(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)hip_stream;
   HIP_TRY(launch_xmodem_tx_step(p->T, p->S, d_mask, d_abort, t->X, t->W, cap_streams, d_totals, st));

@@ -5,6 +5,7 @@ XModemTransport (src/transports/xmodem/xmodem.ts:233-320) applied to the bytes a
 `XModemReceiverBatch`, the same grammar resident on the device over the RX rings of an `FSKProcessorBatch`, and
 `XModemSenderBatch`, `sendData()` for every stream of one: files, packets and the waits' grammar on the device, and
 `XModemFileReceiverBatch`, `receiveData()` for every stream of one: grammar, ACK / NAK, retries and the file on the device.
+All three follow their streams through `remapped`, `snapshot` and `from_snapshot`, as the engine and the processor do.
 Everything computes in libfskhip.so; there is no CPU path here.
 """
 import ctypes as C
@@ -12,6 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .engine import _blob, _struct_dict
 from ._lib import XModemTxEvent, XT_IDLE, XT_WAIT_NAK, XT_WAIT_ACK, XT_WAIT_FINAL_ACK, XT_PROGRESS, XT_DONE, XT_MAX_RETRIES, XT_ABORTED  # noqa: F401
 from ._lib import XModemRecvEvent, XR_IDLE, XR_SEND_NAK, XR_WAIT_BLOCK, XR_SEND_ACK, XR_PROGRESS, XR_DONE, XR_MAX_RETRIES, XR_ABORTED, XR_FILE_FULL  # noqa: F401
 from ._lib import XModemResult, XM_NEED_MORE, XM_EOT, XM_TRUNCATED, XM_INVALID_SEQUENCE, XM_INVALID_CRC, \
@@ -144,12 +146,89 @@ def scan_bursts(bursts, expected, device=0, data_pitch=None):
 RESULT_DTYPE = np.dtype([(k, "<u4" if t is C.c_uint32 else "<i4") for k, t in XModemResult._fields_])
 
 
-class XModemReceiverBatch:
+XMODEM_SNAPSHOT_KINDS = {1: "rx", 2: "tx", 3: "recv"}
+
+
+def xmodem_snapshot_info(snap):
+    """fskhip_xmodem_snapshot_info_get: what an XModem snapshot holds -- kind (1 rx, 2 tx, 3 recv), n_streams, param0 / param1
+    (tx: max_payload_size / max_retries; recv: file_capacity / max_retries), file_bytes -- validated on the host, no device needed"""
+    b = _blob(snap)
+    info = _lib.XModemSnapshotInfo()
+    _lib.check(_lib.lib().fskhip_xmodem_snapshot_info_get(b.ctypes.data, b.nbytes, C.byref(info)))
+    return _struct_dict(info)
+
+
+class _Lifecycle:
+    """remapped / snapshot / from_snapshot of the three resident classes (fskhip_xmodem_<_KIND>_remap, _snapshot_bytes, _snapshot,
+    _restore): the handle's state follows its streams with the map the engine and the processor were carried with.  A class says
+    how a new object like `self` is made over another processor (_like) and from an image's parameters (_from_info)."""
+    _KIND = None
+
+    def _fn(self, what):
+        return getattr(self._L, "fskhip_xmodem_%s_%s" % (self._KIND, what))
+
+    def remapped(self, processor, stream_map):
+        """A new object over `processor` -- the destination the engine and the processor were remapped into with the same
+        stream_map -- whose stream i continues stream stream_map[i] of this one, file included, or starts as a new transport
+        where stream_map[i] is -1.  This object stays usable."""
+        m = np.ascontiguousarray(stream_map, dtype=np.int64).reshape(-1)
+        nxt = self._like(processor)
+        try:
+            _lib.check(self._fn("remap")(nxt._h, self._h, m.ctypes.data if len(m) else None, len(m)))
+        except Exception:
+            nxt.close()
+            raise
+        return nxt
+
+    def snapshot(self, streams=None):
+        """The image of streams `streams` (None: all, in order) as `bytes`: words and files.  This object is read only and stays usable."""
+        sel = None if streams is None else np.ascontiguousarray(streams, dtype=np.int64).reshape(-1)
+        n = self.n_streams if sel is None else len(sel)
+        if sel is not None and not len(sel):
+            sel = np.zeros(1, np.int64)   # (an empty selection, not "all": a non-null pointer with n = 0; `sel` keeps the array alive)
+        sel_p = None if sel is None else sel.ctypes.data
+        w = C.c_size_t(0)
+        rc = self._fn("snapshot")(self._h, sel_p, n, None, 0, C.byref(w))   # the size
+        if rc != _lib.E_OVERFLOW:
+            _lib.check(rc)
+        buf = np.zeros(max(w.value, 1), np.uint8)
+        _lib.check(self._fn("snapshot")(self._h, sel_p, n, buf.ctypes.data, w.value, C.byref(w)))
+        return buf[:w.value].tobytes()
+
+    @classmethod
+    def from_snapshot(cls, processor, snap, stream_map=None, **overrides):
+        """A new object over `processor` that continues the records of a snapshot(): stream i continues record stream_map[i]
+        (-1: a new transport; None: every record, in order).  The constructor's parameters are the image's unless overridden
+        (file_capacity=, max_retries=)."""
+        info = xmodem_snapshot_info(snap)
+        if XMODEM_SNAPSHOT_KINDS.get(info["kind"]) != cls._KIND:
+            raise ValueError("the snapshot is of kind %r, not %r" % (XMODEM_SNAPSHOT_KINDS.get(info["kind"]), cls._KIND))
+        m = np.arange(info["n_streams"], dtype=np.int64) if stream_map is None else np.ascontiguousarray(stream_map, dtype=np.int64).reshape(-1)
+        nxt = cls._from_info(processor, info, overrides)
+        try:
+            b = _blob(snap)
+            _lib.check(nxt._fn("restore")(nxt._h, b.ctypes.data, b.nbytes, m.ctypes.data if len(m) else None, len(m)))
+        except Exception:
+            nxt.close()
+            raise
+        return nxt
+
+
+class XModemReceiverBatch(_Lifecycle):
     """The receive side of XModemTransport for every stream of an FSKProcessorBatch, resident on the device
     (fskhip_xmodem_rx_*): a poll walks the RX rings in place, takes whole packets out of them and returns the accepted
     payloads and one result record per stream with something to answer -- an incomplete packet waits in its ring for
     the next poll.  expectedSequence and the running packetsReceived / packetsDropped live with this object.  Sending
     ACK / NAK, retries and timeouts are the caller's.  The processor must outlive it."""
+
+    _KIND = "rx"
+
+    def _like(self, processor):
+        return XModemReceiverBatch(processor)
+
+    @classmethod
+    def _from_info(cls, processor, info, overrides):
+        return cls(processor, **overrides)
 
     def __init__(self, processor):
         self.processor = processor
@@ -238,13 +317,22 @@ TX_ERROR_FIRST_WAIT = "Operation aborted at sendData"
 TX_WORDS = ("state", "sequence", "fragment_index", "retries", "packets_sent", "retransmitted")
 
 
-class XModemSenderBatch:
+class XModemSenderBatch(_Lifecycle):
     """The send side of XModemTransport for every stream of an FSKProcessorBatch, resident on the device (fskhip_xmodem_tx_*):
     `send` hands each stream a file, a `poll` takes what each waiting stream's RX ring holds as one demodulate() reply, and where
     the control byte a wait is waiting for has arrived it builds the next packet (or the EOT) on the device and starts its
     modulation on the processor.  One poll is one reply, so what a poll finds depends on when it happens, as it does in the
     reference.  The timers are the caller's: a wait that has lasted too long is ended through `abort`.  The processor must
     outlive it."""
+
+    _KIND = "tx"
+
+    def _like(self, processor):
+        return XModemSenderBatch(processor, max_payload_size=self.max_payload_size, max_retries=self.max_retries)
+
+    @classmethod
+    def _from_info(cls, processor, info, overrides):
+        return cls(processor, **dict(dict(max_payload_size=info["param0"], max_retries=info["param1"]), **overrides))
 
     def __init__(self, processor, max_payload_size=128, max_retries=10):
         self.processor = processor
@@ -354,12 +442,21 @@ RECV_STATUS_ERRORS = {XR_MAX_RETRIES: "Receive failed after max retries", XR_ABO
 RECV_WORDS = ("state", "expected", "retries", "file_len", "packets_received", "dropped", "packets_sent")
 
 
-class XModemFileReceiverBatch:
+class XModemFileReceiverBatch(_Lifecycle):
     """receiveData() of XModemTransport for every stream of an FSKProcessorBatch, resident on the device (fskhip_xmodem_recv_*):
     `start` sends the initial NAK, a `poll` walks each waiting stream's RX ring up to the first step of the receive grammar that
     owes a reply, appends an accepted payload to the stream's file on the device, counts retries and starts the ACK or NAK on the
     processor.  Only events come back; `files` reads the assembled files once, at the end.  The timers are the caller's: a wait
     that has lasted too long is named in `timeout`, an external abort in `abort`.  The processor must outlive it."""
+
+    _KIND = "recv"
+
+    def _like(self, processor):
+        return XModemFileReceiverBatch(processor, file_capacity=self.file_capacity, max_retries=self.max_retries)
+
+    @classmethod
+    def _from_info(cls, processor, info, overrides):
+        return cls(processor, **dict(dict(file_capacity=info["param0"], max_retries=info["param1"]), **overrides))
 
     def __init__(self, processor, file_capacity=65536, max_retries=10):
         self.processor = processor
