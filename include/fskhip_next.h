@@ -677,6 +677,63 @@ int fskhip_fir_process_host(fskhip_fir *f, const float *in, size_t n_per_stream,
 int fskhip_fir_reset(fskhip_fir *f, int64_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Rate conversion by an integer factor L, on the device: what puts 8 kHz trunk audio (G.711 or 16-bit PCM) in front of an engine
+ * that runs at 48 kHz, and behind it.  An interpolator is FIRFilter above run over the zero-stuffed signal, a decimator the same
+ * filter with every L-th output kept; both are evaluated polyphase, so neither the zeros nor the dropped outputs are ever made, and
+ * the low rate samples are what crosses PCIe.  With c[0 .. n_taps) the taps and x_s[m] stream s's low rate samples counted from
+ * the handle's creation or last reset (samples before 0 are 0.0):
+ *   up     out_s[t] = f32(sum c[i] * x_s[(t - i) / L]) over the i, ascending, with (t - i) a non-negative multiple of L;
+ *          x = the element's value (fskhip.h: FSKHIP_SAMPLES_*, exact).  Interpolation wants taps with a gain of L.
+ *   down   y_s[k] = f32(sum_i c[i] * u_s[kL - i]), i ascending; element (s, k) of the output is y_s[k] in the format
+ *          (fskhip.h: "The same formats OUT").
+ * precision as for fskhip_fir_create: FSKHIP_PRECISION_F64 rounds every product and sum on its own, FSKHIP_PRECISION_F32 uses
+ * fp32 FMAs; either way the values are fskhip_fir_process_device's of that precision over the zero-stuffed input, bit for bit
+ * (leaving out a product with a stuffed zero can only change a zero's sign).  The handle keeps the last ceil((n_taps - 1) / L)
+ * values (up) or n_taps - 1 floats (down) of every stream, so any cut of a stream into calls gives the same samples.
+ *
+ * Formats, layouts and pitches (in elements) are fskhip.h's: the low rate side is [n_streams][pitch] (FSKHIP_LAYOUT_STREAM_MAJOR) or
+ * frames [sample][pitch >= n_streams] (FSKHIP_LAYOUT_SAMPLE_MAJOR) of the format's elements, the high rate side always float32
+ * [n_streams][pitch].  Nothing outside the samples of a row, or the n_streams columns of a frame, is written.
+ *
+ * Refusals, FSKHIP_E_INVALID before any device call, in this order.  create: taps or out NULL; n_streams or n_taps 0; a direction
+ * that is neither; a factor outside 1..32; an unknown precision; then n_taps > 4096, FSKHIP_E_UNSUPPORTED as for the FIR.  The
+ * up / down calls: a NULL handle; an unknown format, then layout; and for a call with n_in > 0: a NULL buffer; a pitch that is
+ * too small (the float side first); a pointer not aligned to its element; then the wrong call for the handle's direction; and for
+ * down an n_in that is no multiple of the factor -- the decimation grid is therefore the handle's own, output k of a stream is
+ * always at input kL counted from the reset, and no per-stream phase is needed.  A refused call leaves the history as it was.
+ * n_in = 0 is FSKHIP_OK and does nothing once the checks that need no samples have passed: handle, format, layout, direction (the
+ * wrong call for a handle is refused whatever its length).
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct fskhip_resampler fskhip_resampler;
+enum { FSKHIP_RESAMPLE_UP = 0, FSKHIP_RESAMPLE_DOWN = 1 };
+
+int fskhip_resampler_create(int device, int direction, uint32_t factor, const double *taps, uint32_t n_taps, uint32_t n_streams,
+                            int precision, fskhip_resampler **out);
+int fskhip_resampler_destroy(fskhip_resampler *r);
+uint32_t fskhip_resampler_streams(const fskhip_resampler *r);   /* the n_streams it was created for (0 for NULL) */
+uint32_t fskhip_resampler_history(const fskhip_resampler *r);   /* floats of history per stream (0 for NULL) */
+/* history to zero for one stream, or all when stream < 0 */
+int fskhip_resampler_reset(fskhip_resampler *r, int64_t stream);
+/* up: n_in samples per stream at d_src -> n_in * factor floats per stream at d_dst.  Asynchronous on hip_stream. */
+int fskhip_resampler_up_device(fskhip_resampler *r, const void *d_src, int format, int layout, size_t n_in, size_t src_pitch,
+                               float *d_dst, size_t dst_pitch, void *hip_stream);
+/* down: n_in floats per stream at d_src -> n_in / factor samples per stream at d_dst.  d_lens (device, n_streams words; may be
+ * NULL): input element t >= d_lens[s] of stream s reads as 0.0f whatever the row holds there -- also in the history the call
+ * leaves --, so a ragged batch rings out and ends in the format's silence.  Asynchronous on hip_stream. */
+int fskhip_resampler_down_device(fskhip_resampler *r, const float *d_src, size_t n_in, size_t src_pitch, const uint32_t *d_lens,
+                                 void *d_dst, int format, int layout, size_t dst_pitch, void *hip_stream);
+/* the same with host buffers (lens too), through the handle's own staging slabs and stream; synchronous */
+int fskhip_resampler_up_host(fskhip_resampler *r, const void *src, int format, int layout, size_t n_in, size_t src_pitch, float *dst,
+                             size_t dst_pitch);
+int fskhip_resampler_down_host(fskhip_resampler *r, const float *src, size_t n_in, size_t src_pitch, const uint32_t *lens, void *dst,
+                               int format, int layout, size_t dst_pitch);
+/* the history rows, [n_streams][fskhip_resampler_history()] floats on the host, oldest first: what carries a handle across a
+ * remap (get, permute the rows, set on a handle of the same direction, factor and taps).  Synchronous; nothing is copied when
+ * the history is empty.  Snapshot images hold no resampler. */
+int fskhip_resampler_state_get(fskhip_resampler *r, float *state);
+int fskhip_resampler_state_set(fskhip_resampler *r, const float *state);
+
+/* ---------------------------------------------------------------------------------------------------
  * IIR half of src/dsp/filters.ts: IIRFilter (8-106) batched over streams, + FilterFactory.createIIR* (325-344; the
  * designs themselves are fskhip_butterworth_* in fskhip.h).  Inside the demodulator the same filter lives as three
  * hard-wired biquads; this is the generic class: Direct Form I of any order <= 8.

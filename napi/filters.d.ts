@@ -18,6 +18,32 @@ export declare class FIRFilter extends FIRFilterBatch {
   constructor(coefficients: number[], options?: { device?: number; precision?: 0 | 1 });
   process(input: number): number;
 }
+export type SampleFormat = 'f32' | 's16' | 'mulaw' | 'alaw' | 0 | 1 | 2 | 3;
+export type SampleLayout = 'stream' | 'sample' | 0 | 1;
+export interface ResamplerOptions { taps?: number[]; lowRate?: number; device?: number; precision?: 0 | 1 }
+/** Rate conversion by an integer factor on the GPU (fskhip_resampler_*); the history is carried across calls. */
+declare class Resampler {
+  readonly factor: number;
+  readonly nStreams: number;
+  readonly lowRate: number;
+  readonly taps: number[];
+  readonly history: number;
+  reset(stream?: number): void;
+  /** the history rows, [nStreams][history], oldest first */
+  state(): Float32Array;
+  setState(state: Float32Array): void;
+  close(): void;
+}
+export declare class Upsampler extends Resampler {
+  constructor(factor: number, nStreams: number, options?: ResamplerOptions);
+  /** samples: [nStreams][pitch] or frames [nPerStream][pitch]; returns [nStreams][nPerStream * factor] */
+  process(samples: Float32Array | Int16Array | Uint8Array, format: SampleFormat, layout?: SampleLayout, nPerStream?: number, pitch?: number): Float32Array;
+}
+export declare class Downsampler extends Resampler {
+  constructor(factor: number, nStreams: number, options?: ResamplerOptions);
+  /** input: [nStreams][n], n a multiple of factor; returns [nStreams][n / factor] or frames [n / factor][nStreams] */
+  process(input: Float32Array, format: SampleFormat, layout?: SampleLayout, lens?: Uint32Array | null): Float32Array | Int16Array | Uint8Array;
+}
 export declare class FilterFactory {
   static createFIRLowpass(cutoffFreq: number, sampleRate: number, numTaps?: number): FIRFilter;
   static createFIRHighpass(cutoffFreq: number, sampleRate: number, numTaps?: number): FIRFilter;

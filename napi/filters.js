@@ -47,6 +47,66 @@ class FIRFilter extends FIRFilterBatch {          // filters.ts:112-167
   process(input) { return this.processBuffer(Float32Array.of(input))[0]; }
 }
 
+// Rate conversion by an integer factor on the GPU (include/fskhip_next.h: fskhip_resampler_*): capture samples at lowRate <-> float32
+// [nStreams][n] at factor * lowRate, the history carried across calls.  Without taps the design is sincLowpass(0.45 * lowRate,
+// factor * lowRate, 16 * factor + 1) -- times factor in the up direction --: 97 taps and 3 600 Hz for 8 kHz <-> 48 kHz.
+const SAMPLE_FORMATS = { f32: 0, s16: 1, mulaw: 2, alaw: 3 };
+const SAMPLE_TYPES = [Float32Array, Int16Array, Uint8Array, Uint8Array];
+function sampleFormat(f) {
+  const v = typeof f === 'string' ? SAMPLE_FORMATS[f.toLowerCase()] : f;
+  if (!(v >= 0 && v <= 3)) throw new TypeError('unknown sample format ' + f);
+  return v;
+}
+function sampleLayout(l) {
+  const v = l === undefined || l === null ? 0 : typeof l === 'string' ? { stream: 0, sample: 1 }[l.toLowerCase()] : l;
+  if (v !== 0 && v !== 1) throw new TypeError('unknown layout ' + l);
+  return v;
+}
+class Resampler {
+  constructor(direction, factor, nStreams, options = {}) {
+    if (!(Number.isInteger(factor) && factor >= 1 && factor <= 32)) throw new RangeError('factor ' + factor + ' outside 1..32');
+    this.factor = factor;
+    this.nStreams = nStreams;
+    this.lowRate = options.lowRate === undefined ? 8000 : options.lowRate;
+    let taps = options.taps;
+    if (!taps) {
+      taps = FilterDesign.sincLowpass(0.45 * this.lowRate, factor * this.lowRate, 16 * factor + 1);
+      if (direction === 0) taps = taps.map((t) => t * factor);
+    }
+    this.taps = [...taps];
+    this.handle = addon.resamplerCreate(direction, factor, Float64Array.from(this.taps), nStreams, options.device || 0,
+      options.precision === undefined ? PRECISION_F32 : options.precision);
+    this.history = addon.resamplerHistory(this.handle);
+  }
+  reset(stream = -1) { addon.resamplerReset(this.handle, stream); }
+  state() { return addon.resamplerState(this.handle); }             // Float32Array [nStreams][history], oldest first
+  setState(state) { addon.resamplerSetState(this.handle, state); }
+  close() { if (this.handle) { addon.resamplerDestroy(this.handle); this.handle = null; } }
+}
+class Upsampler extends Resampler {
+  constructor(factor, nStreams, options = {}) { super(0, factor, nStreams, options); }
+  // samples: the format's typed array, [nStreams][pitch] (layout 'stream') or frames [nPerStream][pitch >= nStreams] ('sample');
+  // nPerStream and pitch default to a packed array's -> Float32Array [nStreams][nPerStream * factor]
+  process(samples, format, layout = 'stream', nPerStream, pitch) {
+    const f = sampleFormat(format), l = sampleLayout(layout);
+    if (!(samples instanceof SAMPLE_TYPES[f])) throw new TypeError('format ' + format + ' takes a ' + SAMPLE_TYPES[f].name);
+    const n = nPerStream === undefined ? samplesPerStream(samples, this.nStreams) : nPerStream;
+    if (n === 0) return new Float32Array(0);
+    return addon.resamplerUp(this.handle, samples, f, l, n, pitch === undefined ? (l === 1 ? this.nStreams : n) : pitch, this.factor);
+  }
+}
+class Downsampler extends Resampler {
+  constructor(factor, nStreams, options = {}) { super(1, factor, nStreams, options); }
+  // input: Float32Array [nStreams][n], n a multiple of factor; lens (Uint32Array or null): stream s reads as 0.0 from lens[s] on
+  // -> the format's typed array, [nStreams][n / factor] or frames [n / factor][nStreams]
+  process(input, format, layout = 'stream', lens = null) {
+    const f = sampleFormat(format), l = sampleLayout(layout);
+    const n = samplesPerStream(input, this.nStreams);
+    if (n === 0) return new SAMPLE_TYPES[f](0);
+    return addon.resamplerDown(this.handle, input, n, lens, f, l, this.factor);
+  }
+}
+
 class IIRFilterBatch {                            // filters.ts:8-106, S streams per call
   constructor(b, a, nStreams = 1, options = {}) {
     // the constructor's three errors (filters.ts:19-21), before anything touches the GPU
@@ -90,4 +150,4 @@ class FilterFactory {                             // filters.ts:325-368
   static createFIRHighpass(cutoffFreq, sampleRate, numTaps = 51) { return new FIRFilter(FilterDesign.sincHighpass(cutoffFreq, sampleRate, numTaps)); }
   static createFIRBandpass(centerFreq, bandwidth, sampleRate, numTaps = 51) { return new FIRFilter(FilterDesign.sincBandpass(centerFreq, bandwidth, sampleRate, numTaps)); }
 }
-module.exports = { FilterDesign, IIRFilter, IIRFilterBatch, FIRFilter, FIRFilterBatch, FilterFactory, PRECISION_F32, PRECISION_F64 };
+module.exports = { FilterDesign, IIRFilter, IIRFilterBatch, FIRFilter, FIRFilterBatch, Upsampler, Downsampler, FilterFactory, PRECISION_F32, PRECISION_F64 };

@@ -35,6 +35,10 @@
 //   sincLowpass/sincHighpass(cutoff, sampleRate, numTaps), sincBandpass(center, bandwidth, sampleRate, numTaps) -> Float64Array
 //   firCreate(taps: Float64Array, nStreams, device, precision) -> handle;  firDestroy(handle)
 //   firProcess(handle, input: Float32Array, n, pitch, nStreams) -> Float32Array;  firReset(handle, stream)
+//   resamplerCreate(direction, factor, taps: Float64Array, nStreams, device, precision) -> handle;  resamplerDestroy(handle);  resamplerHistory(handle)
+//   resamplerUp(handle, samples, format, layout, nIn, pitch, factor) -> Float32Array [S][nIn * factor]
+//   resamplerDown(handle, input: Float32Array [S][nIn], nIn, lens: Uint32Array|null, format, layout, factor) -> the format's typed array
+//   resamplerReset(handle, stream);  resamplerState(handle) -> Float32Array [S][history];  resamplerSetState(handle, Float32Array)
 //   iirCreate(b, a: Float64Array, nStreams, device, precision) -> handle; iirProcess(handle, Float32Array | Float64Array, n, pitch, nStreams);
 //   iirCoefficients(handle), iirReset(handle, stream), iirDestroy(handle); butterworth(kind, f, bandwidth, sampleRate) -> [b0 b1 b2 a0 a1 a2]
 #include <cstring>
@@ -45,16 +49,24 @@
 
 namespace {
 
-// FIR / IIR filter handles: the external owns a box, so that close() can empty it (a later call throws instead of touching freed
-// memory) and a filter that is never close()d is destroyed when the garbage collector drops the handle
-struct FilterBox { void *p; bool iir; };
+// FIR / IIR filter and resampler handles: the external owns a box, so that close() can empty it (a later call throws instead of
+// touching freed memory) and a filter that is never close()d is destroyed when the garbage collector drops the handle
+enum { BOX_FIR = 0, BOX_IIR = 1, BOX_RESAMPLER = 2 };
+struct FilterBox { void *p; int kind; };
+void filter_box_destroy(FilterBox *b) {
+  if (!b->p) return;
+  if (b->kind == BOX_IIR) fskhip_iir_destroy((fskhip_iir *)b->p);
+  else if (b->kind == BOX_RESAMPLER) fskhip_resampler_destroy((fskhip_resampler *)b->p);
+  else fskhip_fir_destroy((fskhip_fir *)b->p);
+  b->p = nullptr;
+}
 void filter_box_finalize(napi_env, void *data, void *) {
   FilterBox *b = (FilterBox *)data;
-  if (b->p) { if (b->iir) fskhip_iir_destroy((fskhip_iir *)b->p); else fskhip_fir_destroy((fskhip_fir *)b->p); }
+  filter_box_destroy(b);
   delete b;
 }
-napi_value filter_box_new(napi_env env, void *p, bool iir) {
-  FilterBox *b = new FilterBox{p, iir};
+napi_value filter_box_new(napi_env env, void *p, int kind) {
+  FilterBox *b = new FilterBox{p, kind};
   napi_value ext;
   if (napi_create_external(env, b, filter_box_finalize, nullptr, &ext) != napi_ok) { filter_box_finalize(env, b, nullptr); return nullptr; }
   return ext;
@@ -68,8 +80,7 @@ void *filter_of(napi_env env, napi_value v) {
 void filter_box_close(napi_env env, napi_value v) {
   void *q = nullptr;
   if (napi_get_value_external(env, v, &q) != napi_ok || !q) return;
-  FilterBox *b = (FilterBox *)q;
-  if (b->p) { if (b->iir) fskhip_iir_destroy((fskhip_iir *)b->p); else fskhip_fir_destroy((fskhip_fir *)b->p); b->p = nullptr; }
+  filter_box_destroy((FilterBox *)q);
 }
 napi_value Crc16(napi_env env, napi_callback_info info) {
   ARGS(4);
@@ -877,7 +888,7 @@ napi_value FirCreate(napi_env env, napi_callback_info info) {
   fskhip_fir *f = nullptr;
   int rc = fskhip_fir_create(i32(env, argv[2]), (const double *)taps, (uint32_t)nt, u32(env, argv[1]), i32(env, argv[3]), &f);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
-  return filter_box_new(env, f, false);
+  return filter_box_new(env, f, BOX_FIR);
 }
 napi_value FirDestroy(napi_env env, napi_callback_info info) {
   ARGS(1);
@@ -910,6 +921,100 @@ napi_value FirReset(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// ---- resampler (include/fskhip_next.h: fskhip_resampler_*) ----
+napi_value ResamplerCreate(napi_env env, napi_callback_info info) {   // (direction, factor, taps: Float64Array, nStreams, device, precision)
+  ARGS(6);
+  void *taps; size_t nt;
+  if (!typed(env, argv[2], napi_float64_array, &taps, &nt)) return nullptr;
+  fskhip_resampler *r = nullptr;
+  int rc = fskhip_resampler_create(i32(env, argv[4]), i32(env, argv[0]), u32(env, argv[1]), (const double *)taps, (uint32_t)nt, u32(env, argv[3]),
+                                   i32(env, argv[5]), &r);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return filter_box_new(env, r, BOX_RESAMPLER);
+}
+napi_value ResamplerDestroy(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  filter_box_close(env, argv[0]);
+  return nullptr;
+}
+napi_value ResamplerHistory(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
+  if (!r) return nullptr;
+  napi_value v;
+  NAPI_OK(napi_create_uint32(env, fskhip_resampler_history(r), &v));
+  return v;
+}
+// (handle, samples in the format's typed array, format, layout, nIn, pitch, factor) -> Float32Array [S][nIn * factor]
+napi_value ResamplerUp(napi_env env, napi_callback_info info) {
+  ARGS(7);
+  const int32_t format = i32(env, argv[2]), layout = i32(env, argv[3]);
+  if (!sample_format_ok(env, format, layout)) return nullptr;
+  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
+  if (!r) return nullptr;
+  void *in; size_t ilen;
+  if (!typed(env, argv[1], sample_array_type(format), &in, &ilen)) return nullptr;
+  const uint32_t n = u32(env, argv[4]), pitch = u32(env, argv[5]), L = u32(env, argv[6]), S = fskhip_resampler_streams(r);
+  const int64_t need = samples_needed(layout, S, n, pitch);
+  if (need < 0 || (size_t)need > ilen) { napi_throw_range_error(env, nullptr, "input too short"); return nullptr; }
+  void *out;
+  napi_value out_v = make_typed(env, napi_float32_array, (size_t)n * L * S, 4, &out);
+  if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  int rc = fskhip_resampler_up_host(r, in, format, layout, n, pitch, (float *)out, (size_t)n * L);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return out_v;
+}
+// (handle, input: Float32Array [S][nIn], nIn, lens: Uint32Array|null, format, layout, factor) -> the format's typed array, packed
+napi_value ResamplerDown(napi_env env, napi_callback_info info) {
+  ARGS(7);
+  const int32_t format = i32(env, argv[4]), layout = i32(env, argv[5]);
+  if (!sample_format_ok(env, format, layout)) return nullptr;
+  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
+  if (!r) return nullptr;
+  void *in, *lens; size_t ilen, llen;
+  if (!typed(env, argv[1], napi_float32_array, &in, &ilen) || !typed(env, argv[3], napi_uint32_array, &lens, &llen, true)) return nullptr;
+  const uint32_t n = u32(env, argv[2]), L = u32(env, argv[6]), S = fskhip_resampler_streams(r);
+  if (L == 0 || (size_t)n * S > ilen || (lens && llen < S)) { napi_throw_range_error(env, nullptr, "arguments too short"); return nullptr; }
+  const size_t n_out = n / L, pitch = layout == FSKHIP_LAYOUT_SAMPLE_MAJOR ? S : n_out;
+  void *out;
+  napi_value out_v = make_typed(env, sample_array_type(format), n_out * S, fskhip_sample_bytes(format), &out);
+  if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  int rc = fskhip_resampler_down_host(r, (const float *)in, n, n, (const uint32_t *)lens, out, format, layout, pitch ? pitch : 1);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return out_v;
+}
+napi_value ResamplerReset(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
+  if (!r) return nullptr;
+  int64_t s = -1;
+  napi_get_value_int64(env, argv[1], &s);
+  int rc = fskhip_resampler_reset(r, s);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+napi_value ResamplerState(napi_env env, napi_callback_info info) {   // -> Float32Array [S][history]
+  ARGS(1);
+  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
+  if (!r) return nullptr;
+  void *out;
+  napi_value out_v = make_typed(env, napi_float32_array, (size_t)fskhip_resampler_streams(r) * fskhip_resampler_history(r), 4, &out);
+  int rc = fskhip_resampler_state_get(r, (float *)out);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return out_v;
+}
+napi_value ResamplerSetState(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
+  if (!r) return nullptr;
+  void *st; size_t n;
+  if (!typed(env, argv[1], napi_float32_array, &st, &n)) return nullptr;
+  if (n != (size_t)fskhip_resampler_streams(r) * fskhip_resampler_history(r)) { napi_throw_range_error(env, nullptr, "state must be [nStreams][history]"); return nullptr; }
+  int rc = fskhip_resampler_state_set(r, (const float *)st);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+
 // ---- IIRFilter (src/dsp/filters.ts:8-106) ----
 napi_value IirCreate(napi_env env, napi_callback_info info) {   // (b: Float64Array, a: Float64Array, nStreams, device, precision)
   ARGS(5);
@@ -918,7 +1023,7 @@ napi_value IirCreate(napi_env env, napi_callback_info info) {   // (b: Float64Ar
   fskhip_iir *f = nullptr;
   int rc = fskhip_iir_create(i32(env, argv[3]), (const double *)b, (uint32_t)nb, (const double *)a, (uint32_t)na, u32(env, argv[2]), i32(env, argv[4]), &f);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
-  return filter_box_new(env, f, true);
+  return filter_box_new(env, f, BOX_IIR);
 }
 napi_value IirDestroy(napi_env env, napi_callback_info info) {
   ARGS(1);
@@ -1050,6 +1155,14 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"firDestroy", nullptr, FirDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"firProcess", nullptr, FirProcess, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"firReset", nullptr, FirReset, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerCreate", nullptr, ResamplerCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerDestroy", nullptr, ResamplerDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerHistory", nullptr, ResamplerHistory, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerUp", nullptr, ResamplerUp, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerDown", nullptr, ResamplerDown, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerReset", nullptr, ResamplerReset, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerState", nullptr, ResamplerState, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerSetState", nullptr, ResamplerSetState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirCreate", nullptr, IirCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirDestroy", nullptr, IirDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirCoefficients", nullptr, IirCoefficients, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -23,6 +23,7 @@ PRECISION_F32, PRECISION_F64 = 0, 1
 DEMOD_WRITEBACK_AGC = 1
 SAMPLES_F32, SAMPLES_S16, SAMPLES_MULAW, SAMPLES_ALAW = 0, 1, 2, 3
 LAYOUT_STREAM_MAJOR, LAYOUT_SAMPLE_MAJOR = 0, 1
+RESAMPLE_UP, RESAMPLE_DOWN = 0, 1
 
 
 class Config(C.Structure):
@@ -235,6 +236,17 @@ _SYMBOLS = [
     ("fskhip_fir_process_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P]),
     ("fskhip_fir_process_host", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t]),
     ("fskhip_fir_reset", C.c_int, [_P, C.c_int64]),
+    ("fskhip_resampler_create", C.c_int, [C.c_int, C.c_int, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P)]),
+    ("fskhip_resampler_destroy", C.c_int, [_P]),
+    ("fskhip_resampler_streams", C.c_uint32, [_P]),
+    ("fskhip_resampler_history", C.c_uint32, [_P]),
+    ("fskhip_resampler_reset", C.c_int, [_P, C.c_int64]),
+    ("fskhip_resampler_up_device", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P]),
+    ("fskhip_resampler_down_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P, C.c_int, C.c_int, C.c_size_t, _P]),
+    ("fskhip_resampler_up_host", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_size_t]),
+    ("fskhip_resampler_down_host", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P, C.c_int, C.c_int, C.c_size_t]),
+    ("fskhip_resampler_state_get", C.c_int, [_P, _P]),
+    ("fskhip_resampler_state_set", C.c_int, [_P, _P]),
     ("fskhip_iir_create", C.c_int, [C.c_int, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P)]),
     ("fskhip_iir_destroy", C.c_int, [_P]),
     ("fskhip_iir_get_coefficients", C.c_int, [_P, _P, C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint32)]),

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "fsk_filter_host.h"
+#include "fsk_mac_dev.h"
 
 namespace fsk {
 namespace {
@@ -20,13 +21,6 @@ namespace {
 constexpr int kFirBlock = 256;
 constexpr int kFirPerLane = 4;
 constexpr int kFirTile = kFirBlock * kFirPerLane;
-
-template <typename Real>
-__device__ __forceinline__ Real mac(Real acc, Real c, float x);
-template <>
-__device__ __forceinline__ double mac<double>(double acc, double c, float x) { return acc + c * (double)x; }  // two roundings (-ffp-contract=off)
-template <>
-__device__ __forceinline__ float mac<float>(float acc, float c, float x) { return __builtin_fmaf(c, x, acc); }
 
 // hist holds the n_taps-1 inputs before sample 0 of this call, oldest first ([stream][n_taps-1])
 template <typename Real>

@@ -115,6 +115,18 @@ hipError_t launch_ingest(const void *d_src, int format, int layout, uint32_t n_s
 // is launched for an empty batch.
 hipError_t launch_egress(const float *d_src, size_t src_pitch, const uint32_t *d_lens, uint32_t n_streams, size_t n, int format, int layout, void *d_dst,
                          size_t dst_pitch, hipStream_t st);
+// fsk_resample.hip: integer-factor rate conversion between a capture format at the low rate and float32 [stream][pitch] at the high
+// rate (fskhip_resampler_*).  The caller has checked the arguments; nothing is launched for an empty batch; hipErrorInvalidValue
+// where the batch is more workgroups than one launch takes.  precision selects the taps' type (float / double).  up: d_phase_taps is
+// [factor][ceil(n_taps / factor)], phase p's taps c[p], c[p + factor], ...; the histories are [n_streams][ceil((n_taps - 1) / factor)].
+// down: d_taps as given, n_out = outputs per stream (the call reads n_out * factor inputs), histories [n_streams][n_taps - 1]; d_lens
+// (may be null): inputs from d_lens[s] on read as 0.0f.  Both read d_hist_in and write the history after the call to d_hist_out.
+hipError_t launch_resample_up(int precision, const void *d_src, int format, int layout, uint32_t n_streams, size_t n_in, size_t src_pitch, float *d_dst,
+                              size_t dst_pitch, uint32_t factor, uint32_t n_taps, const void *d_phase_taps, const float *d_hist_in, float *d_hist_out,
+                              hipStream_t st);
+hipError_t launch_resample_down(int precision, const float *d_src, size_t n_out, size_t src_pitch, const uint32_t *d_lens, uint32_t n_streams, void *d_dst,
+                                int format, int layout, size_t dst_pitch, uint32_t factor, uint32_t n_taps, const void *d_taps, const float *d_hist_in,
+                                float *d_hist_out, hipStream_t st);
 // fsk_processor_remap.hip: FSKProcessor state (ProcState) between processors and stream-major records (ProcImage).
 // gather: stream i of D continues stream d_map[i] of S, or starts as a created one where d_map[i] = -1.
 // unpack: the same from the slab I of an image's records; streams whose record is in another slab are left alone, new ones are

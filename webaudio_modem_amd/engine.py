@@ -319,6 +319,8 @@ class FSKEngine:
 
     def close(self):
         if getattr(self, "_h", None):
+            for ptr, _cap in self.__dict__.pop("_at_scratch", {}).values():
+                self._L.fskhip_device_free(self._h, ptr)
             self._L.fskhip_destroy(self._h)
             self._h = None
 
@@ -450,6 +452,49 @@ class FSKEngine:
                                                       counts.ctypes.data, eod.ctypes.data, 0))
         return [out[s, :counts[s]].tobytes() for s in range(S)], eod
 
+    def demodulate_samples_at(self, samples, fmt, layout, upsampler, out_pitch=None):
+        """demodulate_samples for capture samples at a lower rate (8 kHz trunk audio in front of a 48 kHz engine): the narrow
+        samples cross PCIe as they are, `upsampler` (filters.Upsampler, on this engine's device, its history carried from call to
+        call) widens and interpolates them into a device tile, and demodulate_device runs on that tile.  Returns what
+        demodulate_data returns."""
+        x, code, lay, S, N, _ = sample_args(samples, fmt, layout)
+        if S != self.n_streams or upsampler.n_streams != S:
+            raise ValueError("expected %d streams, got %d (upsampler: %d)" % (self.n_streams, S, upsampler.n_streams))
+        if upsampler.device != self.device:
+            raise ValueError("the upsampler is on device %d, the engine on %d" % (upsampler.device, self.device))
+        eod = np.zeros(S, dtype=np.uint32)
+        if N == 0:
+            return [b""] * S, eod
+        x = np.ascontiguousarray(x)
+        n = N * upsampler.factor
+        tpitch = (n + 3) & ~3
+        opitch = out_pitch or self.max_bytes(n)
+        out = np.zeros((S, opitch), dtype=np.uint8)
+        counts = np.zeros(S, dtype=np.uint32)
+        d_src, d_tile, d_out, d_counts, d_eod = (self._scratch(k, b) for k, b in (("narrow", x.nbytes), ("tile", 4 * S * tpitch), ("bytes", out.nbytes),
+                                                                                  ("counts", 4 * S), ("eod", 4 * S)))
+        self.h2d(d_src, x)
+        upsampler.process_device(d_src, code, lay, N, x.shape[1], d_tile, tpitch)
+        self.demodulate_device(d_tile, n, tpitch, d_out, opitch, d_counts, d_eod)
+        self.synchronize()
+        for a, d in ((out, d_out), (counts, d_counts), (eod, d_eod)):
+            self.d2h(a, d)
+        return [out[s, :counts[s]].tobytes() for s in range(S)], eod
+
+    def _scratch(self, name, nbytes):
+        """a device buffer of the *_samples_at calls, kept with the engine and only ever grown (freed by close())"""
+        slots = self.__dict__.setdefault("_at_scratch", {})
+        ptr, cap = slots.get(name, (None, 0))
+        if cap < nbytes:
+            if ptr:
+                self.synchronize()
+                self.device_free(ptr)
+                slots.pop(name)
+            cap = max(16, int(nbytes))
+            ptr = self.device_malloc(cap)
+            slots[name] = (ptr, cap)
+        return ptr
+
     def demodulate_device(self, d_samples, n_per_stream, pitch, d_out, out_pitch, d_counts, d_eod=None,
                           flags=0, stream=None):
         """Device-pointer form (ints): asynchronous on `stream` (a hipStream_t handle or None)."""
@@ -488,6 +533,39 @@ class FSKEngine:
         _lib.check(self._L.fskhip_modulate_host_fmt(self._h, pay.ctypes.data, lens.ctypes.data, ppitch, code, lay, out.ctypes.data, n, pitch,
                                                     out_lens.ctypes.data))
         return out, out_lens
+
+    def modulate_samples_at(self, payloads, fmt, layout, downsampler, n_per_stream=None):
+        """modulate_samples at a lower rate (a 48 kHz engine in front of an 8 kHz trunk): modulate_device writes the float tile,
+        `downsampler` (filters.Downsampler, on this engine's device) decimates it with every stream's samples behind its own
+        signal read as zeros, and one narrow copy comes back.  n_per_stream: low rate samples per stream (None: what the longest
+        signal and the filter's ringing behind it take).  Returns (samples, lens): [S, n] or frames [n, S], and each stream's low
+        rate length ceil((len + n_taps - 1) / factor), from where on it is the format's silence."""
+        if len(payloads) != self.n_streams:
+            raise ValueError("need one payload per stream")
+        S, L = self.n_streams, downsampler.factor
+        if downsampler.n_streams != S or downsampler.device != self.device:
+            raise ValueError("the downsampler must have this engine's %d streams and device %d" % (S, self.device))
+        pay, lens, ppitch = payload_args(payloads)
+        n = downsampler.low_rate_length(self.modulated_length(int(lens.max()))) if n_per_stream is None else int(n_per_stream)
+        out, code, lay, pitch = samples_out(fmt, layout, S, n)
+        out_lens = np.zeros(S, dtype=np.uint32)
+        if n == 0:
+            return out, out_lens
+        tpitch = (n * L + 3) & ~3
+        d_pay, d_plens, d_tile, d_lens, d_dst = (self._scratch(k, b) for k, b in (("payloads", pay.nbytes), ("payload_lens", lens.nbytes), ("tile", 4 * S * tpitch),
+                                                                                  ("counts", 4 * S), ("narrow", out.nbytes)))
+        self.h2d(d_pay, pay)
+        self.h2d(d_plens, lens)
+        self.modulate_device(d_pay, d_plens, ppitch, d_tile, tpitch, d_lens)
+        self.synchronize()
+        self.d2h(out_lens, d_lens)
+        if int(out_lens.max()) > n * L:           # refused before the decimator runs: its history stays as it was
+            s = int(np.argmax(out_lens > n * L))
+            raise FskHipError(_lib.E_OVERFLOW, "stream %d needs %d samples, slab holds %d" % (s, out_lens[s], n * L))
+        downsampler.process_device(d_tile, n * L, tpitch, d_lens, d_dst, code, lay, pitch)
+        self.synchronize()
+        self.d2h(out, d_dst)
+        return out, np.minimum((out_lens.astype(np.int64) + len(downsampler.taps) - 1 + L - 1) // L, n).astype(np.uint32)
 
     def modulate_device(self, d_payloads, d_lens, payload_pitch, d_out, out_pitch, d_out_lens, stream=None):
         _lib.check(self._L.fskhip_modulate_device(self._h, d_payloads, d_lens, payload_pitch, d_out, out_pitch,

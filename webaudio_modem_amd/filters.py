@@ -110,6 +110,121 @@ class FIRFilter(FIRFilterBatch):
         return float(self.processBuffer(self._np.array([x], dtype=self._np.float32))[0])
 
 
+class _Resampler:
+    """What Upsampler and Downsampler share: an fskhip_resampler handle (include/fskhip_next.h), its design, reset, the history
+    rows and close."""
+
+    _DIRECTION = None
+
+    def __init__(self, factor, n_streams, taps=None, low_rate=8000, device=0, precision=_lib.PRECISION_F32):
+        import numpy as np
+        self._np = np
+        self.factor, self.n_streams, self.low_rate, self.device, self.precision = int(factor), int(n_streams), low_rate, device, precision
+        if taps is None:
+            if not 1 <= self.factor <= 32:
+                raise ValueError("factor %d outside 1..32" % self.factor)
+            # a Hamming-windowed sinc at 0.45 of the low rate (3 600 Hz at 8 kHz), 16 taps per phase and one
+            taps = FilterDesign.sincLowpass(0.45 * low_rate, self.factor * low_rate, 16 * self.factor + 1)
+            if self._DIRECTION == _lib.RESAMPLE_UP:
+                taps = [t * float(self.factor) for t in taps]     # the stuffed zeros take 1 / factor of the level
+        self.taps = [float(t) for t in taps]
+        self._L = _lib.lib()
+        h = C.c_void_p()
+        _lib.check(self._L.fskhip_resampler_create(device, self._DIRECTION, self.factor, (C.c_double * max(1, len(self.taps)))(*self.taps),
+                                                   len(self.taps), self.n_streams, precision, C.byref(h)))
+        self._h = h
+        self.history = int(self._L.fskhip_resampler_history(h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.fskhip_resampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=-1):
+        _lib.check(self._L.fskhip_resampler_reset(self._h, stream))
+
+    def state(self):
+        """the history rows, float32 [n_streams, history], oldest first (fskhip_resampler_state_get)"""
+        st = self._np.zeros((self.n_streams, self.history), self._np.float32)
+        _lib.check(self._L.fskhip_resampler_state_get(self._h, st.ctypes.data))
+        return st
+
+    def set_state(self, state):
+        """fskhip_resampler_state_set: rows as state() returns them, e.g. permuted by a remap's stream map"""
+        st = self._np.ascontiguousarray(state, dtype=self._np.float32)
+        if st.shape != (self.n_streams, self.history):
+            raise ValueError("state must be [%d, %d]" % (self.n_streams, self.history))
+        _lib.check(self._L.fskhip_resampler_state_set(self._h, st.ctypes.data))
+
+
+class Upsampler(_Resampler):
+    """Capture samples at low_rate -> float32 [S, n * factor] at factor * low_rate, on the GPU: FIRFilterBatch(taps) over the
+    zero-stuffed samples, evaluated polyphase, history carried across calls.  taps None: sincLowpass(0.45 * low_rate,
+    factor * low_rate, 16 * factor + 1) times factor."""
+
+    _DIRECTION = _lib.RESAMPLE_UP
+
+    def process(self, samples, fmt=None, layout="stream"):
+        """samples as FSKEngine.demodulate_samples takes them; returns float32 [S, n * factor]"""
+        from .engine import sample_args
+        x, code, lay, S, N, pitch = sample_args(samples, fmt, layout)
+        if S != self.n_streams:
+            raise ValueError("expected %d streams, got %d" % (self.n_streams, S))
+        out = self._np.zeros((S, N * self.factor), self._np.float32)
+        if N:
+            _lib.check(self._L.fskhip_resampler_up_host(self._h, x.ctypes.data, code, lay, N, pitch, out.ctypes.data, N * self.factor))
+        return out
+
+    def process_device(self, d_src, fmt, layout, n_in, src_pitch, d_dst, dst_pitch, stream=None):
+        """fskhip_resampler_up_device: device pointers (ints), asynchronous on `stream`"""
+        from .engine import _sample_codes
+        _lib.check(self._L.fskhip_resampler_up_device(self._h, d_src, *_sample_codes(fmt, layout, True), n_in, src_pitch, d_dst, dst_pitch, stream))
+
+
+class Downsampler(_Resampler):
+    """float32 [S, n] at factor * low_rate -> samples of a capture format at low_rate, on the GPU: FIRFilterBatch(taps) with every
+    factor-th output kept, encoded; n must be a multiple of factor.  taps None: sincLowpass(0.45 * low_rate, factor * low_rate,
+    16 * factor + 1)."""
+
+    _DIRECTION = _lib.RESAMPLE_DOWN
+
+    def process(self, x, fmt, layout="stream", lens=None, out=None):
+        """x: float32 [S, n]; lens (or None): samples of stream s from lens[s] on read as 0.0.  Returns the samples as
+        FSKEngine.modulate_samples does, [S, n / factor] or frames [n / factor, S]; `out`: the array to write into."""
+        from .engine import samples_out
+        np = self._np
+        x = np.asarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        if x.ndim != 2 or x.shape[0] != self.n_streams:
+            raise ValueError("input must be [n_streams, n]")
+        if x.strides[1] != 4 and x.shape[1] > 1 or x.strides[0] % 4 or (x.shape[0] > 1 and x.strides[0] < 4 * x.shape[1]):
+            x = np.ascontiguousarray(x)
+        n = x.shape[1]
+        out, code, lay, pitch = samples_out(fmt, layout, self.n_streams, n // self.factor, out)
+        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.uint32)
+        if ln is not None and ln.shape != (self.n_streams,):
+            raise ValueError("need one length per stream")
+        _lib.check(self._L.fskhip_resampler_down_host(self._h, x.ctypes.data, n, max(x.strides[0] // 4 if x.shape[0] > 1 else n, n, 1),
+                                                      None if ln is None else ln.ctypes.data, out.ctypes.data, code, lay, pitch))
+        return out
+
+    def process_device(self, d_src, n_in, src_pitch, d_lens, d_dst, fmt, layout, dst_pitch, stream=None):
+        """fskhip_resampler_down_device: device pointers (ints), asynchronous on `stream`"""
+        from .engine import _sample_codes
+        _lib.check(self._L.fskhip_resampler_down_device(self._h, d_src, n_in, src_pitch, d_lens, d_dst, *_sample_codes(fmt, layout, True), dst_pitch, stream))
+
+    def low_rate_length(self, n):
+        """low rate samples that hold a signal of n samples and the filter's ringing behind it"""
+        return (int(n) + len(self.taps) - 1 + self.factor - 1) // self.factor
+
+
 class IIRFilterBatch:
     """`new IIRFilter(b, a)` (filters.ts:8-106) for n_streams streams on one GPU: `processBuffer` on a float32 [S, N]
     block (Float32Array in, Float32Array out), `processSamples` on a float64 block (what `process(x)` returns sample by
