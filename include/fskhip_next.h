@@ -733,6 +733,37 @@ int fskhip_resampler_down_host(fskhip_resampler *r, const float *src, size_t n_i
 int fskhip_resampler_state_get(fskhip_resampler *r, float *state);
 int fskhip_resampler_state_set(fskhip_resampler *r, const float *state);
 
+/*
+ * process() with both sides at the trunk's own rate (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): one FSKProcessor quantum whose
+ * input is interpolated by `up` and whose output is decimated by `down` on the device, so a 20 ms packet of 8 kHz G.711 goes in
+ * and comes out as it is.  n_in, n_out and the pitches count low rate elements; formats, layouts and pitches are fskhip.h's, exactly
+ * as fskhip_processor_process_fmt_* take them.  With Lu / Ld the handles' factors the call IS, bit for bit,
+ *   fskhip_resampler_up_device(up, d_in, ..., X)  ->  fskhip_processor_process_device(p, X, n_in * Lu, ..., Y, n_out * Ld, ...)
+ *   ->  fskhip_resampler_down_device(down, Y, n_out * Ld, ..., d_lens = NULL, d_out, ...):
+ * the elements written, every word of processor and engine state and both handles' histories (fskhip_resampler_state_get) end as
+ * that chain leaves them, so any cut of a stream into quanta gives the same bytes and the same samples.  A side whose buffer is NULL
+ * is absent, as in process(): its handle is ignored (and may be NULL) and its history untouched.
+ *   RX  one interpolator launch writes into a float tile kept with the processor, the demodulators run on that.
+ *   TX  stream-major: one kernel generates the n_out * Ld samples, keeps them in an LDS delay line, evaluates every Ld-th output
+ *       of the decimator's FIR from it, encodes and stores: the high rate floats never reach memory.  A decimator too long for that
+ *       delay line (every default design up to factor 12 fits; the limit is a few hundred taps and depends on factor and format),
+ *       and interleaved frames, for which that measured faster, take two launches through a float tile kept with the processor,
+ *       with the same results.
+ * FSKHIP_PROC_GRAPH is ignored: the handles' history buffers change places from call to call, so these forms launch plainly
+ * whatever that flag says; FSKHIP_PROC_CLEAR_RX_ON_TX_COMPLETE means what it means in process().  The _host form stages the low
+ * rate samples as fskhip_processor_process_fmt_host stages its own and synchronises at the end.
+ * FSKHIP_E_INVALID before any device call, in this order: a null processor; an unknown format, then layout, the input side first
+ * (whether or not the side is NULL); for each side that has a buffer, the input side first: a null handle, a handle of the wrong
+ * direction, one whose fskhip_resampler_streams is not the processor's, one on another device; a pitch that is too small, in before
+ * out; a pointer that is not aligned to its element.  A refused call leaves the processor and both histories as they were.
+ */
+int fskhip_processor_process_rate_device(fskhip_processor *p, fskhip_resampler *up, fskhip_resampler *down, const void *d_in,
+                                         int in_format, int in_layout, size_t n_in, size_t in_pitch, void *d_out, int out_format,
+                                         int out_layout, size_t n_out, size_t out_pitch, uint32_t flags, void *hip_stream);
+int fskhip_processor_process_rate_host(fskhip_processor *p, fskhip_resampler *up, fskhip_resampler *down, const void *in,
+                                       int in_format, int in_layout, size_t n_in, size_t in_pitch, void *out, int out_format,
+                                       int out_layout, size_t n_out, size_t out_pitch, uint32_t flags);
+
 /* ---------------------------------------------------------------------------------------------------
  * IIR half of src/dsp/filters.ts: IIRFilter (8-106) batched over streams, + FilterFactory.createIIR* (325-344; the
  * designs themselves are fskhip_butterworth_* in fskhip.h).  Inside the demodulator the same filter lives as three

@@ -7,6 +7,7 @@
 const path = require('path');
 const addon = require(path.join(__dirname, 'fsk_addon.node'));
 const { FSKBatch, sampleFormat, sampleLayout } = require(path.join(__dirname, 'fsk-core.js'));
+const { Upsampler, Downsampler } = require(path.join(__dirname, 'filters.js'));
 const PROC_CLEAR_RX_ON_TX_COMPLETE = 1, PROC_GRAPH = 2;
 
 class FSKProcessorBatch {
@@ -93,6 +94,38 @@ class FSKProcessorBatch {
     const outPitch = count(output.pitch, 'output pitch') || (outLay ? this.nStreams : nOut);
     if (has) this.processDemodulationCallCount++;      // (as process() counts: behind the argument checks, in front of the call)
     return addon.processorProcessSamples(this.handle, has ? inputs : null, inFmt, inLay, nIn, inPitch, outFmt, outLay, nOut, outPitch, this.flags);
+  }
+  // processSamples() with both sides at the trunk's own rate (fskhip_processor_process_rate_host): input = {format, layout, nIn, pitch,
+  // upsampler}, output = {format, layout, nOut, pitch, downsampler} with the Upsampler / Downsampler of filters.js, which interpolate
+  // the inputs in front of the demodulator and decimate the pending modulation on the device; lengths and pitches count low rate
+  // elements, format defaults to 'mulaw' and layout to 'sample' (interleaved frames).  Both handles carry their histories from call
+  // to call; state and samples are those of Upsampler.process -> process() -> Downsampler.process, bit for bit.  A side without
+  // samples needs no handle.
+  processSamplesAt(inputs, input = {}, output = {}) {
+    if (input === null || typeof input !== 'object' || output === null || typeof output !== 'object') {
+      throw new TypeError('processSamplesAt: input and output must be objects {format, layout, nIn | nOut, pitch, upsampler | downsampler}');
+    }
+    const inFmt = sampleFormat(input.format === undefined ? 'mulaw' : input.format), inLay = sampleLayout(input.layout === undefined ? 'sample' : input.layout);
+    const outFmt = sampleFormat(output.format === undefined ? 'mulaw' : output.format), outLay = sampleLayout(output.layout === undefined ? 'sample' : output.layout);
+    const count = (v, what) => {
+      const n = v === undefined ? 0 : v;
+      if (!Number.isInteger(n) || n < 0 || n > 0xffffffff) throw new RangeError('processSamplesAt: ' + what + ' must be an integer in [0, 2^32)');
+      return n;
+    };
+    const has = inputs !== undefined && inputs !== null;
+    if (has && !ArrayBuffer.isView(inputs)) throw new TypeError('processSamplesAt: inputs must be a typed array or null');
+    const nIn = has ? count(input.nIn, 'nIn') : 0, nOut = count(output.nOut, 'nOut');
+    const inPitch = count(input.pitch, 'input pitch') || (inLay ? this.nStreams : nIn);
+    const outPitch = count(output.pitch, 'output pitch') || (outLay ? this.nStreams : nOut);
+    const handle = (r, kind, what) => {
+      if (!(r instanceof kind)) throw new TypeError('processSamplesAt: ' + what + ' must be an ' + kind.name + ' of filters.js');
+      if (r.nStreams !== this.nStreams) throw new RangeError('processSamplesAt: ' + what + ' has ' + r.nStreams + ' streams, the batch ' + this.nStreams);
+      return r.handle;
+    };
+    const up = has ? handle(input.upsampler, Upsampler, 'upsampler') : null;
+    const down = nOut ? handle(output.downsampler, Downsampler, 'downsampler') : null;
+    if (has) this.processDemodulationCallCount++;      // (as process() counts: behind the argument checks, in front of the call)
+    return addon.processorProcessSamplesAt(this.handle, up, down, has ? inputs : null, inFmt, inLay, nIn, inPitch, outFmt, outLay, nOut, outPitch, this.flags);
   }
   // 'modulate' (87-113): payloads = array of S Uint8Array; mask = optional array of S booleans
   modulate(payloads, mask) {

@@ -38,6 +38,8 @@
 //   resamplerCreate(direction, factor, taps: Float64Array, nStreams, device, precision) -> handle;  resamplerDestroy(handle);  resamplerHistory(handle)
 //   resamplerUp(handle, samples, format, layout, nIn, pitch, factor) -> Float32Array [S][nIn * factor]
 //   resamplerDown(handle, input: Float32Array [S][nIn], nIn, lens: Uint32Array|null, format, layout, factor) -> the format's typed array
+//   processorProcessSamplesAt(handle, up: resampler handle|null, down: resampler handle|null, input, inFormat, inLayout, nIn, inPitch, outFormat,
+//     outLayout, nOut, outPitch, flags) -> as processorProcessSamples, both sides at the handles' low rate (a side without samples needs none)
 //   resamplerReset(handle, stream);  resamplerState(handle) -> Float32Array [S][history];  resamplerSetState(handle, Float32Array)
 //   iirCreate(b, a: Float64Array, nStreams, device, precision) -> handle; iirProcess(handle, Float32Array | Float64Array, n, pitch, nStreams);
 //   iirCoefficients(handle), iirReset(handle, stream), iirDestroy(handle); butterworth(kind, f, bandwidth, sampleRate) -> [b0 b1 b2 a0 a1 a2]
@@ -983,6 +985,40 @@ napi_value ResamplerDown(napi_env env, napi_callback_info info) {
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   return out_v;
 }
+// process() with both sides at a low rate (fskhip_processor_process_rate_host): ProcessorProcessSamples with the two resampler handles in
+// front of the samples; lengths and pitches count low rate elements.  A handle is looked at only where its side has samples.
+napi_value ProcessorProcessSamplesAt(napi_env env, napi_callback_info info) {
+  ARGS(13);
+  const int32_t in_format = i32(env, argv[4]), in_layout = i32(env, argv[5]), out_format = i32(env, argv[8]), out_layout = i32(env, argv[9]);
+  if (!sample_format_ok(env, in_format, in_layout) || !sample_format_ok(env, out_format, out_layout)) return nullptr;
+  Proc *h = get_proc(env, argv[0]);
+  if (!h) return nullptr;
+  void *in; size_t ilen;
+  if (!typed(env, argv[3], sample_array_type(in_format), &in, &ilen, true)) return nullptr;
+  const uint32_t n_in = u32(env, argv[6]), in_pitch = u32(env, argv[7]), n_out = u32(env, argv[10]), out_pitch = u32(env, argv[11]), flags = u32(env, argv[12]);
+  fskhip_resampler *up = nullptr, *down = nullptr;
+  if (in) {
+    if (nullish(env, argv[1])) { napi_throw_type_error(env, nullptr, "input samples need an upsampler"); return nullptr; }
+    if (!(up = (fskhip_resampler *)filter_of(env, argv[1]))) return nullptr;
+    const int64_t need = samples_needed(in_layout, h->S, n_in, in_pitch);
+    if (need < 0 || (size_t)need > ilen) { napi_throw_range_error(env, nullptr, "input too short"); return nullptr; }
+  }
+  void *out = nullptr;
+  napi_value out_v = nullptr;
+  if (n_out) {
+    if (nullish(env, argv[2])) { napi_throw_type_error(env, nullptr, "output samples need a downsampler"); return nullptr; }
+    if (!(down = (fskhip_resampler *)filter_of(env, argv[2]))) return nullptr;
+    const int64_t need = samples_needed(out_layout, h->S, n_out, out_pitch);
+    if (need < 0) { napi_throw_range_error(env, nullptr, "output pitch too small"); return nullptr; }
+    out_v = make_typed(env, sample_array_type(out_format), (size_t)need, fskhip_sample_bytes(out_format), &out);
+    if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+    fill_silence(out_format, out, (size_t)need);
+  }
+  int rc = fskhip_processor_process_rate_host(h->p, up, down, in, in_format, in_layout, n_in, in_pitch, out, out_format, out_layout, n_out, out_pitch, flags);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  if (!out_v) napi_get_null(env, &out_v);
+  return out_v;
+}
 napi_value ResamplerReset(napi_env env, napi_callback_info info) {
   ARGS(2);
   fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
@@ -1160,6 +1196,7 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"resamplerHistory", nullptr, ResamplerHistory, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"resamplerUp", nullptr, ResamplerUp, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"resamplerDown", nullptr, ResamplerDown, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"processorProcessSamplesAt", nullptr, ProcessorProcessSamplesAt, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"resamplerReset", nullptr, ResamplerReset, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"resamplerState", nullptr, ResamplerState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"resamplerSetState", nullptr, ResamplerSetState, nullptr, nullptr, nullptr, napi_default, nullptr},

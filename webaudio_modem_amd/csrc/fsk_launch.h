@@ -88,6 +88,14 @@ hipError_t launch_processor_io(const ModParams &M, const double *coef, const Pro
 // elements): one launch, the kernel encodes behind its generator.  float32 stream-major is launch_processor_io.
 hipError_t launch_processor_io_fmt(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out, size_t demod_pitch, const uint32_t *demod_counts,
                                    bool do_rx, void *out, int format, int layout, size_t n_out, size_t out_pitch, bool clear_rx_on_complete, hipStream_t st);
+// the same quantum with `out` at a decimator's low rate (fskhip_processor_process_rate_*): n_out > 0 outputs per stream of the
+// n_out * factor samples the generator makes, filtered as launch_resample_down does (d_taps in `precision`, histories
+// [n_streams][n_taps - 1], d_hist_in read and d_hist_out written) and encoded, in one launch.  hipErrorInvalidValue where
+// processor_rate_plan (fsk_processor_rate_plan.h) does not fuse the filter or the layout: the caller runs launch_processor_io and
+// launch_resample_down.
+hipError_t launch_processor_io_rate(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out, size_t demod_pitch, const uint32_t *demod_counts,
+                                    bool do_rx, void *out, int format, int layout, size_t n_out, size_t out_pitch, bool clear_rx_on_complete, int precision,
+                                    uint32_t factor, uint32_t n_taps, const void *d_taps, const float *d_hist_in, float *d_hist_out, hipStream_t st);
 hipError_t launch_processor_tx_start(const ModParams &M, const ProcState &T, const uint8_t *payloads, const uint32_t *lens, size_t payload_pitch, const uint8_t *mask,
                                      hipStream_t st);
 hipError_t launch_processor_rx_drain(const ProcState &T, uint32_t n_streams, uint8_t *out, size_t out_pitch, uint32_t *counts, hipStream_t st);

@@ -15,6 +15,8 @@
 #include "fsk_wait.h"
 #include "fsk_launch.h"
 #include "fsk_samples_dev.h"
+#include "fsk_mac_dev.h"
+#include "fsk_processor_rate_plan.h"
 
 namespace fsk {
 
@@ -552,6 +554,45 @@ __global__ __launch_bounds__(64) void processor_io_kernel(ModParams M, const dou
   if (rx_dirty && valid) { T.rx_w[stream] = w; T.rx_r[stream] = r; T.rx_len[stream] = len; }
 }
 
+// The packed code rows of one tile of a one-wave workgroup -- row lr: the kTile codes of stream blockIdx.x * 64 + lr from column t0
+// on, rows kTile * sizeof(Bits) / 4 + 1 words apart -- stored to the stream-major `out`: as 16-byte vectors, 16 / 32 rows of
+// 64 / 32 contiguous bytes per instruction (16-bit / G.711), or -- where the base or the pitch is off the 16-byte grid (vec_ok = 0)
+// -- as single elements, two rows of 32 consecutive ones per instruction.  Nothing is written from column n_out or row n_streams on.
+template <typename Bits>
+__device__ __forceinline__ void store_code_rows(const uint32_t *codes, Bits *out, size_t out_pitch, size_t t0, size_t n_out, uint32_t n_streams, int vec_ok,
+                                                uint32_t lane) {
+  constexpr uint32_t kEsz = (uint32_t)sizeof(Bits);
+  constexpr uint32_t kWords = (uint32_t)kTile * kEsz / 4u, kRowPitch = kWords + 1u;
+  constexpr uint32_t kVecEls = 16u / kEsz;                      // elements of a 16-byte vector
+  if (vec_ok) {
+    constexpr uint32_t kLanesPerRow = kWords / 4u, kRowsPerStore = 64u / kLanesPerRow;
+    const uint32_t sub_row = lane / kLanesPerRow, q = lane % kLanesPerRow;
+#pragma unroll
+    for (uint32_t i = 0; i < kLanesPerRow; i++) {
+      const uint32_t lr = kRowsPerStore * i + sub_row;
+      const uint32_t rr = blockIdx.x * 64u + lr;
+      const size_t c0 = t0 + (size_t)kVecEls * q;
+      if (rr >= n_streams || c0 >= n_out) continue;
+      const uint32_t *src = &codes[lr * kRowPitch + 4u * q];
+      Bits *dst = out + (size_t)rr * out_pitch + c0;
+      if (c0 + kVecEls <= n_out) {
+        *reinterpret_cast<uint4 *>(dst) = make_uint4(src[0], src[1], src[2], src[3]);
+      } else {   // the row's last, partial vector
+        for (uint32_t e = 0; c0 + e < n_out; e++) dst[e] = (Bits)(src[e * kEsz / 4u] >> (8u * ((e * kEsz) & 3u)));
+      }
+    }
+  } else {
+    const uint32_t half = lane >> 5, e = lane & 31u;
+    const size_t col = t0 + e;
+#pragma unroll 4
+    for (uint32_t i = 0; i < 32u; i++) {
+      const uint32_t lr = 2u * i + half;
+      const uint32_t rr = blockIdx.x * 64u + lr;
+      if (rr < n_streams && col < n_out) out[(size_t)rr * out_pitch + col] = (Bits)(codes[lr * kRowPitch + e * kEsz / 4u] >> (8u * ((e * kEsz) & 3u)));
+    }
+  }
+}
+
 // The same quantum with the output in a capture format and layout (fskhip_processor_process_fmt_*; FMT / LAYOUT: include/fskhip.h's
 // FSKHIP_SAMPLES_* / FSKHIP_LAYOUT_*): processor_io_kernel's bookkeeping and generator, statement for statement, and behind the
 // generator SampleFmt<FMT>::encode -- element (s, t) of `out_` is the code of the float that kernel writes there, its zero fill the
@@ -633,35 +674,147 @@ __global__ __launch_bounds__(64) void processor_io_fmt_kernel(ModParams M, const
       }
       if constexpr (LAYOUT == FSKHIP_LAYOUT_STREAM_MAJOR) {
         __syncthreads();
-        constexpr uint32_t kVecEls = 16u / kEsz;                      // elements of a 16-byte vector
-        if (vec_ok) {
-          constexpr uint32_t kLanesPerRow = kWords / 4u, kRowsPerStore = 64u / kLanesPerRow;
-          const uint32_t sub_row = lane / kLanesPerRow, q = lane % kLanesPerRow;
+        store_code_rows(codes, out, out_pitch, t0, n_out, M.n_streams, vec_ok, lane);
+      }
+    }
+    if (active) {
+      if (G.pos >= flen) {  // isComplete: ChunkedModulator.reset() + pendingModulation = null
+        T.tx_pos[stream] = 0u; T.tx_len[stream] = 0u; T.tx_pending[stream] = 0u;
+        T.tx_completed[stream] += 1u;
+        if (clear_rx_on_complete) { w = 0u; r = 0u; len = 0u; rx_dirty = true; }
+      } else {
+        T.tx_phase[stream] = G.phase; T.tx_pos[stream] = G.pos; T.tx_in_bit[stream] = G.in_bit;
+        T.tx_bit_idx[stream] = G.bit_idx; T.tx_cur_bit[stream] = G.cur_bit;
+      }
+    }
+  }
+  if (rx_dirty && valid) { T.rx_w[stream] = w; T.rx_r[stream] = r; T.rx_len[stream] = len; }
+}
+
+// The same quantum with the output at a decimator's low rate (fskhip_processor_process_rate_*): processor_io_kernel's bookkeeping and
+// generator, statement for statement, over n_out * Ld samples that never reach HBM, and behind the generator resample_down_kernel's
+// sum (fsk_resample.hip: y[k] = f32(sum_i c[i] u[kL - i]), i ascending, `mac` in the handle's precision) and SampleFmt<FMT>::encode.
+// Lane = stream; the workgroup's one wave owns its 64 streams for the whole quantum.  The samples go into a delay line in LDS,
+// [slot][lane] with rows kRateLanePitch words apart (fsk_processor_rate_plan.h): a tap is 64 consecutive words, a lane only ever
+// reads and writes its own column, and the taps are wave-uniform (scalar loads).  The handle's history -- n_taps - 1 floats per
+// stream, oldest first -- is read coalesced, 64 consecutive floats of one stream per instruction, into slots [0, n_taps - 1) at
+// entry; the samples follow round the ring, kRateChunk per step of the generator, and every Ld-th one is an output, taken as soon
+// as it is written.  At exit the last n_taps - 1 samples are written to hist_out the same way (the two history buffers ping-pong
+// as the handle's own calls have them).  The codes leave stream-major as processor_io_fmt_kernel's do, through the packed code rows,
+// kTile outputs per flush.  (Interleaved frames take the two launches this kernel replaces: written from the registers, 64
+// consecutive elements of a frame per instruction, it measured 1.10 to 1.26 times that pair -- profiles/processor_rate_bench.jsonl.)
+// The launcher has seen to n_out > 0, a delay line of `slots` >= n_taps - 1 + max(Ld, kRateChunk) samples and the LDS for it.
+template <bool EXACT, typename Real, int FMT>
+__global__ __launch_bounds__(64) void processor_io_rate_kernel(ModParams M, const double *__restrict__ coef, ProcState T,
+                                                               const uint8_t *__restrict__ demod_out, size_t demod_pitch,
+                                                               const uint32_t *__restrict__ demod_counts, int do_rx,
+                                                               void *__restrict__ out_, size_t n_out, size_t out_pitch, int vec_ok,
+                                                               uint32_t clear_rx_on_complete, const float *__restrict__ hist_in,
+                                                               float *__restrict__ hist_out, const void *__restrict__ taps_, uint32_t Ld,
+                                                               uint32_t n_taps, uint32_t slots) {
+  using F = SampleFmt<FMT>;
+  using Bits = typename F::Bits;
+  static_assert(kRateCodeTile == (uint32_t)kTile && kRateChunk == 4u, "the code rows are store_code_rows', the generator's step frame_next4's");
+  constexpr uint32_t kPitch = kRateLanePitch;
+  constexpr uint32_t kRowPitch = (uint32_t)kTile * (uint32_t)sizeof(Bits) / 4u + 1u;
+  extern __shared__ __align__(16) unsigned char rate_lds[];
+  float *const dl = reinterpret_cast<float *>(rate_lds);               // [slots][kPitch]
+  uint32_t *const codes = reinterpret_cast<uint32_t *>(dl + (size_t)slots * kPitch);   // [64][kRowPitch]
+  const uint32_t lane = threadIdx.x;
+  const uint32_t stream = blockIdx.x * 64u + lane;
+  const bool valid = stream < M.n_streams;
+  const uint32_t row = valid ? stream : M.n_streams - 1;
+  const size_t ns = M.n_streams;
+
+  uint32_t w = T.rx_w[row], r = T.rx_r[row], len = T.rx_len[row];
+  bool rx_dirty = false;
+  if (do_rx && valid) {
+    uint32_t cnt = demod_counts[stream];
+    if ((size_t)cnt > demod_pitch) cnt = (uint32_t)demod_pitch;
+    const uint8_t *src = demod_out + (size_t)stream * demod_pitch;
+    uint8_t *ring = T.rx_buf + (size_t)stream * T.rx_cap;
+    for (uint32_t i = 0; i < cnt; i++) {  // put(): overwrite the oldest when full
+      ring[w] = src[i];
+      w = w + 1 == T.rx_cap ? 0u : w + 1;
+      if (len < T.rx_cap) len++;
+      else r = r + 1 == T.rx_cap ? 0u : r + 1;
+    }
+    rx_dirty = cnt != 0;
+  }
+
+  {
+    const uint32_t flen = T.tx_len[row];
+    const bool active = valid && T.tx_pending[row] != 0u && flen > 0u && T.tx_pos[row] < flen;
+    const uint8_t *prow = T.tx_payload + (size_t)row * T.tx_payload_pitch;
+    auto pb = [&](uint32_t i) -> uint8_t { return prow[i]; };
+    FrameGen G;
+    G.start(M, coef[(size_t)CF_mark_w * ns + row], coef[(size_t)CF_space_w * ns + row], T.tx_n_payload[row]);
+    if (active) {
+      G.phase = T.tx_phase[row]; G.pos = T.tx_pos[row]; G.in_bit = T.tx_in_bit[row];
+      G.bit_idx = T.tx_bit_idx[row]; G.cur_bit = T.tx_cur_bit[row];
+    } else {
+      G.pos = G.frame_len;  // nothing to emit: zeros
+    }
+    Bits *const out = (Bits *)out_;
+    const Real *const taps = (const Real *)taps_;
+    const uint32_t H = n_taps - 1u;
+    // the history: sample -H + h of the quantum at slot h; streams past the batch hold zeros
+    for (uint32_t c = 0; c < 64u; c++) {
+      const uint32_t s = blockIdx.x * 64u + c;
+      for (uint32_t h = lane; h < H; h += 64u) dl[h * kPitch + c] = s < M.n_streams ? hist_in[(size_t)s * H + h] : 0.0f;
+    }
+    __syncthreads();
+    const size_t n_high = n_out * Ld;
+    uint32_t wslot = H;        // the slot of sample t0: (H + t0) mod slots
+    uint32_t ph = 0;           // t mod Ld
+    size_t k = 0;              // the next output
+    for (size_t t0 = 0; t0 < n_high; t0 += kRateChunk) {
+      // samples beyond n_high inside the last step must not advance the generator
+      const float4 v = frame_next4<EXACT>(G, M, pb, t0 + 0 < n_high, t0 + 1 < n_high, t0 + 2 < n_high, t0 + 3 < n_high);
+      const float o[4] = {v.x, v.y, v.z, v.w};
+      const uint32_t cnt = n_high - t0 < kRateChunk ? (uint32_t)(n_high - t0) : kRateChunk;
+      uint32_t sl = wslot;
 #pragma unroll
-          for (uint32_t i = 0; i < kLanesPerRow; i++) {
-            const uint32_t lr = kRowsPerStore * i + sub_row;
-            const uint32_t rr = blockIdx.x * 64u + lr;
-            const size_t c0 = t0 + (size_t)kVecEls * q;
-            if (rr >= M.n_streams || c0 >= n_out) continue;
-            const uint32_t *src = &codes[lr * kRowPitch + 4u * q];
-            typename F::Bits *dst = out + (size_t)rr * out_pitch + c0;
-            if (c0 + kVecEls <= n_out) {
-              *reinterpret_cast<uint4 *>(dst) = make_uint4(src[0], src[1], src[2], src[3]);
-            } else {   // the row's last, partial vector
-              for (uint32_t e = 0; c0 + e < n_out; e++) dst[e] = (typename F::Bits)(src[e * kEsz / 4u] >> (8u * ((e * kEsz) & 3u)));
-            }
-          }
-        } else {
-          const uint32_t half = lane >> 5, e = lane & 31u;
-          const size_t col = t0 + e;
-#pragma unroll 4
-          for (uint32_t i = 0; i < 32u; i++) {
-            const uint32_t lr = 2u * i + half;
-            const uint32_t rr = blockIdx.x * 64u + lr;
-            if (rr < M.n_streams && col < n_out)
-              out[(size_t)rr * out_pitch + col] = (typename F::Bits)(codes[lr * kRowPitch + e * kEsz / 4u] >> (8u * ((e * kEsz) & 3u)));
-          }
+      for (uint32_t j = 0; j < kRateChunk; j++) {
+        if (j < cnt) {
+          dl[sl * kPitch + lane] = o[j];
+          sl = sl + 1u == slots ? 0u : sl + 1u;
         }
+      }
+      for (uint32_t j = 0; j < cnt; j++) {
+        if (ph == 0u) {      // sample t0 + j = k Ld: output k, tap i at the slot i behind it
+          uint32_t si = wslot + j;
+          si = si >= slots ? si - slots : si;
+          Real acc = 0;
+#pragma unroll 8
+          for (uint32_t i = 0; i < n_taps; i++) {
+            acc = mac(acc, taps[i], dl[si * kPitch + lane]);
+            si = si == 0u ? slots - 1u : si - 1u;
+          }
+          const uint32_t code = F::encode((float)acc);
+          const uint32_t kk = (uint32_t)(k & (size_t)(kTile - 1));
+          reinterpret_cast<Bits *>(codes + lane * kRowPitch)[kk] = (Bits)code;
+          if (kk == (uint32_t)kTile - 1u || k + 1 == n_out) {
+            __syncthreads();
+            store_code_rows(codes, out, out_pitch, k - kk, n_out, M.n_streams, vec_ok, lane);
+            __syncthreads();   // (the rows' readers, before the next tile's codes)
+          }
+          k++;
+        }
+        ph = ph + 1u == Ld ? 0u : ph + 1u;
+      }
+      wslot = sl;
+    }
+    // the history after the call: samples n_high - H + h, at slot (n_high + h) mod slots
+    __syncthreads();
+    const uint32_t hbase = (uint32_t)(n_high % slots);
+    for (uint32_t c = 0; c < 64u; c++) {
+      const uint32_t s = blockIdx.x * 64u + c;
+      if (s >= M.n_streams) break;
+      for (uint32_t h = lane; h < H; h += 64u) {
+        uint32_t si = hbase + h;
+        si = si >= slots ? si - slots : si;
+        hist_out[(size_t)s * H + h] = dl[si * kPitch + c];
       }
     }
     if (active) {
@@ -760,6 +913,29 @@ hipError_t launch_processor_io_fmt(const ModParams &M, const double *coef, const
   const int vec_ok = out && (out_pitch * esz % 16 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15u) == 0);
   hipLaunchKernelGGL(kIoFmtKernels[M.exact_sin ? 1 : 0][format][layout].fn, dim3(blocks), dim3(64), 0, st, M, coef, T, demod_out, demod_pitch,
                      demod_counts, do_rx ? 1 : 0, out, n_out, out_pitch, vec_ok, clear_rx_on_complete ? 1u : 0u);
+  return hipGetLastError();
+}
+// every low rate instantiation, once: [exact sine][the decimator's precision][format] in the order of the headers' enums
+#define FSK_IO_RATE_KERNELS(EXACT, R) \
+  {FSK_K(processor_io_rate_kernel, EXACT, R, FSKHIP_SAMPLES_F32), FSK_K(processor_io_rate_kernel, EXACT, R, FSKHIP_SAMPLES_S16), \
+   FSK_K(processor_io_rate_kernel, EXACT, R, FSKHIP_SAMPLES_MULAW), FSK_K(processor_io_rate_kernel, EXACT, R, FSKHIP_SAMPLES_ALAW)}
+using IoRateFn = void (*)(ModParams, const double *, ProcState, const uint8_t *, size_t, const uint32_t *, int, void *, size_t, size_t, int, uint32_t, const float *,
+                          float *, const void *, uint32_t, uint32_t, uint32_t);
+static const KernelEntry<IoRateFn> kIoRateKernels[2][2][4] = {{FSK_IO_RATE_KERNELS(false, float), FSK_IO_RATE_KERNELS(false, double)},
+                                                              {FSK_IO_RATE_KERNELS(true, float), FSK_IO_RATE_KERNELS(true, double)}};
+
+hipError_t launch_processor_io_rate(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out, size_t demod_pitch,
+                                    const uint32_t *demod_counts, bool do_rx, void *out, int format, int layout, size_t n_out, size_t out_pitch,
+                                    bool clear_rx_on_complete, int precision, uint32_t factor, uint32_t n_taps, const void *d_taps, const float *d_hist_in,
+                                    float *d_hist_out, hipStream_t st) {
+  const size_t esz = sample_bytes(format);
+  const RatePlan P = processor_rate_plan(factor, n_taps, (uint32_t)esz, layout == FSKHIP_LAYOUT_STREAM_MAJOR);
+  if (!out || n_out == 0 || !P.fused) return hipErrorInvalidValue;
+  const uint32_t blocks = (M.n_streams + 63u) / 64u;
+  const int vec_ok = (out_pitch * esz % 16 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15u) == 0);
+  hipLaunchKernelGGL(kIoRateKernels[M.exact_sin ? 1 : 0][precision == FSKHIP_PRECISION_F64 ? 1 : 0][format].fn, dim3(blocks), dim3(64), P.lds_bytes, st, M,
+                     coef, T, demod_out, demod_pitch, demod_counts, do_rx ? 1 : 0, out, n_out, out_pitch, vec_ok, clear_rx_on_complete ? 1u : 0u, d_hist_in,
+                     d_hist_out, d_taps, factor, n_taps, P.slots);
   return hipGetLastError();
 }
 hipError_t launch_processor_tx_start(const ModParams &M, const ProcState &T, const uint8_t *payloads, const uint32_t *lens,

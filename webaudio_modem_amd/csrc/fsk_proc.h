@@ -25,6 +25,9 @@ struct fskhip_processor {
   // fskhip_processor_process_fmt_*: the float tile [S][fin_pitch] the ingest kernel widens a quantum into (rows on 16-byte
   // boundaries; grown outside any capture), and the _host form's samples as they cross PCIe, either way
   float *d_fin = nullptr; size_t d_fin_cap = 0;
+  // fskhip_processor_process_rate_*: the float tile [S][pitch] of a quantum whose decimator the fused kernel does not take (grown
+  // outside any capture)
+  float *d_ftx = nullptr; size_t d_ftx_cap = 0;
   uint8_t *d_nin = nullptr; size_t d_nin_cap = 0;
   uint8_t *d_nout = nullptr; size_t d_nout_cap = 0;
   // captured quantum
@@ -98,6 +101,15 @@ inline int grow_byte_slab(fskhip_processor *p, size_t n_in) {
   if (rc != FSKHIP_OK) return rc;
   p->bytes_pitch = need;
   return FSKHIP_OK;
+}
+
+// a device buffer that only grows, outside any capture: the captured quantum holds the old pointer and is dropped
+template <typename T>
+int grow_for_quantum(fskhip_processor *p, T *&buf, size_t &cap, size_t need) {
+  if (need <= cap) return FSKHIP_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  drop_graph(p);
+  return ensure(buf, cap, need);
 }
 
 // fsk_processor.hip: the payload store holds rows of at least max_len bytes (a multiple of 64, zero filled), the pending rows

@@ -60,7 +60,7 @@ int fskhip_processor_destroy(fskhip_processor *p) {
   drop_graph(p);
   void *bufs[] = {p->T.rx_buf, p->T.rx_w, p->T.rx_r, p->T.rx_len, p->T.tx_payload, p->T.tx_phase, p->T.tx_pos, p->T.tx_len,
                   p->T.tx_in_bit, p->T.tx_bit_idx, p->T.tx_cur_bit, p->T.tx_n_payload, p->T.tx_pending, p->T.tx_completed,
-                  p->d_bytes, p->d_counts, p->d_eod, p->d_in, p->d_out, p->d_stage, p->d_u32, p->d_mask, p->d_lists, p->d_fin, p->d_nin, p->d_nout};
+                  p->d_bytes, p->d_counts, p->d_eod, p->d_in, p->d_out, p->d_stage, p->d_u32, p->d_mask, p->d_lists, p->d_fin, p->d_ftx, p->d_nin, p->d_nout};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   if (p->stream) (void)hipStreamDestroy(p->stream);

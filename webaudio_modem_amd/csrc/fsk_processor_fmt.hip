@@ -54,15 +54,6 @@ int launch_quantum_fmt(fskhip_processor *p, const Side &in, size_t fin_pitch, co
   return FSKHIP_OK;
 }
 
-// a device buffer that only grows, outside any capture: the captured quantum holds the old pointer and is dropped
-template <typename T>
-int grow_for_quantum(fskhip_processor *p, T *&buf, size_t &cap, size_t need) {
-  if (need <= cap) return FSKHIP_OK;
-  HIP_TRY(hipDeviceSynchronize());
-  drop_graph(p);
-  return ensure(buf, cap, need);
-}
-
 }  // namespace
 
 extern "C" {

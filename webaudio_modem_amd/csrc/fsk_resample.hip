@@ -24,6 +24,7 @@
 #include "fsk_launch.h"
 #include "fsk_mac_dev.h"
 #include "fsk_resample_plan.h"
+#include "fsk_resampler.h"
 #include "fsk_samples_dev.h"
 
 namespace fsk {
@@ -279,16 +280,6 @@ hipError_t launch_resample_down(int precision, const float *d_src, size_t n_out,
 }  // namespace fsk
 
 using namespace fsk;
-
-struct fskhip_resampler : FilterHost {
-  int direction = 0;
-  uint32_t L = 1, n_taps = 0, H = 0;      // H: floats of history per stream (resample_history)
-  double *d_taps = nullptr;               // fp64 path: as given (down), phase by phase [L][K] (up)
-  float *d_taps32 = nullptr;              // the same, rounded once on the host (fp32 path)
-  float *hist[2] = {nullptr, nullptr};    // ping-pong: [cur] is read by the next call
-  int cur = 0;
-  uint32_t *d_lens = nullptr;             // the _host form's per-stream lengths
-};
 
 namespace {
 

@@ -213,6 +213,60 @@ class FSKProcessorBatch:
                                                                d_out, *_sample_codes(out_fmt, out_layout, True), n_out, out_pitch,
                                                                self.flags if flags is None else flags, stream))
 
+    def _rate_handle(self, handle, kind, what):
+        """a side's resampler (filters.Upsampler / Downsampler) as fskhip_processor_process_rate_* wants it: of this batch's
+        stream count and on its engine's device"""
+        from . import filters
+        if not isinstance(handle, kind):
+            raise ValueError("%s must be a filters.%s, got %s" % (what, kind.__name__, type(handle).__name__))
+        if handle.n_streams != self.n_streams:
+            raise ValueError("%s has %d streams, the batch %d" % (what, handle.n_streams, self.n_streams))
+        device = getattr(self.engine, "device", None)
+        if device is not None and handle.device != device:
+            raise ValueError("%s is on device %r, the batch on %r" % (what, handle.device, device))
+        return handle._h
+
+    def process_samples_at(self, inputs=None, in_fmt="mulaw", in_layout="sample", upsampler=None, n_out=0, out_fmt="mulaw", out_layout="sample",
+                           downsampler=None):
+        """process_samples() with both sides at the trunk's own rate: fskhip_processor_process_rate_host.  inputs (or None) are
+        low rate samples, interpolated on the device by `upsampler` (filters.Upsampler) in front of the demodulator; the n_out
+        returned samples are the pending modulation decimated by `downsampler` (filters.Downsampler), which one kernel generates,
+        filters and encodes.  Both handles carry their histories from call to call, so any cut of a stream into quanta gives the
+        same bytes and samples; the state ends as Upsampler.process -> process() -> Downsampler.process leaves it, bit for bit.
+        A side without samples needs no handle."""
+        from . import filters
+        in_code, in_lay = _sample_codes(in_fmt, in_layout)
+        out_code, out_lay = _sample_codes(out_fmt, out_layout)      # (every argument check comes before the call is counted)
+        x, n_in, in_pitch, up_h, down_h = None, 0, 0, None, None
+        if inputs is not None:
+            x, in_code, in_lay, S, n_in, in_pitch = sample_args(inputs, in_fmt, in_layout)
+            if in_pitch is None:      # (an array without elements has no strides to speak of: its rows are packed)
+                in_pitch = max(x.shape[1], 1)
+            if S != self.n_streams:
+                raise ValueError("inputs must be [n_streams, n] (layout 'stream') or [n, n_streams] (layout 'sample')")
+            up_h = self._rate_handle(upsampler, filters.Upsampler, "upsampler")
+        out, out_pitch = None, 0
+        if n_out:
+            down_h = self._rate_handle(downsampler, filters.Downsampler, "downsampler")
+            out, out_code, out_lay, out_pitch = samples_out(out_fmt, out_layout, self.n_streams, int(n_out))
+        if inputs is not None:
+            self.processDemodulationCallCount += 1
+        _lib.check(self._L.fskhip_processor_process_rate_host(
+            self._h, up_h, down_h, x.ctypes.data if x is not None else None, in_code, in_lay, n_in, in_pitch,
+            out.ctypes.data if out is not None else None, out_code, out_lay, int(n_out), out_pitch, self.flags))
+        return out
+
+    def process_samples_at_device(self, d_in, in_fmt, in_layout, n_in, in_pitch, upsampler, d_out, out_fmt, out_layout, n_out, out_pitch, downsampler,
+                                  stream=None, flags=None):
+        """fskhip_processor_process_rate_device: device pointers (ints or None), lengths and pitches in low rate elements,
+        asynchronous on `stream`.  The handle of a side whose pointer is None may be None."""
+        from . import filters
+        up_h = None if d_in is None and upsampler is None else self._rate_handle(upsampler, filters.Upsampler, "upsampler")
+        down_h = None if d_out is None and downsampler is None else self._rate_handle(downsampler, filters.Downsampler, "downsampler")
+        _lib.check(self._L.fskhip_processor_process_rate_device(self._h, up_h, down_h, d_in, *_sample_codes(in_fmt, in_layout, True), n_in, in_pitch,
+                                                                d_out, *_sample_codes(out_fmt, out_layout, True), n_out, out_pitch,
+                                                                self.flags if flags is None else flags, stream))
+
     # ---- 'modulate' fsk-processor.ts:87-113 ------------------------------------------------------------
     def modulate(self, payloads, mask=None):
         """payloads: list of S bytes-like; mask: optional list of S bools (streams to start)."""
