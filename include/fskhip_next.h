@@ -727,11 +727,68 @@ int fskhip_resampler_up_host(fskhip_resampler *r, const void *src, int format, i
                              size_t dst_pitch);
 int fskhip_resampler_down_host(fskhip_resampler *r, const float *src, size_t n_in, size_t src_pitch, const uint32_t *lens, void *dst,
                                int format, int layout, size_t dst_pitch);
-/* the history rows, [n_streams][fskhip_resampler_history()] floats on the host, oldest first: what carries a handle across a
- * remap (get, permute the rows, set on a handle of the same direction, factor and taps).  Synchronous; nothing is copied when
- * the history is empty.  Snapshot images hold no resampler. */
+/* the history rows, [n_streams][fskhip_resampler_history()] floats on the host, oldest first: the by-hand carry of a handle across
+ * a remap (get, permute the rows, set on a handle of the same direction, factor and taps).  Synchronous; nothing is copied when
+ * the history is empty.  fskhip_resampler_remap / _snapshot / _restore below do the same on the device, and a resampler has a
+ * snapshot image of its own. */
 int fskhip_resampler_state_get(fskhip_resampler *r, float *state);
 int fskhip_resampler_state_set(fskhip_resampler *r, const float *state);
+
+/*
+ * A resampler through remap, snapshot and restore (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): the handle follows its streams
+ * with the SAME map the engine (fskhip_remap_streams ...), the processor (fskhip_processor_remap ...) and the resident XModem
+ * handles (fskhip_xmodem_*_remap ...) were carried with, so the cut-invariance of the rate calls holds across a remap.  Unlike
+ * those calls, remap and restore CREATE their handle: a resampler's design (direction, factor, taps, precision) is the source's
+ * or the image's own, so there is no destination that could disagree.  The rows move on the device.  Synchronous host calls.
+ *
+ * fskhip_resampler_remap   *out: a new handle on src's device with src's direction, factor, taps and precision, for n_map streams.
+ *                          Stream i continues stream map[i] of src: its history row verbatim, every bit (NaN payloads and the sign
+ *                          of zero included).  Where map[i] = -1 stream i starts with a zero history, as after reset.  A source
+ *                          named several times gives independent clones; sources not named are dropped.  src is read only and
+ *                          stays usable.  Destroy *out with fskhip_resampler_destroy.
+ * A resampler snapshot is a host-side image: plain little-endian bytes, no pointers, every byte defined.  It is canonical: two
+ * handles in the same observable state give the same bytes, whichever way they came to it.  A history is plain floats and the
+ * taps are create's doubles, so nothing in an image depends on the build that wrote it; the format number says how to read it.
+ *   header, 48 bytes:  u32 magic "FSKR" (0x524B5346) | u32 format (1) | u32 header_bytes (48) | u32 record_bytes (4 x history) |
+ *                      u32 n_records | u32 direction | u32 factor | u32 n_taps | u32 precision | u32 history | u64 checksum
+ *     history: fskhip_resampler_history() of the design.  checksum: the processor snapshot's function over the image's u64 words,
+ *     with the checksum field taken as 0 (the other image formats keep it in the header too).
+ *   the taps, n_taps doubles as given to create
+ *   the rows, n_records x history floats packed tightly, one per selected stream, in selection order, oldest sample first
+ *   zero padding to a multiple of 16 bytes
+ * fskhip_resampler_snapshot_bytes  *bytes = the size of an image of n_sel records of this handle.
+ * fskhip_resampler_snapshot        write streams[0 .. n_sel) (NULL: all streams, in order, whatever n_sel; a stream may be named more
+ *                          than once) into image.  Synchronises with the device's outstanding work; the handle is read only and
+ *                          stays usable.  *written (may be NULL) receives the size; cap too small (or image NULL):
+ *                          FSKHIP_E_OVERFLOW with *written = the size needed and nothing written, so cap 0 is a size query.
+ * fskhip_resampler_restore         remap with the image standing in for src, on any device: map[i] names a RECORD, or is -1; a NULL
+ *                          map takes every record, in order (n_map is then ignored).  The design is the image's.
+ * fskhip_resampler_snapshot_info_get   what an image holds -- on the host, no device needed -- after validating ALL of it.
+ *
+ * Refusals, FSKHIP_E_INVALID before any device call, in this order; a refused call creates nothing, leaves *out alone and the
+ * source as it was.
+ *   remap           src or out NULL; map NULL with n_map > 0; n_map 0; the first map[i] below -1 or not below src's stream count.
+ *   snapshot_bytes  r or bytes NULL.
+ *   snapshot        r NULL; the first streams[i] below 0 or not below the handle's stream count; then the room (FSKHIP_E_OVERFLOW).
+ *   an image        (info_get, restore) NULL; fewer bytes than a header; magic; format; header_bytes; a direction or precision that
+ *                   is neither; factor outside 1..32 or n_taps outside 1..4096 (create's limits); a history that does not follow
+ *                   from direction, factor and n_taps; record_bytes; the size against the layout above; the checksum; a padding
+ *                   byte that is not zero.  info_get then: info NULL.
+ *   restore         out NULL; the image; map non-NULL with n_map 0, or a NULL map over an image without records; the first map[i]
+ *                   below -1 or not below the image's record count.  Then what create refuses for the device.
+ */
+typedef struct fskhip_resampler_snapshot_info {
+  uint32_t n_streams;   /* records in the image */
+  int direction;        /* FSKHIP_RESAMPLE_* */
+  uint32_t factor, n_taps;
+  int precision;        /* FSKHIP_PRECISION_* */
+  uint32_t history;     /* floats per record */
+} fskhip_resampler_snapshot_info;
+int fskhip_resampler_remap(const fskhip_resampler *src, const int64_t *map, uint32_t n_map, fskhip_resampler **out);
+int fskhip_resampler_snapshot_bytes(const fskhip_resampler *r, uint32_t n_sel, size_t *bytes);
+int fskhip_resampler_snapshot(const fskhip_resampler *r, const int64_t *streams, uint32_t n_sel, void *image, size_t cap, size_t *written);
+int fskhip_resampler_restore(int device, const void *image, size_t bytes, const int64_t *map, uint32_t n_map, fskhip_resampler **out);
+int fskhip_resampler_snapshot_info_get(const void *image, size_t bytes, fskhip_resampler_snapshot_info *info);
 
 /*
  * process() with both sides at the trunk's own rate (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): one FSKProcessor quantum whose

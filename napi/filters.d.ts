@@ -32,15 +32,25 @@ declare class Resampler {
   /** the history rows, [nStreams][history], oldest first */
   state(): Float32Array;
   setState(state: Float32Array): void;
+  /** a new object of this design: stream i continues stream map[i] of this one, bit for bit (-1: a zero history) */
+  remap(map: ArrayLike<number>): this;
+  /** the image of `streams` (null: all, in order): the design and the history rows */
+  snapshot(streams?: ArrayLike<number> | null): Buffer;
   close(): void;
 }
+export interface ResamplerSnapshotInfo { nStreams: number; direction: 0 | 1; factor: number; nTaps: number; precision: 0 | 1; history: number; taps: Float64Array }
+/** what a resampler snapshot holds, validated on the host */
+export declare function resamplerSnapshotInfo(buf: Uint8Array): ResamplerSnapshotInfo;
 export declare class Upsampler extends Resampler {
   constructor(factor: number, nStreams: number, options?: ResamplerOptions);
+  /** a new object from a snapshot() alone: stream i continues record map[i] (-1: a zero history; null: every record) */
+  static fromSnapshot(buf: Uint8Array, map?: ArrayLike<number> | null, options?: { device?: number; lowRate?: number }): Upsampler;
   /** samples: [nStreams][pitch] or frames [nPerStream][pitch]; returns [nStreams][nPerStream * factor] */
   process(samples: Float32Array | Int16Array | Uint8Array, format: SampleFormat, layout?: SampleLayout, nPerStream?: number, pitch?: number): Float32Array;
 }
 export declare class Downsampler extends Resampler {
   constructor(factor: number, nStreams: number, options?: ResamplerOptions);
+  static fromSnapshot(buf: Uint8Array, map?: ArrayLike<number> | null, options?: { device?: number; lowRate?: number }): Downsampler;
   /** input: [nStreams][n], n a multiple of factor; returns [nStreams][n / factor] or frames [n / factor][nStreams] */
   process(input: Float32Array, format: SampleFormat, layout?: SampleLayout, lens?: Uint32Array | null): Float32Array | Int16Array | Uint8Array;
 }

@@ -82,8 +82,34 @@ class Resampler {
   state() { return addon.resamplerState(this.handle); }             // Float32Array [nStreams][history], oldest first
   setState(state) { addon.resamplerSetState(this.handle, state); }
   close() { if (this.handle) { addon.resamplerDestroy(this.handle); this.handle = null; } }
+  // an object of this class over a handle the library created (remap, restore)
+  static adopt(handle, design) {
+    const o = Object.create(this.prototype);
+    o.factor = design.factor; o.lowRate = design.lowRate; o.taps = [...design.taps];
+    o.handle = handle;
+    o.nStreams = addon.resamplerStreams(handle);
+    o.history = addon.resamplerHistory(handle);
+    return o;
+  }
+  // fskhip_resampler_remap: a new object of this design whose stream i continues stream map[i] of this one (its history row, bit
+  // for bit; -1: a zero history) -- the map the engine and the processor were remapped with.  This object stays usable.
+  remap(map) { return this.constructor.adopt(addon.resamplerRemap(this.handle, Array.from(map)), this); }
+  // fskhip_resampler_snapshot: the image of `streams` (null: all, in order) as a Buffer -- the design and the history rows
+  snapshot(streams = null) { return addon.resamplerSnapshot(this.handle, streams === null || streams === undefined ? null : Array.from(streams)); }
+  // fskhip_resampler_restore: a new object from a snapshot() alone; stream i continues record map[i] (-1: a zero history; null:
+  // every record, in order).  Upsampler and Downsampler refuse an image of the other direction.
+  static fromSnapshot(buf, map = null, options = {}) {
+    const info = addon.resamplerSnapshotInfo(buf);
+    if (this.DIRECTION !== undefined && info.direction !== this.DIRECTION) {
+      throw new RangeError('the snapshot is of a resampler that goes ' + ['up', 'down'][info.direction] + ', not ' + ['up', 'down'][this.DIRECTION]);
+    }
+    const handle = addon.resamplerRestore(buf, map === null || map === undefined ? null : Array.from(map), options.device || 0);
+    return this.adopt(handle, { factor: info.factor, lowRate: options.lowRate, taps: Array.from(info.taps) });
+  }
 }
+function resamplerSnapshotInfo(buf) { return addon.resamplerSnapshotInfo(buf); }
 class Upsampler extends Resampler {
+  static get DIRECTION() { return 0; }
   constructor(factor, nStreams, options = {}) { super(0, factor, nStreams, options); }
   // samples: the format's typed array, [nStreams][pitch] (layout 'stream') or frames [nPerStream][pitch >= nStreams] ('sample');
   // nPerStream and pitch default to a packed array's -> Float32Array [nStreams][nPerStream * factor]
@@ -96,6 +122,7 @@ class Upsampler extends Resampler {
   }
 }
 class Downsampler extends Resampler {
+  static get DIRECTION() { return 1; }
   constructor(factor, nStreams, options = {}) { super(1, factor, nStreams, options); }
   // input: Float32Array [nStreams][n], n a multiple of factor; lens (Uint32Array or null): stream s reads as 0.0 from lens[s] on
   // -> the format's typed array, [nStreams][n / factor] or frames [n / factor][nStreams]
@@ -150,4 +177,4 @@ class FilterFactory {                             // filters.ts:325-368
   static createFIRHighpass(cutoffFreq, sampleRate, numTaps = 51) { return new FIRFilter(FilterDesign.sincHighpass(cutoffFreq, sampleRate, numTaps)); }
   static createFIRBandpass(centerFreq, bandwidth, sampleRate, numTaps = 51) { return new FIRFilter(FilterDesign.sincBandpass(centerFreq, bandwidth, sampleRate, numTaps)); }
 }
-module.exports = { FilterDesign, IIRFilter, IIRFilterBatch, FIRFilter, FIRFilterBatch, Upsampler, Downsampler, FilterFactory, PRECISION_F32, PRECISION_F64 };
+module.exports = { FilterDesign, IIRFilter, IIRFilterBatch, FIRFilter, FIRFilterBatch, Upsampler, Downsampler, resamplerSnapshotInfo, FilterFactory, PRECISION_F32, PRECISION_F64 };

@@ -35,12 +35,15 @@
 //   sincLowpass/sincHighpass(cutoff, sampleRate, numTaps), sincBandpass(center, bandwidth, sampleRate, numTaps) -> Float64Array
 //   firCreate(taps: Float64Array, nStreams, device, precision) -> handle;  firDestroy(handle)
 //   firProcess(handle, input: Float32Array, n, pitch, nStreams) -> Float32Array;  firReset(handle, stream)
-//   resamplerCreate(direction, factor, taps: Float64Array, nStreams, device, precision) -> handle;  resamplerDestroy(handle);  resamplerHistory(handle)
+//   resamplerCreate(direction, factor, taps: Float64Array, nStreams, device, precision) -> handle;  resamplerDestroy(handle);  resamplerHistory(handle);  resamplerStreams(handle)
 //   resamplerUp(handle, samples, format, layout, nIn, pitch, factor) -> Float32Array [S][nIn * factor]
 //   resamplerDown(handle, input: Float32Array [S][nIn], nIn, lens: Uint32Array|null, format, layout, factor) -> the format's typed array
 //   processorProcessSamplesAt(handle, up: resampler handle|null, down: resampler handle|null, input, inFormat, inLayout, nIn, inPitch, outFormat,
 //     outLayout, nOut, outPitch, flags) -> as processorProcessSamples, both sides at the handles' low rate (a side without samples needs none)
 //   resamplerReset(handle, stream);  resamplerState(handle) -> Float32Array [S][history];  resamplerSetState(handle, Float32Array)
+//   resamplerRemap(handle, map: number[]) -> handle;  resamplerSnapshot(handle, streams: number[]|null) -> Buffer
+//   resamplerRestore(snapshot: Uint8Array, map: number[]|null, device) -> handle
+//   resamplerSnapshotInfo(snapshot) -> {nStreams, direction, factor, nTaps, precision, history, taps: Float64Array}
 //   iirCreate(b, a: Float64Array, nStreams, device, precision) -> handle; iirProcess(handle, Float32Array | Float64Array, n, pitch, nStreams);
 //   iirCoefficients(handle), iirReset(handle, stream), iirDestroy(handle); butterworth(kind, f, bandwidth, sampleRate) -> [b0 b1 b2 a0 a1 a2]
 #include <cstring>
@@ -948,6 +951,14 @@ napi_value ResamplerHistory(napi_env env, napi_callback_info info) {
   return v;
 }
 // (handle, samples in the format's typed array, format, layout, nIn, pitch, factor) -> Float32Array [S][nIn * factor]
+napi_value ResamplerStreams(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
+  if (!r) return nullptr;
+  napi_value v;
+  NAPI_OK(napi_create_uint32(env, fskhip_resampler_streams(r), &v));
+  return v;
+}
 napi_value ResamplerUp(napi_env env, napi_callback_info info) {
   ARGS(7);
   const int32_t format = i32(env, argv[2]), layout = i32(env, argv[3]);
@@ -1049,6 +1060,69 @@ napi_value ResamplerSetState(napi_env env, napi_callback_info info) {
   int rc = fskhip_resampler_state_set(r, (const float *)st);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   return nullptr;
+}
+// ---- a resampler through remap / snapshot / restore (fskhip_resampler_remap ...): remap and restore return a NEW handle
+napi_value ResamplerRemap(napi_env env, napi_callback_info info) {   // (handle, map: number[]) -> handle
+  ARGS(2);
+  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
+  if (!r) return nullptr;
+  std::vector<int64_t> map;
+  if (!index_array(env, argv[1], "resamplerRemap: map must be an Array of integer stream indices (-1: a new stream)", &map)) return nullptr;
+  fskhip_resampler *out = nullptr;
+  int rc = fskhip_resampler_remap(r, index_data(map), (uint32_t)map.size(), &out);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return filter_box_new(env, out, BOX_RESAMPLER);
+}
+napi_value ResamplerSnapshot(napi_env env, napi_callback_info info) {   // (handle, streams: number[]|null) -> Buffer
+  ARGS(2);
+  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
+  if (!r) return nullptr;
+  std::vector<int64_t> sel;
+  const bool all = nullish(env, argv[1]);
+  if (!all && !index_array(env, argv[1], "resamplerSnapshot: streams must be an Array of integer stream indices", &sel)) return nullptr;
+  const uint32_t n = all ? fskhip_resampler_streams(r) : (uint32_t)sel.size();
+  size_t need = 0;
+  int rc = fskhip_resampler_snapshot_bytes(r, n, &need);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  void *data = nullptr;
+  napi_value buf;
+  NAPI_OK(napi_create_buffer(env, need, &data, &buf));
+  rc = fskhip_resampler_snapshot(r, index_data(sel, all), n, data, need, nullptr);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return buf;
+}
+napi_value ResamplerRestore(napi_env env, napi_callback_info info) {   // (snapshot: Uint8Array, map: number[]|null, device) -> handle
+  ARGS(3);
+  void *data; size_t size;
+  if (!typed(env, argv[0], napi_uint8_array, &data, &size)) return nullptr;
+  std::vector<int64_t> map;
+  const bool all = nullish(env, argv[1]);
+  if (!all && !index_array(env, argv[1], "resamplerRestore: map must be an Array of integer record indices (-1: a new stream)", &map)) return nullptr;
+  fskhip_resampler *out = nullptr;
+  int rc = fskhip_resampler_restore(i32(env, argv[2]), data, size, index_data(map, all), (uint32_t)map.size(), &out);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return filter_box_new(env, out, BOX_RESAMPLER);
+}
+napi_value ResamplerSnapshotInfo(napi_env env, napi_callback_info info) {   // (snapshot) -> {nStreams, direction, factor, nTaps, precision, history, taps}
+  ARGS(1);
+  void *data; size_t size;
+  if (!typed(env, argv[0], napi_uint8_array, &data, &size)) return nullptr;
+  fskhip_resampler_snapshot_info si;
+  int rc = fskhip_resampler_snapshot_info_get(data, size, &si);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  set_u32(env, o, "nStreams", si.n_streams);
+  set_u32(env, o, "direction", (uint32_t)si.direction);
+  set_u32(env, o, "factor", si.factor);
+  set_u32(env, o, "nTaps", si.n_taps);
+  set_u32(env, o, "precision", (uint32_t)si.precision);
+  set_u32(env, o, "history", si.history);
+  void *taps;   // (behind the 48-byte header of a validated image)
+  napi_value taps_v = make_typed(env, napi_float64_array, si.n_taps, 8, &taps);
+  memcpy(taps, (const unsigned char *)data + 48, sizeof(double) * (size_t)si.n_taps);
+  napi_set_named_property(env, o, "taps", taps_v);
+  return o;
 }
 
 // ---- IIRFilter (src/dsp/filters.ts:8-106) ----
@@ -1200,6 +1274,11 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"resamplerReset", nullptr, ResamplerReset, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"resamplerState", nullptr, ResamplerState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"resamplerSetState", nullptr, ResamplerSetState, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerStreams", nullptr, ResamplerStreams, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerRemap", nullptr, ResamplerRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerSnapshot", nullptr, ResamplerSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerRestore", nullptr, ResamplerRestore, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"resamplerSnapshotInfo", nullptr, ResamplerSnapshotInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirCreate", nullptr, IirCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirDestroy", nullptr, IirDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirCoefficients", nullptr, IirCoefficients, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -72,6 +72,12 @@ class XModemSnapshotInfo(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("n_streams", C.c_uint32), ("param0", C.c_uint32), ("param1", C.c_uint32), ("file_bytes", C.c_uint64)]
 
 
+class ResamplerSnapshotInfo(C.Structure):
+    """fskhip_resampler_snapshot_info (include/fskhip_next.h): what a resampler snapshot holds"""
+    _fields_ = [("n_streams", C.c_uint32), ("direction", C.c_int), ("factor", C.c_uint32), ("n_taps", C.c_uint32), ("precision", C.c_int),
+                ("history", C.c_uint32)]
+
+
 class XModemResult(C.Structure):
     """fskhip_xmodem_result (include/fskhip_next.h)."""
     _fields_ = [
@@ -247,6 +253,11 @@ _SYMBOLS = [
     ("fskhip_resampler_down_host", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P, C.c_int, C.c_int, C.c_size_t]),
     ("fskhip_resampler_state_get", C.c_int, [_P, _P]),
     ("fskhip_resampler_state_set", C.c_int, [_P, _P]),
+    ("fskhip_resampler_remap", C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P)]),
+    ("fskhip_resampler_snapshot_bytes", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("fskhip_resampler_snapshot", C.c_int, [_P, _P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fskhip_resampler_restore", C.c_int, [C.c_int, _P, C.c_size_t, _P, C.c_uint32, C.POINTER(_P)]),
+    ("fskhip_resampler_snapshot_info_get", C.c_int, [_P, C.c_size_t, C.POINTER(ResamplerSnapshotInfo)]),
     ("fskhip_processor_process_rate_device", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, _P]),
     ("fskhip_processor_process_rate_host", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32]),
     ("fskhip_iir_create", C.c_int, [C.c_int, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P)]),

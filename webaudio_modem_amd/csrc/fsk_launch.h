@@ -135,6 +135,13 @@ hipError_t launch_resample_up(int precision, const void *d_src, int format, int 
 hipError_t launch_resample_down(int precision, const float *d_src, size_t n_out, size_t src_pitch, const uint32_t *d_lens, uint32_t n_streams, void *d_dst,
                                 int format, int layout, size_t dst_pitch, uint32_t factor, uint32_t n_taps, const void *d_taps, const float *d_hist_in,
                                 float *d_hist_out, hipStream_t st);
+// fsk_resample_remap.hip: a resampler's history rows (H floats at a pitch of H floats, both bases 16-byte aligned) gathered through
+// a map (fskhip_resampler_remap / _snapshot / _restore).  Row i of d_dst (n_rows rows) takes row d_map[i] of d_src -- row
+// ident0 + i where d_map is null --, zeros where the entry is -1.  from_image: d_src is a staging slab holding records
+// [first, first + count) of an image; the launch writes only the rows whose record is among them, and the -1 rows where fresh_too.
+// Nothing is launched where n_rows * H is 0; hipErrorInvalidValue where it is more workgroups than one launch takes.
+hipError_t launch_resampler_hist_gather(float *d_dst, uint64_t n_rows, uint32_t H, const int64_t *d_map, int64_t ident0, const float *d_src, bool from_image,
+                                        int64_t first, int64_t count, bool fresh_too, hipStream_t st);
 // fsk_processor_remap.hip: FSKProcessor state (ProcState) between processors and stream-major records (ProcImage).
 // gather: stream i of D continues stream d_map[i] of S, or starts as a created one where d_map[i] = -1.
 // unpack: the same from the slab I of an image's records; streams whose record is in another slab are left alone, new ones are

@@ -361,6 +361,7 @@ int fskhip_resampler_create(int device, int direction, uint32_t factor, const do
   if (!r) return fail(FSKHIP_E_NOMEM, "out of host memory");
   r->device = device; r->precision = precision; r->S = n_streams;
   r->direction = direction; r->L = factor; r->n_taps = n_taps; r->H = resample_history(direction, factor, n_taps);
+  r->h_taps.assign(taps, taps + n_taps);
   // up: phase p's taps c[p], c[p + L], ... side by side (the slots behind a short phase are never read)
   const uint32_t K = resample_phase_len(factor, n_taps);
   std::vector<double> t64(direction == FSKHIP_RESAMPLE_UP ? (size_t)factor * K : (size_t)n_taps, 0.0);

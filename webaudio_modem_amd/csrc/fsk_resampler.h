@@ -1,7 +1,9 @@
-// fsk_resampler.h -- struct fskhip_resampler, for the two C-ABI units over it (fsk_resample.hip: the handle and its own calls;
-// fsk_processor_rate.hip: the FSKProcessor quantum at the low rate, which runs a handle's filter inside its own launches).  Not part
-// of the ABI.
+// fsk_resampler.h -- struct fskhip_resampler, for the C-ABI units over it (fsk_resample.hip: the handle and its own calls;
+// fsk_processor_rate.hip: the FSKProcessor quantum at the low rate, which runs a handle's filter inside its own launches;
+// fsk_resample_remap_api.hip: remap, snapshot and restore).  Not part of the ABI.
 #pragma once
+#include <vector>
+
 #include "fsk_filter_host.h"
 
 struct fskhip_resampler : fsk::FilterHost {
@@ -12,6 +14,7 @@ struct fskhip_resampler : fsk::FilterHost {
   float *hist[2] = {nullptr, nullptr};    // ping-pong: [cur] is read by the next call
   int cur = 0;
   uint32_t *d_lens = nullptr;             // the _host form's per-stream lengths
+  std::vector<double> h_taps;             // the taps as given to create: what a remap designs its new handle from and a snapshot carries
 
   const void *taps() const { return precision == FSKHIP_PRECISION_F64 ? (const void *)d_taps : (const void *)d_taps32; }
 };

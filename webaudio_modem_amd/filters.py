@@ -162,6 +162,73 @@ class _Resampler:
             raise ValueError("state must be [%d, %d]" % (self.n_streams, self.history))
         _lib.check(self._L.fskhip_resampler_state_set(self._h, st.ctypes.data))
 
+    @classmethod
+    def _adopt(cls, h, taps, factor, precision, device, low_rate):
+        """an object of this class over a handle the library has created (remap, restore)"""
+        import numpy as np
+        nxt = cls.__new__(cls)
+        nxt._np, nxt._L, nxt._h = np, _lib.lib(), h
+        nxt.factor, nxt.low_rate, nxt.device, nxt.precision = int(factor), low_rate, device, int(precision)
+        nxt.taps = [float(t) for t in taps]
+        nxt.n_streams = int(nxt._L.fskhip_resampler_streams(h))
+        nxt.history = int(nxt._L.fskhip_resampler_history(h))
+        return nxt
+
+    def remapped(self, stream_map):
+        """fskhip_resampler_remap: a new object of this design whose stream i continues stream stream_map[i] of this one -- its
+        history row, bit for bit -- or starts with a zero history where stream_map[i] is -1: the map the engine and the
+        processor were remapped with.  The rows move on the device.  This object stays usable."""
+        m = self._np.ascontiguousarray(stream_map, dtype=self._np.int64).reshape(-1)
+        h = C.c_void_p()
+        _lib.check(self._L.fskhip_resampler_remap(self._h, m.ctypes.data if len(m) else None, len(m), C.byref(h)))
+        return self._adopt(h, self.taps, self.factor, self.precision, self.device, self.low_rate)
+
+    def snapshot(self, streams=None):
+        """fskhip_resampler_snapshot: the image of streams `streams` (None: all, in order) as `bytes` -- the design (direction,
+        factor, precision, taps) and the history rows.  This object is read only and stays usable."""
+        np = self._np
+        sel = None if streams is None else np.ascontiguousarray(streams, dtype=np.int64).reshape(-1)
+        n = self.n_streams if sel is None else len(sel)
+        if sel is not None and not len(sel):
+            sel = np.zeros(1, np.int64)   # (an empty selection, not "all": a non-null pointer with n = 0)
+        sel_p = None if sel is None else sel.ctypes.data
+        size = C.c_size_t(0)
+        _lib.check(self._L.fskhip_resampler_snapshot_bytes(self._h, n, C.byref(size)))
+        buf = np.zeros(max(size.value, 1), np.uint8)
+        w = C.c_size_t(0)
+        _lib.check(self._L.fskhip_resampler_snapshot(self._h, sel_p, n, buf.ctypes.data, size.value, C.byref(w)))
+        return buf[:w.value].tobytes()
+
+    @classmethod
+    def from_snapshot(cls, snap, stream_map=None, device=0):
+        """fskhip_resampler_restore: a new object on `device` from a snapshot() alone: stream i continues record stream_map[i]
+        (-1: a zero history; None: every record, in order).  Upsampler and Downsampler refuse an image of the other direction."""
+        import numpy as np
+        from .engine import _blob
+        info = resampler_snapshot_info(snap)
+        if cls._DIRECTION is not None and info["direction"] != cls._DIRECTION:
+            raise ValueError("the snapshot is of a resampler that goes %s, not %s" % (("up", "down")[info["direction"]], ("up", "down")[cls._DIRECTION]))
+        kind = cls if cls._DIRECTION is not None else (Upsampler, Downsampler)[info["direction"]]
+        b = _blob(snap)
+        m = None if stream_map is None else np.ascontiguousarray(stream_map, dtype=np.int64).reshape(-1)
+        n = 0 if m is None else len(m)
+        if m is not None and not n:
+            m = np.zeros(1, np.int64)   # (an empty map, not "all": a non-null pointer with n = 0, which the library refuses)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().fskhip_resampler_restore(device, b.ctypes.data, b.nbytes, None if m is None else m.ctypes.data, n, C.byref(h)))
+        taps = np.frombuffer(b.tobytes(), dtype="<f8", count=info["n_taps"], offset=48)   # (the header is 48 bytes; the image has been validated)
+        return kind._adopt(h, taps, info["factor"], info["precision"], device, None)
+
+
+def resampler_snapshot_info(snap):
+    """fskhip_resampler_snapshot_info_get: what a resampler snapshot holds -- n_streams (records), direction (0 up, 1 down), factor,
+    n_taps, precision, history (floats per record) -- validated on the host, no device needed"""
+    from .engine import _blob, _struct_dict
+    b = _blob(snap)
+    info = _lib.ResamplerSnapshotInfo()
+    _lib.check(_lib.lib().fskhip_resampler_snapshot_info_get(b.ctypes.data, b.nbytes, C.byref(info)))
+    return _struct_dict(info)
+
 
 class Upsampler(_Resampler):
     """Capture samples at low_rate -> float32 [S, n * factor] at factor * low_rate, on the GPU: FIRFilterBatch(taps) over the
