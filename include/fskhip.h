@@ -47,8 +47,11 @@ enum {
   FSKHIP_E_HIP = -5,            /* HIP runtime error during a call */
   FSKHIP_E_NOMEM = -6,
   FSKHIP_E_OVERFLOW = -7,       /* an output slab was too small; counts still report the true size */
-  FSKHIP_E_HANDOFF = -8         /* ABI 8: a wave of a multi-wave kernel waited for its neighbour beyond the bound and ended the launch
-                                   early ("Hand-off waits" below); sticky, the engine is to be destroyed */
+  /* -8 is fskhip_next.h's FSKHIP_E_BUSY: the two headers' codes come back through the same int and share one number space */
+  FSKHIP_E_HANDOFF = -9         /* ABI 8: a wave of a multi-wave kernel waited for its neighbour beyond the bound and ended the launch
+                                   early ("Hand-off waits" below); sticky, the engine is to be destroyed.  (It was -8 at first, the
+                                   value of FSKHIP_E_BUSY, which hosts translate into 'Modulation already in progress'; the
+                                   processor's process calls can return either, so it took the first value free in both headers.) */
 };
 
 /* arithmetic the demodulator chain computes in */

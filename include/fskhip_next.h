@@ -14,6 +14,7 @@
 extern "C" {
 #endif
 
+/* (one number space with fskhip.h's enum, whose values run on at -9: every FSKHIP_E_* has a value of its own, tests/test_abi.py) */
 #define FSKHIP_E_BUSY (-8) /* reference: throws 'Modulation already in progress' fsk-processor.ts:90-92 */
 
 /* ---------------------------------------------------------------------------------------------------
@@ -111,6 +112,11 @@ int fskhip_processor_process_device(fskhip_processor *p, float *d_in, size_t n_i
                                     size_t n_out, size_t out_pitch, uint32_t flags, void *hip_stream);
 int fskhip_processor_process_host(fskhip_processor *p, float *in, size_t n_in, size_t in_pitch, float *out,
                                   size_t n_out, size_t out_pitch, uint32_t flags);
+/* What FSKHIP_PROC_GRAPH has done since fskhip_processor_create (ABI 8, an addition; FSKHIP_ABI_VERSION stays 8): quanta that were
+ * captured into a new graph, and quanta that replayed the graph of the call before.  A quantum that ran plainly -- no flag, a
+ * timing bracket or a trace armed, the fskhip_processor_process_rate_* forms -- counts as neither.  Read only; either pointer may be
+ * NULL.  FSKHIP_E_INVALID for a null processor. */
+int fskhip_processor_graph_stats(const fskhip_processor *p, uint64_t *captures, uint64_t *replays);
 
 /*
  * process() with either side in a capture format and layout (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): what a trunk or an RTP

@@ -8,6 +8,7 @@ const path = require('path');
 const addon = require(path.join(__dirname, 'fsk_addon.node'));
 const { FSKBatch, sampleFormat, sampleLayout } = require(path.join(__dirname, 'fsk-core.js'));
 const { Upsampler, Downsampler } = require(path.join(__dirname, 'filters.js'));
+const { busyError } = require(path.join(__dirname, 'errors.js'));
 const PROC_CLEAR_RX_ON_TX_COMPLETE = 1, PROC_GRAPH = 2;
 
 class FSKProcessorBatch {
@@ -137,8 +138,7 @@ class FSKProcessorBatch {
     try {
       addon.processorModulate(this.handle, slab, lens, mx, mask ? Uint8Array.from(mask.map((b) => (b ? 1 : 0))) : null);
     } catch (e) {
-      if (e.code === '-8') throw new Error('Modulation already in progress');   // fsk-processor.ts:91
-      throw e;
+      throw busyError(e, 'Modulation already in progress');   // fsk-processor.ts:91
     }
   }
   txState() { return addon.processorTxState(this.handle); }

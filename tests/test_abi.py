@@ -61,7 +61,7 @@ def test_error_codes_of_the_header_are_the_bindings(lib):
     import re
     hdr = open(os.path.join(ROOT, "include", "fskhip.h")).read()
     codes = {m.group(1): int(m.group(2)) for m in re.finditer(r"FSKHIP_(E_[A-Z_]+) = (-\d+)", hdr)}
-    assert codes and codes["E_HANDOFF"] == -8
+    assert codes and codes["E_HANDOFF"] == -9
     for name, value in codes.items():
         assert getattr(lib, name) == value, name
     csrc = os.path.join(ROOT, "webaudio_modem_amd", "csrc")
@@ -71,6 +71,100 @@ def test_error_codes_of_the_header_are_the_bindings(lib):
         bare = [l for l in src.splitlines() if "__builtin_amdgcn_s_sleep" in l and "//" not in l.split("__builtin_amdgcn_s_sleep")[0]]
         # (the one left: the persistent launch's wait for another workgroup's time slice, bounded in place -- fsk_blk.hip)
         assert len(bare) <= (1 if f == "fsk_blk.hip" else 0), (f, bare)
+
+
+def _header_error_codes():
+    """{name: value} of every FSKHIP_E_* the two headers define -- fskhip.h's enum entries and fskhip_next.h's #defines -- and the
+    list of (name, value) as they were met, so that a name defined twice shows"""
+    met = []
+    for name in ("fskhip.h", "fskhip_next.h"):
+        with open(os.path.join(ROOT, "include", name)) as fh:
+            src = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
+        met += [(m.group(1), int(m.group(2))) for m in re.finditer(r"\bFSKHIP_(E_[A-Z0-9_]+)\s*=\s*(-?\d+)", src)]
+        met += [(m.group(1), int(m.group(2))) for m in re.finditer(r"#define\s+FSKHIP_(E_[A-Z0-9_]+)\s+\(?\s*(-?\d+)\s*\)?", src)]
+    return dict(met), met
+
+
+def _node_error_table():
+    """napi/errors.js's ERRORS as node prints it; None without node"""
+    import json
+    import shutil
+    import subprocess
+    node = shutil.which("node")
+    if node is None:
+        return None
+    js = "console.log(JSON.stringify(require(%r).ERRORS))" % os.path.join(ROOT, "napi", "errors.js")
+    out = subprocess.run([node, "-e", js], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    return json.loads(out.stdout)
+
+
+def test_every_error_code_of_both_headers_has_a_number_of_its_own(lib):
+    """The codes of include/fskhip.h and include/fskhip_next.h come back through the same int: one number, one meaning
+    (FSKHIP_E_HANDOFF and FSKHIP_E_BUSY were both -8, and the hosts turn -8 into 'Modulation already in progress').  The Python
+    bindings' E_* and the Node host's table (napi/errors.js) are the headers' table, name by name, neither more nor less."""
+    codes, met = _header_error_codes()
+    assert {"E_INVALID", "E_OVERFLOW", "E_HANDOFF", "E_BUSY"} <= set(codes) and len(codes) >= 9
+    assert len(met) == len(codes), "a code is defined twice: %r" % (met,)
+    by_value = {}
+    for name, value in met:
+        assert value < 0, (name, value)
+        assert value not in by_value, "FSKHIP_%s and FSKHIP_%s are both %d" % (by_value[value], name, value)
+        by_value[value] = name
+    bound = {k: getattr(lib, k) for k in dir(lib) if re.fullmatch(r"E_[A-Z0-9_]+", k)}
+    assert bound == codes
+    node = _node_error_table()
+    if node is not None:
+        assert node == codes
+
+
+def test_hosts_keep_the_hand_off_fault_apart_from_a_busy_stream(lib):
+    """What the hosts' 'modulate' (and sendData / receiveData) make of a return code, on the mapping functions themselves:
+    FSKHIP_E_BUSY is the reference's own throw with its text; FSKHIP_E_HANDOFF -- the sticky 'destroy the engine' fault the same
+    calls can return -- stays the library's error with its code, and so does every other code."""
+    lib.lib()
+    text = "Modulation already in progress"
+    with pytest.raises(RuntimeError) as ei:
+        lib.check_busy(lib.E_BUSY, text)
+    assert type(ei.value) is RuntimeError and str(ei.value) == text
+    codes, _ = _header_error_codes()
+    for name, value in codes.items():
+        if name == "E_BUSY":
+            continue
+        with pytest.raises(lib.FskHipError) as ei:
+            lib.check_busy(value, text)
+        assert ei.value.code == value and text not in str(ei.value), name
+    assert lib.check_busy(lib.OK, text) == lib.OK
+    import shutil
+    import subprocess
+    node = shutil.which("node")
+    if node is None:
+        return
+    js = """
+const assert = require('assert');
+const { ERRORS, busyError } = require(%r);
+const text = 'Modulation already in progress';
+const thrown = (code) => Object.assign(new Error('as the library worded it'), { code: String(code) });
+const busy = busyError(thrown(ERRORS.E_BUSY), text);
+assert.strictEqual(busy.message, text);
+assert.strictEqual(busy.code, undefined);
+for (const [name, value] of Object.entries(ERRORS)) {
+  if (name === 'E_BUSY') continue;
+  const e = thrown(value);
+  assert.strictEqual(busyError(e, text), e, name);
+  assert.strictEqual(e.code, String(value));
+  assert.notStrictEqual(e.message, text);
+}
+const other = new TypeError('wrong typed array argument');
+assert.strictEqual(busyError(other, text), other);
+// the processor host's 'modulate' goes through it, and spells no code of its own
+const src = require('fs').readFileSync(%r, 'utf8');
+assert.ok(/busyError\\(e, 'Modulation already in progress'\\)/.test(src));
+assert.ok(!/code\\s*===/.test(src));
+console.log('errors ok');
+""" % (os.path.join(ROOT, "napi", "errors.js"), os.path.join(ROOT, "napi", "fsk-processor.js"))
+    out = subprocess.run([node, "-e", js], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and "errors ok" in out.stdout, out.stdout + out.stderr
 
 
 def test_config_struct_layout_matches_oracle(lib):

@@ -860,7 +860,7 @@ def test_hand_off_fault_word_stays_clear_on_every_multi_wave_kernel():
     faults() stay clean.  (The bound itself is exercised by tools/handoff_check.py on a -DFSK_SPIN_CAP_LOG2=0 build: profiles/.)"""
     import webaudio_modem_amd as wm
     from webaudio_modem_amd import _lib
-    assert _lib.E_HANDOFF == -8
+    assert _lib.E_HANDOFF == -9
     g = golden()
     base = g.array("d_noise_bell_10dB_0.in")
     bell = dict(baudRate=1200, markFrequency=1200, spaceFrequency=2200)

@@ -63,7 +63,7 @@ def main():
     for S, N, kernel in ((65536, 48000, "auto"), (131072, 48000, "auto"), (4096, 48000, "auto"), (16384, 48000, "two-wave")):
         ref, why = run("-", S, N, kernel)
         got, why2 = run(capped, S, N, kernel)
-        ok = ref is not None and got is not None and ref[1:3] == ["ok", "ok"] and got[1:3] == ["rc=-8", "rc=-8"] and int(got[3]) < int(ref[3])
+        ok = ref is not None and got is not None and ref[1:3] == ["ok", "ok"] and got[1:3] == ["rc=-9", "rc=-9"] and int(got[3]) < int(ref[3])
         bad += 0 if ok else 1
         print("%-7d x %-6d %-9s shipped: %s   bound 0: %s   %s" % (S, N, kernel, " ".join(ref) if ref else why, " ".join(got) if got else why2, "ok" if ok else "UNEXPECTED"), flush=True)
     print("handoff_check:", "ok" if bad == 0 else "%d UNEXPECTED" % bad)

@@ -11,8 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libfskhip.so")   # (measurement tools load other
 
 MAX_PATTERN_BYTES = 16
 OK = 0
-E_INVALID, E_NOT_CONFIGURED, E_UNSUPPORTED, E_NO_DEVICE, E_HIP, E_NOMEM, E_OVERFLOW, E_HANDOFF = -1, -2, -3, -4, -5, -6, -7, -8
-E_BUSY = -8
+E_INVALID, E_NOT_CONFIGURED, E_UNSUPPORTED, E_NO_DEVICE, E_HIP, E_NOMEM, E_OVERFLOW, E_BUSY, E_HANDOFF = -1, -2, -3, -4, -5, -6, -7, -8, -9
 PROC_CLEAR_RX_ON_TX_COMPLETE, PROC_GRAPH = 1, 2
 XM_NEED_MORE, XM_EOT, XM_TRUNCATED, XM_INVALID_SEQUENCE, XM_INVALID_CRC, XM_UNEXPECTED_SEQUENCE = 0, 1, 2, 3, 4, 5
 XT_IDLE, XT_WAIT_NAK, XT_WAIT_ACK, XT_WAIT_FINAL_ACK = 0, 1, 2, 3
@@ -180,6 +179,7 @@ _SYMBOLS = [
     ("fskhip_processor_destroy", C.c_int, [_P]),
     ("fskhip_processor_process_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_uint32, _P]),
     ("fskhip_processor_process_host", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_uint32]),
+    ("fskhip_processor_graph_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("fskhip_processor_process_fmt_device", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, _P]),
     ("fskhip_processor_process_fmt_host", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32]),
     ("fskhip_processor_modulate_host", C.c_int, [_P, _P, _P, C.c_size_t, _P]),
@@ -301,3 +301,12 @@ def check(rc):
     if rc != OK:
         raise FskHipError(rc, lib().fskhip_last_error().decode("utf-8", "replace"))
     return rc
+
+
+def check_busy(rc, text=None):
+    """check() for the calls that can find a stream busy ('modulate', sendData, receiveData): FSKHIP_E_BUSY, and no other code,
+    is the reference's own throw -- a plain RuntimeError with `text` (None: the library's message).  Every other failure,
+    FSKHIP_E_HANDOFF among them, is check()'s FskHipError with its code."""
+    if rc == E_BUSY:
+        raise RuntimeError(text if text is not None else lib().fskhip_last_error().decode("utf-8", "replace"))
+    return check(rc)

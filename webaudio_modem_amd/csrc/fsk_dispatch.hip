@@ -6,11 +6,18 @@
 
 using namespace fsk;
 
-// everything fskhip_demodulate_device's choice of launches depends on besides its arguments (bits 8 and 16: fsk_processor.hip)
+// everything fskhip_demodulate_device's choice of launches depends on besides its arguments (bits 8 and 16: fsk_processor.hip) --
+// and every kernel argument the host advances from call to call: a captured quantum (fsk_proc.h, run_quantum) holds the launches'
+// arguments by value, so a replay is the plain launch only while all of them are what they were at the capture.
+//   0x1F0000 (fp64 engines)  total_samples & 31: issue_launches' P.nco_anchor, where the generic kernel re-evaluates the NCO phasor.
+//                            A quantum that is no multiple of 32 samples moves it, and captures afresh on every call.
+//   0x600000                 exact_split: whether the fp64 kernel runs on two waves (plan_launches, split2)
 uint32_t fsk::engine_launch_key(const fskhip_engine *e) {
+  const uint32_t anchor = e->precision == FSKHIP_PRECISION_F64 ? (uint32_t)(e->total_samples & 31u) : 0u;
   return (e->ds_uniform ? 1u : 0u) | (e->ds_parity << 1) | (e->force_generic ? 4u : 0u) | (e->timing.on ? 8u : 0u) |
          (e->S.trace_stream != 0xFFFFFFFFu ? 16u : 0u) | (e->gen_odd ? 64u : 0u) | (e->P.quality ? 256u : 0u) | ((uint32_t)(e->pushes & 3u) << 10) |
-         ((e->blk.medium == 3u ? e->blk.med_now : e->blk.medium != 0u) ? 4096u : 0u) | ((uint32_t)e->policy << 13);
+         ((e->blk.medium == 3u ? e->blk.med_now : e->blk.medium != 0u) ? 4096u : 0u) | ((uint32_t)e->policy << 13) | (anchor << 16) |
+         ((e->exact_split & 3u) << 21);
 }
 // "blk_resets" = auto: tiles, and tiles the block path with resets took or would be given, of a sample of the groups since the
 // last look (whatever the last completed copy brought; nothing new = the choice stands).  It wins from about one tile in six on.

@@ -32,6 +32,7 @@ struct fskhip_processor {
   uint8_t *d_nout = nullptr; size_t d_nout_cap = 0;
   // captured quantum
   hipGraphExec_t graph_exec = nullptr;
+  uint64_t graph_captures = 0, graph_replays = 0;   // fskhip_processor_graph_stats: quanta captured afresh / replayed from the last capture
   struct Key {
     float *in; size_t n_in, in_pitch; float *out; size_t n_out, out_pitch; uint32_t flags; hipStream_t st; uint32_t ekey;
     int in_format = FSKHIP_SAMPLES_F32, in_layout = FSKHIP_LAYOUT_STREAM_MAJOR, out_format = FSKHIP_SAMPLES_F32, out_layout = FSKHIP_LAYOUT_STREAM_MAJOR;
@@ -79,12 +80,14 @@ int run_quantum(fskhip_processor *p, fskhip_processor::Key key, bool has_in, Lau
     (void)hipGraphDestroy(graph);
     if (ierr != hipSuccess) { p->graph_exec = nullptr; return fail(FSKHIP_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ierr)); }
     p->graph_key = key;
+    p->graph_captures++;
     // the capture itself already did the host-side accounting of one call; it launched nothing
     HIP_TRY(hipGraphLaunch(p->graph_exec, key.st));
     return FSKHIP_OK;
   }
   if (has_in) engine_note_replayed_call(p->e, key.n_in);
   HIP_TRY(hipGraphLaunch(p->graph_exec, key.st));
+  p->graph_replays++;
   return FSKHIP_OK;
 }
 

@@ -153,6 +153,13 @@ int fskhip_processor_process_host(fskhip_processor *p, float *in, size_t n_in, s
   return FSKHIP_OK;
 }
 
+int fskhip_processor_graph_stats(const fskhip_processor *p, uint64_t *captures, uint64_t *replays) {
+  if (!p) return fail(FSKHIP_E_INVALID, "null processor");
+  if (captures) *captures = p->graph_captures;
+  if (replays) *replays = p->graph_replays;
+  return FSKHIP_OK;
+}
+
 int fskhip_processor_modulate_host(fskhip_processor *p, const uint8_t *payloads, const uint32_t *lens, size_t payload_pitch,
                                    const uint8_t *mask) {
   if (!p) return fail(FSKHIP_E_INVALID, "null processor");

@@ -179,6 +179,13 @@ class FSKProcessorBatch:
             out.ctypes.data if out is not None else None, n_out, n_out, self.flags))
         return out
 
+    def graph_stats(self):
+        """fskhip_processor_graph_stats: (captures, replays) -- the quanta use_graph captured afresh and the quanta that replayed
+        the capture before them, since the batch was made.  A quantum that ran plainly is in neither."""
+        cap, rep = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(self._L.fskhip_processor_graph_stats(self._h, C.byref(cap), C.byref(rep)))
+        return int(cap.value), int(rep.value)
+
     def process_device(self, d_in, n_in, in_pitch, d_out, n_out, out_pitch, stream=None, flags=None):
         _lib.check(self._L.fskhip_processor_process_device(self._h, d_in, n_in, in_pitch, d_out, n_out, out_pitch,
                                                            self.flags if flags is None else flags, stream))
@@ -281,9 +288,7 @@ class FSKProcessorBatch:
         m = None if mask is None else np.ascontiguousarray(np.asarray(mask, dtype=bool).astype(np.uint8))
         rc = self._L.fskhip_processor_modulate_host(self._h, slab.ctypes.data, lens.ctypes.data, pitch,
                                                     m.ctypes.data if m is not None else None)
-        if rc == _lib.E_BUSY:
-            raise RuntimeError("Modulation already in progress")  # fsk-processor.ts:91
-        _lib.check(rc)
+        _lib.check_busy(rc, "Modulation already in progress")  # fsk-processor.ts:91
 
     def tx_state(self):
         S = self.n_streams

@@ -375,9 +375,7 @@ class XModemSenderBatch(_Lifecycle):
         offsets[1:] = np.cumsum([len(r) for r in rows], dtype=np.uint64)
         data = np.frombuffer(b"".join(rows), np.uint8)
         rc = self._L.fskhip_xmodem_tx_send_host(self._h, None if m is None else m.ctypes.data, offsets.ctypes.data, data.ctypes.data if len(data) else None)
-        if rc == _lib.E_BUSY:
-            raise RuntimeError(self._L.fskhip_last_error().decode("utf-8", "replace"))
-        _lib.check(rc)
+        _lib.check_busy(rc)
 
     def poll(self, mask=None, abort=None):
         """(streams, events): the streams where something happened, ascending (uint32), and their event records
@@ -499,9 +497,7 @@ class XModemFileReceiverBatch(_Lifecycle):
         with the reference's text, and nothing is started."""
         m = self._mask(mask)
         rc = self._L.fskhip_xmodem_recv_start_host(self._h, None if m is None else m.ctypes.data)
-        if rc == _lib.E_BUSY:
-            raise RuntimeError(self._L.fskhip_last_error().decode("utf-8", "replace"))
-        _lib.check(rc)
+        _lib.check_busy(rc)
 
     def poll(self, mask=None, timeout=None, abort=None):
         """(streams, events): the streams where something happened, ascending (uint32), and their event records
