@@ -401,6 +401,7 @@ int fskhip_get_faults(fskhip_engine *e, uint8_t *out, uint32_t *n_faulty);
  * scaled by amp_s in [amp_lo, amp_hi]; lead_s = splitmix64(seed,s) mod (lead_max+1).
  * d_out is [n_streams][pitch] float32 on the device.  Payload byte (s, frame, i) and lead_s/amp_s
  * are reproducible on the host with fskhip_synth_payload_byte / fskhip_synth_stream_params.
+ * n_per_stream = 0 writes nothing and returns FSKHIP_OK; a null d_out or pitch < n_per_stream is FSKHIP_E_INVALID.
  */
 int fskhip_synth_device(fskhip_engine *e, float *d_out, size_t n_per_stream, size_t pitch,
                         uint32_t payload_len, uint64_t seed, uint32_t lead_max, double amp_lo,
@@ -410,7 +411,11 @@ void fskhip_synth_stream_params(uint64_t seed, uint32_t stream, uint32_t lead_ma
                                 double amp_hi, uint32_t *lead, double *amp);
 /* Adds white Gaussian noise in place: sigma_s^2 = mean_square(stream s over n_per_stream) /
  * 10^(snr_db/10) (the reference tests' definition, tests/modems/fsk-demodulation.node.test.ts:
- * 1184-1205), counter-based generator keyed by (seed, stream, sample). */
+ * 1184-1205), counter-based generator keyed by (seed, stream, sample): stream counts from 0 over the whole batch,
+ * sample from 0 along the row, and nothing else enters the key.  Sample i of stream s becomes
+ * float32(float64(x) + sigma_s * g(seed, s, i)); a row of zeros stays +0.0.  n_per_stream = 0 touches nothing and
+ * returns FSKHIP_OK.  A null d_buf, pitch < n_per_stream or an snr_db that is not finite (NaN, +-Inf) is
+ * FSKHIP_E_INVALID, with the buffer untouched. */
 int fskhip_add_awgn_device(fskhip_engine *e, float *d_buf, size_t n_per_stream, size_t pitch,
                            double snr_db, uint64_t seed, void *hip_stream);
 

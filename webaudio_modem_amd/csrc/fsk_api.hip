@@ -1,5 +1,6 @@
 // fsk_api.hip -- C ABI of libfskhip.so (include/fskhip.h): the error string, device selection (fsk_host.h), memory helpers, timing, the clock probe and the
 // modulator / synthetic-signal entry points (the rest: fsk_create, fsk_options, fsk_dispatch, fsk_state).  No torch types, no CPU fallback.
+#include <cmath>
 #include <cstdarg>
 
 #include "fsk_engine.h"
@@ -172,6 +173,7 @@ int fskhip_synth_device(fskhip_engine *e, float *d_out, size_t n, size_t pitch, 
                         uint32_t lead_max, double amp_lo, double amp_hi, void *hip_stream) {
   if (!e) return fail(FSKHIP_E_NOT_CONFIGURED, "not configured");
   if (!d_out || pitch < n) return fail(FSKHIP_E_INVALID, "bad buffer");
+  if (n == 0) return FSKHIP_OK;  // nothing to write: no launch
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(launch_synth(e->M, e->S.coef, d_out, n, pitch, payload_len, seed, lead_max, amp_lo, amp_hi,
                        (hipStream_t)hip_stream));
@@ -188,6 +190,8 @@ int fskhip_add_awgn_device(fskhip_engine *e, float *d_buf, size_t n, size_t pitc
                            void *hip_stream) {
   if (!e) return fail(FSKHIP_E_NOT_CONFIGURED, "not configured");
   if (!d_buf || pitch < n) return fail(FSKHIP_E_INVALID, "bad buffer");
+  if (!std::isfinite(snr_db)) return fail(FSKHIP_E_INVALID, "fskhip_add_awgn_device: snr_db is not finite");
+  if (n == 0) return FSKHIP_OK;  // nothing to noise: a zero-wide grid is no launch HIP takes
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(launch_awgn(d_buf, n, pitch, e->n_streams, snr_db, seed, e->d_sigma, (hipStream_t)hip_stream));
   return FSKHIP_OK;
