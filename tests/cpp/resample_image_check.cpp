@@ -24,20 +24,13 @@ using Bytes = std::vector<unsigned char>;
 void seal(Bytes &b) {   // the checksum over the image as it stands
   fsk::RsImageHeader h;
   std::memcpy(&h, b.data(), sizeof(h));
-  h.checksum = 0;
-  fsk::SnapSum s;
-  fsk::snap_sum(s, &h, sizeof(h));
-  fsk::snap_sum(s, b.data() + sizeof(h), b.size() - sizeof(h));
-  h.checksum = fsk::snap_sum_value(s);
-  std::memcpy(b.data(), &h, sizeof(h));
+  fsk::image_seal(h, b.data(), b.size());
 }
 
 // a well-formed image; `tweak` changes the header before the body is laid out by ITS numbers and the checksum is made
 template <class Tweak>
 Bytes build(uint32_t direction, uint32_t factor, uint32_t n_taps, uint32_t n_records, Tweak tweak, bool reseal = true) {
-  fsk::RsImageHeader h;
-  std::memset(&h, 0, sizeof(h));
-  h.magic = fsk::kRsMagic; h.format = fsk::kRsFormat; h.header_bytes = sizeof(h);
+  fsk::RsImageHeader h = fsk::image_header<fsk::RsImageHeader>(fsk::kRsMagic, fsk::kRsFormat);
   h.n_records = n_records; h.direction = direction; h.factor = factor; h.n_taps = n_taps; h.precision = 0;
   h.history = fsk::resample_history((int)direction, factor, n_taps);
   h.record_bytes = 4u * h.history;

@@ -1,6 +1,7 @@
 """Processor remapping and snapshots without a GPU (include/fskhip_next.h): the five functions are declared, exported and bound
 on both hosts, fskhip_processor_snapshot_info_get reads an image crafted by hand here from the documented layout (a 48-byte
-header, fixed-size records), and it and fskhip_processor_restore are loud on every damaged image.  No processor is involved."""
+header, fixed-size records), it and fskhip_processor_restore are loud on every damaged image, and the host-only validator (csrc/fsk_processor_image.h) walks the
+same images as a stand-alone program under ASan + UBSan.  No processor is involved."""
 import ctypes as C
 import os
 import re
@@ -171,6 +172,46 @@ def test_damaged_images_are_refused_with_a_telling_message(lib, name, make, patt
         rc, msg = call()
         assert rc == lib.E_INVALID, (fn, rc, msg)
         assert pattern in msg and fn in msg, (fn, msg)
+
+
+def build_image_check(tmp_path_factory):
+    """tests/cpp/snapshot_image_check.cpp (the stream and processor snapshots' host-only validators) under ASan + UBSan: no library"""
+    exe = str(tmp_path_factory.mktemp("si") / "snapshot_image_check")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "webaudio_modem_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "cpp", "snapshot_image_check.cpp")],
+                   check=True)
+    return exe
+
+
+def walk_images(program, kind, blobs):
+    """the program's line for each image of one kind (None: no image at all)"""
+    text = "".join("%s %s\n" % (kind, "null" if b is None else b.hex() or "-") for b in blobs)
+    r = subprocess.run([program], input=text, capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr, (r.stdout, r.stderr)
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(blobs)
+    return lines
+
+
+@pytest.fixture(scope="module")
+def program(tmp_path_factory):
+    return build_image_check(tmp_path_factory)
+
+
+def test_the_validator_walks_the_same_images_as_a_host_program(lib, program):
+    good = [_image(), _image([], rx_cap=1024, pay_cap=0), _image([_record(50, 0, ring=b"xyz", read=49)], rx_cap=50, pay_cap=0)]
+    bad = [(make() if make else None, pattern) for _, make, pattern in BAD]
+    blobs = good + [b for b, _ in bad]
+    lines = walk_images(program, "P", blobs)
+    for blob, line in zip(blobs, lines):
+        rc, msg, info = _info(lib, blob)
+        if rc == 0:
+            assert line == "0 %d %d %d %d %d" % (info.n_streams, info.rx_capacity, info.payload_capacity, info.record_bytes, sum(blob[HEADER:])), line
+        else:
+            assert line.startswith("-1 ") and msg == "fskhip_processor_snapshot_info_get: " + line[3:], (line, msg)
+    assert [ln[0] for ln in lines[:len(good)]] == ["0"] * len(good)
+    for (_, pattern), line in zip(bad, lines[len(good):]):
+        assert line.startswith("-1 ") and pattern in line, (pattern, line)
 
 
 def test_device_calls_fail_loudly_without_a_processor(lib):

@@ -1,7 +1,8 @@
 """Stream snapshots without a GPU (include/fskhip.h): the six functions are declared, exported and bound on both hosts, and the
 host-side ones -- fskhip_snapshot_info_get, _stream_config, _concat, and the checks fskhip_restore_streams makes before it needs
-its engine -- are loud on every damaged image.  The images are crafted by hand here from the documented layout (a 352-byte
-header, fixed-size records); no engine is involved."""
+its engine -- are loud on every damaged image, and the host-only validator (csrc/fsk_snapshot_image.h) walks the same images as a
+stand-alone program under ASan + UBSan.  The images are crafted by hand here from the documented layout (a 352-byte header,
+fixed-size records); no engine is involved."""
 import ctypes as C
 import os
 import re
@@ -207,6 +208,29 @@ def test_damaged_images_are_refused_with_a_telling_message(lib, name, make, patt
         assert pattern in msg and fn in msg, (fn, msg)
     rc, msg = _concat(lib, [_image(2), blob])[:2]
     assert "snapshot 1" in msg                                   # concat says which of its inputs
+
+
+@pytest.fixture(scope="module")
+def program(tmp_path_factory):
+    from test_processor_snapshot_cpu import build_image_check
+    return build_image_check(tmp_path_factory)
+
+
+def test_the_validator_walks_the_same_images_as_a_host_program(lib, program):
+    from test_processor_snapshot_cpu import walk_images
+    good = [_image(0), _image(3, precision=1), _image(2), _image(3), _image(1)]
+    bad = [(make() if make else None, pattern) for _, make, pattern in BAD]
+    blobs = good + [b for b, _ in bad]
+    lines = walk_images(program, "S", blobs)
+    for blob, line in zip(blobs, lines):
+        rc, msg, info = _info(lib, blob, size=len(blob or b""))
+        if rc == 0:
+            assert line == "0 %d %d %d %d %d" % (info.n_streams, info.precision, info.per_stream_configs, info.record_bytes, sum(blob[HEADER:])), line
+        else:
+            assert line.startswith("-1 ") and msg == "fskhip_snapshot_info_get: " + line[3:], (line, msg)
+    assert [ln[0] for ln in lines[:len(good)]] == ["0"] * len(good)
+    for (_, pattern), line in zip(bad, lines[len(good):]):
+        assert line.startswith("-1 ") and pattern in line, (pattern, line)
 
 
 def test_concat_joins_images_of_one_history_and_names_the_field_that_differs(lib):

@@ -106,7 +106,6 @@ hipError_t launch_remap(int precision, const RemapArgs &A, const int64_t *d_map,
 // pack: records [0, count) of d_out = streams d_sel[first ..] of S (d_sel null: first, first + 1, ...).
 // unpack: stream i of D takes record d_map[i] - rec_first of d_in where that is in [0, rec_count), a new stream's state where
 // d_map[i] = -1 and fresh_too; other streams are left alone (a restore runs it once per slab of records).
-SnapLayout snap_layout(int precision, uint32_t d, uint32_t amp_cap, uint32_t wide, uint32_t frac);
 hipError_t launch_snap_pack(const SnapLayout &L, const DemodState &S, uint32_t n_src, const int64_t *d_sel, uint32_t first, uint32_t count, void *d_out,
                             hipStream_t st);
 hipError_t launch_snap_unpack(int precision, const SnapLayout &L, const DemodState &D, uint32_t n_dst, const int64_t *d_map, uint32_t rec_first, uint32_t rec_count,

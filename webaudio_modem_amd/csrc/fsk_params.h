@@ -201,7 +201,29 @@ struct SnapLayout {
   uint32_t n_sec;
   SnapSection sec[8];
 };
-static constexpr uint32_t kSnapHostWords = 12;   // the host part of a record (fsk_snapshot_api.hip SnapRecordHost)
+static constexpr uint32_t kSnapHostWords = 12;   // the host part of a record (fsk_snapshot_image.h SnapRecordHost)
+inline SnapLayout snap_layout(int precision, uint32_t d, uint32_t amp_cap, uint32_t wide, uint32_t frac) {
+  SnapLayout L{};
+  L.d = d;
+  uint32_t w = 0;
+  auto add = [&](uint32_t kind, uint32_t n, uint32_t e) {
+    if (n == 0) return;
+    L.sec[L.n_sec++] = SnapSection{kind, w, n, e};
+    w += n * e;
+  };
+  const bool f64 = precision == 1;
+  add(SNAP_ZERO, kSnapHostWords / 4, 4);
+  add(SNAP_AMP, amp_cap / 4, 4);
+  if (f64) add(SNAP_RF, RF_COUNT, 2);
+  if (wide) add(SNAP_POLY, d, 2);
+  if (frac) add(SNAP_POLYU, d, 2);
+  if (!f64) add(SNAP_RF, RF_COUNT, 1);
+  add(SNAP_IF, IF_COUNT, 1);
+  if (!wide) add(SNAP_POLY, d, 1);
+  add(SNAP_ZERO, (4u - (w & 3u)) & 3u, 1);
+  L.rec_words = w;
+  return L;
+}
 
 // FSKProcessor + ChunkedModulator per stream (fsk-processor.ts, chunked-modulator.ts), device resident.
 // The pending signal is kept as the modulator's generator state (payload + phase + position), not as samples:

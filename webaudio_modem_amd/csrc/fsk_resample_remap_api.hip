@@ -3,8 +3,8 @@
 // _restore and _snapshot_info_get.  Each of remap and restore CREATES its handle (fskhip_resampler_create, from the source's or the
 // image's own taps), so there is no destination to mismatch.  The rows move on the device (fsk_resample_remap.hip), into the new
 // handle's hist[cur] only; an image's rows cross PCIe in slabs through fsk_stage.h's pipelines, its header, taps and padding
-// being the host's.  The image's format and the one definition of a valid image are fsk_resample_image.h's (host-only); this file
-// is the format's only writer (the frame's header and checksum through fsk_stage.h).
+// being the host's.  The image's format and the one definition of a valid image are fsk_resample_image.h's (host-only, on
+// fsk_image.h's frame); this file is the format's only writer.
 #include <algorithm>
 
 #include "fsk_host.h"
@@ -42,8 +42,7 @@ extern "C" {
 int fskhip_resampler_snapshot_info_get(const void *image, size_t bytes, fskhip_resampler_snapshot_info *info) {
   static const char who[] = "fskhip_resampler_snapshot_info_get";
   RsImage im;
-  char msg[256];
-  if (rs_image_open(image, bytes, &im, msg, sizeof(msg))) return fail(FSKHIP_E_INVALID, "%s: %s", who, msg);
+  if (const int rc = open_image(who, rs_image_open, image, bytes, &im)) return rc;
   if (!info) return fail(FSKHIP_E_INVALID, "%s: null info", who);
   std::memset(info, 0, sizeof(*info));
   info->n_streams = im.h.n_records; info->direction = (int)im.h.direction; info->factor = im.h.factor; info->n_taps = im.h.n_taps;
@@ -60,13 +59,11 @@ int fskhip_resampler_remap(const fskhip_resampler *src, const int64_t *map, uint
   fskhip_resampler *r = nullptr;
   if (const int rc = fskhip_resampler_create(src->device, src->direction, src->L, src->h_taps.data(), src->n_taps, n_map, src->precision, &r)) return rc;
   if (r->H) {
+    Scratch sc;
     int64_t *d_map = nullptr;
-    if (const int rc = dev_alloc(d_map, n_map)) return drop(r, rc);
-    hipError_t err = hipMemcpy(d_map, map, sizeof(int64_t) * n_map, hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = launch_resampler_hist_gather(r->hist[r->cur], n_map, r->H, d_map, 0, src->hist[src->cur], false, 0, 0, false, nullptr);
+    if (const int rc = sc.upload(d_map, map, n_map)) return drop(r, rc);
+    hipError_t err = launch_resampler_hist_gather(r->hist[r->cur], n_map, r->H, d_map, 0, src->hist[src->cur], false, 0, 0, false, nullptr);
     if (err == hipSuccess) err = hipDeviceSynchronize();
-    if (err != hipSuccess) (void)hipDeviceSynchronize();
-    (void)hipFree(d_map);
     if (err != hipSuccess) return drop(r, fail(FSKHIP_E_HIP, "%s: %s", who, hipGetErrorString(err)));
   }
   *out = r;
@@ -90,8 +87,9 @@ int fskhip_resampler_snapshot(const fskhip_resampler *r, const int64_t *streams,
   HIP_TRY(hipSetDevice(r->device));
   HIP_TRY(hipDeviceSynchronize());
 
-  RsImageHeader h = image_header<RsImageHeader>(kRsMagic, kRsFormat, rec_bytes);
-  h.n_records = n_sel; h.direction = (uint32_t)r->direction; h.factor = r->L; h.n_taps = r->n_taps; h.precision = (uint32_t)r->precision; h.history = r->H;
+  RsImageHeader h = image_header<RsImageHeader>(kRsMagic, kRsFormat);
+  h.record_bytes = (uint32_t)rec_bytes; h.n_records = n_sel;
+  h.direction = (uint32_t)r->direction; h.factor = r->L; h.n_taps = r->n_taps; h.precision = (uint32_t)r->precision; h.history = r->H;
   unsigned char *out = (unsigned char *)image, *taps = out + sizeof(h), *rec = taps + sizeof(double) * (size_t)r->n_taps;
   if (rec_bytes && n_sel) {
     const float *rows = r->hist[r->cur];   // (the one buffer the next call reads: an image does not tell which of the two it was)
@@ -105,8 +103,7 @@ int fskhip_resampler_snapshot(const fskhip_resampler *r, const int64_t *streams,
   std::memcpy(taps, r->h_taps.data(), sizeof(double) * (size_t)r->n_taps);
   const size_t live = (size_t)rs_live_bytes(n_sel, r->n_taps, r->H);
   std::memset(out + live, 0, need - live);
-  h.checksum = image_checksum(h, out + sizeof(h), need - sizeof(h));
-  std::memcpy(out, &h, sizeof(h));
+  image_seal(h, out, need);
   return FSKHIP_OK;
 }
 
@@ -114,8 +111,7 @@ int fskhip_resampler_restore(int device, const void *image, size_t bytes, const 
   static const char who[] = "fskhip_resampler_restore";
   if (!out) return fail(FSKHIP_E_INVALID, "%s: null out", who);
   RsImage im;
-  char msg[256];
-  if (rs_image_open(image, bytes, &im, msg, sizeof(msg))) return fail(FSKHIP_E_INVALID, "%s: %s", who, msg);
+  if (const int rc = open_image(who, rs_image_open, image, bytes, &im)) return rc;
   const RsImageHeader &h = im.h;
   std::vector<int64_t> all;
   if (!map) {   // every record, in order

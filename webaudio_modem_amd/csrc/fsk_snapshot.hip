@@ -26,29 +26,6 @@ namespace fsk {
 static constexpr uint32_t kSnapChunk = 128;              // words of a record per LDS pass (a multiple of 4)
 static constexpr uint32_t kSnapPitch = kSnapChunk + 1;   // odd
 
-SnapLayout snap_layout(int precision, uint32_t d, uint32_t amp_cap, uint32_t wide, uint32_t frac) {
-  SnapLayout L{};
-  L.d = d;
-  uint32_t w = 0;
-  auto add = [&](uint32_t kind, uint32_t n, uint32_t e) {
-    if (n == 0) return;
-    L.sec[L.n_sec++] = SnapSection{kind, w, n, e};
-    w += n * e;
-  };
-  const bool f64 = precision == 1;
-  add(SNAP_ZERO, kSnapHostWords / 4, 4);
-  add(SNAP_AMP, amp_cap / 4, 4);
-  if (f64) add(SNAP_RF, RF_COUNT, 2);
-  if (wide) add(SNAP_POLY, d, 2);
-  if (frac) add(SNAP_POLYU, d, 2);
-  if (!f64) add(SNAP_RF, RF_COUNT, 1);
-  add(SNAP_IF, IF_COUNT, 1);
-  if (!wide) add(SNAP_POLY, d, 1);
-  add(SNAP_ZERO, (4u - (w & 3u)) & 3u, 1);
-  L.rec_words = w;
-  return L;
-}
-
 namespace {
 
 // element `e` of a section for stream s, in elements of the section's own size

@@ -1,143 +1,18 @@
 // fsk_snapshot_api.hip -- C ABI of libfskhip.so (include/fskhip.h): stream snapshots.  A snapshot is a host-side image of a set
 // of streams -- one SnapHeader, then fixed-size stream-major records -- that fskhip_restore_streams continues from under
 // fskhip_remap_streams' contract, on any device and in any process running this build.  The format is documented in the
-// header; this file is its only reader and writer.  The pack / unpack kernels are fsk_snapshot.hip's; the checks, the
-// lock-step decision and the host-side counters are the remap's own (fsk_create.hip, fsk_engine.h); the frame of an image
-// (checksum, open front and back, selection and room checks) and the slab pipelines are fsk_stage.h's, shared with the
-// processor snapshots.
+// header; its layout and the one definition of a valid image are fsk_snapshot_image.h's (host-only, on fsk_image.h's frame), and
+// this file is the format's only writer.  The pack / unpack kernels are fsk_snapshot.hip's; the checks, the lock-step decision
+// and the host-side counters are the remap's own (fsk_create.hip, fsk_engine.h); the selection and room checks and the slab
+// pipelines are fsk_stage.h's, shared with the other three snapshot units.
 #include <algorithm>
 
 #include "fsk_engine.h"
 #include "fsk_launch.h"
+#include "fsk_snapshot_image.h"
 #include "fsk_stage.h"
 
 using namespace fsk;
-
-namespace {
-
-constexpr uint32_t kSnapMagic = 0x534B5346u;   // "FSKS"
-constexpr uint32_t kSnapFormat = 1;
-
-// fskhip_config without the padding its int32 / double mix leaves: every byte of a snapshot is defined
-struct SnapConfig {
-  double sampleRate, baudRate, markFrequency, spaceFrequency, syncThreshold, preFilterBandwidth;
-  int32_t preamblePattern[FSKHIP_MAX_PATTERN_BYTES], sfdPattern[FSKHIP_MAX_PATTERN_BYTES];
-  int32_t preambleLen, sfdLen, startBits, stopBits, parity, agcEnabled, adaptiveThreshold, zero;
-};
-static_assert(sizeof(SnapConfig) == 6 * 8 + (2 * FSKHIP_MAX_PATTERN_BYTES + 8) * 4, "SnapConfig has padding");
-
-struct SnapHeader {
-  uint32_t magic, format;
-  uint32_t rf_count, if_count;    // the state-layout stamp: the field counts and ...
-  uint64_t fields_hash;           // ... FNV-1a of the field names in fsk_params.h order (and the spans the fp32 reset words count in)
-  uint64_t checksum;              // snap_sum over the header with this field 0, then the records
-  uint32_t header_bytes, record_bytes;
-  uint32_t n_streams;
-  int32_t precision;
-  uint32_t per_stream_configs;    // 0: every record runs under cfg0
-  uint32_t d, amp_cap, wide, frac, n_bits, ring_cap;    // the geometry fskhip_remap_streams compares
-  uint32_t ds_parity, ds_uniform, gen_odd, quality;     // engine-level values a destination takes over
-  uint32_t grid_poly_phase, grid_amp_pos;               // the ring grid: source row 0's positions (every row's, in lock step)
-  uint32_t frame_valid;           // fp32, one shared configuration, at least one stream: frame_phase is the engine's
-  uint32_t zero[2];
-  uint64_t frame_phase;           // the free-running I/Q frame: NCO phase minus frame offset of source row 0 (64-bit turns)
-  uint64_t calls, total_samples, pushes;
-  SnapConfig cfg0;
-};
-static_assert(sizeof(SnapHeader) == 352 && sizeof(SnapHeader) % 16 == 0, "SnapHeader has padding");
-
-// the host part of a record (kSnapHostWords words): what of a stream lives on the host
-struct SnapRecordHost {
-  double markFrequency, spaceFrequency, preFilterBandwidth;
-  uint32_t adaptiveThreshold, zero;
-  uint64_t base_calls, base_samples;
-};
-static_assert(sizeof(SnapRecordHost) == kSnapHostWords * 4, "SnapRecordHost has padding");
-
-uint64_t fields_hash() {
-  static const char names[] =
-#define X(n) #n ","
-      FSK_REAL_FIELDS(X) FSK_REAL_FIELDS_PIPE(X) FSK_REAL_FIELDS_QUALITY(X) "|" FSK_INT_FIELDS(X) FSK_INT_FIELDS_PIPE(X) FSK_INT_FIELDS_QUALITY(X)
-#undef X
-      ;
-  uint64_t h = 0xcbf29ce484222325ull;
-  for (const char *p = names; *p; p++) h = (h ^ (uint8_t)*p) * 0x100000001b3ull;
-  h = (h ^ kZeroLagPairs) * 0x100000001b3ull;
-  h = (h ^ kHandLag) * 0x100000001b3ull;
-  return h;
-}
-
-SnapConfig pack_config(const fskhip_config &c) {
-  SnapConfig o;
-  std::memset(&o, 0, sizeof(o));
-  o.sampleRate = c.sampleRate; o.baudRate = c.baudRate; o.markFrequency = c.markFrequency; o.spaceFrequency = c.spaceFrequency;
-  o.syncThreshold = c.syncThreshold; o.preFilterBandwidth = c.preFilterBandwidth;
-  // (only the bytes in use: what lies behind preambleLen / sfdLen in the caller's struct is not state)
-  for (int i = 0; i < FSKHIP_MAX_PATTERN_BYTES; i++) {
-    o.preamblePattern[i] = i < c.preambleLen ? c.preamblePattern[i] : 0;
-    o.sfdPattern[i] = i < c.sfdLen ? c.sfdPattern[i] : 0;
-  }
-  o.preambleLen = c.preambleLen; o.sfdLen = c.sfdLen; o.startBits = c.startBits; o.stopBits = c.stopBits; o.parity = c.parity;
-  o.agcEnabled = c.agcEnabled != 0; o.adaptiveThreshold = c.adaptiveThreshold != 0;
-  return o;
-}
-fskhip_config unpack_config(const SnapConfig &c) {
-  fskhip_config o;
-  std::memset(&o, 0, sizeof(o));
-  o.sampleRate = c.sampleRate; o.baudRate = c.baudRate; o.markFrequency = c.markFrequency; o.spaceFrequency = c.spaceFrequency;
-  o.syncThreshold = c.syncThreshold; o.preFilterBandwidth = c.preFilterBandwidth;
-  std::memcpy(o.preamblePattern, c.preamblePattern, sizeof(o.preamblePattern));
-  std::memcpy(o.sfdPattern, c.sfdPattern, sizeof(o.sfdPattern));
-  o.preambleLen = c.preambleLen; o.sfdLen = c.sfdLen; o.startBits = c.startBits; o.stopBits = c.stopBits; o.parity = c.parity;
-  o.agcEnabled = c.agcEnabled; o.adaptiveThreshold = c.adaptiveThreshold;
-  return o;
-}
-
-// A validated snapshot: the header (copied: the caller's bytes need no alignment), its record layout and the records.
-struct Snap {
-  SnapHeader h;
-  SnapLayout L;
-  const unsigned char *rec;
-  SnapRecordHost host_part(size_t i) const {
-    SnapRecordHost r;
-    std::memcpy(&r, rec + i * h.record_bytes, sizeof(r));
-    return r;
-  }
-  fskhip_config config(size_t i) const {
-    fskhip_config c = unpack_config(h.cfg0);
-    const SnapRecordHost r = host_part(i);
-    c.markFrequency = r.markFrequency; c.spaceFrequency = r.spaceFrequency; c.preFilterBandwidth = r.preFilterBandwidth;
-    c.adaptiveThreshold = (int32_t)r.adaptiveThreshold;
-    return c;
-  }
-  uint32_t int_word(size_t i, int f) const {   // IF_* word f of record i
-    uint32_t w0 = 0, v;
-    for (uint32_t k = 0; k < L.n_sec; k++)
-      if (L.sec[k].kind == SNAP_IF) w0 = L.sec[k].w0;
-    std::memcpy(&v, rec + i * h.record_bytes + 4u * (w0 + (uint32_t)f), 4);
-    return v;
-  }
-};
-
-int snap_open(const char *who, const void *buf, size_t size, Snap *s) {
-  SnapHeader &h = s->h;
-  const auto stamp = [&] {
-    if (h.rf_count != RF_COUNT || h.if_count != IF_COUNT || h.fields_hash != fields_hash())
-      return fail(FSKHIP_E_INVALID, "%s: the snapshot's state layout (%u + %u words, stamp %016llx) is another build's (%d + %d words, stamp %016llx)", who, h.rf_count,
-                  h.if_count, (unsigned long long)h.fields_hash, (int)RF_COUNT, (int)IF_COUNT, (unsigned long long)fields_hash());
-    return (int)FSKHIP_OK;
-  };
-  if (const int rc = image_open_front(who, "snapshot", buf, size, kSnapMagic, kSnapFormat, &h, stamp)) return rc;
-  if (h.precision != FSKHIP_PRECISION_F32 && h.precision != FSKHIP_PRECISION_F64) return fail(FSKHIP_E_INVALID, "%s: unknown precision %d in the snapshot", who, h.precision);
-  if (h.amp_cap != 8u * h.d || h.d == 0 || h.d > (1u << 20) || h.wide > 1 || h.frac > 1 || (h.frac && !h.wide))
-    return fail(FSKHIP_E_INVALID, "%s: inconsistent geometry in the snapshot (d %u, amp_cap %u, wide %u, frac %u)", who, h.d, h.amp_cap, h.wide, h.frac);
-  s->L = snap_layout(h.precision, h.d, h.amp_cap, h.wide, h.frac);
-  if (h.record_bytes != 4u * s->L.rec_words)
-    return fail(FSKHIP_E_INVALID, "%s: record_bytes %u, but this geometry and precision make records of %u bytes", who, h.record_bytes, 4u * s->L.rec_words);
-  return image_open_back(who, "n_streams", buf, size, h, h.n_streams, &s->rec);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -159,9 +34,9 @@ int fskhip_snapshot_streams(fskhip_engine *e, const int64_t *sel, uint32_t n_sel
   HIP_TRY(hipDeviceSynchronize());
   if (const int rc = engine_refuse_handoff(who, "the engine", e)) return rc;
 
-  SnapHeader h = image_header<SnapHeader>(kSnapMagic, kSnapFormat, rec_bytes);
+  SnapHeader h = image_header<SnapHeader>(kSnapMagic, kSnapFormat);
   h.rf_count = RF_COUNT; h.if_count = IF_COUNT; h.fields_hash = fields_hash();
-  h.n_streams = n_sel; h.precision = e->precision;
+  h.record_bytes = (uint32_t)rec_bytes; h.n_streams = n_sel; h.precision = e->precision;
   h.per_stream_configs = e->cfgs.size() == 1 ? 0u : 1u;
   h.d = e->P.d; h.amp_cap = e->P.amp_cap; h.wide = e->P.wide; h.frac = e->P.frac; h.n_bits = e->P.n_bits; h.ring_cap = e->P.ring_cap;
   h.ds_parity = e->ds_parity; h.ds_uniform = e->ds_uniform ? 1u : 0u; h.gen_odd = e->gen_odd ? 1u : 0u; h.quality = e->P.quality;
@@ -205,7 +80,7 @@ int fskhip_snapshot_streams(fskhip_engine *e, const int64_t *sel, uint32_t n_sel
 int fskhip_snapshot_info_get(const void *buf, size_t size, fskhip_snapshot_info *info) {
   static const char who[] = "fskhip_snapshot_info_get";
   Snap s;
-  if (const int rc = snap_open(who, buf, size, &s)) return rc;
+  if (const int rc = open_image(who, snap_image_open, buf, size, &s)) return rc;
   if (!info) return fail(FSKHIP_E_INVALID, "%s: null info", who);
   std::memset(info, 0, sizeof(*info));
   info->n_streams = s.h.n_streams; info->precision = s.h.precision; info->per_stream_configs = s.h.per_stream_configs;
@@ -217,7 +92,7 @@ int fskhip_snapshot_info_get(const void *buf, size_t size, fskhip_snapshot_info 
 int fskhip_snapshot_stream_config(const void *buf, size_t size, uint32_t i, fskhip_config *cfg) {
   static const char who[] = "fskhip_snapshot_stream_config";
   Snap s;
-  if (const int rc = snap_open(who, buf, size, &s)) return rc;
+  if (const int rc = open_image(who, snap_image_open, buf, size, &s)) return rc;
   if (!cfg) return fail(FSKHIP_E_INVALID, "%s: null cfg", who);
   // (record 0 of an empty snapshot: the shared configuration, so that a host can still build the destination from the file)
   if (i >= s.h.n_streams && !(i == 0 && s.h.n_streams == 0)) return fail(FSKHIP_E_INVALID, "%s: record %u, the snapshot has %u", who, i, s.h.n_streams);
@@ -230,7 +105,7 @@ int fskhip_snapshot_concat(const void *const *bufs, const size_t *sizes, uint32_
   if (!bufs || !sizes || n == 0) return fail(FSKHIP_E_INVALID, "%s: null / no snapshots", who);
   std::vector<Snap> ss(n);
   for (uint32_t k = 0; k < n; k++)
-    if (const int rc = snap_open(who, bufs[k], sizes[k], &ss[k])) {
+    if (const int rc = open_image(who, snap_image_open, bufs[k], sizes[k], &ss[k])) {
       const std::string msg = fskhip_last_error();
       return fail(rc, "%s (snapshot %u)", msg.c_str(), k);
     }
@@ -274,8 +149,7 @@ int fskhip_snapshot_concat(const void *const *bufs, const size_t *sizes, uint32_
     if (bytes) std::memmove(rec + at, ss[k].rec, bytes);
     at += bytes;
   }
-  h.checksum = image_checksum(h, rec, at);
-  std::memcpy(out, &h, sizeof(h));
+  image_seal(h, out, need);
   return FSKHIP_OK;
 }
 
@@ -283,7 +157,7 @@ int fskhip_restore_streams(fskhip_engine *dst, const void *buf, size_t size, con
   static const char who[] = "fskhip_restore_streams";
   if (const int rc = remap_check_map(who, "a record of the snapshot", map, n_map)) return rc;
   Snap s;
-  if (const int rc = snap_open(who, buf, size, &s)) return rc;
+  if (const int rc = open_image(who, snap_image_open, buf, size, &s)) return rc;
   if (!dst) return fail(FSKHIP_E_INVALID, "%s: null engine", who);
   const SnapHeader &h = s.h;
   StreamSource V{};

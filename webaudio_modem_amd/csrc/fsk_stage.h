@@ -1,17 +1,14 @@
-// fsk_stage.h -- what the two image formats share (fsk_snapshot_api.hip: stream snapshots; fsk_processor_remap_api.hip: processor
-// snapshots), each once: the checksum over an image (fsk_snapsum.h), the frame every image has (the front and the back of opening one, the
-// common header fields, the writers' selection and room checks), and the two slab pipelines that carry records across PCIe --
-// stage_records_out for the writers, stage_records_in for the restores.  The formats keep their own headers, geometry checks
-// and kernels; no event chain is spelled anywhere else.  Not part of the ABI.
+// fsk_stage.h -- what the four snapshot units (fsk_snapshot_api.hip, fsk_processor_remap_api.hip, fsk_xmodem_remap_api.hip,
+// fsk_resample_remap_api.hip) share that needs a device, each once: the writers' selection and room checks, and the two slab
+// pipelines that carry records across PCIe -- stage_records_out for the writers, stage_records_in for the restores; no event chain is
+// spelled anywhere else.  (The frame of an image is host-only: fsk_image.h, under the four fsk_*_image.h.)  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
-#include <cstring>
 
 #include "fsk_host.h"
-#include "fsk_snapsum.h"
 
 namespace fsk {
 
@@ -47,56 +44,6 @@ struct Stage {
     if (copy) (void)hipStreamDestroy(copy);
   }
 };
-
-// ---- the frame of an image: `H` is a format's header, which begins magic, format and has header_bytes, record_bytes, checksum ----
-template <class H>
-uint64_t image_checksum(H h, const void *records, size_t bytes) {
-  h.checksum = 0;
-  SnapSum s;
-  snap_sum(s, &h, sizeof(h));
-  snap_sum(s, records, bytes);
-  return snap_sum_value(s);
-}
-
-// a writer's header: zeroed (every byte of an image is defined), the frame's fields set; the format fills in the rest
-template <class H>
-H image_header(uint32_t magic, uint32_t format, size_t rec_bytes) {
-  H h;
-  std::memset(&h, 0, sizeof(h));
-  h.magic = magic; h.format = format; h.header_bytes = sizeof(H); h.record_bytes = (uint32_t)rec_bytes;
-  return h;
-}
-
-// The front of opening an image, `noun` being what the messages call it: null, shorter than a header, magic, format,
-// header_bytes.  The header is copied to *h (the caller's bytes need no alignment).  `stamp`: a format's check that goes
-// between format and header_bytes (which build wrote the image), returning a code.
-template <class H, class Stamp>
-int image_open_front(const char *who, const char *noun, const void *buf, size_t size, uint32_t magic, uint32_t format, H *h, Stamp stamp) {
-  if (!buf) return fail(FSKHIP_E_INVALID, "%s: null snapshot", who);
-  if (size < sizeof(H)) return fail(FSKHIP_E_INVALID, "%s: %zu bytes are fewer than a %s header's %zu", who, size, noun, sizeof(H));
-  std::memcpy(h, buf, sizeof(H));
-  if (h->magic != magic) return fail(FSKHIP_E_INVALID, "%s: not a %s (magic 0x%08x, expected 0x%08x)", who, noun, h->magic, magic);
-  if (h->format != format) return fail(FSKHIP_E_INVALID, "%s: %s format %u, this library reads format %u", who, noun, h->format, format);
-  if (const int rc = stamp()) return rc;
-  if (h->header_bytes != sizeof(H)) return fail(FSKHIP_E_INVALID, "%s: header_bytes %u, expected %zu", who, h->header_bytes, sizeof(H));
-  return FSKHIP_OK;
-}
-template <class H>
-int image_open_front(const char *who, const char *noun, const void *buf, size_t size, uint32_t magic, uint32_t format, H *h) {
-  return image_open_front(who, noun, buf, size, magic, format, h, [] { return (int)FSKHIP_OK; });
-}
-
-// The back, after the format's own geometry checks have vouched for record_bytes: the size is the header and n records
-// (`count_name`: the header's name for n), and the bytes sum to the checksum.  *rec: the first record.
-template <class H>
-int image_open_back(const char *who, const char *count_name, const void *buf, size_t size, const H &h, uint32_t n, const unsigned char **rec) {
-  if (size != sizeof(H) + (size_t)n * h.record_bytes)
-    return fail(FSKHIP_E_INVALID, "%s: %zu bytes do not match %s x record_bytes (%zu + %u x %u)", who, size, count_name, sizeof(H), n, h.record_bytes);
-  *rec = (const unsigned char *)buf + sizeof(H);
-  const uint64_t c = image_checksum(h, *rec, size - sizeof(H));
-  if (c != h.checksum) return fail(FSKHIP_E_INVALID, "%s: checksum %016llx, the bytes sum to %016llx (a damaged snapshot)", who, (unsigned long long)h.checksum, (unsigned long long)c);
-  return FSKHIP_OK;
-}
 
 // what the writers ask of a selection (`noun`: "engine" / "processor", which has n_streams) ...
 inline int check_sel(const char *who, const char *noun, const int64_t *sel, uint32_t n_sel, uint32_t n_streams) {

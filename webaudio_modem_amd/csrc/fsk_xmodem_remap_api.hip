@@ -2,8 +2,9 @@
 // lifecycle calls the engine and the processor row already have -- fskhip_xmodem_{rx,tx,recv}_remap, _snapshot_bytes, _snapshot,
 // _restore, and fskhip_xmodem_snapshot_info_get for all three kinds of image.  A handle's per-stream words and its files (the
 // sender's packed store, the file receiver's rows) move on the device (fsk_xmodem_remap.hip); an image crosses PCIe once.  The
-// image's format and the one definition of a valid image are fsk_xmodem_image.h's (host-only); this file is the format's only
-// writer.  The selection and room checks are fsk_stage.h's, the map's front check the engine remap's (remap_check_map).
+// image's format and the one definition of a valid image are fsk_xmodem_image.h's (host-only, on fsk_image.h's frame); this file is
+// the format's only writer.  The selection and room checks are fsk_stage.h's, the map's front check the engine remap's
+// (remap_check_map), the per-call device scratch fsk_host.h's.
 #include <algorithm>
 #include <vector>
 
@@ -19,26 +20,6 @@
 using namespace fsk;
 
 namespace {
-
-// device scratch of one call, freed when the call returns (after the device has been synchronised)
-struct Scratch {
-  std::vector<void *> bufs;
-  ~Scratch() {
-    for (void *b : bufs) (void)hipFree(b);
-  }
-  template <typename T>
-  int alloc(T *&p, size_t n) {
-    const int rc = dev_alloc(p, n);
-    if (rc == FSKHIP_OK) bufs.push_back(p);
-    return rc;
-  }
-  template <typename T>
-  int upload(T *&p, const T *host, size_t n) {
-    if (const int rc = alloc(p, n)) return rc;
-    if (n) HIP_TRY(hipMemcpy(p, host, sizeof(T) * n, hipMemcpyHostToDevice));
-    return FSKHIP_OK;
-  }
-};
 
 // a handle's word arrays in the order of its image record, with what a new stream holds
 XmWords words_of(const fskhip_xmodem_rx *r) {
@@ -88,8 +69,7 @@ int check_remap(const char *who, uint32_t kind, const H *dst, const H *src, cons
 template <class H>
 int check_restore(const char *who, uint32_t kind, const H *dst, const void *buf, size_t size, const int64_t *map, uint32_t n_map, XmImage *im) {
   if (const int rc = remap_check_map(who, "a record of the snapshot", map, n_map)) return rc;
-  char msg[256];
-  if (xm_image_open(buf, size, im, msg, sizeof(msg))) return fail(FSKHIP_E_INVALID, "%s: %s", who, msg);
+  if (const int rc = open_image(who, xm_image_open, buf, size, im)) return rc;
   if (im->h.kind != kind)
     return fail(FSKHIP_E_INVALID, "%s: the snapshot is of kind %u (%s), this handle's is %u (%s)", who, im->h.kind, xm_kind_name(im->h.kind), kind, xm_kind_name(kind));
   for (uint32_t i = 0; i < n_map; i++)
@@ -116,25 +96,20 @@ int finish_snapshot(const char *who, XmImageHeader h, const uint8_t *d_body, voi
   const size_t body = need - sizeof(h);
   HIP_TRY(hipDeviceSynchronize());
   if (body) HIP_TRY_AS(hipMemcpy(out + sizeof(h), d_body, body, hipMemcpyDeviceToHost), who, false, (void)0);
-  SnapSum sum;
-  snap_sum(sum, &h, sizeof(h));   // (checksum field still 0)
-  snap_sum(sum, out + sizeof(h), body);
-  h.checksum = snap_sum_value(sum);
-  std::memcpy(out, &h, sizeof(h));
+  image_seal(h, out, need);
   return FSKHIP_OK;
 }
 
 XmImageHeader header_of(uint32_t kind, uint32_t n, uint32_t param0, uint32_t param1, uint64_t file_bytes) {
-  XmImageHeader h;
-  std::memset(&h, 0, sizeof(h));
-  h.magic = kXmMagic; h.format = kXmFormat; h.header_bytes = sizeof(h); h.kind = kind;
+  XmImageHeader h = image_header<XmImageHeader>(kXmMagic, kXmFormat);
+  h.kind = kind;
   h.n_records = n; h.record_words = xm_record_words(kind); h.param0 = param0; h.param1 = param1; h.file_bytes = file_bytes;
   return h;
 }
 
 // the body of an image on the device, its padding behind the files zeroed
 int alloc_body(Scratch &sc, const XmImageHeader &h, uint8_t *&d_body) {
-  const size_t tb = table_bytes(h), fb = (size_t)xm_round16(h.file_bytes);
+  const size_t tb = table_bytes(h), fb = (size_t)image_round16(h.file_bytes);
   if (const int rc = sc.alloc(d_body, std::max<size_t>(tb + fb, 16))) return rc;
   if (fb != h.file_bytes) HIP_TRY(hipMemset(d_body + tb + h.file_bytes, 0, fb - (size_t)h.file_bytes));
   return FSKHIP_OK;
@@ -165,7 +140,7 @@ int tx_carry(const char *who, fskhip_xmodem_tx *dst, Scratch &sc, const int64_t 
     if (f[i].len) spans.push_back(XmSpan{f[i].at, at, f[i].len});
     at += f[i].len;
   }
-  const size_t cap = std::max<size_t>((size_t)xm_round16(total), 4096);
+  const size_t cap = std::max<size_t>((size_t)image_round16(total), 4096);
   uint8_t *store = nullptr;
   if (const int rc = dev_alloc(store, cap)) return rc;
   XmSpan *d_spans = nullptr;
@@ -230,8 +205,7 @@ extern "C" {
 int fskhip_xmodem_snapshot_info_get(const void *buf, size_t size, fskhip_xmodem_snapshot_info *info) {
   static const char who[] = "fskhip_xmodem_snapshot_info_get";
   XmImage im;
-  char msg[256];
-  if (xm_image_open(buf, size, &im, msg, sizeof(msg))) return fail(FSKHIP_E_INVALID, "%s: %s", who, msg);
+  if (const int rc = open_image(who, xm_image_open, buf, size, &im)) return rc;
   if (!info) return fail(FSKHIP_E_INVALID, "%s: null info", who);
   std::memset(info, 0, sizeof(*info));
   info->kind = im.h.kind; info->n_streams = im.h.n_records; info->param0 = im.h.param0; info->param1 = im.h.param1; info->file_bytes = im.h.file_bytes;
