@@ -828,6 +828,68 @@ int fskhip_processor_process_rate_host(fskhip_processor *p, fskhip_resampler *up
                                        int out_layout, size_t n_out, size_t out_pitch, uint32_t flags);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Rate conversion by a ratio L / M, on the device (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): what puts 44.1 kHz audio -- the
+ * common sound-card and WebAudio AudioContext rate -- in front of an engine that runs at 48 kHz (L / M = 160 / 147) and behind it
+ * (147 / 160).  A converter has an up factor L and a down factor M, coprime, each in 1..256, and n_taps taps c[].  It is FIRFilter
+ * above run over the input zero-stuffed by L with every M-th output kept.  With x_s[m] stream s's input samples counted from the
+ * handle's creation or last reset (samples before 0 are 0.0):
+ *   y_s[j] = f32(sum over k = 0, 1, ... while p + kL < n_taps of c[p + kL] * x_s[m - k]),  p = (jM) mod L,  m = (jM) div L
+ * the k ascending: the FIR's own ascending tap order with the products against stuffed zeros left out.  precision as for
+ * fskhip_fir_create: FSKHIP_PRECISION_F64 rounds every product and sum on its own, FSKHIP_PRECISION_F32 uses fp32 FMAs; either way
+ * the values are fskhip_fir_process_device's of that precision over the zero-stuffed input, column jM, bit for bit (only a zero's
+ * sign may differ).  It is evaluated polyphase: no stuffed zero and no dropped output is ever computed or stored.  Interpolation
+ * wants taps with a gain of L.
+ *
+ * A call takes n_in samples per stream, a multiple of M, and writes n_in / M * L per stream: the output grid is the handle's own,
+ * as the decimator's is, and no per-stream phase exists.  The handle keeps the last ceil((n_taps - 1) / L) inputs of every stream,
+ * so any cut of a stream into calls of whole multiples of M gives the same samples.
+ *
+ * The two directions are named for the side that carries the capture format, not for up or down; either may go either way in rate.
+ *   FSKHIP_RATECVT_CAPTURE   reads a format and layout of fskhip.h (FSKHIP_SAMPLES_*, exact; [n_streams][pitch] or frames
+ *                            [sample][pitch >= n_streams]) and writes float32 rows [n_streams][pitch]: 44.1 kHz in front of the engine.
+ *   FSKHIP_RATECVT_PLAYBACK  reads float32 rows and writes the format and layout (fskhip.h: "The same formats OUT"): the engine's
+ *                            output towards 44.1 kHz.  d_lens as fskhip_resampler_down_device takes it.
+ * Nothing outside the samples of a row, or the n_streams columns of a frame, is written.
+ *
+ * Refusals, FSKHIP_E_INVALID before any device call, in this order.  create: taps or out NULL; n_streams or n_taps 0; a direction
+ * that is neither; up or down outside 1..256; up and down not coprime; an unknown precision; then n_taps > 4096,
+ * FSKHIP_E_UNSUPPORTED as for the FIR.  The capture / playback calls: a NULL handle; an unknown format, then layout; and for a call
+ * with n_in > 0: a NULL buffer; a pitch that is too small (the float side first); a pointer not aligned to its element; then the
+ * wrong call for the handle's direction; an n_in that is no multiple of down.  A refused call leaves the history as it was.
+ * n_in = 0 is FSKHIP_OK and does nothing once the checks that need no samples have passed: handle, format, layout, direction.
+ * (The NULL handle comes first, so without a device -- where create ends in FSKHIP_E_NO_DEVICE -- only create's refusals and the NULL
+ * handle's can be met; tests/test_ratecvt_refusals_cpu.py holds those, tests/test_gpu_ratecvt.py the rest, in this order.)
+ * These handles have no remap, snapshot or restore yet: fskhip_ratecvt_state_get / _set are the by-hand carry.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct fskhip_ratecvt fskhip_ratecvt;
+enum { FSKHIP_RATECVT_CAPTURE = 0, FSKHIP_RATECVT_PLAYBACK = 1 };
+
+int fskhip_ratecvt_create(int device, int direction, uint32_t up, uint32_t down, const double *taps, uint32_t n_taps, uint32_t n_streams,
+                          int precision, fskhip_ratecvt **out);
+int fskhip_ratecvt_destroy(fskhip_ratecvt *r);
+uint32_t fskhip_ratecvt_streams(const fskhip_ratecvt *r);   /* the n_streams it was created for (0 for NULL) */
+uint32_t fskhip_ratecvt_history(const fskhip_ratecvt *r);   /* floats of history per stream (0 for NULL) */
+/* history to zero for one stream, or all when stream < 0 */
+int fskhip_ratecvt_reset(fskhip_ratecvt *r, int64_t stream);
+/* capture: n_in samples per stream at d_src -> n_in / down * up floats per stream at d_dst.  Asynchronous on hip_stream. */
+int fskhip_ratecvt_capture_device(fskhip_ratecvt *r, const void *d_src, int format, int layout, size_t n_in, size_t src_pitch,
+                                  float *d_dst, size_t dst_pitch, void *hip_stream);
+/* playback: n_in floats per stream at d_src -> n_in / down * up samples per stream at d_dst.  d_lens (device, n_streams words; may
+ * be NULL): input element t >= d_lens[s] of stream s reads as 0.0f whatever the row holds there -- also in the history the call
+ * leaves --, so a ragged batch rings out and ends in the format's silence.  Asynchronous on hip_stream. */
+int fskhip_ratecvt_playback_device(fskhip_ratecvt *r, const float *d_src, size_t n_in, size_t src_pitch, const uint32_t *d_lens,
+                                   void *d_dst, int format, int layout, size_t dst_pitch, void *hip_stream);
+/* the same with host buffers (lens too), through the handle's own staging slabs and stream; synchronous */
+int fskhip_ratecvt_capture_host(fskhip_ratecvt *r, const void *src, int format, int layout, size_t n_in, size_t src_pitch, float *dst,
+                                size_t dst_pitch);
+int fskhip_ratecvt_playback_host(fskhip_ratecvt *r, const float *src, size_t n_in, size_t src_pitch, const uint32_t *lens, void *dst,
+                                 int format, int layout, size_t dst_pitch);
+/* the history rows, [n_streams][fskhip_ratecvt_history()] floats on the host, oldest first (get, permute the rows, set on a handle
+ * of the same direction, ratio and taps).  Synchronous; nothing is copied when the history is empty. */
+int fskhip_ratecvt_state_get(fskhip_ratecvt *r, float *state);
+int fskhip_ratecvt_state_set(fskhip_ratecvt *r, const float *state);
+
+/* ---------------------------------------------------------------------------------------------------
  * IIR half of src/dsp/filters.ts: IIRFilter (8-106) batched over streams, + FilterFactory.createIIR* (325-344; the
  * designs themselves are fskhip_butterworth_* in fskhip.h).  Inside the demodulator the same filter lives as three
  * hard-wired biquads; this is the generic class: Direct Form I of any order <= 8.

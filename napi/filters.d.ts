@@ -54,6 +54,38 @@ export declare class Downsampler extends Resampler {
   /** input: [nStreams][n], n a multiple of factor; returns [nStreams][n / factor] or frames [n / factor][nStreams] */
   process(input: Float32Array, format: SampleFormat, layout?: SampleLayout, lens?: Uint32Array | null): Float32Array | Int16Array | Uint8Array;
 }
+export interface RateConverterOptions { taps?: number[]; device?: number; precision?: 0 | 1 }
+/** Rate conversion by a ratio up / down on the GPU (fskhip_ratecvt_*): inRate -> outRate, the rates over their gcd; the history is carried across calls. */
+declare class RateConverter {
+  static ratio(inRate: number, outRate: number): { up: number; down: number };
+  static defaultTaps(inRate: number, outRate: number): number[];
+  readonly inRate: number;
+  readonly outRate: number;
+  readonly up: number;
+  readonly down: number;
+  readonly nStreams: number;
+  readonly taps: number[];
+  readonly history: number;
+  /** samples per stream a call with nIn per stream (a multiple of down) gives */
+  outCount(nIn: number): number;
+  reset(stream?: number): void;
+  /** the history rows, [nStreams][history], oldest first */
+  state(): Float32Array;
+  setState(state: Float32Array): void;
+  close(): void;
+}
+export declare class CaptureConverter extends RateConverter {
+  constructor(inRate: number, outRate: number, nStreams: number, options?: RateConverterOptions);
+  /** samples: [nStreams][pitch] or frames [nIn][pitch], nIn a multiple of down; returns [nStreams][nIn / down * up] */
+  process(samples: Float32Array | Int16Array | Uint8Array, format: SampleFormat, layout?: SampleLayout, nIn?: number, pitch?: number): Float32Array;
+}
+export declare class PlaybackConverter extends RateConverter {
+  constructor(inRate: number, outRate: number, nStreams: number, options?: RateConverterOptions);
+  /** input: [nStreams][n], n a multiple of down; returns [nStreams][n / down * up] or frames [n / down * up][nStreams] */
+  process(input: Float32Array, format: SampleFormat, layout?: SampleLayout, lens?: Uint32Array | null): Float32Array | Int16Array | Uint8Array;
+  /** output samples that can be non-zero for a signal of n input samples */
+  outLength(n: number): number;
+}
 export declare class FilterFactory {
   static createFIRLowpass(cutoffFreq: number, sampleRate: number, numTaps?: number): FIRFilter;
   static createFIRHighpass(cutoffFreq: number, sampleRate: number, numTaps?: number): FIRFilter;

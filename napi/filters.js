@@ -134,6 +134,65 @@ class Downsampler extends Resampler {
   }
 }
 
+// Rate conversion by a ratio up / down on the GPU (include/fskhip_next.h: fskhip_ratecvt_*): 44.1 kHz audio either side of a 48 kHz
+// engine.  inRate -> outRate, the rates over their gcd (up and down each at most 256); a call takes a multiple of `down` samples
+// per stream and gives n / down * up, the history carried across calls.  Without taps the design is sincLowpass(0.45 * min(inRate,
+// outRate), up * inRate, 16 * max(up, down) + 1) times up: 2 561 taps and 19 845 Hz between 44.1 and 48 kHz.
+function gcd(a, b) { while (b) { const t = a % b; a = b; b = t; } return a; }
+class RateConverter {
+  static ratio(inRate, outRate) {
+    if (!(Number.isInteger(inRate) && Number.isInteger(outRate) && inRate >= 1 && outRate >= 1)) {
+      throw new RangeError('rates must be positive whole numbers, got ' + inRate + ' and ' + outRate);
+    }
+    const g = gcd(inRate, outRate);
+    return { up: outRate / g, down: inRate / g };
+  }
+  static defaultTaps(inRate, outRate) {
+    const { up, down } = this.ratio(inRate, outRate), n = 16 * Math.max(up, down) + 1;
+    if (n > 4096) throw new RangeError('the default design for ' + up + ' / ' + down + ' needs ' + n + ' taps, the limit is 4096');
+    return FilterDesign.sincLowpass(0.45 * Math.min(inRate, outRate), up * inRate, n).map((t) => t * up);
+  }
+  constructor(direction, inRate, outRate, nStreams, options = {}) {
+    const { up, down } = RateConverter.ratio(inRate, outRate);
+    this.inRate = inRate; this.outRate = outRate; this.up = up; this.down = down;
+    this.nStreams = nStreams;
+    this.taps = [...(options.taps || RateConverter.defaultTaps(inRate, outRate))];
+    this.handle = addon.ratecvtCreate(direction, up, down, Float64Array.from(this.taps), nStreams, options.device || 0,
+      options.precision === undefined ? PRECISION_F32 : options.precision);
+    this.history = addon.ratecvtHistory(this.handle);
+  }
+  outCount(nIn) { return Math.floor(nIn / this.down) * this.up; }
+  reset(stream = -1) { addon.ratecvtReset(this.handle, stream); }
+  state() { return addon.ratecvtState(this.handle); }               // Float32Array [nStreams][history], oldest first
+  setState(state) { addon.ratecvtSetState(this.handle, state); }
+  close() { if (this.handle) { addon.ratecvtDestroy(this.handle); this.handle = null; } }
+}
+class CaptureConverter extends RateConverter {
+  constructor(inRate, outRate, nStreams, options = {}) { super(0, inRate, outRate, nStreams, options); }
+  // samples: the format's typed array, [nStreams][pitch] (layout 'stream') or frames [nIn][pitch >= nStreams] ('sample'); nIn (a
+  // multiple of down) and pitch default to a packed array's -> Float32Array [nStreams][nIn / down * up]
+  process(samples, format, layout = 'stream', nIn, pitch) {
+    const f = sampleFormat(format), l = sampleLayout(layout);
+    if (!(samples instanceof SAMPLE_TYPES[f])) throw new TypeError('format ' + format + ' takes a ' + SAMPLE_TYPES[f].name);
+    const n = nIn === undefined ? samplesPerStream(samples, this.nStreams) : nIn;
+    if (n === 0) return new Float32Array(0);
+    return addon.ratecvtCapture(this.handle, samples, f, l, n, pitch === undefined ? (l === 1 ? this.nStreams : n) : pitch, this.outCount(n));
+  }
+}
+class PlaybackConverter extends RateConverter {
+  constructor(inRate, outRate, nStreams, options = {}) { super(1, inRate, outRate, nStreams, options); }
+  // input: Float32Array [nStreams][n], n a multiple of down; lens (Uint32Array or null): stream s reads as 0.0 from lens[s] on
+  // -> the format's typed array, [nStreams][n / down * up] or frames [n / down * up][nStreams]
+  process(input, format, layout = 'stream', lens = null) {
+    const f = sampleFormat(format), l = sampleLayout(layout);
+    const n = samplesPerStream(input, this.nStreams);
+    if (n === 0) return new SAMPLE_TYPES[f](0);
+    return addon.ratecvtPlayback(this.handle, input, n, lens, f, l, this.outCount(n));
+  }
+  // output samples that can be non-zero for a signal of n input samples
+  outLength(n) { return n ? Math.floor(((n - 1) * this.up + this.taps.length - 1) / this.down) + 1 : 0; }
+}
+
 class IIRFilterBatch {                            // filters.ts:8-106, S streams per call
   constructor(b, a, nStreams = 1, options = {}) {
     // the constructor's three errors (filters.ts:19-21), before anything touches the GPU
@@ -177,4 +236,4 @@ class FilterFactory {                             // filters.ts:325-368
   static createFIRHighpass(cutoffFreq, sampleRate, numTaps = 51) { return new FIRFilter(FilterDesign.sincHighpass(cutoffFreq, sampleRate, numTaps)); }
   static createFIRBandpass(centerFreq, bandwidth, sampleRate, numTaps = 51) { return new FIRFilter(FilterDesign.sincBandpass(centerFreq, bandwidth, sampleRate, numTaps)); }
 }
-module.exports = { FilterDesign, IIRFilter, IIRFilterBatch, FIRFilter, FIRFilterBatch, Upsampler, Downsampler, resamplerSnapshotInfo, FilterFactory, PRECISION_F32, PRECISION_F64 };
+module.exports = { FilterDesign, IIRFilter, IIRFilterBatch, FIRFilter, FIRFilterBatch, Upsampler, Downsampler, CaptureConverter, PlaybackConverter, resamplerSnapshotInfo, FilterFactory, PRECISION_F32, PRECISION_F64 };

@@ -44,6 +44,10 @@
 //   resamplerRemap(handle, map: number[]) -> handle;  resamplerSnapshot(handle, streams: number[]|null) -> Buffer
 //   resamplerRestore(snapshot: Uint8Array, map: number[]|null, device) -> handle
 //   resamplerSnapshotInfo(snapshot) -> {nStreams, direction, factor, nTaps, precision, history, taps: Float64Array}
+//   ratecvtCreate(direction, up, down, taps: Float64Array, nStreams, device, precision) -> handle;  ratecvtDestroy(handle);  ratecvtHistory(handle)
+//   ratecvtCapture(handle, samples, format, layout, nIn, pitch, nOut) -> Float32Array [S][nOut]
+//   ratecvtPlayback(handle, input: Float32Array [S][nIn], nIn, lens: Uint32Array|null, format, layout, nOut) -> the format's typed array
+//   ratecvtReset(handle, stream);  ratecvtState(handle) -> Float32Array [S][history];  ratecvtSetState(handle, Float32Array)
 //   iirCreate(b, a: Float64Array, nStreams, device, precision) -> handle; iirProcess(handle, Float32Array | Float64Array, n, pitch, nStreams);
 //   iirCoefficients(handle), iirReset(handle, stream), iirDestroy(handle); butterworth(kind, f, bandwidth, sampleRate) -> [b0 b1 b2 a0 a1 a2]
 #include <cstring>
@@ -56,12 +60,13 @@ namespace {
 
 // FIR / IIR filter and resampler handles: the external owns a box, so that close() can empty it (a later call throws instead of
 // touching freed memory) and a filter that is never close()d is destroyed when the garbage collector drops the handle
-enum { BOX_FIR = 0, BOX_IIR = 1, BOX_RESAMPLER = 2 };
+enum { BOX_FIR = 0, BOX_IIR = 1, BOX_RESAMPLER = 2, BOX_RATECVT = 3 };
 struct FilterBox { void *p; int kind; };
 void filter_box_destroy(FilterBox *b) {
   if (!b->p) return;
   if (b->kind == BOX_IIR) fskhip_iir_destroy((fskhip_iir *)b->p);
   else if (b->kind == BOX_RESAMPLER) fskhip_resampler_destroy((fskhip_resampler *)b->p);
+  else if (b->kind == BOX_RATECVT) fskhip_ratecvt_destroy((fskhip_ratecvt *)b->p);
   else fskhip_fir_destroy((fskhip_fir *)b->p);
   b->p = nullptr;
 }
@@ -1061,6 +1066,106 @@ napi_value ResamplerSetState(napi_env env, napi_callback_info info) {
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   return nullptr;
 }
+// ---- rate conversion by a ratio (include/fskhip_next.h: fskhip_ratecvt_*) ----
+fskhip_ratecvt *ratecvt_of(napi_env env, napi_value v) {
+  FilterBox *b = (FilterBox *)external(env, v, "filter destroyed");
+  if (!b) return nullptr;
+  if (!b->p) { napi_throw_error(env, nullptr, "filter destroyed"); return nullptr; }
+  if (b->kind != BOX_RATECVT) { napi_throw_type_error(env, nullptr, "not a rate converter handle"); return nullptr; }
+  return (fskhip_ratecvt *)b->p;
+}
+napi_value RatecvtCreate(napi_env env, napi_callback_info info) {   // (direction, up, down, taps: Float64Array, nStreams, device, precision)
+  ARGS(7);
+  void *taps; size_t nt;
+  if (!typed(env, argv[3], napi_float64_array, &taps, &nt)) return nullptr;
+  fskhip_ratecvt *r = nullptr;
+  int rc = fskhip_ratecvt_create(i32(env, argv[5]), i32(env, argv[0]), u32(env, argv[1]), u32(env, argv[2]), (const double *)taps, (uint32_t)nt,
+                                 u32(env, argv[4]), i32(env, argv[6]), &r);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return filter_box_new(env, r, BOX_RATECVT);
+}
+napi_value RatecvtDestroy(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  filter_box_close(env, argv[0]);
+  return nullptr;
+}
+napi_value RatecvtHistory(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
+  if (!r) return nullptr;
+  napi_value v;
+  NAPI_OK(napi_create_uint32(env, fskhip_ratecvt_history(r), &v));
+  return v;
+}
+// (handle, samples in the format's typed array, format, layout, nIn, pitch, nOut = nIn / down * up) -> Float32Array [S][nOut]
+napi_value RatecvtCapture(napi_env env, napi_callback_info info) {
+  ARGS(7);
+  const int32_t format = i32(env, argv[2]), layout = i32(env, argv[3]);
+  if (!sample_format_ok(env, format, layout)) return nullptr;
+  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
+  if (!r) return nullptr;
+  void *in; size_t ilen;
+  if (!typed(env, argv[1], sample_array_type(format), &in, &ilen)) return nullptr;
+  const uint32_t n = u32(env, argv[4]), pitch = u32(env, argv[5]), n_out = u32(env, argv[6]), S = fskhip_ratecvt_streams(r);
+  const int64_t need = samples_needed(layout, S, n, pitch);
+  if (need < 0 || (size_t)need > ilen) { napi_throw_range_error(env, nullptr, "input too short"); return nullptr; }
+  void *out;
+  napi_value out_v = make_typed(env, napi_float32_array, (size_t)n_out * S, 4, &out);
+  if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  int rc = fskhip_ratecvt_capture_host(r, in, format, layout, n, pitch, (float *)out, n_out ? n_out : 1);   // (the library holds n_out to its own count)
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return out_v;
+}
+// (handle, input: Float32Array [S][nIn], nIn, lens: Uint32Array|null, format, layout, nOut = nIn / down * up) -> the format's typed array, packed
+napi_value RatecvtPlayback(napi_env env, napi_callback_info info) {
+  ARGS(7);
+  const int32_t format = i32(env, argv[4]), layout = i32(env, argv[5]);
+  if (!sample_format_ok(env, format, layout)) return nullptr;
+  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
+  if (!r) return nullptr;
+  void *in, *lens; size_t ilen, llen;
+  if (!typed(env, argv[1], napi_float32_array, &in, &ilen) || !typed(env, argv[3], napi_uint32_array, &lens, &llen, true)) return nullptr;
+  const uint32_t n = u32(env, argv[2]), n_out = u32(env, argv[6]), S = fskhip_ratecvt_streams(r);
+  if ((size_t)n * S > ilen || (lens && llen < S)) { napi_throw_range_error(env, nullptr, "arguments too short"); return nullptr; }
+  const size_t pitch = layout == FSKHIP_LAYOUT_SAMPLE_MAJOR ? S : n_out;
+  void *out;
+  napi_value out_v = make_typed(env, sample_array_type(format), (size_t)n_out * S, fskhip_sample_bytes(format), &out);
+  if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
+  int rc = fskhip_ratecvt_playback_host(r, (const float *)in, n, n, (const uint32_t *)lens, out, format, layout, pitch ? pitch : 1);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return out_v;
+}
+napi_value RatecvtReset(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
+  if (!r) return nullptr;
+  int64_t s = -1;
+  napi_get_value_int64(env, argv[1], &s);
+  int rc = fskhip_ratecvt_reset(r, s);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+napi_value RatecvtState(napi_env env, napi_callback_info info) {   // -> Float32Array [S][history]
+  ARGS(1);
+  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
+  if (!r) return nullptr;
+  void *out;
+  napi_value out_v = make_typed(env, napi_float32_array, (size_t)fskhip_ratecvt_streams(r) * fskhip_ratecvt_history(r), 4, &out);
+  int rc = fskhip_ratecvt_state_get(r, (float *)out);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return out_v;
+}
+napi_value RatecvtSetState(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
+  if (!r) return nullptr;
+  void *st; size_t n;
+  if (!typed(env, argv[1], napi_float32_array, &st, &n)) return nullptr;
+  if (n != (size_t)fskhip_ratecvt_streams(r) * fskhip_ratecvt_history(r)) { napi_throw_range_error(env, nullptr, "state must be [nStreams][history]"); return nullptr; }
+  int rc = fskhip_ratecvt_state_set(r, (const float *)st);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
 // ---- a resampler through remap / snapshot / restore (fskhip_resampler_remap ...): remap and restore return a NEW handle
 napi_value ResamplerRemap(napi_env env, napi_callback_info info) {   // (handle, map: number[]) -> handle
   ARGS(2);
@@ -1279,6 +1384,14 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"resamplerSnapshot", nullptr, ResamplerSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"resamplerRestore", nullptr, ResamplerRestore, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"resamplerSnapshotInfo", nullptr, ResamplerSnapshotInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtCreate", nullptr, RatecvtCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtDestroy", nullptr, RatecvtDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtHistory", nullptr, RatecvtHistory, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtCapture", nullptr, RatecvtCapture, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtPlayback", nullptr, RatecvtPlayback, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtReset", nullptr, RatecvtReset, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtState", nullptr, RatecvtState, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtSetState", nullptr, RatecvtSetState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirCreate", nullptr, IirCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirDestroy", nullptr, IirDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirCoefficients", nullptr, IirCoefficients, nullptr, nullptr, nullptr, napi_default, nullptr},

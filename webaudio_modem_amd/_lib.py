@@ -23,6 +23,7 @@ DEMOD_WRITEBACK_AGC = 1
 SAMPLES_F32, SAMPLES_S16, SAMPLES_MULAW, SAMPLES_ALAW = 0, 1, 2, 3
 LAYOUT_STREAM_MAJOR, LAYOUT_SAMPLE_MAJOR = 0, 1
 RESAMPLE_UP, RESAMPLE_DOWN = 0, 1
+RATECVT_CAPTURE, RATECVT_PLAYBACK = 0, 1
 
 
 class Config(C.Structure):
@@ -260,6 +261,17 @@ _SYMBOLS = [
     ("fskhip_resampler_snapshot_info_get", C.c_int, [_P, C.c_size_t, C.POINTER(ResamplerSnapshotInfo)]),
     ("fskhip_processor_process_rate_device", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, _P]),
     ("fskhip_processor_process_rate_host", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32]),
+    ("fskhip_ratecvt_create", C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P)]),
+    ("fskhip_ratecvt_destroy", C.c_int, [_P]),
+    ("fskhip_ratecvt_streams", C.c_uint32, [_P]),
+    ("fskhip_ratecvt_history", C.c_uint32, [_P]),
+    ("fskhip_ratecvt_reset", C.c_int, [_P, C.c_int64]),
+    ("fskhip_ratecvt_capture_device", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P]),
+    ("fskhip_ratecvt_playback_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P, C.c_int, C.c_int, C.c_size_t, _P]),
+    ("fskhip_ratecvt_capture_host", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_size_t]),
+    ("fskhip_ratecvt_playback_host", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P, C.c_int, C.c_int, C.c_size_t]),
+    ("fskhip_ratecvt_state_get", C.c_int, [_P, _P]),
+    ("fskhip_ratecvt_state_set", C.c_int, [_P, _P]),
     ("fskhip_iir_create", C.c_int, [C.c_int, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P)]),
     ("fskhip_iir_destroy", C.c_int, [_P]),
     ("fskhip_iir_get_coefficients", C.c_int, [_P, _P, C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint32)]),

@@ -49,6 +49,11 @@ inline int filter_reset_begin(const FilterHost *f, int64_t stream) {
   return FSKHIP_OK;
 }
 
+// rows x cols elements of esz bytes between the host and a device slab whose rows are padded to whole 16-byte vectors: what the
+// _host calls of the rate converters (fsk_resample.hip, fsk_ratecvt.hip) stage a format's samples through
+struct Slab { size_t rows, cols, esz, pitch; size_t bytes() const { return rows * pitch * esz; } };
+inline Slab slab(size_t rows, size_t cols, size_t esz) { return {rows, cols, esz, (cols * esz + 15u) / 16u * 16u / esz}; }
+
 // A _host call: S rows of n elements from `in` to the device (rows padded to whole 16-byte vectors), device(d_in, d_out, pitch,
 // stream) -- the filter's _device entry point on the handle's stream --, S rows back to `out`.  Pitches in elements; the two
 // texts are the entry point's refusals of a null buffer and of a pitch below n.  Synchronous.

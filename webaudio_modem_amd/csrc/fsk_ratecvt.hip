@@ -1,0 +1,340 @@
+// fsk_ratecvt.hip -- rate conversion by a ratio L / M on the device (include/fskhip_next.h: fskhip_ratecvt_*): 44.1 kHz audio in
+// front of and behind an engine at 48 kHz.  The reference's FIRFilter (src/dsp/filters.ts:112-167) over the input zero-stuffed by L
+// with every M-th output kept, evaluated polyphase -- neither a stuffed zero nor a dropped output is ever made.  One side is in a
+// capture format and layout (fsk_samples_dev.h), the other the float32 [stream][pitch] rows of the engine.  Every output
+// accumulates its products in the FIR's order (ascending tap index, `mac`), so the results are fsk_fir.hip's bit for bit; a
+// skipped product with a stuffed zero can only change a zero's sign.
+//
+// The arithmetic of periods, rows, workgroups and LDS is fsk_ratecvt_plan.h's.  A workgroup stages the decoded inputs of its
+// periods and the history in front of them in LDS, and writes the handle's next history from what it staged (each entry by the one
+// workgroup that owns the sample; the two history buffers ping-pong as fskhip_resampler's do).  A lane owns the same place q of
+// four periods, one per row: consecutive lanes hold consecutive outputs, so they differ in phase -- the taps lie in output order,
+// [k][q], and a wave reads consecutive words of them, once for its four rows -- and their inputs x[m - k] are the same or the next
+// LDS word where L > M, at most ceil(M / L) apart otherwise.  PLAYBACK in sample-major layout leaves through a [outputs][ns + 1]
+// tile.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <new>
+#include <vector>
+
+#include "fsk_filter_host.h"
+#include "fsk_history_host.h"
+#include "fsk_launch.h"
+#include "fsk_mac_dev.h"
+#include "fsk_ratecvt_plan.h"
+#include "fsk_samples_dev.h"
+
+struct fskhip_ratecvt : fsk::FilterHost {
+  int direction = 0;
+  uint32_t L = 1, M = 1, n_taps = 0, H = 0;   // H: floats of history per stream (ratecvt_history)
+  double *d_taps = nullptr;                    // fp64 path: [K][L] in output order (fsk_ratecvt_plan.h)
+  float *d_taps32 = nullptr;                   // the same, rounded once on the host (fp32 path)
+  uint32_t *d_table = nullptr;                 // [L]: ratecvt_table_word
+  float *hist[2] = {nullptr, nullptr};         // ping-pong: [cur] is read by the next call
+  int cur = 0;
+  uint32_t *d_lens = nullptr;                  // the _host form's per-stream lengths
+};
+
+namespace fsk {
+namespace {
+
+struct RatecvtShape { uint32_t hist, G, rows, log2_ns, x_pitch, row_stride, span, seg_periods, split; };   // (RatecvtPlan's, as the kernels take it)
+
+// one signature for both directions: CAPTURE reads `src` in the format and writes float rows, PLAYBACK the other way round;
+// n_in = inputs per stream (a multiple of M); d_lens is PLAYBACK's
+#define FSK_RATECVT_PARAMS                                                                                                       \
+  const void *__restrict__ src_, size_t src_pitch, const uint32_t *__restrict__ d_lens, void *__restrict__ dst_, size_t dst_pitch, \
+      const float *__restrict__ hist_in, float *__restrict__ hist_out, const void *__restrict__ taps_, const uint32_t *__restrict__ table, \
+      uint32_t n_streams, size_t n_in, uint32_t L, uint32_t M, uint32_t n_taps, RatecvtShape G
+#define FSK_RATECVT_ARGS src_, src_pitch, d_lens, dst_, dst_pitch, hist_in, hist_out, taps_, table, n_streams, n_in, L, M, n_taps, G
+
+template <typename Real, int FMT, int LAYOUT, int DIR>
+__device__ __forceinline__ void ratecvt_body(FSK_RATECVT_PARAMS) {
+  using F = SampleFmt<FMT>;
+  constexpr bool kRows = LAYOUT == FSKHIP_LAYOUT_STREAM_MAJOR, kPlay = DIR == FSKHIP_RATECVT_PLAYBACK;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  float *const xs = reinterpret_cast<float *>(lds_raw);                 // [ns][x_pitch]: hist floats of history, then the periods' inputs
+  const Real *const taps = (const Real *)taps_;                          // [K][L]
+  const uint32_t tid = threadIdx.x;
+  const uint32_t H = G.hist, span = G.span, ns = 1u << G.log2_ns;
+  uint32_t *const tile = reinterpret_cast<uint32_t *>(xs + (size_t)ns * G.x_pitch);   // [G L][ns + 1] (PLAYBACK, sample-major)
+  const uint32_t hi = blockIdx.x / G.split, lo = blockIdx.x - hi * G.split;
+  const uint32_t s0 = kRows ? hi : lo << G.log2_ns;
+  const size_t per0 = (size_t)(kRows ? lo : hi) * G.seg_periods;        // the workgroup's first period
+  const size_t m0 = per0 * M, j0 = per0 * L, n_out = n_in / M * L;
+
+  // input i of the staged span of stream s0 + c; `len`: inputs from there on read as 0.0f
+  auto stage = [&](uint32_t c, uint32_t i, size_t len) {
+    const uint32_t s = s0 + c;
+    const int64_t m = (int64_t)m0 + (int64_t)i - (int64_t)H;
+    float v = 0.0f;
+    if (s < n_streams) {
+      if (m >= 0) {
+        if ((size_t)m < len) {
+          if constexpr (kPlay) v = ((const float *)src_)[(size_t)s * src_pitch + (size_t)m];
+          else v = F::decode(((const typename F::T *)src_)[kRows ? (size_t)s * src_pitch + (size_t)m : (size_t)m * src_pitch + s]);
+        }
+      } else {
+        v = hist_in[(size_t)s * H + (size_t)(m + (int64_t)H)];
+      }
+      // the history after the call: the last H samples, each written by the workgroup whose periods hold it (the first
+      // workgroup's for what stays of the old history)
+      const int64_t h = m + (int64_t)H - (int64_t)n_in;
+      if ((i >= H || m0 == 0) && h >= 0 && m < (int64_t)n_in) hist_out[(size_t)s * H + (size_t)h] = v;
+    }
+    xs[c * G.x_pitch + i] = v;
+  };
+  if constexpr (kRows || kPlay) {                                        // the staged side lies stream by stream
+    for (uint32_t c = 0; c < ns; c++) {
+      size_t len = n_in;
+      if (kPlay && d_lens && s0 + c < n_streams) len = d_lens[s0 + c] < n_in ? (size_t)d_lens[s0 + c] : n_in;
+      for (uint32_t i = tid; i < span; i += kResampleThreads) stage(c, i, len);
+    }
+  } else {                                                               // frames: consecutive lanes take a frame's streams
+    for (uint32_t idx = tid; idx < (span << G.log2_ns); idx += kResampleThreads) stage(idx & (ns - 1u), idx >> G.log2_ns, n_in);
+  }
+  __syncthreads();
+
+  // item w: place u = w % (G L) of the rows 4 (w / (G L)) .. + 3.  Row r is block r of the stream (stream-major; output
+  // j0 + r G L + u) or stream s0 + r (sample-major; output j0 + u); its inputs start r * row_stride floats into xs.
+  const uint32_t Qs = G.G * L, n_quads = (G.rows + 3u) / 4u;
+  const uint32_t k_full = n_taps / L, rem = n_taps - k_full * L;        // phase p has k_full + (p < rem) taps
+  for (uint32_t w = tid; w < n_quads * Qs; w += kResampleThreads) {
+    const uint32_t quad = w / Qs, u = w - quad * Qs;
+    const uint32_t per = u / L, q = u - per * L;
+    const uint32_t word = table[q], p = word >> 16;
+    const uint32_t x0 = H + per * M + (word & 0xFFFFu);                  // x[m] of row 0 of the stream's span; x[m - k]: k <= H
+    uint32_t xb[4];
+#pragma unroll
+    for (uint32_t r = 0; r < 4u; r++) {
+      const uint32_t row = quad * 4u + r < G.rows ? quad * 4u + r : quad * 4u;   // (a row past the last computes the quad's first again, unused)
+      xb[r] = row * G.row_stride + x0;
+    }
+    Real acc[4] = {0, 0, 0, 0};
+    const Real *tp = taps + q;
+#pragma unroll 4
+    for (uint32_t k = 0; k < k_full; k++) {
+      const Real cc = tp[(size_t)k * L];
+#pragma unroll
+      for (uint32_t r = 0; r < 4u; r++) acc[r] = mac(acc[r], cc, xs[xb[r] - k]);
+    }
+    if (p < rem) {
+      const Real cc = tp[(size_t)k_full * L];
+#pragma unroll
+      for (uint32_t r = 0; r < 4u; r++) acc[r] = mac(acc[r], cc, xs[xb[r] - k_full]);
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < 4u; r++) {
+      const uint32_t row = quad * 4u + r;
+      if (row >= G.rows) continue;
+      const size_t j = j0 + (kRows ? (size_t)row * Qs : 0u) + u;
+      const uint32_t s = kRows ? s0 : s0 + row;
+      if (j >= n_out || s >= n_streams) continue;
+      if constexpr (!kPlay) {
+        ((float *)dst_)[(size_t)s * dst_pitch + j] = (float)acc[r];
+      } else if constexpr (kRows) {
+        ((typename F::Bits *)dst_)[(size_t)s * dst_pitch + j] = (typename F::Bits)F::encode((float)acc[r]);
+      } else {
+        tile[u * (ns + 1u) + row] = F::encode((float)acc[r]);
+      }
+    }
+  }
+  if constexpr (kPlay && !kRows) {
+    __syncthreads();
+    for (uint32_t idx = tid; idx < (Qs << G.log2_ns); idx += kResampleThreads) {
+      const uint32_t c = idx & (ns - 1u), u = idx >> G.log2_ns;
+      if (s0 + c < n_streams && j0 + u < n_out) ((typename F::Bits *)dst_)[(j0 + u) * dst_pitch + s0 + c] = (typename F::Bits)tile[u * (ns + 1u) + c];
+    }
+  }
+}
+
+template <typename Real, int FMT, int LAYOUT>
+__global__ __launch_bounds__(kResampleThreads) void ratecvt_capture_kernel(FSK_RATECVT_PARAMS) {
+  ratecvt_body<Real, FMT, LAYOUT, FSKHIP_RATECVT_CAPTURE>(FSK_RATECVT_ARGS);
+}
+
+template <typename Real, int FMT, int LAYOUT>
+__global__ __launch_bounds__(kResampleThreads) void ratecvt_playback_kernel(FSK_RATECVT_PARAMS) {
+  ratecvt_body<Real, FMT, LAYOUT, FSKHIP_RATECVT_PLAYBACK>(FSK_RATECVT_ARGS);
+}
+
+// every instantiation, once: [direction][precision][format][layout], in the order of the headers' enums
+using RatecvtFn = void (*)(const void *, size_t, const uint32_t *, void *, size_t, const float *, float *, const void *, const uint32_t *, uint32_t, size_t, uint32_t,
+                           uint32_t, uint32_t, RatecvtShape);
+#define FSK_RATECVT_FORMATS(K, R)                                                                                                     \
+  {{FSK_K(K, R, FSKHIP_SAMPLES_F32, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_F32, FSKHIP_LAYOUT_SAMPLE_MAJOR)},       \
+   {FSK_K(K, R, FSKHIP_SAMPLES_S16, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_S16, FSKHIP_LAYOUT_SAMPLE_MAJOR)},       \
+   {FSK_K(K, R, FSKHIP_SAMPLES_MULAW, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_MULAW, FSKHIP_LAYOUT_SAMPLE_MAJOR)},   \
+   {FSK_K(K, R, FSKHIP_SAMPLES_ALAW, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_ALAW, FSKHIP_LAYOUT_SAMPLE_MAJOR)}}
+const KernelEntry<RatecvtFn> kRatecvtKernels[2][2][4][2] = {
+    {FSK_RATECVT_FORMATS(ratecvt_capture_kernel, float), FSK_RATECVT_FORMATS(ratecvt_capture_kernel, double)},
+    {FSK_RATECVT_FORMATS(ratecvt_playback_kernel, float), FSK_RATECVT_FORMATS(ratecvt_playback_kernel, double)}};
+
+}  // namespace
+}  // namespace fsk
+
+using namespace fsk;
+
+namespace {
+
+// What the four process entry points refuse, in the header's order, behind the null handle: format and layout; then, for a call
+// that has samples, null buffers, pitches and alignments; the handle's direction; an n_in that is no multiple of the down factor.
+// `narrow` is the side in the format, `wide` the float rows; pitches in elements.
+int check_call(const fskhip_ratecvt *r, const char *who, int direction, int format, int layout, size_t n_in, const void *narrow, size_t narrow_pitch,
+               const float *wide, size_t wide_pitch, const uint32_t *lens) {
+  if (!r) return fail(FSKHIP_E_INVALID, "null rate converter");
+  if (const int rc = check_sample_format(who, format, layout)) return rc;
+  if (n_in > 0) {
+    const size_t n_out = n_in / r->M * r->L;   // (of a call that passes the last check)
+    const size_t n_narrow = direction == FSKHIP_RATECVT_CAPTURE ? n_in : n_out, n_wide = direction == FSKHIP_RATECVT_CAPTURE ? n_out : n_in;
+    if (!narrow || !wide) return fail(FSKHIP_E_INVALID, "%s: null buffer", who);
+    if (wide_pitch < n_wide) return fail(FSKHIP_E_INVALID, "%s: float pitch %zu < %zu samples per stream", who, wide_pitch, n_wide);
+    if (layout == FSKHIP_LAYOUT_STREAM_MAJOR && narrow_pitch < n_narrow)
+      return fail(FSKHIP_E_INVALID, "%s: sample pitch %zu < %zu samples per stream", who, narrow_pitch, n_narrow);
+    if (layout == FSKHIP_LAYOUT_SAMPLE_MAJOR && narrow_pitch < r->S) return fail(FSKHIP_E_INVALID, "%s: frame pitch %zu < n_streams %u", who, narrow_pitch, r->S);
+    if ((reinterpret_cast<uintptr_t>(wide) & 3u) != 0 || (reinterpret_cast<uintptr_t>(lens) & 3u) != 0 ||
+        (reinterpret_cast<uintptr_t>(narrow) & (sample_bytes(format) - 1u)) != 0)
+      return fail(FSKHIP_E_INVALID, "%s: a buffer is not aligned to its element size", who);
+  }
+  if (r->direction != direction)
+    return fail(FSKHIP_E_INVALID, "%s: the handle converts for %s", who, r->direction == FSKHIP_RATECVT_CAPTURE ? "capture" : "playback");
+  if (n_in % r->M != 0) return fail(FSKHIP_E_INVALID, "%s: n_in %zu is not a multiple of the down factor %u", who, n_in, r->M);
+  return FSKHIP_OK;
+}
+
+// one launch over device buffers; the histories change places behind it
+int run(fskhip_ratecvt *r, const char *who, const void *d_src, size_t src_pitch, const uint32_t *d_lens, void *d_dst, size_t dst_pitch, int format, int layout,
+        size_t n_in, hipStream_t st) {
+  const RatecvtPlan P = ratecvt_plan(layout == FSKHIP_LAYOUT_STREAM_MAJOR, r->direction == FSKHIP_RATECVT_PLAYBACK, r->L, r->M, r->n_taps, r->S, n_in);
+  if (P.blocks == 0) return fail(FSKHIP_E_INVALID, "%s: %u streams x %zu samples are more workgroups than one launch takes", who, r->S, n_in);
+  const RatecvtShape G = {P.hist, P.G, P.rows, P.log2_ns, P.x_pitch, P.row_stride, P.span, P.seg_periods, P.split};
+  const KernelEntry<RatecvtFn> &k = kRatecvtKernels[r->direction][r->precision == FSKHIP_PRECISION_F64 ? 1 : 0][format][layout];
+  const void *taps = r->precision == FSKHIP_PRECISION_F64 ? (const void *)r->d_taps : (const void *)r->d_taps32;
+  hipLaunchKernelGGL(k.fn, dim3((uint32_t)P.blocks), dim3(kResampleThreads), P.lds_bytes, st, d_src, src_pitch, d_lens, d_dst, dst_pitch, r->hist[r->cur],
+                     r->hist[r->cur ^ 1], taps, r->d_table, r->S, n_in, r->L, r->M, r->n_taps, G);
+  HIP_TRY(hipGetLastError());
+  if (r->H) r->cur ^= 1;
+  return FSKHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t fskhip_ratecvt_streams(const fskhip_ratecvt *r) { return r ? r->S : 0u; }
+uint32_t fskhip_ratecvt_history(const fskhip_ratecvt *r) { return r ? r->H : 0u; }
+
+int fskhip_ratecvt_destroy(fskhip_ratecvt *r) {
+  if (!r) return FSKHIP_OK;
+  filter_close(*r, {r->d_taps, r->d_taps32, r->d_table, r->hist[0], r->hist[1], r->d_lens});
+  delete r;
+  return FSKHIP_OK;
+}
+
+int fskhip_ratecvt_create(int device, int direction, uint32_t up, uint32_t down, const double *taps, uint32_t n_taps, uint32_t n_streams, int precision,
+                          fskhip_ratecvt **out) {
+  if (!taps || !out) return fail(FSKHIP_E_INVALID, "fskhip_ratecvt_create: null taps or out");
+  if (n_streams == 0 || n_taps == 0) return fail(FSKHIP_E_INVALID, "fskhip_ratecvt_create: zero n_streams or n_taps");
+  if (direction != FSKHIP_RATECVT_CAPTURE && direction != FSKHIP_RATECVT_PLAYBACK) return fail(FSKHIP_E_INVALID, "fskhip_ratecvt_create: unknown direction %d", direction);
+  if (up < 1 || up > kRatecvtMaxFactor || down < 1 || down > kRatecvtMaxFactor)
+    return fail(FSKHIP_E_INVALID, "fskhip_ratecvt_create: ratio %u / %u outside 1..%u", up, down, kRatecvtMaxFactor);
+  if (ratecvt_gcd(up, down) != 1) return fail(FSKHIP_E_INVALID, "fskhip_ratecvt_create: %u / %u is not in lowest terms", up, down);
+  if (precision != FSKHIP_PRECISION_F32 && precision != FSKHIP_PRECISION_F64) return fail(FSKHIP_E_INVALID, "unknown precision %d", precision);
+  if (n_taps > kResampleMaxTaps) return fail(FSKHIP_E_UNSUPPORTED, "%u taps do not fit the LDS tile (max %u)", n_taps, kResampleMaxTaps);
+  if (const int rc = select_device(device)) return rc;
+  fskhip_ratecvt *r = new (std::nothrow) fskhip_ratecvt();
+  if (!r) return fail(FSKHIP_E_NOMEM, "out of host memory");
+  r->device = device; r->precision = precision; r->S = n_streams;
+  r->direction = direction; r->L = up; r->M = down; r->n_taps = n_taps; r->H = ratecvt_history(up, n_taps);
+  // column q of the [K][L] table: the taps of phase (q M) mod L, c[p], c[p + L], ... downwards (zeros behind a short phase, never read)
+  const uint32_t K = ratecvt_phase_len(up, n_taps);
+  std::vector<double> t64((size_t)K * up, 0.0);
+  std::vector<uint32_t> table(up);
+  for (uint32_t q = 0; q < up; q++) {
+    table[q] = ratecvt_table_word(up, down, q);
+    for (uint32_t k = 0, i = ratecvt_phase(up, down, q); i < n_taps; k++, i += up) t64[(size_t)k * up + q] = taps[i];
+  }
+  std::vector<float> t32(t64.size());
+  for (size_t i = 0; i < t64.size(); i++) t32[i] = (float)t64[i];
+  const size_t hsz = sizeof(float) * (size_t)n_streams * (r->H ? r->H : 1u);
+  hipError_t err = hipMalloc((void **)&r->d_taps, sizeof(double) * t64.size());
+  if (err == hipSuccess) err = hipMalloc((void **)&r->d_taps32, sizeof(float) * t32.size());
+  if (err == hipSuccess) err = hipMalloc((void **)&r->d_table, sizeof(uint32_t) * table.size());
+  if (err == hipSuccess) err = hipMalloc((void **)&r->hist[0], hsz);
+  if (err == hipSuccess) err = hipMalloc((void **)&r->hist[1], hsz);
+  if (err == hipSuccess) err = hipMalloc((void **)&r->d_lens, sizeof(uint32_t) * n_streams);
+  if (err == hipSuccess) err = hipMemcpy(r->d_taps, t64.data(), sizeof(double) * t64.size(), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = hipMemcpy(r->d_taps32, t32.data(), sizeof(float) * t32.size(), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = hipMemcpy(r->d_table, table.data(), sizeof(uint32_t) * table.size(), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = hipMemset(r->hist[0], 0, hsz);
+  if (err == hipSuccess) err = hipMemset(r->hist[1], 0, hsz);
+  return filter_open(r, err, "fskhip_ratecvt_create", fskhip_ratecvt_destroy, out);
+}
+
+int fskhip_ratecvt_reset(fskhip_ratecvt *r, int64_t stream) { return history_reset(r, "null rate converter", r ? r->hist[r->cur] : nullptr, r ? r->H : 0u, stream); }
+
+int fskhip_ratecvt_state_get(fskhip_ratecvt *r, float *state) {
+  return history_copy(r, "null rate converter", "fskhip_ratecvt_state_get", r ? r->hist[r->cur] : nullptr, r ? r->H : 0u, state, true);
+}
+
+int fskhip_ratecvt_state_set(fskhip_ratecvt *r, const float *state) {
+  return history_copy(r, "null rate converter", "fskhip_ratecvt_state_set", r ? r->hist[r->cur] : nullptr, r ? r->H : 0u, const_cast<float *>(state), false);
+}
+
+int fskhip_ratecvt_capture_device(fskhip_ratecvt *r, const void *d_src, int format, int layout, size_t n_in, size_t src_pitch, float *d_dst, size_t dst_pitch,
+                                  void *hip_stream) {
+  static const char who[] = "fskhip_ratecvt_capture_device";
+  if (const int rc = check_call(r, who, FSKHIP_RATECVT_CAPTURE, format, layout, n_in, d_src, src_pitch, d_dst, dst_pitch, nullptr)) return rc;
+  if (n_in == 0) return FSKHIP_OK;
+  HIP_TRY(hipSetDevice(r->device));
+  return run(r, who, d_src, src_pitch, nullptr, d_dst, dst_pitch, format, layout, n_in, (hipStream_t)hip_stream);
+}
+
+int fskhip_ratecvt_playback_device(fskhip_ratecvt *r, const float *d_src, size_t n_in, size_t src_pitch, const uint32_t *d_lens, void *d_dst, int format,
+                                   int layout, size_t dst_pitch, void *hip_stream) {
+  static const char who[] = "fskhip_ratecvt_playback_device";
+  if (const int rc = check_call(r, who, FSKHIP_RATECVT_PLAYBACK, format, layout, n_in, d_dst, dst_pitch, d_src, src_pitch, d_lens)) return rc;
+  if (n_in == 0) return FSKHIP_OK;
+  HIP_TRY(hipSetDevice(r->device));
+  return run(r, who, d_src, src_pitch, d_lens, d_dst, dst_pitch, format, layout, n_in, (hipStream_t)hip_stream);
+}
+
+int fskhip_ratecvt_capture_host(fskhip_ratecvt *r, const void *src, int format, int layout, size_t n_in, size_t src_pitch, float *dst, size_t dst_pitch) {
+  static const char who[] = "fskhip_ratecvt_capture_host";
+  if (const int rc = check_call(r, who, FSKHIP_RATECVT_CAPTURE, format, layout, n_in, src, src_pitch, dst, dst_pitch, nullptr)) return rc;
+  if (n_in == 0) return FSKHIP_OK;
+  HIP_TRY(hipSetDevice(r->device));
+  const bool rows = layout == FSKHIP_LAYOUT_STREAM_MAJOR;
+  const Slab in = slab(rows ? r->S : n_in, rows ? n_in : r->S, sample_bytes(format)), out = slab(r->S, n_in / r->M * r->L, sizeof(float));
+  int rc;
+  if ((rc = ensure(r->d_in, r->d_in_cap, in.bytes())) != FSKHIP_OK) return rc;
+  if ((rc = ensure(r->d_out, r->d_out_cap, out.bytes())) != FSKHIP_OK) return rc;
+  HIP_TRY(hipMemcpy2DAsync(r->d_in, in.pitch * in.esz, src, src_pitch * in.esz, in.cols * in.esz, in.rows, hipMemcpyHostToDevice, r->stream));
+  if ((rc = run(r, who, r->d_in, in.pitch, nullptr, r->d_out, out.pitch, format, layout, n_in, r->stream)) != FSKHIP_OK) return rc;
+  HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch * out.esz, r->d_out, out.pitch * out.esz, out.cols * out.esz, out.rows, hipMemcpyDeviceToHost, r->stream));
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  return FSKHIP_OK;
+}
+
+int fskhip_ratecvt_playback_host(fskhip_ratecvt *r, const float *src, size_t n_in, size_t src_pitch, const uint32_t *lens, void *dst, int format, int layout,
+                                 size_t dst_pitch) {
+  static const char who[] = "fskhip_ratecvt_playback_host";
+  if (const int rc = check_call(r, who, FSKHIP_RATECVT_PLAYBACK, format, layout, n_in, dst, dst_pitch, src, src_pitch, lens)) return rc;
+  if (n_in == 0) return FSKHIP_OK;
+  HIP_TRY(hipSetDevice(r->device));
+  const bool rows = layout == FSKHIP_LAYOUT_STREAM_MAJOR;
+  const size_t n_out = n_in / r->M * r->L;
+  const Slab in = slab(r->S, n_in, sizeof(float)), out = slab(rows ? r->S : n_out, rows ? n_out : r->S, sample_bytes(format));
+  int rc;
+  if ((rc = ensure(r->d_in, r->d_in_cap, in.bytes())) != FSKHIP_OK) return rc;
+  if ((rc = ensure(r->d_out, r->d_out_cap, out.bytes())) != FSKHIP_OK) return rc;
+  HIP_TRY(hipMemcpy2DAsync(r->d_in, in.pitch * in.esz, src, src_pitch * in.esz, in.cols * in.esz, in.rows, hipMemcpyHostToDevice, r->stream));
+  if (lens) HIP_TRY(hipMemcpyAsync(r->d_lens, lens, sizeof(uint32_t) * r->S, hipMemcpyHostToDevice, r->stream));
+  if ((rc = run(r, who, r->d_in, in.pitch, lens ? r->d_lens : nullptr, r->d_out, out.pitch, format, layout, n_in, r->stream)) != FSKHIP_OK) return rc;
+  HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch * out.esz, r->d_out, out.pitch * out.esz, out.cols * out.esz, out.rows, hipMemcpyDeviceToHost, r->stream));
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  return FSKHIP_OK;
+}
+
+}  // extern "C"

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "fsk_filter_host.h"
+#include "fsk_history_host.h"
 #include "fsk_launch.h"
 #include "fsk_mac_dev.h"
 #include "fsk_resample_plan.h"
@@ -226,13 +227,6 @@ __global__ __launch_bounds__(kResampleThreads) void resample_down_kernel(FSK_RES
   }
 }
 
-__global__ void resample_reset_kernel(float *hist, uint32_t h, uint32_t n_streams, int64_t stream) {
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (size_t)n_streams * h) return;
-  if (stream >= 0 && (int64_t)(idx / h) != stream) return;
-  hist[idx] = 0.0f;
-}
-
 // every instantiation, once: [direction][precision][format][layout], in the order of the headers' enums
 using ResampleFn = void (*)(const void *, size_t, const uint32_t *, void *, size_t, const float *, float *, const void *, uint32_t, size_t, uint32_t, uint32_t,
                             ResampleShape);
@@ -330,10 +324,6 @@ int run_down(fskhip_resampler *r, const char *who, const float *d_src, size_t n_
   return FSKHIP_OK;
 }
 
-// rows x cols elements of esz bytes between the host and a device slab whose rows are padded to whole 16-byte vectors
-struct Slab { size_t rows, cols, esz, pitch; size_t bytes() const { return rows * pitch * esz; } };
-Slab slab(size_t rows, size_t cols, size_t esz) { return {rows, cols, esz, (cols * esz + 15u) / 16u * 16u / esz}; }
-
 }  // namespace
 
 extern "C" {
@@ -381,36 +371,14 @@ int fskhip_resampler_create(int device, int direction, uint32_t factor, const do
   return filter_open(r, err, "fskhip_resampler_create", fskhip_resampler_destroy, out);
 }
 
-int fskhip_resampler_reset(fskhip_resampler *r, int64_t stream) {
-  if (!r) return fail(FSKHIP_E_INVALID, "null resampler");
-  if (const int rc = filter_reset_begin(r, stream)) return rc;
-  if (r->H) {
-    const size_t total = (size_t)r->S * r->H;
-    hipLaunchKernelGGL(resample_reset_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, r->hist[r->cur], r->H, r->S, stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-  }
-  return FSKHIP_OK;
-}
+int fskhip_resampler_reset(fskhip_resampler *r, int64_t stream) { return history_reset(r, "null resampler", r ? r->hist[r->cur] : nullptr, r ? r->H : 0u, stream); }
 
 int fskhip_resampler_state_get(fskhip_resampler *r, float *state) {
-  if (!r) return fail(FSKHIP_E_INVALID, "null resampler");
-  if (!r->H) return FSKHIP_OK;
-  if (!state) return fail(FSKHIP_E_INVALID, "fskhip_resampler_state_get: null buffer");
-  HIP_TRY(hipSetDevice(r->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(state, r->hist[r->cur], sizeof(float) * (size_t)r->S * r->H, hipMemcpyDeviceToHost));
-  return FSKHIP_OK;
+  return history_copy(r, "null resampler", "fskhip_resampler_state_get", r ? r->hist[r->cur] : nullptr, r ? r->H : 0u, state, true);
 }
 
 int fskhip_resampler_state_set(fskhip_resampler *r, const float *state) {
-  if (!r) return fail(FSKHIP_E_INVALID, "null resampler");
-  if (!r->H) return FSKHIP_OK;
-  if (!state) return fail(FSKHIP_E_INVALID, "fskhip_resampler_state_set: null buffer");
-  HIP_TRY(hipSetDevice(r->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(r->hist[r->cur], state, sizeof(float) * (size_t)r->S * r->H, hipMemcpyHostToDevice));
-  return FSKHIP_OK;
+  return history_copy(r, "null resampler", "fskhip_resampler_state_set", r ? r->hist[r->cur] : nullptr, r ? r->H : 0u, const_cast<float *>(state), false);
 }
 
 int fskhip_resampler_up_device(fskhip_resampler *r, const void *d_src, int format, int layout, size_t n_in, size_t src_pitch, float *d_dst, size_t dst_pitch,

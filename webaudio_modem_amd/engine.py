@@ -455,8 +455,10 @@ class FSKEngine:
     def demodulate_samples_at(self, samples, fmt, layout, upsampler, out_pitch=None):
         """demodulate_samples for capture samples at a lower rate (8 kHz trunk audio in front of a 48 kHz engine): the narrow
         samples cross PCIe as they are, `upsampler` (filters.Upsampler, on this engine's device, its history carried from call to
-        call) widens and interpolates them into a device tile, and demodulate_device runs on that tile.  Returns what
-        demodulate_data returns."""
+        call) widens and interpolates them into a device tile, and demodulate_device runs on that tile.  `upsampler` may also be a
+        filters.CaptureConverter (44.1 kHz captures: 160 / 147); the samples per stream must then be a multiple of its `down`.
+        Returns what demodulate_data returns."""
+        from .filters import CaptureConverter
         x, code, lay, S, N, _ = sample_args(samples, fmt, layout)
         if S != self.n_streams or upsampler.n_streams != S:
             raise ValueError("expected %d streams, got %d (upsampler: %d)" % (self.n_streams, S, upsampler.n_streams))
@@ -466,7 +468,12 @@ class FSKEngine:
         if N == 0:
             return [b""] * S, eod
         x = np.ascontiguousarray(x)
-        n = N * upsampler.factor
+        if isinstance(upsampler, CaptureConverter):
+            if N % upsampler.down:
+                raise ValueError("%d samples per stream are not a multiple of the converter's down factor %d" % (N, upsampler.down))
+            n = upsampler.out_count(N)
+        else:
+            n = N * upsampler.factor
         tpitch = (n + 3) & ~3
         opitch = out_pitch or self.max_bytes(n)
         out = np.zeros((S, opitch), dtype=np.uint8)
@@ -539,7 +546,12 @@ class FSKEngine:
         `downsampler` (filters.Downsampler, on this engine's device) decimates it with every stream's samples behind its own
         signal read as zeros, and one narrow copy comes back.  n_per_stream: low rate samples per stream (None: what the longest
         signal and the filter's ringing behind it take).  Returns (samples, lens): [S, n] or frames [n, S], and each stream's low
-        rate length ceil((len + n_taps - 1) / factor), from where on it is the format's silence."""
+        rate length ceil((len + n_taps - 1) / factor), from where on it is the format's silence.  `downsampler` may also be a
+        filters.PlaybackConverter (towards 44.1 kHz: 147 / 160): n_per_stream then counts its output samples and the lengths are
+        its out_length of each stream's signal, capped at n."""
+        from .filters import PlaybackConverter
+        if isinstance(downsampler, PlaybackConverter):
+            return self._modulate_samples_converted(payloads, fmt, layout, downsampler, n_per_stream)
         if len(payloads) != self.n_streams:
             raise ValueError("need one payload per stream")
         S, L = self.n_streams, downsampler.factor
@@ -566,6 +578,40 @@ class FSKEngine:
         self.synchronize()
         self.d2h(out, d_dst)
         return out, np.minimum((out_lens.astype(np.int64) + len(downsampler.taps) - 1 + L - 1) // L, n).astype(np.uint32)
+
+    def _modulate_samples_converted(self, payloads, fmt, layout, converter, n_per_stream):
+        """modulate_samples_at through a filters.PlaybackConverter (a 48 kHz engine in front of a 44.1 kHz sound card): the float
+        tile is padded to a whole number of the converter's periods, so the call writes ceil(n / up) * up samples per stream on
+        the device and the first n come back.  The lengths are the converter's out_length of each stream's signal, capped at n."""
+        if len(payloads) != self.n_streams:
+            raise ValueError("need one payload per stream")
+        S = self.n_streams
+        if converter.n_streams != S or converter.device != self.device:
+            raise ValueError("the converter must have this engine's %d streams and device %d" % (S, self.device))
+        pay, lens, ppitch = payload_args(payloads)
+        n = converter.out_length(self.modulated_length(int(lens.max()))) if n_per_stream is None else int(n_per_stream)
+        out_lens = np.zeros(S, dtype=np.uint32)
+        if n == 0:
+            return samples_out(fmt, layout, S, 0)[0], out_lens
+        periods = -(-n // converter.up)
+        n_in, n_dev = periods * converter.down, periods * converter.up
+        full, code, lay, pitch = samples_out(fmt, layout, S, n_dev)
+        tpitch = (n_in + 3) & ~3
+        d_pay, d_plens, d_tile, d_lens, d_dst = (self._scratch(k, b) for k, b in (("payloads", pay.nbytes), ("payload_lens", lens.nbytes), ("tile", 4 * S * tpitch),
+                                                                                  ("counts", 4 * S), ("narrow", full.nbytes)))
+        self.h2d(d_pay, pay)
+        self.h2d(d_plens, lens)
+        self.modulate_device(d_pay, d_plens, ppitch, d_tile, tpitch, d_lens)
+        self.synchronize()
+        self.d2h(out_lens, d_lens)
+        if int(out_lens.max()) > n_in:            # refused before the converter runs: its history stays as it was
+            s = int(np.argmax(out_lens > n_in))
+            raise FskHipError(_lib.E_OVERFLOW, "stream %d needs %d samples, slab holds %d" % (s, out_lens[s], n_in))
+        converter.process_device(d_tile, n_in, tpitch, d_lens, d_dst, code, lay, pitch)
+        self.synchronize()
+        self.d2h(full, d_dst)
+        out = np.ascontiguousarray(full[:, :n] if lay == _lib.LAYOUT_STREAM_MAJOR else full[:n])
+        return out, np.array([min(converter.out_length(int(v)), n) for v in out_lens], dtype=np.uint32)
 
     def modulate_device(self, d_payloads, d_lens, payload_pitch, d_out, out_pitch, d_out_lens, stream=None):
         _lib.check(self._L.fskhip_modulate_device(self._h, d_payloads, d_lens, payload_pitch, d_out, out_pitch,

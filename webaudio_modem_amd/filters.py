@@ -292,6 +292,144 @@ class Downsampler(_Resampler):
         return (int(n) + len(self.taps) - 1 + self.factor - 1) // self.factor
 
 
+class _RateConverter:
+    """What CaptureConverter and PlaybackConverter share: an fskhip_ratecvt handle (include/fskhip_next.h) that converts in_rate to
+    out_rate by up / down, the rates over their gcd; its design, reset, the history rows and close."""
+
+    _DIRECTION = None
+    MAX_FACTOR, MAX_TAPS = 256, 4096
+
+    @staticmethod
+    def ratio(in_rate, out_rate):
+        """(up, down) for in_rate -> out_rate: the rates, whole numbers, over their gcd"""
+        from math import gcd
+        i, o = int(in_rate), int(out_rate)
+        if i != in_rate or o != out_rate or i < 1 or o < 1:
+            raise ValueError("rates must be positive whole numbers, got %r and %r" % (in_rate, out_rate))
+        g = gcd(i, o)
+        return o // g, i // g
+
+    @classmethod
+    def default_taps(cls, in_rate, out_rate):
+        """the design of taps=None: a Hamming-windowed sinc at 0.45 of the lower rate, designed at up * in_rate, 16 taps per phase of
+        the larger factor and one, times up (the stuffed zeros take 1 / up of the level): 2 561 taps and 19 845 Hz for
+        44.1 kHz <-> 48 kHz"""
+        up, down = cls.ratio(in_rate, out_rate)
+        n = 16 * max(up, down) + 1
+        if n > cls.MAX_TAPS:
+            raise ValueError("the default design for %d / %d needs %d taps, the limit is %d" % (up, down, n, cls.MAX_TAPS))
+        return [t * float(up) for t in FilterDesign.sincLowpass(0.45 * min(in_rate, out_rate), float(up) * in_rate, n)]
+
+    def __init__(self, in_rate, out_rate, n_streams, taps=None, device=0, precision=_lib.PRECISION_F32):
+        import numpy as np
+        self._np = np
+        self.in_rate, self.out_rate, self.n_streams, self.device, self.precision = in_rate, out_rate, int(n_streams), device, precision
+        self.up, self.down = self.ratio(in_rate, out_rate)
+        if taps is None:
+            taps = self.default_taps(in_rate, out_rate)
+        self.taps = [float(t) for t in taps]
+        self._L = _lib.lib()
+        h = C.c_void_p()
+        _lib.check(self._L.fskhip_ratecvt_create(device, self._DIRECTION, self.up, self.down, (C.c_double * max(1, len(self.taps)))(*self.taps),
+                                                 len(self.taps), self.n_streams, precision, C.byref(h)))
+        self._h = h
+        self.history = int(self._L.fskhip_ratecvt_history(h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.fskhip_ratecvt_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def out_count(self, n_in):
+        """samples per stream a call with n_in per stream (a multiple of `down`) writes"""
+        return int(n_in) // self.down * self.up
+
+    def reset(self, stream=-1):
+        _lib.check(self._L.fskhip_ratecvt_reset(self._h, stream))
+
+    def state(self):
+        """the history rows, float32 [n_streams, history], oldest first (fskhip_ratecvt_state_get)"""
+        st = self._np.zeros((self.n_streams, self.history), self._np.float32)
+        _lib.check(self._L.fskhip_ratecvt_state_get(self._h, st.ctypes.data))
+        return st
+
+    def set_state(self, state):
+        """fskhip_ratecvt_state_set: rows as state() returns them, e.g. permuted by a remap's stream map"""
+        st = self._np.ascontiguousarray(state, dtype=self._np.float32)
+        if st.shape != (self.n_streams, self.history):
+            raise ValueError("state must be [%d, %d]" % (self.n_streams, self.history))
+        _lib.check(self._L.fskhip_ratecvt_state_set(self._h, st.ctypes.data))
+
+
+class CaptureConverter(_RateConverter):
+    """Capture samples at in_rate -> float32 [S, n / down * up] at out_rate, on the GPU (44.1 kHz in front of a 48 kHz engine:
+    up / down = 160 / 147): FIRFilterBatch(taps) over the samples zero-stuffed by `up` with every `down`-th output kept, evaluated
+    polyphase, history carried across calls; n must be a multiple of `down`."""
+
+    _DIRECTION = _lib.RATECVT_CAPTURE
+
+    def process(self, samples, fmt=None, layout="stream"):
+        """samples as FSKEngine.demodulate_samples takes them; returns float32 [S, n / down * up]"""
+        from .engine import sample_args
+        x, code, lay, S, N, pitch = sample_args(samples, fmt, layout)
+        if S != self.n_streams:
+            raise ValueError("expected %d streams, got %d" % (self.n_streams, S))
+        n_out = self.out_count(N)
+        out = self._np.zeros((S, n_out), self._np.float32)
+        if N:
+            _lib.check(self._L.fskhip_ratecvt_capture_host(self._h, x.ctypes.data, code, lay, N, pitch, out.ctypes.data, max(n_out, 1)))
+        return out
+
+    def process_device(self, d_src, fmt, layout, n_in, src_pitch, d_dst, dst_pitch, stream=None):
+        """fskhip_ratecvt_capture_device: device pointers (ints), asynchronous on `stream`"""
+        from .engine import _sample_codes
+        _lib.check(self._L.fskhip_ratecvt_capture_device(self._h, d_src, *_sample_codes(fmt, layout, True), n_in, src_pitch, d_dst, dst_pitch, stream))
+
+
+class PlaybackConverter(_RateConverter):
+    """float32 [S, n] at in_rate -> samples of a capture format at out_rate, on the GPU (a 48 kHz engine in front of a 44.1 kHz
+    sound card: up / down = 147 / 160): the same filter, encoded; n must be a multiple of `down`."""
+
+    _DIRECTION = _lib.RATECVT_PLAYBACK
+
+    def process(self, x, fmt, layout="stream", lens=None, out=None):
+        """x: float32 [S, n]; lens (or None): samples of stream s from lens[s] on read as 0.0.  Returns the samples as
+        FSKEngine.modulate_samples does, [S, n / down * up] or frames [n / down * up, S]; `out`: the array to write into."""
+        from .engine import samples_out
+        np = self._np
+        x = np.asarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        if x.ndim != 2 or x.shape[0] != self.n_streams:
+            raise ValueError("input must be [n_streams, n]")
+        if x.strides[1] != 4 and x.shape[1] > 1 or x.strides[0] % 4 or (x.shape[0] > 1 and x.strides[0] < 4 * x.shape[1]):
+            x = np.ascontiguousarray(x)
+        n = x.shape[1]
+        out, code, lay, pitch = samples_out(fmt, layout, self.n_streams, self.out_count(n), out)
+        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.uint32)
+        if ln is not None and ln.shape != (self.n_streams,):
+            raise ValueError("need one length per stream")
+        _lib.check(self._L.fskhip_ratecvt_playback_host(self._h, x.ctypes.data, n, max(x.strides[0] // 4 if x.shape[0] > 1 else n, n, 1),
+                                                        None if ln is None else ln.ctypes.data, out.ctypes.data, code, lay, pitch))
+        return out
+
+    def process_device(self, d_src, n_in, src_pitch, d_lens, d_dst, fmt, layout, dst_pitch, stream=None):
+        """fskhip_ratecvt_playback_device: device pointers (ints), asynchronous on `stream`"""
+        from .engine import _sample_codes
+        _lib.check(self._L.fskhip_ratecvt_playback_device(self._h, d_src, n_in, src_pitch, d_lens, d_dst, *_sample_codes(fmt, layout, True), dst_pitch, stream))
+
+    def out_length(self, n):
+        """output samples that can be non-zero for a signal of n input samples: the signal and the filter's ringing behind it"""
+        n = int(n)
+        return ((n - 1) * self.up + len(self.taps) - 1) // self.down + 1 if n else 0
+
+
 class IIRFilterBatch:
     """`new IIRFilter(b, a)` (filters.ts:8-106) for n_streams streams on one GPU: `processBuffer` on a float32 [S, N]
     block (Float32Array in, Float32Array out), `processSamples` on a float64 block (what `process(x)` returns sample by
