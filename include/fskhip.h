@@ -358,9 +358,30 @@ int fskhip_modulate_host_fmt(fskhip_engine *e, const uint8_t *payloads, const ui
  * out_lens[s] receives the signal length: totalBytes*bitsPerByte*spb + 2*spb + bitsPerByte*spb
  * (fsk.ts:391-394).  fskhip_modulated_length() gives that length for a payload size.
  * FSKHIP_PRECISION_F64 engines evaluate Math.sin with the operation sequence of the engine the reference runs on
- * (V8's fdlibm port), so the Float32Array is bit-identical at any length; FSKHIP_PRECISION_F32 engines use the
- * device library's sin() (about 1.8x faster; a sample can differ by one float ulp where two correct libms round the
- * double differently, about once in 1e9 samples).
+ * (V8's fdlibm port) wherever that sequence is its "medium" argument reduction: phases whose high word is <= 0x413921fb,
+ * that is up to 2^20 * pi/2 = 1 647 099.3 rad (fdlibm's own comment calls the bound "2^19*(pi/2)").  Up to the first sample
+ * whose phase lies beyond it the Float32Array is bit-identical to the reference's by construction -- about 1.05 million
+ * samples of tone with the 9600 / 14400 Hz pair at 48 kHz, some 7.4 million with 1200 / 2200 Hz.  From that sample on fdlibm
+ * reduces by Payne-Hanek, which is not restated: the device library's sin() is used, a sample is then within one float32
+ * spacing of the reference's, and it is the reference's wherever the two sines round to the same float (observed identical on
+ * the 26 339 and 26 703 samples behind the bound of tests/golden/golden_modulate.npz's two long cases).
+ * FSKHIP_PRECISION_F32 engines use the device library's sin() throughout (about 1.8x faster; a sample can differ by one float
+ * ulp where two correct libms round the double differently, about once in 1e9 samples).
+ *
+ * Every call starts at phase 0: nothing of an earlier modulate or demodulate call reaches the signal.
+ * What fskhip_modulate_device writes: row s of d_out receives its signal in columns [0, min(d_out_lens[s], out_pitch)) and
+ * NOTHING else is written -- not the rest of the row from d_out_lens[s] on, not the gap between two rows of a wider pitch, no
+ * word in front of d_out or behind its last row -- whatever the pitch and the alignment of d_out (a multiple of four floats on a
+ * 16-byte boundary is stored as 16-byte vectors, anything else as single floats; fskhip_egress_device's d_lens relies on it).
+ * What fskhip_modulate_host writes: it modulates into a staging slab of the engine's, which other calls use too and which is
+ * never cleared, and copies whole rows of out_pitch floats: row s of `out` holds its signal in columns [0, min(out_lens[s],
+ * out_pitch)), and its columns from out_lens[s] on are OVERWRITTEN with unspecified floats (whatever the slab held).  A caller
+ * that wants silence there writes it from out_lens[s] on, or takes fskhip_modulate_host_fmt, which does.
+ * An out_pitch smaller than a signal cuts it: out_lens[s] is still the FULL length, row s holds the first out_pitch samples of
+ * the signal, and fskhip_modulate_host returns FSKHIP_E_OVERFLOW naming the first such stream, with those prefixes in `out` and
+ * the full lengths in `out_lens` (fskhip_modulate_device returns FSKHIP_OK: the caller compares d_out_lens with its pitch).
+ * Refusals: a null engine is FSKHIP_E_NOT_CONFIGURED; null lens / out / out_lens are FSKHIP_E_INVALID; lens[s] > payload_pitch in
+ * the host call is FSKHIP_E_INVALID naming s, before anything is written.
  */
 size_t fskhip_modulated_length(const fskhip_engine *e, size_t n_bytes);
 int fskhip_modulate_host(fskhip_engine *e, const uint8_t *payloads, const uint32_t *lens,

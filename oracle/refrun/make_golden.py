@@ -9,7 +9,9 @@ TEST INFRASTRUCTURE.  Steps:
   3. this script packs the arrays into tests/golden/golden.npz (compressed; golden_part<k>.npz when over 1 MiB) and writes
      tests/golden/manifest.json; golden_harness_next.js does the same for the SURVEY 8(f) rows (CRC-16 /
      XModem packets, ChunkedModulator, the FSKProcessor quantum loop) -> golden_next.npz + manifest_next.json;
-     golden_harness_hostile.js for NaN / Inf / out-of-range / subnormal input (round 6) -> golden_hostile.npz + manifest_hostile.json.
+     golden_harness_hostile.js for NaN / Inf / out-of-range / subnormal input (round 6) -> golden_hostile.npz + manifest_hostile.json;
+     golden_harness_modulate.js for modulateData on both sides of 32 samples per bit, every framing, and past the sine's medium
+     range -> golden_modulate.npz + manifest_modulate.json.
 Only data (inputs, expected outputs, status snapshots, intermediates) reaches the repo.
 
 usage: python oracle/refrun/make_golden.py [--ref /root/reference]
@@ -59,7 +61,7 @@ def save_npz_parts(gold, npz, arrays):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
-    ap.add_argument("--only", default="", help="'golden.npz', 'golden_next' or 'golden_hostile' to regenerate one set")
+    ap.add_argument("--only", default="", help="'golden.npz', 'golden_next', 'golden_hostile' or 'golden_modulate' to regenerate one set")
     ap.add_argument("--keep", action="store_true", help="keep the temp dir (debugging)")
     args = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix="fsk_golden_")
@@ -69,7 +71,8 @@ def main():
         os.makedirs(gold, exist_ok=True)
         jobs = [("golden_harness.js", "golden.npz", "manifest.json"),
                 ("golden_harness_next.js", "golden_next.npz", "manifest_next.json"),
-                ("golden_harness_hostile.js", "golden_hostile.npz", "manifest_hostile.json")]
+                ("golden_harness_hostile.js", "golden_hostile.npz", "manifest_hostile.json"),
+                ("golden_harness_modulate.js", "golden_modulate.npz", "manifest_modulate.json")]
         for harness, npz, man_name in jobs:
             if args.only and args.only not in npz:
                 continue

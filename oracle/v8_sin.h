@@ -4,11 +4,13 @@
  * of fdlibm 5.3 (s_sin.c, k_sin.c, k_cos.c, e_rem_pio2.c; V8 is not part of /root/reference: it is the engine the
  * reference runs on, restated here from the published fdlibm algorithm).  glibc's sin is at least as accurate but is
  * a different algorithm, so the two can differ in the last ulp of the double; restating the fdlibm operation sequence
- * keeps the oracle's modulated Float32Array identical to the reference's at any length.  Pinned by the modulate
- * fixtures of tests/golden (tests/test_oracle_golden.py).  Built with -ffp-contract=off.
+ * keeps the oracle's modulated Float32Array identical to the reference's over the range below.  Pinned by the modulate
+ * fixtures of tests/golden (tests/test_oracle_golden.py, tests/test_oracle_modulate_edges.py).  Built with -ffp-contract=off.
  *
- * v8_sin() is exact for |x| <= 2^19*pi/2 (fdlibm's medium range); beyond it the reference's libm switches to
- * Payne-Hanek reduction and this file falls back to the C library's sin().
+ * v8_sin() is exact for |x| with a high word <= 0x413921fb: up to 2^20*pi/2 = 1 647 099.3 (fdlibm's medium range; its own
+ * comment calls the bound "2^19*(pi/2)").  Beyond it the reference's libm switches to Payne-Hanek reduction and this file falls
+ * back to the C library's sin(): within one float32 spacing of the reference's sample, and observed identical on the long
+ * cases of tests/golden/golden_modulate.npz.
  */
 #ifndef V8_SIN_H
 #define V8_SIN_H
@@ -48,7 +50,7 @@ static double v8s_kcos(double x, double y) { /* k_cos.c */
   return a - (hz - (z * r - x * y));
 }
 
-static int v8s_rem_pio2(double x, double *y) { /* e_rem_pio2.c, pi/4 < |x| <= 2^19*pi/2 */
+static int v8s_rem_pio2(double x, double *y) { /* e_rem_pio2.c, pi/4 < |x| <= 2^20*pi/2 */
   static const double invpio2 = 6.36619772367581382433e-01, pio2_1 = 1.57079632673412561417e+00,
                       pio2_1t = 6.07710050650619224932e-11, pio2_2 = 6.07710050630396597660e-11,
                       pio2_2t = 2.02226624879595063154e-21, pio2_3 = 2.02226624871116645580e-21,

@@ -68,4 +68,6 @@ def test_modulate_host_fmt_refusals_without_an_engine(L):
     # the float call's own refusal, for comparison: the same code and text
     refused(L, L.fskhip_modulate_host(None, pay.ctypes.data, lens.ctypes.data, 8, out.ctypes.data, 16, out_lens.ctypes.data), E_NOT_CONFIGURED,
             "FSK modulator not configured")
+    refused(L, L.fskhip_modulate_device(None, pay.ctypes.data, lens.ctypes.data, 8, out.ctypes.data, 16, out_lens.ctypes.data, None), E_NOT_CONFIGURED,
+            "FSK modulator not configured")
     assert not out.any() and not out_lens.any()

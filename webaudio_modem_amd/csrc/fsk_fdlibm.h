@@ -2,12 +2,14 @@
 // V8's src/base/ieee754.cc ports.  FSKCore.modulateData stores (float)Math.sin(phase) for an unwrapped phase that grows
 // into the thousands of radians (fsk.ts:398-406); two correctly-working libms can differ in the last ulp of the double
 // and, rarely, flip the float rounding.  Restating the same sequence of IEEE double operations (this TU is built
-// -ffp-contract=off) makes the modulated Float32Array bit-identical to the reference's at any length -- and it is about
+// -ffp-contract=off) makes the modulated Float32Array bit-identical to the reference's over the range below -- and it is about
 // half the instructions of the device library's sin().
 //
-// Covered exactly: |x| <= 2^19 * pi/2 (fdlibm's "medium" argument reduction: three-stage Cody-Waite with the
-// cancellation checks).  Beyond that fdlibm switches to Payne-Hanek (__kernel_rem_pio2); such phases need more than a
-// minute of continuous tone at 48 kHz, and fall through to the device library's sin().
+// Covered exactly: |x| with a high word <= 0x413921fb, that is up to 2^20 * pi/2 = 1 647 099.3 (fdlibm's "medium" argument
+// reduction: three-stage Cody-Waite with the cancellation checks; its own comment calls the bound "2^19*(pi/2)").
+// Beyond that fdlibm switches to Payne-Hanek (__kernel_rem_pio2); such phases need 1.05 million
+// samples of the 9600 / 14400 Hz pair at 48 kHz (7.4 million of 1200 / 2200 Hz), and fall through to the device library's sin():
+// within one float32 spacing of the reference's sample (tests/test_gpu_modulate.py holds both sides of the bound to the reference).
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -61,7 +63,7 @@ __host__ __device__ inline double k_cos(double x, double y) {
   return a - (hz - (z * r - x * y));
 }
 
-// __ieee754_rem_pio2(x, y) for pi/4 < |x| <= 2^19*pi/2; returns n, y[0] + y[1] = x - n*pi/2
+// __ieee754_rem_pio2(x, y) for pi/4 < |x| <= 2^20*pi/2 (high word <= 0x413921fb); returns n, y[0] + y[1] = x - n*pi/2
 __host__ __device__ inline int rem_pio2_medium(double x, double *y0, double *y1) {
   const double invpio2 = 6.36619772367581382433e-01, pio2_1 = 1.57079632673412561417e+00,
                pio2_1t = 6.07710050650619224932e-11, pio2_2 = 6.07710050630396597660e-11,
@@ -141,7 +143,7 @@ __host__ __device__ inline double sin_medium(double x, bool *exact) {
   *exact = true;
   if (ix <= 0x3fe921fbu) return k_sin(x, 0.0, 0);  // |x| <= pi/4
   if (ix >= 0x7ff00000u) return x - x;             // inf / NaN
-  if (ix > 0x413921fbu) {                          // |x| > 2^19 * pi/2
+  if (ix > 0x413921fbu) {                          // |x| > 2^20 * pi/2
     *exact = false;
     return 0.0;
   }

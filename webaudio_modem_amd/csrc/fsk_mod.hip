@@ -93,7 +93,7 @@ __device__ inline uint32_t frame_bit(const ModParams &M, uint32_t bit_idx, ByteF
 __device__ inline double ref_sin(double phase) {
   bool exact;
   double sv = fdlibm::sin_medium(phase, &exact);
-  if (!exact) sv = sin(phase);  // > 2^19*pi/2 rad: device library (see fsk_fdlibm.h)
+  if (!exact) sv = sin(phase);  // high word > 0x413921fb (2^20 * pi/2 rad): device library (see fsk_fdlibm.h)
   return sv;
 }
 
