@@ -62,8 +62,32 @@ function sampleLayout(l) {
   if (v !== 0 && v !== 1) throw new TypeError('unknown layout ' + l);
   return v;
 }
-class Resampler {
+// What the resamplers and the rate converters below share: a handle of the addon's UNIT family (resampler* / ratecvt*): reset, the
+// history rows and close; and the two process calls' marshalling over an object `o` of either, `call` being the addon's function
+// and last(n) its last argument (the factor, or the output count).
+class RateHandle {
+  reset(stream = -1) { addon[this.constructor.UNIT + 'Reset'](this.handle, stream); }
+  state() { return addon[this.constructor.UNIT + 'State'](this.handle); }             // Float32Array [nStreams][history], oldest first
+  setState(state) { addon[this.constructor.UNIT + 'SetState'](this.handle, state); }
+  close() { if (this.handle) { addon[this.constructor.UNIT + 'Destroy'](this.handle); this.handle = null; } }
+}
+function rateWiden(o, call, samples, format, layout, nIn, pitch, last) {
+  const f = sampleFormat(format), l = sampleLayout(layout);
+  if (!(samples instanceof SAMPLE_TYPES[f])) throw new TypeError('format ' + format + ' takes a ' + SAMPLE_TYPES[f].name);
+  const n = nIn === undefined ? samplesPerStream(samples, o.nStreams) : nIn;
+  if (n === 0) return new Float32Array(0);
+  return call(o.handle, samples, f, l, n, pitch === undefined ? (l === 1 ? o.nStreams : n) : pitch, last(n));
+}
+function rateNarrow(o, call, input, format, layout, lens, last) {
+  const f = sampleFormat(format), l = sampleLayout(layout);
+  const n = samplesPerStream(input, o.nStreams);
+  if (n === 0) return new SAMPLE_TYPES[f](0);
+  return call(o.handle, input, n, lens, f, l, last(n));
+}
+class Resampler extends RateHandle {
+  static get UNIT() { return 'resampler'; }
   constructor(direction, factor, nStreams, options = {}) {
+    super();
     if (!(Number.isInteger(factor) && factor >= 1 && factor <= 32)) throw new RangeError('factor ' + factor + ' outside 1..32');
     this.factor = factor;
     this.nStreams = nStreams;
@@ -78,10 +102,6 @@ class Resampler {
       options.precision === undefined ? PRECISION_F32 : options.precision);
     this.history = addon.resamplerHistory(this.handle);
   }
-  reset(stream = -1) { addon.resamplerReset(this.handle, stream); }
-  state() { return addon.resamplerState(this.handle); }             // Float32Array [nStreams][history], oldest first
-  setState(state) { addon.resamplerSetState(this.handle, state); }
-  close() { if (this.handle) { addon.resamplerDestroy(this.handle); this.handle = null; } }
   // an object of this class over a handle the library created (remap, restore)
   static adopt(handle, design) {
     const o = Object.create(this.prototype);
@@ -113,25 +133,14 @@ class Upsampler extends Resampler {
   constructor(factor, nStreams, options = {}) { super(0, factor, nStreams, options); }
   // samples: the format's typed array, [nStreams][pitch] (layout 'stream') or frames [nPerStream][pitch >= nStreams] ('sample');
   // nPerStream and pitch default to a packed array's -> Float32Array [nStreams][nPerStream * factor]
-  process(samples, format, layout = 'stream', nPerStream, pitch) {
-    const f = sampleFormat(format), l = sampleLayout(layout);
-    if (!(samples instanceof SAMPLE_TYPES[f])) throw new TypeError('format ' + format + ' takes a ' + SAMPLE_TYPES[f].name);
-    const n = nPerStream === undefined ? samplesPerStream(samples, this.nStreams) : nPerStream;
-    if (n === 0) return new Float32Array(0);
-    return addon.resamplerUp(this.handle, samples, f, l, n, pitch === undefined ? (l === 1 ? this.nStreams : n) : pitch, this.factor);
-  }
+  process(samples, format, layout = 'stream', nPerStream, pitch) { return rateWiden(this, addon.resamplerUp, samples, format, layout, nPerStream, pitch, () => this.factor); }
 }
 class Downsampler extends Resampler {
   static get DIRECTION() { return 1; }
   constructor(factor, nStreams, options = {}) { super(1, factor, nStreams, options); }
   // input: Float32Array [nStreams][n], n a multiple of factor; lens (Uint32Array or null): stream s reads as 0.0 from lens[s] on
   // -> the format's typed array, [nStreams][n / factor] or frames [n / factor][nStreams]
-  process(input, format, layout = 'stream', lens = null) {
-    const f = sampleFormat(format), l = sampleLayout(layout);
-    const n = samplesPerStream(input, this.nStreams);
-    if (n === 0) return new SAMPLE_TYPES[f](0);
-    return addon.resamplerDown(this.handle, input, n, lens, f, l, this.factor);
-  }
+  process(input, format, layout = 'stream', lens = null) { return rateNarrow(this, addon.resamplerDown, input, format, layout, lens, () => this.factor); }
 }
 
 // Rate conversion by a ratio up / down on the GPU (include/fskhip_next.h: fskhip_ratecvt_*): 44.1 kHz audio either side of a 48 kHz
@@ -139,7 +148,8 @@ class Downsampler extends Resampler {
 // per stream and gives n / down * up, the history carried across calls.  Without taps the design is sincLowpass(0.45 * min(inRate,
 // outRate), up * inRate, 16 * max(up, down) + 1) times up: 2 561 taps and 19 845 Hz between 44.1 and 48 kHz.
 function gcd(a, b) { while (b) { const t = a % b; a = b; b = t; } return a; }
-class RateConverter {
+class RateConverter extends RateHandle {
+  static get UNIT() { return 'ratecvt'; }
   static ratio(inRate, outRate) {
     if (!(Number.isInteger(inRate) && Number.isInteger(outRate) && inRate >= 1 && outRate >= 1)) {
       throw new RangeError('rates must be positive whole numbers, got ' + inRate + ' and ' + outRate);
@@ -153,6 +163,7 @@ class RateConverter {
     return FilterDesign.sincLowpass(0.45 * Math.min(inRate, outRate), up * inRate, n).map((t) => t * up);
   }
   constructor(direction, inRate, outRate, nStreams, options = {}) {
+    super();
     const { up, down } = RateConverter.ratio(inRate, outRate);
     this.inRate = inRate; this.outRate = outRate; this.up = up; this.down = down;
     this.nStreams = nStreams;
@@ -162,33 +173,18 @@ class RateConverter {
     this.history = addon.ratecvtHistory(this.handle);
   }
   outCount(nIn) { return Math.floor(nIn / this.down) * this.up; }
-  reset(stream = -1) { addon.ratecvtReset(this.handle, stream); }
-  state() { return addon.ratecvtState(this.handle); }               // Float32Array [nStreams][history], oldest first
-  setState(state) { addon.ratecvtSetState(this.handle, state); }
-  close() { if (this.handle) { addon.ratecvtDestroy(this.handle); this.handle = null; } }
 }
 class CaptureConverter extends RateConverter {
   constructor(inRate, outRate, nStreams, options = {}) { super(0, inRate, outRate, nStreams, options); }
   // samples: the format's typed array, [nStreams][pitch] (layout 'stream') or frames [nIn][pitch >= nStreams] ('sample'); nIn (a
   // multiple of down) and pitch default to a packed array's -> Float32Array [nStreams][nIn / down * up]
-  process(samples, format, layout = 'stream', nIn, pitch) {
-    const f = sampleFormat(format), l = sampleLayout(layout);
-    if (!(samples instanceof SAMPLE_TYPES[f])) throw new TypeError('format ' + format + ' takes a ' + SAMPLE_TYPES[f].name);
-    const n = nIn === undefined ? samplesPerStream(samples, this.nStreams) : nIn;
-    if (n === 0) return new Float32Array(0);
-    return addon.ratecvtCapture(this.handle, samples, f, l, n, pitch === undefined ? (l === 1 ? this.nStreams : n) : pitch, this.outCount(n));
-  }
+  process(samples, format, layout = 'stream', nIn, pitch) { return rateWiden(this, addon.ratecvtCapture, samples, format, layout, nIn, pitch, (n) => this.outCount(n)); }
 }
 class PlaybackConverter extends RateConverter {
   constructor(inRate, outRate, nStreams, options = {}) { super(1, inRate, outRate, nStreams, options); }
   // input: Float32Array [nStreams][n], n a multiple of down; lens (Uint32Array or null): stream s reads as 0.0 from lens[s] on
   // -> the format's typed array, [nStreams][n / down * up] or frames [n / down * up][nStreams]
-  process(input, format, layout = 'stream', lens = null) {
-    const f = sampleFormat(format), l = sampleLayout(layout);
-    const n = samplesPerStream(input, this.nStreams);
-    if (n === 0) return new SAMPLE_TYPES[f](0);
-    return addon.ratecvtPlayback(this.handle, input, n, lens, f, l, this.outCount(n));
-  }
+  process(input, format, layout = 'stream', lens = null) { return rateNarrow(this, addon.ratecvtPlayback, input, format, layout, lens, (n) => this.outCount(n)); }
   // output samples that can be non-zero for a signal of n input samples
   outLength(n) { return n ? Math.floor(((n - 1) * this.up + this.taps.length - 1) / this.down) + 1 : 0; }
 }

@@ -947,60 +947,111 @@ napi_value ResamplerDestroy(napi_env env, napi_callback_info info) {
   filter_box_close(env, argv[0]);
   return nullptr;
 }
-napi_value ResamplerHistory(napi_env env, napi_callback_info info) {
+// The calls the resampler shares with the rate converter below (fskhip_ratecvt_*), each body once over the unit's C entry points.
+// by_factor: the last argument of the two process calls is the factor, as the resampler's take it, else the output count.
+template <class H>
+struct RateApi {
+  H *(*of)(napi_env, napi_value);
+  uint32_t (*streams)(const H *), (*history)(const H *);
+  int (*reset)(H *, int64_t), (*state_get)(H *, float *), (*state_set)(H *, const float *);
+  int (*widen)(H *, const void *, int, int, size_t, size_t, float *, size_t);
+  int (*narrow)(H *, const float *, size_t, size_t, const uint32_t *, void *, int, int, size_t);
+  bool by_factor;
+};
+template <class H>
+napi_value rate_count(napi_env env, napi_callback_info info, const RateApi<H> &A, uint32_t (*count)(const H *)) {
   ARGS(1);
-  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
+  H *r = A.of(env, argv[0]);
   if (!r) return nullptr;
   napi_value v;
-  NAPI_OK(napi_create_uint32(env, fskhip_resampler_history(r), &v));
+  NAPI_OK(napi_create_uint32(env, count(r), &v));
   return v;
 }
-// (handle, samples in the format's typed array, format, layout, nIn, pitch, factor) -> Float32Array [S][nIn * factor]
-napi_value ResamplerStreams(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
-  if (!r) return nullptr;
-  napi_value v;
-  NAPI_OK(napi_create_uint32(env, fskhip_resampler_streams(r), &v));
-  return v;
-}
-napi_value ResamplerUp(napi_env env, napi_callback_info info) {
+// (handle, samples in the format's typed array, format, layout, nIn, pitch, factor | nOut) -> Float32Array [S][nOut]
+template <class H>
+napi_value rate_widen(napi_env env, napi_callback_info info, const RateApi<H> &A) {
   ARGS(7);
   const int32_t format = i32(env, argv[2]), layout = i32(env, argv[3]);
   if (!sample_format_ok(env, format, layout)) return nullptr;
-  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
+  H *r = A.of(env, argv[0]);
   if (!r) return nullptr;
   void *in; size_t ilen;
   if (!typed(env, argv[1], sample_array_type(format), &in, &ilen)) return nullptr;
-  const uint32_t n = u32(env, argv[4]), pitch = u32(env, argv[5]), L = u32(env, argv[6]), S = fskhip_resampler_streams(r);
+  const uint32_t n = u32(env, argv[4]), pitch = u32(env, argv[5]), last = u32(env, argv[6]), S = A.streams(r);
   const int64_t need = samples_needed(layout, S, n, pitch);
   if (need < 0 || (size_t)need > ilen) { napi_throw_range_error(env, nullptr, "input too short"); return nullptr; }
+  const size_t n_out = A.by_factor ? (size_t)n * last : last;
   void *out;
-  napi_value out_v = make_typed(env, napi_float32_array, (size_t)n * L * S, 4, &out);
+  napi_value out_v = make_typed(env, napi_float32_array, n_out * S, 4, &out);
   if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
-  int rc = fskhip_resampler_up_host(r, in, format, layout, n, pitch, (float *)out, (size_t)n * L);
+  int rc = A.widen(r, in, format, layout, n, pitch, (float *)out, (A.by_factor || n_out) ? n_out : 1);   // (the library holds a given n_out to its own count)
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   return out_v;
 }
-// (handle, input: Float32Array [S][nIn], nIn, lens: Uint32Array|null, format, layout, factor) -> the format's typed array, packed
-napi_value ResamplerDown(napi_env env, napi_callback_info info) {
+// (handle, input: Float32Array [S][nIn], nIn, lens: Uint32Array|null, format, layout, factor | nOut) -> the format's typed array, packed
+template <class H>
+napi_value rate_narrow(napi_env env, napi_callback_info info, const RateApi<H> &A) {
   ARGS(7);
   const int32_t format = i32(env, argv[4]), layout = i32(env, argv[5]);
   if (!sample_format_ok(env, format, layout)) return nullptr;
-  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
+  H *r = A.of(env, argv[0]);
   if (!r) return nullptr;
   void *in, *lens; size_t ilen, llen;
   if (!typed(env, argv[1], napi_float32_array, &in, &ilen) || !typed(env, argv[3], napi_uint32_array, &lens, &llen, true)) return nullptr;
-  const uint32_t n = u32(env, argv[2]), L = u32(env, argv[6]), S = fskhip_resampler_streams(r);
-  if (L == 0 || (size_t)n * S > ilen || (lens && llen < S)) { napi_throw_range_error(env, nullptr, "arguments too short"); return nullptr; }
-  const size_t n_out = n / L, pitch = layout == FSKHIP_LAYOUT_SAMPLE_MAJOR ? S : n_out;
+  const uint32_t n = u32(env, argv[2]), last = u32(env, argv[6]), S = A.streams(r);
+  if ((A.by_factor && last == 0) || (size_t)n * S > ilen || (lens && llen < S)) { napi_throw_range_error(env, nullptr, "arguments too short"); return nullptr; }
+  const size_t n_out = A.by_factor ? n / last : last, pitch = layout == FSKHIP_LAYOUT_SAMPLE_MAJOR ? S : n_out;
   void *out;
   napi_value out_v = make_typed(env, sample_array_type(format), n_out * S, fskhip_sample_bytes(format), &out);
   if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
-  int rc = fskhip_resampler_down_host(r, (const float *)in, n, n, (const uint32_t *)lens, out, format, layout, pitch ? pitch : 1);
+  int rc = A.narrow(r, (const float *)in, n, n, (const uint32_t *)lens, out, format, layout, pitch ? pitch : 1);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   return out_v;
 }
+template <class H>
+napi_value rate_reset(napi_env env, napi_callback_info info, const RateApi<H> &A) {
+  ARGS(2);
+  H *r = A.of(env, argv[0]);
+  if (!r) return nullptr;
+  int64_t s = -1;
+  napi_get_value_int64(env, argv[1], &s);
+  int rc = A.reset(r, s);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+template <class H>
+napi_value rate_state(napi_env env, napi_callback_info info, const RateApi<H> &A) {   // -> Float32Array [S][history]
+  ARGS(1);
+  H *r = A.of(env, argv[0]);
+  if (!r) return nullptr;
+  void *out;
+  napi_value out_v = make_typed(env, napi_float32_array, (size_t)A.streams(r) * A.history(r), 4, &out);
+  int rc = A.state_get(r, (float *)out);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return out_v;
+}
+template <class H>
+napi_value rate_set_state(napi_env env, napi_callback_info info, const RateApi<H> &A) {
+  ARGS(2);
+  H *r = A.of(env, argv[0]);
+  if (!r) return nullptr;
+  void *st; size_t n;
+  if (!typed(env, argv[1], napi_float32_array, &st, &n)) return nullptr;
+  if (n != (size_t)A.streams(r) * A.history(r)) { napi_throw_range_error(env, nullptr, "state must be [nStreams][history]"); return nullptr; }
+  int rc = A.state_set(r, (const float *)st);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+fskhip_resampler *resampler_of(napi_env env, napi_value v) { return (fskhip_resampler *)filter_of(env, v); }
+const RateApi<fskhip_resampler> kResampler = {resampler_of, fskhip_resampler_streams, fskhip_resampler_history, fskhip_resampler_reset, fskhip_resampler_state_get,
+                                              fskhip_resampler_state_set, fskhip_resampler_up_host, fskhip_resampler_down_host, true};
+napi_value ResamplerHistory(napi_env env, napi_callback_info info) { return rate_count(env, info, kResampler, kResampler.history); }
+napi_value ResamplerStreams(napi_env env, napi_callback_info info) { return rate_count(env, info, kResampler, kResampler.streams); }
+napi_value ResamplerUp(napi_env env, napi_callback_info info) { return rate_widen(env, info, kResampler); }
+napi_value ResamplerDown(napi_env env, napi_callback_info info) { return rate_narrow(env, info, kResampler); }
+napi_value ResamplerReset(napi_env env, napi_callback_info info) { return rate_reset(env, info, kResampler); }
+napi_value ResamplerState(napi_env env, napi_callback_info info) { return rate_state(env, info, kResampler); }
+napi_value ResamplerSetState(napi_env env, napi_callback_info info) { return rate_set_state(env, info, kResampler); }
 // process() with both sides at a low rate (fskhip_processor_process_rate_host): ProcessorProcessSamples with the two resampler handles in
 // front of the samples; lengths and pitches count low rate elements.  A handle is looked at only where its side has samples.
 napi_value ProcessorProcessSamplesAt(napi_env env, napi_callback_info info) {
@@ -1035,37 +1086,6 @@ napi_value ProcessorProcessSamplesAt(napi_env env, napi_callback_info info) {
   if (!out_v) napi_get_null(env, &out_v);
   return out_v;
 }
-napi_value ResamplerReset(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
-  if (!r) return nullptr;
-  int64_t s = -1;
-  napi_get_value_int64(env, argv[1], &s);
-  int rc = fskhip_resampler_reset(r, s);
-  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
-  return nullptr;
-}
-napi_value ResamplerState(napi_env env, napi_callback_info info) {   // -> Float32Array [S][history]
-  ARGS(1);
-  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
-  if (!r) return nullptr;
-  void *out;
-  napi_value out_v = make_typed(env, napi_float32_array, (size_t)fskhip_resampler_streams(r) * fskhip_resampler_history(r), 4, &out);
-  int rc = fskhip_resampler_state_get(r, (float *)out);
-  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
-  return out_v;
-}
-napi_value ResamplerSetState(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  fskhip_resampler *r = (fskhip_resampler *)filter_of(env, argv[0]);
-  if (!r) return nullptr;
-  void *st; size_t n;
-  if (!typed(env, argv[1], napi_float32_array, &st, &n)) return nullptr;
-  if (n != (size_t)fskhip_resampler_streams(r) * fskhip_resampler_history(r)) { napi_throw_range_error(env, nullptr, "state must be [nStreams][history]"); return nullptr; }
-  int rc = fskhip_resampler_state_set(r, (const float *)st);
-  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
-  return nullptr;
-}
 // ---- rate conversion by a ratio (include/fskhip_next.h: fskhip_ratecvt_*) ----
 fskhip_ratecvt *ratecvt_of(napi_env env, napi_value v) {
   FilterBox *b = (FilterBox *)external(env, v, "filter destroyed");
@@ -1089,83 +1109,14 @@ napi_value RatecvtDestroy(napi_env env, napi_callback_info info) {
   filter_box_close(env, argv[0]);
   return nullptr;
 }
-napi_value RatecvtHistory(napi_env env, napi_callback_info info) {
-  ARGS(1);
-  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
-  if (!r) return nullptr;
-  napi_value v;
-  NAPI_OK(napi_create_uint32(env, fskhip_ratecvt_history(r), &v));
-  return v;
-}
-// (handle, samples in the format's typed array, format, layout, nIn, pitch, nOut = nIn / down * up) -> Float32Array [S][nOut]
-napi_value RatecvtCapture(napi_env env, napi_callback_info info) {
-  ARGS(7);
-  const int32_t format = i32(env, argv[2]), layout = i32(env, argv[3]);
-  if (!sample_format_ok(env, format, layout)) return nullptr;
-  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
-  if (!r) return nullptr;
-  void *in; size_t ilen;
-  if (!typed(env, argv[1], sample_array_type(format), &in, &ilen)) return nullptr;
-  const uint32_t n = u32(env, argv[4]), pitch = u32(env, argv[5]), n_out = u32(env, argv[6]), S = fskhip_ratecvt_streams(r);
-  const int64_t need = samples_needed(layout, S, n, pitch);
-  if (need < 0 || (size_t)need > ilen) { napi_throw_range_error(env, nullptr, "input too short"); return nullptr; }
-  void *out;
-  napi_value out_v = make_typed(env, napi_float32_array, (size_t)n_out * S, 4, &out);
-  if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
-  int rc = fskhip_ratecvt_capture_host(r, in, format, layout, n, pitch, (float *)out, n_out ? n_out : 1);   // (the library holds n_out to its own count)
-  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
-  return out_v;
-}
-// (handle, input: Float32Array [S][nIn], nIn, lens: Uint32Array|null, format, layout, nOut = nIn / down * up) -> the format's typed array, packed
-napi_value RatecvtPlayback(napi_env env, napi_callback_info info) {
-  ARGS(7);
-  const int32_t format = i32(env, argv[4]), layout = i32(env, argv[5]);
-  if (!sample_format_ok(env, format, layout)) return nullptr;
-  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
-  if (!r) return nullptr;
-  void *in, *lens; size_t ilen, llen;
-  if (!typed(env, argv[1], napi_float32_array, &in, &ilen) || !typed(env, argv[3], napi_uint32_array, &lens, &llen, true)) return nullptr;
-  const uint32_t n = u32(env, argv[2]), n_out = u32(env, argv[6]), S = fskhip_ratecvt_streams(r);
-  if ((size_t)n * S > ilen || (lens && llen < S)) { napi_throw_range_error(env, nullptr, "arguments too short"); return nullptr; }
-  const size_t pitch = layout == FSKHIP_LAYOUT_SAMPLE_MAJOR ? S : n_out;
-  void *out;
-  napi_value out_v = make_typed(env, sample_array_type(format), (size_t)n_out * S, fskhip_sample_bytes(format), &out);
-  if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
-  int rc = fskhip_ratecvt_playback_host(r, (const float *)in, n, n, (const uint32_t *)lens, out, format, layout, pitch ? pitch : 1);
-  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
-  return out_v;
-}
-napi_value RatecvtReset(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
-  if (!r) return nullptr;
-  int64_t s = -1;
-  napi_get_value_int64(env, argv[1], &s);
-  int rc = fskhip_ratecvt_reset(r, s);
-  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
-  return nullptr;
-}
-napi_value RatecvtState(napi_env env, napi_callback_info info) {   // -> Float32Array [S][history]
-  ARGS(1);
-  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
-  if (!r) return nullptr;
-  void *out;
-  napi_value out_v = make_typed(env, napi_float32_array, (size_t)fskhip_ratecvt_streams(r) * fskhip_ratecvt_history(r), 4, &out);
-  int rc = fskhip_ratecvt_state_get(r, (float *)out);
-  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
-  return out_v;
-}
-napi_value RatecvtSetState(napi_env env, napi_callback_info info) {
-  ARGS(2);
-  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
-  if (!r) return nullptr;
-  void *st; size_t n;
-  if (!typed(env, argv[1], napi_float32_array, &st, &n)) return nullptr;
-  if (n != (size_t)fskhip_ratecvt_streams(r) * fskhip_ratecvt_history(r)) { napi_throw_range_error(env, nullptr, "state must be [nStreams][history]"); return nullptr; }
-  int rc = fskhip_ratecvt_state_set(r, (const float *)st);
-  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
-  return nullptr;
-}
+const RateApi<fskhip_ratecvt> kRatecvt = {ratecvt_of, fskhip_ratecvt_streams, fskhip_ratecvt_history, fskhip_ratecvt_reset, fskhip_ratecvt_state_get,
+                                          fskhip_ratecvt_state_set, fskhip_ratecvt_capture_host, fskhip_ratecvt_playback_host, false};
+napi_value RatecvtHistory(napi_env env, napi_callback_info info) { return rate_count(env, info, kRatecvt, kRatecvt.history); }
+napi_value RatecvtCapture(napi_env env, napi_callback_info info) { return rate_widen(env, info, kRatecvt); }
+napi_value RatecvtPlayback(napi_env env, napi_callback_info info) { return rate_narrow(env, info, kRatecvt); }
+napi_value RatecvtReset(napi_env env, napi_callback_info info) { return rate_reset(env, info, kRatecvt); }
+napi_value RatecvtState(napi_env env, napi_callback_info info) { return rate_state(env, info, kRatecvt); }
+napi_value RatecvtSetState(napi_env env, napi_callback_info info) { return rate_set_state(env, info, kRatecvt); }
 // ---- a resampler through remap / snapshot / restore (fskhip_resampler_remap ...): remap and restore return a NEW handle
 napi_value ResamplerRemap(napi_env env, napi_callback_info info) {   // (handle, map: number[]) -> handle
   ARGS(2);

@@ -50,7 +50,7 @@ static void walk(bool rows, bool playback, uint32_t L, uint32_t M, uint32_t taps
     for (uint32_t w = 0; w < n_quads * Qs; w++) {
       const uint32_t quad = w / Qs, u = w % Qs, per = u / L, q = u % L, word = ratecvt_table_word(L, M, q), p = word >> 16;
       const uint32_t x0 = H + per * M + (word & 0xFFFFu), kp = k_full + (p < rem ? 1u : 0u);
-      CHECK(kp == ratecvt_phase_taps(L, taps, p) && (kp == 0 || kp - 1 <= H), "%u/%u taps %u p %u", L, M, taps, p);
+      CHECK(kp == resample_phase_taps(L, taps, p) && (kp == 0 || kp - 1 <= H), "%u/%u taps %u p %u", L, M, taps, p);
       for (uint32_t r = 0; r < 4; r++) {
         const uint32_t row = quad * 4 + r;
         if (row >= P.rows) continue;
@@ -105,10 +105,10 @@ int main(int argc, char **argv) {
     if (16 * (L > M ? L : M) + 1 <= kResampleMaxTaps) tap_counts.push_back(16 * (L > M ? L : M) + 1);
     tap_counts.push_back(kResampleMaxTaps);
     for (const uint32_t taps : tap_counts) {
-      const uint32_t K = ratecvt_phase_len(L, taps), H = ratecvt_history(L, taps);
+      const uint32_t K = resample_phase_len(L, taps), H = resample_history(0, L, taps);
       uint32_t sum = 0, longest = 0;
       for (uint32_t p = 0; p < L; p++) {
-        const uint32_t kp = ratecvt_phase_taps(L, taps, p);
+        const uint32_t kp = resample_phase_taps(L, taps, p);
         sum += kp;
         longest = kp > longest ? kp : longest;
       }
@@ -133,7 +133,7 @@ int main(int argc, char **argv) {
   CHECK(ratecvt_out_length(147, 160, 2561, 0) == 0 && ratecvt_out_length(147, 160, 2561, 1) == 17 && ratecvt_out_length(1, 1, 1, 5) == 5 &&
             ratecvt_out_length(6, 1, 97, 10) == 151 && ratecvt_out_length(1, 6, 97, 48000) == 8016,
         "lengths");
-  CHECK(ratecvt_history(160, 2561) == 16 && ratecvt_history(147, 2561) == 18 && ratecvt_history(1, 1) == 0, "histories");
+  CHECK(resample_history(0, 160, 2561) == 16 && resample_history(0, 147, 2561) == 18 && resample_history(0, 1, 1) == 0, "histories");
   CHECK(ratecvt_plan(true, false, 1, 1, 1, 0x7FFFFFFFu, (size_t)1 << 40).blocks == 0, "a grid past one launch");
   CHECK(ratecvt_plan(false, true, 1, 1, 1, 64, (size_t)1 << 40).blocks == 0, "a grid past one launch");
   if (failures) { std::printf("%d failures\n", failures); return 1; }

@@ -8,7 +8,8 @@
     Hamming-windowed sinc at 19 845 Hz, 16 taps per phase of the larger factor) carried every configuration as they are, so
     neither numTaps nor the cutoff was changed;
   * the host arithmetic (csrc/fsk_ratecvt_plan.h) from a stand-alone program under AddressSanitizer and UBSan, and the GPU tests'
-    own copy of its cut (where they place a length one period past a segment) against what that program prints.
+    own copy of its cut (where they place a length one period past a segment) against what that program prints;
+  * what a process call of this unit and of the resampler is refused for (csrc/fsk_rate_call.h), from another such program.
 The model tests need nothing of the library, so they hold with or without the converter; what fails without it are the plan test
 here, tests/test_ratecvt_refusals_cpu.py and tests/test_gpu_ratecvt.py."""
 import os
@@ -130,3 +131,14 @@ def test_plan_arithmetic_under_sanitizers(tmp_path):
     want = {(L, M, t, pb): (tg._seg_periods(True, bool(pb), L, M, t), tg._seg_periods(False, bool(pb), L, M, t))
             for L, M in tg.PAIRS for t in tg._tap_counts(L, M) for pb in (0, 1)}
     assert table == want and len(want) == 2 * sum(len(tg._tap_counts(L, M)) for L, M in tg.PAIRS)
+
+
+def test_call_refusals_under_sanitizers(tmp_path):
+    """what a process call of either unit is refused for behind the null handle (csrc/fsk_rate_call.h): every refusal in the
+    header's order with all behind it wrong as well, for both units and directions (tests/cpp/rate_call_check.cpp)"""
+    exe = str(tmp_path / "rate_call_check")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "webaudio_modem_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "cpp", "rate_call_check.cpp")],
+                   check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr

@@ -1,6 +1,7 @@
 // fsk_filter_host.h -- the host part the two batched filters share (fsk_fir.hip, fsk_iir.hip), each piece once: what a handle
 // holds besides its coefficients and histories, the tail of create, destroy, the front of reset, and the _host call -- rows
-// through the handle's staging slabs and its _device entry point.  Not part of the ABI.
+// through the handle's staging slabs and its _device entry point; and what the two rate converters' handles hold on top of that
+// (RateHost, Slab).  Not part of the ABI.
 #pragma once
 #include <initializer_list>
 
@@ -14,6 +15,20 @@ struct FilterHost {   // (struct fskhip_fir and struct fskhip_iir derive from it
   uint32_t S = 0;
   hipStream_t stream = nullptr;   // the _host entry points' own
   unsigned char *d_in = nullptr, *d_out = nullptr; size_t d_in_cap = 0, d_out_cap = 0;   // their staging slabs (bytes), kept across calls
+};
+
+// what the handles of the two rate converters hold on top of it (struct fskhip_resampler and struct fskhip_ratecvt derive from
+// it); their host routines are fsk_rate_host.h's
+struct RateHost : FilterHost {
+  int direction = 0;
+  uint32_t L = 1, n_taps = 0, H = 0;      // L: the up factor (the resampler's only one); H: floats of history per stream
+  double *d_taps = nullptr;               // fp64 path, in the order the unit's kernels read them
+  float *d_taps32 = nullptr;              // the same, rounded once on the host (fp32 path)
+  float *hist[2] = {nullptr, nullptr};    // ping-pong: [cur] is read by the next call
+  int cur = 0;
+  uint32_t *d_lens = nullptr;             // the _host form's per-stream lengths
+
+  const void *taps() const { return precision == FSKHIP_PRECISION_F64 ? (const void *)d_taps : (const void *)d_taps32; }
 };
 
 // the tail of create: `err` is what the filter's own allocations, copies and memsets came to; a failed create leaves no handle

@@ -28,6 +28,13 @@ struct DemodCall {
 template <typename Fn>
 struct KernelEntry { Fn fn; const char *name; };
 #define FSK_K(K, ...) {&K<__VA_ARGS__>, "fsk::" #K "<" #__VA_ARGS__ ">"}
+// the eight instantiations K<R, format, layout> of a kernel that reads or writes the capture formats, [format][layout] in the
+// order of include/fskhip.h's enums
+#define FSK_FORMAT_KERNELS(K, R)                                                                                                      \
+  {{FSK_K(K, R, FSKHIP_SAMPLES_F32, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_F32, FSKHIP_LAYOUT_SAMPLE_MAJOR)},       \
+   {FSK_K(K, R, FSKHIP_SAMPLES_S16, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_S16, FSKHIP_LAYOUT_SAMPLE_MAJOR)},       \
+   {FSK_K(K, R, FSKHIP_SAMPLES_MULAW, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_MULAW, FSKHIP_LAYOUT_SAMPLE_MAJOR)},   \
+   {FSK_K(K, R, FSKHIP_SAMPLES_ALAW, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_ALAW, FSKHIP_LAYOUT_SAMPLE_MAJOR)}}
 template <typename Entry, size_t N>
 hipError_t set_lds_limit(const Entry (&table)[N], size_t bytes) {   // every instantiation's limit of dynamic LDS
   for (const Entry &k : table) {

@@ -18,22 +18,15 @@
 #include <new>
 #include <vector>
 
-#include "fsk_filter_host.h"
-#include "fsk_history_host.h"
 #include "fsk_launch.h"
 #include "fsk_mac_dev.h"
+#include "fsk_rate_host.h"
 #include "fsk_ratecvt_plan.h"
 #include "fsk_samples_dev.h"
 
-struct fskhip_ratecvt : fsk::FilterHost {
-  int direction = 0;
-  uint32_t L = 1, M = 1, n_taps = 0, H = 0;   // H: floats of history per stream (ratecvt_history)
-  double *d_taps = nullptr;                    // fp64 path: [K][L] in output order (fsk_ratecvt_plan.h)
-  float *d_taps32 = nullptr;                   // the same, rounded once on the host (fp32 path)
-  uint32_t *d_table = nullptr;                 // [L]: ratecvt_table_word
-  float *hist[2] = {nullptr, nullptr};         // ping-pong: [cur] is read by the next call
-  int cur = 0;
-  uint32_t *d_lens = nullptr;                  // the _host form's per-stream lengths
+struct fskhip_ratecvt : fsk::RateHost {   // L: the up factor; H: resample_history(0, L, n_taps); the taps [K][L] in output order (fsk_ratecvt_plan.h)
+  uint32_t M = 1;                          // the down factor
+  uint32_t *d_table = nullptr;             // [L]: ratecvt_table_word
 };
 
 namespace fsk {
@@ -162,14 +155,9 @@ __global__ __launch_bounds__(kResampleThreads) void ratecvt_playback_kernel(FSK_
 // every instantiation, once: [direction][precision][format][layout], in the order of the headers' enums
 using RatecvtFn = void (*)(const void *, size_t, const uint32_t *, void *, size_t, const float *, float *, const void *, const uint32_t *, uint32_t, size_t, uint32_t,
                            uint32_t, uint32_t, RatecvtShape);
-#define FSK_RATECVT_FORMATS(K, R)                                                                                                     \
-  {{FSK_K(K, R, FSKHIP_SAMPLES_F32, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_F32, FSKHIP_LAYOUT_SAMPLE_MAJOR)},       \
-   {FSK_K(K, R, FSKHIP_SAMPLES_S16, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_S16, FSKHIP_LAYOUT_SAMPLE_MAJOR)},       \
-   {FSK_K(K, R, FSKHIP_SAMPLES_MULAW, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_MULAW, FSKHIP_LAYOUT_SAMPLE_MAJOR)},   \
-   {FSK_K(K, R, FSKHIP_SAMPLES_ALAW, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_ALAW, FSKHIP_LAYOUT_SAMPLE_MAJOR)}}
 const KernelEntry<RatecvtFn> kRatecvtKernels[2][2][4][2] = {
-    {FSK_RATECVT_FORMATS(ratecvt_capture_kernel, float), FSK_RATECVT_FORMATS(ratecvt_capture_kernel, double)},
-    {FSK_RATECVT_FORMATS(ratecvt_playback_kernel, float), FSK_RATECVT_FORMATS(ratecvt_playback_kernel, double)}};
+    {FSK_FORMAT_KERNELS(ratecvt_capture_kernel, float), FSK_FORMAT_KERNELS(ratecvt_capture_kernel, double)},
+    {FSK_FORMAT_KERNELS(ratecvt_playback_kernel, float), FSK_FORMAT_KERNELS(ratecvt_playback_kernel, double)}};
 
 }  // namespace
 }  // namespace fsk
@@ -178,58 +166,46 @@ using namespace fsk;
 
 namespace {
 
-// What the four process entry points refuse, in the header's order, behind the null handle: format and layout; then, for a call
-// that has samples, null buffers, pitches and alignments; the handle's direction; an n_in that is no multiple of the down factor.
-// `narrow` is the side in the format, `wide` the float rows; pitches in elements.
-int check_call(const fskhip_ratecvt *r, const char *who, int direction, int format, int layout, size_t n_in, const void *narrow, size_t narrow_pitch,
-               const float *wide, size_t wide_pitch, const uint32_t *lens) {
+// The four process entry points: `direction` is the entry point's, `host` its form.  Refused in the header's order
+// (fsk_rate_call.h), an n_in that is no multiple of the down factor last; then one launch over the buffers or the staging slabs.
+int process(fskhip_ratecvt *r, const char *who, int direction, bool host, int format, int layout, size_t n_in, const void *src, size_t src_pitch,
+            const uint32_t *lens, void *dst, size_t dst_pitch, hipStream_t st) {
   if (!r) return fail(FSKHIP_E_INVALID, "null rate converter");
-  if (const int rc = check_sample_format(who, format, layout)) return rc;
-  if (n_in > 0) {
-    const size_t n_out = n_in / r->M * r->L;   // (of a call that passes the last check)
-    const size_t n_narrow = direction == FSKHIP_RATECVT_CAPTURE ? n_in : n_out, n_wide = direction == FSKHIP_RATECVT_CAPTURE ? n_out : n_in;
-    if (!narrow || !wide) return fail(FSKHIP_E_INVALID, "%s: null buffer", who);
-    if (wide_pitch < n_wide) return fail(FSKHIP_E_INVALID, "%s: float pitch %zu < %zu samples per stream", who, wide_pitch, n_wide);
-    if (layout == FSKHIP_LAYOUT_STREAM_MAJOR && narrow_pitch < n_narrow)
-      return fail(FSKHIP_E_INVALID, "%s: sample pitch %zu < %zu samples per stream", who, narrow_pitch, n_narrow);
-    if (layout == FSKHIP_LAYOUT_SAMPLE_MAJOR && narrow_pitch < r->S) return fail(FSKHIP_E_INVALID, "%s: frame pitch %zu < n_streams %u", who, narrow_pitch, r->S);
-    if ((reinterpret_cast<uintptr_t>(wide) & 3u) != 0 || (reinterpret_cast<uintptr_t>(lens) & 3u) != 0 ||
-        (reinterpret_cast<uintptr_t>(narrow) & (sample_bytes(format) - 1u)) != 0)
-      return fail(FSKHIP_E_INVALID, "%s: a buffer is not aligned to its element size", who);
+  const RateCall c = rate_call(r, direction, direction == FSKHIP_RATECVT_CAPTURE, format, layout, n_in, ratecvt_out_count(r->L, r->M, n_in), src, src_pitch, lens,
+                               dst, dst_pitch, r->M);
+  switch (const RateRefusal why = rate_call_check(c)) {
+    case RateRefusal::direction:
+      return fail(FSKHIP_E_INVALID, "%s: the handle converts for %s", who, r->direction == FSKHIP_RATECVT_CAPTURE ? "capture" : "playback");
+    case RateRefusal::multiple: return fail(FSKHIP_E_INVALID, "%s: n_in %zu is not a multiple of the down factor %u", who, n_in, r->M);
+    default:
+      if (const int rc = rate_call_fail(who, format, c, why)) return rc;
   }
-  if (r->direction != direction)
-    return fail(FSKHIP_E_INVALID, "%s: the handle converts for %s", who, r->direction == FSKHIP_RATECVT_CAPTURE ? "capture" : "playback");
-  if (n_in % r->M != 0) return fail(FSKHIP_E_INVALID, "%s: n_in %zu is not a multiple of the down factor %u", who, n_in, r->M);
-  return FSKHIP_OK;
-}
-
-// one launch over device buffers; the histories change places behind it
-int run(fskhip_ratecvt *r, const char *who, const void *d_src, size_t src_pitch, const uint32_t *d_lens, void *d_dst, size_t dst_pitch, int format, int layout,
-        size_t n_in, hipStream_t st) {
-  const RatecvtPlan P = ratecvt_plan(layout == FSKHIP_LAYOUT_STREAM_MAJOR, r->direction == FSKHIP_RATECVT_PLAYBACK, r->L, r->M, r->n_taps, r->S, n_in);
-  if (P.blocks == 0) return fail(FSKHIP_E_INVALID, "%s: %u streams x %zu samples are more workgroups than one launch takes", who, r->S, n_in);
-  const RatecvtShape G = {P.hist, P.G, P.rows, P.log2_ns, P.x_pitch, P.row_stride, P.span, P.seg_periods, P.split};
-  const KernelEntry<RatecvtFn> &k = kRatecvtKernels[r->direction][r->precision == FSKHIP_PRECISION_F64 ? 1 : 0][format][layout];
-  const void *taps = r->precision == FSKHIP_PRECISION_F64 ? (const void *)r->d_taps : (const void *)r->d_taps32;
-  hipLaunchKernelGGL(k.fn, dim3((uint32_t)P.blocks), dim3(kResampleThreads), P.lds_bytes, st, d_src, src_pitch, d_lens, d_dst, dst_pitch, r->hist[r->cur],
-                     r->hist[r->cur ^ 1], taps, r->d_table, r->S, n_in, r->L, r->M, r->n_taps, G);
-  HIP_TRY(hipGetLastError());
-  if (r->H) r->cur ^= 1;
-  return FSKHIP_OK;
+  return rate_process(r, c, host, direction == FSKHIP_RATECVT_CAPTURE, src, src_pitch, lens, dst, dst_pitch, st,
+                      [=](const void *d_src, size_t d_src_pitch, const uint32_t *d_lens, void *d_dst, size_t d_dst_pitch, hipStream_t s) {
+    return rate_run(r, [=](const float *hist_in, float *hist_out) -> int {
+      const RatecvtPlan P = ratecvt_plan(layout == FSKHIP_LAYOUT_STREAM_MAJOR, r->direction == FSKHIP_RATECVT_PLAYBACK, r->L, r->M, r->n_taps, r->S, n_in);
+      if (P.blocks == 0) return rate_grid_fail(who, r->S, n_in);
+      const RatecvtShape G = {P.hist, P.G, P.rows, P.log2_ns, P.x_pitch, P.row_stride, P.span, P.seg_periods, P.split};
+      const KernelEntry<RatecvtFn> &k = kRatecvtKernels[r->direction][r->precision == FSKHIP_PRECISION_F64 ? 1 : 0][format][layout];
+      hipLaunchKernelGGL(k.fn, dim3((uint32_t)P.blocks), dim3(kResampleThreads), P.lds_bytes, s, d_src, d_src_pitch, d_lens, d_dst, d_dst_pitch, hist_in, hist_out,
+                         r->taps(), (const uint32_t *)r->d_table, r->S, n_in, r->L, r->M, r->n_taps, G);
+      HIP_TRY(hipGetLastError());
+      return FSKHIP_OK;
+    });
+  });
 }
 
 }  // namespace
 
 extern "C" {
 
-uint32_t fskhip_ratecvt_streams(const fskhip_ratecvt *r) { return r ? r->S : 0u; }
-uint32_t fskhip_ratecvt_history(const fskhip_ratecvt *r) { return r ? r->H : 0u; }
-
-int fskhip_ratecvt_destroy(fskhip_ratecvt *r) {
-  if (!r) return FSKHIP_OK;
-  filter_close(*r, {r->d_taps, r->d_taps32, r->d_table, r->hist[0], r->hist[1], r->d_lens});
-  delete r;
-  return FSKHIP_OK;
+uint32_t fskhip_ratecvt_streams(const fskhip_ratecvt *r) { return rate_streams(r); }
+uint32_t fskhip_ratecvt_history(const fskhip_ratecvt *r) { return rate_history(r); }
+int fskhip_ratecvt_destroy(fskhip_ratecvt *r) { return rate_destroy(r, r ? r->d_table : nullptr); }
+int fskhip_ratecvt_reset(fskhip_ratecvt *r, int64_t stream) { return rate_reset(r, "null rate converter", stream); }
+int fskhip_ratecvt_state_get(fskhip_ratecvt *r, float *state) { return rate_state(r, "null rate converter", "fskhip_ratecvt_state_get", state, true); }
+int fskhip_ratecvt_state_set(fskhip_ratecvt *r, const float *state) {
+  return rate_state(r, "null rate converter", "fskhip_ratecvt_state_set", const_cast<float *>(state), false);
 }
 
 int fskhip_ratecvt_create(int device, int direction, uint32_t up, uint32_t down, const double *taps, uint32_t n_taps, uint32_t n_streams, int precision,
@@ -246,95 +222,36 @@ int fskhip_ratecvt_create(int device, int direction, uint32_t up, uint32_t down,
   fskhip_ratecvt *r = new (std::nothrow) fskhip_ratecvt();
   if (!r) return fail(FSKHIP_E_NOMEM, "out of host memory");
   r->device = device; r->precision = precision; r->S = n_streams;
-  r->direction = direction; r->L = up; r->M = down; r->n_taps = n_taps; r->H = ratecvt_history(up, n_taps);
+  r->direction = direction; r->L = up; r->M = down; r->n_taps = n_taps; r->H = resample_history(0, up, n_taps);
   // column q of the [K][L] table: the taps of phase (q M) mod L, c[p], c[p + L], ... downwards (zeros behind a short phase, never read)
-  const uint32_t K = ratecvt_phase_len(up, n_taps);
+  const uint32_t K = resample_phase_len(up, n_taps);
   std::vector<double> t64((size_t)K * up, 0.0);
   std::vector<uint32_t> table(up);
   for (uint32_t q = 0; q < up; q++) {
     table[q] = ratecvt_table_word(up, down, q);
     for (uint32_t k = 0, i = ratecvt_phase(up, down, q); i < n_taps; k++, i += up) t64[(size_t)k * up + q] = taps[i];
   }
-  std::vector<float> t32(t64.size());
-  for (size_t i = 0; i < t64.size(); i++) t32[i] = (float)t64[i];
-  const size_t hsz = sizeof(float) * (size_t)n_streams * (r->H ? r->H : 1u);
-  hipError_t err = hipMalloc((void **)&r->d_taps, sizeof(double) * t64.size());
-  if (err == hipSuccess) err = hipMalloc((void **)&r->d_taps32, sizeof(float) * t32.size());
-  if (err == hipSuccess) err = hipMalloc((void **)&r->d_table, sizeof(uint32_t) * table.size());
-  if (err == hipSuccess) err = hipMalloc((void **)&r->hist[0], hsz);
-  if (err == hipSuccess) err = hipMalloc((void **)&r->hist[1], hsz);
-  if (err == hipSuccess) err = hipMalloc((void **)&r->d_lens, sizeof(uint32_t) * n_streams);
-  if (err == hipSuccess) err = hipMemcpy(r->d_taps, t64.data(), sizeof(double) * t64.size(), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(r->d_taps32, t32.data(), sizeof(float) * t32.size(), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(r->d_table, table.data(), sizeof(uint32_t) * table.size(), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemset(r->hist[0], 0, hsz);
-  if (err == hipSuccess) err = hipMemset(r->hist[1], 0, hsz);
-  return filter_open(r, err, "fskhip_ratecvt_create", fskhip_ratecvt_destroy, out);
-}
-
-int fskhip_ratecvt_reset(fskhip_ratecvt *r, int64_t stream) { return history_reset(r, "null rate converter", r ? r->hist[r->cur] : nullptr, r ? r->H : 0u, stream); }
-
-int fskhip_ratecvt_state_get(fskhip_ratecvt *r, float *state) {
-  return history_copy(r, "null rate converter", "fskhip_ratecvt_state_get", r ? r->hist[r->cur] : nullptr, r ? r->H : 0u, state, true);
-}
-
-int fskhip_ratecvt_state_set(fskhip_ratecvt *r, const float *state) {
-  return history_copy(r, "null rate converter", "fskhip_ratecvt_state_set", r ? r->hist[r->cur] : nullptr, r ? r->H : 0u, const_cast<float *>(state), false);
+  return rate_open(r, t64, table, &r->d_table, "fskhip_ratecvt_create", fskhip_ratecvt_destroy, out);
 }
 
 int fskhip_ratecvt_capture_device(fskhip_ratecvt *r, const void *d_src, int format, int layout, size_t n_in, size_t src_pitch, float *d_dst, size_t dst_pitch,
                                   void *hip_stream) {
-  static const char who[] = "fskhip_ratecvt_capture_device";
-  if (const int rc = check_call(r, who, FSKHIP_RATECVT_CAPTURE, format, layout, n_in, d_src, src_pitch, d_dst, dst_pitch, nullptr)) return rc;
-  if (n_in == 0) return FSKHIP_OK;
-  HIP_TRY(hipSetDevice(r->device));
-  return run(r, who, d_src, src_pitch, nullptr, d_dst, dst_pitch, format, layout, n_in, (hipStream_t)hip_stream);
+  return process(r, "fskhip_ratecvt_capture_device", FSKHIP_RATECVT_CAPTURE, false, format, layout, n_in, d_src, src_pitch, nullptr, d_dst, dst_pitch, (hipStream_t)hip_stream);
 }
 
 int fskhip_ratecvt_playback_device(fskhip_ratecvt *r, const float *d_src, size_t n_in, size_t src_pitch, const uint32_t *d_lens, void *d_dst, int format,
                                    int layout, size_t dst_pitch, void *hip_stream) {
-  static const char who[] = "fskhip_ratecvt_playback_device";
-  if (const int rc = check_call(r, who, FSKHIP_RATECVT_PLAYBACK, format, layout, n_in, d_dst, dst_pitch, d_src, src_pitch, d_lens)) return rc;
-  if (n_in == 0) return FSKHIP_OK;
-  HIP_TRY(hipSetDevice(r->device));
-  return run(r, who, d_src, src_pitch, d_lens, d_dst, dst_pitch, format, layout, n_in, (hipStream_t)hip_stream);
+  return process(r, "fskhip_ratecvt_playback_device", FSKHIP_RATECVT_PLAYBACK, false, format, layout, n_in, d_src, src_pitch, d_lens, d_dst, dst_pitch, (hipStream_t)hip_stream);
 }
 
 int fskhip_ratecvt_capture_host(fskhip_ratecvt *r, const void *src, int format, int layout, size_t n_in, size_t src_pitch, float *dst, size_t dst_pitch) {
-  static const char who[] = "fskhip_ratecvt_capture_host";
-  if (const int rc = check_call(r, who, FSKHIP_RATECVT_CAPTURE, format, layout, n_in, src, src_pitch, dst, dst_pitch, nullptr)) return rc;
-  if (n_in == 0) return FSKHIP_OK;
-  HIP_TRY(hipSetDevice(r->device));
-  const bool rows = layout == FSKHIP_LAYOUT_STREAM_MAJOR;
-  const Slab in = slab(rows ? r->S : n_in, rows ? n_in : r->S, sample_bytes(format)), out = slab(r->S, n_in / r->M * r->L, sizeof(float));
-  int rc;
-  if ((rc = ensure(r->d_in, r->d_in_cap, in.bytes())) != FSKHIP_OK) return rc;
-  if ((rc = ensure(r->d_out, r->d_out_cap, out.bytes())) != FSKHIP_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(r->d_in, in.pitch * in.esz, src, src_pitch * in.esz, in.cols * in.esz, in.rows, hipMemcpyHostToDevice, r->stream));
-  if ((rc = run(r, who, r->d_in, in.pitch, nullptr, r->d_out, out.pitch, format, layout, n_in, r->stream)) != FSKHIP_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch * out.esz, r->d_out, out.pitch * out.esz, out.cols * out.esz, out.rows, hipMemcpyDeviceToHost, r->stream));
-  HIP_TRY(hipStreamSynchronize(r->stream));
-  return FSKHIP_OK;
+  return process(r, "fskhip_ratecvt_capture_host", FSKHIP_RATECVT_CAPTURE, true, format, layout, n_in, src, src_pitch, nullptr, dst, dst_pitch, nullptr);
 }
 
 int fskhip_ratecvt_playback_host(fskhip_ratecvt *r, const float *src, size_t n_in, size_t src_pitch, const uint32_t *lens, void *dst, int format, int layout,
                                  size_t dst_pitch) {
-  static const char who[] = "fskhip_ratecvt_playback_host";
-  if (const int rc = check_call(r, who, FSKHIP_RATECVT_PLAYBACK, format, layout, n_in, dst, dst_pitch, src, src_pitch, lens)) return rc;
-  if (n_in == 0) return FSKHIP_OK;
-  HIP_TRY(hipSetDevice(r->device));
-  const bool rows = layout == FSKHIP_LAYOUT_STREAM_MAJOR;
-  const size_t n_out = n_in / r->M * r->L;
-  const Slab in = slab(r->S, n_in, sizeof(float)), out = slab(rows ? r->S : n_out, rows ? n_out : r->S, sample_bytes(format));
-  int rc;
-  if ((rc = ensure(r->d_in, r->d_in_cap, in.bytes())) != FSKHIP_OK) return rc;
-  if ((rc = ensure(r->d_out, r->d_out_cap, out.bytes())) != FSKHIP_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(r->d_in, in.pitch * in.esz, src, src_pitch * in.esz, in.cols * in.esz, in.rows, hipMemcpyHostToDevice, r->stream));
-  if (lens) HIP_TRY(hipMemcpyAsync(r->d_lens, lens, sizeof(uint32_t) * r->S, hipMemcpyHostToDevice, r->stream));
-  if ((rc = run(r, who, r->d_in, in.pitch, lens ? r->d_lens : nullptr, r->d_out, out.pitch, format, layout, n_in, r->stream)) != FSKHIP_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch * out.esz, r->d_out, out.pitch * out.esz, out.cols * out.esz, out.rows, hipMemcpyDeviceToHost, r->stream));
-  HIP_TRY(hipStreamSynchronize(r->stream));
-  return FSKHIP_OK;
+  return process(r, "fskhip_ratecvt_playback_host", FSKHIP_RATECVT_PLAYBACK, true, format, layout, n_in, src, src_pitch, lens, dst, dst_pitch, nullptr);
 }
 
 }  // extern "C"
+

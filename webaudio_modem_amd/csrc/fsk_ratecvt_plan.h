@@ -5,8 +5,9 @@
 //
 // Up factor L, down factor M (coprime), n_taps taps:  y[j] = sum_k c[p + kL] x[m - k],  p = (jM) mod L,  m = (jM) div L.  L outputs
 // and M inputs make a period: output q of a period has phase (qM) mod L -- every phase once, L and M being coprime -- and its
-// newest input lies (qM) div L behind the period's first.  Phase p has ratecvt_phase_taps() taps, the longest K = ceil(n_taps / L),
-// and the handle keeps the last H = ceil((n_taps - 1) / L) >= K - 1 inputs of every stream.  The taps lie in OUTPUT order on the
+// newest input lies (qM) div L behind the period's first.  Phase p has resample_phase_taps() taps, the longest K = ceil(n_taps / L)
+// (resample_phase_len), and the handle keeps the last H = ceil((n_taps - 1) / L) >= K - 1 inputs of every stream: the
+// interpolator's, resample_history(0, L, n_taps) (fsk_resample_plan.h).  The taps lie in OUTPUT order on the
 // device, [K][L] with column q holding phase (qM) mod L, so that the consecutive outputs of a wave read consecutive words.
 //
 // A workgroup takes whole periods.  It computes `rows` rows of G periods each, four rows to a lane (the same place q in four
@@ -28,13 +29,10 @@ constexpr uint32_t kRatecvtRowOutputs = 1024;     // outputs per row of a stream
 constexpr uint32_t kRatecvtTileOutputs = 64;      // outputs per stream of a sample-major workgroup, about
 
 inline uint32_t ratecvt_gcd(uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; }
-inline uint32_t ratecvt_history(uint32_t L, uint32_t n_taps) { return (n_taps - 1 + L - 1) / L; }
 // elements per stream a call writes for n_in per stream (a multiple of M)
 inline size_t ratecvt_out_count(uint32_t L, uint32_t M, size_t n_in) { return n_in / M * L; }
 // outputs that can be non-zero for a signal of `len` inputs: the last input meets the last tap at stuffed index (len - 1) L + n_taps - 1
 inline size_t ratecvt_out_length(uint32_t L, uint32_t M, uint32_t n_taps, size_t len) { return len ? ((len - 1) * L + n_taps - 1) / M + 1 : 0; }
-inline uint32_t ratecvt_phase_len(uint32_t L, uint32_t n_taps) { return (n_taps + L - 1) / L; }          // K
-inline uint32_t ratecvt_phase_taps(uint32_t L, uint32_t n_taps, uint32_t p) { return p < n_taps ? (n_taps - p + L - 1) / L : 0u; }
 // output q of a period: its phase and how far its newest input lies behind the period's first
 inline uint32_t ratecvt_phase(uint32_t L, uint32_t M, uint32_t q) { return q * M % L; }
 inline uint32_t ratecvt_offset(uint32_t L, uint32_t M, uint32_t q) { return q * M / L; }
@@ -59,7 +57,7 @@ inline size_t ratecvt_tile_lds(uint32_t H, uint32_t L, uint32_t M, uint32_t G, u
 // n_in: inputs per stream (> 0, a multiple of M); playback: the direction that leaves in the format (it alone needs the tile)
 inline RatecvtPlan ratecvt_plan(bool stream_major, bool playback, uint32_t L, uint32_t M, uint32_t n_taps, uint32_t n_streams, size_t n_in) {
   RatecvtPlan P{};
-  const uint32_t H = P.hist = ratecvt_history(L, n_taps);
+  const uint32_t H = P.hist = resample_history(0, L, n_taps);
   if (stream_major) {
     P.rows = 4;
     P.G = kRatecvtRowOutputs / L ? kRatecvtRowOutputs / L : 1u;
@@ -88,11 +86,7 @@ inline RatecvtPlan ratecvt_plan(bool stream_major, bool playback, uint32_t L, ui
     P.tile_words = playback ? P.G * L * (P.rows + 1u) : 0u;
     P.lds_bytes = ratecvt_tile_lds(H, L, M, P.G, P.log2_ns, playback);
   }
-  const uint64_t segs = (n_in / M + P.seg_periods - 1) / P.seg_periods, ns = 1u << P.log2_ns;
-  const uint64_t tiles = (n_streams + ns - 1) / ns;
-  P.split = (uint32_t)(stream_major ? segs : tiles);
-  P.blocks = stream_major ? segs * n_streams : segs * tiles;
-  if (P.blocks > 0x7FFFFFFFull || segs > 0x7FFFFFFFull) P.blocks = 0;
+  resample_grid(P, P.seg_periods, stream_major, n_streams, n_in / M);
   return P;
 }
 

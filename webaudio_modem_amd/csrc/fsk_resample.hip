@@ -20,10 +20,9 @@
 #include <new>
 #include <vector>
 
-#include "fsk_filter_host.h"
-#include "fsk_history_host.h"
 #include "fsk_launch.h"
 #include "fsk_mac_dev.h"
+#include "fsk_rate_host.h"
 #include "fsk_resample_plan.h"
 #include "fsk_resampler.h"
 #include "fsk_samples_dev.h"
@@ -230,14 +229,9 @@ __global__ __launch_bounds__(kResampleThreads) void resample_down_kernel(FSK_RES
 // every instantiation, once: [direction][precision][format][layout], in the order of the headers' enums
 using ResampleFn = void (*)(const void *, size_t, const uint32_t *, void *, size_t, const float *, float *, const void *, uint32_t, size_t, uint32_t, uint32_t,
                             ResampleShape);
-#define FSK_RESAMPLE_FORMATS(K, R)                                                                                                    \
-  {{FSK_K(K, R, FSKHIP_SAMPLES_F32, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_F32, FSKHIP_LAYOUT_SAMPLE_MAJOR)},       \
-   {FSK_K(K, R, FSKHIP_SAMPLES_S16, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_S16, FSKHIP_LAYOUT_SAMPLE_MAJOR)},       \
-   {FSK_K(K, R, FSKHIP_SAMPLES_MULAW, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_MULAW, FSKHIP_LAYOUT_SAMPLE_MAJOR)},   \
-   {FSK_K(K, R, FSKHIP_SAMPLES_ALAW, FSKHIP_LAYOUT_STREAM_MAJOR), FSK_K(K, R, FSKHIP_SAMPLES_ALAW, FSKHIP_LAYOUT_SAMPLE_MAJOR)}}
 const KernelEntry<ResampleFn> kResampleKernels[2][2][4][2] = {
-    {FSK_RESAMPLE_FORMATS(resample_up_kernel, float), FSK_RESAMPLE_FORMATS(resample_up_kernel, double)},
-    {FSK_RESAMPLE_FORMATS(resample_down_kernel, float), FSK_RESAMPLE_FORMATS(resample_down_kernel, double)}};
+    {FSK_FORMAT_KERNELS(resample_up_kernel, float), FSK_FORMAT_KERNELS(resample_up_kernel, double)},
+    {FSK_FORMAT_KERNELS(resample_down_kernel, float), FSK_FORMAT_KERNELS(resample_down_kernel, double)}};
 
 hipError_t launch_resample(int direction, const ResamplePlan &P, int precision, int format, int layout, const void *d_src, size_t src_pitch, const uint32_t *d_lens,
                            void *d_dst, size_t dst_pitch, const float *hist_in, float *hist_out, const void *d_taps, uint32_t n_streams, size_t n, uint32_t L,
@@ -277,65 +271,44 @@ using namespace fsk;
 
 namespace {
 
-// What the four process entry points refuse, in the header's order, behind the null handle: format and layout; then, for a call that
-// has samples, null buffers, pitches and alignments; the handle's direction; down's n_in that is no multiple of the factor.
-// Pitches in elements; `aligned`: device pointers are held to their element's alignment, host pointers too.
-int check_call(const fskhip_resampler *r, const char *who, int direction, int format, int layout, size_t n_in, const void *narrow, size_t narrow_pitch,
-               const float *wide, size_t wide_pitch, const uint32_t *lens) {
+// The four process entry points: `direction` is the entry point's, `host` its form.  Refused in the header's order
+// (fsk_rate_call.h), down's n_in that is no multiple of the factor last; then one launch over the buffers or the staging slabs.
+int process(fskhip_resampler *r, const char *who, int direction, bool host, int format, int layout, size_t n_in, const void *src, size_t src_pitch,
+            const uint32_t *lens, void *dst, size_t dst_pitch, hipStream_t st) {
   if (!r) return fail(FSKHIP_E_INVALID, "null resampler");
-  if (const int rc = check_sample_format(who, format, layout)) return rc;
-  if (n_in > 0) {
-    const size_t n_narrow = direction == FSKHIP_RESAMPLE_UP ? n_in : n_in / r->L, n_wide = direction == FSKHIP_RESAMPLE_UP ? n_in * r->L : n_in;
-    if (!narrow || !wide) return fail(FSKHIP_E_INVALID, "%s: null buffer", who);
-    if (wide_pitch < n_wide) return fail(FSKHIP_E_INVALID, "%s: float pitch %zu < %zu samples per stream", who, wide_pitch, n_wide);
-    if (layout == FSKHIP_LAYOUT_STREAM_MAJOR && narrow_pitch < n_narrow)
-      return fail(FSKHIP_E_INVALID, "%s: sample pitch %zu < %zu samples per stream", who, narrow_pitch, n_narrow);
-    if (layout == FSKHIP_LAYOUT_SAMPLE_MAJOR && narrow_pitch < r->S) return fail(FSKHIP_E_INVALID, "%s: frame pitch %zu < n_streams %u", who, narrow_pitch, r->S);
-    if ((reinterpret_cast<uintptr_t>(wide) & 3u) != 0 || (reinterpret_cast<uintptr_t>(lens) & 3u) != 0 ||
-        (reinterpret_cast<uintptr_t>(narrow) & (sample_bytes(format) - 1u)) != 0)
-      return fail(FSKHIP_E_INVALID, "%s: a buffer is not aligned to its element size", who);
+  const bool up = direction == FSKHIP_RESAMPLE_UP;
+  const RateCall c = rate_call(r, direction, up, format, layout, n_in, up ? n_in * r->L : n_in / r->L, src, src_pitch, lens, dst, dst_pitch, up ? 1u : r->L);
+  switch (const RateRefusal why = rate_call_check(c)) {
+    case RateRefusal::direction: return fail(FSKHIP_E_INVALID, "%s: the handle resamples %s", who, r->direction == FSKHIP_RESAMPLE_UP ? "up" : "down");
+    case RateRefusal::multiple: return fail(FSKHIP_E_INVALID, "%s: n_in %zu is not a multiple of the factor %u", who, n_in, r->L);
+    default:
+      if (const int rc = rate_call_fail(who, format, c, why)) return rc;
   }
-  if (r->direction != direction) return fail(FSKHIP_E_INVALID, "%s: the handle resamples %s", who, r->direction == FSKHIP_RESAMPLE_UP ? "up" : "down");
-  if (direction == FSKHIP_RESAMPLE_DOWN && n_in % r->L != 0) return fail(FSKHIP_E_INVALID, "%s: n_in %zu is not a multiple of the factor %u", who, n_in, r->L);
-  return FSKHIP_OK;
-}
-
-int launch_result(const char *who, hipError_t err, uint32_t n_streams, size_t n) {
-  if (err == hipErrorInvalidValue) return fail(FSKHIP_E_INVALID, "%s: %u streams x %zu samples are more workgroups than one launch takes", who, n_streams, n);
-  HIP_TRY(err);
-  return FSKHIP_OK;
-}
-
-int run_up(fskhip_resampler *r, const char *who, const void *d_src, int format, int layout, size_t n_in, size_t src_pitch, float *d_dst, size_t dst_pitch,
-           hipStream_t st) {
-  const void *taps = r->precision == FSKHIP_PRECISION_F64 ? (const void *)r->d_taps : (const void *)r->d_taps32;
-  if (const int rc = launch_result(who, launch_resample_up(r->precision, d_src, format, layout, r->S, n_in, src_pitch, d_dst, dst_pitch, r->L, r->n_taps, taps,
-                                                           r->hist[r->cur], r->hist[r->cur ^ 1], st), r->S, n_in)) return rc;
-  if (r->H) r->cur ^= 1;
-  return FSKHIP_OK;
-}
-
-int run_down(fskhip_resampler *r, const char *who, const float *d_src, size_t n_in, size_t src_pitch, const uint32_t *d_lens, void *d_dst, int format, int layout,
-             size_t dst_pitch, hipStream_t st) {
-  const void *taps = r->precision == FSKHIP_PRECISION_F64 ? (const void *)r->d_taps : (const void *)r->d_taps32;
-  if (const int rc = launch_result(who, launch_resample_down(r->precision, d_src, n_in / r->L, src_pitch, d_lens, r->S, d_dst, format, layout, dst_pitch, r->L,
-                                                             r->n_taps, taps, r->hist[r->cur], r->hist[r->cur ^ 1], st), r->S, n_in)) return rc;
-  if (r->H) r->cur ^= 1;
-  return FSKHIP_OK;
+  return rate_process(r, c, host, up, src, src_pitch, lens, dst, dst_pitch, st,
+                      [=](const void *d_src, size_t d_src_pitch, const uint32_t *d_lens, void *d_dst, size_t d_dst_pitch, hipStream_t s) {
+    return rate_run(r, [=](const float *hist_in, float *hist_out) -> int {
+      const hipError_t err =
+          up ? launch_resample_up(r->precision, d_src, format, layout, r->S, n_in, d_src_pitch, (float *)d_dst, d_dst_pitch, r->L, r->n_taps, r->taps(), hist_in, hist_out, s)
+             : launch_resample_down(r->precision, (const float *)d_src, n_in / r->L, d_src_pitch, d_lens, r->S, d_dst, format, layout, d_dst_pitch, r->L, r->n_taps,
+                                    r->taps(), hist_in, hist_out, s);
+      if (err == hipErrorInvalidValue) return rate_grid_fail(who, r->S, n_in);
+      HIP_TRY(err);
+      return FSKHIP_OK;
+    });
+  });
 }
 
 }  // namespace
 
 extern "C" {
 
-uint32_t fskhip_resampler_streams(const fskhip_resampler *r) { return r ? r->S : 0u; }
-uint32_t fskhip_resampler_history(const fskhip_resampler *r) { return r ? r->H : 0u; }
-
-int fskhip_resampler_destroy(fskhip_resampler *r) {
-  if (!r) return FSKHIP_OK;
-  filter_close(*r, {r->d_taps, r->d_taps32, r->hist[0], r->hist[1], r->d_lens});
-  delete r;
-  return FSKHIP_OK;
+uint32_t fskhip_resampler_streams(const fskhip_resampler *r) { return rate_streams(r); }
+uint32_t fskhip_resampler_history(const fskhip_resampler *r) { return rate_history(r); }
+int fskhip_resampler_destroy(fskhip_resampler *r) { return rate_destroy(r); }
+int fskhip_resampler_reset(fskhip_resampler *r, int64_t stream) { return rate_reset(r, "null resampler", stream); }
+int fskhip_resampler_state_get(fskhip_resampler *r, float *state) { return rate_state(r, "null resampler", "fskhip_resampler_state_get", state, true); }
+int fskhip_resampler_state_set(fskhip_resampler *r, const float *state) {
+  return rate_state(r, "null resampler", "fskhip_resampler_state_set", const_cast<float *>(state), false);
 }
 
 int fskhip_resampler_create(int device, int direction, uint32_t factor, const double *taps, uint32_t n_taps, uint32_t n_streams, int precision,
@@ -356,85 +329,27 @@ int fskhip_resampler_create(int device, int direction, uint32_t factor, const do
   const uint32_t K = resample_phase_len(factor, n_taps);
   std::vector<double> t64(direction == FSKHIP_RESAMPLE_UP ? (size_t)factor * K : (size_t)n_taps, 0.0);
   for (uint32_t i = 0; i < n_taps; i++) t64[direction == FSKHIP_RESAMPLE_UP ? (size_t)(i % factor) * K + i / factor : (size_t)i] = taps[i];
-  std::vector<float> t32(t64.size());
-  for (size_t i = 0; i < t64.size(); i++) t32[i] = (float)t64[i];
-  const size_t hsz = sizeof(float) * (size_t)n_streams * (r->H ? r->H : 1u);
-  hipError_t err = hipMalloc((void **)&r->d_taps, sizeof(double) * t64.size());
-  if (err == hipSuccess) err = hipMalloc((void **)&r->d_taps32, sizeof(float) * t32.size());
-  if (err == hipSuccess) err = hipMalloc((void **)&r->hist[0], hsz);
-  if (err == hipSuccess) err = hipMalloc((void **)&r->hist[1], hsz);
-  if (err == hipSuccess) err = hipMalloc((void **)&r->d_lens, sizeof(uint32_t) * n_streams);
-  if (err == hipSuccess) err = hipMemcpy(r->d_taps, t64.data(), sizeof(double) * t64.size(), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(r->d_taps32, t32.data(), sizeof(float) * t32.size(), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemset(r->hist[0], 0, hsz);
-  if (err == hipSuccess) err = hipMemset(r->hist[1], 0, hsz);
-  return filter_open(r, err, "fskhip_resampler_create", fskhip_resampler_destroy, out);
-}
-
-int fskhip_resampler_reset(fskhip_resampler *r, int64_t stream) { return history_reset(r, "null resampler", r ? r->hist[r->cur] : nullptr, r ? r->H : 0u, stream); }
-
-int fskhip_resampler_state_get(fskhip_resampler *r, float *state) {
-  return history_copy(r, "null resampler", "fskhip_resampler_state_get", r ? r->hist[r->cur] : nullptr, r ? r->H : 0u, state, true);
-}
-
-int fskhip_resampler_state_set(fskhip_resampler *r, const float *state) {
-  return history_copy(r, "null resampler", "fskhip_resampler_state_set", r ? r->hist[r->cur] : nullptr, r ? r->H : 0u, const_cast<float *>(state), false);
+  return rate_open(r, t64, {}, nullptr, "fskhip_resampler_create", fskhip_resampler_destroy, out);
 }
 
 int fskhip_resampler_up_device(fskhip_resampler *r, const void *d_src, int format, int layout, size_t n_in, size_t src_pitch, float *d_dst, size_t dst_pitch,
                                void *hip_stream) {
-  static const char who[] = "fskhip_resampler_up_device";
-  if (const int rc = check_call(r, who, FSKHIP_RESAMPLE_UP, format, layout, n_in, d_src, src_pitch, d_dst, dst_pitch, nullptr)) return rc;
-  if (n_in == 0) return FSKHIP_OK;
-  HIP_TRY(hipSetDevice(r->device));
-  return run_up(r, who, d_src, format, layout, n_in, src_pitch, d_dst, dst_pitch, (hipStream_t)hip_stream);
+  return process(r, "fskhip_resampler_up_device", FSKHIP_RESAMPLE_UP, false, format, layout, n_in, d_src, src_pitch, nullptr, d_dst, dst_pitch, (hipStream_t)hip_stream);
 }
 
 int fskhip_resampler_down_device(fskhip_resampler *r, const float *d_src, size_t n_in, size_t src_pitch, const uint32_t *d_lens, void *d_dst, int format,
                                  int layout, size_t dst_pitch, void *hip_stream) {
-  static const char who[] = "fskhip_resampler_down_device";
-  if (const int rc = check_call(r, who, FSKHIP_RESAMPLE_DOWN, format, layout, n_in, d_dst, dst_pitch, d_src, src_pitch, d_lens)) return rc;
-  if (n_in == 0) return FSKHIP_OK;
-  HIP_TRY(hipSetDevice(r->device));
-  return run_down(r, who, d_src, n_in, src_pitch, d_lens, d_dst, format, layout, dst_pitch, (hipStream_t)hip_stream);
+  return process(r, "fskhip_resampler_down_device", FSKHIP_RESAMPLE_DOWN, false, format, layout, n_in, d_src, src_pitch, d_lens, d_dst, dst_pitch, (hipStream_t)hip_stream);
 }
 
 int fskhip_resampler_up_host(fskhip_resampler *r, const void *src, int format, int layout, size_t n_in, size_t src_pitch, float *dst, size_t dst_pitch) {
-  static const char who[] = "fskhip_resampler_up_host";
-  if (const int rc = check_call(r, who, FSKHIP_RESAMPLE_UP, format, layout, n_in, src, src_pitch, dst, dst_pitch, nullptr)) return rc;
-  if (n_in == 0) return FSKHIP_OK;
-  HIP_TRY(hipSetDevice(r->device));
-  const bool rows = layout == FSKHIP_LAYOUT_STREAM_MAJOR;
-  const Slab in = slab(rows ? r->S : n_in, rows ? n_in : r->S, sample_bytes(format)), out = slab(r->S, n_in * r->L, sizeof(float));
-  int rc;
-  if ((rc = ensure(r->d_in, r->d_in_cap, in.bytes())) != FSKHIP_OK) return rc;
-  if ((rc = ensure(r->d_out, r->d_out_cap, out.bytes())) != FSKHIP_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(r->d_in, in.pitch * in.esz, src, src_pitch * in.esz, in.cols * in.esz, in.rows, hipMemcpyHostToDevice, r->stream));
-  if ((rc = run_up(r, who, r->d_in, format, layout, n_in, in.pitch, (float *)r->d_out, out.pitch, r->stream)) != FSKHIP_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch * out.esz, r->d_out, out.pitch * out.esz, out.cols * out.esz, out.rows, hipMemcpyDeviceToHost, r->stream));
-  HIP_TRY(hipStreamSynchronize(r->stream));
-  return FSKHIP_OK;
+  return process(r, "fskhip_resampler_up_host", FSKHIP_RESAMPLE_UP, true, format, layout, n_in, src, src_pitch, nullptr, dst, dst_pitch, nullptr);
 }
 
 int fskhip_resampler_down_host(fskhip_resampler *r, const float *src, size_t n_in, size_t src_pitch, const uint32_t *lens, void *dst, int format, int layout,
                                size_t dst_pitch) {
-  static const char who[] = "fskhip_resampler_down_host";
-  if (const int rc = check_call(r, who, FSKHIP_RESAMPLE_DOWN, format, layout, n_in, dst, dst_pitch, src, src_pitch, lens)) return rc;
-  if (n_in == 0) return FSKHIP_OK;
-  HIP_TRY(hipSetDevice(r->device));
-  const bool rows = layout == FSKHIP_LAYOUT_STREAM_MAJOR;
-  const size_t n_out = n_in / r->L;
-  const Slab in = slab(r->S, n_in, sizeof(float)), out = slab(rows ? r->S : n_out, rows ? n_out : r->S, sample_bytes(format));
-  int rc;
-  if ((rc = ensure(r->d_in, r->d_in_cap, in.bytes())) != FSKHIP_OK) return rc;
-  if ((rc = ensure(r->d_out, r->d_out_cap, out.bytes())) != FSKHIP_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(r->d_in, in.pitch * in.esz, src, src_pitch * in.esz, in.cols * in.esz, in.rows, hipMemcpyHostToDevice, r->stream));
-  if (lens) HIP_TRY(hipMemcpyAsync(r->d_lens, lens, sizeof(uint32_t) * r->S, hipMemcpyHostToDevice, r->stream));
-  if ((rc = run_down(r, who, (const float *)r->d_in, n_in, in.pitch, lens ? r->d_lens : nullptr, r->d_out, format, layout, out.pitch, r->stream)) != FSKHIP_OK)
-    return rc;
-  HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch * out.esz, r->d_out, out.pitch * out.esz, out.cols * out.esz, out.rows, hipMemcpyDeviceToHost, r->stream));
-  HIP_TRY(hipStreamSynchronize(r->stream));
-  return FSKHIP_OK;
+  return process(r, "fskhip_resampler_down_host", FSKHIP_RESAMPLE_DOWN, true, format, layout, n_in, src, src_pitch, lens, dst, dst_pitch, nullptr);
 }
 
 }  // extern "C"
+

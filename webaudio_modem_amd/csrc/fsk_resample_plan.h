@@ -45,8 +45,10 @@ struct ResamplePlan {
   size_t lds_bytes;
 };
 
-inline void resample_grid(ResamplePlan &P, bool stream_major, uint32_t n_streams, size_t n_units) {
-  const uint64_t segs = (n_units + P.seg - 1) / P.seg, ns = 1u << P.log2_ns;
+// the grid of a plan (this one or fsk_ratecvt_plan.h's) whose workgroups take `seg` of a stream's n_units each
+template <class Plan>
+inline void resample_grid(Plan &P, uint32_t seg, bool stream_major, uint32_t n_streams, size_t n_units) {
+  const uint64_t segs = (n_units + seg - 1) / seg, ns = 1u << P.log2_ns;
   const uint64_t tiles = (n_streams + ns - 1) / ns;
   P.split = (uint32_t)(stream_major ? segs : tiles);
   P.blocks = stream_major ? segs * n_streams : segs * tiles;
@@ -64,7 +66,7 @@ inline ResamplePlan resample_up_plan(bool stream_major, uint32_t L, uint32_t n_t
   if (!stream_major)
     while (P.log2_ns < 6 && sizeof(float) * (((size_t)2u << P.log2_ns) * P.x_pitch + out_floats) <= kResampleLdsBytes) P.log2_ns++;
   P.lds_bytes = sizeof(float) * (((size_t)1u << P.log2_ns) * P.x_pitch + out_floats);
-  resample_grid(P, stream_major, n_streams, n_in);
+  resample_grid(P, P.seg, stream_major, n_streams, n_in);
   return P;
 }
 
@@ -82,7 +84,7 @@ inline ResamplePlan resample_down_plan(bool stream_major, uint32_t L, uint32_t n
   if (!stream_major)
     while (P.log2_ns < 6 && sizeof(float) * (((size_t)2u << P.log2_ns) * P.x_pitch + 64u * ((2u << P.log2_ns) + 1u)) <= kResampleLdsBytes) P.log2_ns++;
   P.lds_bytes = sizeof(float) * (((size_t)1u << P.log2_ns) * P.x_pitch + (stream_major ? 0u : 64u * ((1u << P.log2_ns) + 1u)));
-  resample_grid(P, stream_major, n_streams, n_out);
+  resample_grid(P, P.seg, stream_major, n_streams, n_out);
   return P;
 }
 

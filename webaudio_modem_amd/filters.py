@@ -110,10 +110,81 @@ class FIRFilter(FIRFilterBatch):
         return float(self.processBuffer(self._np.array([x], dtype=self._np.float32))[0])
 
 
-class _Resampler:
-    """What Upsampler and Downsampler share: an fskhip_resampler handle (include/fskhip_next.h), its design, reset, the history
-    rows and close."""
+class _RateHandle:
+    """What the resamplers and the rate converters share: a handle of the library's `_PREFIX` family (include/fskhip_next.h:
+    fskhip_resampler_* / fskhip_ratecvt_*) in `_h`, with n_streams and history beside it: close, reset, the history rows, and
+    the two host calls' marshalling."""
 
+    _PREFIX = None
+
+    def _fn(self, name):
+        return getattr(self._L, self._PREFIX + name)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=-1):
+        _lib.check(self._fn("reset")(self._h, stream))
+
+    def state(self):
+        """the history rows, float32 [n_streams, history], oldest first (fskhip_*_state_get)"""
+        st = self._np.zeros((self.n_streams, self.history), self._np.float32)
+        _lib.check(self._fn("state_get")(self._h, st.ctypes.data))
+        return st
+
+    def set_state(self, state):
+        """fskhip_*_state_set: rows as state() returns them, e.g. permuted by a remap's stream map"""
+        st = self._np.ascontiguousarray(state, dtype=self._np.float32)
+        if st.shape != (self.n_streams, self.history):
+            raise ValueError("state must be [%d, %d]" % (self.n_streams, self.history))
+        _lib.check(self._fn("state_set")(self._h, st.ctypes.data))
+
+    def _widen(self, name, samples, fmt, layout, out_count):
+        """the _host call `name` from samples as FSKEngine.demodulate_samples takes them to float32 [S, out_count(n)]"""
+        from .engine import sample_args
+        x, code, lay, S, N, pitch = sample_args(samples, fmt, layout)
+        if S != self.n_streams:
+            raise ValueError("expected %d streams, got %d" % (self.n_streams, S))
+        n_out = out_count(N)
+        out = self._np.zeros((S, n_out), self._np.float32)
+        if N:
+            _lib.check(self._fn(name)(self._h, x.ctypes.data, code, lay, N, pitch, out.ctypes.data, max(n_out, 1)))
+        return out
+
+    def _narrow(self, name, x, fmt, layout, lens, out, out_count):
+        """the _host call `name` from float32 [S, n] to out_count(n) samples per stream as FSKEngine.modulate_samples returns them"""
+        from .engine import samples_out
+        np = self._np
+        x = np.asarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        if x.ndim != 2 or x.shape[0] != self.n_streams:
+            raise ValueError("input must be [n_streams, n]")
+        if x.strides[1] != 4 and x.shape[1] > 1 or x.strides[0] % 4 or (x.shape[0] > 1 and x.strides[0] < 4 * x.shape[1]):
+            x = np.ascontiguousarray(x)
+        n = x.shape[1]
+        out, code, lay, pitch = samples_out(fmt, layout, self.n_streams, out_count(n), out)
+        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.uint32)
+        if ln is not None and ln.shape != (self.n_streams,):
+            raise ValueError("need one length per stream")
+        _lib.check(self._fn(name)(self._h, x.ctypes.data, n, max(x.strides[0] // 4 if x.shape[0] > 1 else n, n, 1),
+                                  None if ln is None else ln.ctypes.data, out.ctypes.data, code, lay, pitch))
+        return out
+
+
+class _Resampler(_RateHandle):
+    """What Upsampler and Downsampler share: an fskhip_resampler handle (include/fskhip_next.h) and its design; remap, snapshot
+    and restore."""
+
+    _PREFIX = "fskhip_resampler_"
     _DIRECTION = None
 
     def __init__(self, factor, n_streams, taps=None, low_rate=8000, device=0, precision=_lib.PRECISION_F32):
@@ -134,33 +205,6 @@ class _Resampler:
                                                    len(self.taps), self.n_streams, precision, C.byref(h)))
         self._h = h
         self.history = int(self._L.fskhip_resampler_history(h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.fskhip_resampler_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, stream=-1):
-        _lib.check(self._L.fskhip_resampler_reset(self._h, stream))
-
-    def state(self):
-        """the history rows, float32 [n_streams, history], oldest first (fskhip_resampler_state_get)"""
-        st = self._np.zeros((self.n_streams, self.history), self._np.float32)
-        _lib.check(self._L.fskhip_resampler_state_get(self._h, st.ctypes.data))
-        return st
-
-    def set_state(self, state):
-        """fskhip_resampler_state_set: rows as state() returns them, e.g. permuted by a remap's stream map"""
-        st = self._np.ascontiguousarray(state, dtype=self._np.float32)
-        if st.shape != (self.n_streams, self.history):
-            raise ValueError("state must be [%d, %d]" % (self.n_streams, self.history))
-        _lib.check(self._L.fskhip_resampler_state_set(self._h, st.ctypes.data))
 
     @classmethod
     def _adopt(cls, h, taps, factor, precision, device, low_rate):
@@ -239,14 +283,7 @@ class Upsampler(_Resampler):
 
     def process(self, samples, fmt=None, layout="stream"):
         """samples as FSKEngine.demodulate_samples takes them; returns float32 [S, n * factor]"""
-        from .engine import sample_args
-        x, code, lay, S, N, pitch = sample_args(samples, fmt, layout)
-        if S != self.n_streams:
-            raise ValueError("expected %d streams, got %d" % (self.n_streams, S))
-        out = self._np.zeros((S, N * self.factor), self._np.float32)
-        if N:
-            _lib.check(self._L.fskhip_resampler_up_host(self._h, x.ctypes.data, code, lay, N, pitch, out.ctypes.data, N * self.factor))
-        return out
+        return self._widen("up_host", samples, fmt, layout, lambda n: n * self.factor)
 
     def process_device(self, d_src, fmt, layout, n_in, src_pitch, d_dst, dst_pitch, stream=None):
         """fskhip_resampler_up_device: device pointers (ints), asynchronous on `stream`"""
@@ -264,23 +301,7 @@ class Downsampler(_Resampler):
     def process(self, x, fmt, layout="stream", lens=None, out=None):
         """x: float32 [S, n]; lens (or None): samples of stream s from lens[s] on read as 0.0.  Returns the samples as
         FSKEngine.modulate_samples does, [S, n / factor] or frames [n / factor, S]; `out`: the array to write into."""
-        from .engine import samples_out
-        np = self._np
-        x = np.asarray(x, dtype=np.float32)
-        if x.ndim == 1:
-            x = x[None, :]
-        if x.ndim != 2 or x.shape[0] != self.n_streams:
-            raise ValueError("input must be [n_streams, n]")
-        if x.strides[1] != 4 and x.shape[1] > 1 or x.strides[0] % 4 or (x.shape[0] > 1 and x.strides[0] < 4 * x.shape[1]):
-            x = np.ascontiguousarray(x)
-        n = x.shape[1]
-        out, code, lay, pitch = samples_out(fmt, layout, self.n_streams, n // self.factor, out)
-        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.uint32)
-        if ln is not None and ln.shape != (self.n_streams,):
-            raise ValueError("need one length per stream")
-        _lib.check(self._L.fskhip_resampler_down_host(self._h, x.ctypes.data, n, max(x.strides[0] // 4 if x.shape[0] > 1 else n, n, 1),
-                                                      None if ln is None else ln.ctypes.data, out.ctypes.data, code, lay, pitch))
-        return out
+        return self._narrow("down_host", x, fmt, layout, lens, out, lambda n: n // self.factor)
 
     def process_device(self, d_src, n_in, src_pitch, d_lens, d_dst, fmt, layout, dst_pitch, stream=None):
         """fskhip_resampler_down_device: device pointers (ints), asynchronous on `stream`"""
@@ -292,10 +313,11 @@ class Downsampler(_Resampler):
         return (int(n) + len(self.taps) - 1 + self.factor - 1) // self.factor
 
 
-class _RateConverter:
+class _RateConverter(_RateHandle):
     """What CaptureConverter and PlaybackConverter share: an fskhip_ratecvt handle (include/fskhip_next.h) that converts in_rate to
-    out_rate by up / down, the rates over their gcd; its design, reset, the history rows and close."""
+    out_rate by up / down, the rates over their gcd, and its design."""
 
+    _PREFIX = "fskhip_ratecvt_"
     _DIRECTION = None
     MAX_FACTOR, MAX_TAPS = 256, 4096
 
@@ -335,36 +357,9 @@ class _RateConverter:
         self._h = h
         self.history = int(self._L.fskhip_ratecvt_history(h))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.fskhip_ratecvt_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def out_count(self, n_in):
         """samples per stream a call with n_in per stream (a multiple of `down`) writes"""
         return int(n_in) // self.down * self.up
-
-    def reset(self, stream=-1):
-        _lib.check(self._L.fskhip_ratecvt_reset(self._h, stream))
-
-    def state(self):
-        """the history rows, float32 [n_streams, history], oldest first (fskhip_ratecvt_state_get)"""
-        st = self._np.zeros((self.n_streams, self.history), self._np.float32)
-        _lib.check(self._L.fskhip_ratecvt_state_get(self._h, st.ctypes.data))
-        return st
-
-    def set_state(self, state):
-        """fskhip_ratecvt_state_set: rows as state() returns them, e.g. permuted by a remap's stream map"""
-        st = self._np.ascontiguousarray(state, dtype=self._np.float32)
-        if st.shape != (self.n_streams, self.history):
-            raise ValueError("state must be [%d, %d]" % (self.n_streams, self.history))
-        _lib.check(self._L.fskhip_ratecvt_state_set(self._h, st.ctypes.data))
 
 
 class CaptureConverter(_RateConverter):
@@ -376,15 +371,7 @@ class CaptureConverter(_RateConverter):
 
     def process(self, samples, fmt=None, layout="stream"):
         """samples as FSKEngine.demodulate_samples takes them; returns float32 [S, n / down * up]"""
-        from .engine import sample_args
-        x, code, lay, S, N, pitch = sample_args(samples, fmt, layout)
-        if S != self.n_streams:
-            raise ValueError("expected %d streams, got %d" % (self.n_streams, S))
-        n_out = self.out_count(N)
-        out = self._np.zeros((S, n_out), self._np.float32)
-        if N:
-            _lib.check(self._L.fskhip_ratecvt_capture_host(self._h, x.ctypes.data, code, lay, N, pitch, out.ctypes.data, max(n_out, 1)))
-        return out
+        return self._widen("capture_host", samples, fmt, layout, self.out_count)
 
     def process_device(self, d_src, fmt, layout, n_in, src_pitch, d_dst, dst_pitch, stream=None):
         """fskhip_ratecvt_capture_device: device pointers (ints), asynchronous on `stream`"""
@@ -401,23 +388,7 @@ class PlaybackConverter(_RateConverter):
     def process(self, x, fmt, layout="stream", lens=None, out=None):
         """x: float32 [S, n]; lens (or None): samples of stream s from lens[s] on read as 0.0.  Returns the samples as
         FSKEngine.modulate_samples does, [S, n / down * up] or frames [n / down * up, S]; `out`: the array to write into."""
-        from .engine import samples_out
-        np = self._np
-        x = np.asarray(x, dtype=np.float32)
-        if x.ndim == 1:
-            x = x[None, :]
-        if x.ndim != 2 or x.shape[0] != self.n_streams:
-            raise ValueError("input must be [n_streams, n]")
-        if x.strides[1] != 4 and x.shape[1] > 1 or x.strides[0] % 4 or (x.shape[0] > 1 and x.strides[0] < 4 * x.shape[1]):
-            x = np.ascontiguousarray(x)
-        n = x.shape[1]
-        out, code, lay, pitch = samples_out(fmt, layout, self.n_streams, self.out_count(n), out)
-        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.uint32)
-        if ln is not None and ln.shape != (self.n_streams,):
-            raise ValueError("need one length per stream")
-        _lib.check(self._L.fskhip_ratecvt_playback_host(self._h, x.ctypes.data, n, max(x.strides[0] // 4 if x.shape[0] > 1 else n, n, 1),
-                                                        None if ln is None else ln.ctypes.data, out.ctypes.data, code, lay, pitch))
-        return out
+        return self._narrow("playback_host", x, fmt, layout, lens, out, self.out_count)
 
     def process_device(self, d_src, n_in, src_pitch, d_lens, d_dst, fmt, layout, dst_pitch, stream=None):
         """fskhip_ratecvt_playback_device: device pointers (ints), asynchronous on `stream`"""
