@@ -889,6 +889,40 @@ int fskhip_ratecvt_playback_host(fskhip_ratecvt *r, const float *src, size_t n_i
 int fskhip_ratecvt_state_get(fskhip_ratecvt *r, float *state);
 int fskhip_ratecvt_state_set(fskhip_ratecvt *r, const float *state);
 
+/*
+ * process() with both sides at a converter's outer rate (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): one FSKProcessor quantum
+ * whose input goes through `capture` and whose output through `playback` on the device, so a receiver bank behind sound cards or a
+ * WebAudio AudioContext at 44.1 kHz takes and gives its quanta as they are.  n_in and in_pitch count capture rate elements, n_out
+ * and out_pitch playback rate elements; n_in is a multiple of capture's down factor Mc, n_out of playback's up factor Lp: whole
+ * periods.  The quantum inside is n_in / Mc * Lc engine samples in and n_out / Lp * Mp engine samples out.  Formats, layouts and
+ * pitches are fskhip.h's, exactly as fskhip_processor_process_fmt_* take them.  The call IS, bit for bit,
+ *   fskhip_ratecvt_capture_device(capture, d_in, ..., X)  ->  fskhip_processor_process_device(p, X, n_in / Mc * Lc, ..., Y, n_out / Lp * Mp, ...)
+ *   ->  fskhip_ratecvt_playback_device(playback, Y, n_out / Lp * Mp, ..., d_lens = NULL, d_out, ...):
+ * the elements written, every word of processor and engine state and both handles' histories (fskhip_ratecvt_state_get) and
+ * ping-pong positions end as that chain leaves them, so any cut of a stream into legal quanta gives the same bytes and the same
+ * samples.  A side whose buffer is NULL is absent, as in process(): its handle is ignored (and may be NULL) and its history untouched.
+ *   RX  one capture launch writes into a float tile kept with the processor, the demodulators run on that.
+ *   TX  stream-major: one kernel generates the engine's samples, keeps them in an LDS delay line of ceil((n_taps - 1) / Lp) + 4
+ *       samples per stream, takes every output of the converter's sum from it as soon as its newest input is written, encodes and
+ *       stores: the engine rate floats never reach memory.  A converter too long for that delay line (its history beyond some 240
+ *       samples per stream; the default 147 / 160 design needs 22), and interleaved frames, take two launches through a float tile
+ *       kept with the processor, with the same results.
+ * FSKHIP_PROC_GRAPH is ignored, as for the fskhip_processor_process_rate_* forms and for their reason;
+ * FSKHIP_PROC_CLEAR_RX_ON_TX_COMPLETE means what it means in process().  The _host form stages the outer rate samples as
+ * fskhip_processor_process_fmt_host stages its own and synchronises at the end.
+ * FSKHIP_E_INVALID before any device call, in this order: a null processor; an unknown format, then layout, the input side first
+ * (whether or not the side is NULL); for each side that has a buffer, the input side first: a null handle, a handle of the wrong
+ * direction, one whose fskhip_ratecvt_streams is not the processor's, one on another device; a pitch that is too small, in before
+ * out; a pointer that is not aligned to its element; an n_in that is no multiple of Mc, then an n_out that is no multiple of Lp
+ * (each for a side that has a buffer).  A refused call leaves the processor and both histories as they were.
+ */
+int fskhip_processor_process_ratecvt_device(fskhip_processor *p, fskhip_ratecvt *capture, fskhip_ratecvt *playback, const void *d_in,
+                                            int in_format, int in_layout, size_t n_in, size_t in_pitch, void *d_out, int out_format,
+                                            int out_layout, size_t n_out, size_t out_pitch, uint32_t flags, void *hip_stream);
+int fskhip_processor_process_ratecvt_host(fskhip_processor *p, fskhip_ratecvt *capture, fskhip_ratecvt *playback, const void *in,
+                                          int in_format, int in_layout, size_t n_in, size_t in_pitch, void *out, int out_format,
+                                          int out_layout, size_t n_out, size_t out_pitch, uint32_t flags);
+
 /* ---------------------------------------------------------------------------------------------------
  * IIR half of src/dsp/filters.ts: IIRFilter (8-106) batched over streams, + FilterFactory.createIIR* (325-344; the
  * designs themselves are fskhip_butterworth_* in fskhip.h).  Inside the demodulator the same filter lives as three

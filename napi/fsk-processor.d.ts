@@ -1,6 +1,6 @@
 // Typings of napi/fsk-processor.js and napi/chunked-modulator.js (src/webaudio/processors/fsk-processor.ts,
 // src/webaudio/chunked-modulator.ts on the device).
-import { Downsampler, Upsampler } from './filters';
+import { CaptureConverter, Downsampler, PlaybackConverter, Upsampler } from './filters';
 import { FSKBatch, FSKConfig, FSKCore, FSKStatus, SampleArray, SampleFormat, SampleLayout } from './fsk-core';
 export declare const PROC_CLEAR_RX_ON_TX_COMPLETE: 1;
 export declare const PROC_GRAPH: 2;
@@ -17,10 +17,13 @@ export declare class FSKProcessorBatch {
   processSamples(inputs: SampleArray | null, input?: { format?: SampleFormat; layout?: SampleLayout; nIn?: number; pitch?: number },
     output?: { format?: SampleFormat; layout?: SampleLayout; nOut?: number; pitch?: number }): SampleArray | null;
   /** processSamples() with both sides at the trunk's own rate, through an Upsampler / Downsampler of filters.js that carry their histories:
-   *  nIn, nOut and the pitches count low rate elements; format defaults to 'mulaw', layout to 'sample'; a side without samples needs no handle */
+   *  nIn, nOut and the pitches count low rate elements; format defaults to 'mulaw', layout to 'sample'; a side without samples needs no handle.
+   *  With a CaptureConverter / PlaybackConverter in the two slots both sides are at the converters' outer rate (44.1 kHz either side of a
+   *  48 kHz engine): nIn is a multiple of the capture converter's `down`, nOut of the playback converter's `up`; one call takes resamplers
+   *  or converters, not one of each */
   processSamplesAt(inputs: SampleArray | null,
-    input?: { format?: SampleFormat; layout?: SampleLayout; nIn?: number; pitch?: number; upsampler?: Upsampler },
-    output?: { format?: SampleFormat; layout?: SampleLayout; nOut?: number; pitch?: number; downsampler?: Downsampler }): SampleArray | null;
+    input?: { format?: SampleFormat; layout?: SampleLayout; nIn?: number; pitch?: number; upsampler?: Upsampler | CaptureConverter },
+    output?: { format?: SampleFormat; layout?: SampleLayout; nOut?: number; pitch?: number; downsampler?: Downsampler | PlaybackConverter }): SampleArray | null;
   /** 'modulate': throws 'Modulation already in progress' when a selected stream still has one */
   modulate(payloads: Uint8Array[], mask?: boolean[]): void;
   txState(): { pos: Uint32Array; total: Uint32Array; pending: Uint8Array; completed: Uint32Array };

@@ -7,7 +7,7 @@
 const path = require('path');
 const addon = require(path.join(__dirname, 'fsk_addon.node'));
 const { FSKBatch, sampleFormat, sampleLayout } = require(path.join(__dirname, 'fsk-core.js'));
-const { Upsampler, Downsampler } = require(path.join(__dirname, 'filters.js'));
+const { Upsampler, Downsampler, CaptureConverter, PlaybackConverter } = require(path.join(__dirname, 'filters.js'));
 const { busyError } = require(path.join(__dirname, 'errors.js'));
 const PROC_CLEAR_RX_ON_TX_COMPLETE = 1, PROC_GRAPH = 2;
 
@@ -101,7 +101,9 @@ class FSKProcessorBatch {
   // the inputs in front of the demodulator and decimate the pending modulation on the device; lengths and pitches count low rate
   // elements, format defaults to 'mulaw' and layout to 'sample' (interleaved frames).  Both handles carry their histories from call
   // to call; state and samples are those of Upsampler.process -> process() -> Downsampler.process, bit for bit.  A side without
-  // samples needs no handle.
+  // samples needs no handle.  With a CaptureConverter as upsampler and a PlaybackConverter as downsampler both sides are at the
+  // converters' outer rate (44.1 kHz either side of a 48 kHz engine; fskhip_processor_process_ratecvt_host): nIn a multiple of the
+  // capture converter's down, nOut of the playback converter's up; one call takes resamplers or converters, not one of each.
   processSamplesAt(inputs, input = {}, output = {}) {
     if (input === null || typeof input !== 'object' || output === null || typeof output !== 'object') {
       throw new TypeError('processSamplesAt: input and output must be objects {format, layout, nIn | nOut, pitch, upsampler | downsampler}');
@@ -118,13 +120,25 @@ class FSKProcessorBatch {
     const nIn = has ? count(input.nIn, 'nIn') : 0, nOut = count(output.nOut, 'nOut');
     const inPitch = count(input.pitch, 'input pitch') || (inLay ? this.nStreams : nIn);
     const outPitch = count(output.pitch, 'output pitch') || (outLay ? this.nStreams : nOut);
-    const handle = (r, kind, what) => {
-      if (!(r instanceof kind)) throw new TypeError('processSamplesAt: ' + what + ' must be an ' + kind.name + ' of filters.js');
+    const handle = (r, kind, converter, what) => {     // (a converter of the side's direction stands in its resampler's place)
+      if (!(r instanceof kind) && !(r instanceof converter)) throw new TypeError('processSamplesAt: ' + what + ' must be an ' + kind.name + ' of filters.js');
       if (r.nStreams !== this.nStreams) throw new RangeError('processSamplesAt: ' + what + ' has ' + r.nStreams + ' streams, the batch ' + this.nStreams);
       return r.handle;
     };
-    const up = has ? handle(input.upsampler, Upsampler, 'upsampler') : null;
-    const down = nOut ? handle(output.downsampler, Downsampler, 'downsampler') : null;
+    const up = has ? handle(input.upsampler, Upsampler, CaptureConverter, 'upsampler') : null;
+    const down = nOut ? handle(output.downsampler, Downsampler, PlaybackConverter, 'downsampler') : null;
+    // converters: both sides at their outer rate (fskhip_processor_process_ratecvt_host), in whole periods; one call takes one kind
+    const capture = has && input.upsampler instanceof CaptureConverter, playback = nOut > 0 && output.downsampler instanceof PlaybackConverter;
+    if (has && nOut && capture !== playback) {
+      throw new TypeError('processSamplesAt: upsampler is a ' + input.upsampler.constructor.name + ' and downsampler a ' + output.downsampler.constructor.name +
+        ': one call takes resamplers or rate converters, not one of each');
+    }
+    if (capture && nIn % input.upsampler.down) {
+      throw new RangeError('processSamplesAt: ' + nIn + ' samples per stream are not a multiple of the converter\'s down factor ' + input.upsampler.down);
+    }
+    if (playback && nOut % output.downsampler.up) {
+      throw new RangeError('processSamplesAt: nOut ' + nOut + ' is not a multiple of the converter\'s up factor ' + output.downsampler.up);
+    }
     if (has) this.processDemodulationCallCount++;      // (as process() counts: behind the argument checks, in front of the call)
     return addon.processorProcessSamplesAt(this.handle, up, down, has ? inputs : null, inFmt, inLay, nIn, inPitch, outFmt, outLay, nOut, outPitch, this.flags);
   }

@@ -1052,8 +1052,16 @@ napi_value ResamplerDown(napi_env env, napi_callback_info info) { return rate_na
 napi_value ResamplerReset(napi_env env, napi_callback_info info) { return rate_reset(env, info, kResampler); }
 napi_value ResamplerState(napi_env env, napi_callback_info info) { return rate_state(env, info, kResampler); }
 napi_value ResamplerSetState(napi_env env, napi_callback_info info) { return rate_set_state(env, info, kResampler); }
-// process() with both sides at a low rate (fskhip_processor_process_rate_host): ProcessorProcessSamples with the two resampler handles in
-// front of the samples; lengths and pitches count low rate elements.  A handle is looked at only where its side has samples.
+// process() with both sides at an outer rate: ProcessorProcessSamples with the two handles in front of the samples; lengths and pitches
+// count outer rate elements.  Resampler handles go to fskhip_processor_process_rate_host, rate converter handles to
+// fskhip_processor_process_ratecvt_host; one call takes one kind.  A handle is looked at only where its side has samples.
+FilterBox *rate_box_of(napi_env env, napi_value v) {
+  FilterBox *b = (FilterBox *)external(env, v, "filter destroyed");
+  if (!b) return nullptr;
+  if (!b->p) { napi_throw_error(env, nullptr, "filter destroyed"); return nullptr; }
+  if (b->kind != BOX_RESAMPLER && b->kind != BOX_RATECVT) { napi_throw_type_error(env, nullptr, "not a resampler or rate converter handle"); return nullptr; }
+  return b;
+}
 napi_value ProcessorProcessSamplesAt(napi_env env, napi_callback_info info) {
   ARGS(13);
   const int32_t in_format = i32(env, argv[4]), in_layout = i32(env, argv[5]), out_format = i32(env, argv[8]), out_layout = i32(env, argv[9]);
@@ -1063,10 +1071,10 @@ napi_value ProcessorProcessSamplesAt(napi_env env, napi_callback_info info) {
   void *in; size_t ilen;
   if (!typed(env, argv[3], sample_array_type(in_format), &in, &ilen, true)) return nullptr;
   const uint32_t n_in = u32(env, argv[6]), in_pitch = u32(env, argv[7]), n_out = u32(env, argv[10]), out_pitch = u32(env, argv[11]), flags = u32(env, argv[12]);
-  fskhip_resampler *up = nullptr, *down = nullptr;
+  FilterBox *up = nullptr, *down = nullptr;
   if (in) {
     if (nullish(env, argv[1])) { napi_throw_type_error(env, nullptr, "input samples need an upsampler"); return nullptr; }
-    if (!(up = (fskhip_resampler *)filter_of(env, argv[1]))) return nullptr;
+    if (!(up = rate_box_of(env, argv[1]))) return nullptr;
     const int64_t need = samples_needed(in_layout, h->S, n_in, in_pitch);
     if (need < 0 || (size_t)need > ilen) { napi_throw_range_error(env, nullptr, "input too short"); return nullptr; }
   }
@@ -1074,14 +1082,20 @@ napi_value ProcessorProcessSamplesAt(napi_env env, napi_callback_info info) {
   napi_value out_v = nullptr;
   if (n_out) {
     if (nullish(env, argv[2])) { napi_throw_type_error(env, nullptr, "output samples need a downsampler"); return nullptr; }
-    if (!(down = (fskhip_resampler *)filter_of(env, argv[2]))) return nullptr;
+    if (!(down = rate_box_of(env, argv[2]))) return nullptr;
+    if (up && up->kind != down->kind) { napi_throw_type_error(env, nullptr, "one call takes resamplers or rate converters, not one of each"); return nullptr; }
     const int64_t need = samples_needed(out_layout, h->S, n_out, out_pitch);
     if (need < 0) { napi_throw_range_error(env, nullptr, "output pitch too small"); return nullptr; }
     out_v = make_typed(env, sample_array_type(out_format), (size_t)need, fskhip_sample_bytes(out_format), &out);
     if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
     fill_silence(out_format, out, (size_t)need);
   }
-  int rc = fskhip_processor_process_rate_host(h->p, up, down, in, in_format, in_layout, n_in, in_pitch, out, out_format, out_layout, n_out, out_pitch, flags);
+  void *const uh = up ? up->p : nullptr, *const dh = down ? down->p : nullptr;
+  const bool cvt = (up ? up : down) && (up ? up : down)->kind == BOX_RATECVT;
+  int rc = cvt ? fskhip_processor_process_ratecvt_host(h->p, (fskhip_ratecvt *)uh, (fskhip_ratecvt *)dh, in, in_format, in_layout, n_in, in_pitch, out, out_format,
+                                                       out_layout, n_out, out_pitch, flags)
+               : fskhip_processor_process_rate_host(h->p, (fskhip_resampler *)uh, (fskhip_resampler *)dh, in, in_format, in_layout, n_in, in_pitch, out, out_format,
+                                                    out_layout, n_out, out_pitch, flags);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   if (!out_v) napi_get_null(env, &out_v);
   return out_v;

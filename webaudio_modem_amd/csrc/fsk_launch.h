@@ -103,6 +103,15 @@ hipError_t launch_processor_io_fmt(const ModParams &M, const double *coef, const
 hipError_t launch_processor_io_rate(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out, size_t demod_pitch, const uint32_t *demod_counts,
                                     bool do_rx, void *out, int format, int layout, size_t n_out, size_t out_pitch, bool clear_rx_on_complete, int precision,
                                     uint32_t factor, uint32_t n_taps, const void *d_taps, const float *d_hist_in, float *d_hist_out, hipStream_t st);
+// the same quantum with `out` behind a playback converter (fskhip_processor_process_ratecvt_*): n_out > 0 outputs per stream, a
+// multiple of `up`, of the n_out / up * down samples the generator makes, filtered as launch_ratecvt's playback direction does
+// (d_taps [K][up] in output order in `precision`, histories [n_streams][ceil((n_taps - 1) / up)], d_hist_in read and d_hist_out
+// written) and encoded, in one launch.  hipErrorInvalidValue where processor_ratecvt_plan (fsk_processor_rate_plan.h) does not
+// fuse the filter or the layout: the caller runs launch_processor_io and launch_ratecvt.
+hipError_t launch_processor_io_ratecvt(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out, size_t demod_pitch,
+                                       const uint32_t *demod_counts, bool do_rx, void *out, int format, int layout, size_t n_out, size_t out_pitch,
+                                       bool clear_rx_on_complete, int precision, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps,
+                                       const float *d_hist_in, float *d_hist_out, hipStream_t st);
 hipError_t launch_processor_tx_start(const ModParams &M, const ProcState &T, const uint8_t *payloads, const uint32_t *lens, size_t payload_pitch, const uint8_t *mask,
                                      hipStream_t st);
 hipError_t launch_processor_rx_drain(const ProcState &T, uint32_t n_streams, uint8_t *out, size_t out_pitch, uint32_t *counts, hipStream_t st);
@@ -141,6 +150,14 @@ hipError_t launch_resample_up(int precision, const void *d_src, int format, int 
 hipError_t launch_resample_down(int precision, const float *d_src, size_t n_out, size_t src_pitch, const uint32_t *d_lens, uint32_t n_streams, void *d_dst,
                                 int format, int layout, size_t dst_pitch, uint32_t factor, uint32_t n_taps, const void *d_taps, const float *d_hist_in,
                                 float *d_hist_out, hipStream_t st);
+// fsk_ratecvt.hip: rate conversion by up / down (fskhip_ratecvt_*), one launch of either direction (FSKHIP_RATECVT_*).  CAPTURE reads
+// d_src in the format and layout and writes float32 rows to d_dst, PLAYBACK the other way round with d_lens as launch_resample_down
+// takes it; n_in > 0 inputs per stream, a multiple of `down`; d_taps [ceil(n_taps / up)][up] in output order and d_table
+// (fsk_ratecvt_plan.h), histories [n_streams][ceil((n_taps - 1) / up)].  The caller has checked the arguments;
+// hipErrorInvalidValue where the batch is more workgroups than one launch takes.
+hipError_t launch_ratecvt(int direction, int precision, const void *d_src, size_t src_pitch, const uint32_t *d_lens, void *d_dst, size_t dst_pitch, int format,
+                          int layout, uint32_t n_streams, size_t n_in, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps, const uint32_t *d_table,
+                          const float *d_hist_in, float *d_hist_out, hipStream_t st);
 // fsk_resample_remap.hip: a resampler's history rows (H floats at a pitch of H floats, both bases 16-byte aligned) gathered through
 // a map (fskhip_resampler_remap / _snapshot / _restore).  Row i of d_dst (n_rows rows) takes row d_map[i] of d_src -- row
 // ident0 + i where d_map is null --, zeros where the entry is -1.  from_image: d_src is a staging slab holding records

@@ -831,6 +831,148 @@ __global__ __launch_bounds__(64) void processor_io_rate_kernel(ModParams M, cons
   if (rx_dirty && valid) { T.rx_w[stream] = w; T.rx_r[stream] = r; T.rx_len[stream] = len; }
 }
 
+// The same quantum with the output behind a playback converter (fskhip_processor_process_ratecvt_*): the rational counterpart of
+// processor_io_rate_kernel, in its shape -- one wave per 64 streams, lane = stream, processor_io_kernel's bookkeeping and generator
+// statement for statement, the samples in the [slot][lane] delay line, the codes out through the packed code rows, the history read
+// at entry and written at exit, coalesced.  The filter is ratecvt_playback_kernel's (fsk_ratecvt.hip) with up factor Lu and down
+// factor Md: output j has phase p = (j Md) mod Lu and newest input m = (j Md) div Lu, both kept by wave-uniform integer
+// accumulators, and is taken as soon as sample m is written -- one sample may complete none, one or several outputs.  Its sum is
+// that kernel's: the k_full = n_taps / Lu products every phase has, k ascending, then the one more of a phase p < n_taps mod Lu,
+// `mac` in the handle's precision, the taps from the [K][Lu] table in output order (column j mod Lu; wave-uniform, scalar loads) --
+// the same float, bit for bit.  The handle's history is H = ceil((n_taps - 1) / Lu) samples per stream, and the sum reaches back at
+// most H from m, so the delay line is H + kRateChunk slots (fsk_processor_rate_plan.h: processor_ratecvt_plan).
+// The launcher has seen to n_out > 0 a multiple of Lu, `slots` >= H + kRateChunk and the LDS for it.
+template <bool EXACT, typename Real, int FMT>
+__global__ __launch_bounds__(64) void processor_io_ratecvt_kernel(ModParams M, const double *__restrict__ coef, ProcState T,
+                                                                  const uint8_t *__restrict__ demod_out, size_t demod_pitch,
+                                                                  const uint32_t *__restrict__ demod_counts, int do_rx,
+                                                                  void *__restrict__ out_, size_t n_out, size_t out_pitch, int vec_ok,
+                                                                  uint32_t clear_rx_on_complete, const float *__restrict__ hist_in,
+                                                                  float *__restrict__ hist_out, const void *__restrict__ taps_, uint32_t Lu,
+                                                                  uint32_t Md, uint32_t n_taps, uint32_t slots) {
+  using F = SampleFmt<FMT>;
+  using Bits = typename F::Bits;
+  static_assert(kRateCodeTile == (uint32_t)kTile && kRateChunk == 4u, "the code rows are store_code_rows', the generator's step frame_next4's");
+  constexpr uint32_t kPitch = kRateLanePitch;
+  constexpr uint32_t kRowPitch = (uint32_t)kTile * (uint32_t)sizeof(Bits) / 4u + 1u;
+  extern __shared__ __align__(16) unsigned char rate_lds[];
+  float *const dl = reinterpret_cast<float *>(rate_lds);               // [slots][kPitch]
+  uint32_t *const codes = reinterpret_cast<uint32_t *>(dl + (size_t)slots * kPitch);   // [64][kRowPitch]
+  const uint32_t lane = threadIdx.x;
+  const uint32_t stream = blockIdx.x * 64u + lane;
+  const bool valid = stream < M.n_streams;
+  const uint32_t row = valid ? stream : M.n_streams - 1;
+  const size_t ns = M.n_streams;
+
+  uint32_t w = T.rx_w[row], r = T.rx_r[row], len = T.rx_len[row];
+  bool rx_dirty = false;
+  if (do_rx && valid) {
+    uint32_t cnt = demod_counts[stream];
+    if ((size_t)cnt > demod_pitch) cnt = (uint32_t)demod_pitch;
+    const uint8_t *src = demod_out + (size_t)stream * demod_pitch;
+    uint8_t *ring = T.rx_buf + (size_t)stream * T.rx_cap;
+    for (uint32_t i = 0; i < cnt; i++) {  // put(): overwrite the oldest when full
+      ring[w] = src[i];
+      w = w + 1 == T.rx_cap ? 0u : w + 1;
+      if (len < T.rx_cap) len++;
+      else r = r + 1 == T.rx_cap ? 0u : r + 1;
+    }
+    rx_dirty = cnt != 0;
+  }
+
+  {
+    const uint32_t flen = T.tx_len[row];
+    const bool active = valid && T.tx_pending[row] != 0u && flen > 0u && T.tx_pos[row] < flen;
+    const uint8_t *prow = T.tx_payload + (size_t)row * T.tx_payload_pitch;
+    auto pb = [&](uint32_t i) -> uint8_t { return prow[i]; };
+    FrameGen G;
+    G.start(M, coef[(size_t)CF_mark_w * ns + row], coef[(size_t)CF_space_w * ns + row], T.tx_n_payload[row]);
+    if (active) {
+      G.phase = T.tx_phase[row]; G.pos = T.tx_pos[row]; G.in_bit = T.tx_in_bit[row];
+      G.bit_idx = T.tx_bit_idx[row]; G.cur_bit = T.tx_cur_bit[row];
+    } else {
+      G.pos = G.frame_len;  // nothing to emit: zeros
+    }
+    Bits *const out = (Bits *)out_;
+    const Real *const taps = (const Real *)taps_;                      // [K][Lu], column q: the taps of output q of a period
+    const uint32_t H = (n_taps - 1u + Lu - 1u) / Lu;
+    const uint32_t k_full = n_taps / Lu, rem = n_taps - k_full * Lu;   // phase p has k_full + (p < rem) taps
+    // the history: sample -H + h of the quantum at slot h; streams past the batch hold zeros
+    for (uint32_t c = 0; c < 64u; c++) {
+      const uint32_t s = blockIdx.x * 64u + c;
+      for (uint32_t h = lane; h < H; h += 64u) dl[h * kPitch + c] = s < M.n_streams ? hist_in[(size_t)s * H + h] : 0.0f;
+    }
+    __syncthreads();
+    const size_t n_high = n_out / Lu * Md;
+    uint32_t wslot = H;        // the slot of sample t0: (H + t0) mod slots
+    size_t k = 0;              // the next output
+    uint32_t q = 0, ph = 0;    // k mod Lu, (k Md) mod Lu
+    size_t m = 0;              // (k Md) div Lu: the sample that completes output k
+    for (size_t t0 = 0; t0 < n_high; t0 += kRateChunk) {
+      // samples beyond n_high inside the last step must not advance the generator
+      const float4 v = frame_next4<EXACT>(G, M, pb, t0 + 0 < n_high, t0 + 1 < n_high, t0 + 2 < n_high, t0 + 3 < n_high);
+      const float o[4] = {v.x, v.y, v.z, v.w};
+      const uint32_t cnt = n_high - t0 < kRateChunk ? (uint32_t)(n_high - t0) : kRateChunk;
+      uint32_t sl = wslot;
+#pragma unroll
+      for (uint32_t j = 0; j < kRateChunk; j++) {
+        if (j < cnt) {
+          dl[sl * kPitch + lane] = o[j];
+          sl = sl + 1u == slots ? 0u : sl + 1u;
+        }
+      }
+      while (k < n_out && m < t0 + cnt) {   // every output the step has completed: input m - i at the slot i behind m's
+        uint32_t si = wslot + (uint32_t)(m - t0);
+        si = si >= slots ? si - slots : si;
+        const Real *tp = taps + q;
+        Real acc = 0;
+#pragma unroll 4
+        for (uint32_t i = 0; i < k_full; i++) {
+          acc = mac(acc, tp[(size_t)i * Lu], dl[si * kPitch + lane]);
+          si = si == 0u ? slots - 1u : si - 1u;
+        }
+        if (ph < rem) acc = mac(acc, tp[(size_t)k_full * Lu], dl[si * kPitch + lane]);
+        const uint32_t code = F::encode((float)acc);
+        const uint32_t kk = (uint32_t)(k & (size_t)(kTile - 1));
+        reinterpret_cast<Bits *>(codes + lane * kRowPitch)[kk] = (Bits)code;
+        if (kk == (uint32_t)kTile - 1u || k + 1 == n_out) {
+          __syncthreads();
+          store_code_rows(codes, out, out_pitch, k - kk, n_out, M.n_streams, vec_ok, lane);
+          __syncthreads();   // (the rows' readers, before the next tile's codes)
+        }
+        k++;
+        q = q + 1u == Lu ? 0u : q + 1u;
+        ph += Md;
+        while (ph >= Lu) { ph -= Lu; m++; }
+      }
+      wslot = sl;
+    }
+    // the history after the call: samples n_high - H + h, at slot (n_high + h) mod slots
+    __syncthreads();
+    const uint32_t hbase = (uint32_t)(n_high % slots);
+    for (uint32_t c = 0; c < 64u; c++) {
+      const uint32_t s = blockIdx.x * 64u + c;
+      if (s >= M.n_streams) break;
+      for (uint32_t h = lane; h < H; h += 64u) {
+        uint32_t si = hbase + h;
+        si = si >= slots ? si - slots : si;
+        hist_out[(size_t)s * H + h] = dl[si * kPitch + c];
+      }
+    }
+    if (active) {
+      if (G.pos >= flen) {  // isComplete: ChunkedModulator.reset() + pendingModulation = null
+        T.tx_pos[stream] = 0u; T.tx_len[stream] = 0u; T.tx_pending[stream] = 0u;
+        T.tx_completed[stream] += 1u;
+        if (clear_rx_on_complete) { w = 0u; r = 0u; len = 0u; rx_dirty = true; }
+      } else {
+        T.tx_phase[stream] = G.phase; T.tx_pos[stream] = G.pos; T.tx_in_bit[stream] = G.in_bit;
+        T.tx_bit_idx[stream] = G.bit_idx; T.tx_cur_bit[stream] = G.cur_bit;
+      }
+    }
+  }
+  if (rx_dirty && valid) { T.rx_w[stream] = w; T.rx_r[stream] = r; T.rx_len[stream] = len; }
+}
+
 // startModulation() for the selected streams: take the payload, arm the generator at sample 0
 __global__ void processor_tx_start_kernel(ModParams M, ProcState T, const uint8_t *__restrict__ payloads,
                                           const uint32_t *__restrict__ lens, size_t payload_pitch,
@@ -936,6 +1078,29 @@ hipError_t launch_processor_io_rate(const ModParams &M, const double *coef, cons
   hipLaunchKernelGGL(kIoRateKernels[M.exact_sin ? 1 : 0][precision == FSKHIP_PRECISION_F64 ? 1 : 0][format].fn, dim3(blocks), dim3(64), P.lds_bytes, st, M,
                      coef, T, demod_out, demod_pitch, demod_counts, do_rx ? 1 : 0, out, n_out, out_pitch, vec_ok, clear_rx_on_complete ? 1u : 0u, d_hist_in,
                      d_hist_out, d_taps, factor, n_taps, P.slots);
+  return hipGetLastError();
+}
+// every instantiation behind a playback converter, once: [exact sine][the converter's precision][format], as above
+#define FSK_IO_RATECVT_KERNELS(EXACT, R) \
+  {FSK_K(processor_io_ratecvt_kernel, EXACT, R, FSKHIP_SAMPLES_F32), FSK_K(processor_io_ratecvt_kernel, EXACT, R, FSKHIP_SAMPLES_S16), \
+   FSK_K(processor_io_ratecvt_kernel, EXACT, R, FSKHIP_SAMPLES_MULAW), FSK_K(processor_io_ratecvt_kernel, EXACT, R, FSKHIP_SAMPLES_ALAW)}
+using IoRatecvtFn = void (*)(ModParams, const double *, ProcState, const uint8_t *, size_t, const uint32_t *, int, void *, size_t, size_t, int, uint32_t, const float *,
+                             float *, const void *, uint32_t, uint32_t, uint32_t, uint32_t);
+static const KernelEntry<IoRatecvtFn> kIoRatecvtKernels[2][2][4] = {{FSK_IO_RATECVT_KERNELS(false, float), FSK_IO_RATECVT_KERNELS(false, double)},
+                                                                    {FSK_IO_RATECVT_KERNELS(true, float), FSK_IO_RATECVT_KERNELS(true, double)}};
+
+hipError_t launch_processor_io_ratecvt(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out, size_t demod_pitch,
+                                       const uint32_t *demod_counts, bool do_rx, void *out, int format, int layout, size_t n_out, size_t out_pitch,
+                                       bool clear_rx_on_complete, int precision, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps,
+                                       const float *d_hist_in, float *d_hist_out, hipStream_t st) {
+  const size_t esz = sample_bytes(format);
+  const RatePlan P = processor_ratecvt_plan(up, n_taps, (uint32_t)esz, layout == FSKHIP_LAYOUT_STREAM_MAJOR);
+  if (!out || n_out == 0 || n_out % up != 0 || !P.fused) return hipErrorInvalidValue;
+  const uint32_t blocks = (M.n_streams + 63u) / 64u;
+  const int vec_ok = (out_pitch * esz % 16 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15u) == 0);
+  hipLaunchKernelGGL(kIoRatecvtKernels[M.exact_sin ? 1 : 0][precision == FSKHIP_PRECISION_F64 ? 1 : 0][format].fn, dim3(blocks), dim3(64), P.lds_bytes, st, M,
+                     coef, T, demod_out, demod_pitch, demod_counts, do_rx ? 1 : 0, out, n_out, out_pitch, vec_ok, clear_rx_on_complete ? 1u : 0u, d_hist_in,
+                     d_hist_out, d_taps, up, down, n_taps, P.slots);
   return hipGetLastError();
 }
 hipError_t launch_processor_tx_start(const ModParams &M, const ProcState &T, const uint8_t *payloads, const uint32_t *lens,

@@ -1,5 +1,6 @@
-// fsk_processor_rate_plan.h -- how fskhip_processor_process_rate_* (fsk_processor_rate.hip) runs its TX side, in plain C++ so that
-// it also compiles without HIP (tests/cpp/processor_rate_plan_check.cpp).  Not part of the ABI.
+// fsk_processor_rate_plan.h -- how fskhip_processor_process_rate_* (fsk_processor_rate.hip) and, at the end of the file,
+// fskhip_processor_process_ratecvt_* (fsk_processor_ratecvt.hip) run their TX sides, in plain C++ so that it also compiles without
+// HIP (tests/cpp/processor_rate_plan_check.cpp, processor_ratecvt_plan_check.cpp).  Not part of the ABI.
 //
 // The fused kernel (fsk_mod.hip: processor_io_rate_kernel) is one wave per 64 streams, lane = stream.  The generator's samples go
 // into a delay line in LDS, [slot][lane] with rows kRateLanePitch words apart, which at entry holds the decimator's history
@@ -36,6 +37,23 @@ inline uint32_t rate_code_pitch(uint32_t esz) { return kRateCodeTile * esz / 4u 
 inline RatePlan processor_rate_plan(uint32_t Ld, uint32_t n_taps, uint32_t esz, bool stream_major) {
   RatePlan P{};
   P.slots = n_taps - 1u + (Ld > kRateChunk ? Ld : kRateChunk);
+  P.code_words = 64u * rate_code_pitch(esz);
+  P.lds_bytes = sizeof(uint32_t) * ((size_t)P.slots * kRateLanePitch + P.code_words);
+  P.fits = P.lds_bytes <= kRateLdsBytes;
+  P.fused = P.fits && stream_major;
+  return P;
+}
+
+// The same for fskhip_processor_process_ratecvt_* (fsk_processor_ratecvt.hip) and its fused kernel (fsk_mod.hip:
+// processor_io_ratecvt_kernel), whose filter is a playback converter's (fsk_ratecvt_plan.h): up factor L, n_taps taps.  Output j's
+// newest input is m = (jM) div L and its sum reaches back K - 1 <= H = ceil((n_taps - 1) / L) inputs from there, so the delay line
+// holds the handle's history of H samples per stream and behind it the generator's step: H + kRateChunk slots, whatever M is --
+// an output is taken as soon as sample m is written, and no sample is written over before the outputs that end at most
+// kRateChunk - 1 samples before it have read their H samples back.  The pair is processor_io_kernel into a float tile, then
+// ratecvt_playback_kernel.
+inline RatePlan processor_ratecvt_plan(uint32_t L, uint32_t n_taps, uint32_t esz, bool stream_major) {
+  RatePlan P{};
+  P.slots = (n_taps - 1u + L - 1u) / L + kRateChunk;
   P.code_words = 64u * rate_code_pitch(esz);
   P.lds_bytes = sizeof(uint32_t) * ((size_t)P.slots * kRateLanePitch + P.code_words);
   P.fits = P.lds_bytes <= kRateLdsBytes;

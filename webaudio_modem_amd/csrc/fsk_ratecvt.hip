@@ -21,13 +21,9 @@
 #include "fsk_launch.h"
 #include "fsk_mac_dev.h"
 #include "fsk_rate_host.h"
+#include "fsk_ratecvt.h"
 #include "fsk_ratecvt_plan.h"
 #include "fsk_samples_dev.h"
-
-struct fskhip_ratecvt : fsk::RateHost {   // L: the up factor; H: resample_history(0, L, n_taps); the taps [K][L] in output order (fsk_ratecvt_plan.h)
-  uint32_t M = 1;                          // the down factor
-  uint32_t *d_table = nullptr;             // [L]: ratecvt_table_word
-};
 
 namespace fsk {
 namespace {
@@ -160,6 +156,19 @@ const KernelEntry<RatecvtFn> kRatecvtKernels[2][2][4][2] = {
     {FSK_FORMAT_KERNELS(ratecvt_playback_kernel, float), FSK_FORMAT_KERNELS(ratecvt_playback_kernel, double)}};
 
 }  // namespace
+
+hipError_t launch_ratecvt(int direction, int precision, const void *d_src, size_t src_pitch, const uint32_t *d_lens, void *d_dst, size_t dst_pitch, int format,
+                          int layout, uint32_t n_streams, size_t n_in, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps, const uint32_t *d_table,
+                          const float *d_hist_in, float *d_hist_out, hipStream_t st) {
+  const RatecvtPlan P = ratecvt_plan(layout == FSKHIP_LAYOUT_STREAM_MAJOR, direction == FSKHIP_RATECVT_PLAYBACK, up, down, n_taps, n_streams, n_in);
+  if (P.blocks == 0) return hipErrorInvalidValue;
+  const RatecvtShape G = {P.hist, P.G, P.rows, P.log2_ns, P.x_pitch, P.row_stride, P.span, P.seg_periods, P.split};
+  const KernelEntry<RatecvtFn> &k = kRatecvtKernels[direction][precision == FSKHIP_PRECISION_F64 ? 1 : 0][format][layout];
+  hipLaunchKernelGGL(k.fn, dim3((uint32_t)P.blocks), dim3(kResampleThreads), P.lds_bytes, st, d_src, src_pitch, d_lens, d_dst, dst_pitch, d_hist_in, d_hist_out, d_taps,
+                     d_table, n_streams, n_in, up, down, n_taps, G);
+  return hipGetLastError();
+}
+
 }  // namespace fsk
 
 using namespace fsk;
@@ -183,13 +192,10 @@ int process(fskhip_ratecvt *r, const char *who, int direction, bool host, int fo
   return rate_process(r, c, host, direction == FSKHIP_RATECVT_CAPTURE, src, src_pitch, lens, dst, dst_pitch, st,
                       [=](const void *d_src, size_t d_src_pitch, const uint32_t *d_lens, void *d_dst, size_t d_dst_pitch, hipStream_t s) {
     return rate_run(r, [=](const float *hist_in, float *hist_out) -> int {
-      const RatecvtPlan P = ratecvt_plan(layout == FSKHIP_LAYOUT_STREAM_MAJOR, r->direction == FSKHIP_RATECVT_PLAYBACK, r->L, r->M, r->n_taps, r->S, n_in);
-      if (P.blocks == 0) return rate_grid_fail(who, r->S, n_in);
-      const RatecvtShape G = {P.hist, P.G, P.rows, P.log2_ns, P.x_pitch, P.row_stride, P.span, P.seg_periods, P.split};
-      const KernelEntry<RatecvtFn> &k = kRatecvtKernels[r->direction][r->precision == FSKHIP_PRECISION_F64 ? 1 : 0][format][layout];
-      hipLaunchKernelGGL(k.fn, dim3((uint32_t)P.blocks), dim3(kResampleThreads), P.lds_bytes, s, d_src, d_src_pitch, d_lens, d_dst, d_dst_pitch, hist_in, hist_out,
-                         r->taps(), (const uint32_t *)r->d_table, r->S, n_in, r->L, r->M, r->n_taps, G);
-      HIP_TRY(hipGetLastError());
+      const hipError_t err = launch_ratecvt(r->direction, r->precision, d_src, d_src_pitch, d_lens, d_dst, d_dst_pitch, format, layout, r->S, n_in, r->L, r->M,
+                                            r->n_taps, r->taps(), r->d_table, hist_in, hist_out, s);
+      if (err == hipErrorInvalidValue) return rate_grid_fail(who, r->S, n_in);
+      HIP_TRY(err);
       return FSKHIP_OK;
     });
   });

@@ -224,7 +224,8 @@ class FSKProcessorBatch:
         """a side's resampler (filters.Upsampler / Downsampler) as fskhip_processor_process_rate_* wants it: of this batch's
         stream count and on its engine's device"""
         from . import filters
-        if not isinstance(handle, kind):
+        converter = {filters.Upsampler: filters.CaptureConverter, filters.Downsampler: filters.PlaybackConverter}[kind]
+        if not isinstance(handle, (kind, converter)):     # (a converter of the side's direction stands in its resampler's place)
             raise ValueError("%s must be a filters.%s, got %s" % (what, kind.__name__, type(handle).__name__))
         if handle.n_streams != self.n_streams:
             raise ValueError("%s has %d streams, the batch %d" % (what, handle.n_streams, self.n_streams))
@@ -233,6 +234,23 @@ class FSKProcessorBatch:
             raise ValueError("%s is on device %r, the batch on %r" % (what, handle.device, device))
         return handle._h
 
+    def _rate_entry(self, form, upsampler, n_in, downsampler, n_out):
+        """the library call of form "host" / "device" for the handles of the sides that have samples (None: the side has none):
+        fskhip_processor_process_rate_* for resamplers, fskhip_processor_process_ratecvt_* for converters (filters.CaptureConverter /
+        PlaybackConverter), whose counts are whole periods.  One call takes one kind."""
+        from . import filters
+        kinds = [isinstance(h, filters._RateConverter) for h in (upsampler, downsampler) if h is not None]
+        if len(set(kinds)) > 1:
+            raise ValueError("upsampler is a %s and downsampler a %s: one call takes resamplers or rate converters, not one of each"
+                             % (type(upsampler).__name__, type(downsampler).__name__))
+        if not any(kinds):
+            return getattr(self._L, "fskhip_processor_process_rate_" + form)
+        if upsampler is not None and n_in % upsampler.down:
+            raise ValueError("%d samples per stream are not a multiple of the converter's down factor %d" % (n_in, upsampler.down))
+        if downsampler is not None and n_out % downsampler.up:
+            raise ValueError("n_out %d is not a multiple of the converter's up factor %d" % (n_out, downsampler.up))
+        return getattr(self._L, "fskhip_processor_process_ratecvt_" + form)
+
     def process_samples_at(self, inputs=None, in_fmt="mulaw", in_layout="sample", upsampler=None, n_out=0, out_fmt="mulaw", out_layout="sample",
                            downsampler=None):
         """process_samples() with both sides at the trunk's own rate: fskhip_processor_process_rate_host.  inputs (or None) are
@@ -240,7 +258,13 @@ class FSKProcessorBatch:
         returned samples are the pending modulation decimated by `downsampler` (filters.Downsampler), which one kernel generates,
         filters and encodes.  Both handles carry their histories from call to call, so any cut of a stream into quanta gives the
         same bytes and samples; the state ends as Upsampler.process -> process() -> Downsampler.process leaves it, bit for bit.
-        A side without samples needs no handle."""
+        A side without samples needs no handle.
+
+        With a filters.CaptureConverter as `upsampler` and a filters.PlaybackConverter as `downsampler` both sides are at the
+        converters' outer rate -- 44.1 kHz either side of a 48 kHz engine -- through fskhip_processor_process_ratecvt_host: the
+        inputs are a multiple of the capture converter's `down` samples per stream, n_out a multiple of the playback
+        converter's `up`, and the state ends as CaptureConverter.process -> process() -> PlaybackConverter.process leaves it,
+        bit for bit.  One call takes resamplers or converters, not one of each."""
         from . import filters
         in_code, in_lay = _sample_codes(in_fmt, in_layout)
         out_code, out_lay = _sample_codes(out_fmt, out_layout)      # (every argument check comes before the call is counted)
@@ -252,13 +276,15 @@ class FSKProcessorBatch:
             if S != self.n_streams:
                 raise ValueError("inputs must be [n_streams, n] (layout 'stream') or [n, n_streams] (layout 'sample')")
             up_h = self._rate_handle(upsampler, filters.Upsampler, "upsampler")
-        out, out_pitch = None, 0
         if n_out:
             down_h = self._rate_handle(downsampler, filters.Downsampler, "downsampler")
+        entry = self._rate_entry("host", upsampler if inputs is not None else None, n_in, downsampler if n_out else None, int(n_out))
+        out, out_pitch = None, 0
+        if n_out:
             out, out_code, out_lay, out_pitch = samples_out(out_fmt, out_layout, self.n_streams, int(n_out))
         if inputs is not None:
             self.processDemodulationCallCount += 1
-        _lib.check(self._L.fskhip_processor_process_rate_host(
+        _lib.check(entry(
             self._h, up_h, down_h, x.ctypes.data if x is not None else None, in_code, in_lay, n_in, in_pitch,
             out.ctypes.data if out is not None else None, out_code, out_lay, int(n_out), out_pitch, self.flags))
         return out
@@ -266,13 +292,14 @@ class FSKProcessorBatch:
     def process_samples_at_device(self, d_in, in_fmt, in_layout, n_in, in_pitch, upsampler, d_out, out_fmt, out_layout, n_out, out_pitch, downsampler,
                                   stream=None, flags=None):
         """fskhip_processor_process_rate_device: device pointers (ints or None), lengths and pitches in low rate elements,
-        asynchronous on `stream`.  The handle of a side whose pointer is None may be None."""
+        asynchronous on `stream`.  The handle of a side whose pointer is None may be None.  With converters
+        (filters.CaptureConverter / PlaybackConverter) it is fskhip_processor_process_ratecvt_device, as in process_samples_at."""
         from . import filters
         up_h = None if d_in is None and upsampler is None else self._rate_handle(upsampler, filters.Upsampler, "upsampler")
         down_h = None if d_out is None and downsampler is None else self._rate_handle(downsampler, filters.Downsampler, "downsampler")
-        _lib.check(self._L.fskhip_processor_process_rate_device(self._h, up_h, down_h, d_in, *_sample_codes(in_fmt, in_layout, True), n_in, in_pitch,
-                                                                d_out, *_sample_codes(out_fmt, out_layout, True), n_out, out_pitch,
-                                                                self.flags if flags is None else flags, stream))
+        entry = self._rate_entry("device", None if d_in is None else upsampler, n_in, None if d_out is None else downsampler, n_out)
+        _lib.check(entry(self._h, up_h, down_h, d_in, *_sample_codes(in_fmt, in_layout, True), n_in, in_pitch,
+                         d_out, *_sample_codes(out_fmt, out_layout, True), n_out, out_pitch, self.flags if flags is None else flags, stream))
 
     # ---- 'modulate' fsk-processor.ts:87-113 ------------------------------------------------------------
     def modulate(self, payloads, mask=None):
