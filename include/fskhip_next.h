@@ -923,6 +923,60 @@ int fskhip_processor_process_ratecvt_host(fskhip_processor *p, fskhip_ratecvt *c
                                           int in_format, int in_layout, size_t n_in, size_t in_pitch, void *out, int out_format,
                                           int out_layout, size_t n_out, size_t out_pitch, uint32_t flags);
 
+/*
+ * Rate conversion in calls of any length (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): what lets a 128-frame WebAudio render
+ * quantum, or a sound card's 256, 441 or 512 frames, go through a converter as they arrive, with no rebuffering to multiples of
+ * `down` in front of it.  A handle carries a position pos in 0 .. down - 1, the inputs taken since the last period boundary (a
+ * period is `down` inputs and `up` outputs), one word for all its streams: 0 at creation and after fskhip_ratecvt_reset(r, -1);
+ * fskhip_ratecvt_reset(r, stream >= 0) leaves it, and that stream goes on as one that has received zeros.  With x_s[m] and y_s[j]
+ * as above, counted from the last boundary, a call of n_in inputs per stream from position pos writes the outputs whose newest
+ * input (jM) div L lies in the call, in order:
+ *   j = ceil(pos * L / M) .. ceil((pos + n_in) * L / M) - 1,   out_count_any(pos, n_in) = ceil((pos + n_in) L / M) - ceil(pos L / M)
+ * of them -- n_in / M * L for whole periods, possibly none where L < M (one input at 13 of the 160 positions of 147 / 160); such a
+ * call still takes its inputs.  Afterwards the position is (pos + n_in) mod M and the history the last ceil((n_taps - 1) / L) inputs.
+ * Every value is the one the whole-period calls give, bit for bit, so any cut of a stream into calls of any lengths gives the same
+ * samples, the same history and the same position.  in_count_any(pos, n_out) is the smallest n_in that writes at least n_out:
+ * 0 for 0, else floor((ceil(pos L / M) + n_out - 1) M / L) + 1 - pos; it writes exactly n_out whenever L <= M.
+ *
+ * The four _any calls are fskhip_ratecvt_capture_device / _playback_device / _capture_host / _playback_host without the multiple:
+ * the same arguments (d_lens counts from the call's first input), the same refusals in the same order but the last, pitches held
+ * to out_count_any, n_in = 0 handled alike; *n_out (may be NULL) is set to the elements per stream a call that is not refused wrote.
+ * The four existing calls still refuse an n_in that is no multiple of `down`; they work from whatever position the handle is at
+ * and leave it where it was.  fskhip_ratecvt_position / _position_set are the by-hand carry beside fskhip_ratecvt_state_get /
+ * _set, whose layout is unchanged; position_set refuses a NULL handle and pos >= down (FSKHIP_E_INVALID).  The two counts answer
+ * from the handle's current position (0 for a NULL handle).
+ *
+ * fskhip_processor_process_ratecvt_device / _host refuse a handle (of a side that has a buffer) whose position is not 0 with
+ * FSKHIP_E_INVALID, behind all their other refusals, the capture handle first: their fused TX kernel begins at a period boundary.
+ * fskhip_processor_process_ratecvt_any_device / _host take the same arguments with any n_in and n_out.  The call IS, bit for bit,
+ *   fskhip_ratecvt_capture_any_device(capture, d_in, ..., n_in, X)  ->  fskhip_processor_process_device(p, X,
+ *   fskhip_ratecvt_out_count_any(capture, n_in), ..., Y, fskhip_ratecvt_in_count_any(playback, n_out), ...)  ->
+ *   fskhip_ratecvt_playback_any_device(playback, Y, ..., d_lens = NULL, d_out, ...)
+ * with a side of the processor call that has 0 engine samples left out (NULL); always in separate launches.  The refusals are the
+ * whole-period call's without the two multiples; then, where `up` > `down`, an n_out the playback handle cannot produce from its
+ * position -- in_count_any(n_out) inputs write more -- is FSKHIP_E_INVALID, the message naming the counts below and above it that
+ * it can produce.  A refused call leaves the processor, both histories and both positions as they were.
+ */
+int fskhip_ratecvt_capture_any_device(fskhip_ratecvt *r, const void *d_src, int format, int layout, size_t n_in, size_t src_pitch,
+                                      float *d_dst, size_t dst_pitch, size_t *n_out, void *hip_stream);
+int fskhip_ratecvt_playback_any_device(fskhip_ratecvt *r, const float *d_src, size_t n_in, size_t src_pitch, const uint32_t *d_lens,
+                                       void *d_dst, int format, int layout, size_t dst_pitch, size_t *n_out, void *hip_stream);
+int fskhip_ratecvt_capture_any_host(fskhip_ratecvt *r, const void *src, int format, int layout, size_t n_in, size_t src_pitch,
+                                    float *dst, size_t dst_pitch, size_t *n_out);
+int fskhip_ratecvt_playback_any_host(fskhip_ratecvt *r, const float *src, size_t n_in, size_t src_pitch, const uint32_t *lens,
+                                     void *dst, int format, int layout, size_t dst_pitch, size_t *n_out);
+uint32_t fskhip_ratecvt_position(const fskhip_ratecvt *r);   /* 0 for NULL */
+int fskhip_ratecvt_position_set(fskhip_ratecvt *r, uint32_t pos);
+size_t fskhip_ratecvt_out_count_any(const fskhip_ratecvt *r, size_t n_in);
+size_t fskhip_ratecvt_in_count_any(const fskhip_ratecvt *r, size_t n_out);
+int fskhip_processor_process_ratecvt_any_device(fskhip_processor *p, fskhip_ratecvt *capture, fskhip_ratecvt *playback,
+                                                const void *d_in, int in_format, int in_layout, size_t n_in, size_t in_pitch,
+                                                void *d_out, int out_format, int out_layout, size_t n_out, size_t out_pitch,
+                                                uint32_t flags, void *hip_stream);
+int fskhip_processor_process_ratecvt_any_host(fskhip_processor *p, fskhip_ratecvt *capture, fskhip_ratecvt *playback, const void *in,
+                                              int in_format, int in_layout, size_t n_in, size_t in_pitch, void *out, int out_format,
+                                              int out_layout, size_t n_out, size_t out_pitch, uint32_t flags);
+
 /* ---------------------------------------------------------------------------------------------------
  * IIR half of src/dsp/filters.ts: IIRFilter (8-106) batched over streams, + FilterFactory.createIIR* (325-344; the
  * designs themselves are fskhip_butterworth_* in fskhip.h).  Inside the demodulator the same filter lives as three

@@ -68,6 +68,14 @@ declare class RateConverter {
   readonly history: number;
   /** samples per stream a call with nIn per stream (a multiple of down) gives */
   outCount(nIn: number): number;
+  /** the inputs taken since the last period boundary, 0 .. down - 1, one number for all streams; 0 at creation and after reset() */
+  readonly position: number;
+  /** the by-hand carry of the position, beside state / setState */
+  setPosition(pos: number): void;
+  /** samples per stream processAny gives for nIn per stream (any) from the current position; possibly 0 */
+  outCountAny(nIn: number): number;
+  /** the fewest samples per stream for which processAny gives at least nOut from the current position */
+  inCountAny(nOut: number): number;
   reset(stream?: number): void;
   /** the history rows, [nStreams][history], oldest first */
   state(): Float32Array;
@@ -78,11 +86,15 @@ export declare class CaptureConverter extends RateConverter {
   constructor(inRate: number, outRate: number, nStreams: number, options?: RateConverterOptions);
   /** samples: [nStreams][pitch] or frames [nIn][pitch], nIn a multiple of down; returns [nStreams][nIn / down * up] */
   process(samples: Float32Array | Int16Array | Uint8Array, format: SampleFormat, layout?: SampleLayout, nIn?: number, pitch?: number): Float32Array;
+  /** process() for any nIn, from the handle's position; returns [nStreams][outCountAny(nIn)] and moves the position on */
+  processAny(samples: Float32Array | Int16Array | Uint8Array, format: SampleFormat, layout?: SampleLayout, nIn?: number, pitch?: number): Float32Array;
 }
 export declare class PlaybackConverter extends RateConverter {
   constructor(inRate: number, outRate: number, nStreams: number, options?: RateConverterOptions);
   /** input: [nStreams][n], n a multiple of down; returns [nStreams][n / down * up] or frames [n / down * up][nStreams] */
   process(input: Float32Array, format: SampleFormat, layout?: SampleLayout, lens?: Uint32Array | null): Float32Array | Int16Array | Uint8Array;
+  /** process() for any n, from the handle's position; returns [nStreams][outCountAny(n)] or frames and moves the position on */
+  processAny(input: Float32Array, format: SampleFormat, layout?: SampleLayout, lens?: Uint32Array | null): Float32Array | Int16Array | Uint8Array;
   /** output samples that can be non-zero for a signal of n input samples */
   outLength(n: number): number;
 }

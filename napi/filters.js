@@ -173,18 +173,33 @@ class RateConverter extends RateHandle {
     this.history = addon.ratecvtHistory(this.handle);
   }
   outCount(nIn) { return Math.floor(nIn / this.down) * this.up; }
+  // Calls of any length (fskhip_ratecvt_*_any_host): the handle carries a position, the inputs taken since the last period boundary
+  // (0 .. down - 1, one number for all streams; 0 at creation and after reset()), and processAny(n) writes the outputs whose
+  // newest input lies in the call -- outCountAny(n) of them from the current position, possibly none -- and moves it on.
+  // inCountAny(nOut): the fewest inputs that write at least nOut.  position / setPosition: the by-hand carry beside state / setState.
+  get position() { return addon.ratecvtPosition(this.handle); }
+  setPosition(pos) {
+    if (!(Number.isInteger(pos) && pos >= 0 && pos < this.down)) throw new RangeError('position ' + pos + ' outside 0..' + (this.down - 1));
+    addon.ratecvtSetPosition(this.handle, pos);
+  }
+  outCountAny(nIn) { return addon.ratecvtOutCountAny(this.handle, nIn); }
+  inCountAny(nOut) { return addon.ratecvtInCountAny(this.handle, nOut); }
 }
 class CaptureConverter extends RateConverter {
   constructor(inRate, outRate, nStreams, options = {}) { super(0, inRate, outRate, nStreams, options); }
   // samples: the format's typed array, [nStreams][pitch] (layout 'stream') or frames [nIn][pitch >= nStreams] ('sample'); nIn (a
   // multiple of down) and pitch default to a packed array's -> Float32Array [nStreams][nIn / down * up]
   process(samples, format, layout = 'stream', nIn, pitch) { return rateWiden(this, addon.ratecvtCapture, samples, format, layout, nIn, pitch, (n) => this.outCount(n)); }
+  // process() for any nIn, from the handle's position -> Float32Array [nStreams][outCountAny(nIn)]
+  processAny(samples, format, layout = 'stream', nIn, pitch) { return rateWiden(this, addon.ratecvtCaptureAny, samples, format, layout, nIn, pitch, (n) => this.outCountAny(n)); }
 }
 class PlaybackConverter extends RateConverter {
   constructor(inRate, outRate, nStreams, options = {}) { super(1, inRate, outRate, nStreams, options); }
   // input: Float32Array [nStreams][n], n a multiple of down; lens (Uint32Array or null): stream s reads as 0.0 from lens[s] on
   // -> the format's typed array, [nStreams][n / down * up] or frames [n / down * up][nStreams]
   process(input, format, layout = 'stream', lens = null) { return rateNarrow(this, addon.ratecvtPlayback, input, format, layout, lens, (n) => this.outCount(n)); }
+  // process() for any n, from the handle's position -> [nStreams][outCountAny(n)] or frames; lens count from the call's first input
+  processAny(input, format, layout = 'stream', lens = null) { return rateNarrow(this, addon.ratecvtPlaybackAny, input, format, layout, lens, (n) => this.outCountAny(n)); }
   // output samples that can be non-zero for a signal of n input samples
   outLength(n) { return n ? Math.floor(((n - 1) * this.up + this.taps.length - 1) / this.down) + 1 : 0; }
 }

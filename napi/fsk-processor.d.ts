@@ -24,6 +24,11 @@ export declare class FSKProcessorBatch {
   processSamplesAt(inputs: SampleArray | null,
     input?: { format?: SampleFormat; layout?: SampleLayout; nIn?: number; pitch?: number; upsampler?: Upsampler | CaptureConverter },
     output?: { format?: SampleFormat; layout?: SampleLayout; nOut?: number; pitch?: number; downsampler?: Downsampler | PlaybackConverter }): SampleArray | null;
+  /** processSamplesAt() through a CaptureConverter and a PlaybackConverter for quanta of any length (128 frames at 44.1 kHz as they arrive):
+   *  the handles carry their positions; state and samples are those of processAny -> process() -> processAny; a resampler is a TypeError */
+  processSamplesAtAny(inputs: SampleArray | null,
+    input?: { format?: SampleFormat; layout?: SampleLayout; nIn?: number; pitch?: number; upsampler?: CaptureConverter },
+    output?: { format?: SampleFormat; layout?: SampleLayout; nOut?: number; pitch?: number; downsampler?: PlaybackConverter }): SampleArray | null;
   /** 'modulate': throws 'Modulation already in progress' when a selected stream still has one */
   modulate(payloads: Uint8Array[], mask?: boolean[]): void;
   txState(): { pos: Uint32Array; total: Uint32Array; pending: Uint8Array; completed: Uint32Array };

@@ -104,25 +104,31 @@ class FSKProcessorBatch {
   // samples needs no handle.  With a CaptureConverter as upsampler and a PlaybackConverter as downsampler both sides are at the
   // converters' outer rate (44.1 kHz either side of a 48 kHz engine; fskhip_processor_process_ratecvt_host): nIn a multiple of the
   // capture converter's down, nOut of the playback converter's up; one call takes resamplers or converters, not one of each.
-  processSamplesAt(inputs, input = {}, output = {}) {
+  processSamplesAt(inputs, input = {}, output = {}) { return this.samplesAt('processSamplesAt', false, inputs, input, output); }
+  // processSamplesAt() through a CaptureConverter and a PlaybackConverter for quanta of any length -- a 128-frame render quantum at
+  // 44.1 kHz as it arrives (fskhip_processor_process_ratecvt_any_host): the handles carry their positions from call to call; state
+  // and samples are those of processAny -> process() with the engine counts the handles give -> processAny, bit for bit.  A
+  // resampler in a slot is a TypeError; an nOut the playback converter cannot write from its position is the library's refusal.
+  processSamplesAtAny(inputs, input = {}, output = {}) { return this.samplesAt('processSamplesAtAny', true, inputs, input, output); }
+  samplesAt(who, anyLength, inputs, input, output) {
     if (input === null || typeof input !== 'object' || output === null || typeof output !== 'object') {
-      throw new TypeError('processSamplesAt: input and output must be objects {format, layout, nIn | nOut, pitch, upsampler | downsampler}');
+      throw new TypeError(who + ': input and output must be objects {format, layout, nIn | nOut, pitch, upsampler | downsampler}');
     }
     const inFmt = sampleFormat(input.format === undefined ? 'mulaw' : input.format), inLay = sampleLayout(input.layout === undefined ? 'sample' : input.layout);
     const outFmt = sampleFormat(output.format === undefined ? 'mulaw' : output.format), outLay = sampleLayout(output.layout === undefined ? 'sample' : output.layout);
     const count = (v, what) => {
       const n = v === undefined ? 0 : v;
-      if (!Number.isInteger(n) || n < 0 || n > 0xffffffff) throw new RangeError('processSamplesAt: ' + what + ' must be an integer in [0, 2^32)');
+      if (!Number.isInteger(n) || n < 0 || n > 0xffffffff) throw new RangeError(who + ': ' + what + ' must be an integer in [0, 2^32)');
       return n;
     };
     const has = inputs !== undefined && inputs !== null;
-    if (has && !ArrayBuffer.isView(inputs)) throw new TypeError('processSamplesAt: inputs must be a typed array or null');
+    if (has && !ArrayBuffer.isView(inputs)) throw new TypeError(who + ': inputs must be a typed array or null');
     const nIn = has ? count(input.nIn, 'nIn') : 0, nOut = count(output.nOut, 'nOut');
     const inPitch = count(input.pitch, 'input pitch') || (inLay ? this.nStreams : nIn);
     const outPitch = count(output.pitch, 'output pitch') || (outLay ? this.nStreams : nOut);
     const handle = (r, kind, converter, what) => {     // (a converter of the side's direction stands in its resampler's place)
-      if (!(r instanceof kind) && !(r instanceof converter)) throw new TypeError('processSamplesAt: ' + what + ' must be an ' + kind.name + ' of filters.js');
-      if (r.nStreams !== this.nStreams) throw new RangeError('processSamplesAt: ' + what + ' has ' + r.nStreams + ' streams, the batch ' + this.nStreams);
+      if (!(r instanceof kind) && !(r instanceof converter)) throw new TypeError(who + ': ' + what + ' must be an ' + kind.name + ' of filters.js');
+      if (r.nStreams !== this.nStreams) throw new RangeError(who + ': ' + what + ' has ' + r.nStreams + ' streams, the batch ' + this.nStreams);
       return r.handle;
     };
     const up = has ? handle(input.upsampler, Upsampler, CaptureConverter, 'upsampler') : null;
@@ -130,14 +136,20 @@ class FSKProcessorBatch {
     // converters: both sides at their outer rate (fskhip_processor_process_ratecvt_host), in whole periods; one call takes one kind
     const capture = has && input.upsampler instanceof CaptureConverter, playback = nOut > 0 && output.downsampler instanceof PlaybackConverter;
     if (has && nOut && capture !== playback) {
-      throw new TypeError('processSamplesAt: upsampler is a ' + input.upsampler.constructor.name + ' and downsampler a ' + output.downsampler.constructor.name +
+      throw new TypeError(who + ': upsampler is a ' + input.upsampler.constructor.name + ' and downsampler a ' + output.downsampler.constructor.name +
         ': one call takes resamplers or rate converters, not one of each');
     }
+    if (anyLength) {
+      if (has && !capture) throw new TypeError(who + ': upsampler is a ' + input.upsampler.constructor.name + ': quanta of any length go through rate converters');
+      if (nOut && !playback) throw new TypeError(who + ': downsampler is a ' + output.downsampler.constructor.name + ': quanta of any length go through rate converters');
+      if (has) this.processDemodulationCallCount++;
+      return addon.processorProcessSamplesAtAny(this.handle, up, down, has ? inputs : null, inFmt, inLay, nIn, inPitch, outFmt, outLay, nOut, outPitch, this.flags);
+    }
     if (capture && nIn % input.upsampler.down) {
-      throw new RangeError('processSamplesAt: ' + nIn + ' samples per stream are not a multiple of the converter\'s down factor ' + input.upsampler.down);
+      throw new RangeError(who + ': ' + nIn + ' samples per stream are not a multiple of the converter\'s down factor ' + input.upsampler.down);
     }
     if (playback && nOut % output.downsampler.up) {
-      throw new RangeError('processSamplesAt: nOut ' + nOut + ' is not a multiple of the converter\'s up factor ' + output.downsampler.up);
+      throw new RangeError(who + ': nOut ' + nOut + ' is not a multiple of the converter\'s up factor ' + output.downsampler.up);
     }
     if (has) this.processDemodulationCallCount++;      // (as process() counts: behind the argument checks, in front of the call)
     return addon.processorProcessSamplesAt(this.handle, up, down, has ? inputs : null, inFmt, inLay, nIn, inPitch, outFmt, outLay, nOut, outPitch, this.flags);

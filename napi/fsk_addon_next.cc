@@ -48,6 +48,9 @@
 //   ratecvtCapture(handle, samples, format, layout, nIn, pitch, nOut) -> Float32Array [S][nOut]
 //   ratecvtPlayback(handle, input: Float32Array [S][nIn], nIn, lens: Uint32Array|null, format, layout, nOut) -> the format's typed array
 //   ratecvtReset(handle, stream);  ratecvtState(handle) -> Float32Array [S][history];  ratecvtSetState(handle, Float32Array)
+//   ratecvtCaptureAny / ratecvtPlaybackAny: the two process calls for any nIn, from the handle's position (nOut: ratecvtOutCountAny's)
+//   ratecvtPosition(handle) -> number;  ratecvtSetPosition(handle, pos);  ratecvtOutCountAny(handle, nIn);  ratecvtInCountAny(handle, nOut)
+//   processorProcessSamplesAtAny: processorProcessSamplesAt for rate converters and counts of any length
 //   iirCreate(b, a: Float64Array, nStreams, device, precision) -> handle; iirProcess(handle, Float32Array | Float64Array, n, pitch, nStreams);
 //   iirCoefficients(handle), iirReset(handle, stream), iirDestroy(handle); butterworth(kind, f, bandwidth, sampleRate) -> [b0 b1 b2 a0 a1 a2]
 #include <cstring>
@@ -1062,7 +1065,8 @@ FilterBox *rate_box_of(napi_env env, napi_value v) {
   if (b->kind != BOX_RESAMPLER && b->kind != BOX_RATECVT) { napi_throw_type_error(env, nullptr, "not a resampler or rate converter handle"); return nullptr; }
   return b;
 }
-napi_value ProcessorProcessSamplesAt(napi_env env, napi_callback_info info) {
+// any_length: fskhip_processor_process_ratecvt_any_host, for rate converters alone
+napi_value processor_process_samples_at(napi_env env, napi_callback_info info, bool any_length) {
   ARGS(13);
   const int32_t in_format = i32(env, argv[4]), in_layout = i32(env, argv[5]), out_format = i32(env, argv[8]), out_layout = i32(env, argv[9]);
   if (!sample_format_ok(env, in_format, in_layout) || !sample_format_ok(env, out_format, out_layout)) return nullptr;
@@ -1075,6 +1079,7 @@ napi_value ProcessorProcessSamplesAt(napi_env env, napi_callback_info info) {
   if (in) {
     if (nullish(env, argv[1])) { napi_throw_type_error(env, nullptr, "input samples need an upsampler"); return nullptr; }
     if (!(up = rate_box_of(env, argv[1]))) return nullptr;
+    if (any_length && up->kind != BOX_RATECVT) { napi_throw_type_error(env, nullptr, "quanta of any length take rate converters"); return nullptr; }
     const int64_t need = samples_needed(in_layout, h->S, n_in, in_pitch);
     if (need < 0 || (size_t)need > ilen) { napi_throw_range_error(env, nullptr, "input too short"); return nullptr; }
   }
@@ -1083,6 +1088,7 @@ napi_value ProcessorProcessSamplesAt(napi_env env, napi_callback_info info) {
   if (n_out) {
     if (nullish(env, argv[2])) { napi_throw_type_error(env, nullptr, "output samples need a downsampler"); return nullptr; }
     if (!(down = rate_box_of(env, argv[2]))) return nullptr;
+    if (any_length && down->kind != BOX_RATECVT) { napi_throw_type_error(env, nullptr, "quanta of any length take rate converters"); return nullptr; }
     if (up && up->kind != down->kind) { napi_throw_type_error(env, nullptr, "one call takes resamplers or rate converters, not one of each"); return nullptr; }
     const int64_t need = samples_needed(out_layout, h->S, n_out, out_pitch);
     if (need < 0) { napi_throw_range_error(env, nullptr, "output pitch too small"); return nullptr; }
@@ -1092,7 +1098,9 @@ napi_value ProcessorProcessSamplesAt(napi_env env, napi_callback_info info) {
   }
   void *const uh = up ? up->p : nullptr, *const dh = down ? down->p : nullptr;
   const bool cvt = (up ? up : down) && (up ? up : down)->kind == BOX_RATECVT;
-  int rc = cvt ? fskhip_processor_process_ratecvt_host(h->p, (fskhip_ratecvt *)uh, (fskhip_ratecvt *)dh, in, in_format, in_layout, n_in, in_pitch, out, out_format,
+  int rc = any_length ? fskhip_processor_process_ratecvt_any_host(h->p, (fskhip_ratecvt *)uh, (fskhip_ratecvt *)dh, in, in_format, in_layout, n_in, in_pitch, out,
+                                                                  out_format, out_layout, n_out, out_pitch, flags)
+           : cvt ? fskhip_processor_process_ratecvt_host(h->p, (fskhip_ratecvt *)uh, (fskhip_ratecvt *)dh, in, in_format, in_layout, n_in, in_pitch, out, out_format,
                                                        out_layout, n_out, out_pitch, flags)
                : fskhip_processor_process_rate_host(h->p, (fskhip_resampler *)uh, (fskhip_resampler *)dh, in, in_format, in_layout, n_in, in_pitch, out, out_format,
                                                     out_layout, n_out, out_pitch, flags);
@@ -1100,6 +1108,8 @@ napi_value ProcessorProcessSamplesAt(napi_env env, napi_callback_info info) {
   if (!out_v) napi_get_null(env, &out_v);
   return out_v;
 }
+napi_value ProcessorProcessSamplesAt(napi_env env, napi_callback_info info) { return processor_process_samples_at(env, info, false); }
+napi_value ProcessorProcessSamplesAtAny(napi_env env, napi_callback_info info) { return processor_process_samples_at(env, info, true); }
 // ---- rate conversion by a ratio (include/fskhip_next.h: fskhip_ratecvt_*) ----
 fskhip_ratecvt *ratecvt_of(napi_env env, napi_value v) {
   FilterBox *b = (FilterBox *)external(env, v, "filter destroyed");
@@ -1131,6 +1141,38 @@ napi_value RatecvtPlayback(napi_env env, napi_callback_info info) { return rate_
 napi_value RatecvtReset(napi_env env, napi_callback_info info) { return rate_reset(env, info, kRatecvt); }
 napi_value RatecvtState(napi_env env, napi_callback_info info) { return rate_state(env, info, kRatecvt); }
 napi_value RatecvtSetState(napi_env env, napi_callback_info info) { return rate_set_state(env, info, kRatecvt); }
+// calls of any length (fskhip_ratecvt_*_any_host): the same marshalling, the output count being the handle's own from its position;
+// a call that writes nothing still needs a buffer to name
+float g_no_output[4];
+int ratecvt_capture_any(fskhip_ratecvt *r, const void *src, int format, int layout, size_t n_in, size_t src_pitch, float *dst, size_t dst_pitch) {
+  return fskhip_ratecvt_capture_any_host(r, src, format, layout, n_in, src_pitch, dst ? dst : g_no_output, dst_pitch, nullptr);
+}
+int ratecvt_playback_any(fskhip_ratecvt *r, const float *src, size_t n_in, size_t src_pitch, const uint32_t *lens, void *dst, int format, int layout, size_t dst_pitch) {
+  return fskhip_ratecvt_playback_any_host(r, src, n_in, src_pitch, lens, dst ? dst : (void *)g_no_output, format, layout, dst_pitch, nullptr);
+}
+const RateApi<fskhip_ratecvt> kRatecvtAny = {ratecvt_of, fskhip_ratecvt_streams, fskhip_ratecvt_history, fskhip_ratecvt_reset, fskhip_ratecvt_state_get,
+                                             fskhip_ratecvt_state_set, ratecvt_capture_any, ratecvt_playback_any, false};
+napi_value RatecvtCaptureAny(napi_env env, napi_callback_info info) { return rate_widen(env, info, kRatecvtAny); }
+napi_value RatecvtPlaybackAny(napi_env env, napi_callback_info info) { return rate_narrow(env, info, kRatecvtAny); }
+napi_value RatecvtPosition(napi_env env, napi_callback_info info) { return rate_count(env, info, kRatecvt, fskhip_ratecvt_position); }
+napi_value RatecvtSetPosition(napi_env env, napi_callback_info info) {   // (handle, pos)
+  ARGS(2);
+  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
+  if (!r) return nullptr;
+  int rc = fskhip_ratecvt_position_set(r, u32(env, argv[1]));
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+napi_value ratecvt_count_any(napi_env env, napi_callback_info info, size_t (*count)(const fskhip_ratecvt *, size_t)) {   // (handle, n) -> number
+  ARGS(2);
+  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
+  if (!r) return nullptr;
+  napi_value v;
+  NAPI_OK(napi_create_double(env, (double)count(r, u32(env, argv[1])), &v));
+  return v;
+}
+napi_value RatecvtOutCountAny(napi_env env, napi_callback_info info) { return ratecvt_count_any(env, info, fskhip_ratecvt_out_count_any); }
+napi_value RatecvtInCountAny(napi_env env, napi_callback_info info) { return ratecvt_count_any(env, info, fskhip_ratecvt_in_count_any); }
 // ---- a resampler through remap / snapshot / restore (fskhip_resampler_remap ...): remap and restore return a NEW handle
 napi_value ResamplerRemap(napi_env env, napi_callback_info info) {   // (handle, map: number[]) -> handle
   ARGS(2);
@@ -1357,6 +1399,13 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"ratecvtReset", nullptr, RatecvtReset, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ratecvtState", nullptr, RatecvtState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ratecvtSetState", nullptr, RatecvtSetState, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtCaptureAny", nullptr, RatecvtCaptureAny, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtPlaybackAny", nullptr, RatecvtPlaybackAny, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtPosition", nullptr, RatecvtPosition, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtSetPosition", nullptr, RatecvtSetPosition, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtOutCountAny", nullptr, RatecvtOutCountAny, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtInCountAny", nullptr, RatecvtInCountAny, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"processorProcessSamplesAtAny", nullptr, ProcessorProcessSamplesAtAny, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirCreate", nullptr, IirCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirDestroy", nullptr, IirDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirCoefficients", nullptr, IirCoefficients, nullptr, nullptr, nullptr, napi_default, nullptr},

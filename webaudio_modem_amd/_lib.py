@@ -274,6 +274,16 @@ _SYMBOLS = [
     ("fskhip_ratecvt_state_set", C.c_int, [_P, _P]),
     ("fskhip_processor_process_ratecvt_device", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, _P]),
     ("fskhip_processor_process_ratecvt_host", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32]),
+    ("fskhip_ratecvt_capture_any_device", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, _P]),
+    ("fskhip_ratecvt_playback_any_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P, C.c_int, C.c_int, C.c_size_t, _P, _P]),
+    ("fskhip_ratecvt_capture_any_host", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P]),
+    ("fskhip_ratecvt_playback_any_host", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P, C.c_int, C.c_int, C.c_size_t, _P]),
+    ("fskhip_ratecvt_position", C.c_uint32, [_P]),
+    ("fskhip_ratecvt_position_set", C.c_int, [_P, C.c_uint32]),
+    ("fskhip_ratecvt_out_count_any", C.c_size_t, [_P, C.c_size_t]),
+    ("fskhip_ratecvt_in_count_any", C.c_size_t, [_P, C.c_size_t]),
+    ("fskhip_processor_process_ratecvt_any_device", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, _P]),
+    ("fskhip_processor_process_ratecvt_any_host", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32]),
     ("fskhip_iir_create", C.c_int, [C.c_int, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P)]),
     ("fskhip_iir_destroy", C.c_int, [_P]),
     ("fskhip_iir_get_coefficients", C.c_int, [_P, _P, C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint32)]),

@@ -134,7 +134,8 @@ int rate_process(RateHost *r, const RateCall &c, bool host, bool narrow_in, cons
   HIP_TRY(hipMemcpy2DAsync(r->d_in, in.pitch * in.esz, src, src_pitch * in.esz, in.cols * in.esz, in.rows, hipMemcpyHostToDevice, r->stream));
   if (lens) HIP_TRY(hipMemcpyAsync(r->d_lens, lens, sizeof(uint32_t) * r->S, hipMemcpyHostToDevice, r->stream));
   if ((rc = run(r->d_in, in.pitch, lens ? r->d_lens : nullptr, r->d_out, out.pitch, r->stream)) != FSKHIP_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch * out.esz, r->d_out, out.pitch * out.esz, out.cols * out.esz, out.rows, hipMemcpyDeviceToHost, r->stream));
+  if (out.rows && out.cols)   // (a call may write nothing and still move the handle on: fskhip_ratecvt_*_any_host)
+    HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch * out.esz, r->d_out, out.pitch * out.esz, out.cols * out.esz, out.rows, hipMemcpyDeviceToHost, r->stream));
   HIP_TRY(hipStreamSynchronize(r->stream));
   return FSKHIP_OK;
 }

@@ -7,4 +7,5 @@
 struct fskhip_ratecvt : fsk::RateHost {   // L: the up factor; H: resample_history(0, L, n_taps); the taps [K][L] in output order (fsk_ratecvt_plan.h)
   uint32_t M = 1;                          // the down factor
   uint32_t *d_table = nullptr;             // [L]: ratecvt_table_word
+  uint32_t pos = 0;                        // inputs taken since the last period boundary, < M: all streams' (fsk_ratecvt_plan.h)
 };

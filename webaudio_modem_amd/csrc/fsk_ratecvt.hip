@@ -12,6 +12,12 @@
 // [k][q], and a wave reads consecutive words of them, once for its four rows -- and their inputs x[m - k] are the same or the next
 // LDS word where L > M, at most ceil(M / L) apart otherwise.  PLAYBACK in sample-major layout leaves through a [outputs][ns + 1]
 // tile.
+//
+// A call of any length from any position of the handle (fsk_ratecvt_plan.h: "Calls of any length") is the same shape of body laid on
+// the period grid `pos` inputs in front of the call's first: it stages from there, skips the places whose output is not the
+// call's and stores output j of the grid at column j - ceil(pos L / M): ratecvt_any_body, a body of its own beside ratecvt_body,
+// with its own instantiations and launch.  The whole-period calls of a handle at position 0 keep ratecvt_body and launch_ratecvt
+// as they were.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -155,6 +161,137 @@ const KernelEntry<RatecvtFn> kRatecvtKernels[2][2][4][2] = {
     {FSK_FORMAT_KERNELS(ratecvt_capture_kernel, float), FSK_FORMAT_KERNELS(ratecvt_capture_kernel, double)},
     {FSK_FORMAT_KERNELS(ratecvt_playback_kernel, float), FSK_FORMAT_KERNELS(ratecvt_playback_kernel, double)}};
 
+// ratecvt_body for a call of any length from position `pos` of the handle (fsk_ratecvt_plan.h: "Calls of any length"): the same
+// staging, rows, tap order and stores, laid on the period grid `pos` inputs in front of the call's first
+template <typename Real, int FMT, int LAYOUT, int DIR>
+__device__ __forceinline__ void ratecvt_any_body(FSK_RATECVT_PARAMS, uint32_t pos) {
+  using F = SampleFmt<FMT>;
+  constexpr bool kRows = LAYOUT == FSKHIP_LAYOUT_STREAM_MAJOR, kPlay = DIR == FSKHIP_RATECVT_PLAYBACK;
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  float *const xs = reinterpret_cast<float *>(lds_raw);                 // [ns][x_pitch]: hist floats of history, then the periods' inputs
+  const Real *const taps = (const Real *)taps_;                          // [K][L]
+  const uint32_t tid = threadIdx.x;
+  const uint32_t H = G.hist, span = G.span, ns = 1u << G.log2_ns;
+  uint32_t *const tile = reinterpret_cast<uint32_t *>(xs + (size_t)ns * G.x_pitch);   // [G L][ns + 1] (PLAYBACK, sample-major)
+  const uint32_t hi = blockIdx.x / G.split, lo = blockIdx.x - hi * G.split;
+  const uint32_t s0 = kRows ? hi : lo << G.log2_ns;
+  const size_t per0 = (size_t)(kRows ? lo : hi) * G.seg_periods;        // the workgroup's first period
+  // m0, j0: the period's first input and output on the period grid, which begins `pos` inputs in front of the call; the call's
+  // outputs are j_lo .. j_hi - 1 of the grid, those whose newest input lies in the call
+  const size_t m0 = per0 * M, j0 = per0 * L;
+  const size_t j_lo = ((size_t)pos * L + M - 1u) / M, j_hi = ((pos + n_in) * L + M - 1u) / M;
+
+  // input i of the staged span of stream s0 + c; `len`: inputs of the call from there on read as 0.0f
+  auto stage = [&](uint32_t c, uint32_t i, size_t len) {
+    const uint32_t s = s0 + c;
+    const int64_t m = (int64_t)m0 + (int64_t)i - (int64_t)H - (int64_t)pos;   // counted from the call's first input
+    float v = 0.0f;
+    if (s < n_streams) {
+      if (m >= 0) {
+        if ((size_t)m < len) {
+          if constexpr (kPlay) v = ((const float *)src_)[(size_t)s * src_pitch + (size_t)m];
+          else v = F::decode(((const typename F::T *)src_)[kRows ? (size_t)s * src_pitch + (size_t)m : (size_t)m * src_pitch + s]);
+        }
+      } else if (m >= -(int64_t)H) {                                    // (the first workgroup's `pos` words in front of the history are no input)
+        v = hist_in[(size_t)s * H + (size_t)(m + (int64_t)H)];
+      }
+      // the history after the call: the last H samples, each written by the workgroup whose periods hold it (the first
+      // workgroup's for what stays of the old history)
+      const int64_t h = m + (int64_t)H - (int64_t)n_in;
+      if ((i >= H || m0 == 0) && h >= 0 && m < (int64_t)n_in) hist_out[(size_t)s * H + (size_t)h] = v;
+    }
+    xs[c * G.x_pitch + i] = v;
+  };
+  if constexpr (kRows || kPlay) {                                        // the staged side lies stream by stream
+    for (uint32_t c = 0; c < ns; c++) {
+      size_t len = n_in;
+      if (kPlay && d_lens && s0 + c < n_streams) len = d_lens[s0 + c] < n_in ? (size_t)d_lens[s0 + c] : n_in;
+      for (uint32_t i = tid; i < span; i += kResampleThreads) stage(c, i, len);
+    }
+  } else {                                                               // frames: consecutive lanes take a frame's streams
+    for (uint32_t idx = tid; idx < (span << G.log2_ns); idx += kResampleThreads) stage(idx & (ns - 1u), idx >> G.log2_ns, n_in);
+  }
+  __syncthreads();
+
+  // item w: place u = w % (G L) of the rows 4 (w / (G L)) .. + 3.  Row r is block r of the stream (stream-major; output
+  // j0 + r G L + u) or stream s0 + r (sample-major; output j0 + u); its inputs start r * row_stride floats into xs.
+  const uint32_t Qs = G.G * L, n_quads = (G.rows + 3u) / 4u;
+  const uint32_t k_full = n_taps / L, rem = n_taps - k_full * L;        // phase p has k_full + (p < rem) taps
+  for (uint32_t w = tid; w < n_quads * Qs; w += kResampleThreads) {
+    const uint32_t quad = w / Qs, u = w - quad * Qs;
+    const uint32_t per = u / L, q = u - per * L;
+    const uint32_t word = table[q], p = word >> 16;
+    const uint32_t x0 = H + per * M + (word & 0xFFFFu);                  // x[m] of row 0 of the stream's span; x[m - k]: k <= H
+    uint32_t xb[4];
+    // a place outside the call's outputs is not evaluated: the lane's first own row is computed again in its stead, unused, and a
+    // lane without one has nothing to do
+    bool own[4];
+    uint32_t first = 4u;
+#pragma unroll
+    for (uint32_t r = 4u; r-- > 0u;) {
+      const uint32_t row = quad * 4u + r;
+      const size_t j = j0 + (kRows ? (size_t)row * Qs : 0u) + u;
+      own[r] = row < G.rows && j >= j_lo && j < j_hi;
+      if (own[r]) first = r;
+    }
+    if (first == 4u) continue;
+#pragma unroll
+    for (uint32_t r = 0; r < 4u; r++) xb[r] = (quad * 4u + (own[r] ? r : first)) * G.row_stride + x0;
+    Real acc[4] = {0, 0, 0, 0};
+    const Real *tp = taps + q;
+#pragma unroll 4
+    for (uint32_t k = 0; k < k_full; k++) {
+      const Real cc = tp[(size_t)k * L];
+#pragma unroll
+      for (uint32_t r = 0; r < 4u; r++) acc[r] = mac(acc[r], cc, xs[xb[r] - k]);
+    }
+    if (p < rem) {
+      const Real cc = tp[(size_t)k_full * L];
+#pragma unroll
+      for (uint32_t r = 0; r < 4u; r++) acc[r] = mac(acc[r], cc, xs[xb[r] - k_full]);
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < 4u; r++) {
+      const uint32_t row = quad * 4u + r;
+      const size_t j = j0 + (kRows ? (size_t)row * Qs : 0u) + u;
+      const uint32_t s = kRows ? s0 : s0 + row;
+      if (!own[r] || s >= n_streams) continue;
+      if constexpr (!kPlay) {
+        ((float *)dst_)[(size_t)s * dst_pitch + (j - j_lo)] = (float)acc[r];
+      } else if constexpr (kRows) {
+        ((typename F::Bits *)dst_)[(size_t)s * dst_pitch + (j - j_lo)] = (typename F::Bits)F::encode((float)acc[r]);
+      } else {
+        tile[u * (ns + 1u) + row] = F::encode((float)acc[r]);
+      }
+    }
+  }
+  if constexpr (kPlay && !kRows) {
+    __syncthreads();
+    for (uint32_t idx = tid; idx < (Qs << G.log2_ns); idx += kResampleThreads) {
+      const uint32_t c = idx & (ns - 1u), u = idx >> G.log2_ns;
+      if (s0 + c < n_streams && j0 + u >= j_lo && j0 + u < j_hi)
+        ((typename F::Bits *)dst_)[(j0 + u - j_lo) * dst_pitch + s0 + c] = (typename F::Bits)tile[u * (ns + 1u) + c];
+    }
+  }
+}
+
+template <typename Real, int FMT, int LAYOUT>
+__global__ __launch_bounds__(kResampleThreads) void ratecvt_capture_any_kernel(FSK_RATECVT_PARAMS, uint32_t pos) {
+  ratecvt_any_body<Real, FMT, LAYOUT, FSKHIP_RATECVT_CAPTURE>(FSK_RATECVT_ARGS, pos);
+}
+
+template <typename Real, int FMT, int LAYOUT>
+__global__ __launch_bounds__(kResampleThreads) void ratecvt_playback_any_kernel(FSK_RATECVT_PARAMS, uint32_t pos) {
+  ratecvt_any_body<Real, FMT, LAYOUT, FSKHIP_RATECVT_PLAYBACK>(FSK_RATECVT_ARGS, pos);
+}
+
+// the any-length instantiations, once: [direction][precision][format][layout]
+using RatecvtAnyFn = void (*)(const void *, size_t, const uint32_t *, void *, size_t, const float *, float *, const void *, const uint32_t *, uint32_t, size_t, uint32_t,
+                              uint32_t, uint32_t, RatecvtShape, uint32_t);
+const KernelEntry<RatecvtAnyFn> kRatecvtAnyKernels[2][2][4][2] = {
+    {FSK_FORMAT_KERNELS(ratecvt_capture_any_kernel, float), FSK_FORMAT_KERNELS(ratecvt_capture_any_kernel, double)},
+    {FSK_FORMAT_KERNELS(ratecvt_playback_any_kernel, float), FSK_FORMAT_KERNELS(ratecvt_playback_any_kernel, double)}};
+
 }  // namespace
 
 hipError_t launch_ratecvt(int direction, int precision, const void *d_src, size_t src_pitch, const uint32_t *d_lens, void *d_dst, size_t dst_pitch, int format,
@@ -169,19 +306,37 @@ hipError_t launch_ratecvt(int direction, int precision, const void *d_src, size_
   return hipGetLastError();
 }
 
+hipError_t launch_ratecvt_any(int direction, int precision, const void *d_src, size_t src_pitch, const uint32_t *d_lens, void *d_dst, size_t dst_pitch, int format,
+                              int layout, uint32_t n_streams, uint32_t pos, size_t n_in, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps,
+                              const uint32_t *d_table, const float *d_hist_in, float *d_hist_out, hipStream_t st) {
+  if (pos == 0 && n_in % down == 0)                                      // whole periods from a boundary keep their own kernels and launch
+    return launch_ratecvt(direction, precision, d_src, src_pitch, d_lens, d_dst, dst_pitch, format, layout, n_streams, n_in, up, down, n_taps, d_taps, d_table, d_hist_in,
+                          d_hist_out, st);
+  const RatecvtPlan P = ratecvt_plan_any(layout == FSKHIP_LAYOUT_STREAM_MAJOR, direction == FSKHIP_RATECVT_PLAYBACK, up, down, n_taps, n_streams, pos, n_in);
+  if (P.blocks == 0) return hipErrorInvalidValue;
+  const RatecvtShape G = {P.hist, P.G, P.rows, P.log2_ns, P.x_pitch, P.row_stride, P.span, P.seg_periods, P.split};
+  const KernelEntry<RatecvtAnyFn> &k = kRatecvtAnyKernels[direction][precision == FSKHIP_PRECISION_F64 ? 1 : 0][format][layout];
+  hipLaunchKernelGGL(k.fn, dim3((uint32_t)P.blocks), dim3(kResampleThreads), P.lds_bytes, st, d_src, src_pitch, d_lens, d_dst, dst_pitch, d_hist_in, d_hist_out, d_taps,
+                     d_table, n_streams, n_in, up, down, n_taps, G, pos);
+  return hipGetLastError();
+}
+
 }  // namespace fsk
 
 using namespace fsk;
 
 namespace {
 
-// The four process entry points: `direction` is the entry point's, `host` its form.  Refused in the header's order
-// (fsk_rate_call.h), an n_in that is no multiple of the down factor last; then one launch over the buffers or the staging slabs.
-int process(fskhip_ratecvt *r, const char *who, int direction, bool host, int format, int layout, size_t n_in, const void *src, size_t src_pitch,
-            const uint32_t *lens, void *dst, size_t dst_pitch, hipStream_t st) {
+// The eight process entry points: `direction` is the entry point's, `host` its form, `any` whether it takes any length.  Refused
+// in the header's order (fsk_rate_call.h), an n_in that is no multiple of the down factor last where the call wants one; then one
+// launch from the handle's position over the buffers or the staging slabs, and the position moves on (by nothing for whole
+// periods).  *n_out (may be null): what a call that was not refused wrote per stream.
+int process(fskhip_ratecvt *r, const char *who, int direction, bool host, bool any, int format, int layout, size_t n_in, const void *src, size_t src_pitch,
+            const uint32_t *lens, void *dst, size_t dst_pitch, size_t *n_out, hipStream_t st) {
   if (!r) return fail(FSKHIP_E_INVALID, "null rate converter");
-  const RateCall c = rate_call(r, direction, direction == FSKHIP_RATECVT_CAPTURE, format, layout, n_in, ratecvt_out_count(r->L, r->M, n_in), src, src_pitch, lens,
-                               dst, dst_pitch, r->M);
+  const uint32_t pos = r->pos;
+  const size_t written = any ? ratecvt_out_count_any(r->L, r->M, pos, n_in) : ratecvt_out_count(r->L, r->M, n_in);
+  const RateCall c = rate_call(r, direction, direction == FSKHIP_RATECVT_CAPTURE, format, layout, n_in, written, src, src_pitch, lens, dst, dst_pitch, any ? 1u : r->M);
   switch (const RateRefusal why = rate_call_check(c)) {
     case RateRefusal::direction:
       return fail(FSKHIP_E_INVALID, "%s: the handle converts for %s", who, r->direction == FSKHIP_RATECVT_CAPTURE ? "capture" : "playback");
@@ -189,16 +344,19 @@ int process(fskhip_ratecvt *r, const char *who, int direction, bool host, int fo
     default:
       if (const int rc = rate_call_fail(who, format, c, why)) return rc;
   }
-  return rate_process(r, c, host, direction == FSKHIP_RATECVT_CAPTURE, src, src_pitch, lens, dst, dst_pitch, st,
-                      [=](const void *d_src, size_t d_src_pitch, const uint32_t *d_lens, void *d_dst, size_t d_dst_pitch, hipStream_t s) {
+  const int rc = rate_process(r, c, host, direction == FSKHIP_RATECVT_CAPTURE, src, src_pitch, lens, dst, dst_pitch, st,
+                              [=](const void *d_src, size_t d_src_pitch, const uint32_t *d_lens, void *d_dst, size_t d_dst_pitch, hipStream_t s) {
     return rate_run(r, [=](const float *hist_in, float *hist_out) -> int {
-      const hipError_t err = launch_ratecvt(r->direction, r->precision, d_src, d_src_pitch, d_lens, d_dst, d_dst_pitch, format, layout, r->S, n_in, r->L, r->M,
-                                            r->n_taps, r->taps(), r->d_table, hist_in, hist_out, s);
+      const hipError_t err = launch_ratecvt_any(r->direction, r->precision, d_src, d_src_pitch, d_lens, d_dst, d_dst_pitch, format, layout, r->S, pos, n_in, r->L,
+                                                r->M, r->n_taps, r->taps(), r->d_table, hist_in, hist_out, s);
       if (err == hipErrorInvalidValue) return rate_grid_fail(who, r->S, n_in);
       HIP_TRY(err);
+      r->pos = ratecvt_next_position(r->M, pos, n_in);
       return FSKHIP_OK;
     });
   });
+  if (rc == FSKHIP_OK && n_out) *n_out = written;
+  return rc;
 }
 
 }  // namespace
@@ -208,7 +366,20 @@ extern "C" {
 uint32_t fskhip_ratecvt_streams(const fskhip_ratecvt *r) { return rate_streams(r); }
 uint32_t fskhip_ratecvt_history(const fskhip_ratecvt *r) { return rate_history(r); }
 int fskhip_ratecvt_destroy(fskhip_ratecvt *r) { return rate_destroy(r, r ? r->d_table : nullptr); }
-int fskhip_ratecvt_reset(fskhip_ratecvt *r, int64_t stream) { return rate_reset(r, "null rate converter", stream); }
+int fskhip_ratecvt_reset(fskhip_ratecvt *r, int64_t stream) {   // (one stream: the position is the handle's, and stays)
+  const int rc = rate_reset(r, "null rate converter", stream);
+  if (rc == FSKHIP_OK && stream < 0) r->pos = 0;
+  return rc;
+}
+uint32_t fskhip_ratecvt_position(const fskhip_ratecvt *r) { return r ? r->pos : 0u; }
+int fskhip_ratecvt_position_set(fskhip_ratecvt *r, uint32_t pos) {
+  if (!r) return fail(FSKHIP_E_INVALID, "null rate converter");
+  if (pos >= r->M) return fail(FSKHIP_E_INVALID, "fskhip_ratecvt_position_set: position %u is not below the down factor %u", pos, r->M);
+  r->pos = pos;
+  return FSKHIP_OK;
+}
+size_t fskhip_ratecvt_out_count_any(const fskhip_ratecvt *r, size_t n_in) { return r ? ratecvt_out_count_any(r->L, r->M, r->pos, n_in) : 0u; }
+size_t fskhip_ratecvt_in_count_any(const fskhip_ratecvt *r, size_t n_out) { return r ? ratecvt_in_count_any(r->L, r->M, r->pos, n_out) : 0u; }
 int fskhip_ratecvt_state_get(fskhip_ratecvt *r, float *state) { return rate_state(r, "null rate converter", "fskhip_ratecvt_state_get", state, true); }
 int fskhip_ratecvt_state_set(fskhip_ratecvt *r, const float *state) {
   return rate_state(r, "null rate converter", "fskhip_ratecvt_state_set", const_cast<float *>(state), false);
@@ -242,21 +413,44 @@ int fskhip_ratecvt_create(int device, int direction, uint32_t up, uint32_t down,
 
 int fskhip_ratecvt_capture_device(fskhip_ratecvt *r, const void *d_src, int format, int layout, size_t n_in, size_t src_pitch, float *d_dst, size_t dst_pitch,
                                   void *hip_stream) {
-  return process(r, "fskhip_ratecvt_capture_device", FSKHIP_RATECVT_CAPTURE, false, format, layout, n_in, d_src, src_pitch, nullptr, d_dst, dst_pitch, (hipStream_t)hip_stream);
+  return process(r, "fskhip_ratecvt_capture_device", FSKHIP_RATECVT_CAPTURE, false, false, format, layout, n_in, d_src, src_pitch, nullptr, d_dst, dst_pitch, nullptr, (hipStream_t)hip_stream);
 }
 
 int fskhip_ratecvt_playback_device(fskhip_ratecvt *r, const float *d_src, size_t n_in, size_t src_pitch, const uint32_t *d_lens, void *d_dst, int format,
                                    int layout, size_t dst_pitch, void *hip_stream) {
-  return process(r, "fskhip_ratecvt_playback_device", FSKHIP_RATECVT_PLAYBACK, false, format, layout, n_in, d_src, src_pitch, d_lens, d_dst, dst_pitch, (hipStream_t)hip_stream);
+  return process(r, "fskhip_ratecvt_playback_device", FSKHIP_RATECVT_PLAYBACK, false, false, format, layout, n_in, d_src, src_pitch, d_lens, d_dst, dst_pitch, nullptr, (hipStream_t)hip_stream);
 }
 
 int fskhip_ratecvt_capture_host(fskhip_ratecvt *r, const void *src, int format, int layout, size_t n_in, size_t src_pitch, float *dst, size_t dst_pitch) {
-  return process(r, "fskhip_ratecvt_capture_host", FSKHIP_RATECVT_CAPTURE, true, format, layout, n_in, src, src_pitch, nullptr, dst, dst_pitch, nullptr);
+  return process(r, "fskhip_ratecvt_capture_host", FSKHIP_RATECVT_CAPTURE, true, false, format, layout, n_in, src, src_pitch, nullptr, dst, dst_pitch, nullptr, nullptr);
 }
 
 int fskhip_ratecvt_playback_host(fskhip_ratecvt *r, const float *src, size_t n_in, size_t src_pitch, const uint32_t *lens, void *dst, int format, int layout,
                                  size_t dst_pitch) {
-  return process(r, "fskhip_ratecvt_playback_host", FSKHIP_RATECVT_PLAYBACK, true, format, layout, n_in, src, src_pitch, lens, dst, dst_pitch, nullptr);
+  return process(r, "fskhip_ratecvt_playback_host", FSKHIP_RATECVT_PLAYBACK, true, false, format, layout, n_in, src, src_pitch, lens, dst, dst_pitch, nullptr, nullptr);
+}
+
+// the same four for calls of any length, from and to the handle's position
+int fskhip_ratecvt_capture_any_device(fskhip_ratecvt *r, const void *d_src, int format, int layout, size_t n_in, size_t src_pitch, float *d_dst, size_t dst_pitch,
+                                      size_t *n_out, void *hip_stream) {
+  return process(r, "fskhip_ratecvt_capture_any_device", FSKHIP_RATECVT_CAPTURE, false, true, format, layout, n_in, d_src, src_pitch, nullptr, d_dst, dst_pitch, n_out,
+                 (hipStream_t)hip_stream);
+}
+
+int fskhip_ratecvt_playback_any_device(fskhip_ratecvt *r, const float *d_src, size_t n_in, size_t src_pitch, const uint32_t *d_lens, void *d_dst, int format,
+                                       int layout, size_t dst_pitch, size_t *n_out, void *hip_stream) {
+  return process(r, "fskhip_ratecvt_playback_any_device", FSKHIP_RATECVT_PLAYBACK, false, true, format, layout, n_in, d_src, src_pitch, d_lens, d_dst, dst_pitch, n_out,
+                 (hipStream_t)hip_stream);
+}
+
+int fskhip_ratecvt_capture_any_host(fskhip_ratecvt *r, const void *src, int format, int layout, size_t n_in, size_t src_pitch, float *dst, size_t dst_pitch,
+                                    size_t *n_out) {
+  return process(r, "fskhip_ratecvt_capture_any_host", FSKHIP_RATECVT_CAPTURE, true, true, format, layout, n_in, src, src_pitch, nullptr, dst, dst_pitch, n_out, nullptr);
+}
+
+int fskhip_ratecvt_playback_any_host(fskhip_ratecvt *r, const float *src, size_t n_in, size_t src_pitch, const uint32_t *lens, void *dst, int format, int layout,
+                                     size_t dst_pitch, size_t *n_out) {
+  return process(r, "fskhip_ratecvt_playback_any_host", FSKHIP_RATECVT_PLAYBACK, true, true, format, layout, n_in, src, src_pitch, lens, dst, dst_pitch, n_out, nullptr);
 }
 
 }  // extern "C"

@@ -16,6 +16,15 @@
 //   sample-major   ns = 1 << log2_ns streams of one block each; LDS holds ns rows of x_pitch >= H + G M floats (x_pitch odd, so
 //                  that the streams of a frame land on different banks), and PLAYBACK a [G L][ns + 1] tile behind them through
 //                  which the frames leave
+//
+// Calls of any length.  A handle carries a position pos in [0, M): the inputs taken since the last period boundary, one word for
+// all its streams, 0 at creation and after a reset of all streams.  A call of n inputs is laid on the period grid as if it began
+// pos inputs before its first sample: input t of the call is input pos + t of the grid, the grid's outputs are numbered from the
+// boundary, and the call owns those whose newest input (jM) div L lies in [pos, pos + n): j from q0 = ceil(pos L / M) up to
+// ceil((pos + n) L / M), written at column j - q0.  Where L < M that can be none; the call still advances position and history.
+// The launch covers ceil((pos + n) / M) periods with the same workgroups, staged from H + pos inputs in front of the call: the first
+// workgroup's pos words in front of the history hold nothing, and the places outside the call's outputs are skipped, so none of them is
+// read (an owned output reads no further back than pos - H of the grid).  Afterwards pos is (pos + n) mod M.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -31,6 +40,17 @@ constexpr uint32_t kRatecvtTileOutputs = 64;      // outputs per stream of a sam
 inline uint32_t ratecvt_gcd(uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; }
 // elements per stream a call writes for n_in per stream (a multiple of M)
 inline size_t ratecvt_out_count(uint32_t L, uint32_t M, size_t n_in) { return n_in / M * L; }
+// the first output of the period grid that a call from position pos owns: ceil(pos L / M)
+inline size_t ratecvt_first_output(uint32_t L, uint32_t M, size_t pos) { return (pos * L + M - 1) / M; }
+// elements per stream a call of n_in per stream writes from position pos (any n_in; pos = 0 and n_in = kM: kL)
+inline size_t ratecvt_out_count_any(uint32_t L, uint32_t M, uint32_t pos, size_t n_in) {
+  return ratecvt_first_output(L, M, (size_t)pos + n_in) - ratecvt_first_output(L, M, pos);
+}
+// the smallest n_in with ratecvt_out_count_any(pos, n_in) >= n_out: the newest input of the last output wanted, and itself
+inline size_t ratecvt_in_count_any(uint32_t L, uint32_t M, uint32_t pos, size_t n_out) {
+  return n_out ? (ratecvt_first_output(L, M, pos) + n_out - 1) * M / L + 1 - pos : 0;
+}
+inline uint32_t ratecvt_next_position(uint32_t M, uint32_t pos, size_t n_in) { return (uint32_t)(((size_t)pos + n_in) % M); }
 // outputs that can be non-zero for a signal of `len` inputs: the last input meets the last tap at stuffed index (len - 1) L + n_taps - 1
 inline size_t ratecvt_out_length(uint32_t L, uint32_t M, uint32_t n_taps, size_t len) { return len ? ((len - 1) * L + n_taps - 1) / M + 1 : 0; }
 // output q of a period: its phase and how far its newest input lies behind the period's first
@@ -54,8 +74,8 @@ inline size_t ratecvt_tile_lds(uint32_t H, uint32_t L, uint32_t M, uint32_t G, u
   return sizeof(float) * (ns * x_pitch + (tile ? (size_t)G * L * (ns + 1u) : 0u));
 }
 
-// n_in: inputs per stream (> 0, a multiple of M); playback: the direction that leaves in the format (it alone needs the tile)
-inline RatecvtPlan ratecvt_plan(bool stream_major, bool playback, uint32_t L, uint32_t M, uint32_t n_taps, uint32_t n_streams, size_t n_in) {
+// a workgroup's shape, all of a plan but its grid; playback: the direction that leaves in the format (it alone needs the tile)
+inline RatecvtPlan ratecvt_shape(bool stream_major, bool playback, uint32_t L, uint32_t M, uint32_t n_taps) {
   RatecvtPlan P{};
   const uint32_t H = P.hist = resample_history(0, L, n_taps);
   if (stream_major) {
@@ -86,7 +106,20 @@ inline RatecvtPlan ratecvt_plan(bool stream_major, bool playback, uint32_t L, ui
     P.tile_words = playback ? P.G * L * (P.rows + 1u) : 0u;
     P.lds_bytes = ratecvt_tile_lds(H, L, M, P.G, P.log2_ns, playback);
   }
+  return P;
+}
+
+// n_in: inputs per stream (> 0, a multiple of M), from a period boundary
+inline RatecvtPlan ratecvt_plan(bool stream_major, bool playback, uint32_t L, uint32_t M, uint32_t n_taps, uint32_t n_streams, size_t n_in) {
+  RatecvtPlan P = ratecvt_shape(stream_major, playback, L, M, n_taps);
   resample_grid(P, P.seg_periods, stream_major, n_streams, n_in / M);
+  return P;
+}
+
+// n_in: inputs per stream (> 0, any), from position pos < M: the periods that hold inputs [pos, pos + n_in) of the grid
+inline RatecvtPlan ratecvt_plan_any(bool stream_major, bool playback, uint32_t L, uint32_t M, uint32_t n_taps, uint32_t n_streams, uint32_t pos, size_t n_in) {
+  RatecvtPlan P = ratecvt_shape(stream_major, playback, L, M, n_taps);
+  resample_grid(P, P.seg_periods, stream_major, n_streams, ((size_t)pos + n_in + M - 1) / M);
   return P;
 }
 

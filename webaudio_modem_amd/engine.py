@@ -262,6 +262,8 @@ def samples_out(fmt, layout, n_streams, n_per_stream, out=None):
         out = np.zeros(shape, _FORMAT_DTYPE[code])
     if not isinstance(out, np.ndarray) or out.dtype != _FORMAT_DTYPE[code] or out.shape != shape or not out.flags.writeable:
         raise ValueError("out must be a writeable %s array of shape %r" % (np.dtype(_FORMAT_DTYPE[code]).name, shape))
+    if not out.size:              # (no elements -- a rate converter's call that writes nothing: no strides to speak of, the rows are packed)
+        return out, code, lay, max(shape[1], 1)
     if _row_pitch(out) is None:
         raise ValueError("out must have contiguous rows at a constant pitch")
     return out, code, lay, _row_pitch(out)

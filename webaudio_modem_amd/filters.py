@@ -147,8 +147,9 @@ class _RateHandle:
             raise ValueError("state must be [%d, %d]" % (self.n_streams, self.history))
         _lib.check(self._fn("state_set")(self._h, st.ctypes.data))
 
-    def _widen(self, name, samples, fmt, layout, out_count):
-        """the _host call `name` from samples as FSKEngine.demodulate_samples takes them to float32 [S, out_count(n)]"""
+    def _widen(self, name, samples, fmt, layout, out_count, *tail):
+        """the _host call `name` from samples as FSKEngine.demodulate_samples takes them to float32 [S, out_count(n)]; `tail`: what
+        the call takes behind the pitches"""
         from .engine import sample_args
         x, code, lay, S, N, pitch = sample_args(samples, fmt, layout)
         if S != self.n_streams:
@@ -156,11 +157,12 @@ class _RateHandle:
         n_out = out_count(N)
         out = self._np.zeros((S, n_out), self._np.float32)
         if N:
-            _lib.check(self._fn(name)(self._h, x.ctypes.data, code, lay, N, pitch, out.ctypes.data, max(n_out, 1)))
+            _lib.check(self._fn(name)(self._h, x.ctypes.data, code, lay, N, pitch, out.ctypes.data, max(n_out, 1), *tail))
         return out
 
-    def _narrow(self, name, x, fmt, layout, lens, out, out_count):
-        """the _host call `name` from float32 [S, n] to out_count(n) samples per stream as FSKEngine.modulate_samples returns them"""
+    def _narrow(self, name, x, fmt, layout, lens, out, out_count, *tail):
+        """the _host call `name` from float32 [S, n] to out_count(n) samples per stream as FSKEngine.modulate_samples returns them;
+        `tail`: what the call takes behind the pitches"""
         from .engine import samples_out
         np = self._np
         x = np.asarray(x, dtype=np.float32)
@@ -176,7 +178,7 @@ class _RateHandle:
         if ln is not None and ln.shape != (self.n_streams,):
             raise ValueError("need one length per stream")
         _lib.check(self._fn(name)(self._h, x.ctypes.data, n, max(x.strides[0] // 4 if x.shape[0] > 1 else n, n, 1),
-                                  None if ln is None else ln.ctypes.data, out.ctypes.data, code, lay, pitch))
+                                  None if ln is None else ln.ctypes.data, out.ctypes.data, code, lay, pitch, *tail))
         return out
 
 
@@ -361,6 +363,28 @@ class _RateConverter(_RateHandle):
         """samples per stream a call with n_in per stream (a multiple of `down`) writes"""
         return int(n_in) // self.down * self.up
 
+    @property
+    def position(self):
+        """fskhip_ratecvt_position: the inputs taken since the last period boundary, 0 .. down - 1, one number for all streams; 0
+        at creation and after reset(), moved on by process_any.  Settable (fskhip_ratecvt_position_set): with state() / set_state()
+        the by-hand carry of a handle"""
+        return int(self._L.fskhip_ratecvt_position(self._h))
+
+    @position.setter
+    def position(self, pos):
+        if not 0 <= int(pos) < self.down:
+            raise ValueError("position %d outside 0..%d" % (int(pos), self.down - 1))
+        _lib.check(self._L.fskhip_ratecvt_position_set(self._h, int(pos)))
+
+    def out_count_any(self, n_in):
+        """samples per stream process_any writes for n_in per stream from the current position (fskhip_ratecvt_out_count_any)"""
+        return int(self._L.fskhip_ratecvt_out_count_any(self._h, int(n_in)))
+
+    def in_count_any(self, n_out):
+        """the fewest samples per stream for which process_any writes at least n_out from the current position -- exactly n_out
+        where up <= down (fskhip_ratecvt_in_count_any)"""
+        return int(self._L.fskhip_ratecvt_in_count_any(self._h, int(n_out)))
+
 
 class CaptureConverter(_RateConverter):
     """Capture samples at in_rate -> float32 [S, n / down * up] at out_rate, on the GPU (44.1 kHz in front of a 48 kHz engine:
@@ -378,6 +402,18 @@ class CaptureConverter(_RateConverter):
         from .engine import _sample_codes
         _lib.check(self._L.fskhip_ratecvt_capture_device(self._h, d_src, *_sample_codes(fmt, layout, True), n_in, src_pitch, d_dst, dst_pitch, stream))
 
+    def process_any(self, samples, fmt=None, layout="stream"):
+        """process() for any number of samples per stream, from the handle's position: returns float32 [S, out_count_any(n)] --
+        possibly no columns -- and moves the position on"""
+        return self._widen("capture_any_host", samples, fmt, layout, self.out_count_any, None)
+
+    def process_any_device(self, d_src, fmt, layout, n_in, src_pitch, d_dst, dst_pitch, stream=None):
+        """fskhip_ratecvt_capture_any_device: device pointers (ints), asynchronous on `stream`; returns the floats written per stream"""
+        from .engine import _sample_codes
+        n_out = C.c_size_t(0)
+        _lib.check(self._L.fskhip_ratecvt_capture_any_device(self._h, d_src, *_sample_codes(fmt, layout, True), n_in, src_pitch, d_dst, dst_pitch, C.byref(n_out), stream))
+        return n_out.value
+
 
 class PlaybackConverter(_RateConverter):
     """float32 [S, n] at in_rate -> samples of a capture format at out_rate, on the GPU (a 48 kHz engine in front of a 44.1 kHz
@@ -394,6 +430,19 @@ class PlaybackConverter(_RateConverter):
         """fskhip_ratecvt_playback_device: device pointers (ints), asynchronous on `stream`"""
         from .engine import _sample_codes
         _lib.check(self._L.fskhip_ratecvt_playback_device(self._h, d_src, n_in, src_pitch, d_lens, d_dst, *_sample_codes(fmt, layout, True), dst_pitch, stream))
+
+    def process_any(self, x, fmt, layout="stream", lens=None, out=None):
+        """process() for any number of floats per stream, from the handle's position: returns [S, out_count_any(n)] samples or
+        frames [out_count_any(n), S] -- possibly none -- and moves the position on; lens count from the call's first input"""
+        return self._narrow("playback_any_host", x, fmt, layout, lens, out, self.out_count_any, None)
+
+    def process_any_device(self, d_src, n_in, src_pitch, d_lens, d_dst, fmt, layout, dst_pitch, stream=None):
+        """fskhip_ratecvt_playback_any_device: device pointers (ints), asynchronous on `stream`; returns the samples written per stream"""
+        from .engine import _sample_codes
+        n_out = C.c_size_t(0)
+        _lib.check(self._L.fskhip_ratecvt_playback_any_device(self._h, d_src, n_in, src_pitch, d_lens, d_dst, *_sample_codes(fmt, layout, True), dst_pitch,
+                                                              C.byref(n_out), stream))
+        return n_out.value
 
     def out_length(self, n):
         """output samples that can be non-zero for a signal of n input samples: the signal and the filter's ringing behind it"""

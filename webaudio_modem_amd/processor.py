@@ -234,11 +234,18 @@ class FSKProcessorBatch:
             raise ValueError("%s is on device %r, the batch on %r" % (what, handle.device, device))
         return handle._h
 
-    def _rate_entry(self, form, upsampler, n_in, downsampler, n_out):
+    def _rate_entry(self, form, upsampler, n_in, downsampler, n_out, any_length=False):
         """the library call of form "host" / "device" for the handles of the sides that have samples (None: the side has none):
         fskhip_processor_process_rate_* for resamplers, fskhip_processor_process_ratecvt_* for converters (filters.CaptureConverter /
-        PlaybackConverter), whose counts are whole periods.  One call takes one kind."""
+        PlaybackConverter), whose counts are whole periods.  One call takes one kind.  any_length: the converters' call for
+        counts of any length, fskhip_processor_process_ratecvt_any_*; a resampler in a slot is a TypeError."""
         from . import filters
+        if any_length:
+            for what, h in (("upsampler", upsampler), ("downsampler", downsampler)):
+                if h is not None and not isinstance(h, filters._RateConverter):
+                    raise TypeError("%s is a %s: quanta of any length go through rate converters (filters.CaptureConverter / PlaybackConverter)"
+                                    % (what, type(h).__name__))
+            return getattr(self._L, "fskhip_processor_process_ratecvt_any_" + form)
         kinds = [isinstance(h, filters._RateConverter) for h in (upsampler, downsampler) if h is not None]
         if len(set(kinds)) > 1:
             raise ValueError("upsampler is a %s and downsampler a %s: one call takes resamplers or rate converters, not one of each"
@@ -265,6 +272,10 @@ class FSKProcessorBatch:
         inputs are a multiple of the capture converter's `down` samples per stream, n_out a multiple of the playback
         converter's `up`, and the state ends as CaptureConverter.process -> process() -> PlaybackConverter.process leaves it,
         bit for bit.  One call takes resamplers or converters, not one of each."""
+        return self._samples_at(False, inputs, in_fmt, in_layout, upsampler, n_out, out_fmt, out_layout, downsampler)
+
+    def _samples_at(self, any_length, inputs, in_fmt, in_layout, upsampler, n_out, out_fmt, out_layout, downsampler):
+        """process_samples_at (any_length False) and process_samples_at_any: the host form behind their argument checks"""
         from . import filters
         in_code, in_lay = _sample_codes(in_fmt, in_layout)
         out_code, out_lay = _sample_codes(out_fmt, out_layout)      # (every argument check comes before the call is counted)
@@ -278,7 +289,7 @@ class FSKProcessorBatch:
             up_h = self._rate_handle(upsampler, filters.Upsampler, "upsampler")
         if n_out:
             down_h = self._rate_handle(downsampler, filters.Downsampler, "downsampler")
-        entry = self._rate_entry("host", upsampler if inputs is not None else None, n_in, downsampler if n_out else None, int(n_out))
+        entry = self._rate_entry("host", upsampler if inputs is not None else None, n_in, downsampler if n_out else None, int(n_out), any_length)
         out, out_pitch = None, 0
         if n_out:
             out, out_code, out_lay, out_pitch = samples_out(out_fmt, out_layout, self.n_streams, int(n_out))
@@ -289,15 +300,35 @@ class FSKProcessorBatch:
             out.ctypes.data if out is not None else None, out_code, out_lay, int(n_out), out_pitch, self.flags))
         return out
 
+    def process_samples_at_any(self, inputs=None, in_fmt="mulaw", in_layout="sample", upsampler=None, n_out=0, out_fmt="mulaw", out_layout="sample",
+                               downsampler=None):
+        """process_samples_at() through a filters.CaptureConverter and a filters.PlaybackConverter for quanta of any length -- a
+        WebAudio render quantum of 128 frames at 44.1 kHz as it arrives: fskhip_processor_process_ratecvt_any_host.  The handles
+        carry their positions (filters: `position`) from call to call beside their histories; the state ends as
+        CaptureConverter.process_any -> process() with the engine counts the handles give (upsampler.out_count_any(n),
+        downsampler.in_count_any(n_out); a side with none is left out) -> PlaybackConverter.process_any leaves it, bit for bit.
+        An n_out that the playback converter cannot write from its position (only where its up > down) is the library's refusal.
+        A resampler in a slot is a TypeError."""
+        return self._samples_at(True, inputs, in_fmt, in_layout, upsampler, n_out, out_fmt, out_layout, downsampler)
+
+    def process_samples_at_any_device(self, d_in, in_fmt, in_layout, n_in, in_pitch, upsampler, d_out, out_fmt, out_layout, n_out, out_pitch, downsampler,
+                                      stream=None, flags=None):
+        """fskhip_processor_process_ratecvt_any_device: process_samples_at_device for converters and counts of any length"""
+        self._samples_at_device(True, d_in, in_fmt, in_layout, n_in, in_pitch, upsampler, d_out, out_fmt, out_layout, n_out, out_pitch, downsampler, stream, flags)
+
     def process_samples_at_device(self, d_in, in_fmt, in_layout, n_in, in_pitch, upsampler, d_out, out_fmt, out_layout, n_out, out_pitch, downsampler,
                                   stream=None, flags=None):
         """fskhip_processor_process_rate_device: device pointers (ints or None), lengths and pitches in low rate elements,
         asynchronous on `stream`.  The handle of a side whose pointer is None may be None.  With converters
         (filters.CaptureConverter / PlaybackConverter) it is fskhip_processor_process_ratecvt_device, as in process_samples_at."""
+        self._samples_at_device(False, d_in, in_fmt, in_layout, n_in, in_pitch, upsampler, d_out, out_fmt, out_layout, n_out, out_pitch, downsampler, stream, flags)
+
+    def _samples_at_device(self, any_length, d_in, in_fmt, in_layout, n_in, in_pitch, upsampler, d_out, out_fmt, out_layout, n_out, out_pitch, downsampler, stream, flags):
+        """process_samples_at_device (any_length False) and process_samples_at_any_device"""
         from . import filters
         up_h = None if d_in is None and upsampler is None else self._rate_handle(upsampler, filters.Upsampler, "upsampler")
         down_h = None if d_out is None and downsampler is None else self._rate_handle(downsampler, filters.Downsampler, "downsampler")
-        entry = self._rate_entry("device", None if d_in is None else upsampler, n_in, None if d_out is None else downsampler, n_out)
+        entry = self._rate_entry("device", None if d_in is None else upsampler, n_in, None if d_out is None else downsampler, n_out, any_length)
         _lib.check(entry(self._h, up_h, down_h, d_in, *_sample_codes(in_fmt, in_layout, True), n_in, in_pitch,
                          d_out, *_sample_codes(out_fmt, out_layout, True), n_out, out_pitch, self.flags if flags is None else flags, stream))
 
