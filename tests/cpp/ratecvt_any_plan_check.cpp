@@ -7,7 +7,7 @@
 //   * ratecvt_out_count_any summed over a cut equals the uncut count, whole periods from 0 give ratecvt_out_count, and the
 //     position after the cut is the position after the whole;
 //   * ratecvt_in_count_any is the smallest n_in that writes n_out, and writes exactly n_out where L <= M;
-//   * walking the launch as ratecvt_any_body cuts it: every output that it would evaluate reads staged indices x0 - k inside
+//   * walking the launch as ratecvt_body<ANY> cuts it: every output that it would evaluate reads staged indices x0 - k inside
 //     [0, span) of its row and inside the call's inputs and the history in front of them, its newest input is input (jM) div L of
 //     the grid; every output of the call is evaluated by exactly one workgroup, row and place, and every word of the next history
 //     is written by exactly one workgroup, from the call's inputs or the old history.
@@ -63,10 +63,10 @@ static void counts(uint32_t L, uint32_t M) {
   }
 }
 
-// one launch over one stream tile, workgroup by workgroup, as ratecvt_any_body cuts it
+// one launch over one stream tile, workgroup by workgroup, as ratecvt_body<ANY> cuts it
 static void walk(bool rows, bool playback, uint32_t L, uint32_t M, uint32_t taps, uint32_t pos, size_t n_in) {
   const uint32_t S = rows ? 1u : 3u;
-  const RatecvtPlan P = ratecvt_plan_any(rows, playback, L, M, taps, S, pos, n_in);
+  const RatecvtPlan P = ratecvt_plan(rows, playback, L, M, taps, S, pos, n_in);
   const uint32_t H = P.hist, ns = 1u << P.log2_ns, Qs = P.G * L, k_full = taps / L, rem = taps % L;
   const size_t j_lo = ratecvt_first_output(L, M, pos), j_hi = ratecvt_first_output(L, M, pos + n_in), n_out = ratecvt_out_count_any(L, M, pos, n_in);
   const size_t x_words = (size_t)ns * P.x_pitch, periods = ceil_div(pos + n_in, M);
@@ -120,8 +120,10 @@ static void ratio(uint32_t L, uint32_t M) {
   counts(L, M);
   for (const uint32_t taps : {1u, L, L + 1u, 16u * (L > M ? L : M) + 1u}) {
     for (int rows = 0; rows < 2; rows++) {
-      // a whole-period launch from 0 is the plan the existing kernels take
-      const RatecvtPlan A = ratecvt_plan_any(rows, true, L, M, taps, 5, 0, (size_t)7 * M), B = ratecvt_plan(rows, true, L, M, taps, 5, (size_t)7 * M);
+      // a whole-period launch from 0 is the plan the whole-period kernels take: the shape's grid over n_in / M periods
+      const RatecvtPlan A = ratecvt_plan(rows, true, L, M, taps, 5, 0, (size_t)7 * M);
+      RatecvtPlan B = ratecvt_shape(rows, true, L, M, taps);
+      resample_grid(B, B.seg_periods, rows, 5, 7);
       CHECK(A.blocks == B.blocks && A.split == B.split && A.span == B.span && A.lds_bytes == B.lds_bytes && A.G == B.G, "%u/%u taps %u", L, M, taps);
       for (uint32_t pos = 0; pos < M; pos++)
         for (size_t n = 1; n <= 3u * M + 1u; n++) walk(rows, rows == 0 && ((pos + n) & 1u), L, M, taps, pos, n);

@@ -29,7 +29,7 @@ static int failures = 0;
 // and the LDS words it touches
 static void walk(bool rows, bool playback, uint32_t L, uint32_t M, uint32_t taps, size_t n_in) {
   const uint32_t S = rows ? 1u : 3u;
-  const RatecvtPlan P = ratecvt_plan(rows, playback, L, M, taps, S, n_in);
+  const RatecvtPlan P = ratecvt_plan(rows, playback, L, M, taps, S, 0, n_in);
   const uint32_t H = P.hist, ns = 1u << P.log2_ns, Qs = P.G * L, k_full = taps / L, rem = taps % L;
   const size_t n_out = ratecvt_out_count(L, M, n_in), x_words = (size_t)ns * P.x_pitch, lds_words = P.lds_bytes / 4;
   const uint64_t segs = rows ? P.split : P.blocks / P.split;
@@ -78,8 +78,8 @@ static int table() {
     const uint32_t L = pr[0], M = pr[1];
     for (const uint32_t taps : {1u, 5u, L > 1 ? L - 1 : 1u, 13u, 16 * (L > M ? L : M) + 1})
       for (int playback = 0; playback < 2; playback++)
-        std::printf("%u %u %u %d %u %u\n", L, M, taps, playback, ratecvt_plan(true, playback, L, M, taps, 1, M).seg_periods,
-                    ratecvt_plan(false, playback, L, M, taps, 1, M).seg_periods);
+        std::printf("%u %u %u %d %u %u\n", L, M, taps, playback, ratecvt_plan(true, playback, L, M, taps, 1, 0, M).seg_periods,
+                    ratecvt_plan(false, playback, L, M, taps, 1, 0, M).seg_periods);
   }
   return 0;
 }
@@ -115,7 +115,7 @@ int main(int argc, char **argv) {
       CHECK(sum == taps && longest == K && H + 1 >= K && (uint64_t)H * L >= taps - 1 && (uint64_t)(H ? H - 1 : 0) * L < taps, "%u/%u taps %u", L, M, taps);
       for (int rows = 0; rows < 2; rows++) {
         for (int playback = 0; playback < 2; playback++) {
-          const RatecvtPlan P = ratecvt_plan(rows, playback, L, M, taps, 130, (size_t)M);
+          const RatecvtPlan P = ratecvt_plan(rows, playback, L, M, taps, 130, 0, (size_t)M);
           const uint32_t ns = 1u << P.log2_ns;
           CHECK(P.lds_bytes <= kResampleLdsBytes && P.hist == H && P.G >= 1 && P.span == H + P.seg_periods * M && P.x_pitch >= P.span, "%u/%u taps %u", L, M, taps);
           CHECK(rows ? (ns == 1 && P.rows == 4 && P.seg_periods == 4 * P.G && P.row_stride == P.G * M && P.lds_bytes == 4ull * P.span)
@@ -134,8 +134,8 @@ int main(int argc, char **argv) {
             ratecvt_out_length(6, 1, 97, 10) == 151 && ratecvt_out_length(1, 6, 97, 48000) == 8016,
         "lengths");
   CHECK(resample_history(0, 160, 2561) == 16 && resample_history(0, 147, 2561) == 18 && resample_history(0, 1, 1) == 0, "histories");
-  CHECK(ratecvt_plan(true, false, 1, 1, 1, 0x7FFFFFFFu, (size_t)1 << 40).blocks == 0, "a grid past one launch");
-  CHECK(ratecvt_plan(false, true, 1, 1, 1, 64, (size_t)1 << 40).blocks == 0, "a grid past one launch");
+  CHECK(ratecvt_plan(true, false, 1, 1, 1, 0x7FFFFFFFu, 0, (size_t)1 << 40).blocks == 0, "a grid past one launch");
+  CHECK(ratecvt_plan(false, true, 1, 1, 1, 64, 0, (size_t)1 << 40).blocks == 0, "a grid past one launch");
   if (failures) { std::printf("%d failures\n", failures); return 1; }
   std::printf("ok\n");
   return 0;

@@ -1,5 +1,5 @@
 """The rate converter's calls of any length on the GPU (include/fskhip_next.h: "Rate conversion in calls of any length";
-csrc/fsk_ratecvt.hip: ratecvt_any_body).  Both directions, fp32 and fp64, s16 / mu-law / A-law / float, both layouts; ratios
+csrc/fsk_ratecvt.hip: the ANY form of ratecvt_body).  Both directions, fp32 and fp64, s16 / mu-law / A-law / float, both layouts; ratios
 3 / 2 and 2 / 3 with 7 and 8 taps, 160 / 147 and 147 / 160 with the default 2 561 taps; 1, 5 and 67 streams (a partly filled
 64-stream tile behind a full one).
 

@@ -152,17 +152,14 @@ hipError_t launch_resample_down(int precision, const float *d_src, size_t n_out,
                                 float *d_hist_out, hipStream_t st);
 // fsk_ratecvt.hip: rate conversion by up / down (fskhip_ratecvt_*), one launch of either direction (FSKHIP_RATECVT_*).  CAPTURE reads
 // d_src in the format and layout and writes float32 rows to d_dst, PLAYBACK the other way round with d_lens as launch_resample_down
-// takes it; n_in > 0 inputs per stream, a multiple of `down`; d_taps [ceil(n_taps / up)][up] in output order and d_table
-// (fsk_ratecvt_plan.h), histories [n_streams][ceil((n_taps - 1) / up)].  The caller has checked the arguments;
-// hipErrorInvalidValue where the batch is more workgroups than one launch takes.
+// takes it; any n_in > 0 inputs per stream from the handle's position pos < down (fsk_ratecvt_plan.h): the call writes
+// ratecvt_out_count_any(up, down, pos, n_in) per stream, possibly none, and always the next history; pos = 0 with n_in a multiple
+// of `down` runs the whole-period kernels.  d_taps [ceil(n_taps / up)][up] in output order and d_table (fsk_ratecvt_plan.h),
+// histories [n_streams][ceil((n_taps - 1) / up)].  The caller has checked the arguments; hipErrorInvalidValue where the batch is
+// more workgroups than one launch takes.
 hipError_t launch_ratecvt(int direction, int precision, const void *d_src, size_t src_pitch, const uint32_t *d_lens, void *d_dst, size_t dst_pitch, int format,
-                          int layout, uint32_t n_streams, size_t n_in, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps, const uint32_t *d_table,
-                          const float *d_hist_in, float *d_hist_out, hipStream_t st);
-// the same for any n_in > 0 from the handle's position pos < down (fsk_ratecvt_plan.h): the call writes ratecvt_out_count_any(up,
-// down, pos, n_in) per stream, possibly none, and always the next history; pos = 0 with whole periods is launch_ratecvt
-hipError_t launch_ratecvt_any(int direction, int precision, const void *d_src, size_t src_pitch, const uint32_t *d_lens, void *d_dst, size_t dst_pitch, int format,
-                              int layout, uint32_t n_streams, uint32_t pos, size_t n_in, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps,
-                              const uint32_t *d_table, const float *d_hist_in, float *d_hist_out, hipStream_t st);
+                          int layout, uint32_t n_streams, uint32_t pos, size_t n_in, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps,
+                          const uint32_t *d_table, const float *d_hist_in, float *d_hist_out, hipStream_t st);
 // fsk_resample_remap.hip: a resampler's history rows (H floats at a pitch of H floats, both bases 16-byte aligned) gathered through
 // a map (fskhip_resampler_remap / _snapshot / _restore).  Row i of d_dst (n_rows rows) takes row d_map[i] of d_src -- row
 // ident0 + i where d_map is null --, zeros where the entry is -1.  from_image: d_src is a staging slab holding records

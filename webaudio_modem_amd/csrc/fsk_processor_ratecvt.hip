@@ -60,9 +60,9 @@ int launch_quantum_ratecvt(const char *who, fskhip_processor *p, const Side &in,
   if (in.ptr) {
     fskhip_ratecvt *const c = cvt(in);
     if (in.n) {
-      if (const int rc = launch_failed(who, launch_ratecvt_any(FSKHIP_RATECVT_CAPTURE, c->precision, in.ptr, in.pitch, nullptr, p->d_fin, fin_pitch, in.format,
-                                                               in.layout, p->S, c->pos, in.n, c->L, c->M, c->n_taps, c->taps(), c->d_table, c->hist[c->cur],
-                                                               c->hist[c->cur ^ 1], st),
+      if (const int rc = launch_failed(who, launch_ratecvt(FSKHIP_RATECVT_CAPTURE, c->precision, in.ptr, in.pitch, nullptr, p->d_fin, fin_pitch, in.format,
+                                                           in.layout, p->S, c->pos, in.n, c->L, c->M, c->n_taps, c->taps(), c->d_table, c->hist[c->cur],
+                                                           c->hist[c->cur ^ 1], st),
                                        p->S, in.n)) return rc;
       if (c->H) c->cur ^= 1;
       c->pos = ratecvt_next_position(c->M, c->pos, in.n);
@@ -82,9 +82,9 @@ int launch_quantum_ratecvt(const char *who, fskhip_processor *p, const Side &in,
                                         d->hist[d->cur ^ 1], st));
   } else {
     HIP_TRY(launch_processor_io(p->e->M, p->e->S.coef, p->T, p->d_bytes, p->bytes_pitch, p->d_counts, rx, p->d_ftx, n_ho, ftx_pitch, clear, st));
-    if (const int rc = launch_failed(who, launch_ratecvt_any(FSKHIP_RATECVT_PLAYBACK, d->precision, p->d_ftx, ftx_pitch, nullptr, const_cast<void *>(out.ptr),
-                                                             out.pitch, out.format, out.layout, p->S, d->pos, n_ho, d->L, d->M, d->n_taps, d->taps(), d->d_table,
-                                                             d->hist[d->cur], d->hist[d->cur ^ 1], st), p->S, n_ho)) return rc;
+    if (const int rc = launch_failed(who, launch_ratecvt(FSKHIP_RATECVT_PLAYBACK, d->precision, p->d_ftx, ftx_pitch, nullptr, const_cast<void *>(out.ptr),
+                                                         out.pitch, out.format, out.layout, p->S, d->pos, n_ho, d->L, d->M, d->n_taps, d->taps(), d->d_table,
+                                                         d->hist[d->cur], d->hist[d->cur ^ 1], st), p->S, n_ho)) return rc;
   }
   if (d->H) d->cur ^= 1;
   d->pos = ratecvt_next_position(d->M, d->pos, n_ho);

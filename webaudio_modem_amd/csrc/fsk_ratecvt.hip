@@ -13,11 +13,11 @@
 // LDS word where L > M, at most ceil(M / L) apart otherwise.  PLAYBACK in sample-major layout leaves through a [outputs][ns + 1]
 // tile.
 //
-// A call of any length from any position of the handle (fsk_ratecvt_plan.h: "Calls of any length") is the same shape of body laid on
-// the period grid `pos` inputs in front of the call's first: it stages from there, skips the places whose output is not the
-// call's and stores output j of the grid at column j - ceil(pos L / M): ratecvt_any_body, a body of its own beside ratecvt_body,
-// with its own instantiations and launch.  The whole-period calls of a handle at position 0 keep ratecvt_body and launch_ratecvt
-// as they were.
+// One body, ratecvt_body, in two forms.  ANY lays a call of any length from any position of the handle (fsk_ratecvt_plan.h: "Calls
+// of any length") on the period grid `pos` inputs in front of the call's first: it stages from there, skips the places whose
+// output is not the call's and stores output j of the grid at column j - ceil(pos L / M).  !ANY is a call of whole periods from
+// position 0, which owns every output of its grid and so has neither the skip nor the position (it measured 1.22 times faster for
+// fp32 playback frames): both forms keep their 32 instantiations, in one table with one signature, and launch_ratecvt picks.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -36,15 +36,15 @@ namespace {
 
 struct RatecvtShape { uint32_t hist, G, rows, log2_ns, x_pitch, row_stride, span, seg_periods, split; };   // (RatecvtPlan's, as the kernels take it)
 
-// one signature for both directions: CAPTURE reads `src` in the format and writes float rows, PLAYBACK the other way round;
-// n_in = inputs per stream (a multiple of M); d_lens is PLAYBACK's
+// one signature for both directions and both forms: CAPTURE reads `src` in the format and writes float rows, PLAYBACK the other
+// way round; n_in = inputs per stream; d_lens is PLAYBACK's; pos: the handle's position (ANY; unused otherwise)
 #define FSK_RATECVT_PARAMS                                                                                                       \
   const void *__restrict__ src_, size_t src_pitch, const uint32_t *__restrict__ d_lens, void *__restrict__ dst_, size_t dst_pitch, \
       const float *__restrict__ hist_in, float *__restrict__ hist_out, const void *__restrict__ taps_, const uint32_t *__restrict__ table, \
-      uint32_t n_streams, size_t n_in, uint32_t L, uint32_t M, uint32_t n_taps, RatecvtShape G
-#define FSK_RATECVT_ARGS src_, src_pitch, d_lens, dst_, dst_pitch, hist_in, hist_out, taps_, table, n_streams, n_in, L, M, n_taps, G
+      uint32_t n_streams, size_t n_in, uint32_t L, uint32_t M, uint32_t n_taps, RatecvtShape G, uint32_t pos
+#define FSK_RATECVT_ARGS src_, src_pitch, d_lens, dst_, dst_pitch, hist_in, hist_out, taps_, table, n_streams, n_in, L, M, n_taps, G, pos
 
-template <typename Real, int FMT, int LAYOUT, int DIR>
+template <typename Real, int FMT, int LAYOUT, int DIR, bool ANY>
 __device__ __forceinline__ void ratecvt_body(FSK_RATECVT_PARAMS) {
   using F = SampleFmt<FMT>;
   constexpr bool kRows = LAYOUT == FSKHIP_LAYOUT_STREAM_MAJOR, kPlay = DIR == FSKHIP_RATECVT_PLAYBACK;
@@ -57,134 +57,15 @@ __device__ __forceinline__ void ratecvt_body(FSK_RATECVT_PARAMS) {
   const uint32_t hi = blockIdx.x / G.split, lo = blockIdx.x - hi * G.split;
   const uint32_t s0 = kRows ? hi : lo << G.log2_ns;
   const size_t per0 = (size_t)(kRows ? lo : hi) * G.seg_periods;        // the workgroup's first period
-  const size_t m0 = per0 * M, j0 = per0 * L, n_out = n_in / M * L;
-
-  // input i of the staged span of stream s0 + c; `len`: inputs from there on read as 0.0f
-  auto stage = [&](uint32_t c, uint32_t i, size_t len) {
-    const uint32_t s = s0 + c;
-    const int64_t m = (int64_t)m0 + (int64_t)i - (int64_t)H;
-    float v = 0.0f;
-    if (s < n_streams) {
-      if (m >= 0) {
-        if ((size_t)m < len) {
-          if constexpr (kPlay) v = ((const float *)src_)[(size_t)s * src_pitch + (size_t)m];
-          else v = F::decode(((const typename F::T *)src_)[kRows ? (size_t)s * src_pitch + (size_t)m : (size_t)m * src_pitch + s]);
-        }
-      } else {
-        v = hist_in[(size_t)s * H + (size_t)(m + (int64_t)H)];
-      }
-      // the history after the call: the last H samples, each written by the workgroup whose periods hold it (the first
-      // workgroup's for what stays of the old history)
-      const int64_t h = m + (int64_t)H - (int64_t)n_in;
-      if ((i >= H || m0 == 0) && h >= 0 && m < (int64_t)n_in) hist_out[(size_t)s * H + (size_t)h] = v;
-    }
-    xs[c * G.x_pitch + i] = v;
-  };
-  if constexpr (kRows || kPlay) {                                        // the staged side lies stream by stream
-    for (uint32_t c = 0; c < ns; c++) {
-      size_t len = n_in;
-      if (kPlay && d_lens && s0 + c < n_streams) len = d_lens[s0 + c] < n_in ? (size_t)d_lens[s0 + c] : n_in;
-      for (uint32_t i = tid; i < span; i += kResampleThreads) stage(c, i, len);
-    }
-  } else {                                                               // frames: consecutive lanes take a frame's streams
-    for (uint32_t idx = tid; idx < (span << G.log2_ns); idx += kResampleThreads) stage(idx & (ns - 1u), idx >> G.log2_ns, n_in);
-  }
-  __syncthreads();
-
-  // item w: place u = w % (G L) of the rows 4 (w / (G L)) .. + 3.  Row r is block r of the stream (stream-major; output
-  // j0 + r G L + u) or stream s0 + r (sample-major; output j0 + u); its inputs start r * row_stride floats into xs.
-  const uint32_t Qs = G.G * L, n_quads = (G.rows + 3u) / 4u;
-  const uint32_t k_full = n_taps / L, rem = n_taps - k_full * L;        // phase p has k_full + (p < rem) taps
-  for (uint32_t w = tid; w < n_quads * Qs; w += kResampleThreads) {
-    const uint32_t quad = w / Qs, u = w - quad * Qs;
-    const uint32_t per = u / L, q = u - per * L;
-    const uint32_t word = table[q], p = word >> 16;
-    const uint32_t x0 = H + per * M + (word & 0xFFFFu);                  // x[m] of row 0 of the stream's span; x[m - k]: k <= H
-    uint32_t xb[4];
-#pragma unroll
-    for (uint32_t r = 0; r < 4u; r++) {
-      const uint32_t row = quad * 4u + r < G.rows ? quad * 4u + r : quad * 4u;   // (a row past the last computes the quad's first again, unused)
-      xb[r] = row * G.row_stride + x0;
-    }
-    Real acc[4] = {0, 0, 0, 0};
-    const Real *tp = taps + q;
-#pragma unroll 4
-    for (uint32_t k = 0; k < k_full; k++) {
-      const Real cc = tp[(size_t)k * L];
-#pragma unroll
-      for (uint32_t r = 0; r < 4u; r++) acc[r] = mac(acc[r], cc, xs[xb[r] - k]);
-    }
-    if (p < rem) {
-      const Real cc = tp[(size_t)k_full * L];
-#pragma unroll
-      for (uint32_t r = 0; r < 4u; r++) acc[r] = mac(acc[r], cc, xs[xb[r] - k_full]);
-    }
-#pragma unroll
-    for (uint32_t r = 0; r < 4u; r++) {
-      const uint32_t row = quad * 4u + r;
-      if (row >= G.rows) continue;
-      const size_t j = j0 + (kRows ? (size_t)row * Qs : 0u) + u;
-      const uint32_t s = kRows ? s0 : s0 + row;
-      if (j >= n_out || s >= n_streams) continue;
-      if constexpr (!kPlay) {
-        ((float *)dst_)[(size_t)s * dst_pitch + j] = (float)acc[r];
-      } else if constexpr (kRows) {
-        ((typename F::Bits *)dst_)[(size_t)s * dst_pitch + j] = (typename F::Bits)F::encode((float)acc[r]);
-      } else {
-        tile[u * (ns + 1u) + row] = F::encode((float)acc[r]);
-      }
-    }
-  }
-  if constexpr (kPlay && !kRows) {
-    __syncthreads();
-    for (uint32_t idx = tid; idx < (Qs << G.log2_ns); idx += kResampleThreads) {
-      const uint32_t c = idx & (ns - 1u), u = idx >> G.log2_ns;
-      if (s0 + c < n_streams && j0 + u < n_out) ((typename F::Bits *)dst_)[(j0 + u) * dst_pitch + s0 + c] = (typename F::Bits)tile[u * (ns + 1u) + c];
-    }
-  }
-}
-
-template <typename Real, int FMT, int LAYOUT>
-__global__ __launch_bounds__(kResampleThreads) void ratecvt_capture_kernel(FSK_RATECVT_PARAMS) {
-  ratecvt_body<Real, FMT, LAYOUT, FSKHIP_RATECVT_CAPTURE>(FSK_RATECVT_ARGS);
-}
-
-template <typename Real, int FMT, int LAYOUT>
-__global__ __launch_bounds__(kResampleThreads) void ratecvt_playback_kernel(FSK_RATECVT_PARAMS) {
-  ratecvt_body<Real, FMT, LAYOUT, FSKHIP_RATECVT_PLAYBACK>(FSK_RATECVT_ARGS);
-}
-
-// every instantiation, once: [direction][precision][format][layout], in the order of the headers' enums
-using RatecvtFn = void (*)(const void *, size_t, const uint32_t *, void *, size_t, const float *, float *, const void *, const uint32_t *, uint32_t, size_t, uint32_t,
-                           uint32_t, uint32_t, RatecvtShape);
-const KernelEntry<RatecvtFn> kRatecvtKernels[2][2][4][2] = {
-    {FSK_FORMAT_KERNELS(ratecvt_capture_kernel, float), FSK_FORMAT_KERNELS(ratecvt_capture_kernel, double)},
-    {FSK_FORMAT_KERNELS(ratecvt_playback_kernel, float), FSK_FORMAT_KERNELS(ratecvt_playback_kernel, double)}};
-
-// ratecvt_body for a call of any length from position `pos` of the handle (fsk_ratecvt_plan.h: "Calls of any length"): the same
-// staging, rows, tap order and stores, laid on the period grid `pos` inputs in front of the call's first
-template <typename Real, int FMT, int LAYOUT, int DIR>
-__device__ __forceinline__ void ratecvt_any_body(FSK_RATECVT_PARAMS, uint32_t pos) {
-  using F = SampleFmt<FMT>;
-  constexpr bool kRows = LAYOUT == FSKHIP_LAYOUT_STREAM_MAJOR, kPlay = DIR == FSKHIP_RATECVT_PLAYBACK;
-  extern __shared__ __align__(16) unsigned char lds_raw[];
-  float *const xs = reinterpret_cast<float *>(lds_raw);                 // [ns][x_pitch]: hist floats of history, then the periods' inputs
-  const Real *const taps = (const Real *)taps_;                          // [K][L]
-  const uint32_t tid = threadIdx.x;
-  const uint32_t H = G.hist, span = G.span, ns = 1u << G.log2_ns;
-  uint32_t *const tile = reinterpret_cast<uint32_t *>(xs + (size_t)ns * G.x_pitch);   // [G L][ns + 1] (PLAYBACK, sample-major)
-  const uint32_t hi = blockIdx.x / G.split, lo = blockIdx.x - hi * G.split;
-  const uint32_t s0 = kRows ? hi : lo << G.log2_ns;
-  const size_t per0 = (size_t)(kRows ? lo : hi) * G.seg_periods;        // the workgroup's first period
-  // m0, j0: the period's first input and output on the period grid, which begins `pos` inputs in front of the call; the call's
-  // outputs are j_lo .. j_hi - 1 of the grid, those whose newest input lies in the call
+  // m0, j0: the period's first input and output on the period grid, which begins `pos` inputs in front of the call (ANY; at the
+  // call's first otherwise); the call's outputs are j_lo .. j_hi - 1 of the grid, those whose newest input lies in the call
   const size_t m0 = per0 * M, j0 = per0 * L;
-  const size_t j_lo = ((size_t)pos * L + M - 1u) / M, j_hi = ((pos + n_in) * L + M - 1u) / M;
+  const size_t j_lo = ANY ? ((size_t)pos * L + M - 1u) / M : 0u, j_hi = ANY ? ((pos + n_in) * L + M - 1u) / M : n_in / M * L;
 
   // input i of the staged span of stream s0 + c; `len`: inputs of the call from there on read as 0.0f
   auto stage = [&](uint32_t c, uint32_t i, size_t len) {
     const uint32_t s = s0 + c;
-    const int64_t m = (int64_t)m0 + (int64_t)i - (int64_t)H - (int64_t)pos;   // counted from the call's first input
+    const int64_t m = (int64_t)m0 + (int64_t)i - (int64_t)H - (int64_t)(ANY ? pos : 0u);   // counted from the call's first input
     float v = 0.0f;
     if (s < n_streams) {
       if (m >= 0) {
@@ -192,7 +73,7 @@ __device__ __forceinline__ void ratecvt_any_body(FSK_RATECVT_PARAMS, uint32_t po
           if constexpr (kPlay) v = ((const float *)src_)[(size_t)s * src_pitch + (size_t)m];
           else v = F::decode(((const typename F::T *)src_)[kRows ? (size_t)s * src_pitch + (size_t)m : (size_t)m * src_pitch + s]);
         }
-      } else if (m >= -(int64_t)H) {                                    // (the first workgroup's `pos` words in front of the history are no input)
+      } else if (!ANY || m >= -(int64_t)H) {                            // (ANY: the first workgroup's `pos` words in front of the history are no input)
         v = hist_in[(size_t)s * H + (size_t)(m + (int64_t)H)];
       }
       // the history after the call: the last H samples, each written by the workgroup whose periods hold it (the first
@@ -222,21 +103,30 @@ __device__ __forceinline__ void ratecvt_any_body(FSK_RATECVT_PARAMS, uint32_t po
     const uint32_t per = u / L, q = u - per * L;
     const uint32_t word = table[q], p = word >> 16;
     const uint32_t x0 = H + per * M + (word & 0xFFFFu);                  // x[m] of row 0 of the stream's span; x[m - k]: k <= H
+    const auto grid_output = [&](uint32_t row) -> size_t { return j0 + (kRows ? (size_t)row * Qs : 0u) + u; };
     uint32_t xb[4];
-    // a place outside the call's outputs is not evaluated: the lane's first own row is computed again in its stead, unused, and a
-    // lane without one has nothing to do
-    bool own[4];
-    uint32_t first = 4u;
+    bool own[4];                                                         // (ANY) row r's output is the call's
+    if constexpr (ANY) {
+      // a place outside the call's outputs is not evaluated: the lane's first own row is computed again in its stead, unused, and
+      // a lane without one has nothing to do
+      uint32_t first = 4u;
 #pragma unroll
-    for (uint32_t r = 4u; r-- > 0u;) {
-      const uint32_t row = quad * 4u + r;
-      const size_t j = j0 + (kRows ? (size_t)row * Qs : 0u) + u;
-      own[r] = row < G.rows && j >= j_lo && j < j_hi;
-      if (own[r]) first = r;
+      for (uint32_t r = 4u; r-- > 0u;) {
+        const uint32_t row = quad * 4u + r;
+        const size_t j = grid_output(row);
+        own[r] = row < G.rows && j >= j_lo && j < j_hi;
+        if (own[r]) first = r;
+      }
+      if (first == 4u) continue;
+#pragma unroll
+      for (uint32_t r = 0; r < 4u; r++) xb[r] = (quad * 4u + (own[r] ? r : first)) * G.row_stride + x0;
+    } else {
+#pragma unroll
+      for (uint32_t r = 0; r < 4u; r++) {
+        const uint32_t row = quad * 4u + r < G.rows ? quad * 4u + r : quad * 4u;   // (a row past the last computes the quad's first again, unused)
+        xb[r] = row * G.row_stride + x0;
+      }
     }
-    if (first == 4u) continue;
-#pragma unroll
-    for (uint32_t r = 0; r < 4u; r++) xb[r] = (quad * 4u + (own[r] ? r : first)) * G.row_stride + x0;
     Real acc[4] = {0, 0, 0, 0};
     const Real *tp = taps + q;
 #pragma unroll 4
@@ -253,9 +143,10 @@ __device__ __forceinline__ void ratecvt_any_body(FSK_RATECVT_PARAMS, uint32_t po
 #pragma unroll
     for (uint32_t r = 0; r < 4u; r++) {
       const uint32_t row = quad * 4u + r;
-      const size_t j = j0 + (kRows ? (size_t)row * Qs : 0u) + u;
+      if (!ANY && row >= G.rows) continue;
+      const size_t j = grid_output(row);
       const uint32_t s = kRows ? s0 : s0 + row;
-      if (!own[r] || s >= n_streams) continue;
+      if ((ANY ? !own[r] : j >= j_hi) || s >= n_streams) continue;
       if constexpr (!kPlay) {
         ((float *)dst_)[(size_t)s * dst_pitch + (j - j_lo)] = (float)acc[r];
       } else if constexpr (kRows) {
@@ -275,52 +166,37 @@ __device__ __forceinline__ void ratecvt_any_body(FSK_RATECVT_PARAMS, uint32_t po
   }
 }
 
-template <typename Real, int FMT, int LAYOUT>
-__global__ __launch_bounds__(kResampleThreads) void ratecvt_capture_any_kernel(FSK_RATECVT_PARAMS, uint32_t pos) {
-  ratecvt_any_body<Real, FMT, LAYOUT, FSKHIP_RATECVT_CAPTURE>(FSK_RATECVT_ARGS, pos);
-}
+#define FSK_RATECVT_KERNEL(NAME, DIR, ANY)                                                                                      \
+  template <typename Real, int FMT, int LAYOUT>                                                                                 \
+  __global__ __launch_bounds__(kResampleThreads) void NAME(FSK_RATECVT_PARAMS) { ratecvt_body<Real, FMT, LAYOUT, DIR, ANY>(FSK_RATECVT_ARGS); }
+FSK_RATECVT_KERNEL(ratecvt_capture_kernel, FSKHIP_RATECVT_CAPTURE, false)
+FSK_RATECVT_KERNEL(ratecvt_playback_kernel, FSKHIP_RATECVT_PLAYBACK, false)
+FSK_RATECVT_KERNEL(ratecvt_capture_any_kernel, FSKHIP_RATECVT_CAPTURE, true)
+FSK_RATECVT_KERNEL(ratecvt_playback_any_kernel, FSKHIP_RATECVT_PLAYBACK, true)
 
-template <typename Real, int FMT, int LAYOUT>
-__global__ __launch_bounds__(kResampleThreads) void ratecvt_playback_any_kernel(FSK_RATECVT_PARAMS, uint32_t pos) {
-  ratecvt_any_body<Real, FMT, LAYOUT, FSKHIP_RATECVT_PLAYBACK>(FSK_RATECVT_ARGS, pos);
-}
-
-// the any-length instantiations, once: [direction][precision][format][layout]
-using RatecvtAnyFn = void (*)(const void *, size_t, const uint32_t *, void *, size_t, const float *, float *, const void *, const uint32_t *, uint32_t, size_t, uint32_t,
-                              uint32_t, uint32_t, RatecvtShape, uint32_t);
-const KernelEntry<RatecvtAnyFn> kRatecvtAnyKernels[2][2][4][2] = {
-    {FSK_FORMAT_KERNELS(ratecvt_capture_any_kernel, float), FSK_FORMAT_KERNELS(ratecvt_capture_any_kernel, double)},
-    {FSK_FORMAT_KERNELS(ratecvt_playback_any_kernel, float), FSK_FORMAT_KERNELS(ratecvt_playback_any_kernel, double)}};
+// every instantiation, once: [any][direction][precision][format][layout], in the order of the headers' enums
+using RatecvtFn = void (*)(const void *, size_t, const uint32_t *, void *, size_t, const float *, float *, const void *, const uint32_t *, uint32_t, size_t, uint32_t,
+                           uint32_t, uint32_t, RatecvtShape, uint32_t);
+const KernelEntry<RatecvtFn> kRatecvtKernels[2][2][2][4][2] = {
+    {{FSK_FORMAT_KERNELS(ratecvt_capture_kernel, float), FSK_FORMAT_KERNELS(ratecvt_capture_kernel, double)},
+     {FSK_FORMAT_KERNELS(ratecvt_playback_kernel, float), FSK_FORMAT_KERNELS(ratecvt_playback_kernel, double)}},
+    {{FSK_FORMAT_KERNELS(ratecvt_capture_any_kernel, float), FSK_FORMAT_KERNELS(ratecvt_capture_any_kernel, double)},
+     {FSK_FORMAT_KERNELS(ratecvt_playback_any_kernel, float), FSK_FORMAT_KERNELS(ratecvt_playback_any_kernel, double)}}};
 
 }  // namespace
 
 hipError_t launch_ratecvt(int direction, int precision, const void *d_src, size_t src_pitch, const uint32_t *d_lens, void *d_dst, size_t dst_pitch, int format,
-                          int layout, uint32_t n_streams, size_t n_in, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps, const uint32_t *d_table,
-                          const float *d_hist_in, float *d_hist_out, hipStream_t st) {
-  const RatecvtPlan P = ratecvt_plan(layout == FSKHIP_LAYOUT_STREAM_MAJOR, direction == FSKHIP_RATECVT_PLAYBACK, up, down, n_taps, n_streams, n_in);
+                          int layout, uint32_t n_streams, uint32_t pos, size_t n_in, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps,
+                          const uint32_t *d_table, const float *d_hist_in, float *d_hist_out, hipStream_t st) {
+  const bool any = pos != 0 || n_in % down != 0;                         // whole periods from a boundary keep their own kernels
+  const RatecvtPlan P = ratecvt_plan(layout == FSKHIP_LAYOUT_STREAM_MAJOR, direction == FSKHIP_RATECVT_PLAYBACK, up, down, n_taps, n_streams, pos, n_in);
   if (P.blocks == 0) return hipErrorInvalidValue;
   const RatecvtShape G = {P.hist, P.G, P.rows, P.log2_ns, P.x_pitch, P.row_stride, P.span, P.seg_periods, P.split};
-  const KernelEntry<RatecvtFn> &k = kRatecvtKernels[direction][precision == FSKHIP_PRECISION_F64 ? 1 : 0][format][layout];
-  hipLaunchKernelGGL(k.fn, dim3((uint32_t)P.blocks), dim3(kResampleThreads), P.lds_bytes, st, d_src, src_pitch, d_lens, d_dst, dst_pitch, d_hist_in, d_hist_out, d_taps,
-                     d_table, n_streams, n_in, up, down, n_taps, G);
-  return hipGetLastError();
-}
-
-hipError_t launch_ratecvt_any(int direction, int precision, const void *d_src, size_t src_pitch, const uint32_t *d_lens, void *d_dst, size_t dst_pitch, int format,
-                              int layout, uint32_t n_streams, uint32_t pos, size_t n_in, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps,
-                              const uint32_t *d_table, const float *d_hist_in, float *d_hist_out, hipStream_t st) {
-  if (pos == 0 && n_in % down == 0)                                      // whole periods from a boundary keep their own kernels and launch
-    return launch_ratecvt(direction, precision, d_src, src_pitch, d_lens, d_dst, dst_pitch, format, layout, n_streams, n_in, up, down, n_taps, d_taps, d_table, d_hist_in,
-                          d_hist_out, st);
-  const RatecvtPlan P = ratecvt_plan_any(layout == FSKHIP_LAYOUT_STREAM_MAJOR, direction == FSKHIP_RATECVT_PLAYBACK, up, down, n_taps, n_streams, pos, n_in);
-  if (P.blocks == 0) return hipErrorInvalidValue;
-  const RatecvtShape G = {P.hist, P.G, P.rows, P.log2_ns, P.x_pitch, P.row_stride, P.span, P.seg_periods, P.split};
-  const KernelEntry<RatecvtAnyFn> &k = kRatecvtAnyKernels[direction][precision == FSKHIP_PRECISION_F64 ? 1 : 0][format][layout];
+  const KernelEntry<RatecvtFn> &k = kRatecvtKernels[any][direction][precision == FSKHIP_PRECISION_F64 ? 1 : 0][format][layout];
   hipLaunchKernelGGL(k.fn, dim3((uint32_t)P.blocks), dim3(kResampleThreads), P.lds_bytes, st, d_src, src_pitch, d_lens, d_dst, dst_pitch, d_hist_in, d_hist_out, d_taps,
                      d_table, n_streams, n_in, up, down, n_taps, G, pos);
   return hipGetLastError();
 }
-
 }  // namespace fsk
 
 using namespace fsk;
@@ -347,8 +223,8 @@ int process(fskhip_ratecvt *r, const char *who, int direction, bool host, bool a
   const int rc = rate_process(r, c, host, direction == FSKHIP_RATECVT_CAPTURE, src, src_pitch, lens, dst, dst_pitch, st,
                               [=](const void *d_src, size_t d_src_pitch, const uint32_t *d_lens, void *d_dst, size_t d_dst_pitch, hipStream_t s) {
     return rate_run(r, [=](const float *hist_in, float *hist_out) -> int {
-      const hipError_t err = launch_ratecvt_any(r->direction, r->precision, d_src, d_src_pitch, d_lens, d_dst, d_dst_pitch, format, layout, r->S, pos, n_in, r->L,
-                                                r->M, r->n_taps, r->taps(), r->d_table, hist_in, hist_out, s);
+      const hipError_t err = launch_ratecvt(r->direction, r->precision, d_src, d_src_pitch, d_lens, d_dst, d_dst_pitch, format, layout, r->S, pos, n_in, r->L,
+                                            r->M, r->n_taps, r->taps(), r->d_table, hist_in, hist_out, s);
       if (err == hipErrorInvalidValue) return rate_grid_fail(who, r->S, n_in);
       HIP_TRY(err);
       r->pos = ratecvt_next_position(r->M, pos, n_in);

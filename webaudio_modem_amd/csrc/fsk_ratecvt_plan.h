@@ -109,15 +109,9 @@ inline RatecvtPlan ratecvt_shape(bool stream_major, bool playback, uint32_t L, u
   return P;
 }
 
-// n_in: inputs per stream (> 0, a multiple of M), from a period boundary
-inline RatecvtPlan ratecvt_plan(bool stream_major, bool playback, uint32_t L, uint32_t M, uint32_t n_taps, uint32_t n_streams, size_t n_in) {
-  RatecvtPlan P = ratecvt_shape(stream_major, playback, L, M, n_taps);
-  resample_grid(P, P.seg_periods, stream_major, n_streams, n_in / M);
-  return P;
-}
-
-// n_in: inputs per stream (> 0, any), from position pos < M: the periods that hold inputs [pos, pos + n_in) of the grid
-inline RatecvtPlan ratecvt_plan_any(bool stream_major, bool playback, uint32_t L, uint32_t M, uint32_t n_taps, uint32_t n_streams, uint32_t pos, size_t n_in) {
+// n_in: inputs per stream (> 0, any), from position pos < M: the periods that hold inputs [pos, pos + n_in) of the grid, n_in / M
+// of them for whole periods from a boundary
+inline RatecvtPlan ratecvt_plan(bool stream_major, bool playback, uint32_t L, uint32_t M, uint32_t n_taps, uint32_t n_streams, uint32_t pos, size_t n_in) {
   RatecvtPlan P = ratecvt_shape(stream_major, playback, L, M, n_taps);
   resample_grid(P, P.seg_periods, stream_major, n_streams, ((size_t)pos + n_in + M - 1) / M);
   return P;
