@@ -674,7 +674,8 @@ int fskhip_fir_create(int device, const double *taps, uint32_t n_taps, uint32_t 
 int fskhip_fir_destroy(fskhip_fir *f);
 uint32_t fskhip_fir_streams(const fskhip_fir *f);   /* the n_streams it was created for (0 for NULL); ABI 7 */
 /* processBuffer(input) (filters.ts:142-148) for every stream: out[s][t] = f32(sum_i c[i] * x_s[t-i]), the delay
- * line carried across calls.  in/out are [n_streams][pitch] float32 and may not alias. */
+ * line carried across calls.  in/out are [n_streams][pitch] float32 and may not alias: the _device call refuses ranges
+ * [p, p + (n_streams - 1) * pitch + n_per_stream) that overlap with FSKHIP_E_INVALID before anything is launched. */
 int fskhip_fir_process_device(fskhip_fir *f, const float *d_in, size_t n_per_stream, size_t in_pitch, float *d_out,
                               size_t out_pitch, void *hip_stream);
 int fskhip_fir_process_host(fskhip_fir *f, const float *in, size_t n_per_stream, size_t in_pitch, float *out,

@@ -6,6 +6,7 @@ bit-identical on the fp64 path and within 1e-5 of full scale on the fp32 path.""
 import numpy as np
 import pytest
 
+import filter_ref
 from conftest import golden, golden_next
 
 pytestmark = pytest.mark.gpu
@@ -152,7 +153,8 @@ def test_fir_matches_reference_golden(run):
     assert np.array_equal(np.concatenate(parts), ref)       # the delay line carries across calls
     f32 = wm.FIRFilter(run["coeffs"], precision=wm.PRECISION_F32)
     y = f32.processBuffer(x)
-    assert np.max(np.abs(y - ref)) <= 1e-5 * max(1.0, float(np.max(np.abs(ref))))
+    want = filter_ref.FIRModel(run["coeffs"], 1, "f32").process_buffer(x[None, :])[0]     # fp32 FMAs in tap order: no tolerance
+    assert np.array_equal(y.view(np.uint32), want.view(np.uint32))
 
 
 def test_fir_factories_and_per_sample_surface():
@@ -492,7 +494,7 @@ def test_filter_host_calls_with_pitches_and_regrowth(kind):
     """fskhip_fir_process_host (fp64 and fp32 engines, 5 taps) and fskhip_iir_process_host / _f64_host (order 2), 65 streams,
     calls of 5, 64 and 7 samples on one handle: host rows wider than n on both sides give, bit for bit, what contiguous arrays
     give on a second handle (the same kernel: no tolerance), nothing outside the n columns is written, and the first run is
-    the oracle's -- bit for bit on the fp64 engines, within 1e-5 of full scale on the fp32 FIR (this module's bar)."""
+    the oracle's bit for bit on the fp64 engines, and tests/filter_ref.py's fp32 model bit for bit on the fp32 FIR."""
     import ctypes as C
     import webaudio_modem_amd as wm
     from webaudio_modem_amd import _lib
@@ -527,6 +529,10 @@ def test_filter_host_calls_with_pitches_and_regrowth(kind):
     assert np.array_equal(got[0].view(bits), got[1].view(bits))
     want = np.stack([oracle(s) for s in range(ROWS_S)])
     if kind == "fir-f32":
-        assert np.max(np.abs(got[0] - want)) <= 1e-5 * max(1.0, float(np.max(np.abs(want))))
+        cuts = np.concatenate([[0], np.cumsum(ROWS_N)])
+        model = filter_ref.FIRModel(taps, ROWS_S, "f32")
+        want32 = np.concatenate([model.process_buffer(x[:, p:q]) for p, q in zip(cuts, cuts[1:])], axis=1)
+        assert np.array_equal(got[0].view(bits), want32.view(bits))
+        assert np.max(np.abs(want32 - want)) <= 1e-5 * max(1.0, float(np.max(np.abs(want))))     # (and the model is near the fp64 oracle)
     else:
         assert np.array_equal(got[0].view(bits), want.astype(dtype).view(bits))

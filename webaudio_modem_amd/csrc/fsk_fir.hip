@@ -211,6 +211,11 @@ int fskhip_fir_process_device(fskhip_fir *f, const float *d_in, size_t n, size_t
   if (n == 0) return FSKHIP_OK;
   if (!d_in || !d_out) return fail(FSKHIP_E_INVALID, "fskhip_fir_process_device: null buffer");
   if (in_pitch < n || out_pitch < n) return fail(FSKHIP_E_INVALID, "pitch < n_per_stream");
+  {  // the kernels read `in` behind every store to `out` (__restrict__, and the delay line is taken from `in` afterwards)
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(d_in), o0 = reinterpret_cast<uintptr_t>(d_out);
+    const uintptr_t i1 = i0 + sizeof(float) * ((size_t)(f->S - 1) * in_pitch + n), o1 = o0 + sizeof(float) * ((size_t)(f->S - 1) * out_pitch + n);
+    if (i0 < o1 && o0 < i1) return fail(FSKHIP_E_INVALID, "fskhip_fir_process_device: the input and output buffers overlap");
+  }
   HIP_TRY(hipSetDevice(f->device));
   hipStream_t st = (hipStream_t)hip_stream;
   const uint32_t tiles = (uint32_t)((n + kFirTile - 1) / kFirTile);
