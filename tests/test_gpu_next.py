@@ -236,6 +236,10 @@ def test_chunked_modulator_mirror_matches_reference():
 
 
 # ---------------------------------------------------------------- FSKProcessor quantum loop -------------
+# These two tests run fp64 engines in quanta of exactly 128 samples through the host entry point (3 or 70 streams, Bell 202 in 8N1), with
+# and without the captured graph.  The fp32 generator, the other framings and samples-per-bit values, quanta that end inside a tile or a
+# four-sample block, store_tile's single stores, stray writes, the workgroup edges, per-stream tones, the long carried phase and the
+# rings per quantum are tests/test_gpu_processor_float.py's.
 @pytest.mark.parametrize("use_graph", [False, True], ids=["launches", "graph"])
 @pytest.mark.parametrize("name", [r["name"] for r in golden_next().manifest["processor"]])
 def test_processor_loop_matches_reference(name, use_graph):
