@@ -860,7 +860,8 @@ int fskhip_processor_process_rate_host(fskhip_processor *p, fskhip_resampler *up
  * n_in = 0 is FSKHIP_OK and does nothing once the checks that need no samples have passed: handle, format, layout, direction.
  * (The NULL handle comes first, so without a device -- where create ends in FSKHIP_E_NO_DEVICE -- only create's refusals and the NULL
  * handle's can be met; tests/test_ratecvt_refusals_cpu.py holds those, tests/test_gpu_ratecvt.py the rest, in this order.)
- * These handles have no remap, snapshot or restore yet: fskhip_ratecvt_state_get / _set are the by-hand carry.
+ * fskhip_ratecvt_state_get / _set are the by-hand carry of a handle; fskhip_ratecvt_remap / _snapshot / _restore ("A rate converter
+ * through remap, snapshot and restore", below) do the same on the device, and a converter has a snapshot image of its own.
  * ------------------------------------------------------------------------------------------------- */
 typedef struct fskhip_ratecvt fskhip_ratecvt;
 enum { FSKHIP_RATECVT_CAPTURE = 0, FSKHIP_RATECVT_PLAYBACK = 1 };
@@ -977,6 +978,69 @@ int fskhip_processor_process_ratecvt_any_device(fskhip_processor *p, fskhip_rate
 int fskhip_processor_process_ratecvt_any_host(fskhip_processor *p, fskhip_ratecvt *capture, fskhip_ratecvt *playback, const void *in,
                                               int in_format, int in_layout, size_t n_in, size_t in_pitch, void *out, int out_format,
                                               int out_layout, size_t n_out, size_t out_pitch, uint32_t flags);
+
+/*
+ * A rate converter through remap, snapshot and restore (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): the handle follows its
+ * streams with the SAME map the engine, the processor, the resident XModem handles and the resamplers were carried with, so a
+ * receiver bank at 44.1 kHz attaches and detaches receivers, checkpoints and moves between GPUs without a click.  The five calls
+ * mirror fskhip_resampler_remap ... argument for argument, and the contract is theirs: remap and restore CREATE their handle, from
+ * the source's or the image's own design (direction, up, down, taps as given to create, precision), so there is no destination that
+ * could disagree; the device's tap order and table are made by create, never read from an image.  A converter's per-stream state is
+ * its history row, fskhip_ratecvt_history() floats for fp32 and fp64 handles alike; the rows move on the device, by the resampler's
+ * gather kernel.  Beside the rows a handle holds one word for all its streams, the position of the any-length calls, and it is
+ * CARRIED: the new handle's position is the source's or the image's.  Synchronous host calls.
+ *
+ * fskhip_ratecvt_remap     *out: a new handle on src's device with src's design and position, for n_map streams.  Stream i
+ *                          continues stream map[i] of src: its history row verbatim, every bit (NaN payloads and the sign of zero
+ *                          included).  Where map[i] = -1 stream i starts with a zero row: at a position that is not 0 that is a
+ *                          stream that has received zeros since the boundary, which is what fskhip_ratecvt_reset(r, stream) means
+ *                          already.  A source named several times gives independent clones; sources not named are dropped.  src
+ *                          is read only and stays usable.  Destroy *out with fskhip_ratecvt_destroy.
+ * A rate converter snapshot is a host-side image: plain little-endian bytes, no pointers, every byte defined.  It is canonical: two
+ * handles in the same observable state give the same bytes, whichever of their two history buffers is current.
+ *   header, 64 bytes:  u32 magic "FSKC" (0x434B5346) | u32 format (1) | u32 header_bytes (64) | u32 record_bytes (4 x history) |
+ *                      u32 n_records | u32 direction | u32 up | u32 down | u32 n_taps | u32 precision | u32 history | u32 position |
+ *                      2 x u32 reserved (0) | u64 checksum
+ *     history: ceil((n_taps - 1) / up).  checksum: the processor snapshot's function over the image's u64 words, with the checksum
+ *     field taken as 0.
+ *   the taps, n_taps doubles as given to create
+ *   the rows, n_records x history floats packed tightly, one per selected stream, in selection order, oldest sample first
+ *   zero padding to a multiple of 16 bytes
+ * fskhip_ratecvt_snapshot_bytes  *bytes = the size of an image of n_sel records of this handle.
+ * fskhip_ratecvt_snapshot        write streams[0 .. n_sel) (NULL: all streams, in order, whatever n_sel; a stream may be named more
+ *                          than once) into image.  Synchronises with the device's outstanding work; the handle is read only and
+ *                          stays usable.  *written (may be NULL) receives the size; cap too small (or image NULL):
+ *                          FSKHIP_E_OVERFLOW with *written = the size needed and nothing written, so cap 0 is a size query.
+ * fskhip_ratecvt_restore         remap with the image standing in for src, on any device: map[i] names a RECORD, or is -1; a NULL
+ *                          map takes every record, in order (n_map is then ignored).  The design and the position are the image's.
+ * fskhip_ratecvt_snapshot_info_get   what an image holds -- on the host, no device needed -- after validating ALL of it.
+ *
+ * Refusals, FSKHIP_E_INVALID before any device call, in this order; a refused call creates nothing, leaves *out alone and the
+ * source as it was.
+ *   remap           src or out NULL; map NULL with n_map > 0; n_map 0; the first map[i] below -1 or not below src's stream count.
+ *   snapshot_bytes  r or bytes NULL.
+ *   snapshot        r NULL; the first streams[i] below 0 or not below the handle's stream count; then the room (FSKHIP_E_OVERFLOW).
+ *   an image        (info_get, restore) NULL; fewer bytes than a header; magic (a resampler's image is named as one); format;
+ *                   header_bytes; a reserved word that is not 0; a direction that is neither; up, then down, outside 1..256; up and
+ *                   down not coprime; n_taps outside 1..4096; a precision that is neither (create's limits); a history that is not
+ *                   ceil((n_taps - 1) / up); a position not below down; record_bytes; the size against the layout above; the
+ *                   checksum; a padding byte that is not zero.  info_get then: info NULL.
+ *   restore         out NULL; the image; map non-NULL with n_map 0, or a NULL map over an image without records; the first map[i]
+ *                   below -1 or not below the image's record count.  Then what create refuses for the device.
+ */
+typedef struct fskhip_ratecvt_snapshot_info {
+  uint32_t n_streams;   /* records in the image */
+  int direction;        /* FSKHIP_RATECVT_* */
+  uint32_t up, down, n_taps;
+  int precision;        /* FSKHIP_PRECISION_* */
+  uint32_t history;     /* floats per record */
+  uint32_t position;    /* inputs taken since the last period boundary, below down */
+} fskhip_ratecvt_snapshot_info;
+int fskhip_ratecvt_remap(const fskhip_ratecvt *src, const int64_t *map, uint32_t n_map, fskhip_ratecvt **out);
+int fskhip_ratecvt_snapshot_bytes(const fskhip_ratecvt *r, uint32_t n_sel, size_t *bytes);
+int fskhip_ratecvt_snapshot(const fskhip_ratecvt *r, const int64_t *streams, uint32_t n_sel, void *image, size_t cap, size_t *written);
+int fskhip_ratecvt_restore(int device, const void *image, size_t bytes, const int64_t *map, uint32_t n_map, fskhip_ratecvt **out);
+int fskhip_ratecvt_snapshot_info_get(const void *image, size_t bytes, fskhip_ratecvt_snapshot_info *info);
 
 /* ---------------------------------------------------------------------------------------------------
  * IIR half of src/dsp/filters.ts: IIRFilter (8-106) batched over streams, + FilterFactory.createIIR* (325-344; the

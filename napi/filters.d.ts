@@ -80,10 +80,21 @@ declare class RateConverter {
   /** the history rows, [nStreams][history], oldest first */
   state(): Float32Array;
   setState(state: Float32Array): void;
+  /** a new object of this design, at this position, whose stream i continues stream map[i] of this one (-1: a zero history); the rows move on the device */
+  remap(map: ArrayLike<number>): this;
+  /** the image of `streams` (null: all, in order): the design, the position and the history rows */
+  snapshot(streams?: ArrayLike<number> | null): Buffer;
   close(): void;
 }
+export interface RatecvtSnapshotInfo { nStreams: number; direction: 0 | 1; up: number; down: number; nTaps: number; precision: 0 | 1; history: number; position: number; taps: Float64Array }
+/** where a restored converter lives, and its rates: an image knows up and down only (default: inRate = down, outRate = up) */
+export interface RatecvtRestoreOptions { device?: number; inRate?: number; outRate?: number }
+/** what a rate converter snapshot holds, validated on the host */
+export declare function ratecvtSnapshotInfo(image: Uint8Array): RatecvtSnapshotInfo;
 export declare class CaptureConverter extends RateConverter {
   constructor(inRate: number, outRate: number, nStreams: number, options?: RateConverterOptions);
+  /** a new object from a snapshot() alone, at its position: stream i continues record map[i] (-1: a zero history; null: every record) */
+  static fromSnapshot(image: Uint8Array, map?: ArrayLike<number> | null, device?: number | RatecvtRestoreOptions): CaptureConverter;
   /** samples: [nStreams][pitch] or frames [nIn][pitch], nIn a multiple of down; returns [nStreams][nIn / down * up] */
   process(samples: Float32Array | Int16Array | Uint8Array, format: SampleFormat, layout?: SampleLayout, nIn?: number, pitch?: number): Float32Array;
   /** process() for any nIn, from the handle's position; returns [nStreams][outCountAny(nIn)] and moves the position on */
@@ -91,6 +102,7 @@ export declare class CaptureConverter extends RateConverter {
 }
 export declare class PlaybackConverter extends RateConverter {
   constructor(inRate: number, outRate: number, nStreams: number, options?: RateConverterOptions);
+  static fromSnapshot(image: Uint8Array, map?: ArrayLike<number> | null, device?: number | RatecvtRestoreOptions): PlaybackConverter;
   /** input: [nStreams][n], n a multiple of down; returns [nStreams][n / down * up] or frames [n / down * up][nStreams] */
   process(input: Float32Array, format: SampleFormat, layout?: SampleLayout, lens?: Uint32Array | null): Float32Array | Int16Array | Uint8Array;
   /** process() for any n, from the handle's position; returns [nStreams][outCountAny(n)] or frames and moves the position on */

@@ -184,8 +184,46 @@ class RateConverter extends RateHandle {
   }
   outCountAny(nIn) { return addon.ratecvtOutCountAny(this.handle, nIn); }
   inCountAny(nOut) { return addon.ratecvtInCountAny(this.handle, nOut); }
+  // an object of this class over a handle the library created (remap, restore)
+  static adopt(handle, design) {
+    const o = Object.create(this.prototype);
+    o.inRate = design.inRate; o.outRate = design.outRate; o.up = design.up; o.down = design.down; o.taps = [...design.taps];
+    o.handle = handle;
+    o.nStreams = addon.ratecvtStreams(handle);
+    o.history = addon.ratecvtHistory(handle);
+    return o;
+  }
+  // fskhip_ratecvt_remap: a new object of this design, at this position, whose stream i continues stream map[i] of this one (its
+  // history row, bit for bit; -1: a zero history) -- the map the engine and the processor were remapped with.  This object stays usable.
+  remap(map) { return this.constructor.adopt(addon.ratecvtRemap(this.handle, Array.from(map)), this); }
+  // fskhip_ratecvt_snapshot: the image of `streams` (null: all, in order) as a Buffer -- the design, the position and the history rows
+  snapshot(streams = null) { return addon.ratecvtSnapshot(this.handle, streams === null || streams === undefined ? null : Array.from(streams)); }
+  // fskhip_ratecvt_restore: a new object from a snapshot() alone, at the image's position; stream i continues record map[i] (-1: a
+  // zero history; null: every record, in order).  `device`: the device's index, or { device, inRate, outRate } -- an image knows
+  // up and down, not the rates: without them inRate / outRate are down / up, and rates of another ratio are refused.
+  // CaptureConverter and PlaybackConverter refuse an image of the other direction; the class they share picks from the image.
+  static fromSnapshot(buf, map = null, device = 0) {
+    const options = typeof device === 'object' && device !== null ? device : { device };
+    const info = addon.ratecvtSnapshotInfo(buf);
+    if (this.DIRECTION !== undefined && info.direction !== this.DIRECTION) {
+      throw new RangeError('the snapshot is of a rate converter for ' + ['capture', 'playback'][info.direction] + ', not ' + ['capture', 'playback'][this.DIRECTION]);
+    }
+    let inRate = info.down, outRate = info.up;
+    if (options.inRate !== undefined || options.outRate !== undefined) {
+      const r = RateConverter.ratio(options.inRate, options.outRate);
+      if (r.up !== info.up || r.down !== info.down) {
+        throw new RangeError(options.inRate + ' -> ' + options.outRate + ' is ' + r.up + ' / ' + r.down + ', the snapshot converts by ' + info.up + ' / ' + info.down);
+      }
+      inRate = options.inRate; outRate = options.outRate;
+    }
+    const handle = addon.ratecvtRestore(buf, map === null || map === undefined ? null : Array.from(map), options.device || 0);
+    const kind = this.DIRECTION !== undefined ? this : [CaptureConverter, PlaybackConverter][info.direction];
+    return kind.adopt(handle, { inRate, outRate, up: info.up, down: info.down, taps: Array.from(info.taps) });
+  }
 }
+function ratecvtSnapshotInfo(buf) { return addon.ratecvtSnapshotInfo(buf); }
 class CaptureConverter extends RateConverter {
+  static get DIRECTION() { return 0; }
   constructor(inRate, outRate, nStreams, options = {}) { super(0, inRate, outRate, nStreams, options); }
   // samples: the format's typed array, [nStreams][pitch] (layout 'stream') or frames [nIn][pitch >= nStreams] ('sample'); nIn (a
   // multiple of down) and pitch default to a packed array's -> Float32Array [nStreams][nIn / down * up]
@@ -194,6 +232,7 @@ class CaptureConverter extends RateConverter {
   processAny(samples, format, layout = 'stream', nIn, pitch) { return rateWiden(this, addon.ratecvtCaptureAny, samples, format, layout, nIn, pitch, (n) => this.outCountAny(n)); }
 }
 class PlaybackConverter extends RateConverter {
+  static get DIRECTION() { return 1; }
   constructor(inRate, outRate, nStreams, options = {}) { super(1, inRate, outRate, nStreams, options); }
   // input: Float32Array [nStreams][n], n a multiple of down; lens (Uint32Array or null): stream s reads as 0.0 from lens[s] on
   // -> the format's typed array, [nStreams][n / down * up] or frames [n / down * up][nStreams]
@@ -247,4 +286,4 @@ class FilterFactory {                             // filters.ts:325-368
   static createFIRHighpass(cutoffFreq, sampleRate, numTaps = 51) { return new FIRFilter(FilterDesign.sincHighpass(cutoffFreq, sampleRate, numTaps)); }
   static createFIRBandpass(centerFreq, bandwidth, sampleRate, numTaps = 51) { return new FIRFilter(FilterDesign.sincBandpass(centerFreq, bandwidth, sampleRate, numTaps)); }
 }
-module.exports = { FilterDesign, IIRFilter, IIRFilterBatch, FIRFilter, FIRFilterBatch, Upsampler, Downsampler, CaptureConverter, PlaybackConverter, resamplerSnapshotInfo, FilterFactory, PRECISION_F32, PRECISION_F64 };
+module.exports = { FilterDesign, IIRFilter, IIRFilterBatch, FIRFilter, FIRFilterBatch, Upsampler, Downsampler, CaptureConverter, PlaybackConverter, resamplerSnapshotInfo, ratecvtSnapshotInfo, FilterFactory, PRECISION_F32, PRECISION_F64 };

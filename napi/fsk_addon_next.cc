@@ -44,12 +44,15 @@
 //   resamplerRemap(handle, map: number[]) -> handle;  resamplerSnapshot(handle, streams: number[]|null) -> Buffer
 //   resamplerRestore(snapshot: Uint8Array, map: number[]|null, device) -> handle
 //   resamplerSnapshotInfo(snapshot) -> {nStreams, direction, factor, nTaps, precision, history, taps: Float64Array}
-//   ratecvtCreate(direction, up, down, taps: Float64Array, nStreams, device, precision) -> handle;  ratecvtDestroy(handle);  ratecvtHistory(handle)
+//   ratecvtCreate(direction, up, down, taps: Float64Array, nStreams, device, precision) -> handle;  ratecvtDestroy(handle);  ratecvtHistory(handle);  ratecvtStreams(handle)
 //   ratecvtCapture(handle, samples, format, layout, nIn, pitch, nOut) -> Float32Array [S][nOut]
 //   ratecvtPlayback(handle, input: Float32Array [S][nIn], nIn, lens: Uint32Array|null, format, layout, nOut) -> the format's typed array
 //   ratecvtReset(handle, stream);  ratecvtState(handle) -> Float32Array [S][history];  ratecvtSetState(handle, Float32Array)
 //   ratecvtCaptureAny / ratecvtPlaybackAny: the two process calls for any nIn, from the handle's position (nOut: ratecvtOutCountAny's)
 //   ratecvtPosition(handle) -> number;  ratecvtSetPosition(handle, pos);  ratecvtOutCountAny(handle, nIn);  ratecvtInCountAny(handle, nOut)
+//   ratecvtRemap(handle, map: number[]) -> handle;  ratecvtSnapshot(handle, streams: number[]|null) -> Buffer
+//   ratecvtRestore(snapshot: Uint8Array, map: number[]|null, device) -> handle
+//   ratecvtSnapshotInfo(snapshot) -> {nStreams, direction, up, down, nTaps, precision, history, position, taps: Float64Array}
 //   processorProcessSamplesAtAny: processorProcessSamplesAt for rate converters and counts of any length
 //   iirCreate(b, a: Float64Array, nStreams, device, precision) -> handle; iirProcess(handle, Float32Array | Float64Array, n, pitch, nStreams);
 //   iirCoefficients(handle), iirReset(handle, stream), iirDestroy(handle); butterworth(kind, f, bandwidth, sampleRate) -> [b0 b1 b2 a0 a1 a2]
@@ -1136,6 +1139,7 @@ napi_value RatecvtDestroy(napi_env env, napi_callback_info info) {
 const RateApi<fskhip_ratecvt> kRatecvt = {ratecvt_of, fskhip_ratecvt_streams, fskhip_ratecvt_history, fskhip_ratecvt_reset, fskhip_ratecvt_state_get,
                                           fskhip_ratecvt_state_set, fskhip_ratecvt_capture_host, fskhip_ratecvt_playback_host, false};
 napi_value RatecvtHistory(napi_env env, napi_callback_info info) { return rate_count(env, info, kRatecvt, kRatecvt.history); }
+napi_value RatecvtStreams(napi_env env, napi_callback_info info) { return rate_count(env, info, kRatecvt, kRatecvt.streams); }
 napi_value RatecvtCapture(napi_env env, napi_callback_info info) { return rate_widen(env, info, kRatecvt); }
 napi_value RatecvtPlayback(napi_env env, napi_callback_info info) { return rate_narrow(env, info, kRatecvt); }
 napi_value RatecvtReset(napi_env env, napi_callback_info info) { return rate_reset(env, info, kRatecvt); }
@@ -1233,6 +1237,71 @@ napi_value ResamplerSnapshotInfo(napi_env env, napi_callback_info info) {   // (
   void *taps;   // (behind the 48-byte header of a validated image)
   napi_value taps_v = make_typed(env, napi_float64_array, si.n_taps, 8, &taps);
   memcpy(taps, (const unsigned char *)data + 48, sizeof(double) * (size_t)si.n_taps);
+  napi_set_named_property(env, o, "taps", taps_v);
+  return o;
+}
+// ---- a rate converter through remap / snapshot / restore (fskhip_ratecvt_remap ...): the resampler's four, over its own C calls
+napi_value RatecvtRemap(napi_env env, napi_callback_info info) {   // (handle, map: number[]) -> handle
+  ARGS(2);
+  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
+  if (!r) return nullptr;
+  std::vector<int64_t> map;
+  if (!index_array(env, argv[1], "ratecvtRemap: map must be an Array of integer stream indices (-1: a new stream)", &map)) return nullptr;
+  fskhip_ratecvt *out = nullptr;
+  int rc = fskhip_ratecvt_remap(r, index_data(map), (uint32_t)map.size(), &out);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return filter_box_new(env, out, BOX_RATECVT);
+}
+napi_value RatecvtSnapshot(napi_env env, napi_callback_info info) {   // (handle, streams: number[]|null) -> Buffer
+  ARGS(2);
+  fskhip_ratecvt *r = ratecvt_of(env, argv[0]);
+  if (!r) return nullptr;
+  std::vector<int64_t> sel;
+  const bool all = nullish(env, argv[1]);
+  if (!all && !index_array(env, argv[1], "ratecvtSnapshot: streams must be an Array of integer stream indices", &sel)) return nullptr;
+  const uint32_t n = all ? fskhip_ratecvt_streams(r) : (uint32_t)sel.size();
+  size_t need = 0;
+  int rc = fskhip_ratecvt_snapshot_bytes(r, n, &need);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  void *data = nullptr;
+  napi_value buf;
+  NAPI_OK(napi_create_buffer(env, need, &data, &buf));
+  rc = fskhip_ratecvt_snapshot(r, index_data(sel, all), n, data, need, nullptr);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return buf;
+}
+napi_value RatecvtRestore(napi_env env, napi_callback_info info) {   // (snapshot: Uint8Array, map: number[]|null, device) -> handle
+  ARGS(3);
+  void *data; size_t size;
+  if (!typed(env, argv[0], napi_uint8_array, &data, &size)) return nullptr;
+  std::vector<int64_t> map;
+  const bool all = nullish(env, argv[1]);
+  if (!all && !index_array(env, argv[1], "ratecvtRestore: map must be an Array of integer record indices (-1: a new stream)", &map)) return nullptr;
+  fskhip_ratecvt *out = nullptr;
+  int rc = fskhip_ratecvt_restore(i32(env, argv[2]), data, size, index_data(map, all), (uint32_t)map.size(), &out);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return filter_box_new(env, out, BOX_RATECVT);
+}
+napi_value RatecvtSnapshotInfo(napi_env env, napi_callback_info info) {   // (snapshot) -> {nStreams, direction, up, down, nTaps, precision, history, position, taps}
+  ARGS(1);
+  void *data; size_t size;
+  if (!typed(env, argv[0], napi_uint8_array, &data, &size)) return nullptr;
+  fskhip_ratecvt_snapshot_info si;
+  int rc = fskhip_ratecvt_snapshot_info_get(data, size, &si);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  set_u32(env, o, "nStreams", si.n_streams);
+  set_u32(env, o, "direction", (uint32_t)si.direction);
+  set_u32(env, o, "up", si.up);
+  set_u32(env, o, "down", si.down);
+  set_u32(env, o, "nTaps", si.n_taps);
+  set_u32(env, o, "precision", (uint32_t)si.precision);
+  set_u32(env, o, "history", si.history);
+  set_u32(env, o, "position", si.position);
+  void *taps;   // (behind the 64-byte header of a validated image)
+  napi_value taps_v = make_typed(env, napi_float64_array, si.n_taps, 8, &taps);
+  memcpy(taps, (const unsigned char *)data + 64, sizeof(double) * (size_t)si.n_taps);
   napi_set_named_property(env, o, "taps", taps_v);
   return o;
 }
@@ -1394,6 +1463,7 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"ratecvtCreate", nullptr, RatecvtCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ratecvtDestroy", nullptr, RatecvtDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ratecvtHistory", nullptr, RatecvtHistory, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtStreams", nullptr, RatecvtStreams, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ratecvtCapture", nullptr, RatecvtCapture, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ratecvtPlayback", nullptr, RatecvtPlayback, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ratecvtReset", nullptr, RatecvtReset, nullptr, nullptr, nullptr, napi_default, nullptr},
@@ -1405,6 +1475,10 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"ratecvtSetPosition", nullptr, RatecvtSetPosition, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ratecvtOutCountAny", nullptr, RatecvtOutCountAny, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ratecvtInCountAny", nullptr, RatecvtInCountAny, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtRemap", nullptr, RatecvtRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtSnapshot", nullptr, RatecvtSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtRestore", nullptr, RatecvtRestore, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ratecvtSnapshotInfo", nullptr, RatecvtSnapshotInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorProcessSamplesAtAny", nullptr, ProcessorProcessSamplesAtAny, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirCreate", nullptr, IirCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"iirDestroy", nullptr, IirDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -78,6 +78,12 @@ class ResamplerSnapshotInfo(C.Structure):
                 ("history", C.c_uint32)]
 
 
+class RatecvtSnapshotInfo(C.Structure):
+    """fskhip_ratecvt_snapshot_info (include/fskhip_next.h): what a rate converter snapshot holds"""
+    _fields_ = [("n_streams", C.c_uint32), ("direction", C.c_int), ("up", C.c_uint32), ("down", C.c_uint32), ("n_taps", C.c_uint32), ("precision", C.c_int),
+                ("history", C.c_uint32), ("position", C.c_uint32)]
+
+
 class XModemResult(C.Structure):
     """fskhip_xmodem_result (include/fskhip_next.h)."""
     _fields_ = [
@@ -284,6 +290,11 @@ _SYMBOLS = [
     ("fskhip_ratecvt_in_count_any", C.c_size_t, [_P, C.c_size_t]),
     ("fskhip_processor_process_ratecvt_any_device", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, _P]),
     ("fskhip_processor_process_ratecvt_any_host", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32]),
+    ("fskhip_ratecvt_remap", C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P)]),
+    ("fskhip_ratecvt_snapshot_bytes", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("fskhip_ratecvt_snapshot", C.c_int, [_P, _P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fskhip_ratecvt_restore", C.c_int, [C.c_int, _P, C.c_size_t, _P, C.c_uint32, C.POINTER(_P)]),
+    ("fskhip_ratecvt_snapshot_info_get", C.c_int, [_P, C.c_size_t, C.POINTER(RatecvtSnapshotInfo)]),
     ("fskhip_iir_create", C.c_int, [C.c_int, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_P)]),
     ("fskhip_iir_destroy", C.c_int, [_P]),
     ("fskhip_iir_get_coefficients", C.c_int, [_P, _P, C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint32)]),

@@ -2,7 +2,7 @@
 // string (fail; open_image for a flaw that a host-only image validator names), device selection, device allocation (dev_alloc,
 // ensure for scratch that grows, Scratch for what lives as long as one call), the HIP_TRY macros and, behind them, the per-stream
 // word arrays of the resident XModem handles (fill_words, get_words, put_words).  What only some units share lives beside them:
-// fsk_filter_host.h (the two filters' handles and _host calls), fsk_stage.h (the four snapshot units' selection and room checks
+// fsk_filter_host.h (the two filters' handles and _host calls), fsk_stage.h (the snapshot units' selection and room checks
 // and slab pipelines; the image formats and their one frame are host-only: fsk_image.h), fsk_proc.h (struct fskhip_processor).
 #pragma once
 #include <hip/hip_runtime.h>

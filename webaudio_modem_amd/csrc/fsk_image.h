@@ -1,5 +1,5 @@
-// fsk_image.h -- the frame every snapshot image of this library has, once for the four formats (fsk_snapshot_image.h,
-// fsk_processor_image.h, fsk_xmodem_image.h, fsk_resample_image.h): a header `H` that names magic, format, header_bytes and checksum
+// fsk_image.h -- the frame every snapshot image of this library has, once for the five formats (fsk_snapshot_image.h,
+// fsk_processor_image.h, fsk_xmodem_image.h, fsk_resample_image.h, fsk_ratecvt_image.h): a header `H` that names magic, format, header_bytes and checksum
 // -- wherever the format puts them --, a body behind it, a checksum over both; a writer's header and seal, a reader's checks and
 // their texts.  Host-only: no HIP and no error string of the library's, so that a format's validator compiles into a stand-alone
 // check program (tests/cpp): a flaw is named in the caller's `msg` (fsk_host.h: open_image).  Not part of the ABI.

@@ -276,6 +276,7 @@ int fskhip_ratecvt_create(int device, int direction, uint32_t up, uint32_t down,
   if (!r) return fail(FSKHIP_E_NOMEM, "out of host memory");
   r->device = device; r->precision = precision; r->S = n_streams;
   r->direction = direction; r->L = up; r->M = down; r->n_taps = n_taps; r->H = resample_history(0, up, n_taps);
+  r->h_taps.assign(taps, taps + n_taps);
   // column q of the [K][L] table: the taps of phase (q M) mod L, c[p], c[p + L], ... downwards (zeros behind a short phase, never read)
   const uint32_t K = resample_phase_len(up, n_taps);
   std::vector<double> t64((size_t)K * up, 0.0);

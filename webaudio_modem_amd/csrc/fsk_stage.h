@@ -1,7 +1,7 @@
-// fsk_stage.h -- what the four snapshot units (fsk_snapshot_api.hip, fsk_processor_remap_api.hip, fsk_xmodem_remap_api.hip,
-// fsk_resample_remap_api.hip) share that needs a device, each once: the writers' selection and room checks, and the two slab
+// fsk_stage.h -- what the snapshot units (fsk_snapshot_api.hip, fsk_processor_remap_api.hip, fsk_xmodem_remap_api.hip, and
+// fsk_rate_remap_host.h for fsk_resample_remap_api.hip and fsk_ratecvt_remap_api.hip) share that needs a device, each once: the writers' selection and room checks, and the two slab
 // pipelines that carry records across PCIe -- stage_records_out for the writers, stage_records_in for the restores; no event chain is
-// spelled anywhere else.  (The frame of an image is host-only: fsk_image.h, under the four fsk_*_image.h.)  Not part of the ABI.
+// spelled anywhere else.  (The frame of an image is host-only: fsk_image.h, under the fsk_*_image.h.)  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

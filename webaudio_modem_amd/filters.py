@@ -385,6 +385,83 @@ class _RateConverter(_RateHandle):
         where up <= down (fskhip_ratecvt_in_count_any)"""
         return int(self._L.fskhip_ratecvt_in_count_any(self._h, int(n_out)))
 
+    @classmethod
+    def _adopt(cls, h, taps, up, down, precision, device, in_rate, out_rate):
+        """an object of this class over a handle the library has created (remap, restore)"""
+        import numpy as np
+        nxt = cls.__new__(cls)
+        nxt._np, nxt._L, nxt._h = np, _lib.lib(), h
+        nxt.up, nxt.down, nxt.in_rate, nxt.out_rate, nxt.device, nxt.precision = int(up), int(down), in_rate, out_rate, device, int(precision)
+        nxt.taps = [float(t) for t in taps]
+        nxt.n_streams = int(nxt._L.fskhip_ratecvt_streams(h))
+        nxt.history = int(nxt._L.fskhip_ratecvt_history(h))
+        return nxt
+
+    def remapped(self, stream_map):
+        """fskhip_ratecvt_remap: a new object of this design, at this position, whose stream i continues stream stream_map[i] of
+        this one -- its history row, bit for bit -- or starts with a zero history where stream_map[i] is -1 (a stream that has
+        received zeros since the last period boundary): the map the engine and the processor were remapped with.  The rows move on
+        the device.  This object stays usable."""
+        m = self._np.ascontiguousarray(stream_map, dtype=self._np.int64).reshape(-1)
+        h = C.c_void_p()
+        _lib.check(self._L.fskhip_ratecvt_remap(self._h, m.ctypes.data if len(m) else None, len(m), C.byref(h)))
+        return self._adopt(h, self.taps, self.up, self.down, self.precision, self.device, self.in_rate, self.out_rate)
+
+    def snapshot(self, streams=None):
+        """fskhip_ratecvt_snapshot: the image of streams `streams` (None: all, in order) as `bytes` -- the design (direction, up,
+        down, precision, taps), the position and the history rows.  This object is read only and stays usable."""
+        np = self._np
+        sel = None if streams is None else np.ascontiguousarray(streams, dtype=np.int64).reshape(-1)
+        n = self.n_streams if sel is None else len(sel)
+        if sel is not None and not len(sel):
+            sel = np.zeros(1, np.int64)   # (an empty selection, not "all": a non-null pointer with n = 0)
+        sel_p = None if sel is None else sel.ctypes.data
+        size = C.c_size_t(0)
+        _lib.check(self._L.fskhip_ratecvt_snapshot_bytes(self._h, n, C.byref(size)))
+        buf = np.zeros(max(size.value, 1), np.uint8)
+        w = C.c_size_t(0)
+        _lib.check(self._L.fskhip_ratecvt_snapshot(self._h, sel_p, n, buf.ctypes.data, size.value, C.byref(w)))
+        return buf[:w.value].tobytes()
+
+    @classmethod
+    def from_snapshot(cls, snap, stream_map=None, device=0, in_rate=None, out_rate=None):
+        """fskhip_ratecvt_restore: a new object on `device` from a snapshot() alone, at the image's position: stream i continues
+        record stream_map[i] (-1: a zero history; None: every record, in order).  CaptureConverter and PlaybackConverter refuse an
+        image of the other direction; _RateConverter picks the class from the image.  An image knows up and down, not the rates:
+        without them in_rate / out_rate are down / up; rates that do not reduce to the image's ratio are a ValueError."""
+        import numpy as np
+        from .engine import _blob
+        info = ratecvt_snapshot_info(snap)
+        names = ("capture", "playback")
+        if cls._DIRECTION is not None and info["direction"] != cls._DIRECTION:
+            raise ValueError("the snapshot is of a rate converter for %s, not %s" % (names[info["direction"]], names[cls._DIRECTION]))
+        kind = cls if cls._DIRECTION is not None else (CaptureConverter, PlaybackConverter)[info["direction"]]
+        if (in_rate is None) != (out_rate is None):
+            raise ValueError("give both in_rate and out_rate, or neither")
+        if in_rate is None:
+            in_rate, out_rate = info["down"], info["up"]
+        elif cls.ratio(in_rate, out_rate) != (info["up"], info["down"]):
+            raise ValueError("%r -> %r is %d / %d, the snapshot converts by %d / %d" % ((in_rate, out_rate) + cls.ratio(in_rate, out_rate) + (info["up"], info["down"])))
+        b = _blob(snap)
+        m = None if stream_map is None else np.ascontiguousarray(stream_map, dtype=np.int64).reshape(-1)
+        n = 0 if m is None else len(m)
+        if m is not None and not n:
+            m = np.zeros(1, np.int64)   # (an empty map, not "all": a non-null pointer with n = 0, which the library refuses)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().fskhip_ratecvt_restore(device, b.ctypes.data, b.nbytes, None if m is None else m.ctypes.data, n, C.byref(h)))
+        taps = np.frombuffer(b, dtype="<f8", count=info["n_taps"], offset=64)   # (the header is 64 bytes; the image has been validated)
+        return kind._adopt(h, taps, info["up"], info["down"], info["precision"], device, in_rate, out_rate)
+
+
+def ratecvt_snapshot_info(snap):
+    """fskhip_ratecvt_snapshot_info_get: what a rate converter snapshot holds -- n_streams (records), direction (0 capture,
+    1 playback), up, down, n_taps, precision, history (floats per record), position -- validated on the host, no device needed"""
+    from .engine import _blob, _struct_dict
+    b = _blob(snap)
+    info = _lib.RatecvtSnapshotInfo()
+    _lib.check(_lib.lib().fskhip_ratecvt_snapshot_info_get(b.ctypes.data, b.nbytes, C.byref(info)))
+    return _struct_dict(info)
+
 
 class CaptureConverter(_RateConverter):
     """Capture samples at in_rate -> float32 [S, n / down * up] at out_rate, on the GPU (44.1 kHz in front of a 48 kHz engine:
