@@ -954,7 +954,10 @@ int fskhip_processor_process_ratecvt_host(fskhip_processor *p, fskhip_ratecvt *c
  *   fskhip_ratecvt_capture_any_device(capture, d_in, ..., n_in, X)  ->  fskhip_processor_process_device(p, X,
  *   fskhip_ratecvt_out_count_any(capture, n_in), ..., Y, fskhip_ratecvt_in_count_any(playback, n_out), ...)  ->
  *   fskhip_ratecvt_playback_any_device(playback, Y, ..., d_lens = NULL, d_out, ...)
- * with a side of the processor call that has 0 engine samples left out (NULL); always in separate launches.  The refusals are the
+ * with a side of the processor call that has 0 engine samples left out (NULL).  TX is the whole-period call's choice: stream-major
+ * output through a converter that fits the delay line takes the fused kernel in its any-length form, which starts from the
+ * playback handle's position (whole periods from position 0 whose engine count is whole periods too: the whole-period form);
+ * interleaved frames and longer converters take the two launches; fskhip_processor_last_tx_kernel says which.  The refusals are the
  * whole-period call's without the two multiples; then, where `up` > `down`, an n_out the playback handle cannot produce from its
  * position -- in_count_any(n_out) inputs write more -- is FSKHIP_E_INVALID, the message naming the counts below and above it that
  * it can produce.  A refused call leaves the processor, both histories and both positions as they were.
@@ -978,6 +981,23 @@ int fskhip_processor_process_ratecvt_any_device(fskhip_processor *p, fskhip_rate
 int fskhip_processor_process_ratecvt_any_host(fskhip_processor *p, fskhip_ratecvt *capture, fskhip_ratecvt *playback, const void *in,
                                               int in_format, int in_layout, size_t n_in, size_t in_pitch, void *out, int out_format,
                                               int out_layout, size_t n_out, size_t out_pitch, uint32_t flags);
+/*
+ * Which TX path the last quantum ran (ABI 8, additions; FSKHIP_ABI_VERSION stays 8), modelled on fskhip_last_kernel: the name of
+ * the kernel that wrote the quantum's output, or of the two launches that stand for one, joined by '+'; "" where the quantum had no
+ * TX side (a NULL output or n_out = 0), before the first quantum and for a NULL processor.  Every process form sets it behind a
+ * quantum it has issued; a call that is refused, or that fails before or in a launch, leaves it:
+ *   fskhip_processor_process_*          "processor_io_kernel"
+ *   fskhip_processor_process_fmt_*      "processor_io_fmt_kernel" ("processor_io_kernel" for float32 stream-major output)
+ *   fskhip_processor_process_rate_*     "processor_io_rate_kernel" or "processor_io_kernel+resample_down_kernel"
+ *   fskhip_processor_process_ratecvt_*  "processor_io_ratecvt_kernel" or "processor_io_kernel+ratecvt_playback_kernel"; the
+ *                                       _any_ forms "processor_io_ratecvt_kernel<any>" or
+ *                                       "processor_io_kernel+ratecvt_playback_any_kernel", and the whole-period names where the
+ *                                       quantum is whole periods of both rates from position 0
+ * The string is static.  FSKHIP_PROC_RATECVT_PAIR in a ratecvt form's flags sends a TX side that would take the fused kernel
+ * through the two launches instead, with the same results bit for bit: for measurements and tests; the other forms ignore it.
+ */
+#define FSKHIP_PROC_RATECVT_PAIR 4u
+const char *fskhip_processor_last_tx_kernel(const fskhip_processor *p);
 
 /*
  * A rate converter through remap, snapshot and restore (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): the handle follows its

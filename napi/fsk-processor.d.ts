@@ -4,6 +4,8 @@ import { CaptureConverter, Downsampler, PlaybackConverter, Upsampler } from './f
 import { FSKBatch, FSKConfig, FSKCore, FSKStatus, SampleArray, SampleFormat, SampleLayout } from './fsk-core';
 export declare const PROC_CLEAR_RX_ON_TX_COMPLETE: 1;
 export declare const PROC_GRAPH: 2;
+/** a ratecvt quantum's TX side through the two launches its fused kernel replaces (measurements, tests) */
+export declare const PROC_RATECVT_PAIR: 4;
 /** FSKProcessorBatch.snapshot(): the FSKBatch's stream snapshot and the processors' own image */
 export interface ProcessorBatchSnapshot { engine: Buffer; processor: Buffer; }
 export declare function processorSnapshotInfo(buf: Uint8Array): { nStreams: number; rxCapacity: number; payloadCapacity: number; recordBytes: number };
@@ -31,6 +33,9 @@ export declare class FSKProcessorBatch {
     output?: { format?: SampleFormat; layout?: SampleLayout; nOut?: number; pitch?: number; downsampler?: PlaybackConverter }): SampleArray | null;
   /** 'modulate': throws 'Modulation already in progress' when a selected stream still has one */
   modulate(payloads: Uint8Array[], mask?: boolean[]): void;
+  /** the kernel that wrote the last quantum's output, or the two launches that stand for one joined by '+'
+   *  ('processor_io_ratecvt_kernel<any>', 'processor_io_kernel+ratecvt_playback_any_kernel', ...); '' where it had no TX side */
+  readonly lastTxKernel: string;
   txState(): { pos: Uint32Array; total: Uint32Array; pending: Uint8Array; completed: Uint32Array };
   /** 'demodulate' without the wait: everything buffered, per stream */
   demodulate(): Uint8Array[];

@@ -9,7 +9,7 @@ const addon = require(path.join(__dirname, 'fsk_addon.node'));
 const { FSKBatch, sampleFormat, sampleLayout } = require(path.join(__dirname, 'fsk-core.js'));
 const { Upsampler, Downsampler, CaptureConverter, PlaybackConverter } = require(path.join(__dirname, 'filters.js'));
 const { busyError } = require(path.join(__dirname, 'errors.js'));
-const PROC_CLEAR_RX_ON_TX_COMPLETE = 1, PROC_GRAPH = 2;
+const PROC_CLEAR_RX_ON_TX_COMPLETE = 1, PROC_GRAPH = 2, PROC_RATECVT_PAIR = 4;
 
 class FSKProcessorBatch {
   // batch: an FSKBatch (fsk-core.js); rxCapacity 1024 = demodulatedBuffer (fsk-processor.ts:84)
@@ -168,6 +168,9 @@ class FSKProcessorBatch {
     }
   }
   txState() { return addon.processorTxState(this.handle); }
+  // fskhip_processor_last_tx_kernel: the kernel that wrote the last quantum's output, or the two launches that stand for one joined
+  // by '+' ('processor_io_ratecvt_kernel<any>', 'processor_io_kernel+ratecvt_playback_any_kernel', ...); '' where it had no TX side
+  get lastTxKernel() { return addon.processorLastTxKernel(this.handle); }
   // 'demodulate' (117-138) without the wait: everything buffered, per stream
   demodulate() {
     const r = addon.processorDrain(this.handle, this.rxCapacity);
@@ -199,4 +202,4 @@ class FSKProcessorBatch {
   }
 }
 const processorSnapshotInfo = (buf) => addon.processorSnapshotInfo(buf);
-module.exports = { FSKProcessorBatch, processorSnapshotInfo, PROC_CLEAR_RX_ON_TX_COMPLETE, PROC_GRAPH };
+module.exports = { FSKProcessorBatch, processorSnapshotInfo, PROC_CLEAR_RX_ON_TX_COMPLETE, PROC_GRAPH, PROC_RATECVT_PAIR };

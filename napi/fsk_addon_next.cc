@@ -13,6 +13,7 @@
 //     nOut, outPitch, flags) -> the output format's typed array | null: the same with either side in a capture format and layout
 //   processorModulate(handle, payloads: Uint8Array, lens: Uint32Array, pitch, mask: Uint8Array|null)
 //   processorTxState(handle) -> {pos, total, pending, completed};  processorRxLength(handle) -> Uint32Array
+//   processorLastTxKernel(handle) -> string
 //   processorDrain(handle, capacity) -> {out, outPitch, counts};  processorReset(handle, stream)
 //   processorDrainSparse(handle, mask: Uint8Array|null, minLen) -> {streams: Uint32Array, offsets: Uint32Array, data: Uint8Array}
 //   xmodemRxCreate(processor) -> handle;  xmodemRxDestroy(handle);  xmodemRxReset(handle, stream)
@@ -284,6 +285,15 @@ napi_value ProcessorRxLength(napi_env env, napi_callback_info info) {
   napi_value v = make_typed(env, napi_uint32_array, h->S, 4, &lens);
   int rc = fskhip_processor_rx_length_host(h->p, (uint32_t *)lens);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return v;
+}
+
+napi_value ProcessorLastTxKernel(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  Proc *h = get_proc(env, argv[0]);
+  if (!h) return nullptr;
+  napi_value v;
+  napi_create_string_utf8(env, fskhip_processor_last_tx_kernel(h->p), NAPI_AUTO_LENGTH, &v);
   return v;
 }
 
@@ -1400,6 +1410,7 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"processorModulate", nullptr, ProcessorModulate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorTxState", nullptr, ProcessorTxState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRxLength", nullptr, ProcessorRxLength, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"processorLastTxKernel", nullptr, ProcessorLastTxKernel, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorDrain", nullptr, ProcessorDrain, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorDrainSparse", nullptr, ProcessorDrainSparse, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorReset", nullptr, ProcessorReset, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -13,6 +13,7 @@ MAX_PATTERN_BYTES = 16
 OK = 0
 E_INVALID, E_NOT_CONFIGURED, E_UNSUPPORTED, E_NO_DEVICE, E_HIP, E_NOMEM, E_OVERFLOW, E_BUSY, E_HANDOFF = -1, -2, -3, -4, -5, -6, -7, -8, -9
 PROC_CLEAR_RX_ON_TX_COMPLETE, PROC_GRAPH = 1, 2
+PROC_RATECVT_PAIR = 4      # (a ratecvt quantum's TX side through the two launches its fused kernel replaces: measurements, tests)
 XM_NEED_MORE, XM_EOT, XM_TRUNCATED, XM_INVALID_SEQUENCE, XM_INVALID_CRC, XM_UNEXPECTED_SEQUENCE = 0, 1, 2, 3, 4, 5
 XT_IDLE, XT_WAIT_NAK, XT_WAIT_ACK, XT_WAIT_FINAL_ACK = 0, 1, 2, 3
 XT_PROGRESS, XT_DONE, XT_MAX_RETRIES, XT_ABORTED = 0, 1, 2, 3
@@ -187,6 +188,7 @@ _SYMBOLS = [
     ("fskhip_processor_process_device", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_uint32, _P]),
     ("fskhip_processor_process_host", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_uint32]),
     ("fskhip_processor_graph_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("fskhip_processor_last_tx_kernel", C.c_char_p, [_P]),
     ("fskhip_processor_process_fmt_device", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, _P]),
     ("fskhip_processor_process_fmt_host", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, _P, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32]),
     ("fskhip_processor_modulate_host", C.c_int, [_P, _P, _P, C.c_size_t, _P]),

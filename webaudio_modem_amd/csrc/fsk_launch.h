@@ -103,15 +103,17 @@ hipError_t launch_processor_io_fmt(const ModParams &M, const double *coef, const
 hipError_t launch_processor_io_rate(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out, size_t demod_pitch, const uint32_t *demod_counts,
                                     bool do_rx, void *out, int format, int layout, size_t n_out, size_t out_pitch, bool clear_rx_on_complete, int precision,
                                     uint32_t factor, uint32_t n_taps, const void *d_taps, const float *d_hist_in, float *d_hist_out, hipStream_t st);
-// the same quantum with `out` behind a playback converter (fskhip_processor_process_ratecvt_*): n_out > 0 outputs per stream, a
-// multiple of `up`, of the n_out / up * down samples the generator makes, filtered as launch_ratecvt's playback direction does
-// (d_taps [K][up] in output order in `precision`, histories [n_streams][ceil((n_taps - 1) / up)], d_hist_in read and d_hist_out
-// written) and encoded, in one launch.  hipErrorInvalidValue where processor_ratecvt_plan (fsk_processor_rate_plan.h) does not
-// fuse the filter or the layout: the caller runs launch_processor_io and launch_ratecvt.
+// the same quantum with `out` behind a playback converter (fskhip_processor_process_ratecvt_*): n_out > 0 outputs per stream from
+// the handle's position pos < down, out of the n_high samples the generator makes: ratecvt_in_count_any(up, down, pos, n_out) of
+// them or more, as long as they write n_out.  pos = 0 with n_out a multiple of `up` and n_high = n_out / up * down is the kernel's
+// whole-period form, everything else its any-length form.  The samples are filtered as launch_ratecvt's playback direction does at
+// that position (d_taps [K][up] in output order in `precision`, histories [n_streams][ceil((n_taps - 1) / up)], d_hist_in read and
+// d_hist_out written) and encoded, in one launch.  hipErrorInvalidValue where processor_ratecvt_plan (fsk_processor_rate_plan.h)
+// does not fuse the filter or the layout: the caller runs launch_processor_io and launch_ratecvt.
 hipError_t launch_processor_io_ratecvt(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out, size_t demod_pitch,
                                        const uint32_t *demod_counts, bool do_rx, void *out, int format, int layout, size_t n_out, size_t out_pitch,
-                                       bool clear_rx_on_complete, int precision, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps,
-                                       const float *d_hist_in, float *d_hist_out, hipStream_t st);
+                                       bool clear_rx_on_complete, int precision, uint32_t up, uint32_t down, uint32_t pos, size_t n_high,
+                                       uint32_t n_taps, const void *d_taps, const float *d_hist_in, float *d_hist_out, hipStream_t st);
 hipError_t launch_processor_tx_start(const ModParams &M, const ProcState &T, const uint8_t *payloads, const uint32_t *lens, size_t payload_pitch, const uint8_t *mask,
                                      hipStream_t st);
 hipError_t launch_processor_rx_drain(const ProcState &T, uint32_t n_streams, uint8_t *out, size_t out_pitch, uint32_t *counts, hipStream_t st);

@@ -841,15 +841,23 @@ __global__ __launch_bounds__(64) void processor_io_rate_kernel(ModParams M, cons
 // `mac` in the handle's precision, the taps from the [K][Lu] table in output order (column j mod Lu; wave-uniform, scalar loads) --
 // the same float, bit for bit.  The handle's history is H = ceil((n_taps - 1) / Lu) samples per stream, and the sum reaches back at
 // most H from m, so the delay line is H + kRateChunk slots (fsk_processor_rate_plan.h: processor_ratecvt_plan).
-// The launcher has seen to n_out > 0 a multiple of Lu, `slots` >= H + kRateChunk and the LDS for it.
-template <bool EXACT, typename Real, int FMT>
+// Two forms of the one body.  !ANY is a quantum of whole periods from a period boundary: n_out a multiple of Lu, the accumulators
+// start at zero and the quantum is n_out / Lu * Md samples; the four trailing arguments are not read.  ANY is a quantum of any n_out
+// from the handle's position (fskhip_processor_process_ratecvt_any_*): the host passes where it starts on the period grid
+// (fsk_processor_rate_plan.h: processor_ratecvt_start) -- n_high_any samples to generate, and the first output's tap column q0,
+// phase ph0 and newest input m0 counted from the quantum's first sample, wave-uniform like everything the tap loads depend on.
+// Output k0 + k of the grid is stored at column k.  The history at exit is the H newest samples in either form: a quantum of fewer
+// than H samples leaves the rest of the old history, which still lies in the ring, in front of its own.
+// The launcher has seen to n_out > 0 (!ANY: a multiple of Lu), `slots` >= H + kRateChunk and the LDS for it.
+template <bool EXACT, typename Real, int FMT, bool ANY>
 __global__ __launch_bounds__(64) void processor_io_ratecvt_kernel(ModParams M, const double *__restrict__ coef, ProcState T,
                                                                   const uint8_t *__restrict__ demod_out, size_t demod_pitch,
                                                                   const uint32_t *__restrict__ demod_counts, int do_rx,
                                                                   void *__restrict__ out_, size_t n_out, size_t out_pitch, int vec_ok,
                                                                   uint32_t clear_rx_on_complete, const float *__restrict__ hist_in,
                                                                   float *__restrict__ hist_out, const void *__restrict__ taps_, uint32_t Lu,
-                                                                  uint32_t Md, uint32_t n_taps, uint32_t slots) {
+                                                                  uint32_t Md, uint32_t n_taps, uint32_t slots, size_t n_high_any,
+                                                                  uint32_t q0, uint32_t ph0, uint32_t m0) {
   using F = SampleFmt<FMT>;
   using Bits = typename F::Bits;
   static_assert(kRateCodeTile == (uint32_t)kTile && kRateChunk == 4u, "the code rows are store_code_rows', the generator's step frame_next4's");
@@ -903,11 +911,11 @@ __global__ __launch_bounds__(64) void processor_io_ratecvt_kernel(ModParams M, c
       for (uint32_t h = lane; h < H; h += 64u) dl[h * kPitch + c] = s < M.n_streams ? hist_in[(size_t)s * H + h] : 0.0f;
     }
     __syncthreads();
-    const size_t n_high = n_out / Lu * Md;
+    const size_t n_high = ANY ? n_high_any : n_out / Lu * Md;
     uint32_t wslot = H;        // the slot of sample t0: (H + t0) mod slots
-    size_t k = 0;              // the next output
-    uint32_t q = 0, ph = 0;    // k mod Lu, (k Md) mod Lu
-    size_t m = 0;              // (k Md) div Lu: the sample that completes output k
+    size_t k = 0;              // the next output (ANY: output k0 + k of the period grid)
+    uint32_t q = ANY ? q0 : 0u, ph = ANY ? ph0 : 0u;    // (k0 + k) mod Lu, ((k0 + k) Md) mod Lu
+    size_t m = ANY ? m0 : 0u;  // ((k0 + k) Md) div Lu - pos: the sample that completes output k
     for (size_t t0 = 0; t0 < n_high; t0 += kRateChunk) {
       // samples beyond n_high inside the last step must not advance the generator
       const float4 v = frame_next4<EXACT>(G, M, pb, t0 + 0 < n_high, t0 + 1 < n_high, t0 + 2 < n_high, t0 + 3 < n_high);
@@ -1081,26 +1089,32 @@ hipError_t launch_processor_io_rate(const ModParams &M, const double *coef, cons
   return hipGetLastError();
 }
 // every instantiation behind a playback converter, once: [exact sine][the converter's precision][format], as above
-#define FSK_IO_RATECVT_KERNELS(EXACT, R) \
-  {FSK_K(processor_io_ratecvt_kernel, EXACT, R, FSKHIP_SAMPLES_F32), FSK_K(processor_io_ratecvt_kernel, EXACT, R, FSKHIP_SAMPLES_S16), \
-   FSK_K(processor_io_ratecvt_kernel, EXACT, R, FSKHIP_SAMPLES_MULAW), FSK_K(processor_io_ratecvt_kernel, EXACT, R, FSKHIP_SAMPLES_ALAW)}
+// (and in front: [any length], the form of the body)
+#define FSK_IO_RATECVT_KERNELS(EXACT, R, ANY) \
+  {FSK_K(processor_io_ratecvt_kernel, EXACT, R, FSKHIP_SAMPLES_F32, ANY), FSK_K(processor_io_ratecvt_kernel, EXACT, R, FSKHIP_SAMPLES_S16, ANY), \
+   FSK_K(processor_io_ratecvt_kernel, EXACT, R, FSKHIP_SAMPLES_MULAW, ANY), FSK_K(processor_io_ratecvt_kernel, EXACT, R, FSKHIP_SAMPLES_ALAW, ANY)}
+#define FSK_IO_RATECVT_FORM(ANY) \
+  {{FSK_IO_RATECVT_KERNELS(false, float, ANY), FSK_IO_RATECVT_KERNELS(false, double, ANY)}, \
+   {FSK_IO_RATECVT_KERNELS(true, float, ANY), FSK_IO_RATECVT_KERNELS(true, double, ANY)}}
 using IoRatecvtFn = void (*)(ModParams, const double *, ProcState, const uint8_t *, size_t, const uint32_t *, int, void *, size_t, size_t, int, uint32_t, const float *,
-                             float *, const void *, uint32_t, uint32_t, uint32_t, uint32_t);
-static const KernelEntry<IoRatecvtFn> kIoRatecvtKernels[2][2][4] = {{FSK_IO_RATECVT_KERNELS(false, float), FSK_IO_RATECVT_KERNELS(false, double)},
-                                                                    {FSK_IO_RATECVT_KERNELS(true, float), FSK_IO_RATECVT_KERNELS(true, double)}};
+                             float *, const void *, uint32_t, uint32_t, uint32_t, uint32_t, size_t, uint32_t, uint32_t, uint32_t);
+static const KernelEntry<IoRatecvtFn> kIoRatecvtKernels[2][2][2][4] = {FSK_IO_RATECVT_FORM(false), FSK_IO_RATECVT_FORM(true)};
 
 hipError_t launch_processor_io_ratecvt(const ModParams &M, const double *coef, const ProcState &T, const uint8_t *demod_out, size_t demod_pitch,
                                        const uint32_t *demod_counts, bool do_rx, void *out, int format, int layout, size_t n_out, size_t out_pitch,
-                                       bool clear_rx_on_complete, int precision, uint32_t up, uint32_t down, uint32_t n_taps, const void *d_taps,
-                                       const float *d_hist_in, float *d_hist_out, hipStream_t st) {
+                                       bool clear_rx_on_complete, int precision, uint32_t up, uint32_t down, uint32_t pos, size_t n_high,
+                                       uint32_t n_taps, const void *d_taps, const float *d_hist_in, float *d_hist_out, hipStream_t st) {
   const size_t esz = sample_bytes(format);
   const RatePlan P = processor_ratecvt_plan(up, n_taps, (uint32_t)esz, layout == FSKHIP_LAYOUT_STREAM_MAJOR);
-  if (!out || n_out == 0 || n_out % up != 0 || !P.fused) return hipErrorInvalidValue;
+  if (!out || n_out == 0 || pos >= down || !P.fused) return hipErrorInvalidValue;
+  const bool any = processor_ratecvt_any(up, down, pos, n_out, n_high);
+  const RatecvtStart B = processor_ratecvt_start(up, down, pos, n_out);
+  if (n_high < B.n_high || ratecvt_out_count_any(up, down, pos, n_high) != n_out) return hipErrorInvalidValue;   // (samples that do not write n_out)
   const uint32_t blocks = (M.n_streams + 63u) / 64u;
   const int vec_ok = (out_pitch * esz % 16 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15u) == 0);
-  hipLaunchKernelGGL(kIoRatecvtKernels[M.exact_sin ? 1 : 0][precision == FSKHIP_PRECISION_F64 ? 1 : 0][format].fn, dim3(blocks), dim3(64), P.lds_bytes, st, M,
-                     coef, T, demod_out, demod_pitch, demod_counts, do_rx ? 1 : 0, out, n_out, out_pitch, vec_ok, clear_rx_on_complete ? 1u : 0u, d_hist_in,
-                     d_hist_out, d_taps, up, down, n_taps, P.slots);
+  hipLaunchKernelGGL(kIoRatecvtKernels[any][M.exact_sin ? 1 : 0][precision == FSKHIP_PRECISION_F64 ? 1 : 0][format].fn, dim3(blocks), dim3(64), P.lds_bytes, st,
+                     M, coef, T, demod_out, demod_pitch, demod_counts, do_rx ? 1 : 0, out, n_out, out_pitch, vec_ok, clear_rx_on_complete ? 1u : 0u, d_hist_in,
+                     d_hist_out, d_taps, up, down, n_taps, P.slots, n_high, B.q, B.ph, B.m);
   return hipGetLastError();
 }
 hipError_t launch_processor_tx_start(const ModParams &M, const ProcState &T, const uint8_t *payloads, const uint32_t *lens,

@@ -11,6 +11,7 @@ struct fskhip_processor {
   uint32_t S = 0;
   fsk::ProcState T{};
   bool used = false;   // a process, modulate, drain or reset call has been made: no longer what fskhip_processor_create left
+  const char *last_tx_kernel = "";   // fskhip_processor_last_tx_kernel: what the last quantum's TX side ran (fsk::kTx* below)
   // demodulator outputs of the current quantum
   uint8_t *d_bytes = nullptr; size_t bytes_pitch = 0;
   uint32_t *d_counts = nullptr, *d_eod = nullptr;
@@ -45,6 +46,19 @@ struct fskhip_processor {
 };
 
 namespace fsk {
+
+// What fskhip_processor_last_tx_kernel reports: the kernel of a quantum's TX side, or the two launches that stand for one.  Every
+// process form decides it in front of its quantum and sets it behind one that was issued (run_quantum_tx): launched, captured or
+// replayed.
+constexpr const char *kTxNone = "";
+constexpr const char *kTxIo = "processor_io_kernel";
+constexpr const char *kTxFmt = "processor_io_fmt_kernel";
+constexpr const char *kTxRate = "processor_io_rate_kernel";
+constexpr const char *kTxRatePair = "processor_io_kernel+resample_down_kernel";
+constexpr const char *kTxRatecvt = "processor_io_ratecvt_kernel";
+constexpr const char *kTxRatecvtAny = "processor_io_ratecvt_kernel<any>";
+constexpr const char *kTxRatecvtPair = "processor_io_kernel+ratecvt_playback_kernel";
+constexpr const char *kTxRatecvtAnyPair = "processor_io_kernel+ratecvt_playback_any_kernel";
 
 inline void drop_graph(fskhip_processor *p) {
   if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
@@ -89,6 +103,15 @@ int run_quantum(fskhip_processor *p, fskhip_processor::Key key, bool has_in, Lau
   HIP_TRY(hipGraphLaunch(p->graph_exec, key.st));
   p->graph_replays++;
   return FSKHIP_OK;
+}
+
+// run_quantum, and behind a quantum that was issued the name of its TX path (fskhip_processor_last_tx_kernel): a call that fails
+// here or in a launch leaves the name of the quantum before, as a refused one does
+template <typename Launch>
+int run_quantum_tx(fskhip_processor *p, const char *tx, fskhip_processor::Key key, bool has_in, Launch launch) {
+  const int rc = run_quantum(p, key, has_in, launch);
+  if (rc == FSKHIP_OK) p->last_tx_kernel = tx;
+  return rc;
 }
 
 // the demodulators' byte slab [S][bytes_pitch] holds a quantum of n_in samples: grown outside any capture, and a captured quantum,

@@ -125,7 +125,7 @@ int fskhip_processor_process_device(fskhip_processor *p, float *d_in, size_t n_i
   hipStream_t st = (hipStream_t)hip_stream;
   if (d_in)   // byte slab of this quantum
     if (const int rc = grow_byte_slab(p, n_in)) return rc;
-  return run_quantum(p, {d_in, n_in, in_pitch, d_out, n_out, out_pitch, flags, st, 0u}, d_in != nullptr,
+  return run_quantum_tx(p, d_out && n_out ? kTxIo : kTxNone, {d_in, n_in, in_pitch, d_out, n_out, out_pitch, flags, st, 0u}, d_in != nullptr,
                      [&](uint32_t f) { return launch_quantum(p, d_in, n_in, in_pitch, d_out, n_out, out_pitch, f, st); });
 }
 
@@ -152,6 +152,8 @@ int fskhip_processor_process_host(fskhip_processor *p, float *in, size_t n_in, s
   HIP_TRY(hipStreamSynchronize(p->stream));
   return FSKHIP_OK;
 }
+
+const char *fskhip_processor_last_tx_kernel(const fskhip_processor *p) { return p ? p->last_tx_kernel : ""; }
 
 int fskhip_processor_graph_stats(const fskhip_processor *p, uint64_t *captures, uint64_t *replays) {
   if (!p) return fail(FSKHIP_E_INVALID, "null processor");

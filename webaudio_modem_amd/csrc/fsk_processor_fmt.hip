@@ -77,7 +77,7 @@ int fskhip_processor_process_fmt_device(fskhip_processor *p, const void *d_in, i
     if (!in.floats())
       if (const int rc = grow_for_quantum(p, p->d_fin, p->d_fin_cap, fin_pitch * p->S)) return rc;
   }
-  return run_quantum(p, {(float *)const_cast<void *>(d_in), n_in, in_pitch, (float *)d_out, n_out, out_pitch, flags, st, 0u, in_format, in_layout, out_format, out_layout},
+  return run_quantum_tx(p, !(d_out && n_out) ? kTxNone : out.floats() ? kTxIo : kTxFmt, {(float *)const_cast<void *>(d_in), n_in, in_pitch, (float *)d_out, n_out, out_pitch, flags, st, 0u, in_format, in_layout, out_format, out_layout},
                      d_in != nullptr, [&](uint32_t f) { return launch_quantum_fmt(p, in, fin_pitch, out, f, st); });
 }
 

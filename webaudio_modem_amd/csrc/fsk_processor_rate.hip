@@ -67,8 +67,9 @@ int process_rate_device(const char *who, fskhip_processor *p, const Side &in, co
   }
   if (out.ptr && out.n && !fused)
     if (const int rc = grow_for_quantum(p, p->d_ftx, p->d_ftx_cap, ftx_pitch * p->S)) return rc;
+  const char *const tx = !(out.ptr && out.n) ? kTxNone : fused ? kTxRate : kTxRatePair;
   // plainly, whatever FSKHIP_PROC_GRAPH says: the handles' history pointers change from call to call
-  return run_quantum(p, {nullptr, n_hi, fin_pitch, nullptr, out.n, out.pitch, flags & ~FSKHIP_PROC_GRAPH, st, 0u}, in.ptr != nullptr,
+  return run_quantum_tx(p, tx, {nullptr, n_hi, fin_pitch, nullptr, out.n, out.pitch, flags & ~FSKHIP_PROC_GRAPH, st, 0u}, in.ptr != nullptr,
                      [&](uint32_t f) { return launch_quantum_rate(who, p, in, fin_pitch, out, fused, ftx_pitch, f, st); });
 }
 

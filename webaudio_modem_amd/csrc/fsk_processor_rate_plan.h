@@ -1,6 +1,7 @@
 // fsk_processor_rate_plan.h -- how fskhip_processor_process_rate_* (fsk_processor_rate.hip) and, at the end of the file,
 // fskhip_processor_process_ratecvt_* (fsk_processor_ratecvt.hip) run their TX sides, in plain C++ so that it also compiles without
-// HIP (tests/cpp/processor_rate_plan_check.cpp, processor_ratecvt_plan_check.cpp).  Not part of the ABI.
+// HIP (tests/cpp/processor_rate_plan_check.cpp, processor_ratecvt_plan_check.cpp, processor_ratecvt_any_plan_check.cpp).  Not part
+// of the ABI.
 //
 // The fused kernel (fsk_mod.hip: processor_io_rate_kernel) is one wave per 64 streams, lane = stream.  The generator's samples go
 // into a delay line in LDS, [slot][lane] with rows kRateLanePitch words apart, which at entry holds the decimator's history
@@ -14,6 +15,8 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+
+#include "fsk_ratecvt_plan.h"
 
 namespace fsk {
 
@@ -59,6 +62,37 @@ inline RatePlan processor_ratecvt_plan(uint32_t L, uint32_t n_taps, uint32_t esz
   P.fits = P.lds_bytes <= kRateLdsBytes;
   P.fused = P.fits && stream_major;
   return P;
+}
+
+// Where the fused kernel's ANY form starts: a quantum of n_out outputs from the playback handle's position pos < M, the engine
+// samples taken since the last period boundary (fsk_ratecvt_plan.h: "Calls of any length").  The kernel takes the grid's outputs in
+// order, each as soon as its newest input is written, so it needs the first one the call owns and that output's accumulators:
+//   k0      ceil(pos L / M), the first output of the period grid whose newest input lies in the call (at most L)
+//   q       k0 mod L, its column of the [K][L] tap table
+//   ph      (k0 M) mod L, its phase
+//   m       (k0 M) div L - pos, its newest input counted from the call's first sample (>= 0 by the choice of k0)
+//   n_high  ratecvt_in_count_any(L, M, pos, n_out): the engine samples the call generates, the newest input of output
+//           k0 + n_out - 1 and itself
+// The whole-period form is pos = 0 with n_out a multiple of L over n_out / L * M samples: k0, q, ph and m are zero.
+struct RatecvtStart {
+  size_t k0;
+  uint32_t q, ph, m;
+  size_t n_high;
+};
+inline RatecvtStart processor_ratecvt_start(uint32_t L, uint32_t M, uint32_t pos, size_t n_out) {
+  RatecvtStart s{};
+  s.k0 = ratecvt_first_output(L, M, pos);
+  s.q = (uint32_t)(s.k0 % L);
+  s.ph = (uint32_t)(s.k0 * M % L);
+  s.m = (uint32_t)(s.k0 * M / L - pos);
+  s.n_high = ratecvt_in_count_any(L, M, pos, n_out);
+  return s;
+}
+// which of the two forms a quantum of n_high engine samples runs: whole periods from a period boundary keep their own
+// instantiations.  (Where L < M the fewest samples that write whole periods of output stop short of the last period's end --
+// 159 of 160 for one period of 147 / 160 -- so the any-length call of such an n_out is the ANY form's.)
+inline bool processor_ratecvt_any(uint32_t L, uint32_t M, uint32_t pos, size_t n_out, size_t n_high) {
+  return pos != 0 || n_out % L != 0 || n_high != n_out / L * M;
 }
 
 }  // namespace fsk

@@ -11,8 +11,10 @@
 // Either way every word of processor, engine and handle state ends as the chain of the three existing calls leaves it.  What the
 // call shares with fsk_processor_rate.hip is fsk_processor_rate_host.h's.
 // fskhip_processor_process_ratecvt_any_* are the same quantum with sides of any length, from the handles' positions
-// (fsk_ratecvt_plan.h): the engine's counts are the handles' own, a side without engine samples is left out of the processor's
-// part, and TX always takes the two launches.
+// (fsk_ratecvt_plan.h): the engine's counts are the handles' own, and a side without engine samples is left out of the processor's
+// part.  TX takes the same choice: the fused kernel's ANY form from the playback handle's position (fsk_processor_rate_plan.h:
+// processor_ratecvt_start) -- its whole-period form for whole periods from position 0 --, the two launches for frames, for a
+// converter beyond the delay line and under FSKHIP_PROC_RATECVT_PAIR.  fskhip_processor_last_tx_kernel says which.
 #include <hip/hip_runtime.h>
 
 #include "fsk_processor_rate_host.h"
@@ -78,8 +80,8 @@ int launch_quantum_ratecvt(const char *who, fskhip_processor *p, const Side &in,
   fskhip_ratecvt *const d = cvt(out);
   if (fused) {
     HIP_TRY(launch_processor_io_ratecvt(p->e->M, p->e->S.coef, p->T, p->d_bytes, p->bytes_pitch, p->d_counts, rx, const_cast<void *>(out.ptr),
-                                        out.format, out.layout, out.n, out.pitch, clear, d->precision, d->L, d->M, d->n_taps, d->taps(), d->hist[d->cur],
-                                        d->hist[d->cur ^ 1], st));
+                                        out.format, out.layout, out.n, out.pitch, clear, d->precision, d->L, d->M, d->pos, n_ho, d->n_taps, d->taps(),
+                                        d->hist[d->cur], d->hist[d->cur ^ 1], st));
   } else {
     HIP_TRY(launch_processor_io(p->e->M, p->e->S.coef, p->T, p->d_bytes, p->bytes_pitch, p->d_counts, rx, p->d_ftx, n_ho, ftx_pitch, clear, st));
     if (const int rc = launch_failed(who, launch_ratecvt(FSKHIP_RATECVT_PLAYBACK, d->precision, p->d_ftx, ftx_pitch, nullptr, const_cast<void *>(out.ptr),
@@ -104,7 +106,8 @@ int process_ratecvt_device(const char *who, bool any, fskhip_processor *p, const
   const size_t n_ho = !out.ptr ? 0 : any ? ratecvt_in_count_any(cvt(out)->L, cvt(out)->M, cvt(out)->pos, out.n) : out.n / cvt(out)->L * cvt(out)->M;
   const bool rx = in.ptr && (!any || n_hi > 0);
   const size_t fin_pitch = n_hi ? (n_hi + 3) & ~(size_t)3 : 4, ftx_pitch = n_ho ? (n_ho + 3) & ~(size_t)3 : 4;   // rows on 16-byte boundaries
-  const bool fused = !any && out.ptr && processor_ratecvt_plan(out.r->L, out.r->n_taps, (uint32_t)sample_bytes(out.format), !out.frames()).fused;
+  const bool fused = out.ptr && !(flags & FSKHIP_PROC_RATECVT_PAIR) &&
+                     processor_ratecvt_plan(out.r->L, out.r->n_taps, (uint32_t)sample_bytes(out.format), !out.frames()).fused;
   if (in.ptr) {  // byte slab and float tile of this quantum
     if (rx)
       if (const int rc = grow_byte_slab(p, n_hi)) return rc;
@@ -112,8 +115,11 @@ int process_ratecvt_device(const char *who, bool any, fskhip_processor *p, const
   }
   if (out.ptr && out.n && !fused)
     if (const int rc = grow_for_quantum(p, p->d_ftx, p->d_ftx_cap, ftx_pitch * p->S)) return rc;
+  // (the pair's second launch chooses as launch_ratecvt does; the fused kernel as its launcher does)
+  const bool tx_any = out.ptr && (fused ? processor_ratecvt_any(cvt(out)->L, cvt(out)->M, cvt(out)->pos, out.n, n_ho) : cvt(out)->pos != 0 || n_ho % cvt(out)->M != 0);
+  const char *const tx = !(out.ptr && out.n) ? kTxNone : fused ? (tx_any ? kTxRatecvtAny : kTxRatecvt) : tx_any ? kTxRatecvtAnyPair : kTxRatecvtPair;
   // plainly, whatever FSKHIP_PROC_GRAPH says: the handles' history pointers change from call to call
-  return run_quantum(p, {nullptr, n_hi, fin_pitch, nullptr, out.n, out.pitch, flags & ~FSKHIP_PROC_GRAPH, st, 0u}, rx,
+  return run_quantum_tx(p, tx, {nullptr, n_hi, fin_pitch, nullptr, out.n, out.pitch, flags & ~FSKHIP_PROC_GRAPH, st, 0u}, rx,
                      [&](uint32_t f) { return launch_quantum_ratecvt(who, p, in, rx, n_hi, fin_pitch, out, n_ho, fused, ftx_pitch, f, st); });
 }
 

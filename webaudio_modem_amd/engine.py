@@ -454,11 +454,15 @@ class FSKEngine:
                                                       counts.ctypes.data, eod.ctypes.data, 0))
         return [out[s, :counts[s]].tobytes() for s in range(S)], eod
 
-    def demodulate_samples_at(self, samples, fmt, layout, upsampler, out_pitch=None):
+    def demodulate_samples_at(self, samples, fmt, layout, upsampler, out_pitch=None, any_length=False):
         """demodulate_samples for capture samples at a lower rate (8 kHz trunk audio in front of a 48 kHz engine): the narrow
         samples cross PCIe as they are, `upsampler` (filters.Upsampler, on this engine's device, its history carried from call to
         call) widens and interpolates them into a device tile, and demodulate_device runs on that tile.  `upsampler` may also be a
         filters.CaptureConverter (44.1 kHz captures: 160 / 147); the samples per stream must then be a multiple of its `down`.
+        any_length=True (a CaptureConverter only) takes any number of samples per stream, from the handle's position -- a capture
+        file of 44.1 kHz audio cut as it comes: process_any_device, then demodulate_device on the out_count_any(n) engine samples
+        it wrote; where that is none, the handle still takes its samples, nothing is demodulated and the returns are empty.  A
+        multiple of `down` from position 0 runs the calls it runs without the flag.
         Returns what demodulate_data returns."""
         from .filters import CaptureConverter
         x, code, lay, S, N, _ = sample_args(samples, fmt, layout)
@@ -467,23 +471,34 @@ class FSKEngine:
         if upsampler.device != self.device:
             raise ValueError("the upsampler is on device %d, the engine on %d" % (upsampler.device, self.device))
         eod = np.zeros(S, dtype=np.uint32)
+        if any_length and not isinstance(upsampler, CaptureConverter):
+            raise TypeError("upsampler is a %s: calls of any length go through a filters.CaptureConverter" % type(upsampler).__name__)
         if N == 0:
             return [b""] * S, eod
         x = np.ascontiguousarray(x)
-        if isinstance(upsampler, CaptureConverter):
+        any_length = any_length and (N % upsampler.down != 0 or upsampler.position != 0)
+        if any_length:
+            n = upsampler.out_count_any(N)
+        elif isinstance(upsampler, CaptureConverter):
             if N % upsampler.down:
                 raise ValueError("%d samples per stream are not a multiple of the converter's down factor %d" % (N, upsampler.down))
             n = upsampler.out_count(N)
         else:
             n = N * upsampler.factor
-        tpitch = (n + 3) & ~3
+        tpitch = max((n + 3) & ~3, 4)      # (a call that completes no engine sample still hands the converter a tile)
         opitch = out_pitch or self.max_bytes(n)
         out = np.zeros((S, opitch), dtype=np.uint8)
         counts = np.zeros(S, dtype=np.uint32)
         d_src, d_tile, d_out, d_counts, d_eod = (self._scratch(k, b) for k, b in (("narrow", x.nbytes), ("tile", 4 * S * tpitch), ("bytes", out.nbytes),
                                                                                   ("counts", 4 * S), ("eod", 4 * S)))
         self.h2d(d_src, x)
-        upsampler.process_device(d_src, code, lay, N, x.shape[1], d_tile, tpitch)
+        if any_length:
+            upsampler.process_any_device(d_src, code, lay, N, x.shape[1], d_tile, tpitch)
+            if n == 0:      # the handle has taken its samples; they completed no engine sample
+                self.synchronize()
+                return [b""] * S, eod
+        else:
+            upsampler.process_device(d_src, code, lay, N, x.shape[1], d_tile, tpitch)
         self.demodulate_device(d_tile, n, tpitch, d_out, opitch, d_counts, d_eod)
         self.synchronize()
         for a, d in ((out, d_out), (counts, d_counts), (eod, d_eod)):
@@ -543,17 +558,25 @@ class FSKEngine:
                                                     out_lens.ctypes.data))
         return out, out_lens
 
-    def modulate_samples_at(self, payloads, fmt, layout, downsampler, n_per_stream=None):
+    def modulate_samples_at(self, payloads, fmt, layout, downsampler, n_per_stream=None, any_length=False):
         """modulate_samples at a lower rate (a 48 kHz engine in front of an 8 kHz trunk): modulate_device writes the float tile,
         `downsampler` (filters.Downsampler, on this engine's device) decimates it with every stream's samples behind its own
         signal read as zeros, and one narrow copy comes back.  n_per_stream: low rate samples per stream (None: what the longest
         signal and the filter's ringing behind it take).  Returns (samples, lens): [S, n] or frames [n, S], and each stream's low
         rate length ceil((len + n_taps - 1) / factor), from where on it is the format's silence.  `downsampler` may also be a
         filters.PlaybackConverter (towards 44.1 kHz: 147 / 160): n_per_stream then counts its output samples and the lengths are
-        its out_length of each stream's signal, capped at n."""
+        its out_length of each stream's signal, capped at n.  any_length=True (a PlaybackConverter only) writes exactly
+        n_per_stream samples from the handle's position, whatever both are, through process_any_device on the
+        in_count_any(n_per_stream) engine samples that takes, and the handle moves on by those (without it the handle converts
+        whole periods, ceil(n / up) of them, and stays at its position); an n_per_stream the handle cannot write from its position
+        (only where up > down) is a ValueError in the processor's words.  The lengths are then the outputs of the call that the
+        stream's signal and the ringing behind it reach.  A multiple of `up` from position 0 runs the calls it runs without the
+        flag."""
         from .filters import PlaybackConverter
+        if any_length and not isinstance(downsampler, PlaybackConverter):
+            raise TypeError("downsampler is a %s: calls of any length go through a filters.PlaybackConverter" % type(downsampler).__name__)
         if isinstance(downsampler, PlaybackConverter):
-            return self._modulate_samples_converted(payloads, fmt, layout, downsampler, n_per_stream)
+            return self._modulate_samples_converted(payloads, fmt, layout, downsampler, n_per_stream, any_length)
         if len(payloads) != self.n_streams:
             raise ValueError("need one payload per stream")
         S, L = self.n_streams, downsampler.factor
@@ -581,22 +604,39 @@ class FSKEngine:
         self.d2h(out, d_dst)
         return out, np.minimum((out_lens.astype(np.int64) + len(downsampler.taps) - 1 + L - 1) // L, n).astype(np.uint32)
 
-    def _modulate_samples_converted(self, payloads, fmt, layout, converter, n_per_stream):
+    def _modulate_samples_converted(self, payloads, fmt, layout, converter, n_per_stream, any_length=False):
         """modulate_samples_at through a filters.PlaybackConverter (a 48 kHz engine in front of a 44.1 kHz sound card): the float
         tile is padded to a whole number of the converter's periods, so the call writes ceil(n / up) * up samples per stream on
-        the device and the first n come back.  The lengths are the converter's out_length of each stream's signal, capped at n."""
+        the device and the first n come back.  The lengths are the converter's out_length of each stream's signal, capped at n.
+        any_length: the call starts at the handle's position pos and writes exactly n through process_any_device on
+        in_count_any(n) engine samples (a multiple of `up` from position 0: the padded call above, which is the same call); n
+        defaults to the outputs from pos that the longest signal and the ringing behind it reach, and the lengths are each
+        stream's count of those, capped at n."""
         if len(payloads) != self.n_streams:
             raise ValueError("need one payload per stream")
         S = self.n_streams
         if converter.n_streams != S or converter.device != self.device:
             raise ValueError("the converter must have this engine's %d streams and device %d" % (S, self.device))
         pay, lens, ppitch = payload_args(payloads)
-        n = converter.out_length(self.modulated_length(int(lens.max()))) if n_per_stream is None else int(n_per_stream)
+        pos = converter.position if any_length else 0
+        first = -(-pos * converter.up // converter.down)      # the first output of the period grid that a call from pos writes
+
+        def reach(v):      # outputs of a call from pos that a signal of v samples and its ringing reach (pos 0: out_length(v))
+            return max(converter.out_length(pos + int(v)) - first, 0) if v else 0
+        n = reach(self.modulated_length(int(lens.max()))) if n_per_stream is None else int(n_per_stream)
         out_lens = np.zeros(S, dtype=np.uint32)
         if n == 0:
             return samples_out(fmt, layout, S, 0)[0], out_lens
-        periods = -(-n // converter.up)
-        n_in, n_dev = periods * converter.down, periods * converter.up
+        any_length = any_length and (n % converter.up != 0 or pos != 0)
+        if any_length:      # exactly n from the handle's position
+            n_in, n_dev = converter.in_count_any(n), n
+            above = converter.out_count_any(n_in)
+            if above != n:
+                raise ValueError("the playback handle at position %d cannot write n_out %d: %d engine samples give %d, %d give %d"
+                                 % (pos, n, n_in - 1, converter.out_count_any(n_in - 1), n_in, above))
+        else:
+            periods = -(-n // converter.up)
+            n_in, n_dev = periods * converter.down, periods * converter.up
         full, code, lay, pitch = samples_out(fmt, layout, S, n_dev)
         tpitch = (n_in + 3) & ~3
         d_pay, d_plens, d_tile, d_lens, d_dst = (self._scratch(k, b) for k, b in (("payloads", pay.nbytes), ("payload_lens", lens.nbytes), ("tile", 4 * S * tpitch),
@@ -609,11 +649,16 @@ class FSKEngine:
         if int(out_lens.max()) > n_in:            # refused before the converter runs: its history stays as it was
             s = int(np.argmax(out_lens > n_in))
             raise FskHipError(_lib.E_OVERFLOW, "stream %d needs %d samples, slab holds %d" % (s, out_lens[s], n_in))
-        converter.process_device(d_tile, n_in, tpitch, d_lens, d_dst, code, lay, pitch)
+        if any_length:
+            converter.process_any_device(d_tile, n_in, tpitch, d_lens, d_dst, code, lay, pitch)
+        else:
+            converter.process_device(d_tile, n_in, tpitch, d_lens, d_dst, code, lay, pitch)
         self.synchronize()
         self.d2h(full, d_dst)
         out = np.ascontiguousarray(full[:, :n] if lay == _lib.LAYOUT_STREAM_MAJOR else full[:n])
-        return out, np.array([min(converter.out_length(int(v)), n) for v in out_lens], dtype=np.uint32)
+        # (output j of the period grid is the call's j - first; a signal of v samples from position pos reaches the outputs up to
+        # out_length(pos + v) - 1 of the grid)
+        return out, np.array([min(reach(v), n) for v in out_lens], dtype=np.uint32)
 
     def modulate_device(self, d_payloads, d_lens, payload_pitch, d_out, out_pitch, d_out_lens, stream=None):
         _lib.check(self._L.fskhip_modulate_device(self._h, d_payloads, d_lens, payload_pitch, d_out, out_pitch,

@@ -14,7 +14,7 @@ import collections
 import numpy as np
 
 from . import _lib
-from ._lib import PROC_CLEAR_RX_ON_TX_COMPLETE, PROC_GRAPH  # noqa: F401
+from ._lib import PROC_CLEAR_RX_ON_TX_COMPLETE, PROC_GRAPH, PROC_RATECVT_PAIR  # noqa: F401
 from .engine import FSKEngine, _blob, _struct_dict, _sample_codes, sample_args, samples_out
 
 
@@ -185,6 +185,13 @@ class FSKProcessorBatch:
         cap, rep = C.c_uint64(0), C.c_uint64(0)
         _lib.check(self._L.fskhip_processor_graph_stats(self._h, C.byref(cap), C.byref(rep)))
         return int(cap.value), int(rep.value)
+
+    @property
+    def last_tx_kernel(self):
+        """fskhip_processor_last_tx_kernel: the kernel that wrote the last quantum's output, or the two launches that stand for one
+        joined by '+' ("processor_io_ratecvt_kernel<any>", "processor_io_kernel+ratecvt_playback_any_kernel", ...); "" where the
+        quantum had no TX side.  Every process form sets it."""
+        return (self._L.fskhip_processor_last_tx_kernel(self._h) or b"").decode()
 
     def process_device(self, d_in, n_in, in_pitch, d_out, n_out, out_pitch, stream=None, flags=None):
         _lib.check(self._L.fskhip_processor_process_device(self._h, d_in, n_in, in_pitch, d_out, n_out, out_pitch,
