@@ -251,6 +251,19 @@ int fskhip_processor_reset(fskhip_processor *p, int64_t stream);
  *                           the caller's duty: restore dst's engine from the stream snapshot taken at the same moment, with the
  *                           same map (fskhip_restore_streams checks the configs).  Every other precondition of the remap
  *                           applies; everything is validated before anything is written, a refused call leaves dst as it was.
+ * fskhip_processor_snapshot_concat  (ABI 8, an addition) host only, no device needed: out = the records of bufs[0], then bufs[1],
+ *                           ... under one header -- fskhip_snapshot_concat's contract (fskhip.h) for processor images, and what
+ *                           lets the shards of a sharded batch (one processor per GPU) stand as one image, beside the stream
+ *                           snapshots' concatenation, so that a live receiver moves from one GPU's processor to another's.
+ *                           Every part is validated as fskhip_processor_snapshot_info_get validates it (a flaw: FSKHIP_E_INVALID,
+ *                           the message names it and the part); parts of differing rx_capacity are refused.  The result is
+ *                           canonical: payload_capacity is per image the longest pending payload of ITS records rounded up
+ *                           to 16, so the parts of one batch differ in it as their payloads do -- the result takes the largest
+ *                           and every record is written at that pitch, zeros behind the shorter payloads.  The concatenation
+ *                           of the shards' images is therefore byte for byte the image one processor holding the same streams
+ *                           writes.  *written (may be NULL) receives the size; out NULL or cap too small (cap 0: the size
+ *                           query): FSKHIP_E_OVERFLOW, nothing written.  n == 0 or a null array: FSKHIP_E_INVALID.  out
+ *                           overlaps no part.
  * Large batches cross in slabs of 8192 streams, as stream snapshots do.  None of these calls returns -8.
  */
 typedef struct fskhip_processor_snapshot_info {
@@ -263,6 +276,7 @@ int fskhip_processor_remap(fskhip_processor *dst, const fskhip_processor *src, c
 size_t fskhip_processor_snapshot_bytes(const fskhip_processor *p, const int64_t *sel, uint32_t n_sel);
 int fskhip_processor_snapshot(fskhip_processor *p, const int64_t *sel, uint32_t n_sel, void *buf, size_t cap, size_t *written);
 int fskhip_processor_snapshot_info_get(const void *buf, size_t size, fskhip_processor_snapshot_info *info);
+int fskhip_processor_snapshot_concat(const void *const *bufs, const size_t *sizes, uint32_t n, void *out, size_t cap, size_t *written);
 int fskhip_processor_restore(fskhip_processor *dst, const void *buf, size_t size, const int64_t *map, uint32_t n_map);
 
 /* ---------------------------------------------------------------------------------------------------

@@ -9,6 +9,8 @@ export declare const PROC_RATECVT_PAIR: 4;
 /** FSKProcessorBatch.snapshot(): the FSKBatch's stream snapshot and the processors' own image */
 export interface ProcessorBatchSnapshot { engine: Buffer; processor: Buffer; }
 export declare function processorSnapshotInfo(buf: Uint8Array): { nStreams: number; rxCapacity: number; payloadCapacity: number; recordBytes: number };
+/** fskhip_processor_snapshot_concat: the records of `bufs` in order under one header, canonical (host only). */
+export declare function processorSnapshotConcat(bufs: Uint8Array[]): Buffer;
 export declare class FSKProcessorBatch {
   constructor(batch: FSKBatch, options?: { rxCapacity?: number; clearRxOnTxComplete?: boolean; useGraph?: boolean });
   readonly nStreams: number;
@@ -50,6 +52,44 @@ export declare class FSKProcessorBatch {
   snapshot(streams?: ArrayLike<number>): ProcessorBatchSnapshot;
   static fromSnapshot(snap: ProcessorBatchSnapshot, map?: ArrayLike<number>, configs?: Partial<FSKConfig> | Partial<FSKConfig>[], device?: number,
     options?: { clearRxOnTxComplete?: boolean; useGraph?: boolean }): FSKProcessorBatch;
+  close(): void;
+}
+export interface ShardedProcessorOptions { devices?: number[]; precision?: number; rxCapacity?: number; clearRxOnTxComplete?: boolean; useGraph?: boolean }
+type ShardedInput<U> = { format?: SampleFormat; layout?: SampleLayout; nIn?: number; pitch?: number; upsampler?: U[] };
+type ShardedOutput<D> = { format?: SampleFormat; layout?: SampleLayout; nOut?: number; pitch?: number; out?: SampleArray | null; downsampler?: D[] };
+/** S FSKProcessors over several GPUs: one FSKBatch and one FSKProcessorBatch per device over contiguous blocks; FSKProcessorBatch's
+ *  methods with global stream indices.  No host copy: a shard reads its row or column block of the caller's array and writes its block of
+ *  ONE output (`out`, also accepted by FSKProcessorBatch's process forms).  The rate forms take arrays of handles, one per shard. */
+export declare class FSKProcessorBatchSharded {
+  constructor(nStreams: number, configs?: Partial<FSKConfig> | Partial<FSKConfig>[], options?: ShardedProcessorOptions);
+  static blocks(nStreams: number, devices: number[]): { first: number; count: number; device: number }[];
+  readonly nStreams: number;
+  readonly shards: { first: number; count: number; device: number; batch: FSKBatch; procs: FSKProcessorBatch }[];
+  readonly processors: FSKProcessorBatch[];
+  readonly batches: FSKBatch[];
+  processDemodulationCallCount: number;
+  locate(stream: number): [{ first: number; count: number; device: number; batch: FSKBatch; procs: FSKProcessorBatch }, number];
+  process(inputs: Float32Array | null, nIn: number, nOut: number, out?: Float32Array | null): Float32Array | null;
+  processSamples(inputs: SampleArray | null, input?: ShardedInput<never>, output?: ShardedOutput<never>): SampleArray | null;
+  processSamplesAt(inputs: SampleArray | null, input?: ShardedInput<Upsampler | CaptureConverter>, output?: ShardedOutput<Downsampler | PlaybackConverter>): SampleArray | null;
+  processSamplesAtAny(inputs: SampleArray | null, input?: ShardedInput<CaptureConverter>, output?: ShardedOutput<PlaybackConverter>): SampleArray | null;
+  /** one entry per shard */
+  readonly lastTxKernel: string[];
+  /** refuses the whole call, on every shard, when a selected stream still has a modulation pending */
+  modulate(payloads: Uint8Array[], mask?: boolean[]): void;
+  txState(): { pos: Uint32Array; total: Uint32Array; pending: Uint8Array; completed: Uint32Array };
+  demodulate(): Uint8Array[];
+  /** global stream numbers, ascending, and one CSR over all shards */
+  rxDrainSparse(options?: { mask?: ArrayLike<boolean | number> | null; minLen?: number }): { streams: Uint32Array; offsets: Uint32Array; data: Uint8Array };
+  rxLengths(): Uint32Array;
+  reset(stream?: number): void;
+  status(stream?: number): FSKStatus & { demodulatedBufferLength: number; pendingModulation: boolean; fskCoreReady: boolean; processDemodulationCallCount: number };
+  /** stream i continues GLOBAL stream map[i] (-1: a new one) across shards and devices (options.devices: default this batch's) */
+  remap(map: ArrayLike<number>, configs?: Partial<FSKConfig> | Partial<FSKConfig>[], options?: ShardedProcessorOptions): FSKProcessorBatchSharded;
+  /** the shards' pairs under one header each (snapshotConcat, processorSnapshotConcat) */
+  snapshot(): ProcessorBatchSnapshot;
+  static fromSnapshot(snap: ProcessorBatchSnapshot, map?: ArrayLike<number>, configs?: Partial<FSKConfig> | Partial<FSKConfig>[],
+    options?: ShardedProcessorOptions): FSKProcessorBatchSharded;
   close(): void;
 }
 export interface ChunkResult { signal: Float32Array; isComplete: boolean; samplesConsumed: number; totalSamples: number; }

@@ -190,8 +190,25 @@ Proc *get_proc(napi_env env, napi_value v) {
   return h;
 }
 
+// the array a process call writes: the caller's `v` -- an optional last argument, which a sharded batch uses to let every shard
+// write its block of ONE array: of the output's type and at least `need` elements, returned as it is -- or, where v is absent or
+// null, a new one of `need` elements.  nullptr: thrown.
+static napi_value output_array(napi_env env, bool given, napi_value v, napi_typedarray_type type, size_t need, size_t elem, void **out, bool *fresh) {
+  *fresh = !given || nullish(env, v);
+  if (*fresh) {
+    napi_value o = make_typed(env, type, need, elem, out);
+    if (!o) napi_throw_error(env, nullptr, "allocation failed");
+    return o;
+  }
+  size_t len = 0;
+  if (!typed(env, v, type, out, &len)) return nullptr;
+  if (len < need) { napi_throw_range_error(env, nullptr, "out too short"); return nullptr; }
+  return v;
+}
+
 napi_value ProcessorProcess(napi_env env, napi_callback_info info) {
-  ARGS(6);
+  ARGS_UPTO(7);
+  if (argc < 6) { napi_throw_type_error(env, nullptr, "too few arguments"); return nullptr; }
   Proc *h = get_proc(env, argv[0]);
   if (!h) return nullptr;
   void *in; size_t ilen;
@@ -200,7 +217,8 @@ napi_value ProcessorProcess(napi_env env, napi_callback_info info) {
   if (in && (in_pitch < n_in || (size_t)in_pitch * (h->S - 1) + n_in > ilen)) { napi_throw_range_error(env, nullptr, "input too short"); return nullptr; }
   void *out = nullptr;
   napi_value out_v = nullptr;
-  if (n_out) out_v = make_typed(env, napi_float32_array, (size_t)n_out * h->S, 4, &out);
+  bool fresh = true;
+  if (n_out && !(out_v = output_array(env, argc > 6, argv[6], napi_float32_array, (size_t)n_out * h->S, 4, &out, &fresh))) return nullptr;
   int rc = fskhip_processor_process_host(h->p, (float *)in, n_in, in_pitch, (float *)out, n_out, n_out, flags);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
   if (!out_v) napi_get_null(env, &out_v);
@@ -218,7 +236,8 @@ static inline int64_t samples_needed(int32_t layout, uint32_t S, uint32_t n, uin
 // typed array or null, the result a new array of the output format's type, [S][outPitch] or [nOut][outPitch >= S] (its padding the
 // format's silence), or null when nOut is 0
 napi_value ProcessorProcessSamples(napi_env env, napi_callback_info info) {
-  ARGS(11);
+  ARGS_UPTO(12);
+  if (argc < 11) { napi_throw_type_error(env, nullptr, "too few arguments"); return nullptr; }
   const int32_t in_format = i32(env, argv[2]), in_layout = i32(env, argv[3]), out_format = i32(env, argv[6]), out_layout = i32(env, argv[7]);
   if (!sample_format_ok(env, in_format, in_layout) || !sample_format_ok(env, out_format, out_layout)) return nullptr;
   Proc *h = get_proc(env, argv[0]);
@@ -235,9 +254,9 @@ napi_value ProcessorProcessSamples(napi_env env, napi_callback_info info) {
   if (n_out) {
     const int64_t need = samples_needed(out_layout, h->S, n_out, out_pitch);
     if (need < 0) { napi_throw_range_error(env, nullptr, "output pitch too small"); return nullptr; }
-    out_v = make_typed(env, sample_array_type(out_format), (size_t)need, fskhip_sample_bytes(out_format), &out);
-    if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
-    fill_silence(out_format, out, (size_t)need);
+    bool fresh = true;
+    if (!(out_v = output_array(env, argc > 11, argv[11], sample_array_type(out_format), (size_t)need, fskhip_sample_bytes(out_format), &out, &fresh))) return nullptr;
+    if (fresh) fill_silence(out_format, out, (size_t)need);
   }
   int rc = fskhip_processor_process_fmt_host(h->p, in, in_format, in_layout, n_in, in_pitch, out, out_format, out_layout, n_out, out_pitch, flags);
   if (rc != FSKHIP_OK) return throw_fsk(env, rc);
@@ -797,6 +816,33 @@ napi_value ProcessorRestore(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// processorSnapshotConcat([image, ...]) -> Buffer: the records of all of them under one header, in canonical form (host only)
+napi_value ProcessorSnapshotConcat(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  bool is_arr = false;
+  if (napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr) { napi_throw_type_error(env, nullptr, "processorSnapshotConcat: an Array of processor snapshots"); return nullptr; }
+  uint32_t n = 0;
+  NAPI_OK(napi_get_array_length(env, argv[0], &n));
+  std::vector<const void *> ptrs(n);
+  std::vector<size_t> sizes(n);
+  for (uint32_t k = 0; k < n; k++) {
+    napi_value v;
+    void *data;
+    NAPI_OK(napi_get_element(env, argv[0], k, &v));
+    if (!typed(env, v, napi_uint8_array, &data, &sizes[k])) return nullptr;
+    ptrs[k] = data;
+  }
+  size_t need = 0;
+  int rc = fskhip_processor_snapshot_concat(ptrs.data(), sizes.data(), n, nullptr, 0, &need);
+  if (rc != FSKHIP_E_OVERFLOW) return throw_fsk(env, rc);
+  void *data = nullptr;
+  napi_value buf;
+  NAPI_OK(napi_create_buffer(env, need, &data, &buf));
+  rc = fskhip_processor_snapshot_concat(ptrs.data(), sizes.data(), n, data, need, nullptr);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return buf;
+}
+
 napi_value ProcessorSnapshotInfo(napi_env env, napi_callback_info info) {
   ARGS(1);
   void *data; size_t size;
@@ -1080,7 +1126,8 @@ FilterBox *rate_box_of(napi_env env, napi_value v) {
 }
 // any_length: fskhip_processor_process_ratecvt_any_host, for rate converters alone
 napi_value processor_process_samples_at(napi_env env, napi_callback_info info, bool any_length) {
-  ARGS(13);
+  ARGS_UPTO(14);
+  if (argc < 13) { napi_throw_type_error(env, nullptr, "too few arguments"); return nullptr; }
   const int32_t in_format = i32(env, argv[4]), in_layout = i32(env, argv[5]), out_format = i32(env, argv[8]), out_layout = i32(env, argv[9]);
   if (!sample_format_ok(env, in_format, in_layout) || !sample_format_ok(env, out_format, out_layout)) return nullptr;
   Proc *h = get_proc(env, argv[0]);
@@ -1105,9 +1152,9 @@ napi_value processor_process_samples_at(napi_env env, napi_callback_info info, b
     if (up && up->kind != down->kind) { napi_throw_type_error(env, nullptr, "one call takes resamplers or rate converters, not one of each"); return nullptr; }
     const int64_t need = samples_needed(out_layout, h->S, n_out, out_pitch);
     if (need < 0) { napi_throw_range_error(env, nullptr, "output pitch too small"); return nullptr; }
-    out_v = make_typed(env, sample_array_type(out_format), (size_t)need, fskhip_sample_bytes(out_format), &out);
-    if (!out_v) { napi_throw_error(env, nullptr, "allocation failed"); return nullptr; }
-    fill_silence(out_format, out, (size_t)need);
+    bool fresh = true;
+    if (!(out_v = output_array(env, argc > 13, argv[13], sample_array_type(out_format), (size_t)need, fskhip_sample_bytes(out_format), &out, &fresh))) return nullptr;
+    if (fresh) fill_silence(out_format, out, (size_t)need);
   }
   void *const uh = up ? up->p : nullptr, *const dh = down ? down->p : nullptr;
   const bool cvt = (up ? up : down) && (up ? up : down)->kind == BOX_RATECVT;
@@ -1440,6 +1487,7 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"processorSnapshot", nullptr, ProcessorSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRestore", nullptr, ProcessorRestore, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorSnapshotInfo", nullptr, ProcessorSnapshotInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"processorSnapshotConcat", nullptr, ProcessorSnapshotConcat, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"xmodemRxRemap", nullptr, XmodemRxRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"xmodemRxSnapshot", nullptr, XmodemRxSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"xmodemRxRestore", nullptr, XmodemRxRestore, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -202,6 +202,7 @@ _SYMBOLS = [
     ("fskhip_processor_snapshot_bytes", C.c_size_t, [_P, _P, C.c_uint32]),
     ("fskhip_processor_snapshot", C.c_int, [_P, _P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("fskhip_processor_snapshot_info_get", C.c_int, [_P, C.c_size_t, C.POINTER(ProcessorSnapshotInfo)]),
+    ("fskhip_processor_snapshot_concat", C.c_int, [C.POINTER(_P), C.POINTER(C.c_size_t), C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("fskhip_processor_restore", C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint32]),
     ("fskhip_xmodem_rx_create", C.c_int, [_P, C.POINTER(_P)]),
     ("fskhip_xmodem_rx_destroy", C.c_int, [_P]),

@@ -1,8 +1,8 @@
 // fsk_processor_remap_api.hip -- C ABI of libfskhip.so (include/fskhip_next.h): fskhip_processor_remap, and processor snapshots
-// (fskhip_processor_snapshot_bytes / _snapshot / _snapshot_info_get, fskhip_processor_restore).  They carry the FSKProcessor row
+// (fskhip_processor_snapshot_bytes / _snapshot / _snapshot_info_get / _snapshot_concat, fskhip_processor_restore).  They carry the FSKProcessor row
 // -- RX rings, pending modulations, `completed` counts -- where fskhip_remap_streams and the stream snapshots carry the FSKCore
 // below it.  The image's format is documented in the header; its layout and the one definition of a valid image are
-// fsk_processor_image.h's (host-only, on fsk_image.h's frame), and this file is the format's only writer.  Kernels:
+// fsk_processor_image.h's (host-only, on fsk_image.h's frame: the header, the sizes and the concatenation are defined there).  Kernels:
 // fsk_processor_remap.hip; the selection and room checks and the slab pipelines: fsk_stage.h, shared with the other three
 // snapshot units.
 #include <algorithm>
@@ -79,7 +79,7 @@ size_t fskhip_processor_snapshot_bytes(const fskhip_processor *p, const int64_t 
   if (hipSetDevice(p->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 0;
   uint32_t max_pay = 0;
   if (max_pending_payload(who, p, sel, n_sel, &max_pay)) return 0;
-  return sizeof(ProcHeader) + (size_t)n_sel * proc_record_bytes(p->T.rx_cap, (uint32_t)image_round16(max_pay));
+  return proc_image_bytes(n_sel, p->T.rx_cap, (uint32_t)image_round16(max_pay));
 }
 
 int fskhip_processor_snapshot(fskhip_processor *p, const int64_t *sel, uint32_t n_sel, void *buf, size_t cap, size_t *written) {
@@ -92,11 +92,10 @@ int fskhip_processor_snapshot(fskhip_processor *p, const int64_t *sel, uint32_t 
   uint32_t max_pay = 0;
   if (const int rc = max_pending_payload(who, p, sel, n_sel, &max_pay)) return rc;
   const uint32_t pay_cap = (uint32_t)image_round16(max_pay);
-  const size_t rec_bytes = proc_record_bytes(p->T.rx_cap, pay_cap), need = sizeof(ProcHeader) + (size_t)n_sel * rec_bytes;
+  const size_t rec_bytes = proc_record_bytes(p->T.rx_cap, pay_cap), need = proc_image_bytes(n_sel, p->T.rx_cap, pay_cap);
   if (const int rc = check_room(who, n_sel, need, buf, cap, written)) return rc;
 
-  ProcHeader h = image_header<ProcHeader>(kProcMagic, kProcFormat);
-  h.record_bytes = (uint32_t)rec_bytes; h.n_records = n_sel; h.rx_capacity = p->T.rx_cap; h.payload_capacity = pay_cap;
+  ProcHeader h = proc_image_header(n_sel, p->T.rx_cap, pay_cap);
   unsigned char *rec = (unsigned char *)buf + sizeof(ProcHeader);
   SnapSum sum;
   snap_sum(sum, &h, sizeof(h));   // (checksum field still 0)
@@ -121,6 +120,13 @@ int fskhip_processor_snapshot_info_get(const void *buf, size_t size, fskhip_proc
   std::memset(info, 0, sizeof(*info));
   info->n_streams = s.h.n_records; info->rx_capacity = s.h.rx_capacity; info->payload_capacity = s.h.payload_capacity;
   info->record_bytes = s.h.record_bytes;
+  return FSKHIP_OK;
+}
+
+int fskhip_processor_snapshot_concat(const void *const *bufs, const size_t *sizes, uint32_t n, void *out, size_t cap, size_t *written) {
+  static_assert(kProcConcatInvalid == FSKHIP_E_INVALID && kProcConcatOverflow == FSKHIP_E_OVERFLOW, "proc_image_concat returns the ABI's codes");
+  char msg[512] = "";
+  if (const int rc = proc_image_concat(bufs, sizes, n, out, cap, written, msg, sizeof(msg))) return fail(rc, "fskhip_processor_snapshot_concat: %s", msg);
   return FSKHIP_OK;
 }
 

@@ -66,12 +66,66 @@ class ChunkedModulator:
 ProcessorBatchSnapshot = collections.namedtuple("ProcessorBatchSnapshot", ["engine", "processor"])
 
 
+def processor_snapshot_concat(blobs):
+    """fskhip_processor_snapshot_concat: one processor snapshot holding the records of `blobs` in order, in canonical form -- byte
+    for byte the image one processor holding the same streams writes (host only, no device needed).  `bytes`."""
+    bs = [_blob(b) for b in blobs]
+    L = _lib.lib()
+    ptrs = (C.c_void_p * len(bs))(*[b.ctypes.data for b in bs])
+    sizes = (C.c_size_t * len(bs))(*[b.nbytes for b in bs])
+    need = C.c_size_t(0)
+    rc = L.fskhip_processor_snapshot_concat(ptrs, sizes, len(bs), None, 0, C.byref(need))
+    if rc != _lib.E_OVERFLOW:
+        _lib.check(rc)
+    out = np.zeros(need.value, np.uint8)
+    _lib.check(L.fskhip_processor_snapshot_concat(ptrs, sizes, len(bs), out.ctypes.data, out.nbytes, C.byref(need)))
+    return out.tobytes()
+
+
 def processor_snapshot_info(blob):
     """fskhip_processor_snapshot_info_get: what a processor snapshot holds (validated on the host, no device needed)"""
     b = _blob(blob)
     info = _lib.ProcessorSnapshotInfo()
     _lib.check(_lib.lib().fskhip_processor_snapshot_info_get(b.ctypes.data, b.nbytes, C.byref(info)))
     return _struct_dict(info)
+
+
+def rate_handle_check(handle, kind, what, n_streams, device):
+    """a side's resampler (filters.Upsampler / Downsampler; `kind`) or the converter of its direction, as a batch of n_streams
+    streams on `device` (None: not known) takes it: ValueError otherwise.  FSKProcessorBatch's check, and each shard's of
+    FSKProcessorBatchSharded."""
+    from . import filters
+    converter = {filters.Upsampler: filters.CaptureConverter, filters.Downsampler: filters.PlaybackConverter}[kind]
+    if not isinstance(handle, (kind, converter)):     # (a converter of the side's direction stands in its resampler's place)
+        raise ValueError("%s must be a filters.%s, got %s" % (what, kind.__name__, type(handle).__name__))
+    if handle.n_streams != n_streams:
+        raise ValueError("%s has %d streams, the batch %d" % (what, handle.n_streams, n_streams))
+    if device is not None and handle.device != device:
+        raise ValueError("%s is on device %r, the batch on %r" % (what, handle.device, device))
+
+
+def rate_call_kind(upsampler, n_in, downsampler, n_out, any_length=False):
+    """which library call a rate quantum with these handles is (None: the side has no samples): "rate" for resamplers, "ratecvt"
+    for converters, whose counts are whole periods, "ratecvt_any" for converters and counts of any length (any_length; a resampler
+    in a slot is a TypeError).  One call takes one kind."""
+    from . import filters
+    if any_length:
+        for what, h in (("upsampler", upsampler), ("downsampler", downsampler)):
+            if h is not None and not isinstance(h, filters._RateConverter):
+                raise TypeError("%s is a %s: quanta of any length go through rate converters (filters.CaptureConverter / PlaybackConverter)"
+                                % (what, type(h).__name__))
+        return "ratecvt_any"
+    kinds = [isinstance(h, filters._RateConverter) for h in (upsampler, downsampler) if h is not None]
+    if len(set(kinds)) > 1:
+        raise ValueError("upsampler is a %s and downsampler a %s: one call takes resamplers or rate converters, not one of each"
+                         % (type(upsampler).__name__, type(downsampler).__name__))
+    if not any(kinds):
+        return "rate"
+    if upsampler is not None and n_in % upsampler.down:
+        raise ValueError("%d samples per stream are not a multiple of the converter's down factor %d" % (n_in, upsampler.down))
+    if downsampler is not None and n_out % downsampler.up:
+        raise ValueError("n_out %d is not a multiple of the converter's up factor %d" % (n_out, downsampler.up))
+    return "ratecvt"
 
 
 class FSKProcessorBatch:
@@ -162,8 +216,13 @@ class FSKProcessorBatch:
         return nxt
 
     # ---- process(inputs, outputs) fsk-processor.ts:152-167 -----------------------------------------
-    def process(self, inputs=None, n_out=0):
-        """inputs: float32 [S, n_in] or None; returns float32 [S, n_out] (or None when n_out == 0)."""
+    def process(self, inputs=None, n_out=0, out=None):
+        """inputs: float32 [S, n_in] or None; returns float32 [S, n_out] (or None when n_out == 0).  out: the float32 [S, n_out]
+        array to write and return instead of a new one -- its rows may be a block of a wider array (engine.samples_out: anything
+        whose dtype, shape or pitch the call cannot express is a ValueError, raised before the call is counted)."""
+        out_pitch = n_out
+        if out is not None or n_out:
+            out, _code, _lay, out_pitch = self._out_array(out, "f32", "stream", n_out)
         x = None
         n_in = 0
         if inputs is not None:
@@ -172,12 +231,17 @@ class FSKProcessorBatch:
                 raise ValueError("inputs must be [n_streams, n]")
             n_in = x.shape[1]
             self.processDemodulationCallCount += 1
-        out = np.zeros((self.n_streams, n_out), dtype=np.float32) if n_out else None
         # the host form stages through the processor's own stream, which a graph capture needs anyway
         _lib.check(self._L.fskhip_processor_process_host(
             self._h, x.ctypes.data if x is not None else None, n_in, n_in,
-            out.ctypes.data if out is not None else None, n_out, n_out, self.flags))
+            out.ctypes.data if out is not None else None, n_out, out_pitch, self.flags))
         return out
+
+    def _out_array(self, out, out_fmt, out_layout, n_out):
+        """engine.samples_out for a quantum's output: a new array, or the caller's `out` checked -- which has to go with an n_out"""
+        if out is not None and not n_out:
+            raise ValueError("out was given, but n_out is 0: the call writes nothing")
+        return samples_out(out_fmt, out_layout, self.n_streams, int(n_out), out)
 
     def graph_stats(self):
         """fskhip_processor_graph_stats: (captures, replays) -- the quanta use_graph captured afresh and the quanta that replayed
@@ -197,12 +261,14 @@ class FSKProcessorBatch:
         _lib.check(self._L.fskhip_processor_process_device(self._h, d_in, n_in, in_pitch, d_out, n_out, out_pitch,
                                                            self.flags if flags is None else flags, stream))
 
-    def process_samples(self, inputs=None, in_fmt="f32", in_layout="stream", n_out=0, out_fmt="f32", out_layout="stream"):
+    def process_samples(self, inputs=None, in_fmt="f32", in_layout="stream", n_out=0, out_fmt="f32", out_layout="stream", out=None):
         """process() with either side in a capture format (SAMPLE_FORMATS: "f32", "s16", "mulaw", "alaw") and layout
         (SAMPLE_LAYOUTS: "stream" = [S, n], "sample" = [n, S], interleaved frames): fskhip_processor_process_fmt_host.  inputs: an
         array of in_fmt's dtype in in_layout's shape (rows may be a block of a wider array, whose other columns are ignored), or
         None; returns an array of out_fmt's dtype, [S, n_out] or [n_out, S] (None when n_out == 0).  The samples cross PCIe as
-        they are; the state ends as process() leaves it on the decoded floats, the output is process()'s, encoded."""
+        they are; the state ends as process() leaves it on the decoded floats, the output is process()'s, encoded.  out: the
+        array of out_fmt's dtype and out_layout's shape to write and return instead of a new one; its rows may be a block of a
+        wider array -- a shard's column block of interleaved frames, at the full frame pitch (process(): a ValueError otherwise)."""
         in_code, in_lay = _sample_codes(in_fmt, in_layout)
         out_code, out_lay = _sample_codes(out_fmt, out_layout)      # (every argument check comes before the call is counted)
         x, n_in, in_pitch = None, 0, 0
@@ -212,10 +278,11 @@ class FSKProcessorBatch:
                 in_pitch = max(x.shape[1], 1)
             if S != self.n_streams:
                 raise ValueError("inputs must be [n_streams, n] (layout 'stream') or [n, n_streams] (layout 'sample')")
+        out_pitch = 0
+        if out is not None or n_out:
+            out, out_code, out_lay, out_pitch = self._out_array(out, out_fmt, out_layout, n_out)
+        if inputs is not None:
             self.processDemodulationCallCount += 1
-        out, out_pitch = None, 0
-        if n_out:
-            out, out_code, out_lay, out_pitch = samples_out(out_fmt, out_layout, self.n_streams, int(n_out))
         _lib.check(self._L.fskhip_processor_process_fmt_host(
             self._h, x.ctypes.data if x is not None else None, in_code, in_lay, n_in, in_pitch,
             out.ctypes.data if out is not None else None, out_code, out_lay, int(n_out), out_pitch, self.flags))
@@ -230,15 +297,7 @@ class FSKProcessorBatch:
     def _rate_handle(self, handle, kind, what):
         """a side's resampler (filters.Upsampler / Downsampler) as fskhip_processor_process_rate_* wants it: of this batch's
         stream count and on its engine's device"""
-        from . import filters
-        converter = {filters.Upsampler: filters.CaptureConverter, filters.Downsampler: filters.PlaybackConverter}[kind]
-        if not isinstance(handle, (kind, converter)):     # (a converter of the side's direction stands in its resampler's place)
-            raise ValueError("%s must be a filters.%s, got %s" % (what, kind.__name__, type(handle).__name__))
-        if handle.n_streams != self.n_streams:
-            raise ValueError("%s has %d streams, the batch %d" % (what, handle.n_streams, self.n_streams))
-        device = getattr(self.engine, "device", None)
-        if device is not None and handle.device != device:
-            raise ValueError("%s is on device %r, the batch on %r" % (what, handle.device, device))
+        rate_handle_check(handle, kind, what, self.n_streams, getattr(self.engine, "device", None))
         return handle._h
 
     def _rate_entry(self, form, upsampler, n_in, downsampler, n_out, any_length=False):
@@ -246,27 +305,10 @@ class FSKProcessorBatch:
         fskhip_processor_process_rate_* for resamplers, fskhip_processor_process_ratecvt_* for converters (filters.CaptureConverter /
         PlaybackConverter), whose counts are whole periods.  One call takes one kind.  any_length: the converters' call for
         counts of any length, fskhip_processor_process_ratecvt_any_*; a resampler in a slot is a TypeError."""
-        from . import filters
-        if any_length:
-            for what, h in (("upsampler", upsampler), ("downsampler", downsampler)):
-                if h is not None and not isinstance(h, filters._RateConverter):
-                    raise TypeError("%s is a %s: quanta of any length go through rate converters (filters.CaptureConverter / PlaybackConverter)"
-                                    % (what, type(h).__name__))
-            return getattr(self._L, "fskhip_processor_process_ratecvt_any_" + form)
-        kinds = [isinstance(h, filters._RateConverter) for h in (upsampler, downsampler) if h is not None]
-        if len(set(kinds)) > 1:
-            raise ValueError("upsampler is a %s and downsampler a %s: one call takes resamplers or rate converters, not one of each"
-                             % (type(upsampler).__name__, type(downsampler).__name__))
-        if not any(kinds):
-            return getattr(self._L, "fskhip_processor_process_rate_" + form)
-        if upsampler is not None and n_in % upsampler.down:
-            raise ValueError("%d samples per stream are not a multiple of the converter's down factor %d" % (n_in, upsampler.down))
-        if downsampler is not None and n_out % downsampler.up:
-            raise ValueError("n_out %d is not a multiple of the converter's up factor %d" % (n_out, downsampler.up))
-        return getattr(self._L, "fskhip_processor_process_ratecvt_" + form)
+        return getattr(self._L, "fskhip_processor_process_%s_%s" % (rate_call_kind(upsampler, n_in, downsampler, n_out, any_length), form))
 
     def process_samples_at(self, inputs=None, in_fmt="mulaw", in_layout="sample", upsampler=None, n_out=0, out_fmt="mulaw", out_layout="sample",
-                           downsampler=None):
+                           downsampler=None, out=None):
         """process_samples() with both sides at the trunk's own rate: fskhip_processor_process_rate_host.  inputs (or None) are
         low rate samples, interpolated on the device by `upsampler` (filters.Upsampler) in front of the demodulator; the n_out
         returned samples are the pending modulation decimated by `downsampler` (filters.Downsampler), which one kernel generates,
@@ -278,10 +320,10 @@ class FSKProcessorBatch:
         converters' outer rate -- 44.1 kHz either side of a 48 kHz engine -- through fskhip_processor_process_ratecvt_host: the
         inputs are a multiple of the capture converter's `down` samples per stream, n_out a multiple of the playback
         converter's `up`, and the state ends as CaptureConverter.process -> process() -> PlaybackConverter.process leaves it,
-        bit for bit.  One call takes resamplers or converters, not one of each."""
-        return self._samples_at(False, inputs, in_fmt, in_layout, upsampler, n_out, out_fmt, out_layout, downsampler)
+        bit for bit.  One call takes resamplers or converters, not one of each.  out: as in process_samples()."""
+        return self._samples_at(False, inputs, in_fmt, in_layout, upsampler, n_out, out_fmt, out_layout, downsampler, out)
 
-    def _samples_at(self, any_length, inputs, in_fmt, in_layout, upsampler, n_out, out_fmt, out_layout, downsampler):
+    def _samples_at(self, any_length, inputs, in_fmt, in_layout, upsampler, n_out, out_fmt, out_layout, downsampler, out=None):
         """process_samples_at (any_length False) and process_samples_at_any: the host form behind their argument checks"""
         from . import filters
         in_code, in_lay = _sample_codes(in_fmt, in_layout)
@@ -297,9 +339,9 @@ class FSKProcessorBatch:
         if n_out:
             down_h = self._rate_handle(downsampler, filters.Downsampler, "downsampler")
         entry = self._rate_entry("host", upsampler if inputs is not None else None, n_in, downsampler if n_out else None, int(n_out), any_length)
-        out, out_pitch = None, 0
-        if n_out:
-            out, out_code, out_lay, out_pitch = samples_out(out_fmt, out_layout, self.n_streams, int(n_out))
+        out_pitch = 0
+        if out is not None or n_out:
+            out, out_code, out_lay, out_pitch = self._out_array(out, out_fmt, out_layout, n_out)
         if inputs is not None:
             self.processDemodulationCallCount += 1
         _lib.check(entry(
@@ -308,15 +350,15 @@ class FSKProcessorBatch:
         return out
 
     def process_samples_at_any(self, inputs=None, in_fmt="mulaw", in_layout="sample", upsampler=None, n_out=0, out_fmt="mulaw", out_layout="sample",
-                               downsampler=None):
+                               downsampler=None, out=None):
         """process_samples_at() through a filters.CaptureConverter and a filters.PlaybackConverter for quanta of any length -- a
         WebAudio render quantum of 128 frames at 44.1 kHz as it arrives: fskhip_processor_process_ratecvt_any_host.  The handles
         carry their positions (filters: `position`) from call to call beside their histories; the state ends as
         CaptureConverter.process_any -> process() with the engine counts the handles give (upsampler.out_count_any(n),
         downsampler.in_count_any(n_out); a side with none is left out) -> PlaybackConverter.process_any leaves it, bit for bit.
         An n_out that the playback converter cannot write from its position (only where its up > down) is the library's refusal.
-        A resampler in a slot is a TypeError."""
-        return self._samples_at(True, inputs, in_fmt, in_layout, upsampler, n_out, out_fmt, out_layout, downsampler)
+        A resampler in a slot is a TypeError.  out: as in process_samples()."""
+        return self._samples_at(True, inputs, in_fmt, in_layout, upsampler, n_out, out_fmt, out_layout, downsampler, out)
 
     def process_samples_at_any_device(self, d_in, in_fmt, in_layout, n_in, in_pitch, upsampler, d_out, out_fmt, out_layout, n_out, out_pitch, downsampler,
                                       stream=None, flags=None):
