@@ -667,6 +667,82 @@ int fskhip_xmodem_recv_snapshot(fskhip_xmodem_recv *r, const int64_t *sel, uint3
 int fskhip_xmodem_recv_restore(fskhip_xmodem_recv *dst, const void *buf, size_t size, const int64_t *map, uint32_t n_map);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The resident XModem wait timers (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): the `timeoutMs` timers of sendData() and
+ * receiveData(), kept on the device for every stream of a file receiver or a sender, in the clock a streaming engine has: the
+ * engine samples it has processed (timeoutMs 3000 is 144 000 samples at 48 kHz).  The polls above leave the timers to the host,
+ * as masks; a host can only build those masks by reading state words and ring lengths back on every quantum.  A timer handle
+ * builds them on the device instead and feeds them to the handle's own poll, so a transfer recovers from a lost packet without
+ * the host looking at any per-stream word.  The polls, their events, the step rules and the image formats are unchanged; the
+ * external abort signal stays with the host, as the polls' abort mask.
+ *
+ * State per stream, kept with the timer handle: waited (engine samples the current wait has lasted, saturating at 2^32 - 1) and
+ * mark (bits 0-1: the stage the timer was armed for, 0..2, always 0 for a sender; bit 2, value 4: was-pending).  fskhip_xmodem_*_remap,
+ * _snapshot and _restore do NOT carry them: state_get on the old timer, take the words by the same map (-1: 0 and 0, a fresh
+ * timer), state_set on a new timer over the new handle.
+ *
+ * fskhip_xmodem_timer_create_recv / _create_tx  a timer over a file receiver / a sender, every stream waited 0, mark 0;
+ *                           timeout_samples is timeoutMs in engine samples.  Allocates the _host forms' staging for n_streams
+ *                           events, so that no poll allocates.  Several timers over one handle are independent.
+ * fskhip_xmodem_timer_reset   waited 0, mark 0 for one stream or all (stream < 0).
+ * fskhip_xmodem_timer_state_get / _state_set  the two arrays ([n_streams] each, either pointer may be NULL).  state_set validates
+ *                           before it sets anything and names the first bad stream: a mark with other bits than these, a
+ *                           stage above 2, a stage on a sender's timer.
+ * These synchronise with the processor's outstanding work.  The timer must be destroyed BEFORE its receiver or sender; one whose
+ * handle was destroyed first refuses every call but _destroy with FSKHIP_E_INVALID.  (Reusing a timer after its own destroy is
+ * undefined, as for every handle here.)
+ *
+ * One timed poll is fire -> the handle's plain poll -> arm.  `elapsed` is the number of engine samples processed since this
+ * timer's previous timed poll; the caller knows it from its own process calls.  The timers are QUANTISED TO THE POLLS: time passes
+ * only as `elapsed`, so a wait ends at the first poll at or after its deadline.  They are meant for one poll per quantum.
+ *   fire, for a stream the poll will select (mask, state not IDLE):
+ *     tx_pending[s] != 0        mark |= 4 and nothing else; flag 0 -- the reference is inside `await sendControl()` / `await
+ *                               modulate()`, where no timer runs.  Time spent pending never counts.
+ *     else, mark & 4 set, or a receiver in SEND_NAK / SEND_ACK: the wait begins at this poll: waited = 0, mark = 0.
+ *     else                      waited = min(waited + elapsed, 2^32 - 1).
+ *     flag = waited >= timeout_samples.
+ *   the poll.  A receiver takes the flags as its timeout mask and `abort` as it is.  A sender takes (flag | abort[s]) as its abort
+ *   mask: a sender's timeout is 'Operation aborted' with nothing retried (the sender's rule 1).
+ *   arm, only if the poll was committed; a poll that stood down (FSKHIP_E_OVERFLOW, d_totals[2] == 0) has fire's changes undone, so
+ *   it changes no word of the timer either.  For a selected stream:
+ *     state IDLE after the poll: waited = 0, mark = 0 (pending or not: an abort ends a pending stream too).
+ *     otherwise a stream that was pending at fire is left alone, and for the others
+ *     receiver   stage = 0 with no live ring byte left, 1 with fewer than 4 (an SOH is at the front), 2 with 4 or more -- the waits at
+ *                xmodem.ts:238 / 267 / 279, 311.  waited = 0 if the stream was listed (something was transmitted), or the poll
+ *                took bytes out of the ring without listing it (noise ends a waitForByte and the loop arms a new one,
+ *                xmodem.ts:247-250), or the stage rose.  Payload bytes that trickle in inside stage 2 do not re-arm.  mark's
+ *                stage = stage.
+ *     sender     waited = 0 if the event has sent_len != 0 or a status other than PROGRESS, or returned an EOT in WAIT_ACK (each
+ *                turn of that loop arms its own timer, xmodem.ts:137-151).  A skipped ACK / EOT in WAIT_NAK, anything in
+ *                WAIT_FINAL_ACK and bytes that are no control bytes leave the timer running: one waitAndSkipForControl /
+ *                waitForACK keeps one timer (xmodem.ts:111, 174).
+ * A stream that is not selected is not touched in any word.  The events, the lists, the overflow rule and d_totals are the plain
+ * polls'.  _device queues fire, fskhip_xmodem_*_poll_device and arm on `hip_stream` with no host synchronisation between them;
+ * _host is the same with the lists copied back at the end.  The timer keeps scratch, and reads the handle's: one poll at a time
+ * per handle, timed or plain.
+ * FSKHIP_E_INVALID before any device call.  create: a null handle or out; timeout_samples 0.  The timed polls: the plain polls'
+ * refusals in their order with the timer in the handle's place (null n_events / d_totals; a null streams or events with
+ * cap_streams != 0; a null timer); then a timer whose handle is gone; a receiver's timer given to the sender's poll or the other
+ * way round.  reset, state_get, state_set: a null timer, a timer whose handle is gone (reset: then a stream out of range).
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct fskhip_xmodem_timer fskhip_xmodem_timer;
+int fskhip_xmodem_timer_create_recv(fskhip_xmodem_recv *r, uint32_t timeout_samples, fskhip_xmodem_timer **out);
+int fskhip_xmodem_timer_create_tx(fskhip_xmodem_tx *t, uint32_t timeout_samples, fskhip_xmodem_timer **out);
+int fskhip_xmodem_timer_destroy(fskhip_xmodem_timer *w);
+int fskhip_xmodem_timer_reset(fskhip_xmodem_timer *w, int64_t stream);
+int fskhip_xmodem_timer_state_get(fskhip_xmodem_timer *w, uint32_t *waited, uint32_t *mark);
+int fskhip_xmodem_timer_state_set(fskhip_xmodem_timer *w, const uint32_t *waited, const uint32_t *mark);
+int fskhip_xmodem_recv_poll_timed_host(fskhip_xmodem_timer *w, uint32_t elapsed, const uint8_t *mask, const uint8_t *abort,
+                                       uint32_t *streams, fskhip_xmodem_recv_event *events, uint32_t cap_streams, uint32_t *n_events);
+int fskhip_xmodem_recv_poll_timed_device(fskhip_xmodem_timer *w, uint32_t elapsed, const uint8_t *d_mask, const uint8_t *d_abort,
+                                         uint32_t *d_streams, fskhip_xmodem_recv_event *d_events, uint32_t cap_streams,
+                                         uint32_t *d_totals, void *hip_stream);
+int fskhip_xmodem_tx_poll_timed_host(fskhip_xmodem_timer *w, uint32_t elapsed, const uint8_t *mask, const uint8_t *abort,
+                                     uint32_t *streams, fskhip_xmodem_tx_event *events, uint32_t cap_streams, uint32_t *n_events);
+int fskhip_xmodem_tx_poll_timed_device(fskhip_xmodem_timer *w, uint32_t elapsed, const uint8_t *d_mask, const uint8_t *d_abort,
+                                       uint32_t *d_streams, fskhip_xmodem_tx_event *d_events, uint32_t cap_streams,
+                                       uint32_t *d_totals, void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * FIR half of src/dsp/filters.ts: FIRFilter (112-167) batched over streams, and the windowed-sinc designs
  * (243-314) + FilterFactory.createFIR* (346-368).
  * ------------------------------------------------------------------------------------------------- */

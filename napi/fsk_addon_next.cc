@@ -29,6 +29,9 @@
 //   xmodemRecvFiles(handle, sel: Uint32Array) -> {offsets: Float64Array[n + 1], data: Uint8Array}
 //   xmodemRecvSetFiles(handle, sel: Uint32Array, offsets: Uint32Array[n + 1], data: Uint8Array)
 //   xmodemRecvState(handle) -> {state, expected, retries, fileLen, packetsReceived, dropped, packetsSent: Uint32Array};  xmodemRecvSetState(handle, the seven|null)
+//   xmodemTimerCreate(overReceiver: boolean, recv or tx handle, timeoutSamples) -> handle;  xmodemTimerDestroy(handle);  xmodemTimerReset(handle, stream)
+//   xmodemTimerPoll(handle, elapsed, mask, abort: Uint8Array|null) -> what xmodemRecvPoll / xmodemTxPoll return
+//   xmodemTimerState(handle) -> {waited, mark: Uint32Array};  xmodemTimerSetState(handle, waited|null, mark|null)
 //   xmodem{Rx,Tx,Recv}Remap(dst, src, map: number[]);  xmodem{Rx,Tx,Recv}Snapshot(handle, sel: number[]|null) -> Buffer
 //   xmodem{Rx,Tx,Recv}Restore(dst, snapshot: Uint8Array, map: number[]);  xmodemSnapshotInfo(snapshot) -> {kind, nStreams, param0, param1, fileBytes}
 //   processorRemap(dst, src, map: number[]);  processorSnapshot(handle, sel: number[]|null) -> Buffer
@@ -769,6 +772,126 @@ napi_value XmodemRecvSetState(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// ---- the resident XModem wait timers (include/fskhip_next.h: fskhip_xmodem_timer_*) over a file receiver's or a sender's handle
+struct XmTimer { fskhip_xmodem_timer *w; uint32_t S; bool recv; };
+void xm_timer_finalize(napi_env, void *data, void *) {
+  XmTimer *h = (XmTimer *)data;
+  if (h->w) fskhip_xmodem_timer_destroy(h->w);
+  delete h;
+}
+XmTimer *get_xm_timer(napi_env env, napi_value v) {
+  XmTimer *h = (XmTimer *)external(env, v, "timers destroyed");
+  if (h && !h->w) { napi_throw_error(env, nullptr, "timers destroyed"); return nullptr; }
+  return h;
+}
+napi_value XmodemTimerCreate(napi_env env, napi_callback_info info) {
+  ARGS(3);
+  bool recv = false;
+  napi_get_value_bool(env, argv[0], &recv);
+  uint32_t timeout_samples = 0, S = 0;
+  napi_get_value_uint32(env, argv[2], &timeout_samples);
+  fskhip_xmodem_timer *w = nullptr;
+  int rc;
+  if (recv) {
+    XmRecv *r = get_xm_recv(env, argv[1]);
+    if (!r) return nullptr;
+    S = r->S;
+    rc = fskhip_xmodem_timer_create_recv(r->r, timeout_samples, &w);
+  } else {
+    XmTx *t = get_xm_tx(env, argv[1]);
+    if (!t) return nullptr;
+    S = t->S;
+    rc = fskhip_xmodem_timer_create_tx(t->t, timeout_samples, &w);
+  }
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  XmTimer *h = new XmTimer{w, S, recv};
+  napi_value ext;
+  if (napi_create_external(env, h, xm_timer_finalize, nullptr, &ext) != napi_ok) { xm_timer_finalize(env, h, nullptr); napi_throw_error(env, nullptr, "xmodemTimerCreate: no handle"); return nullptr; }
+  return ext;
+}
+napi_value XmodemTimerDestroy(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  void *q = nullptr;
+  if (napi_get_value_external(env, argv[0], &q) == napi_ok && q) {
+    XmTimer *h = (XmTimer *)q;
+    if (h->w) fskhip_xmodem_timer_destroy(h->w);
+    h->w = nullptr;
+  }
+  return nullptr;
+}
+// sized with a query call (an overflowing timed poll changes nothing, the timers included), then polled into arrays of exactly that size
+napi_value XmodemTimerPoll(napi_env env, napi_callback_info info) {
+  ARGS(4);
+  XmTimer *h = get_xm_timer(env, argv[0]);
+  if (!h) return nullptr;
+  uint32_t elapsed = 0;
+  napi_get_value_uint32(env, argv[1], &elapsed);
+  void *mask, *abort_; size_t mlen, alen;
+  if (!typed(env, argv[2], napi_uint8_array, &mask, &mlen, true) || !typed(env, argv[3], napi_uint8_array, &abort_, &alen, true)) return nullptr;
+  if ((mask && mlen != h->S) || (abort_ && alen != h->S)) { napi_throw_range_error(env, nullptr, "xmodemTimerPoll: mask and abort must have one entry per stream"); return nullptr; }
+  const size_t words = h->recv ? 12 : 8;
+  auto poll = [&](void *streams, void *events, uint32_t cap, uint32_t *n_events) {
+    return h->recv ? fskhip_xmodem_recv_poll_timed_host(h->w, elapsed, (const uint8_t *)mask, (const uint8_t *)abort_, (uint32_t *)streams, (fskhip_xmodem_recv_event *)events, cap, n_events)
+                   : fskhip_xmodem_tx_poll_timed_host(h->w, elapsed, (const uint8_t *)mask, (const uint8_t *)abort_, (uint32_t *)streams, (fskhip_xmodem_tx_event *)events, cap, n_events);
+  };
+  uint32_t n_events = 0;
+  int rc = poll(nullptr, nullptr, 0, &n_events);
+  if (rc != FSKHIP_OK && rc != FSKHIP_E_OVERFLOW) return throw_fsk(env, rc);
+  void *streams, *events;
+  napi_value str_v = make_typed(env, napi_uint32_array, n_events, 4, &streams);
+  napi_value ev_v = make_typed(env, napi_int32_array, words * (size_t)n_events, 4, &events);
+  if (!str_v || !ev_v) { napi_throw_error(env, nullptr, "xmodemTimerPoll: out of memory"); return nullptr; }
+  if (rc == FSKHIP_E_OVERFLOW) {
+    rc = poll(streams, events, n_events, &n_events);
+    if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  }
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "streams", str_v);
+  napi_set_named_property(env, o, "events", ev_v);
+  return o;
+}
+napi_value XmodemTimerReset(napi_env env, napi_callback_info info) {
+  ARGS(2);
+  XmTimer *h = get_xm_timer(env, argv[0]);
+  if (!h) return nullptr;
+  int64_t s = -1;
+  napi_get_value_int64(env, argv[1], &s);
+  int rc = fskhip_xmodem_timer_reset(h->w, s);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+napi_value XmodemTimerState(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  XmTimer *h = get_xm_timer(env, argv[0]);
+  if (!h) return nullptr;
+  void *a[2]; napi_value v[2];
+  for (int i = 0; i < 2; i++) {
+    v[i] = make_typed(env, napi_uint32_array, h->S, 4, &a[i]);
+    if (!v[i]) { napi_throw_error(env, nullptr, "xmodemTimerState: out of memory"); return nullptr; }
+  }
+  int rc = fskhip_xmodem_timer_state_get(h->w, (uint32_t *)a[0], (uint32_t *)a[1]);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "waited", v[0]);
+  napi_set_named_property(env, o, "mark", v[1]);
+  return o;
+}
+napi_value XmodemTimerSetState(napi_env env, napi_callback_info info) {
+  ARGS(3);
+  XmTimer *h = get_xm_timer(env, argv[0]);
+  if (!h) return nullptr;
+  void *a[2]; size_t n[2];
+  for (int i = 0; i < 2; i++) {
+    if (!typed(env, argv[1 + i], napi_uint32_array, &a[i], &n[i], true)) return nullptr;
+    if (a[i] && n[i] != h->S) { napi_throw_range_error(env, nullptr, "xmodemTimerSetState: state arrays must have one entry per stream"); return nullptr; }
+  }
+  int rc = fskhip_xmodem_timer_state_set(h->w, (const uint32_t *)a[0], (const uint32_t *)a[1]);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  return nullptr;
+}
+
 // ---- processor remap / snapshots (include/fskhip_next.h): a snapshot is a Buffer (or any Uint8Array) on this side
 napi_value ProcessorRemap(napi_env env, napi_callback_info info) {
   ARGS(3);
@@ -1483,6 +1606,12 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"xmodemRecvSetFiles", nullptr, XmodemRecvSetFiles, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"xmodemRecvState", nullptr, XmodemRecvState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"xmodemRecvSetState", nullptr, XmodemRecvSetState, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTimerCreate", nullptr, XmodemTimerCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTimerDestroy", nullptr, XmodemTimerDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTimerPoll", nullptr, XmodemTimerPoll, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTimerReset", nullptr, XmodemTimerReset, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTimerState", nullptr, XmodemTimerState, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTimerSetState", nullptr, XmodemTimerSetState, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRemap", nullptr, ProcessorRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorSnapshot", nullptr, ProcessorSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"processorRestore", nullptr, ProcessorRestore, nullptr, nullptr, nullptr, napi_default, nullptr},

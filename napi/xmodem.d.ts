@@ -138,3 +138,22 @@ export declare class XModemFileReceiverBatch {
 export interface XModemSnapshotInfo { kind: 1 | 2 | 3; nStreams: number; param0: number; param1: number; fileBytes: number; }
 /** what an XModem snapshot holds, after validating all of it on the host */
 export declare function xmodemSnapshotInfo(buf: Uint8Array): XModemSnapshotInfo;
+
+export interface XModemTimersState { waited: Uint32Array; mark: Uint32Array; }
+/** the timeoutMs timers of sendData() / receiveData() for every stream of a file receiver or a sender, resident on the device in the
+ * engine's sample clock (fskhip_xmodem_timer_*); quantised to the polls: poll once per quantum.  Close it before its handle. */
+export declare class XModemTimers {
+  /** timeoutSamples (default 144000: 3000 ms at 48 kHz), or timeoutMs with sampleRate (default 48000), rounded up */
+  constructor(handle: XModemFileReceiverBatch | XModemSenderBatch, options?: { timeoutSamples?: number; timeoutMs?: number; sampleRate?: number });
+  readonly nStreams: number;
+  readonly timeoutSamples: number;
+  /** the handle's own poll between a fire and an arm pass; elapsed: the engine samples processed since the previous poll; abort: the external abort */
+  poll(elapsed: number, options?: { mask?: ArrayLike<boolean | number> | null; abort?: ArrayLike<boolean | number> | null }):
+    { streams: Uint32Array; events: FileReceiverEvent[] | SenderEvent[] };
+  /** waited 0, mark 0 for one stream or all (-1) */
+  reset(stream?: number): void;
+  /** waited: samples the current wait has lasted; mark: bits 0-1 the stage the timer was armed for, 4 was-pending */
+  state(): XModemTimersState;
+  setState(state: { [K in keyof XModemTimersState]?: ArrayLike<number> | null }): void;
+  close(): void;
+}

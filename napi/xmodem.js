@@ -142,6 +142,15 @@ function boolArray(who, name, a, n) {
   if (a.length !== n) throw new RangeError(who + ': ' + name + ' must have one entry per stream (' + n + ')');
   return Uint8Array.from(a, (b) => (b ? 1 : 0));
 }
+// what a sender's poll returns, from the addon's {streams, events: Int32Array[8 * n]}
+function txPolled(r) {
+  const events = Array.from(r.streams, (_, i) => {
+    const q = r.events.subarray(i * 8, i * 8 + 8);
+    return { status: q[0], statusName: TX_STATUS[q[0]], error: TX_ERRORS[q[0]], stateAfter: q[1], stateName: TX_STATES[q[1]], control: q[2], sentLen: q[3],
+      sequence: q[4], fragmentIndex: q[5], nFragments: q[6], retries: q[7] };
+  });
+  return { streams: r.streams, events };
+}
 class XModemSenderBatch {
   constructor(processor, options = {}) {
     if (processor === null || typeof processor !== 'object' || !Number.isInteger(processor.nStreams)) throw new TypeError('XModemSenderBatch: processor must be an FSKProcessorBatch');
@@ -181,13 +190,7 @@ class XModemSenderBatch {
   poll(options = {}) {
     if (options === null || typeof options !== 'object') throw new TypeError('poll: options must be an object {mask, abort}');
     const m = boolArray('poll', 'mask', options.mask, this.nStreams), a = boolArray('poll', 'abort', options.abort, this.nStreams);
-    const r = addon.xmodemTxPoll(this.handle, m, a);
-    const events = Array.from(r.streams, (_, i) => {
-      const q = r.events.subarray(i * 8, i * 8 + 8);
-      return { status: q[0], statusName: TX_STATUS[q[0]], error: TX_ERRORS[q[0]], stateAfter: q[1], stateName: TX_STATES[q[1]], control: q[2], sentLen: q[3],
-        sequence: q[4], fragmentIndex: q[5], nFragments: q[6], retries: q[7] };
-    });
-    return { streams: r.streams, events };
+    return txPolled(addon.xmodemTxPoll(this.handle, m, a));
   }
   // reset() (xmodem.ts:370-383) for one stream, or all (-1): IDLE, sequence 1, the file dropped, the counters 0
   reset(stream = -1) {
@@ -210,6 +213,15 @@ const RECV_STATES = ['IDLE', 'RECEIVING_SEND_NAK', 'RECEIVING_WAIT_BLOCK', 'RECE
 const RECV_STATUS = ['progress', 'done', 'max_retries', 'aborted', 'file_full'];
 const RECV_ERRORS = [null, null, 'Receive failed after max retries', 'Operation aborted', 'File store full'];
 const RECV_WORDS = ['state', 'expected', 'retries', 'fileLen', 'packetsReceived', 'dropped', 'packetsSent'];
+// what a file receiver's poll returns, from the addon's {streams, events: Int32Array[12 * n]}
+function recvPolled(r) {
+  const events = Array.from(r.streams, (_, i) => {
+    const q = r.events.subarray(i * 12, i * 12 + 12);
+    return { status: q[0], statusName: RECV_STATUS[q[0]], error: RECV_ERRORS[q[0]], stateAfter: q[1], stateName: RECV_STATES[q[1]], control: q[2], step: q[3],
+      stepName: XM_STATUS[q[3]], seq: q[4], len: q[5], acceptedLen: q[6], fileLen: q[7], expected: q[8], retries: q[9], crcRx: q[10], crcCalc: q[11] };
+  });
+  return { streams: r.streams, events };
+}
 class XModemFileReceiverBatch {
   constructor(processor, options = {}) {
     if (processor === null || typeof processor !== 'object' || !Number.isInteger(processor.nStreams)) throw new TypeError('XModemFileReceiverBatch: processor must be an FSKProcessorBatch');
@@ -234,13 +246,7 @@ class XModemFileReceiverBatch {
   poll(options = {}) {
     if (options === null || typeof options !== 'object') throw new TypeError('poll: options must be an object {mask, timeout, abort}');
     const n = this.nStreams;
-    const r = addon.xmodemRecvPoll(this.handle, boolArray('poll', 'mask', options.mask, n), boolArray('poll', 'timeout', options.timeout, n), boolArray('poll', 'abort', options.abort, n));
-    const events = Array.from(r.streams, (_, i) => {
-      const q = r.events.subarray(i * 12, i * 12 + 12);
-      return { status: q[0], statusName: RECV_STATUS[q[0]], error: RECV_ERRORS[q[0]], stateAfter: q[1], stateName: RECV_STATES[q[1]], control: q[2], step: q[3],
-        stepName: XM_STATUS[q[3]], seq: q[4], len: q[5], acceptedLen: q[6], fileLen: q[7], expected: q[8], retries: q[9], crcRx: q[10], crcCalc: q[11] };
-    });
-    return { streams: r.streams, events };
+    return recvPolled(addon.xmodemRecvPoll(this.handle, boolArray('poll', 'mask', options.mask, n), boolArray('poll', 'timeout', options.timeout, n), boolArray('poll', 'abort', options.abort, n)));
   }
   _sel(who, streams) {
     if (streams === undefined || streams === null) return Uint32Array.from({ length: this.nStreams }, (_, i) => i);
@@ -287,6 +293,52 @@ class XModemFileReceiverBatch {
   }
 }
 
+// The `timeoutMs` timers of sendData() / receiveData() for every stream of an XModemFileReceiverBatch or an XModemSenderBatch, resident
+// on the device in the engine's sample clock (fskhip_xmodem_timer_*): poll(elapsed) is the handle's own poll between a fire and an arm
+// pass, so a receiver's timeout mask and a sender's abort mask are built on the device.  elapsed: the engine samples processed since this
+// object's previous poll.  The timers are quantised to the polls (a wait ends at the first poll at or after its deadline): poll once per
+// quantum.  The external abort stays the caller's (poll(elapsed, {abort})).  remap / snapshot of the handle do not carry the timers:
+// state() here, take by the map (-1: 0, 0), setState() on a new object over the new handle.  Close it before its handle.
+class XModemTimers {
+  constructor(handle, options = {}) {
+    const recv = handle instanceof XModemFileReceiverBatch;
+    if (!recv && !(handle instanceof XModemSenderBatch)) throw new TypeError('XModemTimers: handle must be an XModemFileReceiverBatch or an XModemSenderBatch');
+    if (!handle.handle) throw new Error('XModemTimers: the handle has been closed');
+    if (options === null || typeof options !== 'object') throw new TypeError('XModemTimers: options must be an object {timeoutSamples} or {timeoutMs, sampleRate}');
+    const { timeoutMs, sampleRate = 48000 } = options;
+    const timeoutSamples = timeoutMs === undefined ? (options.timeoutSamples === undefined ? 144000 : options.timeoutSamples) : Math.ceil(timeoutMs * sampleRate / 1000);
+    if (!Number.isInteger(timeoutSamples) || timeoutSamples < 1 || timeoutSamples > 0xffffffff) throw new RangeError('XModemTimers: the timeout must be an integer number of samples in [1, 2^32)');
+    this.over = handle;
+    this.recv = recv;
+    this.nStreams = handle.nStreams;
+    this.timeoutSamples = timeoutSamples;
+    this.handle = addon.xmodemTimerCreate(recv, handle.handle, timeoutSamples);
+  }
+  close() { if (this.handle) { addon.xmodemTimerDestroy(this.handle); this.handle = null; } }
+  _live(who) {
+    if (!this.handle) throw new Error(who + ': the timers have been closed');
+    if (!this.over.handle) throw new Error(who + ": the timers' handle has been closed");
+    return this.handle;
+  }
+  // exactly what the handle's own poll returns
+  poll(elapsed, options = {}) {
+    if (!Number.isInteger(elapsed) || elapsed < 0 || elapsed > 0xffffffff) throw new RangeError('poll: elapsed must be an integer number of samples in [0, 2^32)');
+    if (options === null || typeof options !== 'object') throw new TypeError('poll: options must be an object {mask, abort}');
+    const m = boolArray('poll', 'mask', options.mask, this.nStreams), a = boolArray('poll', 'abort', options.abort, this.nStreams);
+    const r = addon.xmodemTimerPoll(this._live('poll'), elapsed, m, a);
+    return this.recv ? recvPolled(r) : txPolled(r);
+  }
+  reset(stream = -1) {
+    if (!Number.isInteger(stream)) throw new TypeError('reset: stream must be an integer (-1: all)');
+    addon.xmodemTimerReset(this._live('reset'), stream);
+  }
+  state() { return addon.xmodemTimerState(this._live('state')); }   // {waited, mark}: Uint32Array per stream
+  setState(state) {                                                  // what state() returned, or either part of it
+    if (state === null || typeof state !== 'object') throw new TypeError('setState: state must be an object {waited, mark}');
+    addon.xmodemTimerSetState(this._live('setState'), stateArray('waited', state.waited, this.nStreams), stateArray('mark', state.mark, this.nStreams));
+  }
+}
+
 // remap / snapshot / fromSnapshot of the three resident classes: the handle's state follows its streams with the map the engine and
 // the processor were carried with (fskhip_xmodem_{rx,tx,recv}_remap / _snapshot / _restore).  `like(processor)` makes a new object
 // with this one's parameters over the destination processor; `made(processor, info, options)` one with an image's.
@@ -319,4 +371,4 @@ lifecycle(XModemFileReceiverBatch, 'recv', { remap: addon.xmodemRecvRemap, snaps
   (self, p) => new XModemFileReceiverBatch(p, { fileCapacity: self.fileCapacity, maxRetries: self.maxRetries }),
   (p, info, o) => new XModemFileReceiverBatch(p, Object.assign({ fileCapacity: info.param0, maxRetries: info.param1 }, o)));
 
-module.exports = { xmodemSnapshotInfo, XModemReceiverBatch, XModemSenderBatch, XModemFileReceiverBatch, CRC16, XModemPacket, ControlType, PacketConstants, crc16Batch, serializeBatch, scanBursts };
+module.exports = { xmodemSnapshotInfo, XModemReceiverBatch, XModemSenderBatch, XModemFileReceiverBatch, XModemTimers, CRC16, XModemPacket, ControlType, PacketConstants, crc16Batch, serializeBatch, scanBursts };

@@ -229,6 +229,16 @@ _SYMBOLS = [
     ("fskhip_xmodem_recv_reset", C.c_int, [_P, C.c_int64]),
     ("fskhip_xmodem_recv_files_host", C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_size_t, _P]),
     ("fskhip_xmodem_recv_files_set_host", C.c_int, [_P, _P, C.c_uint32, _P, _P]),
+    ("fskhip_xmodem_timer_create_recv", C.c_int, [_P, C.c_uint32, C.POINTER(_P)]),
+    ("fskhip_xmodem_timer_create_tx", C.c_int, [_P, C.c_uint32, C.POINTER(_P)]),
+    ("fskhip_xmodem_timer_destroy", C.c_int, [_P]),
+    ("fskhip_xmodem_timer_reset", C.c_int, [_P, C.c_int64]),
+    ("fskhip_xmodem_timer_state_get", C.c_int, [_P, _P, _P]),
+    ("fskhip_xmodem_timer_state_set", C.c_int, [_P, _P, _P]),
+    ("fskhip_xmodem_recv_poll_timed_host", C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P]),
+    ("fskhip_xmodem_recv_poll_timed_device", C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, _P]),
+    ("fskhip_xmodem_tx_poll_timed_host", C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P]),
+    ("fskhip_xmodem_tx_poll_timed_device", C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, _P]),
     ("fskhip_xmodem_snapshot_info_get", C.c_int, [_P, C.c_size_t, C.POINTER(XModemSnapshotInfo)]),
     ("fskhip_xmodem_rx_remap", C.c_int, [_P, _P, _P, C.c_uint32]),
     ("fskhip_xmodem_rx_snapshot_bytes", C.c_size_t, [_P, _P, C.c_uint32]),

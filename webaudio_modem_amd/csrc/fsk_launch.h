@@ -285,4 +285,24 @@ size_t xmodem_offsets_scratch_words(uint32_t n);
 hipError_t launch_xmodem_file_offsets(const uint32_t *d_len, const int64_t *d_sel, uint32_t n, uint64_t *d_offsets, uint64_t *d_sums, hipStream_t st);
 hipError_t launch_xmodem_recv_spans(const uint32_t *d_len, uint32_t cap, const int64_t *d_sel, uint32_t n, const uint64_t *d_offsets, XmSpan *d_spans,
                                     hipStream_t st);
+// fsk_xmodem_timer.hip: the wait timers around the file receiver's and the sender's poll (fskhip_xmodem_*_poll_timed_*; the rule
+// is fsk_xmodem_timer.h's).  The caller has checked the arguments.
+// XmTimerState: per stream the two words (waited, mark), and as scratch of one timed poll the words before fire (old_waited;
+// saved: the mark, with what fire found the stream to be above it), the ring's live bytes before the poll (held) and the flag
+// byte the poll takes as its timeout mask (receiver) or abort mask (sender).
+// fire: before the poll, d_state the handle's state words; d_abort (sender only, may be null) is OR-ed into the flag.
+// arm: behind the poll's commit on the same stream, d_ev the poll's per-stream event scratch, d_totals the poll's totals: where
+// d_totals[2] is 0 it puts back what fire changed.
+struct XmTimerState {
+  uint32_t *waited, *mark;
+  uint32_t *old_waited, *saved, *held;
+  uint8_t *flag;
+  uint32_t timeout_samples;
+};
+hipError_t launch_xmodem_timer_fire(const XmTimerState &W, bool is_recv, const uint32_t *d_state, const ProcState &T, uint32_t n_streams, const uint8_t *d_mask,
+                                    const uint8_t *d_abort, uint32_t elapsed, hipStream_t st);
+hipError_t launch_xmodem_timer_arm_recv(const XmTimerState &W, const fskhip_xmodem_recv_event *d_ev, const ProcState &T, uint32_t n_streams,
+                                        const uint32_t *d_totals, hipStream_t st);
+hipError_t launch_xmodem_timer_arm_tx(const XmTimerState &W, const fskhip_xmodem_tx_event *d_ev, const ProcState &T, uint32_t n_streams,
+                                      const uint32_t *d_totals, hipStream_t st);
 }  // namespace fsk

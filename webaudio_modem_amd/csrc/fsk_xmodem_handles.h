@@ -9,6 +9,11 @@
 #include "fsk_launch.h"
 #include "fsk_proc.h"
 
+namespace fsk {
+// fsk_xmodem_timer_api.hip: a file receiver or a sender is going away -- the wait timers created over it refuse every call from now on
+void xmodem_timers_orphan(const void *handle);
+}  // namespace fsk
+
 using fsk::XmRxState; using fsk::XmRxScratch; using fsk::XmTxState; using fsk::XmTxScratch; using fsk::XmRecvState; using fsk::XmRecvScratch;
 
 struct fskhip_xmodem_rx {

@@ -46,6 +46,7 @@ extern "C" {
 
 int fskhip_xmodem_recv_destroy(fskhip_xmodem_recv *r) {
   if (!r) return FSKHIP_OK;
+  xmodem_timers_orphan(r);
   (void)hipSetDevice(r->device);
   (void)hipDeviceSynchronize();
   void *bufs[] = {r->X.state, r->X.expected, r->X.retries, r->X.file_len, r->X.packets, r->X.dropped, r->X.sent, r->X.files,

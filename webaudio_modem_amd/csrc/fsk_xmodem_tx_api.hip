@@ -67,6 +67,7 @@ extern "C" {
 
 int fskhip_xmodem_tx_destroy(fskhip_xmodem_tx *t) {
   if (!t) return FSKHIP_OK;
+  xmodem_timers_orphan(t);
   (void)hipSetDevice(t->device);
   (void)hipDeviceSynchronize();
   void *bufs[] = {t->X.state, t->X.sequence, t->X.index, t->X.n_fragments, t->X.retries, t->X.sent, t->X.retransmitted, t->X.file_off, t->X.file_len,

@@ -4,8 +4,9 @@ and error texts, plus the batch forms that actually feed a GPU and `scan_bursts`
 XModemTransport (src/transports/xmodem/xmodem.ts:233-320) applied to the bytes a demodulate call returned; and
 `XModemReceiverBatch`, the same grammar resident on the device over the RX rings of an `FSKProcessorBatch`, and
 `XModemSenderBatch`, `sendData()` for every stream of one: files, packets and the waits' grammar on the device, and
-`XModemFileReceiverBatch`, `receiveData()` for every stream of one: grammar, ACK / NAK, retries and the file on the device.
-All three follow their streams through `remapped`, `snapshot` and `from_snapshot`, as the engine and the processor do.
+`XModemFileReceiverBatch`, `receiveData()` for every stream of one: grammar, ACK / NAK, retries and the file on the device; and
+`XModemTimers`, the wait timers of those two in the engine's sample clock, on the device as well.
+The three resident classes follow their streams through `remapped`, `snapshot` and `from_snapshot`, as the engine and the processor do.
 Everything computes in libfskhip.so; there is no CPU path here.
 """
 import ctypes as C
@@ -578,3 +579,113 @@ class XModemFileReceiverBatch(_Lifecycle):
         if words:
             raise TypeError("unknown state words: %s" % ", ".join(sorted(words)))
         _lib.check(self._L.fskhip_xmodem_recv_state_set(self._h, *[None if a is None else a.ctypes.data for a in arrs]))
+
+
+TIMER_WORDS = ("waited", "mark")
+TIMER_WAS_PENDING = 4   # mark: bits 0-1 the stage the timer was armed for (0..2, a sender's is always 0), bit 2 was-pending
+
+
+class XModemTimers:
+    """The `timeoutMs` timers of sendData() / receiveData() for every stream of an XModemFileReceiverBatch or an XModemSenderBatch,
+    resident on the device in the engine's sample clock (fskhip_xmodem_timer_*): `poll` is the handle's own poll between a fire
+    and an arm pass, so a receiver's timeout mask and a sender's abort mask are built on the device and a lost packet is recovered
+    from without the host reading any per-stream word.  `elapsed` is the engine samples processed since this object's previous
+    poll.  The timers are quantised to the polls (a wait ends at the first poll at or after its deadline): poll once per quantum.
+    The external abort stays the caller's (`abort`).  remapped / snapshot of the handle do not carry the timers: state() here,
+    take by the map (-1: 0, 0), set_state() on a new object over the new handle.  Close it before its handle."""
+
+    def __init__(self, handle, timeout_samples=144000):
+        if isinstance(handle, XModemFileReceiverBatch):
+            kind = "recv"
+        elif isinstance(handle, XModemSenderBatch):
+            kind = "tx"
+        else:
+            raise TypeError("XModemTimers needs an XModemFileReceiverBatch or an XModemSenderBatch")
+        if not getattr(handle, "_h", None):
+            raise ValueError("the handle has been closed")
+        self.handle, self._kind = handle, kind
+        self._L = _lib.lib()
+        self.n_streams = handle.n_streams
+        self.timeout_samples = int(timeout_samples)
+        self._dtype = RECV_EVENT_DTYPE if kind == "recv" else TX_EVENT_DTYPE
+        self._poll = getattr(self._L, "fskhip_xmodem_%s_poll_timed_host" % kind)
+        h = C.c_void_p()
+        _lib.check(getattr(self._L, "fskhip_xmodem_timer_create_" + kind)(handle._h, self.timeout_samples, C.byref(h)))
+        self._h = h
+        self._cap_streams = 0
+
+    @classmethod
+    def from_ms(cls, handle, timeout_ms, sample_rate=48000):
+        """timeoutMs in the engine's clock: timeout_ms * sample_rate / 1000 samples, rounded up"""
+        return cls(handle, timeout_samples=-(-int(timeout_ms) * int(sample_rate) // 1000))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.fskhip_xmodem_timer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not getattr(self, "_h", None):
+            raise ValueError("the timers have been closed")
+        if not getattr(self.handle, "_h", None):
+            raise ValueError("the timers' handle has been closed")
+        return self._h
+
+    def poll(self, elapsed, mask=None, abort=None):
+        """(streams, events), exactly what the handle's own poll returns.  elapsed: engine samples since the previous poll; abort:
+        the streams to abort from outside.  An overflowing call changes nothing, the timers included, and is repeated with
+        larger lists."""
+        h = self._live()
+        if not 0 <= int(elapsed) <= 0xFFFFFFFF:
+            raise ValueError("elapsed must fit 32 bits")
+        m, a = self.handle._mask(mask), self.handle._mask(abort, "abort")
+        ne = C.c_uint32(0)
+        while True:
+            cs = self._cap_streams
+            streams, events = np.zeros(cs, np.uint32), np.zeros(cs, self._dtype)
+            rc = self._poll(h, int(elapsed), None if m is None else m.ctypes.data, None if a is None else a.ctypes.data,
+                            streams.ctypes.data if cs else None, events.ctypes.data if cs else None, cs, C.byref(ne))
+            if rc != _lib.E_OVERFLOW:
+                _lib.check(rc)
+                break
+            self._cap_streams = max(cs, ne.value)
+        return streams[:ne.value], events[:ne.value]
+
+    def poll_active(self, elapsed, mask=None, abort=None):
+        """{stream: event dict} of one poll, as the handle's poll_active gives it"""
+        streams, events = self.poll(elapsed, mask, abort)
+        names = (RECV_STATUS_NAMES, RECV_STATE_NAMES, RECV_STATUS_ERRORS) if self._kind == "recv" else (TX_STATUS_NAMES, TX_STATE_NAMES, TX_STATUS_ERRORS)
+        out = {}
+        for s, e in zip(streams, events):
+            d = {k: int(e[k]) for k in self._dtype.names}
+            d["status_name"], d["state_name"] = names[0][d["status"]], names[1][d["state_after"]]
+            d["error"] = names[2].get(d["status"])
+            out[int(s)] = d
+        return out
+
+    def reset(self, stream=-1):
+        """waited 0, mark 0 for one stream, or all"""
+        _lib.check(self._L.fskhip_xmodem_timer_reset(self._live(), int(stream)))
+
+    def state(self):
+        """{"waited", "mark"}: uint32 arrays, one entry per stream"""
+        out = {k: np.zeros(self.n_streams, np.uint32) for k in TIMER_WORDS}
+        _lib.check(self._L.fskhip_xmodem_timer_state_get(self._live(), *[out[k].ctypes.data for k in TIMER_WORDS]))
+        return out
+
+    def set_state(self, waited=None, mark=None):
+        """what state() returned, or either part of it (validated before anything is set)"""
+        arrs = []
+        for a in (waited, mark):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.uint32)
+                if a.shape != (self.n_streams,):
+                    raise ValueError("state arrays must have one entry per stream")
+            arrs.append(a)
+        _lib.check(self._L.fskhip_xmodem_timer_state_set(self._live(), *[None if a is None else a.ctypes.data for a in arrs]))
