@@ -676,9 +676,9 @@ int fskhip_xmodem_recv_restore(fskhip_xmodem_recv *dst, const void *buf, size_t 
  * external abort signal stays with the host, as the polls' abort mask.
  *
  * State per stream, kept with the timer handle: waited (engine samples the current wait has lasted, saturating at 2^32 - 1) and
- * mark (bits 0-1: the stage the timer was armed for, 0..2, always 0 for a sender; bit 2, value 4: was-pending).  fskhip_xmodem_*_remap,
- * _snapshot and _restore do NOT carry them: state_get on the old timer, take the words by the same map (-1: 0 and 0, a fresh
- * timer), state_set on a new timer over the new handle.
+ * mark (bits 0-1: the stage the timer was armed for, 0..2, always 0 for a sender; bit 2, value 4: was-pending).  The handles' own
+ * fskhip_xmodem_*_remap, _snapshot and _restore do NOT carry them; the timers have their own calls with the same map
+ * (fskhip_xmodem_timer_remap / _snapshot / _restore, below).
  *
  * fskhip_xmodem_timer_create_recv / _create_tx  a timer over a file receiver / a sender, every stream waited 0, mark 0;
  *                           timeout_samples is timeoutMs in engine samples.  Allocates the _host forms' staging for n_streams
@@ -741,6 +741,62 @@ int fskhip_xmodem_tx_poll_timed_host(fskhip_xmodem_timer *w, uint32_t elapsed, c
 int fskhip_xmodem_tx_poll_timed_device(fskhip_xmodem_timer *w, uint32_t elapsed, const uint8_t *d_mask, const uint8_t *d_abort,
                                        uint32_t *d_streams, fskhip_xmodem_tx_event *d_events, uint32_t cap_streams,
                                        uint32_t *d_totals, void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * The wait timers through remap, snapshot and restore (ABI 8, additions; FSKHIP_ABI_VERSION stays 8): the last step of carrying a
+ * live batch.  The caller carries the engine, the processor over it and the file receiver or the sender (fskhip_xmodem_recv_* /
+ * fskhip_xmodem_tx_remap / _snapshot / _restore), creates a FRESH timer over the destination handle and moves the timers' two
+ * words with the SAME map through the calls below.  They never touch the handle or the processor.  The words move on the device;
+ * an image crosses PCIe once.  Synchronous host calls; _remap, _snapshot and _restore synchronise with the processor's outstanding
+ * work, as state_get does (_snapshot_info_get and _snapshot_bytes are host arithmetic).
+ *
+ * _remap: stream i of dst gets waited and mark of stream map[i] of src, verbatim -- a wait that was 2.9 s into a 3 s timeout goes
+ * on from there, and the was-pending bit keeps the time spent inside `await modulate()` from counting.  Where map[i] = -1 the
+ * stream gets 0 and 0, a fresh timer.  A source stream may be named more than once: independent clones.  Source streams that are
+ * not named are dropped.  src is read only and stays usable.
+ * FSKHIP_E_INVALID, with a message naming the first offending index or field and dst left as it was -- everything is validated
+ * before anything is written -- unless: the arguments are non-null and dst != src; neither timer's handle has been destroyed;
+ * n_map == dst's stream count and every entry is in range or -1; dst and src are of the same kind (both over a file receiver, or
+ * both over a sender); dst and src are on the same device; dst is fresh: no timed poll (one that overflowed included: freshness
+ * records that a call was made, not its effect), reset or state_set call yet.  timeout_samples is the new timer's own and is not
+ * compared.  A timer that has been remapped or restored into is STILL fresh: these calls write every stream of dst, so a second
+ * one replaces the first as a whole.  A call that fails later, with FSKHIP_E_HIP or FSKHIP_E_NOMEM from the device, may leave dst's
+ * words partly written: destroy such a timer and create a new one.
+ *
+ * A timer snapshot is a host-side image: plain little-endian bytes, no pointers, every byte defined; two snapshots of the same
+ * words are byte-identical.  An implementation-versioned checkpoint, not an archive.
+ *   header, 48 bytes:  u32 magic "FSKW" (0x574B5346) | u32 format (1) | u32 header_bytes (48) | u32 kind (2 tx, 3 recv: the XModem
+ *                      image's numbers) | u32 n_records | u32 record_words (2) | u32 timeout_samples | u32 0 | u64 checksum | u64 0
+ *     (the XModem image's field offsets).  checksum: the processor snapshot's function over the image's u64 words, with the checksum
+ *     field taken as 0.
+ *   n_records x (u32 waited, u32 mark), one record per selected stream, in selection order; then zero padding to a multiple of 16.
+ * The whole image is 48 + 8 x n_records bytes, rounded up to 16.
+ *
+ * fskhip_xmodem_timer_snapshot_info_get  what an image holds -- on the host, no device needed -- after validating ALL of it; each
+ *                           flaw is FSKHIP_E_INVALID with a message that names it: magic (an "FSKX" image is named as an XModem
+ *                           handle's snapshot), format, header_bytes, kind in {2, 3}, record_words, timeout_samples != 0, the
+ *                           reserved fields zero; the size against the formula above; the checksum; the padding zero; and per
+ *                           record what state_set asks: mark a mark, and stage 0 where the kind is tx.
+ * _snapshot_bytes           the bytes a snapshot of the selected streams takes.  0 for a null timer.
+ * _snapshot                 write streams sel[0 .. n_sel) (sel NULL: all, in order; a stream may be named more than once) into buf.
+ *                           The timer is read only, stays usable and stays fresh.  *written (may be NULL) receives the size; cap
+ *                           too small: FSKHIP_E_OVERFLOW with *written = the size needed and nothing written, so cap 0 is a size
+ *                           query.  FSKHIP_E_INVALID: a null timer, one whose handle is gone, an entry of sel out of range.
+ * _restore                  _remap with the image standing in for src: map[i] names a RECORD, or is -1.  The same-device condition
+ *                           is dropped; the image's kind must be dst's; the image's timeout_samples is not compared; nothing is
+ *                           written before the whole image and map have passed.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct fskhip_xmodem_timer_snapshot_info {
+  uint32_t kind;             /* 2 tx, 3 recv: the numbers fskhip_xmodem_snapshot_info uses */
+  uint32_t n_streams;        /* records in the image */
+  uint32_t timeout_samples;
+  uint32_t reserved;         /* 0 */
+} fskhip_xmodem_timer_snapshot_info;
+int fskhip_xmodem_timer_snapshot_info_get(const void *buf, size_t size, fskhip_xmodem_timer_snapshot_info *info);
+int fskhip_xmodem_timer_remap(fskhip_xmodem_timer *dst, fskhip_xmodem_timer *src, const int64_t *map, uint32_t n_map);
+size_t fskhip_xmodem_timer_snapshot_bytes(const fskhip_xmodem_timer *w, const int64_t *sel, uint32_t n_sel);
+int fskhip_xmodem_timer_snapshot(fskhip_xmodem_timer *w, const int64_t *sel, uint32_t n_sel, void *buf, size_t cap, size_t *written);
+int fskhip_xmodem_timer_restore(fskhip_xmodem_timer *dst, const void *buf, size_t size, const int64_t *map, uint32_t n_map);
 
 /* ---------------------------------------------------------------------------------------------------
  * FIR half of src/dsp/filters.ts: FIRFilter (112-167) batched over streams, and the windowed-sinc designs

@@ -1030,6 +1030,7 @@ napi_value ProcessorSnapshotInfo(napi_env env, napi_callback_info info) {
 XM_LIFECYCLE(Rx, XmRx, get_xm_rx, r, rx)
 XM_LIFECYCLE(Tx, XmTx, get_xm_tx, t, tx)
 XM_LIFECYCLE(Recv, XmRecv, get_xm_recv, r, recv)
+XM_LIFECYCLE(Timer, XmTimer, get_xm_timer, w, timer)   // the wait timers' two words, with the map their handle was carried with
 #undef XM_LIFECYCLE
 
 napi_value XmodemSnapshotInfo(napi_env env, napi_callback_info info) {
@@ -1046,6 +1047,21 @@ napi_value XmodemSnapshotInfo(napi_env env, napi_callback_info info) {
   set_u32(env, o, "param0", si.param0);
   set_u32(env, o, "param1", si.param1);
   set_num(env, o, "fileBytes", (double)si.file_bytes);
+  return o;
+}
+
+napi_value XmodemTimerSnapshotInfo(napi_env env, napi_callback_info info) {
+  ARGS(1);
+  void *data; size_t size;
+  if (!typed(env, argv[0], napi_uint8_array, &data, &size)) return nullptr;
+  fskhip_xmodem_timer_snapshot_info si;
+  int rc = fskhip_xmodem_timer_snapshot_info_get(data, size, &si);
+  if (rc != FSKHIP_OK) return throw_fsk(env, rc);
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  set_u32(env, o, "kind", si.kind);
+  set_u32(env, o, "nStreams", si.n_streams);
+  set_u32(env, o, "timeoutSamples", si.timeout_samples);
   return o;
 }
 
@@ -1627,6 +1643,10 @@ napi_value InitNext(napi_env env, napi_value exports) {
       {"xmodemRecvSnapshot", nullptr, XmodemRecvSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"xmodemRecvRestore", nullptr, XmodemRecvRestore, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"xmodemSnapshotInfo", nullptr, XmodemSnapshotInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTimerRemap", nullptr, XmodemTimerRemap, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTimerSnapshot", nullptr, XmodemTimerSnapshot, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTimerRestore", nullptr, XmodemTimerRestore, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"xmodemTimerSnapshotInfo", nullptr, XmodemTimerSnapshotInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"sincLowpass", nullptr, SincLowpass, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"sincHighpass", nullptr, SincHighpass, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"sincBandpass", nullptr, SincBandpass, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -156,4 +156,13 @@ export declare class XModemTimers {
   state(): XModemTimersState;
   setState(state: { [K in keyof XModemTimersState]?: ArrayLike<number> | null }): void;
   close(): void;
+  /** a new object over `handle` (the receiver or sender this one's handle was remapped into with the same map): stream i continues the wait of stream map[i]; -1 is a fresh timer.  The timeout is this object's unless given */
+  remap(handle: XModemFileReceiverBatch | XModemSenderBatch, map: ArrayLike<number>, options?: { timeoutSamples?: number }): XModemTimers;
+  /** the image of `streams` (default: all, in order): two words per stream */
+  snapshot(streams?: null | ArrayLike<number>): Buffer;
+  /** a new object over `handle` continuing the records of a snapshot(); the timeout is the image's unless given.  TypeError where the image's kind is not the handle's */
+  static fromSnapshot(handle: XModemFileReceiverBatch | XModemSenderBatch, buf: Uint8Array, map?: ArrayLike<number> | null, options?: { timeoutSamples?: number }): XModemTimers;
 }
+export interface XModemTimerSnapshotInfo { kind: 2 | 3; nStreams: number; timeoutSamples: number; }
+/** what an XModemTimers snapshot holds, after validating all of it on the host */
+export declare function xmodemTimerSnapshotInfo(buf: Uint8Array): XModemTimerSnapshotInfo;

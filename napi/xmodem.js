@@ -298,7 +298,7 @@ class XModemFileReceiverBatch {
 // pass, so a receiver's timeout mask and a sender's abort mask are built on the device.  elapsed: the engine samples processed since this
 // object's previous poll.  The timers are quantised to the polls (a wait ends at the first poll at or after its deadline): poll once per
 // quantum.  The external abort stays the caller's (poll(elapsed, {abort})).  remap / snapshot of the handle do not carry the timers:
-// state() here, take by the map (-1: 0, 0), setState() on a new object over the new handle.  Close it before its handle.
+// they follow their streams through remap / snapshot / fromSnapshot here, with the same map.  Close it before its handle.
 class XModemTimers {
   constructor(handle, options = {}) {
     const recv = handle instanceof XModemFileReceiverBatch;
@@ -337,7 +337,31 @@ class XModemTimers {
     if (state === null || typeof state !== 'object') throw new TypeError('setState: state must be an object {waited, mark}');
     addon.xmodemTimerSetState(this._live('setState'), stateArray('waited', state.waited, this.nStreams), stateArray('mark', state.mark, this.nStreams));
   }
+  // The timers follow their streams (fskhip_xmodem_timer_remap / _snapshot / _restore): `handle` is the receiver or sender this
+  // one's handle was carried into, `map` the map it was carried with.  Stream i of the new object continues the wait of stream
+  // map[i] (of record map[i] of an image), -1: a fresh timer.  The timeout is this object's (the image's) unless given.
+  remap(handle, map, options = {}) {
+    const src = this._live('remap');
+    const next = new XModemTimers(handle, { timeoutSamples: options.timeoutSamples === undefined ? this.timeoutSamples : options.timeoutSamples });
+    try { addon.xmodemTimerRemap(next.handle, src, Array.from(map)); } catch (e) { next.close(); throw e; }
+    return next;
+  }
+  snapshot(streams) {
+    return addon.xmodemTimerSnapshot(this._live('snapshot'), streams === undefined || streams === null ? null : Array.from(streams));
+  }
+  static fromSnapshot(handle, buf, map, options = {}) {
+    const info = xmodemTimerSnapshotInfo(buf);
+    const m = map === undefined || map === null ? Array.from({ length: info.nStreams }, (_, i) => i) : Array.from(map);
+    const next = new XModemTimers(handle, { timeoutSamples: options.timeoutSamples === undefined ? info.timeoutSamples : options.timeoutSamples });
+    try {
+      const kind = next.recv ? 'recv' : 'tx';
+      if (XM_KINDS[info.kind] !== kind) throw new TypeError(`XModemTimers.fromSnapshot: the snapshot is of kind '${XM_KINDS[info.kind]}', the handle's is '${kind}'`);
+      addon.xmodemTimerRestore(next.handle, buf, m);
+    } catch (e) { next.close(); throw e; }
+    return next;
+  }
 }
+function xmodemTimerSnapshotInfo(buf) { return addon.xmodemTimerSnapshotInfo(buf); }   // {kind (2 tx, 3 recv), nStreams, timeoutSamples}
 
 // remap / snapshot / fromSnapshot of the three resident classes: the handle's state follows its streams with the map the engine and
 // the processor were carried with (fskhip_xmodem_{rx,tx,recv}_remap / _snapshot / _restore).  `like(processor)` makes a new object
@@ -371,4 +395,4 @@ lifecycle(XModemFileReceiverBatch, 'recv', { remap: addon.xmodemRecvRemap, snaps
   (self, p) => new XModemFileReceiverBatch(p, { fileCapacity: self.fileCapacity, maxRetries: self.maxRetries }),
   (p, info, o) => new XModemFileReceiverBatch(p, Object.assign({ fileCapacity: info.param0, maxRetries: info.param1 }, o)));
 
-module.exports = { xmodemSnapshotInfo, XModemReceiverBatch, XModemSenderBatch, XModemFileReceiverBatch, XModemTimers, CRC16, XModemPacket, ControlType, PacketConstants, crc16Batch, serializeBatch, scanBursts };
+module.exports = { xmodemSnapshotInfo, xmodemTimerSnapshotInfo, XModemReceiverBatch, XModemSenderBatch, XModemFileReceiverBatch, XModemTimers, CRC16, XModemPacket, ControlType, PacketConstants, crc16Batch, serializeBatch, scanBursts };

@@ -73,6 +73,11 @@ class XModemSnapshotInfo(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("n_streams", C.c_uint32), ("param0", C.c_uint32), ("param1", C.c_uint32), ("file_bytes", C.c_uint64)]
 
 
+class XModemTimerSnapshotInfo(C.Structure):
+    """fskhip_xmodem_timer_snapshot_info (include/fskhip_next.h): what an XModem timer snapshot holds"""
+    _fields_ = [("kind", C.c_uint32), ("n_streams", C.c_uint32), ("timeout_samples", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class ResamplerSnapshotInfo(C.Structure):
     """fskhip_resampler_snapshot_info (include/fskhip_next.h): what a resampler snapshot holds"""
     _fields_ = [("n_streams", C.c_uint32), ("direction", C.c_int), ("factor", C.c_uint32), ("n_taps", C.c_uint32), ("precision", C.c_int),
@@ -239,6 +244,11 @@ _SYMBOLS = [
     ("fskhip_xmodem_recv_poll_timed_device", C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, _P]),
     ("fskhip_xmodem_tx_poll_timed_host", C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P]),
     ("fskhip_xmodem_tx_poll_timed_device", C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, _P]),
+    ("fskhip_xmodem_timer_snapshot_info_get", C.c_int, [_P, C.c_size_t, C.POINTER(XModemTimerSnapshotInfo)]),
+    ("fskhip_xmodem_timer_remap", C.c_int, [_P, _P, _P, C.c_uint32]),
+    ("fskhip_xmodem_timer_snapshot_bytes", C.c_size_t, [_P, _P, C.c_uint32]),
+    ("fskhip_xmodem_timer_snapshot", C.c_int, [_P, _P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fskhip_xmodem_timer_restore", C.c_int, [_P, _P, C.c_size_t, _P, C.c_uint32]),
     ("fskhip_xmodem_snapshot_info_get", C.c_int, [_P, C.c_size_t, C.POINTER(XModemSnapshotInfo)]),
     ("fskhip_xmodem_rx_remap", C.c_int, [_P, _P, _P, C.c_uint32]),
     ("fskhip_xmodem_rx_snapshot_bytes", C.c_size_t, [_P, _P, C.c_uint32]),

@@ -305,4 +305,11 @@ hipError_t launch_xmodem_timer_arm_recv(const XmTimerState &W, const fskhip_xmod
                                         const uint32_t *d_totals, hipStream_t st);
 hipError_t launch_xmodem_timer_arm_tx(const XmTimerState &W, const fskhip_xmodem_tx_event *d_ev, const ProcState &T, uint32_t n_streams,
                                       const uint32_t *d_totals, hipStream_t st);
+// the timers through remap, snapshot and restore (fskhip_xmodem_timer_remap / _snapshot / _restore): one kernel, only the two words
+// of a stream.  gather: stream i of D takes waited and mark of stream d_map[i] of S, 0 and 0 where d_map[i] = -1.  pack: record r
+// of d_table (waited, mark interleaved, 8-byte aligned) = the words of stream d_sel[r] of S (null: r).  unpack: gather from such a
+// table in the place of S, d_map[i] naming a record.  The caller has checked every entry against the source's count.
+hipError_t launch_xmodem_timer_gather(const XmTimerState &D, const XmTimerState &S, const int64_t *d_map, uint32_t n_dst, hipStream_t st);
+hipError_t launch_xmodem_timer_pack(const XmTimerState &S, const int64_t *d_sel, uint32_t n_sel, uint32_t *d_table, hipStream_t st);
+hipError_t launch_xmodem_timer_unpack(const XmTimerState &D, const uint32_t *d_table, const int64_t *d_map, uint32_t n_dst, hipStream_t st);
 }  // namespace fsk

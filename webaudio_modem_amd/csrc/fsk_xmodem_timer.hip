@@ -77,9 +77,51 @@ __global__ __launch_bounds__(256) void xm_timer_arm_kernel(XmTimerState W, const
   if (T.mark != was.mark) W.mark[s] = T.mark;
 }
 
+// The timers through remap, snapshot and restore (fskhip_xmodem_timer_remap / _snapshot / _restore): destination stream i takes
+// the two words of source map[i] -- of i where map is null --, 0 and 0 where the entry is negative.  Either side is the pair of
+// arrays (waited, mark) or, where TABLE, an interleaved record table (waited, mark per record; `waited` is its base, 8-byte
+// aligned, `mark` unused).  The host has checked every entry against the source's count.
+template <bool SRC_TABLE, bool DST_TABLE>
+__global__ __launch_bounds__(256) void xm_timer_gather_kernel(uint32_t *__restrict__ dst_waited, uint32_t *__restrict__ dst_mark,
+                                                              const uint32_t *__restrict__ src_waited, const uint32_t *__restrict__ src_mark,
+                                                              const int64_t *__restrict__ map, uint32_t n_dst) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n_dst) return;
+  const int64_t m = map ? map[i] : (int64_t)i;
+  uint2 T = make_uint2(0u, 0u);
+  if (m >= 0) {
+    if constexpr (SRC_TABLE) T = reinterpret_cast<const uint2 *>(src_waited)[m];
+    else T = make_uint2(src_waited[m], src_mark[m]);
+  }
+  if constexpr (DST_TABLE) {
+    reinterpret_cast<uint2 *>(dst_waited)[i] = T;
+  } else {
+    dst_waited[i] = T.x;
+    dst_mark[i] = T.y;
+  }
+}
+
 uint32_t groups_of(uint32_t n_streams) { return (n_streams + 255u) / 256u; }
 
 }  // namespace
+
+hipError_t launch_xmodem_timer_gather(const XmTimerState &D, const XmTimerState &S, const int64_t *d_map, uint32_t n_dst, hipStream_t st) {
+  if (!n_dst) return hipSuccess;
+  hipLaunchKernelGGL((xm_timer_gather_kernel<false, false>), dim3(groups_of(n_dst)), dim3(256), 0, st, D.waited, D.mark, S.waited, S.mark, d_map, n_dst);
+  return hipGetLastError();
+}
+
+hipError_t launch_xmodem_timer_pack(const XmTimerState &S, const int64_t *d_sel, uint32_t n_sel, uint32_t *d_table, hipStream_t st) {
+  if (!n_sel) return hipSuccess;
+  hipLaunchKernelGGL((xm_timer_gather_kernel<false, true>), dim3(groups_of(n_sel)), dim3(256), 0, st, d_table, nullptr, S.waited, S.mark, d_sel, n_sel);
+  return hipGetLastError();
+}
+
+hipError_t launch_xmodem_timer_unpack(const XmTimerState &D, const uint32_t *d_table, const int64_t *d_map, uint32_t n_dst, hipStream_t st) {
+  if (!n_dst) return hipSuccess;
+  hipLaunchKernelGGL((xm_timer_gather_kernel<true, false>), dim3(groups_of(n_dst)), dim3(256), 0, st, D.waited, D.mark, d_table, nullptr, d_map, n_dst);
+  return hipGetLastError();
+}
 
 hipError_t launch_xmodem_timer_fire(const XmTimerState &W, bool is_recv, const uint32_t *d_state, const ProcState &T, uint32_t n_streams, const uint8_t *d_mask,
                                     const uint8_t *d_abort, uint32_t elapsed, hipStream_t st) {

@@ -2,7 +2,9 @@
 // fskhip_xmodem_recv_poll_timed_*, fskhip_xmodem_tx_poll_timed_*): a handle beside a file receiver or a sender that keeps every
 // stream's wait timer on the device in the engine's sample clock and runs the handle's own poll between a fire and an arm pass
 // (fsk_xmodem_timer.hip), so that the timeout and abort masks never exist on the host.  The external abort signal stays with the
-// host, as the polls' abort mask.
+// host, as the polls' abort mask.  The timers follow their streams through fskhip_xmodem_timer_remap, _snapshot
+// and _restore: the two words move on the device (xm_timer_gather_kernel), an image ("FSKW") crosses PCIe once; its format and the
+// one definition of a valid image are fsk_xmodem_timer_image.h's (host-only), and this file is the format's only writer.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,11 +13,14 @@
 #include <string>
 #include <vector>
 
+#include "fsk_engine.h"
 #include "fsk_host.h"
 #include "fsk_launch.h"
 #include "fsk_proc.h"
+#include "fsk_stage.h"
 #include "fsk_xmodem_handles.h"
 #include "fsk_xmodem_timer.h"
+#include "fsk_xmodem_timer_image.h"
 
 using namespace fsk;
 
@@ -23,6 +28,7 @@ struct fskhip_xmodem_timer {
   fskhip_xmodem_recv *r = nullptr;   // exactly one of the two
   fskhip_xmodem_tx *t = nullptr;
   bool orphan = false;               // the handle was destroyed first: every call but destroy is refused
+  bool fresh = true;                 // no timed poll, reset or state_set call yet: what a remap or restore wants of its destination
   fskhip_processor *p = nullptr;
   int device = 0;
   uint32_t S = 0;
@@ -100,6 +106,7 @@ int create(const char *fn, fskhip_xmodem_recv *r, fskhip_xmodem_tx *t, uint32_t 
 int timed_recv(fskhip_xmodem_timer *w, uint32_t elapsed, const uint8_t *d_mask, const uint8_t *d_abort, uint32_t *d_streams, fskhip_xmodem_recv_event *d_events,
                uint32_t cap_streams, uint32_t *d_totals, hipStream_t st) {
   fskhip_xmodem_recv *r = w->r;
+  w->fresh = false;
   HIP_TRY(hipSetDevice(w->device));
   HIP_TRY(launch_xmodem_timer_fire(w->W, true, r->X.state, w->p->T, w->S, d_mask, nullptr, elapsed, st));
   if (const int rc = fskhip_xmodem_recv_poll_device(r, d_mask, w->W.flag, d_abort, d_streams, d_events, cap_streams, d_totals, st)) return rc;
@@ -110,6 +117,7 @@ int timed_recv(fskhip_xmodem_timer *w, uint32_t elapsed, const uint8_t *d_mask, 
 int timed_tx(fskhip_xmodem_timer *w, uint32_t elapsed, const uint8_t *d_mask, const uint8_t *d_abort, uint32_t *d_streams, fskhip_xmodem_tx_event *d_events,
              uint32_t cap_streams, uint32_t *d_totals, hipStream_t st) {
   fskhip_xmodem_tx *t = w->t;
+  w->fresh = false;
   HIP_TRY(hipSetDevice(w->device));
   HIP_TRY(launch_xmodem_timer_fire(w->W, false, t->X.state, w->p->T, w->S, d_mask, d_abort, elapsed, st));
   if (const int rc = fskhip_xmodem_tx_poll_device(t, d_mask, w->W.flag, d_streams, d_events, cap_streams, d_totals, st)) return rc;
@@ -137,6 +145,16 @@ int timed_host(fskhip_xmodem_timer *w, const uint8_t *mask, const uint8_t *abort
     HIP_TRY(hipMemcpy(streams, w->d_streams, sizeof(uint32_t) * totals[0], hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(events, w->d_events, sizeof(EV) * totals[0], hipMemcpyDeviceToHost));
   }
+  return FSKHIP_OK;
+}
+
+uint32_t kind_of(const fskhip_xmodem_timer *w) { return w->r ? kXwKindRecv : kXwKindTx; }
+
+// the last thing a remap or a restore asks of its destination.  (Neither call ends dst's freshness -- the header lists the calls
+// that do --: they write every stream of dst, so a later one replaces the earlier one as a whole.)
+int check_fresh(const char *who, const char *verb, const fskhip_xmodem_timer *dst) {
+  if (!dst->fresh)
+    return fail(FSKHIP_E_INVALID, "%s: the destination has been used already (timed poll, reset or state_set: %s into a freshly created timer)", who, verb);
   return FSKHIP_OK;
 }
 
@@ -180,6 +198,7 @@ int fskhip_xmodem_timer_reset(fskhip_xmodem_timer *w, int64_t stream) {
   if (stream >= (int64_t)w->S) return fail(FSKHIP_E_INVALID, "stream out of range");
   HIP_TRY(hipSetDevice(w->device));
   HIP_TRY(hipDeviceSynchronize());
+  w->fresh = false;
   const size_t first = stream < 0 ? 0 : (size_t)stream, n = stream < 0 ? w->S : 1;
   if (const int rc = fill_words(w->W.waited + first, n, 0u)) return rc;
   if (const int rc = fill_words(w->W.mark + first, n, 0u)) return rc;
@@ -206,6 +225,7 @@ int fskhip_xmodem_timer_state_set(fskhip_xmodem_timer *w, const uint32_t *waited
   }
   HIP_TRY(hipSetDevice(w->device));
   HIP_TRY(hipDeviceSynchronize());
+  w->fresh = false;
   int rc;
   if ((rc = put_words(w->W.waited, waited, w->S)) != FSKHIP_OK || (rc = put_words(w->W.mark, mark, w->S)) != FSKHIP_OK) return rc;
   HIP_TRY(hipDeviceSynchronize());
@@ -240,6 +260,101 @@ int fskhip_xmodem_tx_poll_timed_host(fskhip_xmodem_timer *w, uint32_t elapsed, c
                     [&](const uint8_t *m, const uint8_t *a, uint32_t *ds, fskhip_xmodem_tx_event *de, uint32_t *dt) {
                       return timed_tx(w, elapsed, m, a, ds, de, cap_streams, dt, nullptr);
                     });
+}
+
+// ---- remap, snapshot, restore ---------------------------------------------------------------------------------------------------
+int fskhip_xmodem_timer_snapshot_info_get(const void *buf, size_t size, fskhip_xmodem_timer_snapshot_info *info) {
+  static const char who[] = "fskhip_xmodem_timer_snapshot_info_get";
+  XwImage im;
+  if (const int rc = open_image(who, xw_image_open, buf, size, &im)) return rc;
+  if (!info) return fail(FSKHIP_E_INVALID, "%s: null info", who);
+  std::memset(info, 0, sizeof(*info));
+  info->kind = im.h.kind; info->n_streams = im.h.n_records; info->timeout_samples = im.h.timeout_samples;
+  return FSKHIP_OK;
+}
+
+int fskhip_xmodem_timer_remap(fskhip_xmodem_timer *dst, fskhip_xmodem_timer *src, const int64_t *map, uint32_t n_map) {
+  static const char who[] = "fskhip_xmodem_timer_remap";
+  if (!dst || !src) return fail(FSKHIP_E_INVALID, "%s: null timer", who);
+  if (dst == src) return fail(FSKHIP_E_INVALID, "%s: dst and src are the same timer", who);
+  if (const int rc = usable(who, dst)) return rc;
+  if (const int rc = usable(who, src)) return rc;
+  if (const int rc = remap_check_map(who, "a source stream", map, n_map)) return rc;
+  if (n_map != dst->S) return fail(FSKHIP_E_INVALID, "%s: n_map %u != the destination's %u streams", who, n_map, dst->S);
+  for (uint32_t i = 0; i < n_map; i++)
+    if (map[i] >= (int64_t)src->S) return fail(FSKHIP_E_INVALID, "%s: map[%u] = %lld, the source has %u streams", who, i, (long long)map[i], src->S);
+  if (kind_of(dst) != kind_of(src))
+    return fail(FSKHIP_E_INVALID, "%s: the timers are of different kinds (the destination's is over a %s, the source's over a %s)", who,
+                dst->r ? "receiver" : "sender", src->r ? "receiver" : "sender");
+  if (dst->device != src->device) return fail(FSKHIP_E_INVALID, "%s: the timers are on different devices (%d, %d): use a snapshot", who, dst->device, src->device);
+  if (const int rc = check_fresh(who, "remap", dst)) return rc;
+  HIP_TRY(hipSetDevice(dst->device));
+  HIP_TRY(hipDeviceSynchronize());
+  Scratch sc;
+  int64_t *d_map = nullptr;
+  if (const int rc = sc.upload(d_map, map, n_map)) return rc;
+  HIP_TRY(launch_xmodem_timer_gather(dst->W, src->W, d_map, n_map, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  return FSKHIP_OK;
+}
+
+size_t fskhip_xmodem_timer_snapshot_bytes(const fskhip_xmodem_timer *w, const int64_t *sel, uint32_t n_sel) {
+  if (!w) return 0;
+  return (size_t)xw_image_bytes(sel ? n_sel : w->S);
+}
+
+int fskhip_xmodem_timer_snapshot(fskhip_xmodem_timer *w, const int64_t *sel, uint32_t n_sel, void *buf, size_t cap, size_t *written) {
+  static const char who[] = "fskhip_xmodem_timer_snapshot";
+  if (const int rc = usable(who, w)) return rc;
+  if (!sel) n_sel = w->S;
+  if (const int rc = check_sel(who, "timer", sel, n_sel, w->S)) return rc;
+  const size_t need = (size_t)xw_image_bytes(n_sel);
+  if (const int rc = check_room(who, n_sel, need, buf, cap, written)) return rc;
+  HIP_TRY(hipSetDevice(w->device));
+  HIP_TRY(hipDeviceSynchronize());
+  XwImageHeader h = image_header<XwImageHeader>(kXwMagic, kXwFormat);
+  h.kind = kind_of(w); h.n_records = n_sel; h.record_words = kXwRecordWords; h.timeout_samples = w->W.timeout_samples;
+  const size_t body = need - sizeof(h), live = (size_t)xw_live_bytes(n_sel) - sizeof(h);
+  Scratch sc;
+  int64_t *d_sel = nullptr;
+  uint8_t *d_body = nullptr;
+  if (sel)
+    if (const int rc = sc.upload(d_sel, sel, n_sel)) return rc;
+  if (const int rc = sc.alloc(d_body, std::max<size_t>(body, 16))) return rc;
+  if (body != live) HIP_TRY(hipMemset(d_body + live, 0, body - live));   // the padding behind an odd number of records
+  HIP_TRY(launch_xmodem_timer_pack(w->W, d_sel, n_sel, (uint32_t *)d_body, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned char *out = (unsigned char *)buf;
+  if (body) HIP_TRY(hipMemcpy(out + sizeof(h), d_body, body, hipMemcpyDeviceToHost));
+  image_seal(h, out, need);
+  return FSKHIP_OK;
+}
+
+int fskhip_xmodem_timer_restore(fskhip_xmodem_timer *dst, const void *buf, size_t size, const int64_t *map, uint32_t n_map) {
+  static const char who[] = "fskhip_xmodem_timer_restore";
+  if (const int rc = usable(who, dst)) return rc;
+  if (const int rc = remap_check_map(who, "a record of the snapshot", map, n_map)) return rc;
+  XwImage im;
+  if (const int rc = open_image(who, xw_image_open, buf, size, &im)) return rc;
+  if (im.h.kind != kind_of(dst))
+    return fail(FSKHIP_E_INVALID, "%s: the snapshot is of kind %u (%s), this timer's is %u (%s)", who, im.h.kind, xw_kind_name(im.h.kind), kind_of(dst),
+                xw_kind_name(kind_of(dst)));
+  for (uint32_t i = 0; i < n_map; i++)
+    if (map[i] >= (int64_t)im.h.n_records)
+      return fail(FSKHIP_E_INVALID, "%s: map[%u] = %lld, the snapshot has %u records", who, i, (long long)map[i], im.h.n_records);
+  if (n_map != dst->S) return fail(FSKHIP_E_INVALID, "%s: n_map %u != the destination's %u streams", who, n_map, dst->S);
+  if (const int rc = check_fresh(who, "restore", dst)) return rc;
+  HIP_TRY(hipSetDevice(dst->device));
+  HIP_TRY(hipDeviceSynchronize());
+  Scratch sc;
+  int64_t *d_map = nullptr;
+  uint8_t *d_table = nullptr;
+  const size_t table_bytes = (size_t)8u * im.h.n_records;
+  if (const int rc = sc.upload(d_map, map, n_map)) return rc;
+  if (const int rc = sc.upload(d_table, (const uint8_t *)im.table, table_bytes)) return rc;
+  HIP_TRY(launch_xmodem_timer_unpack(dst->W, (const uint32_t *)d_table, d_map, n_map, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  return FSKHIP_OK;
 }
 
 }  // extern "C"

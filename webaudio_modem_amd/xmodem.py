@@ -585,14 +585,57 @@ TIMER_WORDS = ("waited", "mark")
 TIMER_WAS_PENDING = 4   # mark: bits 0-1 the stage the timer was armed for (0..2, a sender's is always 0), bit 2 was-pending
 
 
-class XModemTimers:
+def xmodem_timer_snapshot_info(snap):
+    """fskhip_xmodem_timer_snapshot_info_get: what an XModemTimers snapshot holds -- kind (2 tx, 3 recv), n_streams,
+    timeout_samples -- validated on the host, no device needed"""
+    b = _blob(snap)
+    info = _lib.XModemTimerSnapshotInfo()
+    _lib.check(_lib.lib().fskhip_xmodem_timer_snapshot_info_get(b.ctypes.data, b.nbytes, C.byref(info)))
+    return _struct_dict(info)
+
+
+class XModemTimers(_Lifecycle):
     """The `timeoutMs` timers of sendData() / receiveData() for every stream of an XModemFileReceiverBatch or an XModemSenderBatch,
     resident on the device in the engine's sample clock (fskhip_xmodem_timer_*): `poll` is the handle's own poll between a fire
     and an arm pass, so a receiver's timeout mask and a sender's abort mask are built on the device and a lost packet is recovered
     from without the host reading any per-stream word.  `elapsed` is the engine samples processed since this object's previous
     poll.  The timers are quantised to the polls (a wait ends at the first poll at or after its deadline): poll once per quantum.
-    The external abort stays the caller's (`abort`).  remapped / snapshot of the handle do not carry the timers: state() here,
-    take by the map (-1: 0, 0), set_state() on a new object over the new handle.  Close it before its handle."""
+    The external abort stays the caller's (`abort`).  remapped / snapshot of the handle do not carry the timers; they follow
+    their streams through remapped / snapshot / from_snapshot here, with the map the handle was carried with, so that a running
+    wait goes on from where it was.  Close it before its handle."""
+
+    _KIND = "timer"   # (_Lifecycle: fskhip_xmodem_timer_snapshot and its kin; snapshot() is _Lifecycle's as it is)
+
+    def remapped(self, handle, stream_map, timeout_samples=None):
+        """A new object over `handle` -- the receiver or sender this one's handle was remapped into with the same stream_map --
+        whose stream i continues the wait of stream stream_map[i] of this one, or has a fresh timer where stream_map[i] is -1.
+        The timeout is this object's unless given.  This object stays usable."""
+        m = np.ascontiguousarray(stream_map, dtype=np.int64).reshape(-1)
+        src = self._live()
+        nxt = XModemTimers(handle, self.timeout_samples if timeout_samples is None else timeout_samples)
+        try:
+            _lib.check(self._L.fskhip_xmodem_timer_remap(nxt._h, src, m.ctypes.data if len(m) else None, len(m)))
+        except Exception:
+            nxt.close()
+            raise
+        return nxt
+
+    @classmethod
+    def from_snapshot(cls, handle, snap, stream_map=None, timeout_samples=None):
+        """A new object over `handle` that continues the records of a snapshot(): stream i continues record stream_map[i]
+        (-1: a fresh timer; None: every record, in order).  The timeout is the image's unless given."""
+        info = xmodem_timer_snapshot_info(snap)
+        m = np.arange(info["n_streams"], dtype=np.int64) if stream_map is None else np.ascontiguousarray(stream_map, dtype=np.int64).reshape(-1)
+        nxt = cls(handle, info["timeout_samples"] if timeout_samples is None else timeout_samples)
+        try:
+            if XMODEM_SNAPSHOT_KINDS[info["kind"]] != nxt._kind:
+                raise ValueError("the snapshot is of kind %r, the handle's is %r" % (XMODEM_SNAPSHOT_KINDS[info["kind"]], nxt._kind))
+            b = _blob(snap)
+            _lib.check(nxt._L.fskhip_xmodem_timer_restore(nxt._h, b.ctypes.data, b.nbytes, m.ctypes.data if len(m) else None, len(m)))
+        except Exception:
+            nxt.close()
+            raise
+        return nxt
 
     def __init__(self, handle, timeout_samples=144000):
         if isinstance(handle, XModemFileReceiverBatch):
